@@ -2,7 +2,7 @@
 """bench.py -- DLRM training throughput (samples/s) of the MI355X-native path, one JSON line.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload terabyte|kaggle|tiny|mlperf|giant|giant-row]
-                  [--scaling strong|weak] [--per-gpu-batch B]
+                  [--scaling strong|weak] [--per-gpu-batch B] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment: this process never touches a GPU -- it starts N child
 ranks of itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT set), relays rank 0's single
@@ -20,7 +20,9 @@ data-parallel and, by default, keeps the global batch at 32768 ("scaling": "stro
 over RCCL, called from the C++ host layer on a communicator bootstrapped over torch.distributed ("nccl");
 `--torch-collectives` serves them through torch.distributed instead.  fp32 throughout (the reference's arithmetic).
 
-Besides the contract fields the line carries
+A plain run sets up, warms up, times the K steps and prints the headline line (samples/s, ms_per_step, the workload, the
+loss over the timed steps; at N > 1 the collective counts and payloads).  `--dump-outputs DIR` writes what the last timed step
+computed (dump_outputs()) before the line is printed.  With `--full` the line also carries
   roofline      the embedding gather kernel (BASELINE's second metric) of THIS workload on rank 0: algorithmic bytes
                 (B*(L*(8+4D)+4D) per table; 26,832 B/sample at the Terabyte shape = 879 MB per launch at
                 N = 1) / average HIP-event time of back-to-back launches on the model's own stream; `traffic` = HBM
@@ -31,6 +33,7 @@ Besides the contract fields the line carries
                 the same process after the headline (skipped with --no-secondary and for N > 1)
   cpu_baseline  the same application on the host cores with the CPU oracle as kernel library (kind "port": the
                 reference has no CPU path for this step), N = 1 only, on a bounded sample (stated in `sample`)
+  collectives_in_step_us  (N > 1 or --force-exchange) the collectives' intervals inside real eager steps
 
 The measured path always runs the HIP library and refuses to start without a GPU.  (tests/test_launchers.py walks this
 file's N > 1 rank code on the CPU through the hidden --functional-test-backend <kernel library> flag -- gloo collectives, an
@@ -406,6 +409,61 @@ def kaggle_secondary(ffmodel, local_rank):
             "fused_update": {"us_per_launch": round(t_bwd * 1e6, 2), "GB/s": round(T * B * (8 + 12 * D) / t_bwd / 1e9, 1)}}
 
 
+DUMP_BYTES = 64_000_000     # --dump-outputs: the files of one run together
+DUMP_TABLE_ROWS = 1024      # rows sampled per embedding table
+
+
+def dump_outputs(app, out_dir, device, on_gpu):
+    """--dump-outputs (one rank): what the last timed step computed, as float32 DIR/<name>.npy -- the predictions, the MLP layers'
+    parameters after the update and, of each embedding table (tens of GB at the Terabyte shape), the rows at a fixed sample of
+    the batch's lookups, drawn with seed 0 (rows the step wrote), gathered by the kernel library the model runs on.  The model's
+    inputs and initial weights come from its fixed seed, so equal arguments give equal inputs in every run."""
+    import numpy as np
+    from dlrm_flexflow_amd import capi
+    m = app.model
+    m.sync()
+    arrays = {"predictions": m.layer_output(m.num_layers - 1).get()}
+    tables = []
+    for layer in range(m.num_layers):
+        name = m.layer_name(layer)
+        if name.startswith("Embedding"):
+            tables.append((name, m.parameter(layer, 0)))
+        else:
+            for i in range(m.layer_num_weights(layer)):
+                arrays[f"{name}.weight{i}"] = m.parameter(layer, i).get_weights()
+    left = DUMP_BYTES - sum(a.nbytes for a in arrays.values())
+    if tables:
+        assert len(tables) == app.num_tables, f"{len(tables)} embedding layers, {app.num_tables} sparse inputs"
+        lib = capi.FFHLib(m.backend["path"], device)
+        rng = np.random.default_rng(0)
+        try:
+            for t, (name, p) in enumerate(tables):
+                R, D = p.dims
+                ids = app.sparse_input(t).get(np.int64).reshape(-1)
+                k = min(ids.size, DUMP_TABLE_ROWS, left // (4 * D * len(tables)))
+                sel = np.ascontiguousarray(ids[np.sort(rng.choice(ids.size, k, replace=False))]).reshape(k, 1)
+                if k == 0 or sel.min() < 0 or sel.max() >= R:
+                    raise SystemExit(f"bench: --dump-outputs: {name}: ids outside [0, {R}) or no room left")
+                if on_gpu:
+                    import torch
+                    idx, rows = torch.from_numpy(sel).to(f"cuda:{device}"), torch.empty(k, D, device=f"cuda:{device}")
+                else:
+                    idx, rows = sel, np.empty((k, D), np.float32)
+                lib.call("ffh_embedding_fwd", idx, rows, p.device_ptr, 1, D, k, R, D, capi.AGGR_MODE_SUM, None)
+                if on_gpu:
+                    torch.cuda.synchronize(device)
+                    rows = rows.cpu().numpy()
+                arrays[f"{name}.rows"] = rows
+        finally:
+            lib.close()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float32))
+    print(f"bench: wrote {len(arrays)} arrays ({total / 1e6:.1f} MB) to {out_dir}", file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -414,8 +472,12 @@ def main():
     ap.add_argument("--workload", default="terabyte", help="terabyte (default, BASELINE configs[2] shape at global batch 32768) | kaggle | tiny | mlperf | giant | giant-row | mlperf-allpairs")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"], help="N > 1: keep the GLOBAL batch (strong, default: BASELINE configs[2]) or the per-GPU batch (weak)")
     ap.add_argument("--per-gpu-batch", type=int, default=None, help="samples per GPU and step (implies weak scaling)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the Kaggle-shape block under `kernels` (profile runs: keeps the rocprof averages single-shape)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure what the headline does not need: the per-kernel rooflines, "
+                    "the in-step probes, the bf16-pipe modes, the Kaggle-shape block and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the last timed step computed as DIR/<name>.npy (float32, "
+                    f"at most {DUMP_BYTES // 1_000_000} MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the bf16-pipe modes and the Kaggle-shape block (profile runs: keeps the rocprof averages single-shape)")
     ap.add_argument("--no-trace", action="store_true")
     ap.add_argument("--force-graph", action="store_true", help="time the hipGraph-replayed step even where eager launches are faster (diagnosis)")
     ap.add_argument("--force-exchange", action="store_true", help="1 GPU: still run the all-to-all / all-reduce path (1-rank RCCL group)")
@@ -433,6 +495,8 @@ def main():
     ap.add_argument("--functional-test-backend", default="", help=argparse.SUPPRESS)   # tests only: walk this file's whole rank path on the
     #                      CPU (gloo + the given kernel library, i.e. the oracle); the line it prints is not a measurement
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs is for one GPU: with more ranks a table may be split over them")
     args.shim_flags = args.shim_flags.replace(",", " ")      # (a comma also separates flags: one shell word in scripted visits)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not args.cpu_baseline_leg:
         sys.exit(spawn_ranks(args.gpus))   # the parent: no torch import, no HIP call, nothing that initialises a GPU
@@ -548,32 +612,37 @@ def main():
 
     pm = app.model.perf_metrics()                  # loss over the K timed steps (before the kernel probes below touch the tables)
     calls = dict(comm.calls) if comm is not None and hasattr(comm, "calls") else None     # collectives of warm-up + W + K steps (the probes below add theirs)
-    # per-kernel device time, HIP events on the stream the kernels are launched on (the model's stream)
+    if args.dump_outputs:
+        dump_outputs(app, args.dump_outputs, local_rank, on_gpu=not ftest)
     T = len(w["rows"].split("-"))
     rows_of = [int(r) for r in w["rows"].split("-")]
     replicated = [t for t in range(T) if world > 1 and 0 < rows_of[t] <= args.replicate_embedding_rows]
     owned = len([t for t in range(T) if t % world == rank and t not in replicated])      # tables in this rank's gather launch / all-to-all
     B, D = w["B"], w["D"]
     table_wise = not any(f in w.get("extra", []) for f in ("--column-shard-rows", "--row-shard-rows")) or world == 1
-    n_g = 200 if B * owned <= 65536 else 40
-    t_fwd = app.time_kernel(8, n_g) * 1e-3 if (rank == 0 and table_wise and owned) else None           # gather kernel alone (no exchange)
-    t_bwd = app.time_kernel(9, max(10, n_g // 2)) * 1e-3 if (rank == 0 and table_wise and owned) else None   # fused update kernels alone
-    # the same kernels and the collectives inside real eager steps, by events on the streams they are issued on.  COLLECTIVE: the
-    # steps run the exchange, so at N > 1 every rank walks them (round-3 advisor: rank 0 alone hung in the first all-to-all); the
-    # line reports rank 0's intervals and the maximum over the ranks
-    # (also when the timed steps were replayed from a hipGraph: the probed steps are launched eagerly, the kernels are the same)
-    in_step = app.probe_step(10 if B > 4096 else 50)
-    in_step_max = dict(in_step)
-    if world > 1:
-        keys = sorted(in_step)
-        t = torch.tensor([in_step[k] for k in keys], dtype=torch.float64, device="cpu" if ftest else "cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        in_step_max = {k: float(v) for k, v in zip(keys, t.tolist())}
-    t_fwd_in = in_step["gather"] * 1e-3 if (in_step and t_fwd and in_step["gather"] > 0) else None
-    t_bwd_in = in_step["table_update"] * 1e-3 if (in_step and t_bwd and in_step["table_update"] > 0) else None
-    t_step_dev = app.time_kernel(2 if trace else 4, 20 if B > 4096 else 100) * 1e-3 if solo else None
-    t_lin_fwd = app.time_kernel(6, 20 if B > 4096 else 200) * 1e-3 if solo else None      # largest Linear layer alone: forward, backward (dX + dW)
-    t_lin_bwd = app.time_kernel(7, 20 if B > 4096 else 100) * 1e-3 if solo else None
+    t_fwd = t_bwd = t_fwd_in = t_bwd_in = t_step_dev = t_lin_fwd = t_lin_bwd = None
+    in_step = in_step_max = {}
+    if args.full:
+        # per-kernel device time, HIP events on the stream the kernels are launched on (the model's stream)
+        n_g = 200 if B * owned <= 65536 else 40
+        t_fwd = app.time_kernel(8, n_g) * 1e-3 if (rank == 0 and table_wise and owned) else None           # gather kernel alone (no exchange)
+        t_bwd = app.time_kernel(9, max(10, n_g // 2)) * 1e-3 if (rank == 0 and table_wise and owned) else None   # fused update kernels alone
+        # the same kernels and the collectives inside real eager steps, by events on the streams they are issued on.  COLLECTIVE: the
+        # steps run the exchange, so at N > 1 every rank walks them (round-3 advisor: rank 0 alone hung in the first all-to-all); the
+        # line reports rank 0's intervals and the maximum over the ranks
+        # (also when the timed steps were replayed from a hipGraph: the probed steps are launched eagerly, the kernels are the same)
+        in_step = app.probe_step(10 if B > 4096 else 50)
+        in_step_max = dict(in_step)
+        if world > 1:
+            keys = sorted(in_step)
+            t = torch.tensor([in_step[k] for k in keys], dtype=torch.float64, device="cpu" if ftest else "cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            in_step_max = {k: float(v) for k, v in zip(keys, t.tolist())}
+        t_fwd_in = in_step["gather"] * 1e-3 if (in_step and t_fwd and in_step["gather"] > 0) else None
+        t_bwd_in = in_step["table_update"] * 1e-3 if (in_step and t_bwd and in_step["table_update"] > 0) else None
+        t_step_dev = app.time_kernel(2 if trace else 4, 20 if B > 4096 else 100) * 1e-3 if solo else None
+        t_lin_fwd = app.time_kernel(6, 20 if B > 4096 else 200) * 1e-3 if solo else None      # largest Linear layer alone: forward, backward (dX + dW)
+        t_lin_bwd = app.time_kernel(7, 20 if B > 4096 else 100) * 1e-3 if solo else None
     uses_graph = app.model.uses_graph and trace
     backend = app.model.backend       # the kernel library the timed steps ran on (host/backend.cc honours --backend / $FFH_BACKEND_LIB)
     nbk = max(app.model.counter("allreduce_buckets"), 0)
@@ -652,7 +721,8 @@ def main():
                 "exposed_on_the_compute_stream_us": round((in_step_max["allreduce"] + in_step_max["allreduce_wait"] + in_step_max["join_wait"]) * 1e3, 1)}
     if args.force_exchange:
         out["config"]["parallelism"] = f"1 rank, exchange path forced: {layout} + all-reduce; {collectives}"
-    out["kernels"] = {}
+    if args.full:
+        out["kernels"] = {}
     if t_fwd:
         key = args.workload if (world == 1 and w["B"] == DEFAULT_BATCH[args.workload]) else None
         pmc, src = pmc_traffic(key) if key else ({}, None)
@@ -676,7 +746,7 @@ def main():
             out["kernels"]["embedding_bwd_sgd_fused"]["in_step_covers"] = (
                 "the whole update, sort + apply (one GPU, >= 8192 samples: the early sort is off by shape -- beside the top MLP's first forward GEMM "
                 "it cost more than it saved; --early-sort forces it)")
-    if solo:
+    if solo and args.full:
         flops = mlp_flops_per_sample(w) * B
         peak = BF16_PEAK_TFLOPS if bf16 else F32_PEAK_TFLOPS
         out["kernels"]["linear_largest_layer"] = largest_linear(w, B, t_lin_fwd, t_lin_bwd, bf16)
@@ -698,7 +768,7 @@ def main():
                 out["kernels"]["kaggle_secondary"] = kaggle_secondary(ffmodel, local_rank)
             except Exception as e:  # noqa: BLE001
                 out["kernels"]["kaggle_secondary"] = {"error": repr(e)}
-    if not args.no_cpu_baseline and not ftest and world == 1:
+    if args.full and not args.no_cpu_baseline and not ftest and world == 1:
         # host only, rank 0, at N = 1 only (the contract): on the N > 1 lines the other ranks would stand in the closing barrier while rank 0's host cores run it
         out["cpu_baseline"] = cpu_baseline(args, budget_s=24.0)
     print(json.dumps(out), file=json_out, flush=True)

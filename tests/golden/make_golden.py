@@ -9,7 +9,8 @@ Sources of truth, in the order SURVEY.md section 8c ranks them:
                           the oracle the reference's own op tests use
                           ([ref: tests/ops/test_harness.py:201-283,300-405,425-510]); same seeds
                           (np.random.seed(0)) and the reference's small known-answer shapes.
-The fixtures are plain arrays (inputs + expected outputs) in .npz files; no reference
+The fixtures are plain arrays (inputs + expected outputs) in .npz files, and SHA-256 digests of
+seeded inputs and the reference's outputs for them in embedding_fwd_ref_large.json; no reference
 source text is stored.  Re-run:  python tests/golden/make_golden.py
 """
 import os
@@ -70,6 +71,31 @@ def embedding_from_reference():
     cases["ragged_out_mean"] = out_mean
     cases["n_cases"] = np.array(k)
     save("embedding_fwd_ref", **cases)
+
+
+LARGE_FWD_CASES = ((128, 1), (64, 4), (16, 1), (256, 2), (7, 3))     # (D, L) over a 5000-row table, 777 bags
+
+
+def embedding_fwd_large_from_reference():
+    """The reference's lookup on bigger seeded inputs than embedding_fwd_ref.  The test draws the inputs again from the seed and
+    compares bit for bit, so the fixture holds SHA-256 digests: of each case's table and ids (a changed random stream is told apart
+    from a changed result) and of the reference's output bytes."""
+    import hashlib
+    import json
+    assert oracle.ref_available(), "run `make -C oracle ref` with /root/reference present"
+    rng = np.random.default_rng(123)
+    cases = []
+    for D, L in LARGE_FWD_CASES:
+        w = rng.uniform(-1, 1, (5000, D)).astype(np.float32)
+        idx = rng.integers(0, 5000, (777, L)).astype(np.int64)
+        cases.append({"D": D, "L": L, "w_sha256": hashlib.sha256(w.tobytes()).hexdigest(),
+                      "idx_sha256": hashlib.sha256(idx.tobytes()).hexdigest(),
+                      "out_sha256": hashlib.sha256(oracle.ref_embedding_fwd(idx, w).tobytes()).hexdigest()})
+    path = os.path.join(HERE, "embedding_fwd_ref_large.json")
+    with open(path, "w") as f:
+        json.dump(cases, f, indent=1)
+        f.write("\n")
+    print(f"embedding_fwd_ref_large.json  {os.path.getsize(path)} bytes")
 
 
 def embedding_bwd_from_reference():
@@ -281,6 +307,7 @@ def dlrm_step_from_torch():
 
 if __name__ == "__main__":
     embedding_from_reference()
+    embedding_fwd_large_from_reference()
     embedding_bwd_from_reference()
     linear_from_torch()
     concat_from_numpy()

@@ -10,6 +10,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -194,7 +195,7 @@ def test_run_dlrm_one_rank_on_gpu(hip):
 def test_bench_one_rank_exchange_line_on_gpu(hip):
     """bench.py through the exchange path on one RCCL rank: the line carries roofline, the collective counts and the rank count."""
     r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--force-exchange", "--workload", "kaggle", "--steps", "5", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["config"]["ranks_observed"] == 1
@@ -217,7 +218,7 @@ def _bench_env():
 
 @pytest.mark.parametrize("scaling", ["strong", "weak"])
 def test_bench_two_ranks_functional_on_cpu(oracle, scaling):
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--workload", "tiny", "--steps", "3", "--warmup", "1", "--scaling", scaling,
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--workload", "tiny", "--steps", "3", "--warmup", "1", "--scaling", scaling, "--full",
                         "--functional-test-backend", oracle.ORACLE_LIB], env=_bench_env(), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -241,6 +242,30 @@ def test_bench_two_ranks_functional_on_cpu(oracle, scaling):
     pay = d["config"]["collective_payload_bytes_per_step_rank0"]
     B, D = d["config"]["global_batch"], 16
     assert pay["alltoall_forward_sent"] == pay["alltoall_backward_sent"] == 4 * B * D * 4 // 2 and pay["allreduce_buffer"] > 0
+
+
+def test_bench_plain_line_and_dump_outputs_functional_on_cpu(oracle, tmp_path):
+    """A plain run prints the headline line without the blocks --full adds; --dump-outputs writes the last timed step's predictions,
+    parameters and sampled table rows as float32 .npy within 64 MB, the same arrays for the same arguments, other ones after more steps."""
+    def run(out, steps):
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--workload", "tiny", "--steps", str(steps), "--warmup", "1",
+                            "--dump-outputs", str(out), "--functional-test-backend", oracle.ORACLE_LIB],
+                           env=_bench_env(), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0]), {f: np.load(os.path.join(out, f)) for f in sorted(os.listdir(out))}
+
+    d, a = run(tmp_path / "a", 3)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["metric"] == "dlrm_training_samples_per_sec" and d["dtype"] == "f32"
+    assert not {"roofline", "kernels", "cpu_baseline", "fp32_split", "collectives_in_step_us"} & set(d)
+    assert a["predictions.npy"].shape == (128, 1) and a["Dense_100.weight0.npy"].shape == (64, 13)
+    assert sum(f.endswith(".rows.npy") for f in a) == 8 and a["Embedding_102.rows.npy"].shape == (128, 16)
+    assert all(v.dtype == np.float32 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64_000_000
+    _, b = run(tmp_path / "b", 3)
+    assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    _, c = run(tmp_path / "c", 4)
+    assert not np.array_equal(a["predictions.npy"], c["predictions.npy"])
 
 
 def test_bench_failing_rank_is_named_in_the_parents_output(oracle):

@@ -6,10 +6,14 @@
 Tolerances follow the reference's harness [ref: tests/ops/test_harness.py:203,302,425,504]
 or tighter, and are written next to each check.
 """
+import hashlib
+import json
+import os
+
 import numpy as np
 import pytest
 
-from conftest import golden
+from conftest import GOLDEN, golden
 from dlrm_flexflow_amd import capi
 
 
@@ -45,15 +49,23 @@ def test_embedding_fwd_ragged_reference_golden(oracle):
         pos += ln
 
 
-@pytest.mark.skipif(not __import__("oracle.oracle", fromlist=["x"]).ref_available(),
-                    reason="oracle/_ref not built (needs /root/reference)")
 def test_embedding_fwd_matches_live_reference(oracle):
-    """Where oracle/_ref exists, compare on fresh seeded inputs too (bigger than the fixtures)."""
+    """Seeded inputs bigger than the fixtures above, bit for bit against the reference's outputs for them: the SHA-256 digests of
+    those outputs in embedding_fwd_ref_large.json (with digests of the inputs, drawn again here from the seed); where oracle/_ref
+    exists, against the live reference function too."""
+    with open(os.path.join(GOLDEN, "embedding_fwd_ref_large.json")) as f:
+        cases = json.load(f)
+    assert len(cases) == 5
+    sha = lambda a: hashlib.sha256(a.tobytes()).hexdigest()
     rng = np.random.default_rng(123)
-    for D, L in ((128, 1), (64, 4), (16, 1), (256, 2), (7, 3)):
-        w = rng.uniform(-1, 1, (5000, D)).astype(np.float32)
-        idx = rng.integers(0, 5000, (777, L))
-        assert oracle.embedding_fwd(idx, w).tobytes() == oracle.ref_embedding_fwd(idx, w).tobytes()
+    for k, c in enumerate(cases):
+        w = rng.uniform(-1, 1, (5000, c["D"])).astype(np.float32)
+        idx = rng.integers(0, 5000, (777, c["L"])).astype(np.int64)
+        assert sha(w) == c["w_sha256"] and sha(idx) == c["idx_sha256"], "the seeded stream differs from the one the fixture was made with"
+        out = oracle.embedding_fwd(idx, w)
+        assert sha(out) == c["out_sha256"], f"case {k} D={c['D']} L={c['L']}"
+        if oracle.ref_available():
+            assert out.tobytes() == oracle.ref_embedding_fwd(idx, w).tobytes()
 
 
 def test_embedding_fwd_rejects_out_of_range(oracle):

@@ -11,10 +11,10 @@ line() { grep '^{' | tail -1; }
 bash tools/pmc_traffic.sh > $O/pmc_traffic.log 2>&1; cp gpurun_out/pmc_traffic/pmc_traffic.json $O/${P}_pmc_traffic.json; cp $O/${P}_pmc_traffic.json profiles/${P}_pmc_traffic.json
 
 # 1. the default command, unprofiled: headline + roofline + kernels (bf16 mode, Kaggle secondary) + cpu_baseline
-python3 bench.py 2> $O/bench_default.err | line > $O/${P}_bench_terabyte.json
+python3 bench.py --full 2> $O/bench_default.err | line > $O/${P}_bench_terabyte.json
 
 # 2. the same command under the kernel trace (program directly after --; single-shape: no secondary blocks)
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --no-cpu-baseline --no-secondary 2> $O/prof.err | line > $O/${P}_bench_terabyte_under_rocprof.json
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 bench.py --full --no-cpu-baseline --no-secondary 2> $O/prof.err | line > $O/${P}_bench_terabyte_under_rocprof.json
 S=$(find $O/prof -name "*kernel_stats.csv" | head -1); cp $S $O/${P}_bench_terabyte_kernel_stats.csv
 T=$(find $O/prof -name "*kernel_trace.csv" | head -1)
 python3 tools/trace_summary.py $T > $O/${P}_bench_terabyte_step_timeline.txt
@@ -28,33 +28,33 @@ bash tools/pmc_sq.sh > $O/pmc_sq.log 2>&1; cp gpurun_out/pmc_sq/summary.json $O/
 bash tools/pmc_gemm.sh > $O/pmc_gemm.log 2>&1; cp gpurun_out/pmc_gemm/summary.json $O/${P}_pmc_sq_counters.json
 
 # 4. the other workloads (one GPU)
-python3 bench.py --no-cpu-baseline --no-secondary --shim-flags=--allow-tensor-op-math-conversion 2>/dev/null | line > $O/${P}_bench_terabyte_bf16_mode.json
-python3 bench.py --no-cpu-baseline --no-secondary --shim-flags=--fp32-split-bf16x3 2>/dev/null | line > $O/${P}_bench_terabyte_split_bf16x3_mode.json
-python3 bench.py --workload kaggle --steps 300 --warmup 30 2>/dev/null | line > $O/${P}_bench_kaggle.json
-python3 bench.py --workload tiny --steps 500 --warmup 50 2>/dev/null | line > $O/${P}_bench_tiny.json
-python3 bench.py --workload mlperf --steps 50 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | line > $O/${P}_bench_mlperf.json
-python3 bench.py --workload giant --steps 100 --warmup 10 --no-cpu-baseline --no-secondary 2>/dev/null | line > $O/${P}_bench_giant.json
-python3 bench.py --force-exchange --steps 30 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | line > $O/${P}_bench_terabyte_exchange_1rank.json
-python3 bench.py --workload kaggle --force-exchange --steps 300 --warmup 30 --no-cpu-baseline --no-secondary 2>/dev/null | line > $O/${P}_bench_kaggle_exchange_1rank.json
-python3 bench.py --per-gpu-batch 4096 --steps 100 --warmup 10 --no-cpu-baseline --no-secondary 2>/dev/null | line > $O/${P}_bench_terabyte_b4096.json
-python3 bench.py --per-gpu-batch 4096 --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --force-exchange 2>/dev/null | line > $O/${P}_bench_terabyte_b4096_exchange_1rank.json
+python3 bench.py --full --no-cpu-baseline --no-secondary --shim-flags=--allow-tensor-op-math-conversion 2>/dev/null | line > $O/${P}_bench_terabyte_bf16_mode.json
+python3 bench.py --full --no-cpu-baseline --no-secondary --shim-flags=--fp32-split-bf16x3 2>/dev/null | line > $O/${P}_bench_terabyte_split_bf16x3_mode.json
+python3 bench.py --full --workload kaggle --steps 300 --warmup 30 2>/dev/null | line > $O/${P}_bench_kaggle.json
+python3 bench.py --full --workload tiny --steps 500 --warmup 50 2>/dev/null | line > $O/${P}_bench_tiny.json
+python3 bench.py --full --workload mlperf --steps 50 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | line > $O/${P}_bench_mlperf.json
+python3 bench.py --full --workload giant --steps 100 --warmup 10 --no-cpu-baseline --no-secondary 2>/dev/null | line > $O/${P}_bench_giant.json
+python3 bench.py --full --force-exchange --steps 30 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | line > $O/${P}_bench_terabyte_exchange_1rank.json
+python3 bench.py --full --workload kaggle --force-exchange --steps 300 --warmup 30 --no-cpu-baseline --no-secondary 2>/dev/null | line > $O/${P}_bench_kaggle_exchange_1rank.json
+python3 bench.py --full --per-gpu-batch 4096 --steps 100 --warmup 10 --no-cpu-baseline --no-secondary 2>/dev/null | line > $O/${P}_bench_terabyte_b4096.json
+python3 bench.py --full --per-gpu-batch 4096 --steps 100 --warmup 10 --no-cpu-baseline --no-secondary --force-exchange 2>/dev/null | line > $O/${P}_bench_terabyte_b4096_exchange_1rank.json
 # ... and its kernel timelines (the per-rank step of the 8-GPU job), plain and exchange-forced
 for v in plain exchange; do
   F=""; [ $v = exchange ] && F="--force-exchange"
-  timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/prof_b4096_$v -- python3 bench.py --per-gpu-batch 4096 --steps 30 --warmup 5 --no-cpu-baseline --no-secondary $F > /dev/null 2>&1
+  timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/prof_b4096_$v -- python3 bench.py --full --per-gpu-batch 4096 --steps 30 --warmup 5 --no-cpu-baseline --no-secondary $F > /dev/null 2>&1
   T=$(find $O/prof_b4096_$v -name "*kernel_trace.csv" | head -1); python3 tools/trace_summary.py $T > $O/${P}_terabyte_b4096_${v}_step_timeline.txt
   find $O/prof_b4096_$v -name "*.csv" -size +10M -delete
 done
 
-timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/prof_mlperf -- python3 bench.py --workload mlperf --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > /dev/null 2>&1
+timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/prof_mlperf -- python3 bench.py --full --workload mlperf --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > /dev/null 2>&1
 T=$(find $O/prof_mlperf -name "*kernel_trace.csv" | head -1); python3 tools/trace_summary.py $T > $O/${P}_mlperf_step_timeline.txt; find $O/prof_mlperf -name "*.csv" -size +10M -delete
 
 # 5. hipGraph replay against eager launches, one step each
 for mode in graph eager; do
   F="--force-graph"; [ $mode = eager ] && F="--no-trace"
-  timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/prof_$mode -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-secondary $F 2>/dev/null | line > $O/tb_$mode.json
+  timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/prof_$mode -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-secondary $F 2>/dev/null | line > $O/tb_$mode.json
   T=$(find $O/prof_$mode -name "*kernel_trace.csv" | head -1); python3 tools/trace_summary.py $T -3 > $O/${P}_terabyte_${mode}_step_timeline.txt
-  timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/profk_$mode -- python3 bench.py --workload kaggle --steps 20 --warmup 5 --no-cpu-baseline --no-secondary $F 2>/dev/null | line > $O/kg_$mode.json
+  timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/profk_$mode -- python3 bench.py --full --workload kaggle --steps 20 --warmup 5 --no-cpu-baseline --no-secondary $F 2>/dev/null | line > $O/kg_$mode.json
   T=$(find $O/profk_$mode -name "*kernel_trace.csv" | head -1); python3 tools/trace_summary.py $T > $O/${P}_kaggle_${mode}_step_timeline.txt
   find $O/prof_$mode $O/profk_$mode -name "*.csv" -size +10M -delete
 done
