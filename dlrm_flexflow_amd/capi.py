@@ -174,6 +174,49 @@ _SIGS = {
 }
 
 
+# include/ff_hip_bf16.h: the optional bf16-table extension (its own list and version; libffhip.so exports it, the oracle does not)
+BF16_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_bf16.h")
+BF16_ROUND_STOCHASTIC, BF16_ROUND_NEAREST = 0, 1
+
+
+class EmbTableBf16(C.Structure):
+    """struct ffh_emb_table_bf16"""
+    _fields_ = [("idx", P), ("weight", P), ("io", P), ("num_entries", L), ("ld", L), ("table", C.c_int32), ("col0", C.c_int32)]
+
+
+class Bf16Rounding(C.Structure):
+    """struct ffh_bf16_rounding"""
+    _fields_ = [("mode", C.c_int32), ("reserved_", C.c_int32), ("seed", U64), ("counter", P)]
+
+
+_SIGS_BF16 = {
+    "ffh_bf16_abi_version": (I, []),
+    "ffh_embedding_fwd_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), I, I, I, L, I, P]),
+    "ffh_embedding_bwd_sgd_fused_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), I, I, I, L, I, F, C.POINTER(Bf16Rounding), P]),
+    "ffh_embedding_bwd_sort_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), I, I, I, L, P]),
+    "ffh_embedding_bwd_sgd_apply_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), I, I, I, L, I, F, C.POINTER(Bf16Rounding), P]),
+    "ffh_init_uniform_bf16": (I, [P, P, L, U64, F, F, P]),
+    "ffh_bf16_counter_advance": (I, [P, P, P]),
+}
+
+
+def bf16_header_symbols(header_path: str = BF16_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_BF16_API_LIST X-macro in include/ff_hip_bf16.h."""
+    text = open(header_path).read()
+    m = re.search(r"#define FFH_BF16_API_LIST\(X\)(.*?)\n\n", text, re.S)
+    if not m:
+        raise RuntimeError("FFH_BF16_API_LIST not found in " + header_path)
+    return re.findall(r"X\((\w+)\)", m.group(1))
+
+
+def bf16_header_abi_version(header_path: str = BF16_HEADER_PATH) -> int:
+    """FFH_BF16_ABI_VERSION of include/ff_hip_bf16.h."""
+    m = re.search(r"#define\s+FFH_BF16_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_BF16_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
 def header_symbols(header_path: str = HEADER_PATH) -> list[str]:
     """Every symbol of the FFH_API_LIST X-macro in include/ff_hip.h."""
     text = open(header_path).read()
@@ -305,6 +348,53 @@ class FFHLib:
         ba = (L * n)(*[int(v) for v in in_blk])
         la = (L * n)(*[int(v) for v in in_ld]) if in_ld is not None else None
         self.check(getattr(self.lib, name)(self.ctx, ptr(big), out_blk, pa, ba, la, n, num_blocks, ptr(stream)), name)
+
+
+class Bf16Api:
+    """The bf16-table extension (include/ff_hip_bf16.h) of a loaded FFHLib; `bf16_api(lib)` builds it or raises."""
+
+    def __init__(self, lib: FFHLib):
+        self.base = lib
+        for name, (res, args) in _SIGS_BF16.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no bf16-table extension ({name} missing; include/ff_hip_bf16.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_bf16_abi_version()
+        if got != bf16_header_abi_version():
+            raise FFHError(f"{lib.path}: bf16 ABI version {got}, include/ff_hip_bf16.h says {bf16_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+    def call(self, name: str, *args):
+        """Call `name(ctx, *args)` of the extension; pointers may be tensors/arrays/ints/None."""
+        sig = _SIGS_BF16[name][1][1:]
+        if len(args) != len(sig):
+            raise TypeError(f"{name}: expected {len(sig)} args, got {len(args)}")
+        conv = [ptr(a) if t is P else a for a, t in zip(args, sig)]
+        self.base.check(getattr(self.lib, name)(self.ctx, *conv), name)
+
+    @staticmethod
+    def tables(entries) -> "C.Array":
+        """entries: iterable of (idx, weight, io, num_entries, ld[, table[, col0]]); `table` defaults to the entry's position."""
+        entries = list(entries)
+        arr = (EmbTableBf16 * len(entries))()
+        for k, e in enumerate(entries):
+            idx, w, io, r, ld = e[:5]
+            table = int(e[5]) if len(e) > 5 else k
+            col0 = int(e[6]) if len(e) > 6 else 0
+            arr[k] = EmbTableBf16(ptr(idx), ptr(w), ptr(io), int(r), int(ld), table, col0)
+        return arr
+
+    @staticmethod
+    def rounding(mode: int = BF16_ROUND_STOCHASTIC, seed: int = 0, counter=None) -> Bf16Rounding:
+        return Bf16Rounding(int(mode), 0, int(seed) & (2**64 - 1), ptr(counter))
+
+
+def bf16_api(lib: FFHLib) -> Bf16Api:
+    """The bf16-table entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
+    return Bf16Api(lib)
 
 
 _hip_singleton: FFHLib | None = None

@@ -15,6 +15,8 @@
 //     in registers by the lane-group that owns the run, and each touched row is
 //     read-modified-written exactly once.
 #include "ffh_common.h"
+#include "../../include/ff_hip_bf16.h"
+#include "../../include/ffh_bf16.h"
 #ifdef FFH_MSD_TIMING
 #include <vector>
 #endif
@@ -42,12 +44,25 @@ struct EmbArgs {
 // ---------------------------------------------------------------------------
 // forward: out[b][:] = sum_j W[idx[b][j]][:]
 // ---------------------------------------------------------------------------
-// VEC = floats per lane per access (4: 16-B accesses; 1: any D / alignment)
-template <int VEC, int UNROLL>
+// VEC = table elements per lane per access: 4 (fp32 tables: 16-B accesses; bf16 tables, WT = uint16_t (ff_hip_bf16.h): 8-B accesses)
+// or 1 (any D / alignment).  A bf16 element widens exactly and the sums run in the same order: the same bits as the fp32 gather on
+// the widened table.
+template <int VEC, class WT> struct RowVec { typedef typename std::conditional<VEC == 4, float4, float>::type type; };
+template <> struct RowVec<4, uint16_t> { typedef uint2 type; };
+template <> struct RowVec<1, uint16_t> { typedef unsigned short type; };
+template <int VEC, class WT>
+__device__ __forceinline__ float row_elem(const typename RowVec<VEC, WT>::type& v, int k) {
+  if constexpr (std::is_same<WT, float>::value) return reinterpret_cast<const float*>(&v)[k];
+  else return ffh_bf16_to_f32(reinterpret_cast<const unsigned short*>(&v)[k]);
+}
+
+template <int VEC, int UNROLL, class WT = float>
 __global__ __launch_bounds__(256) void emb_fwd_kernel(const EmbArgs a) {
   ffh_kernel_prio();
-  using vec_t = typename std::conditional<VEC == 4, float4, float>::type;
+  using vec_t = typename RowVec<VEC, WT>::type;
+  constexpr int NQ = VEC / 4;                     // 16-B groups of output floats per lane-access (0: scalar)
   const ffh_emb_table tb = a.t[blockIdx.y];
+  const WT* const wt = reinterpret_cast<const WT*>(tb.weight);
   unsigned short* const o16 = a.out16[blockIdx.y];
   char* const o3 = a.out3[blockIdx.y];
   const int o3c = a.out3c[blockIdx.y];
@@ -83,38 +98,47 @@ __global__ __launch_bounds__(256) void emb_fwd_kernel(const EmbArgs a) {
 #pragma unroll
         for (int u = 0; u < UNROLL; u++)
           if (row[u] >= 0) {
-            const vec_t* src = reinterpret_cast<const vec_t*>(tb.weight + row[u] * (int64_t)D) + c;
-            if (VEC == 4 && (a.nt & 2) && tb.num_entries > a.nt_rows) { typedef float f4 __attribute__((ext_vector_type(4))); const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4*>(src)); val[u] = *reinterpret_cast<const vec_t*>(&t); }
+            const vec_t* src = reinterpret_cast<const vec_t*>(wt + row[u] * (int64_t)D) + c;
+            if (sizeof(vec_t) == 16 && (a.nt & 2) && tb.num_entries > a.nt_rows) { typedef float f4 __attribute__((ext_vector_type(4))); const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4*>(src)); val[u] = *reinterpret_cast<const vec_t*>(&t); }
             else val[u] = *src;
           }
 #pragma unroll
         for (int u = 0; u < UNROLL; u++)
           if (row[u] >= 0) {
-            const float* f = reinterpret_cast<const float*>(&val[u]);
 #pragma unroll
-            for (int v = 0; v < VEC; v++) acc[u][v] = acc[u][v] + f[v];   // 0 + w first: (+0)+(-0) = +0 as the reference
+            for (int v = 0; v < VEC; v++) acc[u][v] = acc[u][v] + row_elem<VEC, WT>(val[u], v);   // 0 + w first: (+0)+(-0) = +0 as the reference
           }
       }
 #pragma unroll
       for (int u = 0; u < UNROLL; u++) {
         const int64_t b = b0 + (int64_t)u * rpw;
         if (active && b < a.batch) {
-          vec_t o;
-          float* f = reinterpret_cast<float*>(&o);
+          float f[VEC];
 #pragma unroll
           for (int v = 0; v < VEC; v++) f[v] = avg ? acc[u][v] * inv : acc[u][v];
-          if (VEC == 4 && (a.nt & 1)) { typedef float f4 __attribute__((ext_vector_type(4))); __builtin_nontemporal_store(*reinterpret_cast<const f4*>(&o), reinterpret_cast<f4*>(tb.io + b * tb.ld) + c); }
-          else reinterpret_cast<vec_t*>(tb.io + b * tb.ld)[c] = o;
-          if (VEC == 4 && o16) {      // the twin the first top-MLP GEMM reads its operand from (ffh_ctx_bf16_mirror_set)
-            typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-            const bf2 lo = {(__bf16)f[0], (__bf16)f[1]}, hi = {(__bf16)f[2], (__bf16)f[3]};
-            reinterpret_cast<uint2*>(o16 + b * tb.ld)[c] = make_uint2(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi));
-          }
-          if (VEC == 4 && o3) {       // split mode: the three-plane image of the row piece (ffh_ctx_bf16x3_mirror_set; ld a multiple of 32)
-            uint2 p1, p2, p3;
-            ffh_split_bf16x3(make_float4(f[0], f[1], f[2], f[3]), p1, p2, p3);
-            char* d = o3 + b * tb.ld * 6 + ffh_i32_off(o3c + 4 * c);
-            *reinterpret_cast<uint2*>(d) = p1; *reinterpret_cast<uint2*>(d + 64) = p2; *reinterpret_cast<uint2*>(d + 128) = p3;
+          if constexpr (NQ == 0) {
+            tb.io[b * tb.ld + c] = f[0];
+          } else {
+#pragma unroll
+            for (int h = 0; h < NQ; h++) {
+              const int q = c * NQ + h;                 // float4 index in the output row
+              const float* g = f + 4 * h;
+              typedef float f4 __attribute__((ext_vector_type(4)));
+              const f4 o = {g[0], g[1], g[2], g[3]};
+              if (a.nt & 1) __builtin_nontemporal_store(o, reinterpret_cast<f4*>(tb.io + b * tb.ld) + q);
+              else reinterpret_cast<f4*>(tb.io + b * tb.ld)[q] = o;
+              if (o16) {      // the twin the first top-MLP GEMM reads its operand from (ffh_ctx_bf16_mirror_set)
+                typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+                const bf2 lo = {(__bf16)g[0], (__bf16)g[1]}, hi = {(__bf16)g[2], (__bf16)g[3]};
+                reinterpret_cast<uint2*>(o16 + b * tb.ld)[q] = make_uint2(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi));
+              }
+              if (o3) {       // split mode: the three-plane image of the row piece (ffh_ctx_bf16x3_mirror_set; ld a multiple of 32)
+                uint2 p1, p2, p3;
+                ffh_split_bf16x3(make_float4(g[0], g[1], g[2], g[3]), p1, p2, p3);
+                char* d = o3 + b * tb.ld * 6 + ffh_i32_off(o3c + 4 * q);
+                *reinterpret_cast<uint2*>(d) = p1; *reinterpret_cast<uint2*>(d + 64) = p2; *reinterpret_cast<uint2*>(d + 128) = p3;
+              }
+            }
           }
         }
       }
@@ -389,10 +413,78 @@ enum : uint32_t { kMetaNone = 0, kMetaFirst = 1, kMetaCont = 2 };
 // of the kernels: 0 = plain SGD (the fused update of SURVEY 8a-4, unchanged instructions), 1 = sgd_update with weight decay /
 // momentum / nesterov, 2 = adam_update -- the element arithmetic of sgd_kernel / adam_kernel (elementwise.hip), statement by
 // statement, so a row hit by one gradient row ends up with the bits the dense optimizer gives that row.
-struct OptP { float lr, wd, mom, b1, b2, eps, omb1, omb2; int nesterov; int64_t nt_rows; };   // nt_rows: tables of more rows have their rows read and written nontemporal (plain SGD, 16-byte form)
+// OPT 3 (kOptSgdBf16): plain SGD on a bf16 table (ff_hip_bf16.h): the weight row is 16-bit, w32 = fmaf(-lr, sum, (float)w16) as
+// OPT 0 computes it on the widened table, then one rounding (ffh_bf16.h) keyed by the update counter, table, global row and column.
+// sr_* / SrKey: that rounding (sr_counter: the update number in device memory).
+struct OptP { float lr, wd, mom, b1, b2, eps, omb1, omb2; int nesterov; int64_t nt_rows;   // nt_rows: tables of more rows have their rows read and written nontemporal (plain SGD, 16-byte form)
+              int sr_mode; uint64_t sr_seed; const uint64_t* sr_counter; };
+constexpr int kOptSgdBf16 = 3;
+
+constexpr bool opt_plain(int OPT) { return OPT == 0 || OPT == kOptSgdBf16; }   // no optimizer state
+constexpr bool opt_state(int OPT) { return OPT == 1 || OPT == 2; }
+struct Bf16Keys { int32_t table[FFH_MAX_TABLES]; int32_t col0[FFH_MAX_TABLES]; };   // kOptSgdBf16: in place of the (unused) s1 pointers
+struct SrKey { uint64_t tkey; int64_t col0; };                                      // per table: ffh_bf16_sr_table_key, global column of column 0
+template <int OPT>
+__device__ __forceinline__ SrKey sr_key(const OptP& o, const Bf16Keys& k, int tix) {
+  SrKey r{0, 0};
+  if (OPT == kOptSgdBf16) {
+    r.col0 = k.col0[tix];
+    if (o.sr_mode == FFH_BF16_ROUND_STOCHASTIC) r.tkey = ffh_bf16_sr_table_key(o.sr_seed, *o.sr_counter, (uint64_t)k.table[tix]);
+  }
+  return r;
+}
+// the row's first element: fp32 tables and bf16 tables alike come in as `float* weight` (ffh_emb_table; the bf16 entry points cast)
+template <int OPT>
+__device__ __forceinline__ float* weight_row(float* w, uint32_t row, int D) {
+  if (OPT == kOptSgdBf16) return reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(w) + (int64_t)row * D);
+  return w + (int64_t)row * D;
+}
+
+// the row's stochastic-rounding key (ffh_bf16_sr_row_key), once per row rather than per vector of it; 0 where unused
+template <int OPT>
+__device__ __forceinline__ uint64_t sr_row_key(const OptP& o, const SrKey& sk, uint32_t row) {
+  return (OPT == kOptSgdBf16 && o.sr_mode == FFH_BF16_ROUND_STOCHASTIC) ? ffh_bf16_sr_row_key(sk.tkey, row) : 0;
+}
 
 template <int VEC, int OPT>
-__device__ __forceinline__ void apply_row(const OptP& o, float* wrow, float* s0row, float* s1row, int c, const float (&acc)[VEC], const bool nt = false) {
+__device__ __forceinline__ void apply_row(const OptP& o, float* wrow, float* s0row, float* s1row, int c, const float (&acc)[VEC], const bool nt = false,
+                                          const SrKey& sk = SrKey{0, 0}, uint64_t rkey = 0) {
+  if (OPT == kOptSgdBf16) {
+    uint16_t* const w16 = reinterpret_cast<uint16_t*>(wrow);
+    uint16_t h[VEC];
+    if (VEC == 4) {
+      uint2 v;
+      if (nt) { typedef unsigned u2 __attribute__((ext_vector_type(2))); const u2 t = __builtin_nontemporal_load(reinterpret_cast<const u2*>(w16) + c); v = make_uint2(t.x, t.y); }
+      else v = reinterpret_cast<const uint2*>(w16)[c];
+      h[0] = (uint16_t)v.x; h[1] = (uint16_t)(v.x >> 16); h[2] = (uint16_t)v.y; h[3] = (uint16_t)(v.y >> 16);
+    } else {
+      h[0] = w16[c];
+    }
+    const int64_t g0 = sk.col0 + (int64_t)c * VEC;                 // global column of element 0
+    uint64_t grp = 0;
+    const bool sr = o.sr_mode == FFH_BF16_ROUND_STOCHASTIC;
+    if (sr) {
+      if (VEC == 4 && (g0 & 3) == 0) grp = ffh_bf16_sr_group(rkey, (uint64_t)g0);      // one hash serves the four columns
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; k++) {
+      const float w = __fmaf_rn(-o.lr, acc[k], ffh_bf16_to_f32(h[k]));
+      uint32_t r = 0;
+      if (sr) {
+        const uint64_t gc = (uint64_t)(g0 + k);
+        r = ffh_bf16_sr_field((VEC == 4 && (g0 & 3) == 0) ? grp : ffh_bf16_sr_group(rkey, gc), gc);
+      }
+      h[k] = ffh_bf16_round(w, o.sr_mode, r);
+    }
+    if (VEC == 4) {
+      const uint2 v = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
+      if (nt) { typedef unsigned u2 __attribute__((ext_vector_type(2))); const u2 t = {v.x, v.y}; __builtin_nontemporal_store(t, reinterpret_cast<u2*>(w16) + c); }
+      else reinterpret_cast<uint2*>(w16)[c] = v;
+    } else {
+      w16[c] = h[0];
+    }
+    return;
+  }
   if (OPT == 0) {
     if (VEC == 4 && nt) {
       typedef float f4 __attribute__((ext_vector_type(4)));
@@ -474,7 +566,10 @@ struct RedArgs {
   int       nchunks1;
   OptP      op;             // the row rule's parameters (op.lr = the plain update's lr)
   float*    s0[FFH_MAX_TABLES];   // OPT 1: momentum buffer V; OPT 2: first moment M -- [num_entries][D] like the table, or null
-  float*    s1[FFH_MAX_TABLES];   // OPT 2: second moment V
+  union {
+    float*  s1[FFH_MAX_TABLES];   // OPT 2: second moment V
+    Bf16Keys b16;                 // kOptSgdBf16: the tables' rounding keys
+  };
   // bucket form (emb_sgd_reduce_kernel<.., MSD = true>): kp[parity] is ordered by the top digit only
   uint8_t   shift_t[FFH_MAX_TABLES];   // the digit's position (0: the table is completely sorted)
 #ifdef FFH_MSD_TIMING
@@ -559,7 +654,7 @@ struct RedShared {
 template <int VEC, bool AGENT, int OPT>
 __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const uint2* kp,
                                                  float* partial_t, uint2* meta_t, int64_t N, int nchunks, int tile, int tile_index,
-                                                 int L, int D_, bool avg_, const OptP& op, float* st0, float* st1, RedShared& sh, const int tid = threadIdx.x,
+                                                 int L, int D_, bool avg_, const OptP& op, float* st0, float* st1, const SrKey& sk, RedShared& sh, const int tid = threadIdx.x,
                                                  const bool preloaded = false) {
   uint32_t* s_key = sh.key;
   uint32_t* s_pos = sh.pos;
@@ -641,7 +736,8 @@ __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const 
       const int odd = (s % FFH_EMB_CHUNK) ? 1 : 0;
       const bool single = head && tail;
       if (!single && c0 == 0) s_meta[(int)(chunk - tile0 / FFH_EMB_CHUNK) * 2 + odd] = make_uint2(head ? kMetaFirst : kMetaCont, key);
-      float* wrow = tb.weight + (int64_t)key * D;
+      float* wrow = weight_row<OPT>(tb.weight, key, D);
+      const uint64_t rkey = single ? sr_row_key<OPT>(op, sk, key) : 0;
       float* prow = partial_t + (chunk * 2 + odd) * D;
       for (int c = c0; c < nvec; c += lpr) {
         float acc[VEC];
@@ -664,7 +760,7 @@ __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const 
           for (int v = 0; v < VEC; v++) acc[v] = acc[v] + v0[v];
         }
         if (single) {
-          apply_row<VEC, OPT>(op, wrow, OPT ? st0 + (int64_t)key * D : nullptr, OPT == 2 ? st1 + (int64_t)key * D : nullptr, c, acc, tb.num_entries > op.nt_rows);
+          apply_row<VEC, OPT>(op, wrow, opt_state(OPT) ? st0 + (int64_t)key * D : nullptr, OPT == 2 ? st1 + (int64_t)key * D : nullptr, c, acc, tb.num_entries > op.nt_rows, sk, rkey);
         } else {
           xwg_store_row<VEC, AGENT>(prow, c, acc);
         }
@@ -690,7 +786,7 @@ __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const 
 // block's reduce tiles to finish, see emb_sgd_reduce_kernel) then needs nothing another block's tiles write.
 template <int VEC, bool AGENT, int OPT>
 __device__ __forceinline__ void fold_table_body(const ffh_emb_table& tb, const float* part, const uint2* meta, float* pout_t, uint2* mout_t,
-                                                int nin, int ratio, int D, const OptP& op, float* st0, float* st1, int64_t slot_lo, int64_t slot_hi,
+                                                int nin, int ratio, int D, const OptP& op, float* st0, float* st1, const SrKey& sk, int64_t slot_lo, int64_t slot_hi,
                                                 int64_t group0, int64_t ngroups, const uint2* keys = nullptr,
                                                 const uint2* staged = nullptr, int64_t staged_lo = 0, int staged_n = 0,
                                                 const uint32_t* nextkey = nullptr) {
@@ -744,7 +840,8 @@ __device__ __forceinline__ void fold_table_body(const ffh_emb_table& tb, const f
     const bool complete = head && !cont_after;
     const int64_t oslot = 2 * B + (at_block_start ? 0 : 1);
     if (!complete && c0 == 0) xwg_store2<AGENT>(mout_t + oslot, make_uint2(head ? kMetaFirst : kMetaCont, m.y));
-    float* wrow = tb.weight + (int64_t)m.y * D;
+    float* wrow = weight_row<OPT>(tb.weight, m.y, D);
+    const uint64_t rkey = complete ? sr_row_key<OPT>(op, sk, m.y) : 0;
     float* orow = pout_t + oslot * D;
     for (int c = c0; c < nvec; c += lpr) {
       float acc[VEC];
@@ -766,7 +863,7 @@ __device__ __forceinline__ void fold_table_body(const ffh_emb_table& tb, const f
         for (int v = 0; v < VEC; v++) acc[v] = acc[v] + v0[v];
       }
       if (complete) {
-        apply_row<VEC, OPT>(op, wrow, OPT ? st0 + (int64_t)m.y * D : nullptr, OPT == 2 ? st1 + (int64_t)m.y * D : nullptr, c, acc, tb.num_entries > op.nt_rows);
+        apply_row<VEC, OPT>(op, wrow, opt_state(OPT) ? st0 + (int64_t)m.y * D : nullptr, OPT == 2 ? st1 + (int64_t)m.y * D : nullptr, c, acc, tb.num_entries > op.nt_rows, sk, rkey);
       } else {
         xwg_store_row<VEC, AGENT>(orow, c, acc);
       }
@@ -1128,14 +1225,15 @@ __device__ __forceinline__ void msd_window(const uint2* __restrict__ kp, const u
 // trips, so every tile of the launch should be resident at once -- at 74 registers 1,536 of the 26-table shape's 1,664 tiles are,
 // and the launch takes 336 instead of 230 us.
 // OPT != 0 (momentum / weight-decay SGD, Adam on the touched rows): the row rule holds up to three more rows' worth of registers;
-// those instantiations are compiled for 4 waves per SIMD instead of spilling.
+// those instantiations are compiled for 4 waves per SIMD instead of spilling.  OPT kOptSgdBf16 (bf16 rows, the rounding hash): 6 waves per
+// SIMD -- at 8 it spilled 30 VGPRs; 6 and 4 were measured 193 / 192 against 200 us at the Terabyte shape.
 // MSD: the bucket form above (the list is grouped by top digit only; six workgroups per CU: the window needs 25 KB of LDS).
 struct RedSmem { RedShared sh; uint2 fmeta[kFoldStage]; };
 union MsdSmem { RedSmem red; MsdShared ms; };          // the window is dead once the tile's entries sit in registers
 template <bool MSD> struct RedSmemOf { typedef RedSmem type; static __device__ __forceinline__ RedSmem& red(RedSmem& s) { return s; } };
 template <> struct RedSmemOf<true> { typedef MsdSmem type; static __device__ __forceinline__ RedSmem& red(MsdSmem& s) { return s.red; } };
 template <int VEC, int OPT, bool MSD = false>
-__global__ __launch_bounds__(kRedThreads, MSD ? (OPT == 0 ? 6 : 4) : (OPT == 0 ? 8 : 4)) void emb_sgd_reduce_kernel(const RedArgs a) {
+__global__ __launch_bounds__(kRedThreads, MSD ? (opt_plain(OPT) ? 6 : 4) : (OPT == 0 ? 8 : OPT == kOptSgdBf16 ? 6 : 4)) void emb_sgd_reduce_kernel(const RedArgs a) {
   ffh_kernel_prio();
   __shared__ typename RedSmemOf<MSD>::type smem;
   __shared__ int s_last;
@@ -1146,8 +1244,9 @@ __global__ __launch_bounds__(kRedThreads, MSD ? (OPT == 0 ? 6 : 4) : (OPT == 0 ?
   const uint2* keys = a.kp[a.parity[tix]] + (int64_t)tix * a.N;
   float* p0 = a.partial + (int64_t)tix * 2 * a.nchunks * a.D;
   uint2* m0 = a.meta + (int64_t)tix * 2 * a.nchunks;
-  float* const st0 = a.s0[tix];
-  float* const st1 = a.s1[tix];
+  float* const st0 = opt_state(OPT) ? a.s0[tix] : nullptr;
+  float* const st1 = OPT == 2 ? a.s1[tix] : nullptr;
+  const SrKey sk = sr_key<OPT>(a.op, a.b16, tix);
   bool preloaded = false;
 #ifdef FFH_MSD_TIMING
   unsigned long long* dbg = a.dbg + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8;
@@ -1177,7 +1276,7 @@ __global__ __launch_bounds__(kRedThreads, MSD ? (OPT == 0 ? 6 : 4) : (OPT == 0 ?
   }
   MSD_STAMP(1);
   reduce_tile_body<VEC, true, OPT>(tb, keys, p0, m0, a.N, a.nchunks, a.tile,
-                        (int)blockIdx.x, a.L, a.D, a.avg != 0, a.op, st0, st1, sh, threadIdx.x, preloaded);
+                        (int)blockIdx.x, a.L, a.D, a.avg != 0, a.op, st0, st1, sk, sh, threadIdx.x, preloaded);
   MSD_STAMP(2);
 
   const int nvec = a.D / VEC;
@@ -1224,7 +1323,7 @@ __global__ __launch_bounds__(kRedThreads, MSD ? (OPT == 0 ? 6 : 4) : (OPT == 0 ?
     const int64_t lo = 2 * B1 * kRatio;
     const int64_t hi = lo + 2 * kRatio < 2 * (int64_t)a.nchunks ? lo + 2 * kRatio : 2 * (int64_t)a.nchunks;
     if (stage(m0, lo, hi))
-      fold_table_body<VEC, true, OPT>(tb, p0, m0, p1, m1, a.nchunks, kRatio, a.D, a.op, st0, st1, lo, hi, group0, ngroups, MSD ? nullptr : keys, s_fmeta, lo, (int)(hi - lo), nextkey);
+      fold_table_body<VEC, true, OPT>(tb, p0, m0, p1, m1, a.nchunks, kRatio, a.D, a.op, st0, st1, sk, lo, hi, group0, ngroups, MSD ? nullptr : keys, s_fmeta, lo, (int)(hi - lo), nextkey);
     xwg_stores_done();
     __syncthreads();
     if (threadIdx.x == 0) s_last = __hip_atomic_fetch_add(&arrive[a.nchunks1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)a.nchunks1 - 1u;
@@ -1232,11 +1331,11 @@ __global__ __launch_bounds__(kRedThreads, MSD ? (OPT == 0 ? 6 : 4) : (OPT == 0 ?
     if (!s_last) return;
     const int64_t hi1 = 2 * (int64_t)a.nchunks1;
     if (stage(m1, 0, hi1))
-      fold_table_body<VEC, true, OPT>(tb, p1, m1, p1, m1, a.nchunks1, 0, a.D, a.op, st0, st1, 0, hi1, group0, ngroups, nullptr, s_fmeta, 0, (int)(hi1 < kFoldStage ? hi1 : kFoldStage));
+      fold_table_body<VEC, true, OPT>(tb, p1, m1, p1, m1, a.nchunks1, 0, a.D, a.op, st0, st1, sk, 0, hi1, group0, ngroups, nullptr, s_fmeta, 0, (int)(hi1 < kFoldStage ? hi1 : kFoldStage));
   } else {
     const int64_t hi0 = 2 * (int64_t)a.nchunks;
     if (stage(m0, 0, hi0))
-      fold_table_body<VEC, true, OPT>(tb, p0, m0, p1, m1, a.nchunks, 0, a.D, a.op, st0, st1, 0, hi0, group0, ngroups, nullptr, s_fmeta, 0, (int)hi0);
+      fold_table_body<VEC, true, OPT>(tb, p0, m0, p1, m1, a.nchunks, 0, a.D, a.op, st0, st1, sk, 0, hi0, group0, ngroups, nullptr, s_fmeta, 0, (int)hi0);
   }
 }
 
@@ -1258,7 +1357,7 @@ struct SmallArgs {
   int tile;            // sorted entries per reduce team (multiple of FFH_EMB_CHUNK, <= kRedTile)
   OptP op;
   float* s0[FFH_MAX_TABLES];
-  float* s1[FFH_MAX_TABLES];
+  union { float* s1[FFH_MAX_TABLES]; Bf16Keys b16; };     // kOptSgdBf16: the tables' rounding keys in place of s1
 };
 
 constexpr int kSmallWaves = 8;                        // threads per table = 64 x this: sort ranks kSmallMax / threads entries per thread, reduce = teams of 256
@@ -1287,8 +1386,9 @@ __global__ __launch_bounds__(kSmallThreads) void emb_sgd_small_kernel(const Smal
   uint32_t (*s_off)[kMaxRadix] = sm.sort.off;
   const int tix = blockIdx.x;
   const ffh_emb_table tb = a.t[tix];
-  float* const st0 = a.s0[tix];
-  float* const st1 = a.s1[tix];
+  float* const st0 = opt_state(OPT) ? a.s0[tix] : nullptr;
+  float* const st1 = OPT == 2 ? a.s1[tix] : nullptr;
+  const SrKey sk = sr_key<OPT>(a.op, a.b16, tix);
   const int64_t N = a.N;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int radix = 1 << a.rb;
@@ -1348,7 +1448,7 @@ __global__ __launch_bounds__(kSmallThreads) void emb_sgd_small_kernel(const Smal
   const int team = threadIdx.x / kRedThreads, ttid = threadIdx.x % kRedThreads;
   const int ntiles = (int)((N + a.tile - 1) / a.tile);
   for (int t0 = 0; t0 < ntiles; t0 += kSmallRedParts) {
-    reduce_tile_body<VEC, false, OPT>(tb, keys, p0, m0, N, a.nch0, a.tile, t0 + team, a.L, a.D, a.avg != 0, a.op, st0, st1, sm.red[team], ttid);
+    reduce_tile_body<VEC, false, OPT>(tb, keys, p0, m0, N, a.nch0, a.tile, t0 + team, a.L, a.D, a.avg != 0, a.op, st0, st1, sk, sm.red[team], ttid);
     __syncthreads();
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1362,13 +1462,13 @@ __global__ __launch_bounds__(kSmallThreads) void emb_sgd_small_kernel(const Smal
   const int64_t ngroups = (int64_t)NW * rpw;
   float* p1 = a.partial1 + (int64_t)tix * 2 * a.nch1 * a.D;
   if (a.nch1 > 1) {
-    fold_table_body<VEC, false, OPT>(tb, p0, m0, p1, m1, a.nch0, FFH_EMB_CHUNK1 / FFH_EMB_CHUNK, a.D, a.op, st0, st1, 0, 2 * (int64_t)a.nch0, group0, ngroups);
+    fold_table_body<VEC, false, OPT>(tb, p0, m0, p1, m1, a.nch0, FFH_EMB_CHUNK1 / FFH_EMB_CHUNK, a.D, a.op, st0, st1, sk, 0, 2 * (int64_t)a.nch0, group0, ngroups);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    fold_table_body<VEC, false, OPT>(tb, p1, m1, p1, m1, a.nch1, 0, a.D, a.op, st0, st1, 0, 2 * (int64_t)a.nch1, group0, ngroups);
+    fold_table_body<VEC, false, OPT>(tb, p1, m1, p1, m1, a.nch1, 0, a.D, a.op, st0, st1, sk, 0, 2 * (int64_t)a.nch1, group0, ngroups);
   } else {
-    fold_table_body<VEC, false, OPT>(tb, p0, m0, p1, m1, a.nch0, 0, a.D, a.op, st0, st1, 0, 2 * (int64_t)a.nch0, group0, ngroups);
+    fold_table_body<VEC, false, OPT>(tb, p0, m0, p1, m1, a.nch0, 0, a.D, a.op, st0, st1, sk, 0, 2 * (int64_t)a.nch0, group0, ngroups);
   }
 }
 
@@ -1452,22 +1552,36 @@ __global__ __launch_bounds__(256) void emb_localize_kernel(const int64_t* __rest
 
 extern "C" {
 
-int ffh_embedding_fwd_multi(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L, int D, int64_t batch, int aggr, ffh_stream s) {
+}  // extern "C"
+
+// WT = float: ffh_embedding_fwd_multi; WT = uint16_t: ffh_embedding_fwd_multi_bf16 (`tables[i].weight` holds bf16 bits)
+template <class WT>
+static int emb_fwd_launch(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L, int D, int64_t batch, int aggr, ffh_stream s) {
   int rc = validate_tables(c, tables, nt, L, D, batch, aggr, "embedding_fwd");
   if (rc) return rc;
   if (nt == 0 || batch == 0) return FFH_OK;
+  constexpr bool b16 = std::is_same<WT, uint16_t>::value;
   const bool v4 = can_vec4(tables, nt, D);
-  const int nvec = v4 ? D / 4 : D;
+  int vec = v4 ? 4 : 1;
+  if (b16) {
+    // 4 bf16 per 8-B access, the output side as in the fp32 form.  (8 per 16-B access -- the lanes per row halved, the same bytes in
+    // flight per wave -- was measured at the Terabyte shape and was slower: 107 VGPRs, occupancy 4, 163 against 146 us; UNROLL 2
+    // did not help. profiles/bf16_table_bench.txt)
+    bool ok = D % 4 == 0;
+    for (int i = 0; i < nt; i++) ok = ok && ((uintptr_t)tables[i].weight & 7) == 0 && aligned16(tables[i].io) && tables[i].ld % 4 == 0;
+    vec = ok ? 4 : 1;
+  }
+  const int nvec = D / vec;
   if ((nvec + 63) / 64 > kMaxChunks * 64) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_fwd: out_dim too large");
   EmbArgs a;
   memset(&a, 0, sizeof a);
   for (int i = 0; i < nt; i++) {
     a.t[i] = tables[i];
     // tensor-op mode with a registered twin of the destination: the gather writes the bf16 roundings beside the fp32 rows
-    a.out16[i] = (v4 && tables[i].ld % 4 == 0) ? ffh_mirror_of(c, tables[i].io, (size_t)((batch - 1) * tables[i].ld + D) * 4) : nullptr;
+    a.out16[i] = (vec >= 4 && tables[i].ld % 4 == 0) ? ffh_mirror_of(c, tables[i].io, (size_t)((batch - 1) * tables[i].ld + D) * 4) : nullptr;
     // split mode with a registered image of the destination (rows a whole number of 32-element groups apart): the three terms beside the fp32 rows
     int col0 = 0;
-    a.out3[i] = (v4 && tables[i].ld % 32 == 0) ? ffh_planes_of(c, tables[i].io, (size_t)((batch - 1) * tables[i].ld + D) * 4, &col0) : nullptr;
+    a.out3[i] = (vec >= 4 && tables[i].ld % 32 == 0) ? ffh_planes_of(c, tables[i].io, (size_t)((batch - 1) * tables[i].ld + D) * 4, &col0) : nullptr;
     a.out3c[i] = col0;
     if (a.out3[i] && (col0 & 3)) a.out3[i] = nullptr;
   }
@@ -1477,7 +1591,7 @@ int ffh_embedding_fwd_multi(ffh_ctx* c, const ffh_emb_table* tables, int nt, int
   // not evict the rows of the 18 small tables (62 MB) that do live in L2 / Infinity Cache.  One box, interleaved: 139.4 -> 133.7 (stores) / 133.8
   // (loads) / 130.9 us (both) = 0.79 -> 0.84 of 8 TB/s by the algorithmic-bytes formula; the step unchanged.  Same bits.
   a.nt = FFH_LAB_INT("FFH_EMB_NT", 3);
-  a.nt_rows = (int64_t)FFH_LAB_INT("FFH_EMB_NT_MB", 64) * (1 << 20) / ((int64_t)D * 4);      // tables above 64 MB
+  a.nt_rows = (int64_t)FFH_LAB_INT("FFH_EMB_NT_MB", 64) * (1 << 20) / ((int64_t)D * (int64_t)sizeof(WT));      // tables above 64 MB (bytes, not rows)
   const int lpr = nvec < 64 ? nvec : 64;
   const int rpw = 64 / lpr;
   constexpr int U = 4;
@@ -1488,10 +1602,16 @@ int ffh_embedding_fwd_multi(ffh_ctx* c, const ffh_emb_table* tables, int nt, int
   const int64_t cap = cap_env / nt > 0 ? cap_env / nt : 1;
   if (gx > cap) gx = cap;
   dim3 grid((unsigned)gx, (unsigned)nt);
-  if (v4) hipLaunchKernelGGL((emb_fwd_kernel<4, U>), grid, dim3(256), 0, as_stream(s), a);
-  else hipLaunchKernelGGL((emb_fwd_kernel<1, U>), grid, dim3(256), 0, as_stream(s), a);
+  if (vec == 4) hipLaunchKernelGGL((emb_fwd_kernel<4, U, WT>), grid, dim3(256), 0, as_stream(s), a);
+  else hipLaunchKernelGGL((emb_fwd_kernel<1, U, WT>), grid, dim3(256), 0, as_stream(s), a);
   FFH_LAUNCH_CHECK(c, "emb_fwd_kernel");
   return FFH_OK;
+}
+
+extern "C" {
+
+int ffh_embedding_fwd_multi(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L, int D, int64_t batch, int aggr, ffh_stream s) {
+  return emb_fwd_launch<float>(c, tables, nt, L, D, batch, aggr, s);
 }
 
 int ffh_embedding_fwd(ffh_ctx* c, const int64_t* idx, float* out, const float* weight, int L, int D, int64_t batch,
@@ -1530,17 +1650,26 @@ size_t ffh_embedding_bwd_workspace_bytes(int nt, int L, int D, int64_t batch) {
 // needs the output gradients -- segmented reduce, folds, the SGD step -- when they exist (ffh_embedding_bwd_sgd_apply_multi).
 // Same launches in the same order on the same workspace: the fused entry is both phases back to back.
 // `opt` / `states`: the row rule (ffh_sparse_opt) and the per-table optimizer state it updates; null opt = plain SGD with `lr`
+// `b16`: bf16 tables (ff_hip_bf16.h; `tables[i].weight` holds bf16 bits): plain SGD with `lr`, the kOptSgdBf16 row rule
+struct Bf16Cfg { const ffh_bf16_rounding* r; Bf16Keys keys; };
 static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L, int D, int64_t batch,
                           int aggr, float lr, ffh_stream s, const bool do_sort, const bool do_apply,
-                          const ffh_sparse_opt* opt = nullptr, const ffh_emb_state* states = nullptr) {
+                          const ffh_sparse_opt* opt = nullptr, const ffh_emb_state* states = nullptr, const Bf16Cfg* b16 = nullptr) {
   int rc = validate_tables(c, tables, nt, L, D, batch, aggr, "embedding_bwd_sgd_fused");
   if (rc) return rc;
   OptP op{};
   op.lr = lr;
+  if (b16 && do_apply) {
+    const ffh_bf16_rounding* r = b16->r;
+    if (!r) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_bf16: null ffh_bf16_rounding");
+    if (r->mode != FFH_BF16_ROUND_STOCHASTIC && r->mode != FFH_BF16_ROUND_NEAREST) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_bf16: unknown rounding mode");
+    if (r->mode == FFH_BF16_ROUND_STOCHASTIC && !r->counter) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_bf16: stochastic rounding needs the update counter");
+    op.sr_mode = r->mode; op.sr_seed = r->seed; op.sr_counter = r->counter;
+  }
   // (round 6) the rows of a table above 64 MB are read and written back NONTEMPORAL by the plain-SGD apply step: a row of such a table is touched once
   // per launch and must not evict the small tables' rows from L2 / Infinity Cache (as in the gather): 26 tables x 32768 lookups 198.0 -> 188.2 us
   // = 0.83 -> 0.875 of 8 TB/s, interleaved on one box; same bits
-  op.nt_rows = (int64_t)FFH_LAB_INT("FFH_EMB_APPLY_NT_MB", 64) * (int64_t)(1 << 20) / ((int64_t)D * 4);
+  op.nt_rows = (int64_t)FFH_LAB_INT("FFH_EMB_APPLY_NT_MB", 64) * (int64_t)(1 << 20) / ((int64_t)D * (b16 ? 2 : 4));      // (bytes, not rows)
   int kind = FFH_SPARSE_OPT_SGD;
   if (opt && do_apply) {
     kind = opt->kind;
@@ -1610,13 +1739,14 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
     sm.N = N; sm.nch0 = lay.nchunks; sm.nch1 = lay.nchunks1; sm.rb = rb_s; sm.L = L; sm.D = D;
     sm.avg = aggr == FFH_AGGR_MODE_AVG ? 1 : 0; sm.op = op;
     for (int i = 0; i < nt && kind != FFH_SPARSE_OPT_SGD; i++) { sm.s0[i] = states[i].s0; sm.s1[i] = states[i].s1; }
+    if (b16) sm.b16 = b16->keys;
     int tile = (int)((N + kSmallRedParts - 1) / kSmallRedParts);          // one tile per 256-thread team
     tile = (tile + FFH_EMB_CHUNK - 1) / FFH_EMB_CHUNK * FFH_EMB_CHUNK;
     sm.tile = tile < FFH_EMB_CHUNK ? FFH_EMB_CHUNK : tile;
 #define FFH_SMALL(OPTV)                                                                                               \
     { if (v4) hipLaunchKernelGGL((emb_sgd_small_kernel<4, OPTV>), dim3(nt), dim3(kSmallThreads), 0, as_stream(s), sm);  \
       else hipLaunchKernelGGL((emb_sgd_small_kernel<1, OPTV>), dim3(nt), dim3(kSmallThreads), 0, as_stream(s), sm); }
-    if (kind == FFH_SPARSE_OPT_SGD) FFH_SMALL(0) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_SMALL(1) else FFH_SMALL(2)
+    if (b16) FFH_SMALL(kOptSgdBf16) else if (kind == FFH_SPARSE_OPT_SGD) FFH_SMALL(0) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_SMALL(1) else FFH_SMALL(2)
 #undef FFH_SMALL
     FFH_LAUNCH_CHECK(c, "emb_sgd_small_kernel");
     return FFH_OK;
@@ -1691,6 +1821,7 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   ra.avg = aggr == FFH_AGGR_MODE_AVG ? 1 : 0;
   ra.op = op;
   for (int i = 0; i < nt && kind != FFH_SPARSE_OPT_SGD; i++) { ra.s0[i] = states[i].s0; ra.s1[i] = states[i].s1; }
+  if (b16) ra.b16 = b16->keys;
   ra.partial1 = (float*)(ws + lay.partial1);
   ra.meta1 = (uint2*)(ws + lay.meta1); ra.nchunks1 = lay.nchunks1;
   ra.arrive = (uint32_t*)(ws + lay.arrive);
@@ -1704,7 +1835,8 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   if (!dbg_buf) hipMalloc(&dbg_buf, 8 * 8 * 65536);
   ra.dbg = dbg_buf;
 #endif
-  if (msd) { if (kind == FFH_SPARSE_OPT_SGD) FFH_RED(0, true) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_RED(1, true) else FFH_RED(2, true) }
+  if (b16) { if (msd) FFH_RED(kOptSgdBf16, true) else FFH_RED(kOptSgdBf16, false) }
+  else if (msd) { if (kind == FFH_SPARSE_OPT_SGD) FFH_RED(0, true) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_RED(1, true) else FFH_RED(2, true) }
   else { if (kind == FFH_SPARSE_OPT_SGD) FFH_RED(0, false) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_RED(1, false) else FFH_RED(2, false) }
 #undef FFH_RED
   FFH_LAUNCH_CHECK(c, "emb_sgd_reduce/fold");
@@ -1760,3 +1892,80 @@ int ffh_embedding_bwd_sgd_fused(ffh_ctx* c, const int64_t* idx, const float* g, 
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// bf16 tables (include/ff_hip_bf16.h): the fp32 launchers with 16-bit weight rows, the numerics of include/ffh_bf16.h
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void init_uniform_bf16_kernel(uint16_t* __restrict__ p, int64_t n, uint64_t seed, float lo, float hi) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    p[i] = ffh_bf16_rne(ffh_uniform(ffh_hash(seed, (uint64_t)i), lo, hi));
+}
+
+__global__ void bf16_counter_advance_kernel(uint64_t* counter) { *counter = *counter + 1; }
+
+// the tables as ffh_emb_table (the weight pointer carries the bf16 bits; the kernels read it through WT / kOptSgdBf16) and their keys
+static int bf16_tables(ffh_ctx* c, const ffh_emb_table_bf16* in, int nt, ffh_emb_table* out, Bf16Keys* keys) {
+  if (nt < 0 || nt > FFH_MAX_TABLES) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bf16: ntables out of range");
+  if (nt > 0 && !in) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bf16: null tables");
+  for (int i = 0; i < nt; i++) {
+    if (in[i].table < 0 || in[i].col0 < 0) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bf16: negative table index or col0");
+    out[i] = ffh_emb_table{in[i].idx, reinterpret_cast<float*>(in[i].weight), in[i].io, in[i].num_entries, in[i].ld};
+    if (keys) { keys->table[i] = in[i].table; keys->col0[i] = in[i].col0; }
+  }
+  return FFH_OK;
+}
+
+static int emb_bwd_bf16(ffh_ctx* c, const ffh_emb_table_bf16* tables, int nt, int L, int D, int64_t batch, int aggr, float lr,
+                        const ffh_bf16_rounding* r, ffh_stream s, bool do_sort, bool do_apply) {
+  ffh_emb_table t[FFH_MAX_TABLES];
+  Bf16Cfg cfg;
+  memset(&cfg, 0, sizeof cfg);
+  cfg.r = r;
+  const int rc = bf16_tables(c, tables, nt, t, &cfg.keys);
+  if (rc) return rc;
+  return emb_bwd_phases(c, t, nt, L, D, batch, aggr, lr, s, do_sort, do_apply, nullptr, nullptr, &cfg);
+}
+
+extern "C" {
+
+int ffh_bf16_abi_version(void) { return FFH_BF16_ABI_VERSION; }
+
+int ffh_embedding_fwd_multi_bf16(ffh_ctx* c, const ffh_emb_table_bf16* tables, int nt, int L, int D, int64_t batch, int aggr, ffh_stream s) {
+  ffh_emb_table t[FFH_MAX_TABLES];
+  const int rc = bf16_tables(c, tables, nt, t, nullptr);
+  if (rc) return rc;
+  return emb_fwd_launch<uint16_t>(c, t, nt, L, D, batch, aggr, s);
+}
+
+int ffh_embedding_bwd_sgd_fused_multi_bf16(ffh_ctx* c, const ffh_emb_table_bf16* tables, int nt, int L, int D, int64_t batch,
+                                           int aggr, float lr, const ffh_bf16_rounding* r, ffh_stream s) {
+  return emb_bwd_bf16(c, tables, nt, L, D, batch, aggr, lr, r, s, true, true);
+}
+
+int ffh_embedding_bwd_sort_multi_bf16(ffh_ctx* c, const ffh_emb_table_bf16* tables, int nt, int L, int D, int64_t batch, ffh_stream s) {
+  return emb_bwd_bf16(c, tables, nt, L, D, batch, FFH_AGGR_MODE_SUM, 0.0f, nullptr, s, true, false);
+}
+
+int ffh_embedding_bwd_sgd_apply_multi_bf16(ffh_ctx* c, const ffh_emb_table_bf16* tables, int nt, int L, int D, int64_t batch,
+                                           int aggr, float lr, const ffh_bf16_rounding* r, ffh_stream s) {
+  return emb_bwd_bf16(c, tables, nt, L, D, batch, aggr, lr, r, s, false, true);
+}
+
+int ffh_init_uniform_bf16(ffh_ctx* c, uint16_t* p, int64_t n, uint64_t seed, float lo, float hi, ffh_stream s) {
+  FFH_REQUIRE(c, n >= 0 && (p || n == 0), "init_uniform_bf16: bad args");
+  if (n == 0) return FFH_OK;
+  hipLaunchKernelGGL(init_uniform_bf16_kernel, dim3(ffh_grid(n, 256, 8192)), dim3(256), 0, as_stream(s), p, n, seed, lo, hi);
+  FFH_LAUNCH_CHECK(c, "init_uniform_bf16");
+  return FFH_OK;
+}
+
+int ffh_bf16_counter_advance(ffh_ctx* c, uint64_t* counter, ffh_stream s) {
+  FFH_REQUIRE(c, counter != nullptr, "bf16_counter_advance: null counter");
+  hipLaunchKernelGGL(bf16_counter_advance_kernel, dim3(1), dim3(1), 0, as_stream(s), counter);
+  FFH_LAUNCH_CHECK(c, "bf16_counter_advance");
+  return FFH_OK;
+}
+
+}  // extern "C"
+static_assert(sizeof(RedArgs) <= 4096 && sizeof(SmallArgs) <= 4096 && sizeof(EmbArgs) <= 4096, "kernel arguments");

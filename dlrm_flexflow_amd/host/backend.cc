@@ -52,6 +52,23 @@ const KernelApi* load_kernel_api(const std::string& path_in) {
     fprintf(stderr, "FATAL: %s has ABI version %d, expected %d\n", path.c_str(), api->ffh_abi_version(), FFH_ABI_VERSION);
     abort();
   }
+  // the bf16-table extension: absent is fine (the library loads as before), present means complete and of this version
+  if (dlsym(h, "ffh_bf16_abi_version")) {
+    KernelApiBf16* b = new KernelApiBf16();
+#define FFH_LOAD(name)                                                        \
+  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
+  if (!b->name) {                                                             \
+    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_bf16.h: %s is missing\n", path.c_str(), #name);   \
+    abort();                                                                  \
+  }
+    FFH_BF16_API_LIST(FFH_LOAD)
+#undef FFH_LOAD
+    if (b->ffh_bf16_abi_version() != FFH_BF16_ABI_VERSION) {
+      fprintf(stderr, "FATAL: %s has bf16 ABI version %d, expected %d\n", path.c_str(), b->ffh_bf16_abi_version(), FFH_BF16_ABI_VERSION);
+      abort();
+    }
+    api->bf16 = b;
+  }
   if (path_in.empty() && g_env_override)
     fprintf(stderr, "[DLRM] FFH_BACKEND_LIB: kernel library %s (%s)\n", path.c_str(), api->ffh_backend_name());
   cache[path] = api;
