@@ -37,8 +37,7 @@ struct EmbArgs {
   int     L;
   int     D;
   int     aggr;
-  int     nt;            // bit 0: nontemporal stores of the output rows; bit 1: nontemporal loads of the rows of tables of more than nt_rows rows (below)
-  int64_t nt_rows;
+  int64_t nt_rows;       // tables of more rows: the 16-byte row loads carry a nontemporal hint, which the compiler drops (emb_fwd_launch)
 };
 
 // ---------------------------------------------------------------------------
@@ -99,7 +98,7 @@ __global__ __launch_bounds__(256) void emb_fwd_kernel(const EmbArgs a) {
         for (int u = 0; u < UNROLL; u++)
           if (row[u] >= 0) {
             const vec_t* src = reinterpret_cast<const vec_t*>(wt + row[u] * (int64_t)D) + c;
-            if (sizeof(vec_t) == 16 && (a.nt & 2) && tb.num_entries > a.nt_rows) { typedef float f4 __attribute__((ext_vector_type(4))); const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4*>(src)); val[u] = *reinterpret_cast<const vec_t*>(&t); }
+            if (sizeof(vec_t) == 16 && tb.num_entries > a.nt_rows) { typedef float f4 __attribute__((ext_vector_type(4))); const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4*>(src)); val[u] = *reinterpret_cast<const vec_t*>(&t); }
             else val[u] = *src;
           }
 #pragma unroll
@@ -125,8 +124,7 @@ __global__ __launch_bounds__(256) void emb_fwd_kernel(const EmbArgs a) {
               const float* g = f + 4 * h;
               typedef float f4 __attribute__((ext_vector_type(4)));
               const f4 o = {g[0], g[1], g[2], g[3]};
-              if (a.nt & 1) __builtin_nontemporal_store(o, reinterpret_cast<f4*>(tb.io + b * tb.ld) + q);
-              else reinterpret_cast<f4*>(tb.io + b * tb.ld)[q] = o;
+              reinterpret_cast<f4*>(tb.io + b * tb.ld)[q] = o;
               if (o16) {      // the twin the first top-MLP GEMM reads its operand from (ffh_ctx_bf16_mirror_set)
                 typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
                 const bf2 lo = {(__bf16)g[0], (__bf16)g[1]}, hi = {(__bf16)g[2], (__bf16)g[3]};
@@ -1590,7 +1588,8 @@ static int emb_fwd_launch(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   // Infinity Cache holds -- and a row of a table too big to stay cached is touched once per launch: both as NONTEMPORAL accesses, so that they do
   // not evict the rows of the 18 small tables (62 MB) that do live in L2 / Infinity Cache.  One box, interleaved: 139.4 -> 133.7 (stores) / 133.8
   // (loads) / 130.9 us (both) = 0.79 -> 0.84 of 8 TB/s by the algorithmic-bytes formula; the step unchanged.  Same bits.
-  a.nt = FFH_LAB_INT("FFH_EMB_NT", 3);
+  // As compiled, neither hint survives: the compiler merged each hinted access with its plain twin and dropped the hint, so the
+  // kernel's loads and stores are plain.  The stores are now written plain; making the policy real is a change of its own, to be measured.
   a.nt_rows = (int64_t)FFH_LAB_INT("FFH_EMB_NT_MB", 64) * (1 << 20) / ((int64_t)D * (int64_t)sizeof(WT));      // tables above 64 MB (bytes, not rows)
   const int lpr = nvec < 64 ? nvec : 64;
   const int rpw = 64 / lpr;

@@ -29,7 +29,8 @@ using namespace ffh_gemm;
 // The plain forward instantiation of the 128 x 128 x 16 kernel is compiled for four workgroups per CU (128 registers, 8 bytes of
 // scratch) instead of the three its natural 164 registers allow: +1 % on the big layers' forward (1,737 -> 1,720 us), +0.35 %
 // on the Terabyte step, three interleaved pairs.  The masking / weight-gradient forms lose as much under the same limit and
-// keep theirs.  (Fewer than three workgroups per CU costs 6 % per workgroup: DESIGN 3.3.)
+// keep theirs.  (Fewer than three workgroups per CU costs 6 % per workgroup: DESIGN 3.3.)  The 128 x 128 forms that take relu' on
+// the dy operand (FUSE_DY) are bounded to three: left to itself the compiler gives the data-gradient one 172 registers, i.e. two.
 #ifndef FFH_FWD_OCC4
 #define FFH_FWD_OCC4 1
 #endif
@@ -42,30 +43,11 @@ namespace {
 //                 ways (intra-workgroup split-K), partial accumulators meet in LDS in a fixed order.
 //                 For the skinny DLRM layers (2048 x 256, 2048 x 64 ...) this gives 4x the waves of
 //                 a 64x64 tiling: a 32x32x2 MFMA chain over K = 512 alone is 16k cycles.
-template <int BM, int BN, int BK, bool AKC, bool BKC, bool SPLITW, bool FUSE_DY, bool CMAP>
-__device__ __forceinline__ void gemm_f32_tile(const GemmArgs& g, const unsigned lin, const unsigned nbx, const unsigned nby, const unsigned nbz);
-
-// One workgroup per tile (3-D grid), or -- g.tnx != 0 -- a persistent 1-D grid whose workgroups walk the tile space with
-// stride gridDim.x: the hardware dispatcher hands out tiles of a multi-round launch unevenly over the CUs (a launch of 2048
-// equal tiles at three resident workgroups per CU ends with some CUs a whole tile behind); a grid of exactly
-// (resident workgroups per CU) x (CUs) workgroups, each with the same number of tiles, does not.  gridDim.x is a multiple of 8
-// in that mode, so a workgroup's tiles stay in its XCD's contiguous range of the tile space.
+// One workgroup per tile of the 3-D grid.
 template <int BM, int BN, int BK, bool AKC, bool BKC, bool SPLITW = false, bool FUSE_DY = false, bool CMAP = false>
-__global__ __launch_bounds__(256, (FFH_FWD_OCC4 && BM == 128 && BN == 128 && BK == 16 && AKC && BKC && !SPLITW && !FUSE_DY && !CMAP) ? 4 : 1)
+__global__ __launch_bounds__(256, (FFH_FWD_OCC4 && BM == 128 && BN == 128 && BK == 16 && AKC && BKC && !SPLITW && !FUSE_DY && !CMAP) ? 4 : ((FUSE_DY && BM == 128) ? 3 : 1))
 void gemm_f32_kernel(const GemmArgs g) {
   ffh_kernel_prio();
-  const bool pers = g.tnx != 0;
-  const unsigned nbx = pers ? g.tnx : gridDim.x, nby = pers ? g.tny : gridDim.y, nbz = pers ? g.tnz : gridDim.z;
-  const unsigned total = nbx * nby * nbz;
-  const unsigned stride = pers ? gridDim.x : total;
-  for (unsigned lin = pers ? blockIdx.x : (blockIdx.z * nby + blockIdx.y) * nbx + blockIdx.x; lin < total; lin += stride) {
-    gemm_f32_tile<BM, BN, BK, AKC, BKC, SPLITW, FUSE_DY, CMAP>(g, lin, nbx, nby, nbz);
-    if (lin + stride < total) __syncthreads();   // the epilogue's LDS exchanges (bias sums, split-wave reduction) end before the next tile stages
-  }
-}
-
-template <int BM, int BN, int BK, bool AKC, bool BKC, bool SPLITW, bool FUSE_DY, bool CMAP>
-__device__ __forceinline__ void gemm_f32_tile(const GemmArgs& g, const unsigned lin, const unsigned nbx, const unsigned nby, const unsigned nbz) {
   constexpr int PA = AKC ? 1 : 4, PB = BKC ? 1 : 4;
   constexpr int LA = BM + PA, LB = BN + PB;
   constexpr int NA = BM * BK / 1024, NB = BN * BK / 1024;   // float4 staging slots per thread
@@ -83,6 +65,8 @@ __device__ __forceinline__ void gemm_f32_tile(const GemmArgs& g, const unsigned 
   // the small shared operand is fetched by all eight.
   int bx, by, bz;
   {
+    const unsigned nbx = gridDim.x, nby = gridDim.y, nbz = gridDim.z;
+    const unsigned lin = (blockIdx.z * nby + blockIdx.y) * nbx + blockIdx.x;
     const unsigned total = nbx * nby * nbz;
     const unsigned xcd = lin & 7u, loc = lin >> 3;
     const unsigned q = total >> 3, rem = total & 7u;
@@ -923,10 +907,9 @@ int launch_gemm(ffh_ctx* c, GemmArgs& g, int64_t batch, ffh_stream s, const char
   else if (tiles64 >= 2 * c->num_cus || g.K < 64) cfg = 1;
   else cfg = 2;
   static const int forced = FFH_LAB_INT("FFH_GEMM_CFG", -1);   // A/B switch (tools/gemm_tune.py)
-  if (forced >= 0 && forced <= 5 && (forced <= 2 || cfg == 0)) cfg = forced;
-  if (CMAP) cfg = (cfg == 0 || cfg == 3 || cfg == 4 || cfg == 5) ? 0 : 1;     // the column-map epilogue exists for the two plain tile shapes
-  const int BMv = cfg == 3 ? 256 : (cfg == 5 ? 128 : (cfg == 0 || cfg == 4 ? 128 : (cfg == 1 ? 64 : 32)));
-  const int BNv = cfg == 3 ? 128 : (cfg == 5 ? 256 : BMv);
+  if (forced >= 0 && forced <= 2) cfg = forced;
+  if (CMAP && cfg == 2) cfg = 1;     // the column-map epilogue exists for the two plain tile shapes
+  const int BMv = cfg == 0 ? 128 : (cfg == 1 ? 64 : 32), BNv = BMv;
   const int gx = (g.N + BNv - 1) / BNv, gy = (g.M + BMv - 1) / BMv;
   int gz = (int)batch;
   g.splitk = 1;
@@ -948,21 +931,8 @@ int launch_gemm(ffh_ctx* c, GemmArgs& g, int64_t batch, ffh_stream s, const char
     if (batch != 1) return ffh_fail(c, FFH_ERR_BAD_ARG, "gemm: split-K with a batch");
   }
   if (gy > 65535 || gz > 65535) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "gemm: grid too large");
-  dim3 grid(gx, gy, gz);
-  g.tnx = g.tny = g.tnz = 0;
-  {
-    // persistent form (see gemm_f32_kernel): launches of more tiles than the chip holds at once
-    static const int persist = FFH_LAB_INT("FFH_GEMM_PERSIST", 0);   // A/B switch: resident workgroups per CU, 0 = off
-    const int64_t total = (int64_t)gx * gy * gz;
-    if (persist > 0 && total > (int64_t)persist * c->num_cus && total < (1LL << 31)) {
-      g.tnx = (unsigned)gx; g.tny = (unsigned)gy; g.tnz = (unsigned)gz;
-      grid = dim3((unsigned)(persist * c->num_cus), 1, 1);
-    }
-  }
-  if (cfg == 3) hipLaunchKernelGGL((gemm_f32_kernel<256, 128, 16, AKC, BKC, false, FUSE_DY>), grid, dim3(256), 0, as_stream(s), g);
-  else if (cfg == 4) hipLaunchKernelGGL((gemm_f32_kernel<128, 128, 32, AKC, BKC, false, FUSE_DY>), grid, dim3(256), 0, as_stream(s), g);
-  else if (cfg == 5) hipLaunchKernelGGL((gemm_f32_kernel<128, 256, 16, AKC, BKC, false, FUSE_DY>), grid, dim3(256), 0, as_stream(s), g);
-  else if (cfg == 0) hipLaunchKernelGGL((gemm_f32_kernel<128, 128, 16, AKC, BKC, false, FUSE_DY, CMAP>), grid, dim3(256), 0, as_stream(s), g);
+  const dim3 grid(gx, gy, gz);
+  if (cfg == 0) hipLaunchKernelGGL((gemm_f32_kernel<128, 128, 16, AKC, BKC, false, FUSE_DY, CMAP>), grid, dim3(256), 0, as_stream(s), g);
   else if (cfg == 1) hipLaunchKernelGGL((gemm_f32_kernel<64, 64, 32, AKC, BKC, false, FUSE_DY, CMAP>), grid, dim3(256), 0, as_stream(s), g);
   else hipLaunchKernelGGL((gemm_f32_kernel<32, 32, 64, AKC, BKC, true, FUSE_DY>), grid, dim3(256), 0, as_stream(s), g);
   hipError_t e = hipGetLastError();
@@ -1035,68 +1005,6 @@ __global__ __launch_bounds__(512) void linear_thin_fwd_kernel(const float* __res
   for (int v = 0; v < 16; v++) {
     const int64_t i = b0 + 8 * (v >> 2) + 4 * h + (v & 3);
     if (i < batch) y[i * ldy + n0 + r] = act_apply(acc[v] + bs, act);
-  }
-}
-
-// The same layer as an HBM-write-bound stream (the 13 -> 512 layer at 32768 samples writes 67 MB and reads 1.7 MB): a wave owns
-// a ROW and 256 consecutive columns -- lane l the four columns 4l .. 4l+3, so a row segment leaves as ONE 1-KiB store
-// instruction; the <= 16 inputs of the row are wave-uniform (staged through LDS, below), the lane's 4 x in weights stay in registers for
-// all of the workgroup's rows.  52 FMAs per 16 bytes written: the VALU work is a tenth of the store time.  Each output is
-// the ascending-k fmaf chain from 0, then + bias, then the activation -- the oracle's order, bit for bit.
-constexpr int kThinRowsPerWg = 128;
-__global__ __launch_bounds__(256) void linear_thin_fwd_rows_kernel(const float* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy,
-                                                                   const float* __restrict__ w, const float* __restrict__ bias, int in, int out,
-                                                                   int64_t batch, int act) {
-  ffh_kernel_prio();
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int n0 = (blockIdx.y * 64 + lane) * 4;
-  const bool live = n0 < out;                    // out % 4 == 0 (host check)
-  // the workgroup's 256 x in slice of w is contiguous: one coalesced sweep into LDS, transposed ([k][column], rows of 260 floats),
-  // from where a lane takes its 4 columns of every k with one ds_read_b128 -- read straight from memory this was 52 loads per
-  // lane with 64 lanes 208 bytes apart, 64 cache lines per instruction (32.5 -> 30 us; 67 MB written: the stream alone would be ~13)
-  __shared__ __attribute__((aligned(16))) float wT[16][260];
-  {
-    const int c0 = blockIdx.y * 256;
-    const int ncol = out - c0 < 256 ? out - c0 : 256;
-    for (int e = threadIdx.x; e < 16 * 256; e += 256) wT[e >> 8][e & 255] = 0.0f;
-    __syncthreads();
-    const float* wb = w + (int64_t)c0 * in;
-    for (int e = threadIdx.x; e < ncol * in; e += 256) wT[e % in][e / in] = wb[e];
-    __syncthreads();
-  }
-  float wr[16][4];
-#pragma unroll
-  for (int k = 0; k < 16; k++) {
-    const float4 t = *reinterpret_cast<const float4*>(&wT[k][4 * lane]);
-    wr[k][0] = t.x; wr[k][1] = t.y; wr[k][2] = t.z; wr[k][3] = t.w;
-  }
-  float4 bs = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (live && bias) bs = *reinterpret_cast<const float4*>(bias + n0);
-  // the workgroup's 128 input rows go through LDS in one coalesced sweep (rows padded to 16 floats): a wave then takes a row's
-  // inputs with four broadcast ds_read_b128 instead of a chain of dependent scalar loads per row (39 -> 32.5 us at 32768 samples)
-  __shared__ __attribute__((aligned(16))) float xs_l[kThinRowsPerWg][16];
-  const int64_t r0 = (int64_t)blockIdx.x * kThinRowsPerWg;
-  const int nrows = (int)(batch - r0 < kThinRowsPerWg ? batch - r0 : kThinRowsPerWg);
-  for (int i = threadIdx.x; i < kThinRowsPerWg * 16; i += 256) {
-    const int rr = i >> 4, k = i & 15;
-    xs_l[rr][k] = (rr < nrows && k < in) ? x[(r0 + rr) * ldx + k] : 0.0f;
-  }
-  __syncthreads();
-  for (int rr = wave; rr < nrows; rr += 4) {
-    const float4* xr = reinterpret_cast<const float4*>(xs_l[rr]);
-    const float4 q0 = xr[0], q1 = xr[1], q2 = xr[2], q3 = xr[3];
-    const float xs[16] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w};
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-      if (k < in) {
-        a0 = __fmaf_rn(xs[k], wr[k][0], a0); a1 = __fmaf_rn(xs[k], wr[k][1], a1);
-        a2 = __fmaf_rn(xs[k], wr[k][2], a2); a3 = __fmaf_rn(xs[k], wr[k][3], a3);
-      }
-    }
-    if (bias) { a0 = a0 + bs.x; a1 = a1 + bs.y; a2 = a2 + bs.z; a3 = a3 + bs.w; }
-    if (live) *reinterpret_cast<float4*>(y + (r0 + rr) * ldy + n0) = make_float4(act_apply(a0, act), act_apply(a1, act), act_apply(a2, act), act_apply(a3, act));
   }
 }
 
@@ -1617,20 +1525,9 @@ int ffh_linear_fwd(ffh_ctx* c, const float* x, int64_t ldx, float* y, int64_t ld
     return FFH_OK;
   }
   static const int no_thin = FFH_LAB_INT("FFH_NO_THIN", 0);   // A/B switch (tools/ab.sh)
-  // (rows kernel from 8192 samples up: it keeps 128 rows per workgroup to amortise its weight registers, so a 2048-sample launch
-  //  would be 32 workgroups -- the MFMA form below is the faster one there: Kaggle step 208 vs 185 us)
-  // Round 4 re-measured the three forms of the 13 -> 512 layer alone (profiles/r04_ab_schedule.txt): at 32768 samples the rows kernel
-  // 31.8 us, the MFMA thin kernel 25.4, the ordinary GEMM path 23.4; at 8192: 23.9 / 9.5 / 14.0; at 4096: 7.7 / 7.5 / 8.2 -- the rows
-  // kernel is off (A/B: FFH_THIN_ROWS_MIN_BATCH), the thin kernel serves below 16384 samples (FFH_THIN_MAX_BATCH)
-  static const int64_t thin_rows_min = FFH_LAB_I64("FFH_THIN_ROWS_MIN_BATCH", (int64_t)1 << 40);   // A/B switch
+  // Round 4 measured the 13 -> 512 layer alone (profiles/r04_ab_schedule.txt): at 32768 samples the thin kernel 25.4 us, the ordinary
+  // GEMM path 23.4; at 8192: 9.5 / 14.0; at 4096: 7.5 / 8.2 -- the thin kernel serves below 16384 samples (FFH_THIN_MAX_BATCH)
   static const int64_t thin_max = FFH_LAB_I64("FFH_THIN_MAX_BATCH", 16384);
-  if (!no_thin && in <= 16 && out >= 64 && out % 4 == 0 && ldy % 4 == 0 && (((uintptr_t)y | (uintptr_t)(bias ? bias : w)) & 15) == 0 && batch >= thin_rows_min) {
-    hipLaunchKernelGGL(linear_thin_fwd_rows_kernel, dim3((unsigned)((batch + kThinRowsPerWg - 1) / kThinRowsPerWg), (unsigned)((out + 255) / 256)), dim3(256), 0,
-                       as_stream(s), x, ldx, y, ldy, w, bias, in, out, batch, act);
-    FFH_LAUNCH_CHECK(c, "linear_thin_fwd_rows_kernel");
-    ffh_route_add(c, "linear_fwd|thin_rows");
-    return FFH_OK;
-  }
   if (!no_thin && in <= 16 && out >= 64 && batch < thin_max) {
     hipLaunchKernelGGL(linear_thin_fwd_kernel, dim3((unsigned)((batch + 31) / 32), (unsigned)((out + 255) / 256)), dim3(512), 0, as_stream(s), x, ldx, y, ldy,
                        w, bias, in, out, batch, act);

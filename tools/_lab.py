@@ -1,7 +1,7 @@
 """Tools-only loader: the product kernel library reads no environment variable; the A/B switches (FFH_GEMM_CFG, FFH_SK_NO_SPLIT ...)
 exist in lab builds only --
     tools/build_variant.sh tools/lab/libffhip_lab.so -DFFH_LAB
-    FFH_TOOLS_LIB=tools/lab/libffhip_lab.so FFH_GEMM_CFG=3 python tools/gemm_big.py ...
+    FFH_TOOLS_LIB=tools/lab/libffhip_lab.so python tools/gemm_big.py -1,1
     FFH_SK_NO_SPLIT=1 python bench.py --shim-flags="--backend tools/lab/libffhip_lab.so" ...
 Without FFH_TOOLS_LIB the tools measure the product library (every switch at its default)."""
 import os

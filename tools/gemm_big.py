@@ -36,6 +36,6 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
             line += f" || hipBLASLt fwd {fl/t1/1e6:6.1f} dX {fl/t2/1e6:6.1f} dW {fl/t3/1e6:6.1f} TF"
         print(line, flush=True)
 else:
-    for cfg in (sys.argv[1].split(",") if len(sys.argv) > 1 else ("-1", "3", "4", "5")):
+    for cfg in (sys.argv[1].split(",") if len(sys.argv) > 1 else ("-1", "0")):
         print("FFH_GEMM_CFG =", cfg, flush=True)
         subprocess.run([sys.executable, __file__, "child", *sys.argv[2:]], env=dict(os.environ, FFH_GEMM_CFG=cfg))

@@ -5,8 +5,8 @@
 R=$(pwd); O=$R/gpurun_out/pmc_gemm; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp; cd $R
 for SH in 32768x1024x1024 32768x3456x1024; do
-  FFH_GEMM_CFG=-1 timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $O/a_$SH -- python3 tools/gemm_big.py child $SH > $O/a_$SH.log 2>&1
-  FFH_GEMM_CFG=-1 timeout 600 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_WAIT_INST_LDS SQ_INSTS_LDS GRBM_GUI_ACTIVE --output-format csv -d $O/b_$SH -- python3 tools/gemm_big.py child $SH > $O/b_$SH.log 2>&1
+  timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES --output-format csv -d $O/a_$SH -- python3 tools/gemm_big.py child $SH > $O/a_$SH.log 2>&1
+  timeout 600 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_WAIT_INST_LDS SQ_INSTS_LDS GRBM_GUI_ACTIVE --output-format csv -d $O/b_$SH -- python3 tools/gemm_big.py child $SH > $O/b_$SH.log 2>&1
   python3 tools/pmc_summary.py --all $(find $O/a_$SH $O/b_$SH -name "*counter_collection.csv") > $O/raw_$SH.json
 done
 python3 - <<'PY'
