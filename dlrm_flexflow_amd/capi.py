@@ -197,6 +197,8 @@ _SIGS_BF16 = {
     "ffh_embedding_bwd_sgd_apply_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), I, I, I, L, I, F, C.POINTER(Bf16Rounding), P]),
     "ffh_init_uniform_bf16": (I, [P, P, L, U64, F, F, P]),
     "ffh_bf16_counter_advance": (I, [P, P, P]),
+    "ffh_embedding_bwd_opt_fused_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), C.POINTER(Bf16Rounding), P]),
+    "ffh_embedding_bwd_opt_apply_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), C.POINTER(Bf16Rounding), P]),
 }
 
 

@@ -417,31 +417,47 @@ enum : uint32_t { kMetaNone = 0, kMetaFirst = 1, kMetaCont = 2 };
 struct OptP { float lr, wd, mom, b1, b2, eps, omb1, omb2; int nesterov; int64_t nt_rows;   // nt_rows: tables of more rows have their rows read and written nontemporal (plain SGD, 16-byte form)
               int sr_mode; uint64_t sr_seed; const uint64_t* sr_counter; };
 constexpr int kOptSgdBf16 = 3;
+// OPT 4 / 5 (kOptMomentumBf16, kOptAdamBf16): OPT 1 / 2 on a bf16 table -- the state update and w32 statement by statement those of OPT 1 / 2
+// on the widened row w = (float)w16, fp32 state, then the one rounding of kOptSgdBf16
+constexpr int kOptMomentumBf16 = 4;
+constexpr int kOptAdamBf16 = 5;
 
-constexpr bool opt_plain(int OPT) { return OPT == 0 || OPT == kOptSgdBf16; }   // no optimizer state
-constexpr bool opt_state(int OPT) { return OPT == 1 || OPT == 2; }
-struct Bf16Keys { int32_t table[FFH_MAX_TABLES]; int32_t col0[FFH_MAX_TABLES]; };   // kOptSgdBf16: in place of the (unused) s1 pointers
+constexpr bool opt_bf16(int OPT) { return OPT >= kOptSgdBf16; }                // 16-bit weight rows
+constexpr int opt_base(int OPT) { return opt_bf16(OPT) ? OPT - kOptSgdBf16 : OPT; }   // the fp32 row rule: 0 plain SGD, 1 momentum / wd SGD, 2 Adam
+constexpr bool opt_plain(int OPT) { return opt_base(OPT) == 0; }                // no optimizer state
+constexpr bool opt_state(int OPT) { return opt_base(OPT) != 0; }
+struct Bf16Keys { int32_t table[FFH_MAX_TABLES]; int32_t col0[FFH_MAX_TABLES]; };   // kOptSgdBf16 / kOptMomentumBf16: in place of the (unused) s1 pointers
+// kOptAdamBf16 needs the s1 pointers AND the keys: at most FFH_BF16_MAX_STATEFUL_TABLES tables, both in the space of s1[FFH_MAX_TABLES]
+struct Bf16AdamKeys { float* s1[FFH_BF16_MAX_STATEFUL_TABLES]; int32_t table[FFH_BF16_MAX_STATEFUL_TABLES]; int32_t col0[FFH_BF16_MAX_STATEFUL_TABLES]; };
+static_assert(sizeof(Bf16AdamKeys) <= sizeof(float*) * FFH_MAX_TABLES && sizeof(Bf16Keys) <= sizeof(float*) * FFH_MAX_TABLES, "bf16 keys in the s1 space");
 struct SrKey { uint64_t tkey; int64_t col0; };                                      // per table: ffh_bf16_sr_table_key, global column of column 0
-template <int OPT>
-__device__ __forceinline__ SrKey sr_key(const OptP& o, const Bf16Keys& k, int tix) {
+// a kernel's arguments (RedArgs, SmallArgs): the table's second state row pointer and its rounding key, wherever OPT keeps them
+template <int OPT, class A>
+__device__ __forceinline__ float* state1_of(const A& a, int tix) {
+  if (opt_base(OPT) != 2) return nullptr;
+  return OPT == kOptAdamBf16 ? a.b16a.s1[tix] : a.s1[tix];
+}
+template <int OPT, class A>
+__device__ __forceinline__ SrKey sr_key(const A& a, int tix) {
   SrKey r{0, 0};
-  if (OPT == kOptSgdBf16) {
-    r.col0 = k.col0[tix];
-    if (o.sr_mode == FFH_BF16_ROUND_STOCHASTIC) r.tkey = ffh_bf16_sr_table_key(o.sr_seed, *o.sr_counter, (uint64_t)k.table[tix]);
+  if (opt_bf16(OPT)) {
+    const int32_t table = OPT == kOptAdamBf16 ? a.b16a.table[tix] : a.b16.table[tix];
+    r.col0 = OPT == kOptAdamBf16 ? a.b16a.col0[tix] : a.b16.col0[tix];
+    if (a.op.sr_mode == FFH_BF16_ROUND_STOCHASTIC) r.tkey = ffh_bf16_sr_table_key(a.op.sr_seed, *a.op.sr_counter, (uint64_t)table);
   }
   return r;
 }
 // the row's first element: fp32 tables and bf16 tables alike come in as `float* weight` (ffh_emb_table; the bf16 entry points cast)
 template <int OPT>
 __device__ __forceinline__ float* weight_row(float* w, uint32_t row, int D) {
-  if (OPT == kOptSgdBf16) return reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(w) + (int64_t)row * D);
+  if (opt_bf16(OPT)) return reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(w) + (int64_t)row * D);
   return w + (int64_t)row * D;
 }
 
 // the row's stochastic-rounding key (ffh_bf16_sr_row_key), once per row rather than per vector of it; 0 where unused
 template <int OPT>
 __device__ __forceinline__ uint64_t sr_row_key(const OptP& o, const SrKey& sk, uint32_t row) {
-  return (OPT == kOptSgdBf16 && o.sr_mode == FFH_BF16_ROUND_STOCHASTIC) ? ffh_bf16_sr_row_key(sk.tkey, row) : 0;
+  return (opt_bf16(OPT) && o.sr_mode == FFH_BF16_ROUND_STOCHASTIC) ? ffh_bf16_sr_row_key(sk.tkey, row) : 0;
 }
 
 template <int VEC, int OPT>
@@ -500,21 +516,29 @@ __device__ __forceinline__ void apply_row(const OptP& o, float* wrow, float* s0r
     }
     return;
   }
+  constexpr int BASE = opt_base(OPT);
   float wv[VEC], av[VEC], bv[VEC];
-  const bool has0 = OPT == 2 || o.mom > 0.f;
+  const bool has0 = BASE == 2 || o.mom > 0.f;
+  uint16_t* const w16 = reinterpret_cast<uint16_t*>(wrow);
   if (VEC == 4) {
-    const float4 w = reinterpret_cast<const float4*>(wrow)[c];
-    wv[0] = w.x; wv[1] = w.y; wv[2] = w.z; wv[3] = w.w;
+    if (opt_bf16(OPT)) {
+      const uint2 v = reinterpret_cast<const uint2*>(w16)[c];
+      wv[0] = ffh_bf16_to_f32((uint16_t)v.x); wv[1] = ffh_bf16_to_f32((uint16_t)(v.x >> 16));
+      wv[2] = ffh_bf16_to_f32((uint16_t)v.y); wv[3] = ffh_bf16_to_f32((uint16_t)(v.y >> 16));
+    } else {
+      const float4 w = reinterpret_cast<const float4*>(wrow)[c];
+      wv[0] = w.x; wv[1] = w.y; wv[2] = w.z; wv[3] = w.w;
+    }
     if (has0) { const float4 a = reinterpret_cast<const float4*>(s0row)[c]; av[0] = a.x; av[1] = a.y; av[2] = a.z; av[3] = a.w; }
-    if (OPT == 2) { const float4 b = reinterpret_cast<const float4*>(s1row)[c]; bv[0] = b.x; bv[1] = b.y; bv[2] = b.z; bv[3] = b.w; }
+    if (BASE == 2) { const float4 b = reinterpret_cast<const float4*>(s1row)[c]; bv[0] = b.x; bv[1] = b.y; bv[2] = b.z; bv[3] = b.w; }
   } else {
-    wv[0] = wrow[c];
+    wv[0] = opt_bf16(OPT) ? ffh_bf16_to_f32(w16[c]) : wrow[c];
     if (has0) av[0] = s0row[c];
-    if (OPT == 2) bv[0] = s1row[c];
+    if (BASE == 2) bv[0] = s1row[c];
   }
 #pragma unroll
   for (int k = 0; k < VEC; k++) {
-    if (OPT == 1) {            // sgd_update [ref: src/runtime/optimizer_kernel.cu:23-41], as sgd_kernel spells it
+    if (BASE == 1) {           // sgd_update [ref: src/runtime/optimizer_kernel.cu:23-41], as sgd_kernel spells it
       float gt = __fmaf_rn(o.wd, wv[k], acc[k]);
       if (o.mom > 0.f) {
         av[k] = __fmaf_rn(av[k], o.mom, gt);
@@ -535,14 +559,34 @@ __device__ __forceinline__ void apply_row(const OptP& o, float* wrow, float* s0r
       wv[k] = wv[k] - step;
     }
   }
-  if (VEC == 4) {
+  if (opt_bf16(OPT)) {
+    // one rounding of w32 with the key of kOptSgdBf16 (global table, row, column; the update counter)
+    uint16_t h[VEC];
+    const int64_t g0 = sk.col0 + (int64_t)c * VEC;
+    const bool sr = o.sr_mode == FFH_BF16_ROUND_STOCHASTIC;
+    const uint64_t grp = (sr && VEC == 4 && (g0 & 3) == 0) ? ffh_bf16_sr_group(rkey, (uint64_t)g0) : 0;
+#pragma unroll
+    for (int k = 0; k < VEC; k++) {
+      uint32_t r = 0;
+      if (sr) {
+        const uint64_t gc = (uint64_t)(g0 + k);
+        r = ffh_bf16_sr_field((VEC == 4 && (g0 & 3) == 0) ? grp : ffh_bf16_sr_group(rkey, gc), gc);
+      }
+      h[k] = ffh_bf16_round(wv[k], o.sr_mode, r);
+    }
+    if (VEC == 4) reinterpret_cast<uint2*>(w16)[c] = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
+    else w16[c] = h[0];
+  } else if (VEC == 4) {
     reinterpret_cast<float4*>(wrow)[c] = make_float4(wv[0], wv[1], wv[2], wv[3]);
-    if (has0) reinterpret_cast<float4*>(s0row)[c] = make_float4(av[0], av[1], av[2], av[3]);
-    if (OPT == 2) reinterpret_cast<float4*>(s1row)[c] = make_float4(bv[0], bv[1], bv[2], bv[3]);
   } else {
     wrow[c] = wv[0];
+  }
+  if (VEC == 4) {
+    if (has0) reinterpret_cast<float4*>(s0row)[c] = make_float4(av[0], av[1], av[2], av[3]);
+    if (BASE == 2) reinterpret_cast<float4*>(s1row)[c] = make_float4(bv[0], bv[1], bv[2], bv[3]);
+  } else {
     if (has0) s0row[c] = av[0];
-    if (OPT == 2) s1row[c] = bv[0];
+    if (BASE == 2) s1row[c] = bv[0];
   }
 }
 
@@ -566,7 +610,8 @@ struct RedArgs {
   float*    s0[FFH_MAX_TABLES];   // OPT 1: momentum buffer V; OPT 2: first moment M -- [num_entries][D] like the table, or null
   union {
     float*  s1[FFH_MAX_TABLES];   // OPT 2: second moment V
-    Bf16Keys b16;                 // kOptSgdBf16: the tables' rounding keys
+    Bf16Keys b16;                 // kOptSgdBf16, kOptMomentumBf16: the tables' rounding keys
+    Bf16AdamKeys b16a;            // kOptAdamBf16: s1 and the keys of at most FFH_BF16_MAX_STATEFUL_TABLES tables
   };
   // bucket form (emb_sgd_reduce_kernel<.., MSD = true>): kp[parity] is ordered by the top digit only
   uint8_t   shift_t[FFH_MAX_TABLES];   // the digit's position (0: the table is completely sorted)
@@ -758,7 +803,7 @@ __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const 
           for (int v = 0; v < VEC; v++) acc[v] = acc[v] + v0[v];
         }
         if (single) {
-          apply_row<VEC, OPT>(op, wrow, opt_state(OPT) ? st0 + (int64_t)key * D : nullptr, OPT == 2 ? st1 + (int64_t)key * D : nullptr, c, acc, tb.num_entries > op.nt_rows, sk, rkey);
+          apply_row<VEC, OPT>(op, wrow, opt_state(OPT) ? st0 + (int64_t)key * D : nullptr, opt_base(OPT) == 2 ? st1 + (int64_t)key * D : nullptr, c, acc, tb.num_entries > op.nt_rows, sk, rkey);
         } else {
           xwg_store_row<VEC, AGENT>(prow, c, acc);
         }
@@ -861,7 +906,7 @@ __device__ __forceinline__ void fold_table_body(const ffh_emb_table& tb, const f
         for (int v = 0; v < VEC; v++) acc[v] = acc[v] + v0[v];
       }
       if (complete) {
-        apply_row<VEC, OPT>(op, wrow, opt_state(OPT) ? st0 + (int64_t)m.y * D : nullptr, OPT == 2 ? st1 + (int64_t)m.y * D : nullptr, c, acc, tb.num_entries > op.nt_rows, sk, rkey);
+        apply_row<VEC, OPT>(op, wrow, opt_state(OPT) ? st0 + (int64_t)m.y * D : nullptr, opt_base(OPT) == 2 ? st1 + (int64_t)m.y * D : nullptr, c, acc, tb.num_entries > op.nt_rows, sk, rkey);
       } else {
         xwg_store_row<VEC, AGENT>(orow, c, acc);
       }
@@ -1243,8 +1288,8 @@ __global__ __launch_bounds__(kRedThreads, MSD ? (opt_plain(OPT) ? 6 : 4) : (OPT 
   float* p0 = a.partial + (int64_t)tix * 2 * a.nchunks * a.D;
   uint2* m0 = a.meta + (int64_t)tix * 2 * a.nchunks;
   float* const st0 = opt_state(OPT) ? a.s0[tix] : nullptr;
-  float* const st1 = OPT == 2 ? a.s1[tix] : nullptr;
-  const SrKey sk = sr_key<OPT>(a.op, a.b16, tix);
+  float* const st1 = state1_of<OPT>(a, tix);
+  const SrKey sk = sr_key<OPT>(a, tix);
   bool preloaded = false;
 #ifdef FFH_MSD_TIMING
   unsigned long long* dbg = a.dbg + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8;
@@ -1355,7 +1400,7 @@ struct SmallArgs {
   int tile;            // sorted entries per reduce team (multiple of FFH_EMB_CHUNK, <= kRedTile)
   OptP op;
   float* s0[FFH_MAX_TABLES];
-  union { float* s1[FFH_MAX_TABLES]; Bf16Keys b16; };     // kOptSgdBf16: the tables' rounding keys in place of s1
+  union { float* s1[FFH_MAX_TABLES]; Bf16Keys b16; Bf16AdamKeys b16a; };     // as in RedArgs
 };
 
 constexpr int kSmallWaves = 8;                        // threads per table = 64 x this: sort ranks kSmallMax / threads entries per thread, reduce = teams of 256
@@ -1385,8 +1430,8 @@ __global__ __launch_bounds__(kSmallThreads) void emb_sgd_small_kernel(const Smal
   const int tix = blockIdx.x;
   const ffh_emb_table tb = a.t[tix];
   float* const st0 = opt_state(OPT) ? a.s0[tix] : nullptr;
-  float* const st1 = OPT == 2 ? a.s1[tix] : nullptr;
-  const SrKey sk = sr_key<OPT>(a.op, a.b16, tix);
+  float* const st1 = state1_of<OPT>(a, tix);
+  const SrKey sk = sr_key<OPT>(a, tix);
   const int64_t N = a.N;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int radix = 1 << a.rb;
@@ -1651,6 +1696,15 @@ size_t ffh_embedding_bwd_workspace_bytes(int nt, int L, int D, int64_t batch) {
 // `opt` / `states`: the row rule (ffh_sparse_opt) and the per-table optimizer state it updates; null opt = plain SGD with `lr`
 // `b16`: bf16 tables (ff_hip_bf16.h; `tables[i].weight` holds bf16 bits): plain SGD with `lr`, the kOptSgdBf16 row rule
 struct Bf16Cfg { const ffh_bf16_rounding* r; Bf16Keys keys; };
+// the bf16 keys into a kernel's arguments: beside the s0 / s1 pointers already set (kOptAdamBf16: s1 moves into Bf16AdamKeys)
+// (`keys` and `adam` are the same union of the arguments)
+static void set_bf16_keys(Bf16Keys& keys, Bf16AdamKeys& adam, const Bf16Cfg& b16, const ffh_emb_state* states, int nt, int kind) {
+  if (kind != FFH_SPARSE_OPT_ADAM) { keys = b16.keys; return; }
+  Bf16AdamKeys k;
+  memset(&k, 0, sizeof k);
+  for (int i = 0; i < nt; i++) { k.s1[i] = states[i].s1; k.table[i] = b16.keys.table[i]; k.col0[i] = b16.keys.col0[i]; }
+  adam = k;
+}
 static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L, int D, int64_t batch,
                           int aggr, float lr, ffh_stream s, const bool do_sort, const bool do_apply,
                           const ffh_sparse_opt* opt = nullptr, const ffh_emb_state* states = nullptr, const Bf16Cfg* b16 = nullptr) {
@@ -1674,6 +1728,8 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
     kind = opt->kind;
     if (kind != FFH_SPARSE_OPT_SGD && kind != FFH_SPARSE_OPT_SGD_MOMENTUM && kind != FFH_SPARSE_OPT_ADAM)
       return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt: unknown ffh_sparse_opt.kind");
+    if (b16 && kind != FFH_SPARSE_OPT_SGD && nt > FFH_BF16_MAX_STATEFUL_TABLES)
+      return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt_multi_bf16: momentum / Adam take at most FFH_BF16_MAX_STATEFUL_TABLES (32) tables per call");
     op.lr = opt->lr; op.wd = opt->weight_decay; op.mom = opt->momentum; op.nesterov = opt->nesterov ? 1 : 0;
     op.b1 = opt->beta1; op.b2 = opt->beta2; op.eps = opt->epsilon; op.omb1 = 1.0f - opt->beta1; op.omb2 = 1.0f - opt->beta2;
     if (kind == FFH_SPARSE_OPT_SGD && (op.wd != 0.0f || op.mom != 0.0f)) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt: FFH_SPARSE_OPT_SGD takes no weight decay / momentum (use FFH_SPARSE_OPT_SGD_MOMENTUM)");
@@ -1738,14 +1794,15 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
     sm.N = N; sm.nch0 = lay.nchunks; sm.nch1 = lay.nchunks1; sm.rb = rb_s; sm.L = L; sm.D = D;
     sm.avg = aggr == FFH_AGGR_MODE_AVG ? 1 : 0; sm.op = op;
     for (int i = 0; i < nt && kind != FFH_SPARSE_OPT_SGD; i++) { sm.s0[i] = states[i].s0; sm.s1[i] = states[i].s1; }
-    if (b16) sm.b16 = b16->keys;
+    if (b16) set_bf16_keys(sm.b16, sm.b16a, *b16, states, nt, kind);
     int tile = (int)((N + kSmallRedParts - 1) / kSmallRedParts);          // one tile per 256-thread team
     tile = (tile + FFH_EMB_CHUNK - 1) / FFH_EMB_CHUNK * FFH_EMB_CHUNK;
     sm.tile = tile < FFH_EMB_CHUNK ? FFH_EMB_CHUNK : tile;
 #define FFH_SMALL(OPTV)                                                                                               \
     { if (v4) hipLaunchKernelGGL((emb_sgd_small_kernel<4, OPTV>), dim3(nt), dim3(kSmallThreads), 0, as_stream(s), sm);  \
       else hipLaunchKernelGGL((emb_sgd_small_kernel<1, OPTV>), dim3(nt), dim3(kSmallThreads), 0, as_stream(s), sm); }
-    if (b16) FFH_SMALL(kOptSgdBf16) else if (kind == FFH_SPARSE_OPT_SGD) FFH_SMALL(0) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_SMALL(1) else FFH_SMALL(2)
+    if (b16) { if (kind == FFH_SPARSE_OPT_SGD) FFH_SMALL(kOptSgdBf16) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_SMALL(kOptMomentumBf16) else FFH_SMALL(kOptAdamBf16) }
+    else if (kind == FFH_SPARSE_OPT_SGD) FFH_SMALL(0) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_SMALL(1) else FFH_SMALL(2)
 #undef FFH_SMALL
     FFH_LAUNCH_CHECK(c, "emb_sgd_small_kernel");
     return FFH_OK;
@@ -1820,7 +1877,7 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   ra.avg = aggr == FFH_AGGR_MODE_AVG ? 1 : 0;
   ra.op = op;
   for (int i = 0; i < nt && kind != FFH_SPARSE_OPT_SGD; i++) { ra.s0[i] = states[i].s0; ra.s1[i] = states[i].s1; }
-  if (b16) ra.b16 = b16->keys;
+  if (b16) set_bf16_keys(ra.b16, ra.b16a, *b16, states, nt, kind);
   ra.partial1 = (float*)(ws + lay.partial1);
   ra.meta1 = (uint2*)(ws + lay.meta1); ra.nchunks1 = lay.nchunks1;
   ra.arrive = (uint32_t*)(ws + lay.arrive);
@@ -1834,7 +1891,9 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   if (!dbg_buf) hipMalloc(&dbg_buf, 8 * 8 * 65536);
   ra.dbg = dbg_buf;
 #endif
-  if (b16) { if (msd) FFH_RED(kOptSgdBf16, true) else FFH_RED(kOptSgdBf16, false) }
+  if (b16 && kind == FFH_SPARSE_OPT_SGD) { if (msd) FFH_RED(kOptSgdBf16, true) else FFH_RED(kOptSgdBf16, false) }
+  else if (b16 && kind == FFH_SPARSE_OPT_SGD_MOMENTUM) { if (msd) FFH_RED(kOptMomentumBf16, true) else FFH_RED(kOptMomentumBf16, false) }
+  else if (b16) { if (msd) FFH_RED(kOptAdamBf16, true) else FFH_RED(kOptAdamBf16, false) }
   else if (msd) { if (kind == FFH_SPARSE_OPT_SGD) FFH_RED(0, true) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_RED(1, true) else FFH_RED(2, true) }
   else { if (kind == FFH_SPARSE_OPT_SGD) FFH_RED(0, false) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_RED(1, false) else FFH_RED(2, false) }
 #undef FFH_RED
@@ -1916,14 +1975,15 @@ static int bf16_tables(ffh_ctx* c, const ffh_emb_table_bf16* in, int nt, ffh_emb
 }
 
 static int emb_bwd_bf16(ffh_ctx* c, const ffh_emb_table_bf16* tables, int nt, int L, int D, int64_t batch, int aggr, float lr,
-                        const ffh_bf16_rounding* r, ffh_stream s, bool do_sort, bool do_apply) {
+                        const ffh_bf16_rounding* r, ffh_stream s, bool do_sort, bool do_apply,
+                        const ffh_sparse_opt* opt = nullptr, const ffh_emb_state* states = nullptr) {
   ffh_emb_table t[FFH_MAX_TABLES];
   Bf16Cfg cfg;
   memset(&cfg, 0, sizeof cfg);
   cfg.r = r;
   const int rc = bf16_tables(c, tables, nt, t, &cfg.keys);
   if (rc) return rc;
-  return emb_bwd_phases(c, t, nt, L, D, batch, aggr, lr, s, do_sort, do_apply, nullptr, nullptr, &cfg);
+  return emb_bwd_phases(c, t, nt, L, D, batch, aggr, lr, s, do_sort, do_apply, opt, states, &cfg);
 }
 
 extern "C" {
@@ -1949,6 +2009,18 @@ int ffh_embedding_bwd_sort_multi_bf16(ffh_ctx* c, const ffh_emb_table_bf16* tabl
 int ffh_embedding_bwd_sgd_apply_multi_bf16(ffh_ctx* c, const ffh_emb_table_bf16* tables, int nt, int L, int D, int64_t batch,
                                            int aggr, float lr, const ffh_bf16_rounding* r, ffh_stream s) {
   return emb_bwd_bf16(c, tables, nt, L, D, batch, aggr, lr, r, s, false, true);
+}
+
+int ffh_embedding_bwd_opt_fused_multi_bf16(ffh_ctx* c, const ffh_emb_table_bf16* tables, const ffh_emb_state* states, int nt, int L, int D,
+                                           int64_t batch, int aggr, const ffh_sparse_opt* opt, const ffh_bf16_rounding* r, ffh_stream s) {
+  if (!opt) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt_fused_multi_bf16: null ffh_sparse_opt");
+  return emb_bwd_bf16(c, tables, nt, L, D, batch, aggr, opt->lr, r, s, true, true, opt, states);
+}
+
+int ffh_embedding_bwd_opt_apply_multi_bf16(ffh_ctx* c, const ffh_emb_table_bf16* tables, const ffh_emb_state* states, int nt, int L, int D,
+                                           int64_t batch, int aggr, const ffh_sparse_opt* opt, const ffh_bf16_rounding* r, ffh_stream s) {
+  if (!opt) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt_apply_multi_bf16: null ffh_sparse_opt");
+  return emb_bwd_bf16(c, tables, nt, L, D, batch, aggr, opt->lr, r, s, false, true, opt, states);
 }
 
 int ffh_init_uniform_bf16(ffh_ctx* c, uint16_t* p, int64_t n, uint64_t seed, float lo, float hi, ffh_stream s) {

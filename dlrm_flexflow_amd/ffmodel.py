@@ -20,6 +20,8 @@ HOST_LIB_PATH = os.path.join(_HERE, "host", "libffmodel.so")
 
 # enums [ref: include/ffconst.h:4-57]
 DT_FLOAT, DT_INT64 = 40, 43
+DT_BF16 = 140                  # this build: bf16 embedding tables (--embedding-dtype bf16); values are uint16 bit patterns
+ROUND_STOCHASTIC, ROUND_NEAREST = 0, 1   # --embedding-rounding (include/ffh_bf16.h)
 LOSS_MSE_AVG, LOSS_MSE_SUM = 52, 53
 METRICS_ACCURACY, METRICS_MSE = 1001, 1008
 COMP_MODE_TRAINING = 70
@@ -76,6 +78,7 @@ def lib() -> C.CDLL:
         "flexflow_config_set_backend": (None, [H, C.c_char_p]), "flexflow_config_set_seed": (None, [H, C.c_uint64]),
         "flexflow_config_set_device": (None, [H, I]), "flexflow_config_set_enable_graph": (None, [H, B]),
         "flexflow_config_set_overlap_embedding": (None, [H, B]), "flexflow_config_set_dense_embedding_update": (None, [H, B]),
+        "flexflow_config_set_embedding_dtype": (None, [H, I]), "flexflow_config_set_embedding_rounding": (None, [H, I]),
         "flexflow_model_create": (H, [H]), "flexflow_model_destroy": (None, [H]),
         "flexflow_tensor_create": (H, [H, I, IP, I, B]),
         "flexflow_model_add_dense": (H, [H, H, I, I, B, H, H, C.c_char_p]),
@@ -110,6 +113,8 @@ def lib() -> C.CDLL:
         "flexflow_tensor_set_float": (None, [H, H, IP, I, P]), "flexflow_tensor_set_int64": (None, [H, H, IP, I, P]),
         "flexflow_tensor_get_float": (None, [H, H, P]), "flexflow_tensor_get_int64": (None, [H, H, P]),
         "flexflow_tensor_get_grad_float": (None, [H, H, P]),
+        "flexflow_tensor_get_data_type": (I, [H]),
+        "flexflow_tensor_set_bf16": (None, [H, H, IP, I, P]), "flexflow_tensor_get_bf16": (None, [H, H, P]),
         "flexflow_dlrm_create": (H, [I, C.POINTER(C.c_char_p), C.POINTER(FFComm)]), "flexflow_dlrm_destroy": (None, [H]),
         "flexflow_dlrm_get_model": (H, [H]), "flexflow_dlrm_get_num_samples": (I, [H]), "flexflow_dlrm_get_num_tables": (I, [H]),
         "flexflow_dlrm_get_sparse_input": (H, [H, I]), "flexflow_dlrm_get_dense_input": (H, [H]),
@@ -159,6 +164,11 @@ class Tensor:
     def ld(self) -> int:
         return lib().flexflow_tensor_get_ld(self.h)
 
+    @property
+    def data_type(self) -> int:
+        """DT_FLOAT, DT_INT64, ... or DT_BF16 (a bf16 embedding table)"""
+        return lib().flexflow_tensor_get_data_type(self.h)
+
     def _local_shape(self):
         d = self.dims
         if len(d) == 1:
@@ -167,17 +177,27 @@ class Tensor:
             return (self.local_rows, d[1])
         return (self.local_rows // int(np.prod(d[1:-1])),) + d[1:]
 
-    def set(self, arr: np.ndarray):
+    def set(self, arr: np.ndarray, raw_bf16: bool = False):
+        """fp32 into a bf16 table is rounded to nearest even; raw_bf16=True: `arr` holds the uint16 bit patterns, copied as they are."""
         a = np.ascontiguousarray(arr)
         dims = (C.c_int * a.ndim)(*a.shape)
-        if a.dtype == np.float32:
+        if raw_bf16:
+            if a.dtype != np.uint16:
+                raise TypeError(f"raw_bf16 takes uint16 bit patterns, not {a.dtype}")
+            lib().flexflow_tensor_set_bf16(self.h, self.model.h, dims, a.ndim, a.ctypes.data)
+        elif a.dtype == np.float32:
             lib().flexflow_tensor_set_float(self.h, self.model.h, dims, a.ndim, a.ctypes.data)
         elif a.dtype == np.int64:
             lib().flexflow_tensor_set_int64(self.h, self.model.h, dims, a.ndim, a.ctypes.data)
         else:
             raise TypeError(a.dtype)
 
-    def get(self, dtype=np.float32) -> np.ndarray:
+    def get(self, dtype=np.float32, raw_bf16: bool = False) -> np.ndarray:
+        """A bf16 table comes out widened exactly to fp32; raw_bf16=True: its uint16 bit patterns."""
+        if raw_bf16:
+            out = np.empty(self._local_shape(), np.uint16)
+            lib().flexflow_tensor_get_bf16(self.h, self.model.h, out.ctypes.data)
+            return out
         out = np.empty(self._local_shape(), dtype)
         if dtype == np.float32:
             lib().flexflow_tensor_get_float(self.h, self.model.h, out.ctypes.data)
@@ -210,12 +230,24 @@ class FFConfig:
     batch_size = property(lambda s: lib().flexflow_config_get_batch_size(s.h),
                           lambda s, v: lib().flexflow_config_set_batch_size(s.h, v))
 
-    def set(self, seed=None, device=None, enable_graph=None, overlap_embedding=None, dense_embedding_update=None):
+    def set(self, seed=None, device=None, enable_graph=None, overlap_embedding=None, dense_embedding_update=None,
+            embedding_dtype=None, embedding_rounding=None):
+        """embedding_dtype: "fp32" | "bf16"; embedding_rounding: "stochastic" | "nearest" (the --embedding-* flags)"""
         if seed is not None: lib().flexflow_config_set_seed(self.h, seed)
         if device is not None: lib().flexflow_config_set_device(self.h, device)
         if enable_graph is not None: lib().flexflow_config_set_enable_graph(self.h, enable_graph)
         if overlap_embedding is not None: lib().flexflow_config_set_overlap_embedding(self.h, overlap_embedding)
         if dense_embedding_update is not None: lib().flexflow_config_set_dense_embedding_update(self.h, dense_embedding_update)
+        if embedding_dtype is not None:
+            dt = {"fp32": DT_FLOAT, "bf16": DT_BF16}.get(embedding_dtype)
+            if dt is None:
+                raise ValueError(f"embedding_dtype {embedding_dtype!r}: 'fp32' or 'bf16'")
+            lib().flexflow_config_set_embedding_dtype(self.h, dt)
+        if embedding_rounding is not None:
+            mode = {"stochastic": ROUND_STOCHASTIC, "nearest": ROUND_NEAREST}.get(embedding_rounding)
+            if mode is None:
+                raise ValueError(f"embedding_rounding {embedding_rounding!r}: 'stochastic' or 'nearest'")
+            lib().flexflow_config_set_embedding_rounding(self.h, mode)
         return self
 
 
@@ -278,6 +310,9 @@ class FFModel:
 
     @staticmethod
     def zero_initializer(): return lib().flexflow_zero_initializer_create()
+
+    @staticmethod
+    def glorot_uniform_initializer(seed): return lib().flexflow_glorot_uniform_initializer_create(seed)
 
     def set_sgd_optimizer(self, lr=0.01, momentum=0.0, nesterov=False, weight_decay=0.0):
         self._opt = lib().flexflow_sgd_optimizer_create(self.h, lr, momentum, nesterov, weight_decay)

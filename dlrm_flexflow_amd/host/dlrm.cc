@@ -15,6 +15,7 @@
 
 #include "backend.h"
 #include "../../include/ffh_rng.h"
+#include "../../include/ffh_bf16.h"
 
 namespace {
 double now_us() {
@@ -344,6 +345,20 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
   metrics.push_back(METRICS_ACCURACY);
   metrics.push_back(METRICS_MEAN_SQUARED_ERROR);
   ff->compile(optimizer, LOSS_MEAN_SQUARED_ERROR_AVG_REDUCE, metrics);
+  if (chatty && ffconfig.embedding_dtype == DT_BF16) {
+    // what --embedding-dtype bf16 did: data-parallel (replicated) tables live in the dense slab and stay fp32
+    size_t bytes = 0;
+    int n16 = 0;
+    std::string fp32_tables;
+    for (const Embedding* e : ff->embeddings) {
+      if (e->weights[0].impl && e->weights[0].impl->ptr) bytes += e->weights[0].impl->bytes;
+      if (e->bf16_weights()) n16++;
+      else fp32_tables += std::string(fp32_tables.empty() ? "" : ",") + e->name;
+    }
+    printf("[DLRM] embedding tables: bf16 (%s rounding) %d of %zu, %.3f GB on rank %d; fp32 (data-parallel): %s\n",
+           ffconfig.embedding_rounding == FFH_BF16_ROUND_NEAREST ? "nearest" : "stochastic", n16, ff->embeddings.size(), bytes / 1e9,
+           ff->rank, fp32_tables.empty() ? "none" : fp32_tables.c_str());
+  }
   loader = new DataLoader(*ff, dlrm, sparse_inputs, dense_input, ff->label_tensor);
   ff->init_layers();
 }

@@ -25,12 +25,14 @@
 #include <vector>
 
 #include "../../include/ff_hip.h"
+#include "../../include/ff_hip_bf16.h"
 #include "ffcomm.h"
 
 // ---- enums: identical values to [ref: include/ffconst.h:4-57] -------------------------------
 enum ActiMode { AC_MODE_NONE = 10, AC_MODE_RELU = 11, AC_MODE_SIGMOID = 12, AC_MODE_TANH = 13, AC_MODE_GELU = 14 };
 enum AggrMode { AGGR_MODE_NONE = 20, AGGR_MODE_SUM = 21, AGGR_MODE_AVG = 22 };
-enum DataType { DT_FLOAT = 40, DT_DOUBLE = 41, DT_INT32 = 42, DT_INT64 = 43, DT_BOOLEAN = 44, DT_NONE = 49 };
+enum DataType { DT_FLOAT = 40, DT_DOUBLE = 41, DT_INT32 = 42, DT_INT64 = 43, DT_BOOLEAN = 44, DT_NONE = 49,
+                DT_BF16 = 140 };   // DT_BF16: this build's own (bf16 embedding tables, --embedding-dtype bf16), outside the reference's values
 enum LossType {
   LOSS_CATEGORICAL_CROSSENTROPY = 50,
   LOSS_SPARSE_CATEGORICAL_CROSSENTROPY = 51,
@@ -144,6 +146,8 @@ class FFConfig {
   bool async_launch;           // auxiliary streams are fed by their own host threads (HIP backend only)
   bool parallel_dw;            // weight-gradient GEMMs on their own stream beside the data-gradient chain
   bool force_exchange;         // run the all-to-all / all-reduce path even with one rank (tests the collectives on 1 GPU)
+  DataType embedding_dtype;    // --embedding-dtype fp32|bf16: storage of the tables the fused update owns (table-wise; compile() refuses sharded ones); DT_FLOAT or DT_BF16
+  int embedding_rounding;      // --embedding-rounding stochastic|nearest: FFH_BF16_ROUND_STOCHASTIC / _NEAREST (include/ffh_bf16.h) of the bf16 table update
   ffcomm comm;                 // rank / world_size / collectives supplied by the launcher (ffcomm.h)
 };
 
@@ -374,6 +378,7 @@ class Embedding : public Op {
   void set_replicated(const FFModel& model, bool on);
   float* opt_state[2] = {nullptr, nullptr};   // --sparse-embedding-optimizer: per-row state of this rank's slice (SGD momentum: V; Adam: M, V)
   bool held_here(int rank) const { return owner_rank == rank || column_sharded || row_sharded || replicated; }
+  bool bf16_weights() const { return weights[0].data_type == DT_BF16; }   // --embedding-dtype bf16: 16-bit storage (include/ff_hip_bf16.h)
 };
 
 class Concat : public Op {
@@ -590,6 +595,14 @@ class FFModel {
   static constexpr int kProbeEvents = 30;     // pairs: gather, update, a2a fwd, a2a bwd, all-reduce (rest / single bucket), join wait, the compute stream's wait for the buckets, buckets 0..7
   mutable ffh_event probe_ev[kProbeEvents] = {};
   void probe_record(int which, ffh_stream s, ffh_ctx* cx) const;
+  // bf16 tables (--embedding-dtype bf16): the update counter the stochastic rounding is keyed by (one uint64 in device memory, zeroed at
+  // compile(), advanced once per step behind the last table update), and the rounding of this model
+  uint64_t* bf16_counter = nullptr;
+  ffh_bf16_rounding bf16_rounding() const;
+  uint64_t read_bf16_counter() const;          // device -> host (synchronises)
+  void advance_bf16_counter(ffh_stream s, ffh_ctx* cx) const;
+  size_t bf16_tables_per_launch() const;      // FFH_MAX_TABLES, or FFH_BF16_MAX_STATEFUL_TABLES for momentum / Adam on bf16 tables
+  mutable int64_t n_early_sorts = 0;          // sort-only launches issued behind the gather (tests: flexflow_model_get_counter "early_sorts")
   bool fused_embedding_update() const;        // the tables are updated on the sorted segments (plain SGD, or any optimizer with --sparse-embedding-optimizer)
   bool sparse_rule(ffh_sparse_opt& rule) const;   // the row rule in force; false: plain SGD
   mutable bool opt_next_done = false;          // Optimizer::next() has run for the step in flight (update() does it; backward() clears it)

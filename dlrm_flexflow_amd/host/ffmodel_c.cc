@@ -36,6 +36,14 @@ void flexflow_config_set_device(flexflow_config_t h, int d) { C(h)->device = d; 
 void flexflow_config_set_enable_graph(flexflow_config_t h, bool v) { C(h)->enable_graph = v; }
 void flexflow_config_set_overlap_embedding(flexflow_config_t h, bool v) { C(h)->overlap_embedding = v; }
 void flexflow_config_set_dense_embedding_update(flexflow_config_t h, bool v) { C(h)->dense_embedding_update = v; }
+void flexflow_config_set_embedding_dtype(flexflow_config_t h, int dt) {
+  if (dt != DT_FLOAT && dt != DT_BF16) { fprintf(stderr, "FATAL: embedding data type %d: %d (fp32) or %d (bf16)\n", dt, (int)DT_FLOAT, (int)DT_BF16); abort(); }
+  C(h)->embedding_dtype = (DataType)dt;
+}
+void flexflow_config_set_embedding_rounding(flexflow_config_t h, int mode) {
+  if (mode != 0 && mode != 1) { fprintf(stderr, "FATAL: embedding rounding %d: 0 (stochastic) or 1 (nearest)\n", mode); abort(); }
+  C(h)->embedding_rounding = mode;
+}
 
 flexflow_model_t flexflow_model_create(flexflow_config_t c) { flexflow_model_t h; h.impl = new FFModel(*C(c)); return h; }
 void flexflow_model_destroy(flexflow_model_t h) { delete M(h); }
@@ -134,6 +142,8 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   }
   if (n == "allreduce_bucket_channel_own") return M(m)->config.comm.bucket_channel_own;
   if (n == "direct_allreduces") return M(m)->n_direct_allreduces;
+  if (n == "bf16_updates") return (int64_t)M(m)->read_bf16_counter();
+  if (n == "early_sorts") return M(m)->n_early_sorts;
   if (n == "tensor_op_exact_backward_layers") {      // Linear layers whose backward runs in exact mode under --allow-tensor-op-math-conversion (allocate() step 7)
     int64_t k = 0;
     for (Op* op : M(m)->layers) if (op->op_type == OP_LINEAR && static_cast<Linear*>(op)->bwd_exact) k++;
@@ -153,6 +163,15 @@ void flexflow_tensor_set_int64(flexflow_tensor_t t, flexflow_model_t m, const in
 void flexflow_tensor_get_float(flexflow_tensor_t t, flexflow_model_t m, float* d) { T(t)->get_tensor<float>(M(m), d); }
 void flexflow_tensor_get_int64(flexflow_tensor_t t, flexflow_model_t m, int64_t* d) { T(t)->get_tensor<int64_t>(M(m), d); }
 void flexflow_tensor_get_grad_float(flexflow_tensor_t t, flexflow_model_t m, float* d) { T(t)->get_grad<float>(M(m), d); }
+int flexflow_tensor_get_data_type(flexflow_tensor_t t) { return (int)T(t)->data_type; }
+void flexflow_tensor_set_bf16(flexflow_tensor_t t, flexflow_model_t m, const int* dims, int nd, const uint16_t* d) {
+  if (T(t)->data_type != DT_BF16) { fprintf(stderr, "FATAL: flexflow_tensor_set_bf16: not a bf16 tensor\n"); abort(); }
+  T(t)->set_tensor<uint16_t>(M(m), dims_vec(dims, nd), d);
+}
+void flexflow_tensor_get_bf16(flexflow_tensor_t t, flexflow_model_t m, uint16_t* d) {
+  if (T(t)->data_type != DT_BF16) { fprintf(stderr, "FATAL: flexflow_tensor_get_bf16: not a bf16 tensor\n"); abort(); }
+  T(t)->get_tensor<uint16_t>(M(m), d);
+}
 
 flexflow_dlrm_t flexflow_dlrm_create(int argc, char** argv, const ffcomm* comm) { flexflow_dlrm_t h; h.impl = new DLRMApp(argc, argv, comm); return h; }
 void flexflow_dlrm_destroy(flexflow_dlrm_t h) { delete A(h); }

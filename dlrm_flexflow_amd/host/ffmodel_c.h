@@ -39,6 +39,10 @@ void flexflow_config_set_device(flexflow_config_t, int);
 void flexflow_config_set_enable_graph(flexflow_config_t, bool);
 void flexflow_config_set_overlap_embedding(flexflow_config_t, bool);
 void flexflow_config_set_dense_embedding_update(flexflow_config_t, bool);
+/* bf16 embedding tables (--embedding-dtype / --embedding-rounding): data_type 40 (DT_FLOAT, default) or 140 (DT_BF16);
+ * mode 0 stochastic (default) or 1 nearest even (include/ffh_bf16.h).  Other values abort. */
+void flexflow_config_set_embedding_dtype(flexflow_config_t, int data_type);
+void flexflow_config_set_embedding_rounding(flexflow_config_t, int mode);
 
 /* FFModel */
 flexflow_model_t flexflow_model_create(flexflow_config_t);
@@ -88,7 +92,8 @@ const char* flexflow_model_get_backend_name(flexflow_model_t);   /* ffh_backend_
 const char* flexflow_model_get_backend_path(flexflow_model_t);   /* ... and the file it was loaded from */
 void flexflow_model_set_trace_mode(flexflow_model_t, int mode);   /* 0: replay a trace only where that is not slower than launching it (decided on its first calls); 1: always replay */
 int  flexflow_model_trace_replays(flexflow_model_t, int trace_id);   /* 0 once the adaptive mode has settled on eager launches for this trace */
-int64_t flexflow_model_get_counter(flexflow_model_t, const char* name);   /* diagnostics for tests: "mlp_chain_fwd_calls", "mlp_chain_bwd_calls"; -1: unknown */
+int64_t flexflow_model_get_counter(flexflow_model_t, const char* name);   /* diagnostics for tests: "mlp_chain_fwd_calls", "mlp_chain_bwd_calls",
+                                                                            "bf16_updates" (the bf16 tables' update counter, synchronises); -1: unknown */
 
 /* Tensor / Parameter host<->device [ref: flexflow_parameter_set_weights_float, python/flexflow_c.h:498-546] */
 int  flexflow_tensor_get_num_dims(flexflow_tensor_t);
@@ -96,13 +101,18 @@ void flexflow_tensor_get_dims(flexflow_tensor_t, int* dims);            /* natur
 int64_t flexflow_tensor_get_local_rows(flexflow_tensor_t);
 bool flexflow_tensor_is_local(flexflow_tensor_t);                       /* false: table owned by another rank */
 void* flexflow_tensor_get_device_ptr(flexflow_tensor_t);                /* address of element (0, 0) in the backend's memory (tests / tools: on-device
-                                                                           comparisons of tables too large to copy out); NULL when not local */
+                                                                           comparisons of tables too large to copy out); NULL when not local.
+                                                                           A bf16 table (data type 140): it points at bf16 bit patterns */
+int  flexflow_tensor_get_data_type(flexflow_tensor_t);                  /* 40 DT_FLOAT, 43 DT_INT64, 140 DT_BF16 (a bf16 embedding table), ... */
 int64_t flexflow_tensor_get_ld(flexflow_tensor_t);                      /* elements between consecutive rows */
 void flexflow_tensor_set_float(flexflow_tensor_t, flexflow_model_t, const int* dims, int num_dims, const float* data);
 void flexflow_tensor_set_int64(flexflow_tensor_t, flexflow_model_t, const int* dims, int num_dims, const int64_t* data);
 void flexflow_tensor_get_float(flexflow_tensor_t, flexflow_model_t, float* data);
 void flexflow_tensor_get_int64(flexflow_tensor_t, flexflow_model_t, int64_t* data);
 void flexflow_tensor_get_grad_float(flexflow_tensor_t, flexflow_model_t, float* data);
+/* a bf16 table: _set_float rounds to nearest even, _get_float widens exactly; _set_bf16 / _get_bf16 copy the uint16 bit patterns */
+void flexflow_tensor_set_bf16(flexflow_tensor_t, flexflow_model_t, const int* dims, int num_dims, const uint16_t* data);
+void flexflow_tensor_get_bf16(flexflow_tensor_t, flexflow_model_t, uint16_t* data);
 
 /* DLRM application (examples/cpp/DLRM) */
 flexflow_dlrm_t flexflow_dlrm_create(int argc, char** argv, const ffcomm* comm);

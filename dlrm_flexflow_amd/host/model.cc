@@ -80,7 +80,8 @@ int64_t Tensor::rows() const {
 template <typename T>
 bool Tensor::set_tensor(const FFModel* model, const std::vector<int>& dims, const T* data) {
   if (!impl || !impl->ptr) die("set_tensor before compile()");
-  if (sizeof(T) != dtype_size(data_type)) die("set_tensor: element type does not match the tensor's data type");
+  const bool to_bf16 = std::is_same<T, float>::value && data_type == DT_BF16;   // fp32 into a bf16 table: rounded to nearest even
+  if (sizeof(T) != dtype_size(data_type) && !to_bf16) die("set_tensor: element type does not match the tensor's data type");
   size_t vol = 1;
   for (int d : dims) vol *= (size_t)d;
   const int64_t cols_ = adim[0];
@@ -94,7 +95,17 @@ bool Tensor::set_tensor(const FFModel* model, const std::vector<int>& dims, cons
   model->check(model->api->ffh_stream_sync(model->ctx, model->side_stream), "set_tensor sync");
   model->check(model->api->ffh_stream_sync(model->ctx, model->dw_stream), "set_tensor sync");
   model->check(model->api->ffh_stream_sync(model->ctx, model->ar_stream), "set_tensor sync");
-  if (impl->ld == cols_) {
+  if (to_bf16) {
+    if (impl->ld != cols_) die("set_tensor: a bf16 table is contiguous");
+    // ffh_bf16_rne (include/ffh_bf16.h) in bounded chunks: tables reach tens of GB
+    std::vector<uint16_t> h(std::min<size_t>(vol, kBf16Chunk));
+    for (size_t i0 = 0; i0 < vol; i0 += h.size()) {
+      const size_t n = std::min(h.size(), vol - i0);
+      for (size_t i = 0; i < n; i++) h[i] = ffh_bf16_rne((float)data[i0 + i]);
+      model->check(model->api->ffh_memcpy_h2d(model->ctx, (uint16_t*)impl->ptr + i0, h.data(), n * 2, model->stream), "set_tensor");
+      model->check(model->api->ffh_stream_sync(model->ctx, model->stream), "set_tensor sync");
+    }
+  } else if (impl->ld == cols_) {
     model->check(model->api->ffh_memcpy_h2d(model->ctx, impl->ptr, data, vol * sizeof(T), model->stream), "set_tensor");
   } else {
     for (int64_t r = 0; r < nrows; r++)
@@ -118,7 +129,18 @@ bool copy_out(const FFModel* model, const Tensor& t, const void* base, int64_t l
   model->check(model->api->ffh_stream_sync(model->ctx, model->side_stream), "get_tensor sync");
   model->check(model->api->ffh_stream_sync(model->ctx, model->dw_stream), "get_tensor sync");
   model->check(model->api->ffh_stream_sync(model->ctx, model->ar_stream), "get_tensor sync");
-  if (ld == cols_) {
+  if (std::is_same<T, float>::value && t.data_type == DT_BF16 && base == t.impl->ptr) {
+    // a bf16 table out as fp32: exact widening, in bounded chunks
+    if (ld != cols_) die("get_tensor: a bf16 table is contiguous");
+    const size_t vol = (size_t)nrows * cols_;
+    std::vector<uint16_t> h(std::min<size_t>(vol, kBf16Chunk));
+    for (size_t i0 = 0; i0 < vol; i0 += h.size()) {
+      const size_t n = std::min(h.size(), vol - i0);
+      model->check(model->api->ffh_memcpy_d2h(model->ctx, h.data(), (const uint16_t*)base + i0, n * 2, model->stream), "get_tensor");
+      model->check(model->api->ffh_stream_sync(model->ctx, model->stream), "get_tensor sync");
+      for (size_t i = 0; i < n; i++) data[i0 + i] = (T)ffh_bf16_to_f32(h[i]);
+    }
+  } else if (ld == cols_) {
     model->check(model->api->ffh_memcpy_d2h(model->ctx, data, base, (size_t)nrows * cols_ * sizeof(T), model->stream), "get_tensor");
   } else {
     for (int64_t r = 0; r < nrows; r++)
@@ -132,7 +154,8 @@ bool copy_out(const FFModel* model, const Tensor& t, const void* base, int64_t l
 
 template <typename T>
 bool Tensor::get_tensor(const FFModel* model, T* data) const {
-  if (sizeof(T) != dtype_size(data_type)) die("get_tensor: element type does not match the tensor's data type");
+  if (sizeof(T) != dtype_size(data_type) && !(std::is_same<T, float>::value && data_type == DT_BF16))
+    die("get_tensor: element type does not match the tensor's data type");
   return copy_out<T>(model, *this, impl ? impl->ptr : nullptr, impl ? impl->ld : 0, data);
 }
 template <typename T>
@@ -152,6 +175,8 @@ template bool Tensor::set_tensor<int64_t>(const FFModel*, const std::vector<int>
 template bool Tensor::get_tensor<float>(const FFModel*, float*) const;
 template bool Tensor::get_tensor<int64_t>(const FFModel*, int64_t*) const;
 template bool Tensor::get_grad<float>(const FFModel*, float*) const;
+template bool Tensor::set_tensor<uint16_t>(const FFModel*, const std::vector<int>&, const uint16_t*);   // bf16 tables: raw bit patterns
+template bool Tensor::get_tensor<uint16_t>(const FFModel*, uint16_t*) const;
 template bool Parameter::set_weights<float>(const FFModel*, const std::vector<int>&, const float*);
 template bool Parameter::get_weights<float>(const FFModel*, float*) const;
 
@@ -159,18 +184,40 @@ template bool Parameter::get_weights<float>(const FFModel*, float*) const;
 // Initializers [ref: src/runtime/initializer.cc, initializer_kernel.cu:24-276]
 // The reference draws from cuRAND; streams here come from include/ffh_rng.h.
 // =============================================================================================
+// bf16 tables (--embedding-dtype bf16): every initializer leaves the nearest-even rounding of what it writes into an fp32 table --
+// uniform and Glorot through ffh_init_uniform_bf16 with the seed they pass to ffh_init_uniform, the others on the host
+namespace {
+void upload_bf16(const FFModel* ff, const Parameter* p, const std::function<float(size_t)>& value, const char* what) {
+  const size_t n = p->get_volume();
+  std::vector<uint16_t> h(std::min<size_t>(n, kBf16Chunk));
+  for (size_t i0 = 0; i0 < n; i0 += h.size()) {
+    const size_t k = std::min(h.size(), n - i0);
+    for (size_t i = 0; i < k; i++) h[i] = ffh_bf16_rne(value(i0 + i));
+    ff->check(ff->api->ffh_memcpy_h2d(ff->ctx, (uint16_t*)p->impl->ptr + i0, h.data(), k * 2, ff->stream), what);
+    ff->check(ff->api->ffh_stream_sync(ff->ctx, ff->stream), what);
+  }
+  ff->note_weight_write(p->impl->ptr);
+}
+void init_uniform(const FFModel* ff, const Parameter* p, uint64_t seed, float lo, float hi, const char* what) {
+  if (p->data_type == DT_BF16)
+    ff->check(ff->api->bf16->ffh_init_uniform_bf16(ff->ctx, (uint16_t*)p->impl->ptr, (int64_t)p->get_volume(), seed, lo, hi, ff->stream), what);
+  else
+    ff->check(ff->api->ffh_init_uniform(ff->ctx, (float*)p->impl->ptr, (int64_t)p->get_volume(), seed, lo, hi, ff->stream), what);
+}
+}  // namespace
+
 void ZeroInitializer::init(const FFModel* ff, const Parameter* p) {
-  ff->check(ff->api->ffh_zero(ff->ctx, p->impl->ptr, p->get_volume() * sizeof(float), ff->stream), "ZeroInitializer");
+  ff->check(ff->api->ffh_zero(ff->ctx, p->impl->ptr, p->get_volume() * dtype_size(p->data_type), ff->stream), "ZeroInitializer");
   ff->note_weight_write(p->impl->ptr);
 }
 void ConstantInitializer::init(const FFModel* ff, const Parameter* p) {
+  const float v = value;
+  if (p->data_type == DT_BF16) { upload_bf16(ff, p, [v](size_t) { return v; }, "ConstantInitializer"); return; }
   ff->check(ff->api->ffh_fill_f32(ff->ctx, (float*)p->impl->ptr, (int64_t)p->get_volume(), value, ff->stream), "ConstantInitializer");
   ff->note_weight_write(p->impl->ptr);
 }
 void UniformInitializer::init(const FFModel* ff, const Parameter* p) {
-  ff->check(ff->api->ffh_init_uniform(ff->ctx, (float*)p->impl->ptr, (int64_t)p->get_volume(),
-                                      ff->config.seed * 0x9E3779B1ULL + (uint64_t)(uint32_t)seed, min_val, max_val, ff->stream),
-            "UniformInitializer");
+  init_uniform(ff, p, ff->config.seed * 0x9E3779B1ULL + (uint64_t)(uint32_t)seed, min_val, max_val, "UniformInitializer");
   ff->note_weight_write(p->impl->ptr);
 }
 void NormInitializer::init(const FFModel* ff, const Parameter* p) {
@@ -185,6 +232,7 @@ void NormInitializer::init(const FFModel* ff, const Parameter* p) {
     const double z = std::sqrt(-2.0 * std::log(u1)) * std::cos(6.283185307179586476925 * u2);
     h[i] = (float)((double)mean + (double)stddev * z);
   }
+  if (p->data_type == DT_BF16) { upload_bf16(ff, p, [&h](size_t i) { return h[i]; }, "NormInitializer"); return; }
   ff->check(ff->api->ffh_memcpy_h2d(ff->ctx, p->impl->ptr, h.data(), n * sizeof(float), ff->stream), "NormInitializer");
   ff->check(ff->api->ffh_stream_sync(ff->ctx, ff->stream), "NormInitializer sync");
   ff->note_weight_write(p->impl->ptr);
@@ -193,9 +241,7 @@ void GlorotUniform::init(const FFModel* ff, const Parameter* p) {
   // scale = sqrt(6 / (fan_in + fan_out)) [ref: src/runtime/initializer_kernel.cu:24-60]
   const float fan = (float)(p->adim[0] + (p->numDim > 1 ? p->adim[1] : 0));
   const float scale = std::sqrt(6.0f / fan);
-  ff->check(ff->api->ffh_init_uniform(ff->ctx, (float*)p->impl->ptr, (int64_t)p->get_volume(),
-                                      ff->config.seed * 0x9E3779B1ULL + (uint64_t)(uint32_t)seed, -scale, scale, ff->stream),
-            "GlorotUniform");
+  init_uniform(ff, p, ff->config.seed * 0x9E3779B1ULL + (uint64_t)(uint32_t)seed, -scale, scale, "GlorotUniform");
   ff->note_weight_write(p->impl->ptr);
 }
 
@@ -732,7 +778,10 @@ void Embedding::set_row_sharding(const FFModel& model, bool on) {
 void Embedding::create_output_and_partition(FFModel&) {}
 void Embedding::create_weights(FFModel& model) {
   const int dims[2] = {row_sharded ? (int)rows_local : num_entries, local_cols};   // column- / row-sharded: this rank's slice only
-  weights[0] = model.create_weight<2>(dims, this, DT_FLOAT, kernel_initializer);
+  // --embedding-dtype bf16: the tables the fused update owns; a data-parallel table stays fp32 in the dense slab (compile() refuses
+  // bf16 with a row- or column-sharded one)
+  const DataType dt = model.config.embedding_dtype == DT_BF16 && !replicated ? DT_BF16 : DT_FLOAT;
+  weights[0] = model.create_weight<2>(dims, this, dt, kernel_initializer);
 }
 void Embedding::forward(const FFModel& ff) {
   // The first table launches the whole group.  With overlap it goes to the side stream, ordered behind the

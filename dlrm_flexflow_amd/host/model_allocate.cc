@@ -167,6 +167,23 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
   // (first: Adam never captures -- alpha_t is a new launch argument every step -- so it must not lose the side-stream overlap to a
   //  capture that will not happen; round-4 advisor)
   if (dynamic_cast<AdamOptimizer*>(optimizer) && config.enable_graph) config.enable_graph = false;
+  // bf16 tables (--embedding-dtype bf16, include/ff_hip_bf16.h): the fused sorted-segments update owns them, so every case it does not
+  // cover is refused here, before anything is allocated or launched
+  if (config.embedding_dtype == DT_BF16 && !embeddings.empty()) {
+    for (const Embedding* e : embeddings)
+      if (e->row_sharded)
+        die("--embedding-dtype bf16: %s is row-sharded; bf16 tables are table-wise for now: drop --row-shard-rows or use --embedding-dtype fp32", e->name);
+    if (config.dense_embedding_update)
+      die("--embedding-dtype bf16 needs the fused sparse table update: drop --dense-embedding-update or use --embedding-dtype fp32");
+    if (!fused_embedding_update())
+      die("--embedding-dtype bf16 with momentum / weight-decay SGD or Adam needs --sparse-embedding-optimizer (or --embedding-dtype fp32)");
+    for (const Embedding* e : embeddings)
+      if (e->column_sharded)
+        die("--embedding-dtype bf16: %s is column-sharded; bf16 tables are table-wise for now: drop --column-shard-rows or use --embedding-dtype fp32", e->name);
+    if (!api->bf16)
+      die("--embedding-dtype bf16: %s (%s) is a kernel library without the bf16 extension (include/ff_hip_bf16.h); use --embedding-dtype fp32",
+          api->path.c_str(), api->ffh_backend_name());
+  }
   if (exchange && config.enable_graph && config.capture_exchange) config.overlap_embedding = false;
   // Any optimizer x any placement (round 4).  Plain SGD: the fused sorted-segments update.  Momentum / weight-decay SGD, Adam:
   // by default the reference's own path on the rank(s) that hold the table -- an owner-local dense gradient (zeroed, scatter-added
@@ -198,6 +215,11 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
       if (e->held_here(rank)) e->kernel_initializer->init(this, &e->weights[0]);
     }
   }
+  for (const Embedding* e : embeddings)
+    if (e->bf16_weights() && e->held_here(rank) && !bf16_counter) {
+      bf16_counter = (uint64_t*)dmalloc(sizeof(uint64_t));
+      check(api->ffh_zero(ctx, bf16_counter, sizeof(uint64_t), stream), "bf16 update counter");
+    }
   compiled = true;
   optimizer->init();
   {   // per-row optimizer state of the touched-rows rule: the shape of the local table (+ the zero row of a row block)
@@ -206,7 +228,7 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
       const int nstate = rule.kind == FFH_SPARSE_OPT_ADAM ? 2 : (rule.momentum > 0.0f ? 1 : 0);
       for (Embedding* e : embeddings) {
         if (!e->held_here(rank) || e->replicated) continue;
-        const size_t bytes = e->weights[0].impl->bytes + (e->row_sharded ? (size_t)e->out_channels * 4 : 0);
+        const size_t bytes = e->weights[0].get_volume() * 4 + (e->row_sharded ? (size_t)e->out_channels * 4 : 0);   // fp32 state, whatever the table's storage
         for (int k = 0; k < nstate; k++) {
           e->opt_state[k] = (float*)dmalloc(bytes);
           check(api->ffh_zero(ctx, e->opt_state[k], bytes, stream), "sparse optimizer state");
@@ -651,7 +673,7 @@ void FFModel::allocate() {
     } else {
       Embedding* e = static_cast<Embedding*>(p.owner_op);
       if (!e->held_here(rank)) continue;   // sole owner (or one column / row block per rank): never replicated, never all-reduced
-      im->bytes = p.get_volume() * 4;
+      im->bytes = p.get_volume() * dtype_size(p.data_type);
       im->ptr = dmalloc(im->bytes + (e->row_sharded ? (size_t)e->out_channels * 4 : 0));   // row block: + the zero row
       if (e->row_sharded) check(api->ffh_zero(ctx, (char*)im->ptr + im->bytes, (size_t)e->out_channels * 4, stream), "zero row");
       if (!fused) {

@@ -13,8 +13,9 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
   const bool ruled = (what == kFusedUpdate || what == kApplyOnly) && ff->sparse_rule(rule);     // momentum / wd SGD, Adam on the touched rows
   const int L = ff->embeddings[0]->inputs[0].adim[0];
   const int aggr = (int)ff->embeddings[0]->aggr;
-  std::map<int, std::vector<ffh_emb_table>> by_cols;
-  std::map<int, std::vector<ffh_emb_state>> st_by_cols;
+  // by shard width, then storage (bf16 tables: include/ff_hip_bf16.h, keyed by global table index and global column)
+  struct Group { std::vector<ffh_emb_table> t; std::vector<ffh_emb_table_bf16> t16; std::vector<ffh_emb_state> st; };
+  std::map<std::pair<int, bool>, Group> groups;
   size_t owned_i = 0;
   for (const FFModel::EmbShard& sh : ff->shards) {
     if (sh.owner != ff->rank) continue;
@@ -32,35 +33,98 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
       t.io = (fwd ? ff->xsend : ff->grecv) + sh.off;
       t.ld = ff->rank_width[ff->rank];
     }
-    by_cols[sh.cols].push_back(t);
-    st_by_cols[sh.cols].push_back(ffh_emb_state{e->opt_state[0], e->opt_state[1]});
+    Group& g = groups[{sh.cols, e->bf16_weights()}];
+    if (e->bf16_weights()) g.t16.push_back(ffh_emb_table_bf16{t.idx, (uint16_t*)t.weight, t.io, t.num_entries, t.ld, e->table_index, sh.col0});
+    else g.t.push_back(t);
+    g.st.push_back(ffh_emb_state{e->opt_state[0], e->opt_state[1]});
   }
-  for (auto& kv : by_cols) {
-    std::vector<ffh_emb_table>& tabs = kv.second;
-    const std::vector<ffh_emb_state>& sts = st_by_cols[kv.first];
+  const int64_t B = ff->config.batchSize;
+  for (auto& kv : groups) {
+    const int D = kv.first.first;
+    const Group& g = kv.second;
+    if (kv.first.second) {
+      const KernelApiBf16* b16 = ff->api->bf16;
+      const ffh_bf16_rounding rnd = ff->bf16_rounding();
+      const size_t per = ff->bf16_tables_per_launch();       // momentum / Adam: FFH_BF16_MAX_STATEFUL_TABLES (the sort of an early-sorted group matches it)
+      for (size_t b = 0; b < g.t16.size(); b += per) {
+        const int n = (int)std::min<size_t>(per, g.t16.size() - b);
+        const ffh_emb_table_bf16* tb = g.t16.data() + b;
+        const ffh_emb_state* st = g.st.data() + b;
+        switch (what) {
+          case kGather: ff->check(b16->ffh_embedding_fwd_multi_bf16(cx, tb, n, L, D, B, aggr, s), "embedding_fwd_multi_bf16"); break;
+          case kFusedUpdate:
+            if (ruled) ff->check(b16->ffh_embedding_bwd_opt_fused_multi_bf16(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, s), "embedding_bwd_opt_fused_multi_bf16");
+            else ff->check(b16->ffh_embedding_bwd_sgd_fused_multi_bf16(cx, tb, n, L, D, B, aggr, rule.lr, &rnd, s), "embedding_bwd_sgd_fused_multi_bf16");
+            break;
+          case kSortOnly: ff->check(b16->ffh_embedding_bwd_sort_multi_bf16(cx, tb, n, L, D, B, s), "embedding_bwd_sort_multi_bf16"); ff->n_early_sorts++; break;
+          case kApplyOnly:
+            if (ruled) ff->check(b16->ffh_embedding_bwd_opt_apply_multi_bf16(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, s), "embedding_bwd_opt_apply_multi_bf16");
+            else ff->check(b16->ffh_embedding_bwd_sgd_apply_multi_bf16(cx, tb, n, L, D, B, aggr, rule.lr, &rnd, s), "embedding_bwd_sgd_apply_multi_bf16");
+            break;
+        }
+      }
+      continue;
+    }
+    const std::vector<ffh_emb_table>& tabs = g.t;
+    const std::vector<ffh_emb_state>& sts = g.st;
     for (size_t b = 0; b < tabs.size(); b += FFH_MAX_TABLES) {
       const int n = (int)std::min<size_t>(FFH_MAX_TABLES, tabs.size() - b);
-      const int64_t B = ff->config.batchSize;
       switch (what) {
-        case kGather: ff->check(ff->api->ffh_embedding_fwd_multi(cx, tabs.data() + b, n, L, kv.first, B, aggr, s), "embedding_fwd_multi"); break;
+        case kGather: ff->check(ff->api->ffh_embedding_fwd_multi(cx, tabs.data() + b, n, L, D, B, aggr, s), "embedding_fwd_multi"); break;
         case kFusedUpdate:
-          if (ruled) ff->check(ff->api->ffh_embedding_bwd_opt_fused_multi(cx, tabs.data() + b, sts.data() + b, n, L, kv.first, B, aggr, &rule, s), "embedding_bwd_opt_fused_multi");
-          else ff->check(ff->api->ffh_embedding_bwd_sgd_fused_multi(cx, tabs.data() + b, n, L, kv.first, B, aggr, rule.lr, s), "embedding_bwd_sgd_fused_multi");
+          if (ruled) ff->check(ff->api->ffh_embedding_bwd_opt_fused_multi(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, s), "embedding_bwd_opt_fused_multi");
+          else ff->check(ff->api->ffh_embedding_bwd_sgd_fused_multi(cx, tabs.data() + b, n, L, D, B, aggr, rule.lr, s), "embedding_bwd_sgd_fused_multi");
           break;
-        case kSortOnly: ff->check(ff->api->ffh_embedding_bwd_sort_multi(cx, tabs.data() + b, n, L, kv.first, B, s), "embedding_bwd_sort_multi"); break;
+        case kSortOnly: ff->check(ff->api->ffh_embedding_bwd_sort_multi(cx, tabs.data() + b, n, L, D, B, s), "embedding_bwd_sort_multi"); ff->n_early_sorts++; break;
         case kApplyOnly:
-          if (ruled) ff->check(ff->api->ffh_embedding_bwd_opt_apply_multi(cx, tabs.data() + b, sts.data() + b, n, L, kv.first, B, aggr, &rule, s), "embedding_bwd_opt_apply_multi");
-          else ff->check(ff->api->ffh_embedding_bwd_sgd_apply_multi(cx, tabs.data() + b, n, L, kv.first, B, aggr, rule.lr, s), "embedding_bwd_sgd_apply_multi");
+          if (ruled) ff->check(ff->api->ffh_embedding_bwd_opt_apply_multi(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, s), "embedding_bwd_opt_apply_multi");
+          else ff->check(ff->api->ffh_embedding_bwd_sgd_apply_multi(cx, tabs.data() + b, n, L, D, B, aggr, rule.lr, s), "embedding_bwd_sgd_apply_multi");
           break;
       }
     }
   }
 }
+
+// bf16 tables: the rounding of this model's table update.  The stochastic bits' seed is ffh_hash(FFConfig::seed, kBf16SeedSalt) --
+// the one place it is derived -- and the update number comes from the counter in device memory
+static constexpr uint64_t kBf16SeedSalt = 0xBF16;
+ffh_bf16_rounding FFModel::bf16_rounding() const {
+  ffh_bf16_rounding r;
+  r.mode = config.embedding_rounding;
+  r.reserved_ = 0;
+  r.seed = ffh_hash(config.seed, kBf16SeedSalt);
+  r.counter = bf16_counter;
+  return r;
+}
+// once per step behind the step's last bf16 table update, on its stream (a captured step replays it too)
+void FFModel::advance_bf16_counter(ffh_stream s, ffh_ctx* cx) const {
+  if (bf16_counter) check(api->bf16->ffh_bf16_counter_advance(cx, bf16_counter, s), "bf16_counter_advance");
+}
+// tables per bf16 launch: the stateful bf16 entries take at most FFH_BF16_MAX_STATEFUL_TABLES (include/ff_hip_bf16.h)
+size_t FFModel::bf16_tables_per_launch() const {
+  ffh_sparse_opt rule;
+  bool any16 = false;
+  for (const Embedding* e : embeddings) any16 = any16 || e->bf16_weights();
+  return any16 && fused_embedding_update() && sparse_rule(rule) ? FFH_BF16_MAX_STATEFUL_TABLES : FFH_MAX_TABLES;
+}
+uint64_t FFModel::read_bf16_counter() const {
+  if (!bf16_counter) return 0;
+  if (dw_worker) dw_worker->drain();
+  if (side_worker) side_worker->drain();
+  check(api->ffh_stream_sync(ctx, side_stream), "bf16 counter sync");
+  check(api->ffh_stream_sync(ctx, stream), "bf16 counter sync");
+  uint64_t v = 0;
+  check(api->ffh_memcpy_d2h(ctx, &v, bf16_counter, sizeof v, stream), "bf16 counter");
+  check(api->ffh_stream_sync(ctx, stream), "bf16 counter sync");
+  return v;
+}
+
 // the batched gather (fwd) or fused update kernels of this rank's shards alone, no exchange: what bench.py times as the
 // roofline kernels of a multi-rank job
 void FFModel::embedding_kernels_only(bool fwd, ffh_stream s, const std::vector<const int64_t*>* idx_override) const {
   if (embeddings.empty() || (!fwd && !fused_embedding_update())) return;
   launch_shard_groups(this, fwd ? kGather : kFusedUpdate, s, ctx, idx_override);
+  if (!fwd) advance_bf16_counter(s, ctx);
 }
 
 // The sort of the fused update reads only the sparse ids, which are final when the gather starts: issued behind the gather on
@@ -89,7 +153,7 @@ bool FFModel::early_sort_possible(int where) const {
   }
   for (const Embedding* e : embeddings)
     if (e->row_sharded) return false;
-  return n > 0 && n <= FFH_MAX_TABLES;
+  return n > 0 && (size_t)n <= bf16_tables_per_launch();
 }
 
 void FFModel::probe_record(int which, ffh_stream s, ffh_ctx* cx) const {
@@ -204,6 +268,7 @@ void FFModel::embedding_group_update(ffh_stream s, ffh_ctx* on_ctx) const {
     }
     check(api->ffh_zero(cx, w + e->rows_local * (int64_t)D, (size_t)D * 4, s), "zero row");   // (its optimizer state is never read for a row of the block)
   }
+  advance_bf16_counter(s, cx);
 }
 
 // The reference's own table update on the rank(s) that hold a table, for optimizers the fused update does not cover (default for

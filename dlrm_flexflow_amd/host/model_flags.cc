@@ -66,6 +66,8 @@ FFConfig::FFConfig() {
   allow_tensor_op_math_conversion = false;
   fp32_split_bf16x3 = false;
   deterministic = false;
+  embedding_dtype = DT_FLOAT;
+  embedding_rounding = FFH_BF16_ROUND_STOCHASTIC;
   memset(&comm, 0, sizeof comm);
   comm.rank = 0;
   comm.world_size = 1;
@@ -147,5 +149,19 @@ void FFConfig::parse_args(char** argv, int argc) {
     if (is("--no-bf16-twins")) { bf16_twins = false; continue; }               // A/B and tests: tensor-op mode rounding its operands inside the kernels
     if (is("--force-async-launch")) { force_async_launch = true; continue; }   // tests: the launch-worker threads on a synchronous backend
     if (is("--sparse-embedding-optimizer")) { sparse_embedding_optimizer = true; continue; }
+    if (is("--embedding-dtype")) {
+      const char* v = next();
+      if (!strcmp(v, "fp32")) embedding_dtype = DT_FLOAT;
+      else if (!strcmp(v, "bf16")) embedding_dtype = DT_BF16;
+      else die("--embedding-dtype %s: 'fp32' or 'bf16'", v);
+      continue;
+    }
+    if (is("--embedding-rounding")) {
+      const char* v = next();
+      if (!strcmp(v, "stochastic")) embedding_rounding = FFH_BF16_ROUND_STOCHASTIC;
+      else if (!strcmp(v, "nearest")) embedding_rounding = FFH_BF16_ROUND_NEAREST;
+      else die("--embedding-rounding %s: 'stochastic' or 'nearest'", v);
+      continue;
+    }
   }
 }

@@ -18,8 +18,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <type_traits>
 
 #include "../../include/ffh_rng.h"
+#include "../../include/ffh_bf16.h"
 #include "backend.h"
 
 [[noreturn]] inline void die(const char* fmt, ...) {
@@ -43,9 +46,13 @@ inline size_t dtype_size(DataType t) {
     case DT_INT32: return 4;
     case DT_INT64: return 8;
     case DT_BOOLEAN: return 1;
+    case DT_BF16: return 2;
     default: return 0;
   }
 }
+
+// elements per host-staged conversion of a bf16 table (8 MiB of bf16): set / get weights and initializers in bounded chunks
+constexpr size_t kBf16Chunk = (size_t)1 << 22;
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 

@@ -8,7 +8,12 @@
  * (bit-identical to that entry on the widened fp32 table, SUM and AVG, twin / three-plane outputs included); the update
  * computes the row sums and w32 = fmaf(-lr, sum, (float)w16) exactly as ffh_embedding_bwd_sgd_fused_multi does on the
  * widened table, then rounds once to bf16 (include/ffh_bf16.h: nearest even, or stochastic with bits keyed by seed,
- * the update counter in device memory, global table index, global row and global column).  Plain SGD only.
+ * the update counter in device memory, global table index, global row and global column).
+ * Version 2 adds momentum / weight-decay SGD and Adam on bf16 tables (ffh_embedding_bwd_opt_{fused,apply}_multi_bf16): the row gradient
+ * is the canonical FFH_EMB_CHUNK-order sum, w is the widened (float)w16, and the state update and the fp32 result w32 are statement by
+ * statement those of FFH_SPARSE_OPT_SGD_MOMENTUM / FFH_SPARSE_OPT_ADAM in ffh_embedding_bwd_opt_fused_multi on the widened table.  The state
+ * stays fp32 (ffh_emb_state, [num_entries][out_dim]) and is bit-identical to what the fp32 entry leaves on the widened table; w32 is then
+ * rounded once to bf16 with the key above.  kind == FFH_SPARSE_OPT_SGD gives the bits of ffh_embedding_bwd_sgd_*_multi_bf16.
  */
 #ifndef FF_HIP_BF16_H_
 #define FF_HIP_BF16_H_
@@ -19,7 +24,13 @@
 extern "C" {
 #endif
 
-#define FFH_BF16_ABI_VERSION 1   /* 1: gather, fused update (one call or sort + apply), uniform init, counter advance */
+#define FFH_BF16_ABI_VERSION 2   /* 2: ffh_embedding_bwd_opt_fused_multi_bf16 / _apply_multi_bf16 (momentum / weight-decay SGD, Adam);
+                                    1: gather, fused update (one call or sort + apply), uniform init, counter advance */
+
+/* the stateful entries (momentum / Adam) take at most this many tables per call: their kernel arguments hold the tables, the state pointers
+ * AND the rounding keys, which for 64 tables would pass the 4 KB of kernel arguments; more tables are refused with FFH_ERR_BAD_ARG
+ * (split the call).  kind == FFH_SPARSE_OPT_SGD takes FFH_MAX_TABLES like the SGD entries. */
+#define FFH_BF16_MAX_STATEFUL_TABLES 32
 
 /* One bf16 table of a batched launch: ffh_emb_table with 16-bit weights and the table's place in the model. */
 typedef struct ffh_emb_table_bf16 {
@@ -55,6 +66,14 @@ int ffh_embedding_bwd_sort_multi_bf16(ffh_ctx* ctx, const ffh_emb_table_bf16* ta
                                       int64_t batch, ffh_stream stream);
 int ffh_embedding_bwd_sgd_apply_multi_bf16(ffh_ctx* ctx, const ffh_emb_table_bf16* tables, int ntables, int in_dim, int out_dim,
                                            int64_t batch, int aggr, float lr, const ffh_bf16_rounding* rounding, ffh_stream stream);
+/* Fused backward + the row rule `opt` (ffh_embedding_bwd_opt_fused_multi semantics on the widened table, fp32 state `states`, then one
+ * rounding); the apply half behind ffh_embedding_bwd_sort_multi_bf16, with the same one-shot rule (one apply per sort). */
+int ffh_embedding_bwd_opt_fused_multi_bf16(ffh_ctx* ctx, const ffh_emb_table_bf16* tables, const ffh_emb_state* states, int ntables, int in_dim,
+                                           int out_dim, int64_t batch, int aggr, const ffh_sparse_opt* opt, const ffh_bf16_rounding* rounding,
+                                           ffh_stream stream);
+int ffh_embedding_bwd_opt_apply_multi_bf16(ffh_ctx* ctx, const ffh_emb_table_bf16* tables, const ffh_emb_state* states, int ntables, int in_dim,
+                                           int out_dim, int64_t batch, int aggr, const ffh_sparse_opt* opt, const ffh_bf16_rounding* rounding,
+                                           ffh_stream stream);
 /* p[i] = ffh_bf16_rne(ffh_uniform(ffh_hash(seed, i), lo, hi)): the rounding of ffh_init_uniform's output. */
 int ffh_init_uniform_bf16(ffh_ctx* ctx, uint16_t* p, int64_t n, uint64_t seed, float lo, float hi, ffh_stream stream);
 /* *counter += 1, one lane, on `stream`. */
@@ -66,6 +85,7 @@ int ffh_bf16_counter_advance(ffh_ctx* ctx, uint64_t* counter, ffh_stream stream)
 
 #define FFH_BF16_API_LIST(X) \
   X(ffh_bf16_abi_version) X(ffh_embedding_fwd_multi_bf16) X(ffh_embedding_bwd_sgd_fused_multi_bf16) \
-  X(ffh_embedding_bwd_sort_multi_bf16) X(ffh_embedding_bwd_sgd_apply_multi_bf16) X(ffh_init_uniform_bf16) X(ffh_bf16_counter_advance)
+  X(ffh_embedding_bwd_sort_multi_bf16) X(ffh_embedding_bwd_sgd_apply_multi_bf16) X(ffh_init_uniform_bf16) X(ffh_bf16_counter_advance) \
+  X(ffh_embedding_bwd_opt_fused_multi_bf16) X(ffh_embedding_bwd_opt_apply_multi_bf16)
 
 #endif /* FF_HIP_BF16_H_ */
