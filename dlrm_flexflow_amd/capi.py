@@ -202,6 +202,43 @@ _SIGS_BF16 = {
 }
 
 
+# include/ff_hip_ctr.h: the optional CTR extension (binary cross-entropy, evaluation histograms); same rule as the bf16 extension
+CTR_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_ctr.h")
+METRIC_BCE = 16
+AUC_BINS = 65536
+
+
+class CtrEval(C.Structure):
+    """struct ffh_ctr_eval"""
+    _fields_ = [("samples", U64), ("positives", U64), ("correct", U64), ("nan_predictions", U64), ("logloss_sum", F), ("pad_", F * 3),
+                ("hist_pos", U64 * AUC_BINS), ("hist_neg", U64 * AUC_BINS)]
+
+
+_SIGS_CTR = {
+    "ffh_ctr_abi_version": (I, []),
+    "ffh_bce_bwd_metrics": (I, [P, P, P, P, P, P, L, I, F, I, P]),
+    "ffh_linear_bwd_bce": (I, [P, P, L, P, L, P, L, P, L, P, P, P, I, I, L, I, I, P, F, P, P, I, P]),
+    "ffh_ctr_eval_update": (I, [P, P, P, P, L, P]),
+}
+
+
+def ctr_header_symbols(header_path: str = CTR_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_CTR_API_LIST X-macro in include/ff_hip_ctr.h."""
+    text = open(header_path).read()
+    m = re.search(r"#define FFH_CTR_API_LIST\(X\)(.*?)\n\n", text, re.S)
+    if not m:
+        raise RuntimeError("FFH_CTR_API_LIST not found in " + header_path)
+    return re.findall(r"X\((\w+)\)", m.group(1))
+
+
+def ctr_header_abi_version(header_path: str = CTR_HEADER_PATH) -> int:
+    """FFH_CTR_ABI_VERSION of include/ff_hip_ctr.h."""
+    m = re.search(r"#define\s+FFH_CTR_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_CTR_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
 def bf16_header_symbols(header_path: str = BF16_HEADER_PATH) -> list[str]:
     """Every symbol of the FFH_BF16_API_LIST X-macro in include/ff_hip_bf16.h."""
     text = open(header_path).read()
@@ -397,6 +434,41 @@ class Bf16Api:
 def bf16_api(lib: FFHLib) -> Bf16Api:
     """The bf16-table entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
     return Bf16Api(lib)
+
+
+class CtrApi:
+    """The CTR extension (include/ff_hip_ctr.h) of a loaded FFHLib; `ctr_api(lib)` builds it or raises."""
+
+    def __init__(self, lib: FFHLib):
+        self.base = lib
+        for name, (res, args) in _SIGS_CTR.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no CTR extension ({name} missing; include/ff_hip_ctr.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_ctr_abi_version()
+        if got != ctr_header_abi_version():
+            raise FFHError(f"{lib.path}: CTR ABI version {got}, include/ff_hip_ctr.h says {ctr_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+    def rc(self, name: str, *args) -> int:
+        """`name(ctx, *args)` of the extension, returning its status code (FFH_OK, FFH_ERR_UNSUPPORTED, ...)."""
+        sig = _SIGS_CTR[name][1][1:]
+        if len(args) != len(sig):
+            raise TypeError(f"{name}: expected {len(sig)} args, got {len(args)}")
+        conv = [ptr(a) if t is P else a for a, t in zip(args, sig)]
+        return getattr(self.lib, name)(self.ctx, *conv)
+
+    def call(self, name: str, *args):
+        """Call `name(ctx, *args)` of the extension; pointers may be tensors/arrays/ints/None."""
+        self.base.check(self.rc(name, *args), name)
+
+
+def ctr_api(lib: FFHLib) -> CtrApi:
+    """The CTR entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
+    return CtrApi(lib)
 
 
 _hip_singleton: FFHLib | None = None

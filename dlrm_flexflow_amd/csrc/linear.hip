@@ -18,6 +18,7 @@
 // reluBackward/sigmoid_backward + cublasSgemm x2 + cublasSgemv [ref: src/ops/linear.cu:624-659],
 // cublasSgemmStridedBatched [ref: src/ops/batch_matmul.cu:238-241,393-398].
 #include "linear_gemm.h"
+#include "../../include/ff_hip_ctr.h"   // FFH_METRIC_BCE, ffh_linear_bwd_bce: the BCE loss kind of the one-launch skinny backward
 
 #include <hip/hip_ext.h>   // hipExtLaunchKernelGGL: a launch that carries its own completion event
 
@@ -1017,6 +1018,7 @@ struct SkinnyBwdArgs {
   int do_db, do_dw, do_dx, dx_overwrite, mask_by_x;
   // MSE loss step folded in (ffh_linear_bwd_mse): dy is not read but made here from y and label; metrics as metrics_kernel
   const float* label;  float loss_scale;  ffh_perf_metrics* perf;  int metrics_flags;
+  float* bce_sum;             // loss kind BCE (ffh_linear_bwd_bce, include/ff_hip_ctr.h): where the log-loss sum goes (FFH_METRIC_BCE)
   unsigned short* dx16;       // tensor-op mode: the bf16 twin of dx (ffh_ctx_bf16_mirror_set), written beside it, or null
   // dW / db without atomic chains: workgroup b leaves its partial row [out * in + out] at ws + b * ws_stride, the last one to arrive
   // (ws_cnt) adds the rows up in block order and adds the total to dw / db.  Null: one atomic per weight per workgroup.
@@ -1026,7 +1028,9 @@ struct SkinnyBwdArgs {
 // NC: 16-byte column chunks per lane (in <= 256 * NC), NO: output slots kept in registers (out <= NO),
 // RPW: rows per wave-instruction -- a row of in = 256 / RPW floats fills 64 / RPW lanes, so RPW rows go side by side
 // (lane = rsub * (64 / RPW) + chunk) instead of leaving three quarters of the wave idle on the 64-wide layer
-template <int NC, int NO, int RPW = 1>
+// BCE: the folded loss step is binary cross-entropy on the layer's sigmoid output instead of MSE (dz = (p - label) * scale, no sigmoid
+// derivative: the launcher passes act NONE); the MSE / no-loss instantiations compile as before
+template <int NC, int NO, int RPW = 1, bool BCE = false>
 __global__ __launch_bounds__(256) void linear_skinny_bwd_kernel(const SkinnyBwdArgs a) {
   ffh_kernel_prio();
   static_assert(RPW == 1 || NC == 1, "row packing is for rows narrower than a wave");
@@ -1039,13 +1043,20 @@ __global__ __launch_bounds__(256) void linear_skinny_bwd_kernel(const SkinnyBwdA
   // 1. activation gradient of this block's rows: reluBackward [ref: src/runtime/cuda_helper.cu:71-78] /
   //    sigmoid_backward [ref: src/ops/linear.cu:600-607], once per element, then shared through LDS
   float mse_s = 0.f, rmse_s = 0.f, mae_s = 0.f;
+  float bce_s = 0.f;
   int m_all = 0, m_correct = 0;
   for (int e = tid; e < rows * a.out; e += 256) {
     const int r = e / a.out, o = e - r * a.out;
     float d;
     if (a.label) {
       // mean_squared_error_avg_loss_backward + scale [ref: src/loss_functions/loss_functions.cu:65-76,160-166], same rounding as metrics_kernel
-      d = __fmaf_rn(a.loss_scale - 0.0f, a.y[(b0 + r) * a.ldy + o] - a.label[(b0 + r) * a.out + o], 0.0f);
+      if (BCE) {
+        const float pv = a.y[(b0 + r) * a.ldy + o], lv = a.label[(b0 + r) * a.out + o];
+        d = __fmul_rn(__fsub_rn(pv, lv), a.loss_scale);               // include/ff_hip_ctr.h: two roundings, no fma
+        if (a.metrics_flags & FFH_METRIC_BCE) bce_s += -(lv * fmaxf(logf(pv), -100.0f) + (1.0f - lv) * fmaxf(logf(1.0f - pv), -100.0f));
+      } else {
+        d = __fmaf_rn(a.loss_scale - 0.0f, a.y[(b0 + r) * a.ldy + o] - a.label[(b0 + r) * a.out + o], 0.0f);
+      }
       if (o == 0) {   // per-sample metrics [ref: src/metrics_functions/metrics_functions.cu:108-173], as metrics_kernel computes them
         const float* lg = a.y + (b0 + r) * a.ldy;
         const float* lb = a.label + (b0 + r) * a.out;
@@ -1081,14 +1092,16 @@ __global__ __launch_bounds__(256) void linear_skinny_bwd_kernel(const SkinnyBwdA
     s_dz[e] = d;
   }
   if (a.label) {   // one atomic per counter per workgroup (uniform branch: label is a kernel argument)
-    __shared__ float s_mf[3][4];
+    constexpr int kBceRow = BCE ? 3 : 0;            // the log-loss partials: a fourth row in the BCE instantiations only
+    __shared__ float s_mf[BCE ? 4 : 3][4];
     __shared__ int s_mi[2][4];
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
       mse_s += __shfl_down(mse_s, o); rmse_s += __shfl_down(rmse_s, o); mae_s += __shfl_down(mae_s, o);
+      if (BCE) bce_s += __shfl_down(bce_s, o);
       m_all += __shfl_down(m_all, o); m_correct += __shfl_down(m_correct, o);
     }
-    if (lane == 0) { s_mf[0][wave] = mse_s; s_mf[1][wave] = rmse_s; s_mf[2][wave] = mae_s; s_mi[0][wave] = m_all; s_mi[1][wave] = m_correct; }
+    if (lane == 0) { s_mf[0][wave] = mse_s; s_mf[1][wave] = rmse_s; s_mf[2][wave] = mae_s; s_mi[0][wave] = m_all; s_mi[1][wave] = m_correct; if (BCE) s_mf[kBceRow][wave] = bce_s; }
     __syncthreads();
     if (tid == 0) {
       const int al = s_mi[0][0] + s_mi[0][1] + s_mi[0][2] + s_mi[0][3];
@@ -1098,6 +1111,7 @@ __global__ __launch_bounds__(256) void linear_skinny_bwd_kernel(const SkinnyBwdA
       if (a.metrics_flags & 2) atomicAdd(&a.perf->mse_loss, (s_mf[0][0] + s_mf[0][1]) + (s_mf[0][2] + s_mf[0][3]));
       if (a.metrics_flags & 4) atomicAdd(&a.perf->rmse_loss, (s_mf[1][0] + s_mf[1][1]) + (s_mf[1][2] + s_mf[1][3]));
       if (a.metrics_flags & 8) atomicAdd(&a.perf->mae_loss, (s_mf[2][0] + s_mf[2][1]) + (s_mf[2][2] + s_mf[2][3]));
+      if (BCE && (a.metrics_flags & FFH_METRIC_BCE)) atomicAdd(a.bce_sum, (s_mf[kBceRow][0] + s_mf[kBceRow][1]) + (s_mf[kBceRow][2] + s_mf[kBceRow][3]));
     }
   }
   __syncthreads();
@@ -1591,7 +1605,7 @@ bool skinny_ws_for(ffh_ctx* c, hipStream_t s, float** ws, unsigned** cnt) {
 int linear_bwd_impl(ffh_ctx* c, const float* x, int64_t ldx, float* dx, int64_t lddx, const float* y, int64_t ldy,
                     float* dy, int64_t lddy, const float* w, float* dw, float* db,
                     int in, int out, int64_t batch, int act, int flags, ffh_stream s, ffh_stream s_dw,
-                    const float* label, float loss_scale, ffh_perf_metrics* perf, int metrics_flags) {
+                    const float* label, float loss_scale, ffh_perf_metrics* perf, int metrics_flags, float* bce_sum = nullptr, bool bce = false) {
   FFH_REQUIRE(c, in > 0 && out > 0 && batch >= 0 && ldx >= in && ldy >= out && lddy >= out && (!dx || lddx >= in), "linear_bwd: bad dims");
   FFH_REQUIRE(c, batch == 0 || (x && y && dy && w && dw), "linear_bwd: null pointer");
   FFH_REQUIRE(c, batch < (1LL << 31), "linear_bwd: batch too large");
@@ -1628,6 +1642,7 @@ int linear_bwd_impl(ffh_ctx* c, const float* x, int64_t ldx, float* dx, int64_t 
       if (only_dx || only_dw || premasked || out > kSkinnyMaxOut) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "linear_bwd_mse: not a whole one-launch layer");
       a.label = label; a.loss_scale = loss_scale; a.perf = perf; a.metrics_flags = metrics_flags;
       a.write_back = 1;              // dy must end up holding what the loss step + the layer's in-place pass leave there
+      if (bce) { a.bce_sum = bce_sum; a.act = FFH_AC_MODE_NONE; }      // dz is final: p (1 - p) cancelled (include/ff_hip_ctr.h)
     }
     // dW / db: the workgroups' partial rows meet in ctx-owned scratch and the last one to arrive adds them up (no atomic chains); then
     // the number of workgroups follows what the x / dX stream wants.  Without scratch (a capture in flight before the stream's first
@@ -1658,12 +1673,16 @@ int linear_bwd_impl(ffh_ctx* c, const float* x, int64_t ldx, float* dx, int64_t 
       if (lds < 4096) lds = 4096;                          // the last arriver's cross-thread combine
     }
     const int nc = in <= 256 ? 1 : (in <= 512 ? 2 : 4);
-#define FFH_SKINNY(NCV, NOV) hipLaunchKernelGGL((linear_skinny_bwd_kernel<NCV, NOV>), dim3(grid), dim3(256), lds, as_stream(s), a)
+#define FFH_SKINNY(NCV, NOV)                                                                                                          \
+  do {                                                                                                                                \
+    if (bce) hipLaunchKernelGGL((linear_skinny_bwd_kernel<NCV, NOV, 1, true>), dim3(grid), dim3(256), lds, as_stream(s), a);          \
+    else hipLaunchKernelGGL((linear_skinny_bwd_kernel<NCV, NOV>), dim3(grid), dim3(256), lds, as_stream(s), a);                       \
+  } while (0)
     if (out == 1) { if (nc == 1) FFH_SKINNY(1, 1); else if (nc == 2) FFH_SKINNY(2, 1); else FFH_SKINNY(4, 1); }
     else if (out <= 4) { if (nc == 1) FFH_SKINNY(1, 4); else if (nc == 2) FFH_SKINNY(2, 4); else FFH_SKINNY(4, 4); }
     else if (in == 64) hipLaunchKernelGGL((linear_skinny_bwd_kernel<1, 16, 4>), dim3(grid), dim3(256), lds, as_stream(s), a);
     else if (in == 128) hipLaunchKernelGGL((linear_skinny_bwd_kernel<1, 16, 2>), dim3(grid), dim3(256), lds, as_stream(s), a);
-    else FFH_SKINNY(1, 16);
+    else hipLaunchKernelGGL((linear_skinny_bwd_kernel<1, 16>), dim3(grid), dim3(256), lds, as_stream(s), a);      // (a folded loss step is out <= 4: no BCE form)
 #undef FFH_SKINNY
     FFH_LAUNCH_CHECK(c, "linear_skinny_bwd_kernel");
     ffh_route_add(c, "linear_bwd|skinny");
@@ -1964,6 +1983,24 @@ int ffh_linear_bwd_mse(ffh_ctx* c, const float* x, int64_t ldx, float* dx, int64
   c->colsum_used = 0;
   const int rc = linear_bwd_impl(c, x, ldx, dx, lddx, y, ldy, dy, lddy, w, dw, db, in, out, batch, act, flags, s, nullptr, label, scale, perf, metrics_flags);
   c->colsum_dst = nullptr;             // ffh_linear_bwd_set_dx_colsum: one call only, taken or not (this launch never takes it)
+  return rc;
+}
+
+// include/ff_hip_ctr.h: the same launch with the binary cross-entropy loss step
+int ffh_linear_bwd_bce(ffh_ctx* c, const float* x, int64_t ldx, float* dx, int64_t lddx, const float* y, int64_t ldy,
+                       float* dy, int64_t lddy, const float* w, float* dw, float* db,
+                       int in, int out, int64_t batch, int act, int flags,
+                       const float* label, float scale, ffh_perf_metrics* perf, float* bce_sum, int metrics_flags, ffh_stream s) {
+  FFH_REQUIRE(c, label && perf, "linear_bwd_bce: label and perf are required");
+  FFH_REQUIRE(c, act == FFH_AC_MODE_SIGMOID, "linear_bwd_bce: the loss is defined on a sigmoid output");
+  FFH_REQUIRE(c, bce_sum || !(metrics_flags & FFH_METRIC_BCE), "linear_bwd_bce: FFH_METRIC_BCE needs bce_sum");
+  if (flags & (FFH_LINEAR_ONLY_DX | FFH_LINEAR_ONLY_DW | FFH_LINEAR_DY_PREMASKED)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "linear_bwd_bce: split / premasked forms");
+  if (ldy != out || lddy != out) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "linear_bwd_bce: y and dy must be contiguous [batch][out_dim]");
+  if (batch == 0) return FFH_OK;
+  ffh_route_clear(c);
+  c->colsum_used = 0;
+  const int rc = linear_bwd_impl(c, x, ldx, dx, lddx, y, ldy, dy, lddy, w, dw, db, in, out, batch, act, flags, s, nullptr, label, scale, perf, metrics_flags, bce_sum, true);
+  c->colsum_dst = nullptr;
   return rc;
 }
 

@@ -24,7 +24,10 @@ DT_BF16 = 140                  # this build: bf16 embedding tables (--embedding-
 ROUND_STOCHASTIC, ROUND_NEAREST = 0, 1   # --embedding-rounding (include/ffh_bf16.h)
 LOSS_MSE_AVG, LOSS_MSE_SUM = 52, 53
 METRICS_ACCURACY, METRICS_MSE = 1001, 1008
-COMP_MODE_TRAINING = 70
+COMP_MODE_TRAINING, COMP_MODE_INFERENCE = 70, 71
+# this build: binary cross-entropy on the final sigmoid and held-out evaluation (include/ff_hip_ctr.h), outside the reference's values
+LOSS_BCE = 150
+METRICS_BCE, METRICS_AUC = 2001, 2002
 
 
 class _H(C.Structure):
@@ -35,6 +38,12 @@ class PerfMetrics(C.Structure):
     _fields_ = [("train_all", C.c_int), ("train_correct", C.c_int), ("cce_loss", C.c_float),
                 ("sparse_cce_loss", C.c_float), ("mse_loss", C.c_float), ("rmse_loss", C.c_float),
                 ("mae_loss", C.c_float)]
+
+
+class EvalMetricsC(C.Structure):
+    """struct flexflow_eval_metrics_t"""
+    _fields_ = [("samples", C.c_uint64), ("positives", C.c_uint64), ("correct", C.c_uint64), ("nan_predictions", C.c_uint64),
+                ("logloss_sum", C.c_double), ("auc", C.c_double)]
 
 
 ALLTOALL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.c_void_p, C.POINTER(C.c_int64), C.c_void_p)
@@ -121,6 +130,11 @@ def lib() -> C.CDLL:
         "flexflow_dlrm_warmup": (None, [H]), "flexflow_dlrm_train_steps": (None, [H, I, B]),
         "flexflow_dlrm_run_epochs": (D, [H]), "flexflow_dlrm_time_kernel": (F, [H, I, I]),
         "flexflow_dlrm_probe_step": (None, [H, I, C.POINTER(F), I]),
+        "flexflow_perf_metrics_get_bce_loss": (F, [H]), "flexflow_model_eval_batch": (None, [H]),
+        "flexflow_model_reset_eval_metrics": (None, [H]),
+        "flexflow_model_get_eval_metrics": (None, [H, C.POINTER(EvalMetricsC), P, P]),
+        "flexflow_auc_bins": (I, []), "flexflow_auc_from_histograms": (D, [P, P, I]),
+        "flexflow_dlrm_evaluate": (D, [H, I, C.POINTER(EvalMetricsC)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -128,6 +142,22 @@ def lib() -> C.CDLL:
         fn.argtypes = args
     _lib = L
     return L
+
+
+def _eval_dict(e: EvalMetricsC) -> dict:
+    n = int(e.samples)
+    return {"samples": n, "positives": int(e.positives), "correct": int(e.correct), "nan_predictions": int(e.nan_predictions),
+            "logloss_sum": float(e.logloss_sum), "logloss": float(e.logloss_sum) / n if n else 0.0,
+            "accuracy": int(e.correct) / n if n else 0.0, "auc": float(e.auc)}
+
+
+def auc_from_histograms(hist_pos, hist_neg) -> float:
+    """ffh_auc_from_histograms (include/ff_hip_ctr.h) on two uint64 numpy arrays of equal length; NaN without positives or negatives."""
+    import numpy as np
+    hp, hn = np.ascontiguousarray(hist_pos, dtype=np.uint64), np.ascontiguousarray(hist_neg, dtype=np.uint64)
+    if hp.shape != hn.shape or hp.ndim != 1:
+        raise ValueError("auc_from_histograms: two 1-D arrays of equal length")
+    return float(lib().flexflow_auc_from_histograms(hp.ctypes.data, hn.ctypes.data, hp.shape[0]))
 
 
 def _argv(args):
@@ -367,6 +397,29 @@ class FFModel:
         lib().flexflow_model_get_perf_metrics(self.h, C.byref(p))
         return p
 
+    def bce_loss(self) -> float:
+        """log-loss sum of the training batches since reset_metrics() (LOSS_BCE)"""
+        return float(lib().flexflow_perf_metrics_get_bce_loss(self.h))
+
+    # -- held-out evaluation (include/ff_hip_ctr.h) -----------------------------------------------
+    def eval_batch(self): lib().flexflow_model_eval_batch(self.h)
+    def reset_eval_metrics(self): lib().flexflow_model_reset_eval_metrics(self.h)
+
+    def eval_metrics(self, histograms=False) -> dict:
+        """Global figures of the eval_batch() calls since reset_eval_metrics(): samples, positives, correct, nan_predictions, logloss_sum,
+        logloss, accuracy, auc; with histograms=True also hist_pos / hist_neg (uint64 numpy arrays, flexflow_auc_bins() bins)."""
+        e = EvalMetricsC()
+        hp = hn = None
+        if histograms:
+            import numpy as np
+            k = lib().flexflow_auc_bins()
+            hp, hn = np.zeros(k, dtype=np.uint64), np.zeros(k, dtype=np.uint64)
+        lib().flexflow_model_get_eval_metrics(self.h, C.byref(e), hp.ctypes.data if histograms else None, hn.ctypes.data if histograms else None)
+        out = _eval_dict(e)
+        if histograms:
+            out["hist_pos"], out["hist_neg"] = hp, hn
+        return out
+
     def close(self):
         if self._owned and self.h is not None:
             lib().flexflow_model_destroy(self.h)
@@ -389,6 +442,12 @@ class DLRM:
     def warmup(self): lib().flexflow_dlrm_warmup(self.h)
     def train_steps(self, n, trace=True): lib().flexflow_dlrm_train_steps(self.h, n, trace)
     def run_epochs(self) -> float: return lib().flexflow_dlrm_run_epochs(self.h)
+    def evaluate(self, epoch=0) -> dict:
+        """--eval-batches: the held-out batches through eval_batch(), as the driver does after an epoch (prints its EVAL line)"""
+        e = EvalMetricsC()
+        secs = lib().flexflow_dlrm_evaluate(self.h, epoch, C.byref(e))
+        return dict(_eval_dict(e), seconds=float(secs))
+
     def time_kernel(self, which, iters) -> float: return lib().flexflow_dlrm_time_kernel(self.h, which, iters)
 
     PROBE_PAIRS = ("gather", "table_update", "alltoall_fwd", "alltoall_bwd", "allreduce", "join_wait", "allreduce_wait") + tuple(f"bucket{i}" for i in range(8))

@@ -69,6 +69,23 @@ const KernelApi* load_kernel_api(const std::string& path_in) {
     }
     api->bf16 = b;
   }
+  // the CTR extension (include/ff_hip_ctr.h): the same rule
+  if (dlsym(h, "ffh_ctr_abi_version")) {
+    KernelApiCtr* b = new KernelApiCtr();
+#define FFH_LOAD(name)                                                        \
+  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
+  if (!b->name) {                                                             \
+    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_ctr.h: %s is missing\n", path.c_str(), #name);   \
+    abort();                                                                  \
+  }
+    FFH_CTR_API_LIST(FFH_LOAD)
+#undef FFH_LOAD
+    if (b->ffh_ctr_abi_version() != FFH_CTR_ABI_VERSION) {
+      fprintf(stderr, "FATAL: %s has CTR ABI version %d, expected %d\n", path.c_str(), b->ffh_ctr_abi_version(), FFH_CTR_ABI_VERSION);
+      abort();
+    }
+    api->ctr = b;
+  }
   if (path_in.empty() && g_env_override)
     fprintf(stderr, "[DLRM] FFH_BACKEND_LIB: kernel library %s (%s)\n", path.c_str(), api->ffh_backend_name());
   cache[path] = api;

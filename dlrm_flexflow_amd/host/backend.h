@@ -5,6 +5,7 @@
 #include <string>
 #include "../../include/ff_hip.h"
 #include "../../include/ff_hip_bf16.h"
+#include "../../include/ff_hip_ctr.h"
 
 // The optional bf16-table extension (include/ff_hip_bf16.h): all of its list or none of it.
 struct KernelApiBf16 {
@@ -13,11 +14,19 @@ struct KernelApiBf16 {
 #undef FFH_DECL
 };
 
+// The optional CTR extension (include/ff_hip_ctr.h: binary cross-entropy, evaluation histograms): all of its list or none of it.
+struct KernelApiCtr {
+#define FFH_DECL(name) decltype(&::name) name;
+  FFH_CTR_API_LIST(FFH_DECL)
+#undef FFH_DECL
+};
+
 struct KernelApi {
 #define FFH_DECL(name) decltype(&::name) name;
   FFH_API_LIST(FFH_DECL)
 #undef FFH_DECL
   const KernelApiBf16* bf16 = nullptr;   // null: the library does not export the extension (e.g. the CPU oracle)
+  const KernelApiCtr* ctr = nullptr;     // likewise for include/ff_hip_ctr.h
   void* handle;
   std::string path;
   bool overridden = false;      // chosen by --backend or $FFH_BACKEND_LIB rather than the product default: the driver says so on its THROUGHPUT line

@@ -118,26 +118,43 @@ Tensor interact_features(FFModel* model, const Tensor& x, const std::vector<Tens
   abort();
 }
 
+static void check_eval_batches(int eval_batches, int nb);
+
 // =============================================================================================
 DataLoader::DataLoader(FFModel& ff, const DLRMConfig& dlrm, const std::vector<Tensor>& sparse_inputs, Tensor dense_input, Tensor label)
     : num_samples(0), next_index(0), batch_sparse_inputs(sparse_inputs), batch_dense_input(dense_input), batch_label(label),
       full_dense(nullptr), full_label(nullptr), model(&ff) {
+  num_train = 0;
   bag = dlrm.embedding_bag_size;
   dense_dim = dense_input.adim[0];
   full_sparse.assign(sparse_inputs.size(), nullptr);
   if (dlrm.dataset_path != "") load_hdf5(ff, dlrm);
   else generate_random(ff, dlrm);
   ff.check(ff.api->ffh_stream_sync(ff.ctx, ff.stream), "dataset sync");
+  check_eval_batches(ff.config.eval_batches, num_samples / ff.config.batchSize);
+  num_train = num_samples - ff.config.eval_batches * ff.config.batchSize;
+}
+
+// samples of the synthetic data set [ref: dlrm.cc:272-276], whole batches
+static int random_num_samples(const FFConfig& cfg, const DLRMConfig& dlrm, int world_size) {
+  int n = dlrm.data_size > 0 ? dlrm.data_size : 256 * 4 * std::max(1, world_size) * cfg.numNodes;
+  const int B = cfg.batchSize;
+  if (n < B) n = B;
+  return n / B * B;
+}
+
+static void check_eval_batches(int eval_batches, int nb) {
+  if (eval_batches < nb) return;
+  fprintf(stderr, "FATAL: --eval-batches %d: only %d batches were loaded, and at least one must be left to train on (load more with --data-size, or hold out fewer)\n",
+          eval_batches, nb);
+  abort();
 }
 
 void DataLoader::generate_random(FFModel& ff, const DLRMConfig& dlrm) {
   const bool chatty = ff.world_size <= 1 || ff.rank == 0;
   if (chatty) printf("[DLRM] Use random dataset...\n");
-  if (dlrm.data_size > 0) num_samples = dlrm.data_size;
-  else num_samples = 256 * 4 * std::max(1, ff.world_size) * ff.config.numNodes;   // [ref: dlrm.cc:272-276]
+  num_samples = random_num_samples(ff.config, dlrm, ff.world_size);
   const int B = ff.config.batchSize;
-  if (num_samples < B) num_samples = B;
-  num_samples = num_samples / B * B;
   if (chatty) printf("[DLRM] Number of random samples = %d\n", num_samples);
   const uint64_t s0 = ff.config.seed * 1000003ULL;
   const int nb = num_samples / B;
@@ -157,6 +174,29 @@ void DataLoader::generate_random(FFModel& ff, const DLRMConfig& dlrm) {
     const int64_t n0 = (int64_t)k * B + (int64_t)ff.rank * Bl;
     ff.check(ff.api->ffh_gen_uniform01(ff.ctx, full_dense + (int64_t)k * Bl * dense_dim, Bl * dense_dim, s0 + 5, n0 * dense_dim, ff.stream), "gen dense");
     ff.check(ff.api->ffh_gen_bernoulli(ff.ctx, full_label + (int64_t)k * Bl, Bl, s0 + 7, n0, ff.stream), "gen label");
+  }
+  if (ff.config.synthetic_labels == 1) {
+    // --synthetic-labels logistic: label ~ Bernoulli(sigmoid(4 * sum_j a_j (x_j - 1/2))) with hidden weights a_j in [-1, 1) fixed by the hash
+    // (not by --seed: every seed draws other samples from the SAME model), the coin of sample n the hash stream the Bernoulli labels use.
+    // On the host, from the dense features read back: same code for every kernel library.
+    const size_t nd = (size_t)nb * Bl * dense_dim, nl = (size_t)nb * Bl;
+    std::vector<float> xd(nd), lab(nl), a((size_t)dense_dim);
+    for (int j = 0; j < dense_dim; j++) a[j] = ffh_uniform(ffh_hash(0x10615C1CULL, (uint64_t)j), -1.0f, 1.0f);
+    ff.check(ff.api->ffh_stream_sync(ff.ctx, ff.stream), "synthetic labels");
+    ff.check(ff.api->ffh_memcpy_d2h(ff.ctx, xd.data(), full_dense, nd * sizeof(float), ff.stream), "synthetic labels d2h");
+    ff.check(ff.api->ffh_stream_sync(ff.ctx, ff.stream), "synthetic labels");
+    for (int k = 0; k < nb; k++)
+      for (int64_t i = 0; i < Bl; i++) {
+        const size_t r = (size_t)k * Bl + (size_t)i;
+        double z = 0.0;
+        for (int j = 0; j < dense_dim; j++) z += (double)a[j] * ((double)xd[r * dense_dim + j] - 0.5);
+        const double p = 1.0 / (1.0 + std::exp(-4.0 * z));
+        const uint64_t n = (uint64_t)k * B + (uint64_t)ff.rank * Bl + (uint64_t)i;
+        lab[r] = (double)ffh_u24(ffh_hash(s0 + 7, n)) < p ? 1.0f : 0.0f;
+      }
+    ff.check(ff.api->ffh_memcpy_h2d(ff.ctx, full_label, lab.data(), nl * sizeof(float), ff.stream), "synthetic labels h2d");
+    ff.check(ff.api->ffh_stream_sync(ff.ctx, ff.stream), "synthetic labels");
+    if (chatty) printf("[DLRM] synthetic labels: logistic model of the %d dense features\n", dense_dim);
   }
 }
 
@@ -268,20 +308,25 @@ DataLoader::~DataLoader() {
 // [ref: examples/cpp/DLRM/dlrm.cc:482-585, dlrm.cu:19-122]: device-to-device copies on the compute stream
 void DataLoader::next_batch(FFModel& ff) {
   const int B = ff.config.batchSize;
-  if (next_index + B > num_samples) next_index = 0;
+  if (next_index + B > num_train) next_index = 0;
+  load_batch(ff, next_index / B);
+  next_index += B;
+}
+
+void DataLoader::load_batch(FFModel& ff, int k) {
+  const int B = ff.config.batchSize;
   const int64_t Bl = ff.local_batch;
-  const int k = next_index / B;
+  const int64_t first = (int64_t)k * B;          // first sample of batch k
   ff.order_input_writes_behind_update();       // eager steps: the last step's table update may still be reading the ids
   for (size_t t = 0; t < batch_sparse_inputs.size(); t++) {
     if (!full_sparse[t]) continue;
-    ff.check(ff.api->ffh_memcpy_d2d(ff.ctx, batch_sparse_inputs[t].impl->ptr, full_sparse[t] + (int64_t)next_index * bag,
+    ff.check(ff.api->ffh_memcpy_d2d(ff.ctx, batch_sparse_inputs[t].impl->ptr, full_sparse[t] + first * bag,
                                     (size_t)B * bag * sizeof(int64_t), ff.stream), "load sparse");
   }
   ff.check(ff.api->ffh_memcpy_d2d(ff.ctx, batch_dense_input.impl->ptr, full_dense + (int64_t)k * Bl * dense_dim,
                                   (size_t)Bl * dense_dim * sizeof(float), ff.stream), "load dense");
   ff.check(ff.api->ffh_memcpy_d2d(ff.ctx, batch_label.impl->ptr, full_label + (int64_t)k * Bl, (size_t)Bl * sizeof(float), ff.stream),
            "load label");
-  next_index += B;
   ff.inputs_dirty = true;
 }
 
@@ -344,7 +389,15 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
   std::vector<MetricsType> metrics;
   metrics.push_back(METRICS_ACCURACY);
   metrics.push_back(METRICS_MEAN_SQUARED_ERROR);
-  ff->compile(optimizer, LOSS_MEAN_SQUARED_ERROR_AVG_REDUCE, metrics);
+  const bool bce = ffconfig.driver_loss == LOSS_BINARY_CROSSENTROPY;
+  if (bce) metrics.push_back(METRICS_BINARY_CROSSENTROPY);
+  if (ffconfig.eval_batches > 0) metrics.push_back(METRICS_AUC);
+  if (ffconfig.eval_only && ffconfig.eval_batches <= 0) { fprintf(stderr, "FATAL: --eval-only needs --eval-batches N\n"); abort(); }
+  // (synthetic data: its size is known here, so a hold-out that leaves nothing to train on is refused before anything is allocated; a file: by the loader)
+  if (ffconfig.eval_batches > 0 && dlrm.dataset_path.empty())
+    check_eval_batches(ffconfig.eval_batches, random_num_samples(ffconfig, dlrm, std::max(1, ffconfig.comm.world_size)) / ffconfig.batchSize);
+  if (chatty) printf("[DLRM] loss: %s\n", bce ? "bce" : "mse");
+  ff->compile(optimizer, (LossType)ffconfig.driver_loss, metrics);
   if (chatty && ffconfig.embedding_dtype == DT_BF16) {
     // what --embedding-dtype bf16 did: data-parallel (replicated) tables live in the dense slab and stay fp32
     size_t bytes = 0;
@@ -383,11 +436,31 @@ void DLRMApp::warmup() {
   warmed_up = true;
 }
 
+double DLRMApp::evaluate(int epoch, EvalMetrics* out) {
+  ff->sync();
+  const double t0 = now_us();
+  const int B = ffconfig.batchSize, first = loader->num_train / B, nb = loader->num_samples / B;
+  ff->reset_eval_metrics();
+  for (int k = first; k < nb; k++) {
+    loader->load_batch(*ff, k);
+    ff->eval_batch();
+  }
+  EvalMetrics m = ff->get_eval_metrics();
+  loader->load_batch(*ff, 0);            // what the warm-up left in the inputs: a synthetic run trains on it without reloading
+  ff->sync();
+  const double secs = 1e-6 * (now_us() - t0);
+  if (ff->rank == 0)
+    printf("EVAL epoch %d: samples %llu logloss %.4f accuracy %.4f auc %.4f time %.4fs\n", epoch, (unsigned long long)m.samples, m.logloss(), m.accuracy(),
+           m.auc, secs);
+  if (out) *out = m;
+  return secs;
+}
+
 void DLRMApp::train_steps(int n, bool trace) {
   for (int it = 0; it < n; it++) {
     // random input: the batch loaded in the warm-up is reused; a dataset advances every iteration, outside the trace
     // [ref: examples/cpp/DLRM/dlrm.cc:167-175]
-    if (!dlrm.dataset_path.empty()) loader->next_batch(*ff);
+    if (!dlrm.dataset_path.empty() || ffconfig.synthetic_labels == 1) loader->next_batch(*ff);      // (learnable synthetic labels: iterated like a data set)
     if (trace) ff->begin_trace(111 /*trace_id*/);
     ff->forward();
     ff->zero_gradients();
@@ -398,7 +471,7 @@ void DLRMApp::train_steps(int n, bool trace) {
 }
 
 double DLRMApp::run_epochs() {
-  if (!warmed_up) warmup();
+  if (!warmed_up && !ffconfig.eval_only) warmup();      // (--eval-only: no training step at all)
   if (ff->config.trace_mode < 0) ff->config.trace_mode = 0;     // the driver's loop: a step is replayed only where the replay is not slower (FFConfig::trace_mode)
   const bool chatty = ff->rank == 0;
   ff->sync();   // issue_execution_fence + timing measurement
@@ -406,26 +479,30 @@ double DLRMApp::run_epochs() {
   if (chatty) {
     printf("[DLRM] Warmup finished...Start timer...\n");
     printf("[DLRM] Num. epochs = %d\n", ffconfig.epochs);
-    printf("[DLRM] Num. iterations/epoch = %d\n", loader->num_samples / ffconfig.batchSize);
+    printf("[DLRM] Num. iterations/epoch = %d\n", loader->num_train / ffconfig.batchSize);
     printf("parameters.size() = %lu\n", ff->parameters.size());
   }
+  double eval_secs = 0.0;                // evaluation is outside the timed region: its wall time is taken out again below
   const double ts_start = now_us();
-  for (int epoch = 0; epoch < ffconfig.epochs; epoch++) {
+  if (ffconfig.eval_only) eval_secs += evaluate(0);
+  for (int epoch = 0; epoch < ffconfig.epochs && !ffconfig.eval_only; epoch++) {
     loader->reset();
     ff->reset_metrics();
-    const int iterations = loader->num_samples / ffconfig.batchSize;
+    const int iterations = loader->num_train / ffconfig.batchSize;
     train_steps(iterations, epoch > 0 /* the reference traces from the second epoch on */);
+    if (ffconfig.eval_batches > 0) eval_secs += evaluate(epoch + 1);
   }
   ff->sync();
   if (ffconfig.comm.world_size > 1 && ffconfig.comm.barrier) ffconfig.comm.barrier(ffconfig.comm.user);
   const double ts_end = now_us();
-  const double run_time = 1e-6 * (ts_end - ts_start);
-  if (chatty) {
+  const double run_time = 1e-6 * (ts_end - ts_start) - eval_secs;
+  if (chatty && !ffconfig.eval_only) {      // (--eval-only trained nothing: no training metrics, no throughput)
     PerfMetrics pm = ff->get_perf_metrics();
     pm.print(ff->metrics_flags);
     // [ref: examples/cpp/DLRM/dlrm.cc:193-194] -- the reference's line as it is; a kernel library other than the product's own
     // (--backend / FFH_BACKEND_LIB: the CPU oracle in tests, an A/B build) is named on it, so a number can never be mistaken
-    printf("ELAPSED TIME = %.4fs, THROUGHPUT = %.2f samples/s", run_time, loader->num_samples * (double)ffconfig.epochs / run_time);
+    printf("ELAPSED TIME = %.4fs, THROUGHPUT = %.2f samples/s", run_time, loader->num_train * (double)ffconfig.epochs / run_time);
+    if (ffconfig.eval_batches > 0) printf("  [wall time minus %.4fs of evaluation]", eval_secs);
     if (ff->api->overridden) printf("  [kernel library: %s, %s]", ff->api->ffh_backend_name(), ff->api->path.c_str());
     printf("\n");
   }

@@ -35,10 +35,12 @@ class DataLoader {
  public:
   DataLoader(FFModel& ff, const DLRMConfig& dlrm, const std::vector<Tensor>& sparse_inputs, Tensor dense_input, Tensor label);
   ~DataLoader();
-  void next_batch(FFModel& ff);
+  void next_batch(FFModel& ff);                 // the next TRAINING batch (wraps at num_train)
+  void load_batch(FFModel& ff, int k);          // batch k of what was loaded into the model inputs; the training cursor does not move
   void shuffle() {}
   void reset() { next_index = 0; }
   int num_samples, next_index;
+  int num_train;                                // num_samples minus the held-out tail (--eval-batches)
 
  private:
   void generate_random(FFModel& ff, const DLRMConfig& dlrm);
@@ -67,6 +69,9 @@ struct DLRMApp {
   void warmup();                 // the reference's single warm-up iteration
   void train_steps(int n, bool trace);   // n x {forward, zero_gradients, backward, update}
   double run_epochs();           // the timed loop; returns elapsed seconds and prints the THROUGHPUT line
+  // --eval-batches: the held-out tail through FFModel::eval_batch(), one "EVAL epoch E: ..." line on rank 0; returns its wall time in seconds.
+  // The model inputs hold the training batch of the warm-up again afterwards (synthetic input is not reloaded per step).
+  double evaluate(int epoch, EvalMetrics* out = nullptr);
 };
 
 int dlrm_main(int argc, char** argv, const ffcomm* comm);

@@ -26,6 +26,7 @@
 
 #include "../../include/ff_hip.h"
 #include "../../include/ff_hip_bf16.h"
+#include "../../include/ff_hip_ctr.h"
 #include "ffcomm.h"
 
 // ---- enums: identical values to [ref: include/ffconst.h:4-57] -------------------------------
@@ -38,6 +39,7 @@ enum LossType {
   LOSS_SPARSE_CATEGORICAL_CROSSENTROPY = 51,
   LOSS_MEAN_SQUARED_ERROR_AVG_REDUCE = 52,
   LOSS_MEAN_SQUARED_ERROR_SUM_REDUCE = 53,
+  LOSS_BINARY_CROSSENTROPY = 150,   // this build's own (include/ff_hip_ctr.h; --loss bce), outside the reference's values: mean over the global batch
 };
 enum CompMode { COMP_MODE_TRAINING = 70, COMP_MODE_INFERENCE = 71 };
 enum ParameterSyncType { NONE = 80, PS = 81, NCCL = 82 };
@@ -48,6 +50,9 @@ enum MetricsType {
   METRICS_MEAN_SQUARED_ERROR = 1008,
   METRICS_ROOT_MEAN_SQUARED_ERROR = 1016,
   METRICS_MEAN_ABSOLUTE_ERROR = 1032,
+  METRICS_BINARY_CROSSENTROPY = 2001,   // this build's own (include/ff_hip_ctr.h): the log-loss of the training batches
+  METRICS_AUC = 2002,                   // a marker: the run will call eval_batch() / get_eval_metrics() (the AUC is never a training-batch figure).  compile() checks what
+                                        // evaluation needs (final sigmoid column, the CTR extension, held-out data in a training run) and allocates the device histograms
 };
 enum OperatorType { OP_INPUT, OP_LINEAR, OP_EMBEDDING, OP_CONCAT, OP_BATCHMATMUL, OP_TRANSPOSE, OP_RESHAPE, OP_FLAT, OP_TRIL, OP_DOT_INTERACTION };
 
@@ -140,6 +145,11 @@ class FFConfig {
   int64_t mlp_chain_max_weights;     // chains of at most this many weights in all (every CU streams all of them from L2: --mlp-chain-max-weights N)
   bool attach_events;          // hang ev_grad_ready on the producing kernel's completion instead of a record packet (A/B: --no-attach-event)
   bool timing_events;          // A/B: stream-ordering events created with timestamps, as before
+  int driver_loss;             // --loss mse | bce: the loss the DLRM driver and run_dlrm.py compile with (LossType; default the MSE mean)
+  int eval_batches;            // --eval-batches N: the last N loaded batches are held out of training and evaluated after every epoch (0: none)
+  int synthetic_labels;        // --synthetic-labels bernoulli (0, default: coin flips, the reference's) | logistic (1: drawn from a fixed hidden logistic model of the dense features,
+                               // so that a synthetic run has something to learn; its batches are then iterated like a data set's instead of reusing the warm-up batch)
+  bool eval_only;              // --eval-only: no training, one evaluation of the held-out batches
   bool fuse_loss;              // loss step + metrics inside the last layer's one-launch backward (A/B: --no-fused-loss)
   int64_t replicate_embedding_rows;   // world_size > 1: tables with at most this many rows are data-parallel (replicated) instead of owned by one rank (0: none)
   int64_t row_shard_rows;      // ... row-wise instead: partial bag sums + reduce-scatter (0: never; wins over column_shard_rows)
@@ -276,12 +286,24 @@ class AdamOptimizer : public Optimizer {
 };
 
 // ---------------------------------------------------------------------------------------------
+// What FFModel::get_eval_metrics() returns (include/ff_hip_ctr.h): NaN predictions are counted and left out of everything else.
+struct EvalMetrics {
+  uint64_t samples = 0, positives = 0, correct = 0, nan_predictions = 0;
+  double logloss_sum = 0.0;
+  double logloss() const { return samples ? logloss_sum / (double)samples : 0.0; }
+  double accuracy() const { return samples ? (double)correct / (double)samples : 0.0; }
+  double auc = 0.0;                         // NaN without a positive or without a negative sample
+  std::vector<uint64_t> hist_pos, hist_neg; // FFH_AUC_BINS each, on request
+};
+
+// ---------------------------------------------------------------------------------------------
 struct PerfMetrics {
   PerfMetrics();
   void update(const PerfMetrics& one);
   void print(int flags) const;       // the reference's "[Metrics] ..." line on stderr
   int train_all, train_correct;
   float cce_loss, sparse_cce_loss, mse_loss, rmse_loss, mae_loss;
+  float bce_loss;                    // METRICS_BINARY_CROSSENTROPY: log-loss sum of the training batches (this build's own)
   double start_time;
 };
 
@@ -508,6 +530,12 @@ class FFModel {
   void end_trace(int trace_id);
   void sync();                                   // issue_execution_fence + wait
   PerfMetrics get_perf_metrics();
+  // Held-out evaluation (include/ff_hip_ctr.h).  eval_batch(): the forward pass on the current inputs, then the evaluation metrics of
+  // this rank's rows; no backward, no table update, no optimizer, no all-reduce, the bf16 rounding counter does not move, and nothing a
+  // later training step relies on changes (no early sort is issued; a captured step replays as before).  Not inside begin/end_trace.
+  void eval_batch();
+  void reset_eval_metrics();
+  EvalMetrics get_eval_metrics(bool with_histograms = false);   // global figures: counts and histograms summed over the ranks exactly
   // seeds of the initializers: a private counter-hash sequence from config.seed (the reference draws them from the
   // unseeded global std::rand(), [ref: examples/cpp/DLRM/dlrm.cc:32,34,45] -- any library calling rand() would shift it)
   Initializer* own(Initializer* init) { owned_initializers.push_back(init); return init; }   // deleted with the model (the reference leaks these)
@@ -562,6 +590,7 @@ class FFModel {
   void issue_one_bucket(size_t k, bool wait_main);      // wait_main: also behind what the compute stream holds now
   int  big_dw_chunks_now() const;                       // row blocks the biggest layer's weight gradient is cut into this step (1: not cut)
   mutable int64_t n_bucket_allreduces = 0;
+  int64_t n_fused_loss_calls = 0;      // backward() calls whose loss step rode the final layer's one-launch backward (either loss)
   mutable int64_t n_chain_fwd_calls = 0, n_chain_bwd_calls = 0;   // successful ffh_mlp_chain_fwd / _bwd calls (tests: flexflow_model_get_counter)
   bool mlp_chain_usable(int64_t rows, bool fwd) const;      // the chain launches are allowed in this mode / at this batch
   int run_chain_fwd(const Linear* lowest) const;  // FFH_OK, or FFH_ERR_UNSUPPORTED with nothing launched
@@ -640,6 +669,10 @@ class FFModel {
   void* workspace;  size_t workspace_bytes;
   void* repl_workspace;  size_t repl_workspace_bytes;          // scratch of the data-parallel tables' gradient (own buffer: it runs beside the side-stream update)
   ffh_perf_metrics* d_perf;
+  float* d_bce_sum;            // the training batches' log-loss sum (LOSS_BINARY_CROSSENTROPY / METRICS_BINARY_CROSSENTROPY)
+  ffh_ctr_eval* d_eval;        // eval_batch(): allocated by the first call
+  bool want_eval;              // METRICS_AUC was compiled in
+  bool evaluating;             // inside eval_batch(): forward() issues no early sort
   // one unit of the exchange: a whole table (table-wise) or a column block of a giant table (column-wise)
   struct EmbShard { Embedding* e; int owner; int col0; int cols; int64_t off; };
   std::vector<EmbShard> shards;

@@ -1,4 +1,5 @@
 // ffmodel_c.cc -- see ffmodel_c.h
+#include <cstring>
 #include "ffmodel_c.h"
 #include <string>
 
@@ -134,6 +135,7 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   const std::string n(name ? name : "");
   if (n == "mlp_chain_fwd_calls") return M(m)->n_chain_fwd_calls;
   if (n == "mlp_chain_bwd_calls") return M(m)->n_chain_bwd_calls;
+  if (n == "fused_loss_calls") return M(m)->n_fused_loss_calls;
   if (n == "allreduce_bucket_calls") return M(m)->n_bucket_allreduces;
   if (n == "allreduce_buckets") return (int64_t)M(m)->grad_buckets.size();
   if (n.rfind("allreduce_bucket_floats_", 0) == 0) {      // floats of bucket k, in issue order
@@ -181,6 +183,27 @@ int flexflow_dlrm_get_num_tables(flexflow_dlrm_t h) { return (int)A(h)->sparse_i
 flexflow_tensor_t flexflow_dlrm_get_sparse_input(flexflow_dlrm_t h, int t) { return wrap(A(h)->sparse_inputs.at(t)); }
 flexflow_tensor_t flexflow_dlrm_get_dense_input(flexflow_dlrm_t h) { return wrap(A(h)->dense_input); }
 void flexflow_dlrm_warmup(flexflow_dlrm_t h) { A(h)->warmup(); }
+static void to_c(const EvalMetrics& m, flexflow_eval_metrics_t* out) {
+  out->samples = m.samples; out->positives = m.positives; out->correct = m.correct; out->nan_predictions = m.nan_predictions;
+  out->logloss_sum = m.logloss_sum; out->auc = m.auc;
+}
+double flexflow_dlrm_evaluate(flexflow_dlrm_t h, int epoch, flexflow_eval_metrics_t* out) {
+  EvalMetrics m;
+  const double secs = A(h)->evaluate(epoch, &m);
+  if (out) to_c(m, out);
+  return secs;
+}
+float flexflow_perf_metrics_get_bce_loss(flexflow_model_t m) { return M(m)->get_perf_metrics().bce_loss; }
+void flexflow_model_eval_batch(flexflow_model_t m) { M(m)->eval_batch(); }
+void flexflow_model_reset_eval_metrics(flexflow_model_t m) { M(m)->reset_eval_metrics(); }
+void flexflow_model_get_eval_metrics(flexflow_model_t m, flexflow_eval_metrics_t* out, uint64_t* hist_pos, uint64_t* hist_neg) {
+  const EvalMetrics e = M(m)->get_eval_metrics(hist_pos || hist_neg);
+  to_c(e, out);
+  if (hist_pos) memcpy(hist_pos, e.hist_pos.data(), sizeof(uint64_t) * FFH_AUC_BINS);
+  if (hist_neg) memcpy(hist_neg, e.hist_neg.data(), sizeof(uint64_t) * FFH_AUC_BINS);
+}
+int flexflow_auc_bins(void) { return FFH_AUC_BINS; }
+double flexflow_auc_from_histograms(const uint64_t* hist_pos, const uint64_t* hist_neg, int bins) { return ffh_auc_from_histograms(hist_pos, hist_neg, bins); }
 void flexflow_dlrm_train_steps(flexflow_dlrm_t h, int n, bool trace) { A(h)->train_steps(n, trace); }
 double flexflow_dlrm_run_epochs(flexflow_dlrm_t h) { return A(h)->run_epochs(); }
 

@@ -26,6 +26,17 @@ typedef struct flexflow_perf_metrics_t {
   float cce_loss, sparse_cce_loss, mse_loss, rmse_loss, mae_loss;
 } flexflow_perf_metrics_t;
 
+/* Binary cross-entropy and held-out evaluation (include/ff_hip_ctr.h; this build's own, the reference has neither).
+ * Constants for flexflow_model_compile: loss 150 (LOSS_BINARY_CROSSENTROPY, mean over the global batch; the final layer must be a dense
+ * layer with sigmoid activation and one output column), metrics 2001 (METRICS_BINARY_CROSSENTROPY) and 2002 (METRICS_AUC). */
+#define FLEXFLOW_LOSS_BINARY_CROSSENTROPY 150
+#define FLEXFLOW_METRICS_BINARY_CROSSENTROPY 2001
+#define FLEXFLOW_METRICS_AUC 2002
+typedef struct flexflow_eval_metrics_t {
+  uint64_t samples, positives, correct, nan_predictions;   /* global counts; NaN predictions are left out of everything else */
+  double logloss_sum, auc;                                  /* auc: NaN without a positive or without a negative sample */
+} flexflow_eval_metrics_t;
+
 /* FFConfig */
 flexflow_config_t flexflow_config_create(void);
 void flexflow_config_destroy(flexflow_config_t);
@@ -80,6 +91,13 @@ void flexflow_model_begin_trace(flexflow_model_t, int trace_id);
 void flexflow_model_end_trace(flexflow_model_t, int trace_id);
 void flexflow_model_sync(flexflow_model_t);
 void flexflow_model_get_perf_metrics(flexflow_model_t, flexflow_perf_metrics_t* out);
+float flexflow_perf_metrics_get_bce_loss(flexflow_model_t);   /* log-loss sum of the training batches since reset_metrics (synchronises) */
+void flexflow_model_eval_batch(flexflow_model_t);             /* forward pass on the current inputs + evaluation metrics; no gradient, no update */
+void flexflow_model_reset_eval_metrics(flexflow_model_t);
+/* hist_pos / hist_neg: NULL, or flexflow_auc_bins() counters each (the raw histograms of the predictions, labels >= 0.5 / the rest) */
+void flexflow_model_get_eval_metrics(flexflow_model_t, flexflow_eval_metrics_t* out, uint64_t* hist_pos, uint64_t* hist_neg);
+int  flexflow_auc_bins(void);
+double flexflow_auc_from_histograms(const uint64_t* hist_pos, const uint64_t* hist_neg, int bins);   /* ffh_auc_from_histograms */
 flexflow_tensor_t flexflow_model_get_label_tensor(flexflow_model_t);
 int  flexflow_model_get_num_layers(flexflow_model_t);
 const char* flexflow_model_get_layer_name(flexflow_model_t, int layer);
@@ -92,7 +110,7 @@ const char* flexflow_model_get_backend_name(flexflow_model_t);   /* ffh_backend_
 const char* flexflow_model_get_backend_path(flexflow_model_t);   /* ... and the file it was loaded from */
 void flexflow_model_set_trace_mode(flexflow_model_t, int mode);   /* 0: replay a trace only where that is not slower than launching it (decided on its first calls); 1: always replay */
 int  flexflow_model_trace_replays(flexflow_model_t, int trace_id);   /* 0 once the adaptive mode has settled on eager launches for this trace */
-int64_t flexflow_model_get_counter(flexflow_model_t, const char* name);   /* diagnostics for tests: "mlp_chain_fwd_calls", "mlp_chain_bwd_calls",
+int64_t flexflow_model_get_counter(flexflow_model_t, const char* name);   /* diagnostics for tests: "mlp_chain_fwd_calls", "mlp_chain_bwd_calls", "fused_loss_calls",
                                                                             "bf16_updates" (the bf16 tables' update counter, synchronises); -1: unknown */
 
 /* Tensor / Parameter host<->device [ref: flexflow_parameter_set_weights_float, python/flexflow_c.h:498-546] */
@@ -125,6 +143,8 @@ flexflow_tensor_t flexflow_dlrm_get_dense_input(flexflow_dlrm_t);
 void flexflow_dlrm_warmup(flexflow_dlrm_t);
 void flexflow_dlrm_train_steps(flexflow_dlrm_t, int steps, bool trace);
 double flexflow_dlrm_run_epochs(flexflow_dlrm_t);
+/* --eval-batches: evaluates the held-out batches as the driver does after an epoch (prints its EVAL line on rank 0); returns the wall time */
+double flexflow_dlrm_evaluate(flexflow_dlrm_t, int epoch, flexflow_eval_metrics_t* out);
 /* average device time (ms) of `iters` back-to-back launches, HIP events on the launch stream:
  * which = 0 embedding gather (all owned tables, one launch), 1 fused embedding backward + SGD,
  *         2 whole training step (forward, zero_gradients, backward, update; traced if enabled) */

@@ -249,12 +249,12 @@ void GlorotUniform::init(const FFModel* ff, const Parameter* p) {
 // PerfMetrics [ref: src/metrics_functions/metrics_functions.cc:20-80]
 // =============================================================================================
 PerfMetrics::PerfMetrics()
-    : train_all(0), train_correct(0), cce_loss(0), sparse_cce_loss(0), mse_loss(0), rmse_loss(0), mae_loss(0) {
+    : train_all(0), train_correct(0), cce_loss(0), sparse_cce_loss(0), mse_loss(0), rmse_loss(0), mae_loss(0), bce_loss(0) {
   start_time = now_us();
 }
 void PerfMetrics::update(const PerfMetrics& o) {
   train_all += o.train_all; train_correct += o.train_correct; cce_loss += o.cce_loss;
-  sparse_cce_loss += o.sparse_cce_loss; mse_loss += o.mse_loss; rmse_loss += o.rmse_loss; mae_loss += o.mae_loss;
+  sparse_cce_loss += o.sparse_cce_loss; mse_loss += o.mse_loss; rmse_loss += o.rmse_loss; mae_loss += o.mae_loss; bce_loss += o.bce_loss;
 }
 void PerfMetrics::print(int flags) const {
   std::string out = "[Metrics]";
@@ -265,6 +265,8 @@ void PerfMetrics::print(int flags) const {
   if (flags & 2) out += " mean_squared_error: " + std::to_string(train_all ? mse_loss / train_all : 0.0f);
   if (flags & 4) out += " root_mean_squared_error: " + std::to_string(train_all ? rmse_loss / train_all : 0.0f);
   if (flags & 8) out += " mean_absolute_error: " + std::to_string(train_all ? mae_loss / train_all : 0.0f);
+  // (flag 16, FFH_METRIC_BCE: the loss needs one output column, where accuracy counts every sample twice in train_all -- the reference's rule)
+  if (flags & 16) out += " binary_crossentropy: " + std::to_string(train_all ? bce_loss / (train_all / ((flags & 1) ? 2 : 1)) : 0.0f);
   fprintf(stderr, "%s\n", out.c_str());
 }
 
@@ -327,7 +329,7 @@ FFModel::FFModel(FFConfig& _config)
       metrics_flags(0), seq_length(-1), api(nullptr), ctx(nullptr), stream(nullptr), side_stream(nullptr),
       ev_fork(nullptr), ev_join(nullptr), ev_grad_ready(nullptr), ev_update_done(nullptr), compiled(false),
       emb_forward_issued(false), emb_forward_joined(false), emb_update_pending(false), emb_sorted_early(false), mlp_weights(nullptr), mlp_grads(nullptr), mlp_count(0),
-      act_slab(nullptr), act_grad_slab(nullptr), act_grad_bytes(0), workspace(nullptr), workspace_bytes(0), repl_workspace(nullptr), repl_workspace_bytes(0), d_perf(nullptr),
+      act_slab(nullptr), act_grad_slab(nullptr), act_grad_bytes(0), workspace(nullptr), workspace_bytes(0), repl_workspace(nullptr), repl_workspace_bytes(0), d_perf(nullptr), d_bce_sum(nullptr), d_eval(nullptr), want_eval(false), evaluating(false),
       xsend(nullptr), xrecv(nullptr), gsend(nullptr), grecv(nullptr), capturing_trace(-1), replaying_trace(-1), inputs_dirty(true), fork_recorded(false) {
   seed_counter = 0;
   dw_stream = nullptr; ev_dw_done = nullptr; big_dw_layer = -1; need_zero_act_grads = true; need_zero_gsend = true; dw_forked = false; mlp_grads_clean = false; dw_worker = side_worker = nullptr;
@@ -390,7 +392,7 @@ FFModel::~FFModel() {
     delete t;
   }
   for (void* p : {w_twin, act_twin, grad_twin, (void*)ar_scratch}) if (p) api->ffh_free(ctx, p);
-  for (void* p : {(void*)mlp_weights, (void*)mlp_grads, (void*)act_slab, (void*)act_grad_slab, workspace, repl_workspace, (void*)d_perf, (void*)xsend,
+  for (void* p : {(void*)mlp_weights, (void*)mlp_grads, (void*)act_slab, (void*)act_grad_slab, workspace, repl_workspace, (void*)d_perf, (void*)d_bce_sum, (void*)d_eval, (void*)xsend,
                   (void*)xrecv, (void*)gsend, (void*)grecv})
     if (p) api->ffh_free(ctx, p);
   for (Embedding* e : embeddings)

@@ -129,11 +129,15 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
   optimizer = _optimizer;
   loss_type = _loss_type;
   config.computationMode = comp_mode;
-  if (loss_type != LOSS_MEAN_SQUARED_ERROR_AVG_REDUCE && loss_type != LOSS_MEAN_SQUARED_ERROR_SUM_REDUCE)
-    die("loss type %d is not on the DLRM path (only the two MSE losses)", (int)loss_type);
+  const bool bce = loss_type == LOSS_BINARY_CROSSENTROPY;
+  if (loss_type != LOSS_MEAN_SQUARED_ERROR_AVG_REDUCE && loss_type != LOSS_MEAN_SQUARED_ERROR_SUM_REDUCE && !bce)
+    die("loss type %d is not on the DLRM path (the two MSE losses and LOSS_BINARY_CROSSENTROPY)", (int)loss_type);
   metrics_flags = 0;
+  bool want_auc = false;
   for (MetricsType m : metrics) {
     switch (m) {
+      case METRICS_BINARY_CROSSENTROPY: metrics_flags |= FFH_METRIC_BCE; break;
+      case METRICS_AUC: want_auc = true; break;
       case METRICS_ACCURACY: metrics_flags |= 1; break;
       case METRICS_MEAN_SQUARED_ERROR: metrics_flags |= 2; break;
       case METRICS_ROOT_MEAN_SQUARED_ERROR: metrics_flags |= 4; break;
@@ -141,6 +145,23 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
       default: die("metrics type %d is not on the DLRM path", (int)m);
     }
   }
+  // binary cross-entropy and evaluation (include/ff_hip_ctr.h): refused here, before anything is allocated or launched
+  if (bce || want_auc || (metrics_flags & FFH_METRIC_BCE)) {
+    const char* what = bce ? "--loss bce" : (want_auc ? "METRICS_AUC" : "METRICS_BINARY_CROSSENTROPY");
+    Linear* last = dynamic_cast<Linear*>(layers.back());
+    if (!last || last->activation != AC_MODE_SIGMOID || last->out_channels != 1)
+      die("%s: the final operator must be a Linear with sigmoid activation and one output column (the loss is defined on a probability): "
+          "set --sigmoid-top to the last layer of --arch-mlp-top, or use --loss mse", what);
+    if (!api->ctr)
+      die("%s: %s (%s) is a kernel library without the CTR extension (include/ff_hip_ctr.h); use --loss mse", what, api->path.c_str(),
+          api->ffh_backend_name());
+    if ((metrics_flags & FFH_METRIC_BCE) && !bce) die("METRICS_BINARY_CROSSENTROPY is accumulated by the loss step of --loss bce: compile with LOSS_BINARY_CROSSENTROPY");
+    if (want_auc && comp_mode == COMP_MODE_TRAINING && config.eval_batches <= 0)
+      die("METRICS_AUC in a training compile() needs held-out data to evaluate: set --eval-batches N (or compile with COMP_MODE_INFERENCE)");
+    // dz of the loss step is the gradient at the pre-activation: the final layer never applies its sigmoid derivative
+    if (bce) last->dy_premasked = true;
+  }
+  want_eval = want_auc;
   for (Op* op : layers) {
     op->create_output_and_partition(*this);
     op->create_weights(*this);
@@ -784,6 +805,11 @@ void FFModel::allocate() {
   for (ffh_event& e : layer_events) check(api->ffh_event_create(ctx, &e), "event create");
   d_perf = (ffh_perf_metrics*)dmalloc(sizeof(ffh_perf_metrics));
   check(api->ffh_zero(ctx, d_perf, sizeof(ffh_perf_metrics), stream), "zero");
+  if (want_eval) reset_eval_metrics();      // METRICS_AUC: the device histograms exist from here on
+  if (loss_type == LOSS_BINARY_CROSSENTROPY) {
+    d_bce_sum = (float*)dmalloc(256);
+    check(api->ffh_zero(ctx, d_bce_sum, 256, stream), "zero");
+  }
   check(api->ffh_zero(ctx, act_slab, std::max<size_t>(act_bytes, 256), stream), "zero");
   check(api->ffh_zero(ctx, act_grad_slab, std::max<size_t>(act_grad_bytes, 256), stream), "zero");
 

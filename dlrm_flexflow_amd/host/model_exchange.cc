@@ -134,7 +134,7 @@ void FFModel::embedding_kernels_only(bool fwd, ffh_stream s, const std::vector<c
 // FFH_MAX_TABLES shards), no row-wise sharded table (its own fused call), launches issued inline.
 bool FFModel::early_sort_possible(int where) const {
   if (!config.early_sort || !config.overlap_embedding || !fused_embedding_update() || config.profiling) return false;
-  if (config.computationMode != COMP_MODE_TRAINING || use_workers()) return false;
+  if (config.computationMode != COMP_MODE_TRAINING || use_workers() || evaluating) return false;      // (eval_batch(): no update follows)
   // by shape (round 4, profiles/r04_ab_schedule.txt): behind the exchange the whole update sits between the backward all-to-all and
   // the next gather, so the sort leaves that chain; on one GPU it pays at small per-GPU batches (4096 samples: 1.178 vs 1.191 ms)
   // and costs at large ones, where it runs beside the top MLP's first forward GEMM (32768: 7.76-7.79 vs 7.71-7.73; 8192, MLPerf

@@ -31,6 +31,10 @@ FFConfig::FFConfig() {
   row_shard_rows = 0;
   replicate_embedding_rows = 0;
   fuse_loss = true;
+  driver_loss = LOSS_MEAN_SQUARED_ERROR_AVG_REDUCE;
+  eval_batches = 0;
+  eval_only = false;
+  synthetic_labels = 0;
   timing_events = false;
   attach_events = true;
   fuse_pair = true;
@@ -122,6 +126,22 @@ void FFConfig::parse_args(char** argv, int argc) {
     if (is("--row-shard-rows")) { row_shard_rows = atoll(next()); continue; }
     if (is("--replicate-embedding-rows")) { replicate_embedding_rows = atoll(next()); continue; }
     if (is("--no-fused-loss")) { fuse_loss = false; continue; }
+    if (is("--loss")) {
+      const char* v = next();
+      if (!strcmp(v, "mse")) driver_loss = LOSS_MEAN_SQUARED_ERROR_AVG_REDUCE;
+      else if (!strcmp(v, "bce")) driver_loss = LOSS_BINARY_CROSSENTROPY;
+      else die("--loss %s: 'mse' or 'bce'", v);
+      continue;
+    }
+    if (is("--eval-batches")) { eval_batches = atoi(next()); if (eval_batches < 0) die("--eval-batches %d: must be >= 0", eval_batches); continue; }
+    if (is("--eval-only")) { eval_only = true; continue; }
+    if (is("--synthetic-labels")) {
+      const char* v = next();
+      if (!strcmp(v, "bernoulli")) synthetic_labels = 0;
+      else if (!strcmp(v, "logistic")) synthetic_labels = 1;
+      else die("--synthetic-labels %s: 'bernoulli' or 'logistic'", v);
+      continue;
+    }
     if (is("--timing-events")) { timing_events = true; continue; }
     if (is("--no-attach-event")) { attach_events = false; continue; }
     if (is("--no-fused-pair")) { fuse_pair = false; continue; }

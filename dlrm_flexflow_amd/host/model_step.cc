@@ -8,6 +8,7 @@
 void FFModel::reset_metrics() {
   if (replaying_trace >= 0) return;
   check(api->ffh_zero(ctx, d_perf, sizeof(ffh_perf_metrics), stream), "reset_metrics");
+  if (d_bce_sum) check(api->ffh_zero(ctx, d_bce_sum, sizeof(float), stream), "reset_metrics");
 }
 
 // tensor-op mode: the weights' bf16 twin after a host write / (re)initialisation.  Called where a step STARTS -- from begin_trace()
@@ -166,7 +167,8 @@ void FFModel::backward(int _seq_length) {
   // compute_metrics() + loss backward [ref: src/runtime/model.cc:1443-1452; src/loss_functions/loss_functions.cu:141-170,196-237]
   // in one launch; scale_factor = 1 / global batch
   const Tensor& fin = layers.back()->outputs[0];
-  const float scale = loss_type == LOSS_MEAN_SQUARED_ERROR_AVG_REDUCE ? 1.0f / (float)fin.adim[fin.numDim - 1] : 1.0f;
+  const bool bce = loss_type == LOSS_BINARY_CROSSENTROPY;      // mean over the global batch, dz at the pre-activation (include/ff_hip_ctr.h)
+  const float scale = (bce || loss_type == LOSS_MEAN_SQUARED_ERROR_AVG_REDUCE) ? 1.0f / (float)fin.adim[fin.numDim - 1] : 1.0f;
   if (fin.impl->grad_ld != fin.adim[0] || fin.impl->ld != fin.adim[0]) die("final layer output must be contiguous");
   dw_forked = false;
   opt_next_done = false;
@@ -180,16 +182,28 @@ void FFModel::backward(int _seq_length) {
   if (last) {
     const Tensor& x = last->inputs[0];
     const int flags = (last->dx_overwrite ? FFH_LINEAR_DX_OVERWRITE : 0) | (last->dx_mask_by_x ? FFH_LINEAR_DX_MASK_BY_X : 0);
+    if (bce)
+      rc = api->ctr->ffh_linear_bwd_bce(ctx, (const float*)x.impl->ptr, x.impl->ld, last->discard_input_grad ? nullptr : x.impl->grad, x.impl->grad_ld,
+                                        (const float*)fin.impl->ptr, fin.impl->ld, fin.impl->grad, fin.impl->grad_ld,
+                                        (const float*)last->weights[0].impl->ptr, last->weights[0].impl->grad,
+                                        last->use_bias ? last->weights[1].impl->grad : nullptr, last->in_channels, last->out_channels,
+                                        local_rows(fin, this), (int)last->activation, flags, (const float*)label_tensor.impl->ptr, scale, d_perf,
+                                        d_bce_sum, metrics_flags, stream);
+    else
     rc = api->ffh_linear_bwd_mse(ctx, (const float*)x.impl->ptr, x.impl->ld, last->discard_input_grad ? nullptr : x.impl->grad, x.impl->grad_ld,
                                  (const float*)fin.impl->ptr, fin.impl->ld, fin.impl->grad, fin.impl->grad_ld,
                                  (const float*)last->weights[0].impl->ptr, last->weights[0].impl->grad,
                                  last->use_bias ? last->weights[1].impl->grad : nullptr, last->in_channels, last->out_channels,
                                  local_rows(fin, this), (int)last->activation, flags, (const float*)label_tensor.impl->ptr, scale, d_perf,
                                  metrics_flags, stream);
+    if (rc == FFH_OK) n_fused_loss_calls++;
     if (rc == FFH_OK) first--;                          // the last layer is done
     else if (rc != FFH_ERR_UNSUPPORTED) check(rc, "loss + last layer backward");
   }
-  if (rc != FFH_OK)
+  if (rc != FFH_OK && bce)      // the two-call route: the final layer then runs with FFH_LINEAR_DY_PREMASKED (compile() set dy_premasked)
+    check(api->ctr->ffh_bce_bwd_metrics(ctx, fin.impl->grad, (const float*)fin.impl->ptr, (const float*)label_tensor.impl->ptr, d_perf, d_bce_sum,
+                                        local_rows(fin, this), fin.adim[0], scale, metrics_flags, stream), "metrics + loss backward (bce)");
+  else if (rc != FFH_OK)
     check(api->ffh_mse_bwd_metrics(ctx, fin.impl->grad, (const float*)fin.impl->ptr, (const float*)label_tensor.impl->ptr, d_perf,
                                    local_rows(fin, this), fin.adim[0], scale, metrics_flags, stream), "metrics + loss backward");
   grad_ready_attached = false;
@@ -468,5 +482,83 @@ PerfMetrics FFModel::get_perf_metrics() {
   PerfMetrics p;
   p.train_all = h.train_all; p.train_correct = h.train_correct; p.cce_loss = h.cce_loss;
   p.sparse_cce_loss = h.sparse_cce_loss; p.mse_loss = h.mse_loss; p.rmse_loss = h.rmse_loss; p.mae_loss = h.mae_loss;
+  if (d_bce_sum) {
+    check(api->ffh_memcpy_d2h(ctx, &p.bce_loss, d_bce_sum, sizeof(float), stream), "metrics d2h");
+    check(api->ffh_stream_sync(ctx, stream), "sync");
+  }
   return p;
+}
+
+// =============================================================================================
+// held-out evaluation (include/ff_hip_ctr.h)
+// =============================================================================================
+void FFModel::reset_eval_metrics() {
+  if (!api->ctr) die("reset_eval_metrics(): %s is a kernel library without the CTR extension (include/ff_hip_ctr.h)", api->path.c_str());
+  if (capturing_trace >= 0 || replaying_trace >= 0) die("reset_eval_metrics() inside begin_trace / end_trace");
+  if (!d_eval) d_eval = (ffh_ctr_eval*)dmalloc(sizeof(ffh_ctr_eval));
+  check(api->ffh_zero(ctx, d_eval, sizeof(ffh_ctr_eval), stream), "reset_eval_metrics");
+}
+
+void FFModel::eval_batch() {
+  if (!compiled) die("eval_batch() before compile()");
+  if (capturing_trace >= 0 || replaying_trace >= 0) die("eval_batch() inside begin_trace / end_trace: evaluate between steps");
+  const Linear* last = dynamic_cast<const Linear*>(layers.back());
+  if (!last || last->activation != AC_MODE_SIGMOID || last->out_channels != 1)
+    die("eval_batch(): the final operator must be a Linear with sigmoid activation and one output column (--sigmoid-top)");
+  if (!d_eval) reset_eval_metrics();
+  // The forward pass as a training step issues it, with two differences: the side-stream gather is always ordered behind `stream` (the
+  // batch was just written there, and a replayed step joins its table update into `stream`), and no early sort is issued (it would
+  // leave a sorted list of THESE ids in the workspace for the next training step's apply phase).  Nothing else a step carries across its
+  // boundary is touched: gradients, the optimizer's step count, the bf16 rounding counter, the captured graphs.
+  evaluating = true;
+  inputs_dirty = true;
+  forward();
+  evaluating = false;
+  inputs_dirty = true;     // the next training step's gather: behind whatever writes its batch (and behind this pass's readers)
+  const Tensor& fin = layers.back()->outputs[0];
+  check(api->ctr->ffh_ctr_eval_update(ctx, (const float*)fin.impl->ptr, (const float*)label_tensor.impl->ptr, d_eval, local_rows(fin, this), stream),
+        "eval_batch");
+}
+
+// Counts and histograms are summed over the ranks EXACTLY through ffcomm's fp32 all-reduce: every 64-bit count travels as four 16-bit
+// pieces, each below 2^16, so a sum over up to 8 ranks stays below 2^19 and is exact in fp32; the pieces are re-assembled in integers.
+EvalMetrics FFModel::get_eval_metrics(bool with_histograms) {
+  if (!d_eval) reset_eval_metrics();
+  sync();
+  std::vector<uint64_t> h(sizeof(ffh_ctr_eval) / 8);
+  check(api->ffh_memcpy_d2h(ctx, h.data(), d_eval, sizeof(ffh_ctr_eval), stream), "eval metrics d2h");
+  check(api->ffh_stream_sync(ctx, stream), "sync");
+  ffh_ctr_eval* e = reinterpret_cast<ffh_ctr_eval*>(h.data());
+  double logloss = (double)e->logloss_sum;
+  if (exchange && world_size > 1) {
+    if (world_size > 8) die("get_eval_metrics(): the exact count exchange is sized for up to 8 ranks");
+    float ll = e->logloss_sum;
+    e->logloss_sum = 0.0f; e->pad_[0] = e->pad_[1] = e->pad_[2] = 0.0f;
+    const size_t nw = h.size(), nf = nw * 4 + 1;
+    float* d = (float*)dmalloc(nf * sizeof(float));
+    std::vector<float> f(nf);
+    for (size_t i = 0; i < nw; i++)
+      for (int k = 0; k < 4; k++) f[i * 4 + k] = (float)((h[i] >> (16 * k)) & 0xffffULL);
+    f[nf - 1] = ll;
+    check(api->ffh_memcpy_h2d(ctx, d, f.data(), nf * sizeof(float), stream), "eval metrics h2d");
+    if (config.comm.allreduce_sum_f32(config.comm.user, d, (int64_t)nf, stream) != 0) die("allreduce (evaluation metrics) failed");
+    check(api->ffh_memcpy_d2h(ctx, f.data(), d, nf * sizeof(float), stream), "eval metrics d2h");
+    check(api->ffh_stream_sync(ctx, stream), "sync");
+    api->ffh_free(ctx, d);
+    for (size_t i = 0; i < nw; i++) {
+      uint64_t v = 0;
+      for (int k = 0; k < 4; k++) v += (uint64_t)f[i * 4 + k] << (16 * k);
+      h[i] = v;
+    }
+    logloss = (double)f[nf - 1];
+  }
+  EvalMetrics m;
+  m.samples = e->samples; m.positives = e->positives; m.correct = e->correct; m.nan_predictions = e->nan_predictions;
+  m.logloss_sum = logloss;
+  m.auc = ffh_auc_from_histograms(e->hist_pos, e->hist_neg, FFH_AUC_BINS);
+  if (with_histograms) {
+    m.hist_pos.assign(e->hist_pos, e->hist_pos + FFH_AUC_BINS);
+    m.hist_neg.assign(e->hist_neg, e->hist_neg + FFH_AUC_BINS);
+  }
+  return m;
 }
