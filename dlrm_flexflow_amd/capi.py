@@ -222,6 +222,52 @@ _SIGS_CTR = {
 }
 
 
+# include/ff_hip_lr.h: the optional learning-rate extension (schedule state in device memory, optimizer entries that read it); same rule
+LR_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_lr.h")
+
+
+class LrSchedule(C.Structure):
+    """struct ffh_lr_schedule"""
+    _fields_ = [("base", C.c_double), ("warmup_steps", L), ("decay_start", L), ("decay_steps", L), ("beta1", C.c_double), ("beta2", C.c_double)]
+
+
+class LrValues(C.Structure):
+    """struct ffh_lr_values"""
+    _fields_ = [("k", L), ("lr", F), ("alpha_t", F), ("beta1_t", C.c_double), ("beta2_t", C.c_double)]
+
+
+_SIGS_LR = {
+    "ffh_lr_abi_version": (I, []),
+    "ffh_lr_state_bytes": (SZ, []),
+    "ffh_lr_state_init": (I, [P, P, C.POINTER(LrSchedule), L, P]),
+    "ffh_lr_state_advance": (I, [P, P, P]),
+    "ffh_lr_state_read": (I, [P, P, C.POINTER(LrValues), P]),
+    "ffh_sgd_update_ex_lr": (I, [P, P, P, P, L, P, F, F, I, I, P]),
+    "ffh_adam_update_lr": (I, [P, P, P, P, P, L, P, F, F, F, F, I, P]),
+    "ffh_embedding_bwd_opt_fused_multi_lr": (I, [P, C.POINTER(EmbTable), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), P, P]),
+    "ffh_embedding_bwd_opt_apply_multi_lr": (I, [P, C.POINTER(EmbTable), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), P, P]),
+    "ffh_embedding_bwd_opt_fused_multi_bf16_lr": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), C.POINTER(Bf16Rounding), P, P]),
+    "ffh_embedding_bwd_opt_apply_multi_bf16_lr": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), C.POINTER(Bf16Rounding), P, P]),
+}
+
+
+def lr_header_symbols(header_path: str = LR_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_LR_API_LIST X-macro in include/ff_hip_lr.h."""
+    text = open(header_path).read()
+    m = re.search(r"#define FFH_LR_API_LIST\(X\)(.*?)\n\n", text, re.S)
+    if not m:
+        raise RuntimeError("FFH_LR_API_LIST not found in " + header_path)
+    return re.findall(r"X\((\w+)\)", m.group(1))
+
+
+def lr_header_abi_version(header_path: str = LR_HEADER_PATH) -> int:
+    """FFH_LR_ABI_VERSION of include/ff_hip_lr.h."""
+    m = re.search(r"#define\s+FFH_LR_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_LR_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
 def ctr_header_symbols(header_path: str = CTR_HEADER_PATH) -> list[str]:
     """Every symbol of the FFH_CTR_API_LIST X-macro in include/ff_hip_ctr.h."""
     text = open(header_path).read()
@@ -469,6 +515,49 @@ class CtrApi:
 def ctr_api(lib: FFHLib) -> CtrApi:
     """The CTR entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
     return CtrApi(lib)
+
+
+class LrApi:
+    """The learning-rate extension (include/ff_hip_lr.h) of a loaded FFHLib; `lr_api(lib)` builds it or raises."""
+
+    def __init__(self, lib: FFHLib):
+        self.base = lib
+        for name, (res, args) in _SIGS_LR.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no learning-rate extension ({name} missing; include/ff_hip_lr.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_lr_abi_version()
+        if got != lr_header_abi_version():
+            raise FFHError(f"{lib.path}: learning-rate ABI version {got}, include/ff_hip_lr.h says {lr_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+    def call(self, name: str, *args):
+        """Call `name(ctx, *args)` of the extension; pointers may be tensors/arrays/ints/None."""
+        sig = _SIGS_LR[name][1][1:]
+        if len(args) != len(sig):
+            raise TypeError(f"{name}: expected {len(sig)} args, got {len(args)}")
+        conv = [ptr(a) if t is P else a for a, t in zip(args, sig)]
+        self.base.check(getattr(self.lib, name)(self.ctx, *conv), name)
+
+    def state_bytes(self) -> int:
+        return int(self.lib.ffh_lr_state_bytes())
+
+    def init(self, block, base, W=0, S=0, N=0, beta1=0.0, beta2=0.0, first_step=0, stream=None):
+        sc = LrSchedule(float(base), int(W), int(S), int(N), float(beta1), float(beta2))
+        self.call("ffh_lr_state_init", block, C.byref(sc), int(first_step), stream)
+
+    def read(self, block, stream=None) -> LrValues:
+        v = LrValues()
+        self.call("ffh_lr_state_read", block, C.byref(v), stream)
+        return v
+
+
+def lr_api(lib: FFHLib) -> LrApi:
+    """The learning-rate entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
+    return LrApi(lib)
 
 
 _hip_singleton: FFHLib | None = None

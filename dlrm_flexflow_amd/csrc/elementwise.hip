@@ -3,6 +3,7 @@
 // op (the reference launches copy_with_stride / add_with_stride once per concat input,
 // [ref: src/ops/concat.cu:243-248,353-357]).
 #include "ffh_common.h"
+#include "lr_state.h"
 
 namespace {
 
@@ -278,10 +279,11 @@ __device__ __forceinline__ void store_mirrors(const float4 v, unsigned short* tw
   }
 }
 
+// sgd_kernel (lr a launch argument) and sgd_lr_kernel (lr read from an ffh_lr_state block, include/ff_hip_lr.h) run this one body
 template <int VEC>
-__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ v,
-                                                  int64_t n, float lr, float wd, float mom, int nesterov, int zero_grad,
-                                                  unsigned short* __restrict__ twin, char* __restrict__ planes, int64_t e0) {
+__device__ __forceinline__ void sgd_body(float* __restrict__ w, float* __restrict__ g, float* __restrict__ v,
+                                         int64_t n, float lr, float wd, float mom, int nesterov, int zero_grad,
+                                         unsigned short* __restrict__ twin, char* __restrict__ planes, int64_t e0) {
   ffh_kernel_prio();
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t nv = n / VEC;
@@ -318,11 +320,25 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ w, float* 
   }
 }
 
-// adam_update [ref: src/runtime/optimizer_kernel.cu:206-226]; canonical rounding as stated in ff_hip.h
 template <int VEC>
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                   int64_t n, float alpha_t, float b1, float b2, float wd, float eps, int zero_grad,
-                                                   unsigned short* __restrict__ twin, char* __restrict__ planes, int64_t e0) {
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ v,
+                                                  int64_t n, float lr, float wd, float mom, int nesterov, int zero_grad,
+                                                  unsigned short* __restrict__ twin, char* __restrict__ planes, int64_t e0) {
+  sgd_body<VEC>(w, g, v, n, lr, wd, mom, nesterov, zero_grad, twin, planes, e0);
+}
+template <int VEC>
+__global__ __launch_bounds__(256) void sgd_lr_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ v,
+                                                     int64_t n, const float* __restrict__ lr_src, float wd, float mom, int nesterov, int zero_grad,
+                                                     unsigned short* __restrict__ twin, char* __restrict__ planes, int64_t e0) {
+  sgd_body<VEC>(w, g, v, n, *lr_src, wd, mom, nesterov, zero_grad, twin, planes, e0);      // one wave-uniform load
+}
+
+// adam_update [ref: src/runtime/optimizer_kernel.cu:206-226]; canonical rounding as stated in ff_hip.h
+// (adam_kernel / adam_lr_kernel: as sgd_kernel / sgd_lr_kernel)
+template <int VEC>
+__device__ __forceinline__ void adam_body(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                          int64_t n, float alpha_t, float b1, float b2, float wd, float eps, int zero_grad,
+                                          unsigned short* __restrict__ twin, char* __restrict__ planes, int64_t e0) {
   ffh_kernel_prio();
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   const int64_t nv = n / VEC;
@@ -366,6 +382,18 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, float*
       if (zero_grad) g[i] = 0.f;
     }
   }
+}
+template <int VEC>
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                   int64_t n, float alpha_t, float b1, float b2, float wd, float eps, int zero_grad,
+                                                   unsigned short* __restrict__ twin, char* __restrict__ planes, int64_t e0) {
+  adam_body<VEC>(w, g, m, v, n, alpha_t, b1, b2, wd, eps, zero_grad, twin, planes, e0);
+}
+template <int VEC>
+__global__ __launch_bounds__(256) void adam_lr_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                      int64_t n, const float* __restrict__ alpha_src, float b1, float b2, float wd, float eps, int zero_grad,
+                                                      unsigned short* __restrict__ twin, char* __restrict__ planes, int64_t e0) {
+  adam_body<VEC>(w, g, m, v, n, *alpha_src, b1, b2, wd, eps, zero_grad, twin, planes, e0);
 }
 
 __global__ __launch_bounds__(256) void add_scaled_kernel(float* __restrict__ d, const float* __restrict__ src, int64_t n, float scale) {
@@ -493,8 +521,10 @@ int ffh_mse_bwd_metrics(ffh_ctx* c, float* lg, const float* logit, const float* 
   return FFH_OK;
 }
 
-int ffh_sgd_update_ex(ffh_ctx* c, float* w, float* g, float* v, int64_t n, float lr, float wd, float mom, int nesterov, int flags,
-                      ffh_stream s) {
+}  // extern "C"
+// lr_src: null = `lr` as a launch argument (the scalar entry), else the rate is read from there (include/ff_hip_lr.h)
+static int sgd_update_impl(ffh_ctx* c, float* w, float* g, float* v, int64_t n, float lr, const float* lr_src, float wd, float mom, int nesterov, int flags,
+                           ffh_stream s) {
   FFH_REQUIRE(c, n >= 0 && ((w && g) || n == 0), "sgd_update: bad args");
   FFH_REQUIRE(c, !(mom > 0.f) || v, "sgd_update: momentum needs V");
   FFH_REQUIRE(c, (flags & ~FFH_OPT_ZERO_GRAD) == 0, "sgd_update: unknown flags");
@@ -507,7 +537,10 @@ int ffh_sgd_update_ex(ffh_ctx* c, float* w, float* g, float* v, int64_t n, float
   int col0 = 0;
   char* pl = const_cast<char*>(ffh_planes_of(c, w, (size_t)n * 4, &col0));
   const bool fused = vec && (!tw || ((uintptr_t)tw & 7) == 0) && (!pl || col0 % 4 == 0);
-  if (vec) hipLaunchKernelGGL((sgd_kernel<4>), dim3(ffh_grid(n / 4, 256)), dim3(256), 0, as_stream(s), w, g, v, n, lr, wd, mom, nesterov, zg, fused ? tw : nullptr, fused ? pl : nullptr, (int64_t)col0);
+  if (lr_src) {
+    if (vec) hipLaunchKernelGGL((sgd_lr_kernel<4>), dim3(ffh_grid(n / 4, 256)), dim3(256), 0, as_stream(s), w, g, v, n, lr_src, wd, mom, nesterov, zg, fused ? tw : nullptr, fused ? pl : nullptr, (int64_t)col0);
+    else hipLaunchKernelGGL((sgd_lr_kernel<1>), dim3(ffh_grid(n, 256)), dim3(256), 0, as_stream(s), w, g, v, n, lr_src, wd, mom, nesterov, zg, (unsigned short*)nullptr, (char*)nullptr, (int64_t)0);
+  } else if (vec) hipLaunchKernelGGL((sgd_kernel<4>), dim3(ffh_grid(n / 4, 256)), dim3(256), 0, as_stream(s), w, g, v, n, lr, wd, mom, nesterov, zg, fused ? tw : nullptr, fused ? pl : nullptr, (int64_t)col0);
   else hipLaunchKernelGGL((sgd_kernel<1>), dim3(ffh_grid(n, 256)), dim3(256), 0, as_stream(s), w, g, v, n, lr, wd, mom, nesterov, zg, (unsigned short*)nullptr, (char*)nullptr, (int64_t)0);
   FFH_LAUNCH_CHECK(c, "sgd_kernel");
   if (!fused && tw) return ffh_convert_f32_to_bf16(c, tw, w, n, s);
@@ -515,12 +548,26 @@ int ffh_sgd_update_ex(ffh_ctx* c, float* w, float* g, float* v, int64_t n, float
   return FFH_OK;
 }
 
+extern "C" {
+
+int ffh_sgd_update_ex(ffh_ctx* c, float* w, float* g, float* v, int64_t n, float lr, float wd, float mom, int nesterov, int flags,
+                      ffh_stream s) {
+  return sgd_update_impl(c, w, g, v, n, lr, nullptr, wd, mom, nesterov, flags, s);
+}
+
+int ffh_sgd_update_ex_lr(ffh_ctx* c, float* w, float* g, float* v, int64_t n, const ffh_lr_state* block, float wd, float mom, int nesterov,
+                         int flags, ffh_stream s) {
+  FFH_REQUIRE(c, block != nullptr, "sgd_update_ex_lr: null ffh_lr_state");
+  return sgd_update_impl(c, w, g, v, n, 0.0f, ffh_lr_rate_ptr(block, false), wd, mom, nesterov, flags, s);
+}
+
 int ffh_sgd_update(ffh_ctx* c, float* w, const float* g, float* v, int64_t n, float lr, float wd, float mom, int nesterov, ffh_stream s) {
   return ffh_sgd_update_ex(c, w, const_cast<float*>(g), v, n, lr, wd, mom, nesterov, 0, s);
 }
 
-int ffh_adam_update(ffh_ctx* c, float* w, float* g, float* m, float* v, int64_t n, float alpha_t, float b1, float b2, float wd, float eps,
-                    int flags, ffh_stream s) {
+}  // extern "C"
+static int adam_update_impl(ffh_ctx* c, float* w, float* g, float* m, float* v, int64_t n, float alpha_t, const float* alpha_src, float b1, float b2, float wd,
+                            float eps, int flags, ffh_stream s) {
   FFH_REQUIRE(c, n >= 0 && ((w && g && m && v) || n == 0), "adam_update: bad args");
   FFH_REQUIRE(c, (flags & ~FFH_OPT_ZERO_GRAD) == 0, "adam_update: unknown flags");
   if (n == 0) return FFH_OK;
@@ -530,12 +577,28 @@ int ffh_adam_update(ffh_ctx* c, float* w, float* g, float* m, float* v, int64_t 
   int col0 = 0;
   char* pl = const_cast<char*>(ffh_planes_of(c, w, (size_t)n * 4, &col0));
   const bool fused = vec && (!tw || ((uintptr_t)tw & 7) == 0) && (!pl || col0 % 4 == 0);
-  if (vec) hipLaunchKernelGGL((adam_kernel<4>), dim3(ffh_grid(n / 4, 256)), dim3(256), 0, as_stream(s), w, g, m, v, n, alpha_t, b1, b2, wd, eps, zg, fused ? tw : nullptr, fused ? pl : nullptr, (int64_t)col0);
+  if (alpha_src) {
+    if (vec) hipLaunchKernelGGL((adam_lr_kernel<4>), dim3(ffh_grid(n / 4, 256)), dim3(256), 0, as_stream(s), w, g, m, v, n, alpha_src, b1, b2, wd, eps, zg, fused ? tw : nullptr, fused ? pl : nullptr, (int64_t)col0);
+    else hipLaunchKernelGGL((adam_lr_kernel<1>), dim3(ffh_grid(n, 256)), dim3(256), 0, as_stream(s), w, g, m, v, n, alpha_src, b1, b2, wd, eps, zg, (unsigned short*)nullptr, (char*)nullptr, (int64_t)0);
+  } else if (vec) hipLaunchKernelGGL((adam_kernel<4>), dim3(ffh_grid(n / 4, 256)), dim3(256), 0, as_stream(s), w, g, m, v, n, alpha_t, b1, b2, wd, eps, zg, fused ? tw : nullptr, fused ? pl : nullptr, (int64_t)col0);
   else hipLaunchKernelGGL((adam_kernel<1>), dim3(ffh_grid(n, 256)), dim3(256), 0, as_stream(s), w, g, m, v, n, alpha_t, b1, b2, wd, eps, zg, (unsigned short*)nullptr, (char*)nullptr, (int64_t)0);
   FFH_LAUNCH_CHECK(c, "adam_kernel");
   if (!fused && tw) return ffh_convert_f32_to_bf16(c, tw, w, n, s);
   if (!fused && pl) return ffh_convert_f32_to_bf16x3(c, w, 1, n, n, s);
   return FFH_OK;
+}
+
+extern "C" {
+
+int ffh_adam_update(ffh_ctx* c, float* w, float* g, float* m, float* v, int64_t n, float alpha_t, float b1, float b2, float wd, float eps,
+                    int flags, ffh_stream s) {
+  return adam_update_impl(c, w, g, m, v, n, alpha_t, nullptr, b1, b2, wd, eps, flags, s);
+}
+
+int ffh_adam_update_lr(ffh_ctx* c, float* w, float* g, float* m, float* v, int64_t n, const ffh_lr_state* block, float b1, float b2, float wd,
+                       float eps, int flags, ffh_stream s) {
+  FFH_REQUIRE(c, block != nullptr, "adam_update_lr: null ffh_lr_state");
+  return adam_update_impl(c, w, g, m, v, n, 0.0f, ffh_lr_rate_ptr(block, true), b1, b2, wd, eps, flags, s);
 }
 
 int ffh_add_scaled(ffh_ctx* c, float* d, const float* src, int64_t n, float scale, ffh_stream s) {

@@ -17,6 +17,7 @@
 #include "ffh_common.h"
 #include "../../include/ff_hip_bf16.h"
 #include "../../include/ffh_bf16.h"
+#include "lr_state.h"
 #ifdef FFH_MSD_TIMING
 #include <vector>
 #endif
@@ -414,8 +415,20 @@ enum : uint32_t { kMetaNone = 0, kMetaFirst = 1, kMetaCont = 2 };
 // OPT 3 (kOptSgdBf16): plain SGD on a bf16 table (ff_hip_bf16.h): the weight row is 16-bit, w32 = fmaf(-lr, sum, (float)w16) as
 // OPT 0 computes it on the widened table, then one rounding (ffh_bf16.h) keyed by the update counter, table, global row and column.
 // sr_* / SrKey: that rounding (sr_counter: the update number in device memory).
-struct OptP { float lr, wd, mom, b1, b2, eps, omb1, omb2; int nesterov; int64_t nt_rows;   // nt_rows: tables of more rows have their rows read and written nontemporal (plain SGD, 16-byte form)
-              int sr_mode; uint64_t sr_seed; const uint64_t* sr_counter; };
+// lr_src_lo / _hi (include/ff_hip_lr.h): the two halves of the address the LRP instantiations of the kernels read lr from, once per wave; zero and
+// unread otherwise.  They sit in the two 4-byte holes the struct already had (behind nesterov and behind sr_mode), so no member moves and the
+// kernel arguments do not grow: the instantiations the scalar entries launch read every argument where they always did.
+struct OptP { float lr, wd, mom, b1, b2, eps, omb1, omb2; int nesterov; uint32_t lr_src_lo; int64_t nt_rows;   // nt_rows: tables of more rows have their rows read and written nontemporal (plain SGD, 16-byte form)
+              int sr_mode; uint32_t lr_src_hi; uint64_t sr_seed; const uint64_t* sr_counter; };
+static_assert(sizeof(OptP) == 72, "OptP: the rate address must fit in the padding it replaced");
+static inline void opt_set_lr_src(OptP& o, const float* p) { o.lr_src_lo = (uint32_t)(uintptr_t)p; o.lr_src_hi = (uint32_t)((uintptr_t)p >> 32); }
+__host__ __device__ __forceinline__ const float* opt_lr_src(const OptP& o) { return reinterpret_cast<const float*>(((uintptr_t)o.lr_src_hi << 32) | o.lr_src_lo); }
+// the row rule as the kernel applies it: LRP = false: the kernel arguments' own (no copy, the instructions of before); LRP = true: a copy with
+// lr loaded from that address -- a uniform address, so one scalar load per wave
+#define FFH_OPT_OF(LRP, name, args_op)                                   \
+  OptP name##_l;                                                          \
+  if (LRP) { name##_l = (args_op); name##_l.lr = *opt_lr_src(args_op); }    \
+  const OptP& name = LRP ? name##_l : (args_op)
 constexpr int kOptSgdBf16 = 3;
 // OPT 4 / 5 (kOptMomentumBf16, kOptAdamBf16): OPT 1 / 2 on a bf16 table -- the state update and w32 statement by statement those of OPT 1 / 2
 // on the widened row w = (float)w16, fp32 state, then the one rounding of kOptSgdBf16
@@ -1275,9 +1288,10 @@ struct RedSmem { RedShared sh; uint2 fmeta[kFoldStage]; };
 union MsdSmem { RedSmem red; MsdShared ms; };          // the window is dead once the tile's entries sit in registers
 template <bool MSD> struct RedSmemOf { typedef RedSmem type; static __device__ __forceinline__ RedSmem& red(RedSmem& s) { return s; } };
 template <> struct RedSmemOf<true> { typedef MsdSmem type; static __device__ __forceinline__ RedSmem& red(MsdSmem& s) { return s.red; } };
-template <int VEC, int OPT, bool MSD = false>
+template <int VEC, int OPT, bool MSD = false, bool LRP = false>
 __global__ __launch_bounds__(kRedThreads, MSD ? (opt_plain(OPT) ? 6 : 4) : (OPT == 0 ? 8 : OPT == kOptSgdBf16 ? 6 : 4)) void emb_sgd_reduce_kernel(const RedArgs a) {
   ffh_kernel_prio();
+  FFH_OPT_OF(LRP, op, a.op);
   __shared__ typename RedSmemOf<MSD>::type smem;
   __shared__ int s_last;
   RedShared& sh = RedSmemOf<MSD>::red(smem).sh;
@@ -1319,7 +1333,7 @@ __global__ __launch_bounds__(kRedThreads, MSD ? (opt_plain(OPT) ? 6 : 4) : (OPT 
   }
   MSD_STAMP(1);
   reduce_tile_body<VEC, true, OPT>(tb, keys, p0, m0, a.N, a.nchunks, a.tile,
-                        (int)blockIdx.x, a.L, a.D, a.avg != 0, a.op, st0, st1, sk, sh, threadIdx.x, preloaded);
+                        (int)blockIdx.x, a.L, a.D, a.avg != 0, op, st0, st1, sk, sh, threadIdx.x, preloaded);
   MSD_STAMP(2);
 
   const int nvec = a.D / VEC;
@@ -1366,7 +1380,7 @@ __global__ __launch_bounds__(kRedThreads, MSD ? (opt_plain(OPT) ? 6 : 4) : (OPT 
     const int64_t lo = 2 * B1 * kRatio;
     const int64_t hi = lo + 2 * kRatio < 2 * (int64_t)a.nchunks ? lo + 2 * kRatio : 2 * (int64_t)a.nchunks;
     if (stage(m0, lo, hi))
-      fold_table_body<VEC, true, OPT>(tb, p0, m0, p1, m1, a.nchunks, kRatio, a.D, a.op, st0, st1, sk, lo, hi, group0, ngroups, MSD ? nullptr : keys, s_fmeta, lo, (int)(hi - lo), nextkey);
+      fold_table_body<VEC, true, OPT>(tb, p0, m0, p1, m1, a.nchunks, kRatio, a.D, op, st0, st1, sk, lo, hi, group0, ngroups, MSD ? nullptr : keys, s_fmeta, lo, (int)(hi - lo), nextkey);
     xwg_stores_done();
     __syncthreads();
     if (threadIdx.x == 0) s_last = __hip_atomic_fetch_add(&arrive[a.nchunks1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (uint32_t)a.nchunks1 - 1u;
@@ -1374,11 +1388,11 @@ __global__ __launch_bounds__(kRedThreads, MSD ? (opt_plain(OPT) ? 6 : 4) : (OPT 
     if (!s_last) return;
     const int64_t hi1 = 2 * (int64_t)a.nchunks1;
     if (stage(m1, 0, hi1))
-      fold_table_body<VEC, true, OPT>(tb, p1, m1, p1, m1, a.nchunks1, 0, a.D, a.op, st0, st1, sk, 0, hi1, group0, ngroups, nullptr, s_fmeta, 0, (int)(hi1 < kFoldStage ? hi1 : kFoldStage));
+      fold_table_body<VEC, true, OPT>(tb, p1, m1, p1, m1, a.nchunks1, 0, a.D, op, st0, st1, sk, 0, hi1, group0, ngroups, nullptr, s_fmeta, 0, (int)(hi1 < kFoldStage ? hi1 : kFoldStage));
   } else {
     const int64_t hi0 = 2 * (int64_t)a.nchunks;
     if (stage(m0, 0, hi0))
-      fold_table_body<VEC, true, OPT>(tb, p0, m0, p1, m1, a.nchunks, 0, a.D, a.op, st0, st1, sk, 0, hi0, group0, ngroups, nullptr, s_fmeta, 0, (int)hi0);
+      fold_table_body<VEC, true, OPT>(tb, p0, m0, p1, m1, a.nchunks, 0, a.D, op, st0, st1, sk, 0, hi0, group0, ngroups, nullptr, s_fmeta, 0, (int)hi0);
   }
 }
 
@@ -1418,9 +1432,10 @@ union SmallShared {                                    // the sort arrays are de
   RedShared red[kSmallRedParts];
 };
 
-template <int VEC, int OPT>
+template <int VEC, int OPT, bool LRP = false>
 __global__ __launch_bounds__(kSmallThreads) void emb_sgd_small_kernel(const SmallArgs a) {
   ffh_kernel_prio();
+  FFH_OPT_OF(LRP, op, a.op);
   constexpr int NW = kSmallWaves;
   constexpr int E = kSmallMax / kSmallThreads;         // 2 entries per thread, wave w owns [128 w, 128 w + 128)
   __shared__ SmallShared sm;
@@ -1491,7 +1506,7 @@ __global__ __launch_bounds__(kSmallThreads) void emb_sgd_small_kernel(const Smal
   const int team = threadIdx.x / kRedThreads, ttid = threadIdx.x % kRedThreads;
   const int ntiles = (int)((N + a.tile - 1) / a.tile);
   for (int t0 = 0; t0 < ntiles; t0 += kSmallRedParts) {
-    reduce_tile_body<VEC, false, OPT>(tb, keys, p0, m0, N, a.nch0, a.tile, t0 + team, a.L, a.D, a.avg != 0, a.op, st0, st1, sk, sm.red[team], ttid);
+    reduce_tile_body<VEC, false, OPT>(tb, keys, p0, m0, N, a.nch0, a.tile, t0 + team, a.L, a.D, a.avg != 0, op, st0, st1, sk, sm.red[team], ttid);
     __syncthreads();
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1505,13 +1520,13 @@ __global__ __launch_bounds__(kSmallThreads) void emb_sgd_small_kernel(const Smal
   const int64_t ngroups = (int64_t)NW * rpw;
   float* p1 = a.partial1 + (int64_t)tix * 2 * a.nch1 * a.D;
   if (a.nch1 > 1) {
-    fold_table_body<VEC, false, OPT>(tb, p0, m0, p1, m1, a.nch0, FFH_EMB_CHUNK1 / FFH_EMB_CHUNK, a.D, a.op, st0, st1, sk, 0, 2 * (int64_t)a.nch0, group0, ngroups);
+    fold_table_body<VEC, false, OPT>(tb, p0, m0, p1, m1, a.nch0, FFH_EMB_CHUNK1 / FFH_EMB_CHUNK, a.D, op, st0, st1, sk, 0, 2 * (int64_t)a.nch0, group0, ngroups);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    fold_table_body<VEC, false, OPT>(tb, p1, m1, p1, m1, a.nch1, 0, a.D, a.op, st0, st1, sk, 0, 2 * (int64_t)a.nch1, group0, ngroups);
+    fold_table_body<VEC, false, OPT>(tb, p1, m1, p1, m1, a.nch1, 0, a.D, op, st0, st1, sk, 0, 2 * (int64_t)a.nch1, group0, ngroups);
   } else {
-    fold_table_body<VEC, false, OPT>(tb, p0, m0, p1, m1, a.nch0, 0, a.D, a.op, st0, st1, sk, 0, 2 * (int64_t)a.nch0, group0, ngroups);
+    fold_table_body<VEC, false, OPT>(tb, p0, m0, p1, m1, a.nch0, 0, a.D, op, st0, st1, sk, 0, 2 * (int64_t)a.nch0, group0, ngroups);
   }
 }
 
@@ -1707,7 +1722,8 @@ static void set_bf16_keys(Bf16Keys& keys, Bf16AdamKeys& adam, const Bf16Cfg& b16
 }
 static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L, int D, int64_t batch,
                           int aggr, float lr, ffh_stream s, const bool do_sort, const bool do_apply,
-                          const ffh_sparse_opt* opt = nullptr, const ffh_emb_state* states = nullptr, const Bf16Cfg* b16 = nullptr) {
+                          const ffh_sparse_opt* opt = nullptr, const ffh_emb_state* states = nullptr, const Bf16Cfg* b16 = nullptr,
+                          const ffh_lr_state* lr_block = nullptr) {
   int rc = validate_tables(c, tables, nt, L, D, batch, aggr, "embedding_bwd_sgd_fused");
   if (rc) return rc;
   OptP op{};
@@ -1733,6 +1749,7 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
     op.lr = opt->lr; op.wd = opt->weight_decay; op.mom = opt->momentum; op.nesterov = opt->nesterov ? 1 : 0;
     op.b1 = opt->beta1; op.b2 = opt->beta2; op.eps = opt->epsilon; op.omb1 = 1.0f - opt->beta1; op.omb2 = 1.0f - opt->beta2;
     if (kind == FFH_SPARSE_OPT_SGD && (op.wd != 0.0f || op.mom != 0.0f)) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt: FFH_SPARSE_OPT_SGD takes no weight decay / momentum (use FFH_SPARSE_OPT_SGD_MOMENTUM)");
+    if (lr_block) { op.lr = 0.0f; opt_set_lr_src(op, ffh_lr_rate_ptr(lr_block, kind == FFH_SPARSE_OPT_ADAM)); }      // (include/ff_hip_lr.h: opt->lr is ignored)
     const bool need0 = kind == FFH_SPARSE_OPT_ADAM || (kind == FFH_SPARSE_OPT_SGD_MOMENTUM && op.mom > 0.0f);
     for (int i = 0; i < nt && batch > 0; i++) {
       if (need0 && (!states || !states[i].s0)) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt: optimizer state (s0) missing");
@@ -1798,12 +1815,14 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
     int tile = (int)((N + kSmallRedParts - 1) / kSmallRedParts);          // one tile per 256-thread team
     tile = (tile + FFH_EMB_CHUNK - 1) / FFH_EMB_CHUNK * FFH_EMB_CHUNK;
     sm.tile = tile < FFH_EMB_CHUNK ? FFH_EMB_CHUNK : tile;
-#define FFH_SMALL(OPTV)                                                                                               \
-    { if (v4) hipLaunchKernelGGL((emb_sgd_small_kernel<4, OPTV>), dim3(nt), dim3(kSmallThreads), 0, as_stream(s), sm);  \
-      else hipLaunchKernelGGL((emb_sgd_small_kernel<1, OPTV>), dim3(nt), dim3(kSmallThreads), 0, as_stream(s), sm); }
+#define FFH_SMALL_L(OPTV, LRPV)                                                                                             \
+    { if (v4) hipLaunchKernelGGL((emb_sgd_small_kernel<4, OPTV, LRPV>), dim3(nt), dim3(kSmallThreads), 0, as_stream(s), sm);  \
+      else hipLaunchKernelGGL((emb_sgd_small_kernel<1, OPTV, LRPV>), dim3(nt), dim3(kSmallThreads), 0, as_stream(s), sm); }
+#define FFH_SMALL(OPTV) { if (lr_block) FFH_SMALL_L(OPTV, true) else FFH_SMALL_L(OPTV, false) }
     if (b16) { if (kind == FFH_SPARSE_OPT_SGD) FFH_SMALL(kOptSgdBf16) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_SMALL(kOptMomentumBf16) else FFH_SMALL(kOptAdamBf16) }
     else if (kind == FFH_SPARSE_OPT_SGD) FFH_SMALL(0) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_SMALL(1) else FFH_SMALL(2)
 #undef FFH_SMALL
+#undef FFH_SMALL_L
     FFH_LAUNCH_CHECK(c, "emb_sgd_small_kernel");
     return FFH_OK;
   }
@@ -1883,9 +1902,10 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   ra.arrive = (uint32_t*)(ws + lay.arrive);
   // segmented sums + both folds (32-block partials -> 1024-block partials -> row totals) + the SGD step: one launch
   dim3 rgrid((unsigned)((N + ra.tile - 1) / ra.tile), (unsigned)nt);
-#define FFH_RED(OPTV, MSDV)                                                                                                 \
-  { if (v4) hipLaunchKernelGGL((emb_sgd_reduce_kernel<4, OPTV, MSDV>), rgrid, dim3(kRedThreads), 0, as_stream(s), ra);        \
-    else hipLaunchKernelGGL((emb_sgd_reduce_kernel<1, OPTV, MSDV>), rgrid, dim3(kRedThreads), 0, as_stream(s), ra); }
+#define FFH_RED_L(OPTV, MSDV, LRPV)                                                                                               \
+  { if (v4) hipLaunchKernelGGL((emb_sgd_reduce_kernel<4, OPTV, MSDV, LRPV>), rgrid, dim3(kRedThreads), 0, as_stream(s), ra);        \
+    else hipLaunchKernelGGL((emb_sgd_reduce_kernel<1, OPTV, MSDV, LRPV>), rgrid, dim3(kRedThreads), 0, as_stream(s), ra); }
+#define FFH_RED(OPTV, MSDV) { if (lr_block) FFH_RED_L(OPTV, MSDV, true) else FFH_RED_L(OPTV, MSDV, false) }
 #ifdef FFH_MSD_TIMING
   static unsigned long long* dbg_buf = nullptr;
   if (!dbg_buf) hipMalloc(&dbg_buf, 8 * 8 * 65536);
@@ -1897,6 +1917,7 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   else if (msd) { if (kind == FFH_SPARSE_OPT_SGD) FFH_RED(0, true) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_RED(1, true) else FFH_RED(2, true) }
   else { if (kind == FFH_SPARSE_OPT_SGD) FFH_RED(0, false) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_RED(1, false) else FFH_RED(2, false) }
 #undef FFH_RED
+#undef FFH_RED_L
   FFH_LAUNCH_CHECK(c, "emb_sgd_reduce/fold");
 #ifdef FFH_MSD_TIMING
   {
@@ -1943,6 +1964,19 @@ int ffh_embedding_bwd_opt_apply_multi(ffh_ctx* c, const ffh_emb_table* tables, c
   return emb_bwd_phases(c, tables, nt, L, D, batch, aggr, opt->lr, s, false, true, opt, states);
 }
 
+// include/ff_hip_lr.h: the row rule's rate read from a state block in device memory
+int ffh_embedding_bwd_opt_fused_multi_lr(ffh_ctx* c, const ffh_emb_table* tables, const ffh_emb_state* states, int nt, int L, int D, int64_t batch,
+                                         int aggr, const ffh_sparse_opt* opt, const ffh_lr_state* block, ffh_stream s) {
+  if (!opt || !block) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt_fused_multi_lr: null ffh_sparse_opt or ffh_lr_state");
+  return emb_bwd_phases(c, tables, nt, L, D, batch, aggr, 0.0f, s, true, true, opt, states, nullptr, block);
+}
+
+int ffh_embedding_bwd_opt_apply_multi_lr(ffh_ctx* c, const ffh_emb_table* tables, const ffh_emb_state* states, int nt, int L, int D, int64_t batch,
+                                         int aggr, const ffh_sparse_opt* opt, const ffh_lr_state* block, ffh_stream s) {
+  if (!opt || !block) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt_apply_multi_lr: null ffh_sparse_opt or ffh_lr_state");
+  return emb_bwd_phases(c, tables, nt, L, D, batch, aggr, 0.0f, s, false, true, opt, states, nullptr, block);
+}
+
 int ffh_embedding_bwd_sgd_fused(ffh_ctx* c, const int64_t* idx, const float* g, float* weight, int L, int D, int64_t batch,
                                 int64_t num_entries, int64_t gld, int aggr, float lr, ffh_stream s) {
   ffh_emb_table t{idx, weight, const_cast<float*>(g), num_entries, gld};
@@ -1976,14 +2010,14 @@ static int bf16_tables(ffh_ctx* c, const ffh_emb_table_bf16* in, int nt, ffh_emb
 
 static int emb_bwd_bf16(ffh_ctx* c, const ffh_emb_table_bf16* tables, int nt, int L, int D, int64_t batch, int aggr, float lr,
                         const ffh_bf16_rounding* r, ffh_stream s, bool do_sort, bool do_apply,
-                        const ffh_sparse_opt* opt = nullptr, const ffh_emb_state* states = nullptr) {
+                        const ffh_sparse_opt* opt = nullptr, const ffh_emb_state* states = nullptr, const ffh_lr_state* lr_block = nullptr) {
   ffh_emb_table t[FFH_MAX_TABLES];
   Bf16Cfg cfg;
   memset(&cfg, 0, sizeof cfg);
   cfg.r = r;
   const int rc = bf16_tables(c, tables, nt, t, &cfg.keys);
   if (rc) return rc;
-  return emb_bwd_phases(c, t, nt, L, D, batch, aggr, lr, s, do_sort, do_apply, opt, states, &cfg);
+  return emb_bwd_phases(c, t, nt, L, D, batch, aggr, lr, s, do_sort, do_apply, opt, states, &cfg, lr_block);
 }
 
 extern "C" {
@@ -2021,6 +2055,20 @@ int ffh_embedding_bwd_opt_apply_multi_bf16(ffh_ctx* c, const ffh_emb_table_bf16*
                                            int64_t batch, int aggr, const ffh_sparse_opt* opt, const ffh_bf16_rounding* r, ffh_stream s) {
   if (!opt) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt_apply_multi_bf16: null ffh_sparse_opt");
   return emb_bwd_bf16(c, tables, nt, L, D, batch, aggr, opt->lr, r, s, false, true, opt, states);
+}
+
+int ffh_embedding_bwd_opt_fused_multi_bf16_lr(ffh_ctx* c, const ffh_emb_table_bf16* tables, const ffh_emb_state* states, int nt, int L, int D,
+                                              int64_t batch, int aggr, const ffh_sparse_opt* opt, const ffh_bf16_rounding* r, const ffh_lr_state* block,
+                                              ffh_stream s) {
+  if (!opt || !block) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt_fused_multi_bf16_lr: null ffh_sparse_opt or ffh_lr_state");
+  return emb_bwd_bf16(c, tables, nt, L, D, batch, aggr, 0.0f, r, s, true, true, opt, states, block);
+}
+
+int ffh_embedding_bwd_opt_apply_multi_bf16_lr(ffh_ctx* c, const ffh_emb_table_bf16* tables, const ffh_emb_state* states, int nt, int L, int D,
+                                              int64_t batch, int aggr, const ffh_sparse_opt* opt, const ffh_bf16_rounding* r, const ffh_lr_state* block,
+                                              ffh_stream s) {
+  if (!opt || !block) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt_apply_multi_bf16_lr: null ffh_sparse_opt or ffh_lr_state");
+  return emb_bwd_bf16(c, tables, nt, L, D, batch, aggr, 0.0f, r, s, false, true, opt, states, block);
 }
 
 int ffh_init_uniform_bf16(ffh_ctx* c, uint16_t* p, int64_t n, uint64_t seed, float lo, float hi, ffh_stream s) {

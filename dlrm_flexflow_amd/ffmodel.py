@@ -88,6 +88,9 @@ def lib() -> C.CDLL:
         "flexflow_config_set_device": (None, [H, I]), "flexflow_config_set_enable_graph": (None, [H, B]),
         "flexflow_config_set_overlap_embedding": (None, [H, B]), "flexflow_config_set_dense_embedding_update": (None, [H, B]),
         "flexflow_config_set_embedding_dtype": (None, [H, I]), "flexflow_config_set_embedding_rounding": (None, [H, I]),
+        "flexflow_config_set_lr_schedule": (None, [H, C.c_int64, C.c_int64, C.c_int64, I]),
+        "flexflow_lr_schedule_value": (D, [C.c_int64, D, C.c_int64, C.c_int64, C.c_int64]),
+        "flexflow_model_get_current_lr": (D, [H]),
         "flexflow_model_create": (H, [H]), "flexflow_model_destroy": (None, [H]),
         "flexflow_tensor_create": (H, [H, I, IP, I, B]),
         "flexflow_model_add_dense": (H, [H, H, I, I, B, H, H, C.c_char_p]),
@@ -158,6 +161,12 @@ def auc_from_histograms(hist_pos, hist_neg) -> float:
     if hp.shape != hn.shape or hp.ndim != 1:
         raise ValueError("auc_from_histograms: two 1-D arrays of equal length")
     return float(lib().flexflow_auc_from_histograms(hp.ctypes.data, hn.ctypes.data, hp.shape[0]))
+
+
+def lr_schedule_value(k: int, base: float, W: int = 0, S: int = 0, N: int = 0) -> float:
+    """The learning-rate schedule of include/ff_hip_lr.h, a pure function: the rate of zero-based optimizer step k, computed in double and
+    rounded to float once (linear warm-up over W steps, `base`, quadratic decay over N steps from step S, then held)."""
+    return float(lib().flexflow_lr_schedule_value(int(k), float(base), int(W), int(S), int(N)))
 
 
 def _argv(args):
@@ -261,8 +270,17 @@ class FFConfig:
                           lambda s, v: lib().flexflow_config_set_batch_size(s.h, v))
 
     def set(self, seed=None, device=None, enable_graph=None, overlap_embedding=None, dense_embedding_update=None,
-            embedding_dtype=None, embedding_rounding=None):
-        """embedding_dtype: "fp32" | "bf16"; embedding_rounding: "stochastic" | "nearest" (the --embedding-* flags)"""
+            embedding_dtype=None, embedding_rounding=None, lr_warmup_steps=None, lr_decay_start_step=None, lr_num_decay_steps=None,
+            device_lr=None):
+        """embedding_dtype: "fp32" | "bf16"; embedding_rounding: "stochastic" | "nearest" (the --embedding-* flags).
+        lr_*: the schedule of --lr-num-warmup-steps / --lr-decay-start-step / --lr-num-decay-steps; device_lr: True = --device-lr,
+        False = --host-lr-schedule, None = compile() chooses the route."""
+        if any(v is not None for v in (lr_warmup_steps, lr_decay_start_step, lr_num_decay_steps, device_lr)):
+            self._lr = tuple(old if new is None else int(new) for old, new in zip(getattr(self, "_lr", (0, 0, 0)),
+                                                                               (lr_warmup_steps, lr_decay_start_step, lr_num_decay_steps)))
+            if device_lr is not None:
+                self._device_lr = 1 if device_lr else -1
+            lib().flexflow_config_set_lr_schedule(self.h, *self._lr, getattr(self, "_device_lr", 0))
         if seed is not None: lib().flexflow_config_set_seed(self.h, seed)
         if device is not None: lib().flexflow_config_set_device(self.h, device)
         if enable_graph is not None: lib().flexflow_config_set_enable_graph(self.h, enable_graph)
@@ -382,6 +400,10 @@ class FFModel:
     def layer_output(self, layer) -> Tensor: return Tensor(lib().flexflow_model_get_layer_output(self.h, layer), self)
     @property
     def stream(self) -> int: return lib().flexflow_model_get_stream(self.h) or 0
+    def current_lr(self) -> float:
+        """The scheduled rate of the next optimizer step (base: the optimizer's lr / alpha), as the float the kernels receive."""
+        return float(lib().flexflow_model_get_current_lr(self.h))
+
     @property
     def uses_graph(self) -> bool: return bool(lib().flexflow_model_uses_graph(self.h))
     def set_trace_mode(self, mode: int): lib().flexflow_model_set_trace_mode(self.h, int(mode))

@@ -86,6 +86,23 @@ const KernelApi* load_kernel_api(const std::string& path_in) {
     }
     api->ctr = b;
   }
+  // the learning-rate extension (include/ff_hip_lr.h): the same rule
+  if (dlsym(h, "ffh_lr_abi_version")) {
+    KernelApiLr* b = new KernelApiLr();
+#define FFH_LOAD(name)                                                        \
+  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
+  if (!b->name) {                                                             \
+    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_lr.h: %s is missing\n", path.c_str(), #name);   \
+    abort();                                                                  \
+  }
+    FFH_LR_API_LIST(FFH_LOAD)
+#undef FFH_LOAD
+    if (b->ffh_lr_abi_version() != FFH_LR_ABI_VERSION) {
+      fprintf(stderr, "FATAL: %s has learning-rate ABI version %d, expected %d\n", path.c_str(), b->ffh_lr_abi_version(), FFH_LR_ABI_VERSION);
+      abort();
+    }
+    api->lr = b;
+  }
   if (path_in.empty() && g_env_override)
     fprintf(stderr, "[DLRM] FFH_BACKEND_LIB: kernel library %s (%s)\n", path.c_str(), api->ffh_backend_name());
   cache[path] = api;

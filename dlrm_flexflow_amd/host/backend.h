@@ -6,6 +6,7 @@
 #include "../../include/ff_hip.h"
 #include "../../include/ff_hip_bf16.h"
 #include "../../include/ff_hip_ctr.h"
+#include "../../include/ff_hip_lr.h"
 
 // The optional bf16-table extension (include/ff_hip_bf16.h): all of its list or none of it.
 struct KernelApiBf16 {
@@ -21,12 +22,20 @@ struct KernelApiCtr {
 #undef FFH_DECL
 };
 
+// The optional learning-rate extension (include/ff_hip_lr.h: the state block in device memory and the optimizer entries that read it).
+struct KernelApiLr {
+#define FFH_DECL(name) decltype(&::name) name;
+  FFH_LR_API_LIST(FFH_DECL)
+#undef FFH_DECL
+};
+
 struct KernelApi {
 #define FFH_DECL(name) decltype(&::name) name;
   FFH_API_LIST(FFH_DECL)
 #undef FFH_DECL
   const KernelApiBf16* bf16 = nullptr;   // null: the library does not export the extension (e.g. the CPU oracle)
   const KernelApiCtr* ctr = nullptr;     // likewise for include/ff_hip_ctr.h
+  const KernelApiLr* lr = nullptr;       // likewise for include/ff_hip_lr.h
   void* handle;
   std::string path;
   bool overridden = false;      // chosen by --backend or $FFH_BACKEND_LIB rather than the product default: the driver says so on its THROUGHPUT line

@@ -382,8 +382,9 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
   // Use SGD Optimizer [ref: examples/cpp/DLRM/dlrm.cc:130: SGDOptimizer(&ff, 0.01f), the reference driver's only choice].
   // --optimizer (this build): the other optimizers of the reference's library behind the same driver -- "sgd-momentum" =
   // SGDOptimizer(lr 0.01, momentum 0.9), "adam" = AdamOptimizer with its defaults [ref: include/optimizer.h:40-42,62-85]
-  if (dlrm.optimizer == "sgd") optimizer = new SGDOptimizer(ff, 0.01f);
-  else if (dlrm.optimizer == "sgd-momentum") optimizer = new SGDOptimizer(ff, 0.01f, 0.9f);
+  // SGD's rate is --lr (FFConfig::learningRate; its default is the reference driver's 0.01f): the base rate of the schedule
+  if (dlrm.optimizer == "sgd") optimizer = new SGDOptimizer(ff, ffconfig.learningRate);
+  else if (dlrm.optimizer == "sgd-momentum") optimizer = new SGDOptimizer(ff, ffconfig.learningRate, 0.9f);
   else if (dlrm.optimizer == "adam") optimizer = new AdamOptimizer(ff);
   else { fprintf(stderr, "FATAL: --optimizer %s: 'sgd', 'sgd-momentum' or 'adam'\n", dlrm.optimizer.c_str()); abort(); }
   std::vector<MetricsType> metrics;
@@ -398,6 +399,9 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
     check_eval_batches(ffconfig.eval_batches, random_num_samples(ffconfig, dlrm, std::max(1, ffconfig.comm.world_size)) / ffconfig.batchSize);
   if (chatty) printf("[DLRM] loss: %s\n", bce ? "bce" : "mse");
   ff->compile(optimizer, (LossType)ffconfig.driver_loss, metrics);
+  // which learning-rate route runs, and why; silent without the flags
+  if (chatty && (ffconfig.lr_warmup_steps || ffconfig.lr_num_decay_steps || ffconfig.lr_decay_start_step || ffconfig.device_lr || ffconfig.host_lr_schedule))
+    printf("[DLRM] lr schedule: %s\n", ff->lr_schedule_line().c_str());
   if (chatty && ffconfig.embedding_dtype == DT_BF16) {
     // what --embedding-dtype bf16 did: data-parallel (replicated) tables live in the dense slab and stay fp32
     size_t bytes = 0;

@@ -27,6 +27,7 @@
 #include "../../include/ff_hip.h"
 #include "../../include/ff_hip_bf16.h"
 #include "../../include/ff_hip_ctr.h"
+#include "../../include/ff_hip_lr.h"
 #include "ffcomm.h"
 
 // ---- enums: identical values to [ref: include/ffconst.h:4-57] -------------------------------
@@ -158,6 +159,11 @@ class FFConfig {
   bool force_exchange;         // run the all-to-all / all-reduce path even with one rank (tests the collectives on 1 GPU)
   DataType embedding_dtype;    // --embedding-dtype fp32|bf16: storage of the tables the fused update owns (table-wise; compile() refuses sharded ones); DT_FLOAT or DT_BF16
   int embedding_rounding;      // --embedding-rounding stochastic|nearest: FFH_BF16_ROUND_STOCHASTIC / _NEAREST (include/ffh_bf16.h) of the bf16 table update
+  // learning-rate schedule (include/ff_hip_lr.h): linear warm-up over lr_warmup_steps, then the optimizer's rate, then a quadratic
+  // decay over lr_num_decay_steps from lr_decay_start_step on; all 0: the constant rate of before
+  int64_t lr_warmup_steps, lr_decay_start_step, lr_num_decay_steps;   // --lr-num-warmup-steps / --lr-decay-start-step / --lr-num-decay-steps
+  bool device_lr;              // --device-lr: the rate lives in device memory even when it is constant (a captured step can then replay Adam)
+  bool host_lr_schedule;       // --host-lr-schedule: the scheduled value is a launch argument computed on the host each step (A/B; never captured)
   ffcomm comm;                 // rank / world_size / collectives supplied by the launcher (ffcomm.h)
 };
 
@@ -631,6 +637,24 @@ class FFModel {
   uint64_t read_bf16_counter() const;          // device -> host (synchronises)
   void advance_bf16_counter(ffh_stream s, ffh_ctx* cx) const;
   size_t bf16_tables_per_launch() const;      // FFH_MAX_TABLES, or FFH_BF16_MAX_STATEFUL_TABLES for momentum / Adam on bf16 tables
+  // learning-rate schedule (FFConfig::lr_*).  kLrHost: the rate of step k is written into the optimizer object before the step
+  // and travels as a launch argument (any library, any path; never captured).  kLrDevice: one ffh_lr_state block per READER STREAM --
+  // [0] the dense optimizer (compute stream), [1] the table update (whichever stream it is issued on) -- each advanced by a one-lane launch
+  // enqueued right behind its own reader, so neither stream ever sees another step's value, eager or replayed.
+  enum LrRoute { kLrOff = 0, kLrHost = 1, kLrDevice = 2 };
+  int lr_route = kLrOff;
+  std::string lr_route_why;                   // why this route (the driver's start-up line)
+  double lr_base = 0.0;                       // the optimizer's own rate at compile(): --lr / alpha
+  int64_t lr_host_steps = 0;                  // kLrHost: optimizer steps taken
+  ffh_lr_state* lr_block[2] = {nullptr, nullptr};
+  void lr_choose_route();                     // compile(): refusals, the route and its reason
+  void lr_allocate();                         // compile(): the blocks (kLrDevice) / the rate of step 0 (kLrHost)
+  void lr_host_set(int64_t k);                // kLrHost: the rate of step k into the optimizer object
+  void advance_lr(int which, ffh_stream s, ffh_ctx* cx) const;   // kLrDevice: behind the step's reader of lr_block[which], on its stream
+  double current_lr();                        // the scheduled rate of the next optimizer step (base rate: --lr / alpha), as the float the kernels get
+  int64_t lr_steps();                         // optimizer steps taken (kLrDevice: read back from lr_block[0]; synchronises)
+  std::string lr_schedule_line() const;       // "W=.. S=.. N=.. route=..": the driver's start-up line
+  mutable int64_t n_graph_replays = 0;        // hipGraph launches of an already captured trace (tests: flexflow_model_get_counter "graph_replays")
   mutable int64_t n_early_sorts = 0;          // sort-only launches issued behind the gather (tests: flexflow_model_get_counter "early_sorts")
   bool fused_embedding_update() const;        // the tables are updated on the sorted segments (plain SGD, or any optimizer with --sparse-embedding-optimizer)
   bool sparse_rule(ffh_sparse_opt& rule) const;   // the row rule in force; false: plain SGD

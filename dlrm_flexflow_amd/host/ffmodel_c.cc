@@ -45,6 +45,12 @@ void flexflow_config_set_embedding_rounding(flexflow_config_t h, int mode) {
   if (mode != 0 && mode != 1) { fprintf(stderr, "FATAL: embedding rounding %d: 0 (stochastic) or 1 (nearest)\n", mode); abort(); }
   C(h)->embedding_rounding = mode;
 }
+void flexflow_config_set_lr_schedule(flexflow_config_t h, int64_t warmup_steps, int64_t decay_start_step, int64_t num_decay_steps, int device_lr) {
+  C(h)->lr_warmup_steps = warmup_steps; C(h)->lr_decay_start_step = decay_start_step; C(h)->lr_num_decay_steps = num_decay_steps;
+  C(h)->device_lr = device_lr == 1;
+  C(h)->host_lr_schedule = device_lr == -1;
+}
+double flexflow_lr_schedule_value(int64_t k, double base, int64_t W, int64_t S, int64_t N) { return (double)(float)ffh_lr_schedule_value(k, base, W, S, N); }
 
 flexflow_model_t flexflow_model_create(flexflow_config_t c) { flexflow_model_t h; h.impl = new FFModel(*C(c)); return h; }
 void flexflow_model_destroy(flexflow_model_t h) { delete M(h); }
@@ -128,6 +134,7 @@ flexflow_tensor_t flexflow_model_get_parameter(flexflow_model_t m, int l, int i)
 }
 flexflow_tensor_t flexflow_model_get_layer_output(flexflow_model_t m, int l) { return wrap(M(m)->layers.at(l)->outputs[0]); }
 void* flexflow_model_get_stream(flexflow_model_t m) { return M(m)->stream; }
+double flexflow_model_get_current_lr(flexflow_model_t m) { return M(m)->current_lr(); }
 int flexflow_model_uses_graph(flexflow_model_t m) { return M(m)->config.enable_graph ? 1 : 0; }
 void flexflow_model_set_trace_mode(flexflow_model_t m, int mode) { M(m)->config.trace_mode = mode; }
 int flexflow_model_trace_replays(flexflow_model_t m, int trace_id) { return M(m)->trace_replays(trace_id) ? 1 : 0; }
@@ -146,6 +153,9 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   if (n == "direct_allreduces") return M(m)->n_direct_allreduces;
   if (n == "bf16_updates") return (int64_t)M(m)->read_bf16_counter();
   if (n == "early_sorts") return M(m)->n_early_sorts;
+  if (n == "lr_steps") return M(m)->lr_steps();
+  if (n == "lr_route") return M(m)->lr_route;          // 0 off (the scalar launches of before), 1 host, 2 device
+  if (n == "graph_replays") return M(m)->n_graph_replays;
   if (n == "tensor_op_exact_backward_layers") {      // Linear layers whose backward runs in exact mode under --allow-tensor-op-math-conversion (allocate() step 7)
     int64_t k = 0;
     for (Op* op : M(m)->layers) if (op->op_type == OP_LINEAR && static_cast<Linear*>(op)->bwd_exact) k++;

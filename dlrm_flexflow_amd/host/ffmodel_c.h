@@ -54,6 +54,11 @@ void flexflow_config_set_dense_embedding_update(flexflow_config_t, bool);
  * mode 0 stochastic (default) or 1 nearest even (include/ffh_bf16.h).  Other values abort. */
 void flexflow_config_set_embedding_dtype(flexflow_config_t, int data_type);
 void flexflow_config_set_embedding_rounding(flexflow_config_t, int mode);
+/* learning-rate schedule (include/ff_hip_lr.h): warm-up steps W, decay start step S, decay steps N (all 0: the constant rate); device_lr: 1 = the rate lives
+ * in device memory (--device-lr), -1 = force the host route (--host-lr-schedule), 0 = compile() chooses.  compile() refuses bad values, naming the flag. */
+void flexflow_config_set_lr_schedule(flexflow_config_t, int64_t warmup_steps, int64_t decay_start_step, int64_t num_decay_steps, int device_lr);
+/* the schedule itself, a pure function: the rate of zero-based step k as the float the kernels receive */
+double flexflow_lr_schedule_value(int64_t k, double base, int64_t W, int64_t S, int64_t N);
 
 /* FFModel */
 flexflow_model_t flexflow_model_create(flexflow_config_t);
@@ -106,6 +111,7 @@ flexflow_tensor_t flexflow_model_get_parameter(flexflow_model_t, int layer, int 
 flexflow_tensor_t flexflow_model_get_layer_output(flexflow_model_t, int layer);
 void* flexflow_model_get_stream(flexflow_model_t);
 int  flexflow_model_uses_graph(flexflow_model_t);
+double flexflow_model_get_current_lr(flexflow_model_t);   /* the scheduled rate of the next optimizer step (synchronises on the device route); counters "lr_steps", "lr_route", "graph_replays" */
 const char* flexflow_model_get_backend_name(flexflow_model_t);   /* ffh_backend_name() of the kernel library the model loaded: "hip-gfx950" | "oracle-cpu" */
 const char* flexflow_model_get_backend_path(flexflow_model_t);   /* ... and the file it was loaded from */
 void flexflow_model_set_trace_mode(flexflow_model_t, int mode);   /* 0: replay a trace only where that is not slower than launching it (decided on its first calls); 1: always replay */

@@ -1128,6 +1128,12 @@ void SGDOptimizer::next(void) {}
 void SGDOptimizer::update(const Parameter* p) {
   if (!p->impl->grad) return;   // embedding tables on the fused path have no dense gradient
   float* v = momentum > 0.0 ? v_values[p->impl->ptr] : nullptr;
+  if (model->lr_route == FFModel::kLrDevice) {      // the rate from the dense optimizer's block (include/ff_hip_lr.h); model->stream is its reader stream
+    model->check(model->api->lr->ffh_sgd_update_ex_lr(model->ctx, (float*)p->impl->ptr, p->impl->grad, v, (int64_t)(p->impl->bytes / sizeof(float)),
+                                                     model->lr_block[0], (float)weight_decay, (float)momentum, nesterov ? 1 : 0, 0, model->stream),
+                 "sgd_update_ex_lr");
+    return;
+  }
   model->check(model->api->ffh_sgd_update(model->ctx, (float*)p->impl->ptr, p->impl->grad, v, (int64_t)(p->impl->bytes / sizeof(float)), (float)lr,
                                           (float)weight_decay, (float)momentum, nesterov ? 1 : 0, model->stream), "sgd_update");
 }

@@ -187,7 +187,10 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
   // on the capturing stream itself the capture works, so a captured exchange step runs its embedding branch on the compute stream.
   // (first: Adam never captures -- alpha_t is a new launch argument every step -- so it must not lose the side-stream overlap to a
   //  capture that will not happen; round-4 advisor)
-  if (dynamic_cast<AdamOptimizer*>(optimizer) && config.enable_graph) config.enable_graph = false;
+  //  With the rate in device memory (lr_route == kLrDevice, include/ff_hip_lr.h) alpha_t is no launch argument any more and Adam captures like SGD;
+  //  a schedule on the host route makes the rate of EVERY optimizer a new launch argument each step and switches capture off the same way.)
+  lr_choose_route();
+  if (lr_route != kLrDevice && (dynamic_cast<AdamOptimizer*>(optimizer) || lr_route == kLrHost) && config.enable_graph) config.enable_graph = false;
   // bf16 tables (--embedding-dtype bf16, include/ff_hip_bf16.h): the fused sorted-segments update owns them, so every case it does not
   // cover is refused here, before anything is allocated or launched
   if (config.embedding_dtype == DT_BF16 && !embeddings.empty()) {
@@ -243,6 +246,7 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
     }
   compiled = true;
   optimizer->init();
+  lr_allocate();
   {   // per-row optimizer state of the touched-rows rule: the shape of the local table (+ the zero row of a row block)
     ffh_sparse_opt rule;
     if (fused_embedding_update() && sparse_rule(rule)) {

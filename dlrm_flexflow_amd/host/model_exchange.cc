@@ -11,6 +11,9 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
   const bool fwd = what == kGather;
   ffh_sparse_opt rule;
   const bool ruled = (what == kFusedUpdate || what == kApplyOnly) && ff->sparse_rule(rule);     // momentum / wd SGD, Adam on the touched rows
+  // the rate from device memory (include/ff_hip_lr.h): the opt entries with the table update's own block; kind FFH_SPARSE_OPT_SGD = the plain update's bits
+  const ffh_lr_state* lrb = ff->lr_route == FFModel::kLrDevice ? ff->lr_block[1] : nullptr;
+  const KernelApiLr* lra = ff->api->lr;
   const int L = ff->embeddings[0]->inputs[0].adim[0];
   const int aggr = (int)ff->embeddings[0]->aggr;
   // by shard width, then storage (bf16 tables: include/ff_hip_bf16.h, keyed by global table index and global column)
@@ -53,12 +56,14 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
         switch (what) {
           case kGather: ff->check(b16->ffh_embedding_fwd_multi_bf16(cx, tb, n, L, D, B, aggr, s), "embedding_fwd_multi_bf16"); break;
           case kFusedUpdate:
-            if (ruled) ff->check(b16->ffh_embedding_bwd_opt_fused_multi_bf16(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, s), "embedding_bwd_opt_fused_multi_bf16");
+            if (lrb) ff->check(lra->ffh_embedding_bwd_opt_fused_multi_bf16_lr(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, lrb, s), "embedding_bwd_opt_fused_multi_bf16_lr");
+            else if (ruled) ff->check(b16->ffh_embedding_bwd_opt_fused_multi_bf16(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, s), "embedding_bwd_opt_fused_multi_bf16");
             else ff->check(b16->ffh_embedding_bwd_sgd_fused_multi_bf16(cx, tb, n, L, D, B, aggr, rule.lr, &rnd, s), "embedding_bwd_sgd_fused_multi_bf16");
             break;
           case kSortOnly: ff->check(b16->ffh_embedding_bwd_sort_multi_bf16(cx, tb, n, L, D, B, s), "embedding_bwd_sort_multi_bf16"); ff->n_early_sorts++; break;
           case kApplyOnly:
-            if (ruled) ff->check(b16->ffh_embedding_bwd_opt_apply_multi_bf16(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, s), "embedding_bwd_opt_apply_multi_bf16");
+            if (lrb) ff->check(lra->ffh_embedding_bwd_opt_apply_multi_bf16_lr(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, lrb, s), "embedding_bwd_opt_apply_multi_bf16_lr");
+            else if (ruled) ff->check(b16->ffh_embedding_bwd_opt_apply_multi_bf16(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, s), "embedding_bwd_opt_apply_multi_bf16");
             else ff->check(b16->ffh_embedding_bwd_sgd_apply_multi_bf16(cx, tb, n, L, D, B, aggr, rule.lr, &rnd, s), "embedding_bwd_sgd_apply_multi_bf16");
             break;
         }
@@ -72,12 +77,14 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
       switch (what) {
         case kGather: ff->check(ff->api->ffh_embedding_fwd_multi(cx, tabs.data() + b, n, L, D, B, aggr, s), "embedding_fwd_multi"); break;
         case kFusedUpdate:
-          if (ruled) ff->check(ff->api->ffh_embedding_bwd_opt_fused_multi(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, s), "embedding_bwd_opt_fused_multi");
+          if (lrb) ff->check(lra->ffh_embedding_bwd_opt_fused_multi_lr(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, lrb, s), "embedding_bwd_opt_fused_multi_lr");
+          else if (ruled) ff->check(ff->api->ffh_embedding_bwd_opt_fused_multi(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, s), "embedding_bwd_opt_fused_multi");
           else ff->check(ff->api->ffh_embedding_bwd_sgd_fused_multi(cx, tabs.data() + b, n, L, D, B, aggr, rule.lr, s), "embedding_bwd_sgd_fused_multi");
           break;
         case kSortOnly: ff->check(ff->api->ffh_embedding_bwd_sort_multi(cx, tabs.data() + b, n, L, D, B, s), "embedding_bwd_sort_multi"); ff->n_early_sorts++; break;
         case kApplyOnly:
-          if (ruled) ff->check(ff->api->ffh_embedding_bwd_opt_apply_multi(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, s), "embedding_bwd_opt_apply_multi");
+          if (lrb) ff->check(lra->ffh_embedding_bwd_opt_apply_multi_lr(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, lrb, s), "embedding_bwd_opt_apply_multi_lr");
+          else if (ruled) ff->check(ff->api->ffh_embedding_bwd_opt_apply_multi(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, s), "embedding_bwd_opt_apply_multi");
           else ff->check(ff->api->ffh_embedding_bwd_sgd_apply_multi(cx, tabs.data() + b, n, L, D, B, aggr, rule.lr, s), "embedding_bwd_sgd_apply_multi");
           break;
       }
@@ -269,6 +276,7 @@ void FFModel::embedding_group_update(ffh_stream s, ffh_ctx* on_ctx) const {
     check(api->ffh_zero(cx, w + e->rows_local * (int64_t)D, (size_t)D * 4, s), "zero row");   // (its optimizer state is never read for a row of the block)
   }
   advance_bf16_counter(s, cx);
+  advance_lr(1, s, cx);      // behind this step's last reader of the table update's block, on its stream
 }
 
 // The reference's own table update on the rank(s) that hold a table, for optimizers the fused update does not cover (default for

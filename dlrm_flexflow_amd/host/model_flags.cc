@@ -72,6 +72,9 @@ FFConfig::FFConfig() {
   deterministic = false;
   embedding_dtype = DT_FLOAT;
   embedding_rounding = FFH_BF16_ROUND_STOCHASTIC;
+  lr_warmup_steps = lr_decay_start_step = lr_num_decay_steps = 0;
+  device_lr = false;
+  host_lr_schedule = false;
   memset(&comm, 0, sizeof comm);
   comm.rank = 0;
   comm.world_size = 1;
@@ -176,6 +179,11 @@ void FFConfig::parse_args(char** argv, int argc) {
       else die("--embedding-dtype %s: 'fp32' or 'bf16'", v);
       continue;
     }
+    if (is("--lr-num-warmup-steps")) { lr_warmup_steps = atoll(next()); continue; }
+    if (is("--lr-decay-start-step")) { lr_decay_start_step = atoll(next()); continue; }
+    if (is("--lr-num-decay-steps")) { lr_num_decay_steps = atoll(next()); continue; }
+    if (is("--device-lr")) { device_lr = true; continue; }
+    if (is("--host-lr-schedule")) { host_lr_schedule = true; continue; }
     if (is("--embedding-rounding")) {
       const char* v = next();
       if (!strcmp(v, "stochastic")) embedding_rounding = FFH_BF16_ROUND_STOCHASTIC;

@@ -352,8 +352,14 @@ void FFModel::update() {
   // one launch over the whole MLP slab; it also clears the gradients it consumed, so the next zero_gradients()
   // has nothing to sweep [ref: one update task per parameter, src/runtime/optimizer.cc:93-189,256-330]
   const size_t opt_count = mlp_count;
+  const ffh_lr_state* lrb = lr_route == kLrDevice ? lr_block[0] : nullptr;     // the rate from device memory (include/ff_hip_lr.h)
   if (adam) {
-    if (mlp_count) {
+    if (mlp_count && lrb) {
+      check(api->lr->ffh_adam_update_lr(ctx, mlp_weights, mlp_grads, adam->mlp_m, adam->mlp_v, (int64_t)opt_count, lrb, (float)adam->beta1,
+                                        (float)adam->beta2, (float)adam->weight_decay, (float)adam->epsilon, FFH_OPT_ZERO_GRAD, stream),
+            "adam_update_lr (MLP slab)");
+      mlp_grads_clean = true;
+    } else if (mlp_count) {
       check(api->ffh_adam_update(ctx, mlp_weights, mlp_grads, adam->mlp_m, adam->mlp_v, (int64_t)opt_count, (float)adam->alpha_t,
                                  (float)adam->beta1, (float)adam->beta2, (float)adam->weight_decay, (float)adam->epsilon,
                                  FFH_OPT_ZERO_GRAD, stream), "adam_update (MLP slab)");
@@ -362,6 +368,10 @@ void FFModel::update() {
   } else if (sgd->momentum > 0.0) {
     for (const Parameter& p : parameters)
       if (in_dense_slab(p)) sgd->update(&p);
+  } else if (mlp_count && lrb) {
+    check(api->lr->ffh_sgd_update_ex_lr(ctx, mlp_weights, mlp_grads, nullptr, (int64_t)opt_count, lrb, (float)sgd->weight_decay, 0.0f, 0, FFH_OPT_ZERO_GRAD,
+                                        stream), "sgd_update_ex_lr (MLP slab)");
+    mlp_grads_clean = true;
   } else if (mlp_count) {
     check(api->ffh_sgd_update_ex(ctx, mlp_weights, mlp_grads, nullptr, (int64_t)opt_count, (float)sgd->lr, (float)sgd->weight_decay, 0.0f,
                                  0, FFH_OPT_ZERO_GRAD, stream), "sgd_update (MLP slab)");
@@ -379,6 +389,10 @@ void FFModel::update() {
   } else {
     embedding_dense_update();
   }
+  // the schedule moves on: the dense optimizer's block behind its reader on `stream` (captured with the step, so a replay advances it too);
+  // the host route writes the next step's rate into the optimizer object (the table update of that step is issued before its update())
+  advance_lr(0, stream, ctx);
+  if (lr_route == kLrHost) lr_host_set(++lr_host_steps);
 }
 
 bool FFModel::trace_replays(int trace_id) const {
@@ -461,6 +475,7 @@ void FFModel::end_trace(int trace_id) {
   }
   if (replaying_trace == trace_id) {
     check(api->ffh_graph_launch(ctx, graphs[trace_id], stream), "graph launch");
+    n_graph_replays++;
     replaying_trace = -1;
   }
 }
@@ -561,4 +576,104 @@ EvalMetrics FFModel::get_eval_metrics(bool with_histograms) {
     m.hist_neg.assign(e->hist_neg, e->hist_neg + FFH_AUC_BINS);
   }
   return m;
+}
+
+// =============================================================================================
+// learning-rate schedule (include/ff_hip_lr.h)
+// =============================================================================================
+void FFModel::lr_choose_route() {
+  const int64_t W = config.lr_warmup_steps, S = config.lr_decay_start_step, N = config.lr_num_decay_steps;
+  if (W < 0) die("--lr-num-warmup-steps %lld: must be >= 0", (long long)W);
+  if (S < 0) die("--lr-decay-start-step %lld: must be >= 0", (long long)S);
+  if (N < 0) die("--lr-num-decay-steps %lld: must be >= 0", (long long)N);
+  if (N > 0 && S < W)
+    die("--lr-decay-start-step %lld lies inside the warm-up of %lld steps: raise --lr-decay-start-step to at least --lr-num-warmup-steps (or lower that)",
+        (long long)S, (long long)W);
+  if (config.device_lr && config.host_lr_schedule) die("--device-lr and --host-lr-schedule exclude each other: drop one");
+  const bool scheduled = W > 0 || N > 0;
+  SGDOptimizer* sgd = dynamic_cast<SGDOptimizer*>(optimizer);
+  AdamOptimizer* adam = dynamic_cast<AdamOptimizer*>(optimizer);
+  lr_base = sgd ? sgd->lr : (adam ? adam->alpha : 0.0);
+  lr_route = kLrOff;
+  lr_route_why = "constant rate";
+  if (config.device_lr && !api->lr)
+    die("--device-lr: %s (%s) is a kernel library without the learning-rate extension (include/ff_hip_lr.h); drop --device-lr (a schedule then runs "
+        "on the host route)", api->path.c_str(), api->ffh_backend_name());
+  if (!scheduled && !config.device_lr) return;
+  if (config.computationMode != COMP_MODE_TRAINING) return;
+  // the device route needs an _lr form of every optimizer launch this model issues
+  const char* no = nullptr;
+  if (config.host_lr_schedule) no = "--host-lr-schedule";
+  else if (!api->lr) no = "the kernel library has no learning-rate extension";
+  else if (!sgd && !adam) no = "unknown optimizer";
+  else if (!embeddings.empty() && !fused_embedding_update()) no = "the tables take the owner-local dense update";
+  else if (config.profiling) no = "--profiling times the table update as the embedding group's backward";
+  else {
+    for (const Embedding* e : embeddings)
+      if (e->row_sharded) no = "a table is row-sharded";
+  }
+  if (!no) { lr_route = kLrDevice; lr_route_why = config.device_lr ? "--device-lr" : "every optimizer launch has an _lr form"; return; }
+  if (config.device_lr && !scheduled) {      // nothing to schedule: the scalar launches of before
+    lr_route_why = std::string("constant rate; --device-lr not possible: ") + no;
+    return;
+  }
+  lr_route = kLrHost;
+  lr_route_why = no;
+}
+
+void FFModel::lr_allocate() {
+  if (lr_route == kLrHost) { lr_host_steps = 0; lr_host_set(0); return; }
+  if (lr_route != kLrDevice) return;
+  AdamOptimizer* adam = dynamic_cast<AdamOptimizer*>(optimizer);
+  ffh_lr_schedule sc;
+  memset(&sc, 0, sizeof sc);
+  sc.base = lr_base; sc.warmup_steps = config.lr_warmup_steps; sc.decay_start = config.lr_decay_start_step; sc.decay_steps = config.lr_num_decay_steps;
+  if (adam) { sc.beta1 = adam->beta1; sc.beta2 = adam->beta2; }
+  for (int i = 0; i < 2; i++) {
+    lr_block[i] = (ffh_lr_state*)dmalloc(api->lr->ffh_lr_state_bytes());
+    check(api->lr->ffh_lr_state_init(ctx, lr_block[i], &sc, 0, stream), "lr_state_init");
+  }
+}
+
+void FFModel::lr_host_set(int64_t k) {
+  const double v = ffh_lr_schedule_value(k, lr_base, config.lr_warmup_steps, config.lr_decay_start_step, config.lr_num_decay_steps);
+  if (SGDOptimizer* sgd = dynamic_cast<SGDOptimizer*>(optimizer)) sgd->lr = v;
+  else if (AdamOptimizer* adam = dynamic_cast<AdamOptimizer*>(optimizer)) adam->alpha = v;
+}
+
+void FFModel::advance_lr(int which, ffh_stream s, ffh_ctx* cx) const {
+  if (lr_route == kLrDevice) check(api->lr->ffh_lr_state_advance(cx, lr_block[which], s), "lr_state_advance");
+}
+
+int64_t FFModel::lr_steps() {
+  if (lr_route == kLrHost) return lr_host_steps;
+  if (lr_route != kLrDevice) return 0;
+  sync();
+  ffh_lr_values v;
+  check(api->lr->ffh_lr_state_read(ctx, lr_block[0], &v, stream), "lr_state_read");
+  return v.k;
+}
+
+double FFModel::current_lr() {
+  if (lr_route == kLrDevice) {
+    sync();
+    ffh_lr_values v;
+    check(api->lr->ffh_lr_state_read(ctx, lr_block[0], &v, stream), "lr_state_read");
+    return (double)v.lr;
+  }
+  const int64_t k = lr_route == kLrHost ? lr_host_steps : 0;
+  if (lr_route == kLrOff) {
+    if (SGDOptimizer* sgd = dynamic_cast<SGDOptimizer*>(optimizer)) return (double)(float)sgd->lr;
+    if (AdamOptimizer* adam = dynamic_cast<AdamOptimizer*>(optimizer)) return (double)(float)adam->alpha;
+    return 0.0;
+  }
+  return (double)(float)ffh_lr_schedule_value(k, lr_base, config.lr_warmup_steps, config.lr_decay_start_step, config.lr_num_decay_steps);
+}
+
+std::string FFModel::lr_schedule_line() const {
+  char buf[512];
+  snprintf(buf, sizeof buf, "warmup W=%lld, decay start S=%lld, decay steps N=%lld, base %g, route=%s (%s)", (long long)config.lr_warmup_steps,
+           (long long)config.lr_decay_start_step, (long long)config.lr_num_decay_steps, lr_base,
+           lr_route == kLrDevice ? "device" : (lr_route == kLrHost ? "host" : "off"), lr_route_why.c_str());
+  return buf;
 }
