@@ -251,6 +251,45 @@ _SIGS_LR = {
 }
 
 
+# include/ff_hip_data.h: the optional data extension (one shuffled training batch gathered in one launch); same rule
+DATA_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_data.h")
+GATHER_LOCAL_ROWS, GATHER_GLOBAL_ROWS = 0, 1
+GATHER_MAX_SEGMENTS = 64
+
+
+class GatherSegment(C.Structure):
+    """struct ffh_gather_segment"""
+    _fields_ = [("src", P), ("dst", P), ("row_bytes", C.c_int32), ("kind", C.c_int32)]
+
+
+class BatchOrder(C.Structure):
+    """struct ffh_batch_order"""
+    _fields_ = [("seed", U64), ("epoch", L), ("step", L), ("local_batch", L), ("n_local", L), ("world", C.c_int32), ("rank", C.c_int32)]
+
+
+_SIGS_DATA = {
+    "ffh_data_abi_version": (I, []),
+    "ffh_batch_gather": (I, [P, C.POINTER(GatherSegment), I, C.POINTER(BatchOrder), P]),
+}
+
+
+def data_header_symbols(header_path: str = DATA_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_DATA_API_LIST X-macro in include/ff_hip_data.h."""
+    text = open(header_path).read()
+    m = re.search(r"#define FFH_DATA_API_LIST\(X\)(.*?)\n\n", text, re.S)
+    if not m:
+        raise RuntimeError("FFH_DATA_API_LIST not found in " + header_path)
+    return re.findall(r"X\((\w+)\)", m.group(1))
+
+
+def data_header_abi_version(header_path: str = DATA_HEADER_PATH) -> int:
+    """FFH_DATA_ABI_VERSION of include/ff_hip_data.h."""
+    m = re.search(r"#define\s+FFH_DATA_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_DATA_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
 def lr_header_symbols(header_path: str = LR_HEADER_PATH) -> list[str]:
     """Every symbol of the FFH_LR_API_LIST X-macro in include/ff_hip_lr.h."""
     text = open(header_path).read()
@@ -558,6 +597,40 @@ class LrApi:
 def lr_api(lib: FFHLib) -> LrApi:
     """The learning-rate entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
     return LrApi(lib)
+
+
+class DataApi:
+    """The data extension (include/ff_hip_data.h) of a loaded FFHLib; `data_api(lib)` builds it or raises."""
+
+    def __init__(self, lib: FFHLib):
+        self.base = lib
+        for name, (res, args) in _SIGS_DATA.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no data extension ({name} missing; include/ff_hip_data.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_data_abi_version()
+        if got != data_header_abi_version():
+            raise FFHError(f"{lib.path}: data ABI version {got}, include/ff_hip_data.h says {data_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+    def batch_gather_rc(self, segments, seed, epoch, step, local_batch, n_local, world=1, rank=0, stream=None) -> int:
+        """ffh_batch_gather; `segments`: (src, dst, row_bytes, kind) tuples, pointers as tensors/arrays/ints/None.  Returns the status code."""
+        arr = (GatherSegment * max(1, len(segments)))()
+        for k, (src, dst, row_bytes, kind) in enumerate(segments):
+            arr[k] = GatherSegment(ptr(src), ptr(dst), int(row_bytes), int(kind))
+        order = BatchOrder(int(seed) & (2**64 - 1), int(epoch), int(step), int(local_batch), int(n_local), int(world), int(rank))
+        return self.lib.ffh_batch_gather(self.ctx, arr, len(segments), C.byref(order), ptr(stream))
+
+    def batch_gather(self, segments, seed, epoch, step, local_batch, n_local, world=1, rank=0, stream=None):
+        self.base.check(self.batch_gather_rc(segments, seed, epoch, step, local_batch, n_local, world, rank, stream), "ffh_batch_gather")
+
+
+def data_api(lib: FFHLib) -> DataApi:
+    """The data entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
+    return DataApi(lib)
 
 
 _hip_singleton: FFHLib | None = None

@@ -91,6 +91,8 @@ def lib() -> C.CDLL:
         "flexflow_config_set_lr_schedule": (None, [H, C.c_int64, C.c_int64, C.c_int64, I]),
         "flexflow_lr_schedule_value": (D, [C.c_int64, D, C.c_int64, C.c_int64, C.c_int64]),
         "flexflow_model_get_current_lr": (D, [H]),
+        "flexflow_shuffle_index": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
+        "flexflow_shuffle_indices": (None, [C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, P]),
         "flexflow_model_create": (H, [H]), "flexflow_model_destroy": (None, [H]),
         "flexflow_tensor_create": (H, [H, I, IP, I, B]),
         "flexflow_model_add_dense": (H, [H, H, I, I, B, H, H, C.c_char_p]),
@@ -167,6 +169,24 @@ def lr_schedule_value(k: int, base: float, W: int = 0, S: int = 0, N: int = 0) -
     """The learning-rate schedule of include/ff_hip_lr.h, a pure function: the rate of zero-based optimizer step k, computed in double and
     rounded to float once (linear warm-up over W steps, `base`, quadratic decay over N steps from step S, then held)."""
     return float(lib().flexflow_lr_schedule_value(int(k), float(base), int(W), int(S), int(N)))
+
+
+def shuffle_index(seed: int, epoch: int, i: int, n: int) -> int:
+    """The order of --data-randomize total, a pure function (ffh_perm_index of include/ffh_perm.h): the row of a stripe of n rows that
+    position i of epoch `epoch` trains on.  For every (seed, epoch) a bijection of [0, n)."""
+    if not 0 <= int(i) < max(int(n), 1):
+        raise ValueError(f"shuffle_index: position {i} outside [0, {n})")
+    return int(lib().flexflow_shuffle_index(int(seed) & (2**64 - 1), int(epoch), int(i), int(n)))
+
+
+def shuffle_indices(seed: int, epoch: int, n: int, first: int = 0, count: int | None = None) -> np.ndarray:
+    """shuffle_index for the positions first .. first + count - 1 (default: all n) as an int64 array."""
+    count = int(n) - int(first) if count is None else int(count)
+    if first < 0 or count < 0 or first + count > max(int(n), 1):
+        raise ValueError(f"shuffle_indices: positions [{first}, {first + count}) outside [0, {n})")
+    out = np.empty(count, np.uint64)
+    lib().flexflow_shuffle_indices(int(seed) & (2**64 - 1), int(epoch), int(first), count, int(n), out.ctypes.data)
+    return out.astype(np.int64)
 
 
 def _argv(args):
@@ -461,6 +481,9 @@ class DLRM:
     num_tables = property(lambda s: lib().flexflow_dlrm_get_num_tables(s.h))
     def sparse_input(self, t) -> Tensor: return Tensor(lib().flexflow_dlrm_get_sparse_input(self.h, t), self.model)
     def dense_input(self) -> Tensor: return Tensor(lib().flexflow_dlrm_get_dense_input(self.h), self.model)
+    def label_input(self) -> Tensor:
+        """the labels of the batch the latest step trained on (this rank's rows), beside sparse_input / dense_input"""
+        return self.model.label_tensor
     def warmup(self): lib().flexflow_dlrm_warmup(self.h)
     def train_steps(self, n, trace=True): lib().flexflow_dlrm_train_steps(self.h, n, trace)
     def run_epochs(self) -> float: return lib().flexflow_dlrm_run_epochs(self.h)

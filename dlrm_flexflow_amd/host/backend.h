@@ -7,6 +7,7 @@
 #include "../../include/ff_hip_bf16.h"
 #include "../../include/ff_hip_ctr.h"
 #include "../../include/ff_hip_lr.h"
+#include "../../include/ff_hip_data.h"
 
 // The optional bf16-table extension (include/ff_hip_bf16.h): all of its list or none of it.
 struct KernelApiBf16 {
@@ -29,6 +30,13 @@ struct KernelApiLr {
 #undef FFH_DECL
 };
 
+// The optional data extension (include/ff_hip_data.h: one shuffled training batch gathered in one launch).
+struct KernelApiData {
+#define FFH_DECL(name) decltype(&::name) name;
+  FFH_DATA_API_LIST(FFH_DECL)
+#undef FFH_DECL
+};
+
 struct KernelApi {
 #define FFH_DECL(name) decltype(&::name) name;
   FFH_API_LIST(FFH_DECL)
@@ -36,6 +44,7 @@ struct KernelApi {
   const KernelApiBf16* bf16 = nullptr;   // null: the library does not export the extension (e.g. the CPU oracle)
   const KernelApiCtr* ctr = nullptr;     // likewise for include/ff_hip_ctr.h
   const KernelApiLr* lr = nullptr;       // likewise for include/ff_hip_lr.h
+  const KernelApiData* data = nullptr;   // likewise for include/ff_hip_data.h
   void* handle;
   std::string path;
   bool overridden = false;      // chosen by --backend or $FFH_BACKEND_LIB rather than the product default: the driver says so on its THROUGHPUT line

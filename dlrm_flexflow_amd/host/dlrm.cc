@@ -122,7 +122,7 @@ static void check_eval_batches(int eval_batches, int nb);
 
 // =============================================================================================
 DataLoader::DataLoader(FFModel& ff, const DLRMConfig& dlrm, const std::vector<Tensor>& sparse_inputs, Tensor dense_input, Tensor label)
-    : num_samples(0), next_index(0), batch_sparse_inputs(sparse_inputs), batch_dense_input(dense_input), batch_label(label),
+    : num_samples(0), next_index(0), epoch(0), batch_sparse_inputs(sparse_inputs), batch_dense_input(dense_input), batch_label(label),
       full_dense(nullptr), full_label(nullptr), model(&ff) {
   num_train = 0;
   bag = dlrm.embedding_bag_size;
@@ -133,6 +133,12 @@ DataLoader::DataLoader(FFModel& ff, const DLRMConfig& dlrm, const std::vector<Te
   ff.check(ff.api->ffh_stream_sync(ff.ctx, ff.stream), "dataset sync");
   check_eval_batches(ff.config.eval_batches, num_samples / ff.config.batchSize);
   num_train = num_samples - ff.config.eval_batches * ff.config.batchSize;
+  if (ff.config.data_randomize) {
+    for (size_t t = 0; t < batch_sparse_inputs.size(); t++)
+      segments.push_back({full_sparse[t], full_sparse[t] ? batch_sparse_inputs[t].impl->ptr : nullptr, 8 * bag, FFH_GATHER_GLOBAL_ROWS});
+    segments.push_back({full_dense, batch_dense_input.impl->ptr, 4 * dense_dim, FFH_GATHER_LOCAL_ROWS});
+    segments.push_back({full_label, batch_label.impl->ptr, 4, FFH_GATHER_LOCAL_ROWS});
+  }
 }
 
 // samples of the synthetic data set [ref: dlrm.cc:272-276], whole batches
@@ -308,9 +314,27 @@ DataLoader::~DataLoader() {
 // [ref: examples/cpp/DLRM/dlrm.cc:482-585, dlrm.cu:19-122]: device-to-device copies on the compute stream
 void DataLoader::next_batch(FFModel& ff) {
   const int B = ff.config.batchSize;
-  if (next_index + B > num_train) next_index = 0;
-  load_batch(ff, next_index / B);
+  if (next_index + B > num_train) { next_index = 0; epoch++; }      // (file order: every epoch is the same)
+  if (ff.config.data_randomize) gather_batch(ff, next_index / B);
+  else load_batch(ff, next_index / B);
   next_index += B;
+}
+
+// --data-randomize total (include/ffh_perm.h states the order and the stripe rule): where load_batch copies one block per
+// array, the rows of a shuffled batch are scattered -- one gather launch on the compute stream, outside any captured step
+void DataLoader::gather_batch(FFModel& ff, int64_t step) {
+  const int64_t Bl = ff.local_batch;
+  ffh_batch_order order;
+  order.seed = ff.config.seed;
+  order.epoch = epoch;
+  order.step = step;
+  order.local_batch = Bl;
+  order.n_local = (int64_t)(num_train / ff.config.batchSize) * Bl;
+  order.world = std::max(1, ff.world_size);
+  order.rank = ff.rank;
+  ff.order_input_writes_behind_update();       // as load_batch
+  ff.check(ff.api->data->ffh_batch_gather(ff.ctx, segments.data(), (int)segments.size(), &order, ff.stream), "batch gather");
+  ff.inputs_dirty = true;
 }
 
 void DataLoader::load_batch(FFModel& ff, int k) {
@@ -398,6 +422,17 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
   if (ffconfig.eval_batches > 0 && dlrm.dataset_path.empty())
     check_eval_batches(ffconfig.eval_batches, random_num_samples(ffconfig, dlrm, std::max(1, ffconfig.comm.world_size)) / ffconfig.batchSize);
   if (chatty) printf("[DLRM] loss: %s\n", bce ? "bce" : "mse");
+  // --data-randomize total reorders what train_steps loads; a run that loads nothing per step has nothing to reorder
+  if (ffconfig.data_randomize && dlrm.dataset_path.empty() && ffconfig.synthetic_labels != 1) {
+    fprintf(stderr, "FATAL: --data-randomize total: this run never advances its batch (plain synthetic data trains on the warm-up batch again and again); "
+                    "give it a data set to walk with --dataset FILE or --synthetic-labels logistic, or use --data-randomize none\n");
+    abort();
+  }
+  if (chatty) {
+    if (!ffconfig.data_randomize) printf("[DLRM] data order: none (file order, the same every epoch)\n");
+    else printf("[DLRM] data order: total (seed %llu, a new order every epoch%s)\n", (unsigned long long)ffconfig.seed,
+                ffconfig.comm.world_size > 1 ? ", per-rank stripes" : "");
+  }
   ff->compile(optimizer, (LossType)ffconfig.driver_loss, metrics);
   // which learning-rate route runs, and why; silent without the flags
   if (chatty && (ffconfig.lr_warmup_steps || ffconfig.lr_num_decay_steps || ffconfig.lr_decay_start_step || ffconfig.device_lr || ffconfig.host_lr_schedule))
@@ -428,8 +463,8 @@ DLRMApp::~DLRMApp() {
 }
 
 void DLRMApp::warmup() {
-  // [ref: examples/cpp/DLRM/dlrm.cc:139-149]
-  loader->reset();
+  // [ref: examples/cpp/DLRM/dlrm.cc:139-149]; --data-randomize total: batch 0 of epoch 0's order
+  loader->reset(0);
   ff->reset_metrics();
   loader->next_batch(*ff);
   ff->forward();
@@ -490,7 +525,7 @@ double DLRMApp::run_epochs() {
   const double ts_start = now_us();
   if (ffconfig.eval_only) eval_secs += evaluate(0);
   for (int epoch = 0; epoch < ffconfig.epochs && !ffconfig.eval_only; epoch++) {
-    loader->reset();
+    loader->reset(epoch);
     ff->reset_metrics();
     const int iterations = loader->num_train / ffconfig.batchSize;
     train_steps(iterations, epoch > 0 /* the reference traces from the second epoch on */);

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "ffmodel.h"
+#include "../../include/ff_hip_data.h"
 
 #define MAX_NUM_EMB 1000
 
@@ -35,17 +36,22 @@ class DataLoader {
  public:
   DataLoader(FFModel& ff, const DLRMConfig& dlrm, const std::vector<Tensor>& sparse_inputs, Tensor dense_input, Tensor label);
   ~DataLoader();
-  void next_batch(FFModel& ff);                 // the next TRAINING batch (wraps at num_train)
-  void load_batch(FFModel& ff, int k);          // batch k of what was loaded into the model inputs; the training cursor does not move
+  // the next TRAINING batch (wraps at num_train).  --data-randomize total: batch next_index / B of epoch `epoch`'s order, one gather launch
+  // (include/ff_hip_data.h); a wrap without reset() moves on to the next epoch's order
+  void next_batch(FFModel& ff);
+  void load_batch(FFModel& ff, int k);          // batch k of what was loaded into the model inputs, in file order; the training cursor does not move
   void shuffle() {}
-  void reset() { next_index = 0; }
+  void reset(int64_t epoch_ = 0) { next_index = 0; epoch = epoch_; }
   int num_samples, next_index;
+  int64_t epoch;                                // which order next_batch follows (--data-randomize total)
   int num_train;                                // num_samples minus the held-out tail (--eval-batches)
 
  private:
   void generate_random(FFModel& ff, const DLRMConfig& dlrm);
   void generate_zipf(FFModel& ff, int64_t* dst, int64_t n, uint64_t seed, int64_t rows, double alpha);
   void load_hdf5(FFModel& ff, const DLRMConfig& dlrm);      // --dataset: X_int / X_cat / y of the reference's Criteo file
+  void gather_batch(FFModel& ff, int64_t step);             // --data-randomize total: batch `step` of epoch `epoch`'s order
+  std::vector<ffh_gather_segment> segments;                 // ... its segments: one per table (null destination: not held by this rank), the dense features, the labels
   std::vector<Tensor> batch_sparse_inputs;
   Tensor batch_dense_input, batch_label;
   std::vector<int64_t*> full_sparse;   // per owned table: [num_samples][bag]

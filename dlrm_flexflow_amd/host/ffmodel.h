@@ -151,6 +151,8 @@ class FFConfig {
   int synthetic_labels;        // --synthetic-labels bernoulli (0, default: coin flips, the reference's) | logistic (1: drawn from a fixed hidden logistic model of the dense features,
                                // so that a synthetic run has something to learn; its batches are then iterated like a data set's instead of reusing the warm-up batch)
   bool eval_only;              // --eval-only: no training, one evaluation of the held-out batches
+  int data_randomize;          // --data-randomize none (0, default: file order, the same every epoch) | total (1: every epoch in a new order, a stateless function of
+                               // (--seed, epoch, position), include/ffh_perm.h; the batch is one gather launch of include/ff_hip_data.h)
   bool fuse_loss;              // loss step + metrics inside the last layer's one-launch backward (A/B: --no-fused-loss)
   int64_t replicate_embedding_rows;   // world_size > 1: tables with at most this many rows are data-parallel (replicated) instead of owned by one rank (0: none)
   int64_t row_shard_rows;      // ... row-wise instead: partial bag sums + reduce-scatter (0: never; wins over column_shard_rows)

@@ -51,6 +51,10 @@ void flexflow_config_set_lr_schedule(flexflow_config_t h, int64_t warmup_steps, 
   C(h)->host_lr_schedule = device_lr == -1;
 }
 double flexflow_lr_schedule_value(int64_t k, double base, int64_t W, int64_t S, int64_t N) { return (double)(float)ffh_lr_schedule_value(k, base, W, S, N); }
+uint64_t flexflow_shuffle_index(uint64_t seed, uint64_t epoch, uint64_t i, uint64_t n) { return ffh_perm_index(seed, epoch, i, n); }
+void flexflow_shuffle_indices(uint64_t seed, uint64_t epoch, uint64_t first, uint64_t count, uint64_t n, uint64_t* out) {
+  for (uint64_t j = 0; j < count; j++) out[j] = ffh_perm_index(seed, epoch, first + j, n);
+}
 
 flexflow_model_t flexflow_model_create(flexflow_config_t c) { flexflow_model_t h; h.impl = new FFModel(*C(c)); return h; }
 void flexflow_model_destroy(flexflow_model_t h) { delete M(h); }
@@ -311,7 +315,8 @@ float flexflow_dlrm_time_kernel(flexflow_dlrm_t h, int which, int iters) {
         const Tensor& fin = ff->layers.back()->outputs[0];
         ff->check(ff->api->ffh_mse_bwd(ff->ctx, fin.impl->grad, (const float*)fin.impl->ptr, (const float*)ff->label_tensor.impl->ptr,
                                        fin.impl->rows_local * fin.adim[0], 1.0f, ff->stream), "mse_bwd");
-      } else if (which == 4) app->train_steps(1, false);   // eager step (no graph)
+      } else if (which == 12) app->loader->next_batch(*ff);   // the batch load alone: load_batch's copies, or the one gather launch of --data-randomize total
+      else if (which == 4) app->train_steps(1, false);   // eager step (no graph)
       else app->train_steps(1, true);
     }
   };

@@ -59,6 +59,10 @@ void flexflow_config_set_embedding_rounding(flexflow_config_t, int mode);
 void flexflow_config_set_lr_schedule(flexflow_config_t, int64_t warmup_steps, int64_t decay_start_step, int64_t num_decay_steps, int device_lr);
 /* the schedule itself, a pure function: the rate of zero-based step k as the float the kernels receive */
 double flexflow_lr_schedule_value(int64_t k, double base, int64_t W, int64_t S, int64_t N);
+/* --data-randomize total: ffh_perm_index of include/ffh_perm.h (position i of epoch `epoch` -> row of a stripe of n rows; i < n), and the
+ * same for positions first .. first + count - 1 into out[count] */
+uint64_t flexflow_shuffle_index(uint64_t seed, uint64_t epoch, uint64_t i, uint64_t n);
+void flexflow_shuffle_indices(uint64_t seed, uint64_t epoch, uint64_t first, uint64_t count, uint64_t n, uint64_t* out);
 
 /* FFModel */
 flexflow_model_t flexflow_model_create(flexflow_config_t);
@@ -153,7 +157,8 @@ double flexflow_dlrm_run_epochs(flexflow_dlrm_t);
 double flexflow_dlrm_evaluate(flexflow_dlrm_t, int epoch, flexflow_eval_metrics_t* out);
 /* average device time (ms) of `iters` back-to-back launches, HIP events on the launch stream:
  * which = 0 embedding gather (all owned tables, one launch), 1 fused embedding backward + SGD,
- *         2 whole training step (forward, zero_gradients, backward, update; traced if enabled) */
+ *         2 whole training step (forward, zero_gradients, backward, update; traced if enabled),
+ *         12 the batch load alone (DataLoader::next_batch: the copies of file order, or the one gather launch of --data-randomize total) */
 void flexflow_dlrm_probe_step(flexflow_dlrm_t, int iters, float* out_ms, int nout);   /* in-step event intervals, see ffmodel_c.cc; collective at world_size > 1 */
 float flexflow_dlrm_time_kernel(flexflow_dlrm_t, int which, int iters);
 

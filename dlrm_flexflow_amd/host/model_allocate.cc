@@ -162,6 +162,10 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
     if (bce) last->dy_premasked = true;
   }
   want_eval = want_auc;
+  // a shuffled data order (include/ff_hip_data.h): its batches are one gather launch that only a library with the extension has
+  if (config.data_randomize && !api->data)
+    die("--data-randomize total: %s (%s) is a kernel library without the data extension (include/ff_hip_data.h); use --data-randomize none",
+        api->path.c_str(), api->ffh_backend_name());
   for (Op* op : layers) {
     op->create_output_and_partition(*this);
     op->create_weights(*this);

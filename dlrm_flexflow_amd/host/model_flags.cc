@@ -35,6 +35,7 @@ FFConfig::FFConfig() {
   eval_batches = 0;
   eval_only = false;
   synthetic_labels = 0;
+  data_randomize = 0;
   timing_events = false;
   attach_events = true;
   fuse_pair = true;
@@ -143,6 +144,13 @@ void FFConfig::parse_args(char** argv, int argc) {
       if (!strcmp(v, "bernoulli")) synthetic_labels = 0;
       else if (!strcmp(v, "logistic")) synthetic_labels = 1;
       else die("--synthetic-labels %s: 'bernoulli' or 'logistic'", v);
+      continue;
+    }
+    if (is("--data-randomize")) {
+      const char* v = next();
+      if (!strcmp(v, "none")) data_randomize = 0;
+      else if (!strcmp(v, "total")) data_randomize = 1;
+      else die("--data-randomize %s: 'none' or 'total'", v);
       continue;
     }
     if (is("--timing-events")) { timing_events = true; continue; }
