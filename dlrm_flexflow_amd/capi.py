@@ -273,6 +273,34 @@ _SIGS_DATA = {
 }
 
 
+# include/ff_hip_cross.h: the optional cross extension (the elementwise combine of a DCNv2 low-rank cross layer); same rule
+CROSS_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_cross.h")
+CROSS_SKIP, CROSS_STORE, CROSS_ADD = 0, 1, 2
+
+_SIGS_CROSS = {
+    "ffh_cross_abi_version": (I, []),
+    "ffh_cross_fwd": (I, [P, P, L, P, L, P, L, P, L, L, L, P]),
+    "ffh_cross_bwd": (I, [P, P, L, P, L, P, L, P, L, P, L, I, P, L, I, L, L, P]),
+}
+
+
+def cross_header_symbols(header_path: str = CROSS_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_CROSS_API_LIST X-macro in include/ff_hip_cross.h."""
+    text = open(header_path).read()
+    m = re.search(r"#define FFH_CROSS_API_LIST\(X\)(.*?)\n\n", text, re.S)
+    if not m:
+        raise RuntimeError("FFH_CROSS_API_LIST not found in " + header_path)
+    return re.findall(r"X\((\w+)\)", m.group(1))
+
+
+def cross_header_abi_version(header_path: str = CROSS_HEADER_PATH) -> int:
+    """FFH_CROSS_ABI_VERSION of include/ff_hip_cross.h."""
+    m = re.search(r"#define\s+FFH_CROSS_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_CROSS_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
 def data_header_symbols(header_path: str = DATA_HEADER_PATH) -> list[str]:
     """Every symbol of the FFH_DATA_API_LIST X-macro in include/ff_hip_data.h."""
     text = open(header_path).read()
@@ -631,6 +659,41 @@ class DataApi:
 def data_api(lib: FFHLib) -> DataApi:
     """The data entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
     return DataApi(lib)
+
+
+class CrossApi:
+    """The cross extension (include/ff_hip_cross.h) of a loaded FFHLib; `cross_api(lib)` builds it or raises."""
+
+    def __init__(self, lib: FFHLib):
+        self.base = lib
+        for name, (res, args) in _SIGS_CROSS.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no cross extension ({name} missing; include/ff_hip_cross.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_cross_abi_version()
+        if got != cross_header_abi_version():
+            raise FFHError(f"{lib.path}: cross ABI version {got}, include/ff_hip_cross.h says {cross_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+    def rc(self, name: str, *args) -> int:
+        """`name(ctx, *args)` of the extension, returning its status code (FFH_OK, FFH_ERR_BAD_ARG, ...)."""
+        sig = _SIGS_CROSS[name][1][1:]
+        if len(args) != len(sig):
+            raise TypeError(f"{name}: expected {len(sig)} args, got {len(args)}")
+        conv = [ptr(a) if t is P else a for a, t in zip(args, sig)]
+        return getattr(self.lib, name)(self.ctx, *conv)
+
+    def call(self, name: str, *args):
+        """Call `name(ctx, *args)` of the extension; pointers may be tensors/arrays/ints/None."""
+        self.base.check(self.rc(name, *args), name)
+
+
+def cross_api(lib: FFHLib) -> CrossApi:
+    """The cross entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
+    return CrossApi(lib)
 
 
 _hip_singleton: FFHLib | None = None

@@ -102,6 +102,8 @@ def lib() -> C.CDLL:
         "flexflow_model_add_flat": (H, [H, H, C.c_char_p]),
         "flexflow_model_add_tril": (H, [H, H, C.c_char_p]),
         "flexflow_model_add_dot_interaction": (H, [H, H, I, C.c_char_p]),
+        "flexflow_model_add_cross_combine": (H, [H, H, H, H, C.c_char_p]),
+        "flexflow_model_add_cross_net": (H, [H, H, I, I, C.c_char_p]),
         "flexflow_model_add_transpose": (H, [H, H, I, IP, C.c_char_p]),
         "flexflow_model_add_reshape": (H, [H, H, I, IP, C.c_char_p]),
         "flexflow_zero_initializer_create": (H, []), "flexflow_uniform_initializer_create": (H, [I, F, F]),
@@ -187,6 +189,27 @@ def shuffle_indices(seed: int, epoch: int, n: int, first: int = 0, count: int | 
     out = np.empty(count, np.uint64)
     lib().flexflow_shuffle_indices(int(seed) & (2**64 - 1), int(epoch), int(first), count, int(n), out.ctypes.data)
     return out.astype(np.int64)
+
+
+def cross_reference(x0, v, xl) -> np.ndarray:
+    """The combine of a DCNv2 low-rank cross layer as include/ff_hip_cross.h states it, in float32 numpy: fadd_rn(fmul_rn(x0, v), xl) -- two
+    separately rounded float32 operations per element (numpy never contracts them), which ffh_cross_fwd equals bit for bit."""
+    x0, v, xl = (np.asarray(a, dtype=np.float32) for a in (x0, v, xl))
+    with np.errstate(all="ignore"):
+        return (x0 * v).astype(np.float32) + xl
+
+
+def cross_reference_backward(dy, x0, v, aliased=False):
+    """Backward of cross_reference for the output gradient dy, as ffh_cross_bwd states it.  Returns (dv, g_x0, g_xl): dv = fmul_rn(dy, x0),
+    g_x0 = fmul_rn(dy, v), g_xl = dy -- what a STORE leaves in the destination and what an ADD adds to it (fadd_rn(old, g)).
+    aliased=True (layer 0: xl is x0, one gradient buffer): (dv, fadd_rn(fmul_rn(dy, v), dy), None)."""
+    dy, x0, v = (np.asarray(a, dtype=np.float32) for a in (dy, x0, v))
+    with np.errstate(all="ignore"):
+        dv = (dy * x0).astype(np.float32)
+        g0 = (dy * v).astype(np.float32)
+        if aliased:
+            return dv, g0 + dy, None
+        return dv, g0, dy.copy()
 
 
 def _argv(args):
@@ -357,6 +380,16 @@ class FFModel:
         """[batch][c * d] (concat of the bottom-MLP output and the embedding outputs) -> [batch][d + c (c - 1) / 2]:
         row 0 passed through, then the pairwise dot products i > j -- the whole interaction in one launch each way."""
         return Tensor(lib().flexflow_model_add_dot_interaction(self.h, input.h, d, name.encode() if name else None), self)
+
+    def cross_combine(self, x0: Tensor, v: Tensor, xl: Tensor, name=None) -> Tensor:
+        """x0 (.) v + xl on three [batch][D] tensors: the third line of a DCNv2 low-rank cross layer (include/ff_hip_cross.h); in layer 0
+        xl is x0.  Needs a kernel library with the cross extension: compile() refuses the model otherwise."""
+        return Tensor(lib().flexflow_model_add_cross_combine(self.h, x0.h, v.h, xl.h, name.encode() if name else None), self)
+
+    def cross_net(self, x0: Tensor, num_layers: int = 3, low_rank: int = 512, name=None) -> Tensor:
+        """torchrec's LowRankCrossNet on x0 [batch][D]: per layer u = dense(x_l, low_rank, no bias), v = dense(u, D), x_{l+1} =
+        cross_combine(x0, v, x_l) -- 3 * num_layers operators; returns x_L."""
+        return Tensor(lib().flexflow_model_add_cross_net(self.h, x0.h, int(num_layers), int(low_rank), name.encode() if name else None), self)
 
     def tril(self, input: Tensor, name=None) -> Tensor:
         """Strict lower triangle of [batch][n][n] -> [batch][n (n - 1) / 2] (MLPerf-DLRM's pick of the pairwise dots)."""

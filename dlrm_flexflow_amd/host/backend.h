@@ -8,6 +8,7 @@
 #include "../../include/ff_hip_ctr.h"
 #include "../../include/ff_hip_lr.h"
 #include "../../include/ff_hip_data.h"
+#include "../../include/ff_hip_cross.h"
 
 // The optional bf16-table extension (include/ff_hip_bf16.h): all of its list or none of it.
 struct KernelApiBf16 {
@@ -37,6 +38,13 @@ struct KernelApiData {
 #undef FFH_DECL
 };
 
+// The optional cross extension (include/ff_hip_cross.h: the elementwise combine of a DCNv2 low-rank cross layer and its backward).
+struct KernelApiCross {
+#define FFH_DECL(name) decltype(&::name) name;
+  FFH_CROSS_API_LIST(FFH_DECL)
+#undef FFH_DECL
+};
+
 struct KernelApi {
 #define FFH_DECL(name) decltype(&::name) name;
   FFH_API_LIST(FFH_DECL)
@@ -45,6 +53,7 @@ struct KernelApi {
   const KernelApiCtr* ctr = nullptr;     // likewise for include/ff_hip_ctr.h
   const KernelApiLr* lr = nullptr;       // likewise for include/ff_hip_lr.h
   const KernelApiData* data = nullptr;   // likewise for include/ff_hip_data.h
+  const KernelApiCross* cross = nullptr; // likewise for include/ff_hip_cross.h
   void* handle;
   std::string path;
   bool overridden = false;      // chosen by --backend or $FFH_BACKEND_LIB rather than the product default: the driver says so on its THROUGHPUT line

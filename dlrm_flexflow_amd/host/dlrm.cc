@@ -30,7 +30,7 @@ void print_vector(const std::string& name, const std::vector<int>& v) {
 
 DLRMConfig::DLRMConfig(void)
     : sparse_feature_size(2), sigmoid_bot(-1), sigmoid_top(-1), embedding_bag_size(1), loss_threshold(0.0f),
-      arch_interaction_op("cat"), dataset_path(""), data_size(-1), optimizer("sgd"), zipf_alpha(0.0) {
+      arch_interaction_op("cat"), dataset_path(""), data_size(-1), optimizer("sgd"), zipf_alpha(0.0), dcn_num_layers(3), dcn_low_rank_dim(512) {
   embedding_size.push_back(4);
   mlp_bot.push_back(4); mlp_bot.push_back(2);
   mlp_top.push_back(8); mlp_top.push_back(2);
@@ -46,6 +46,19 @@ void parse_input_args(char** argv, int argc, DLRMConfig& config) {
     return v;
   };
   for (int i = 1; i < argc; i++) {
+    // the DCNv2 flags (not reference flags) take "--flag value" and "--flag=value", as FFConfig::parse_args does
+    {
+      const char* eq = strncmp(argv[i], "--", 2) == 0 ? strchr(argv[i], '=') : nullptr;
+      auto is = [&](const char* a) { return eq ? (strlen(a) == (size_t)(eq - argv[i]) && !strncmp(argv[i], a, (size_t)(eq - argv[i]))) : !strcmp(argv[i], a); };
+      auto next = [&]() -> const char* {
+        if (eq) return eq + 1;
+        if (i + 1 >= argc) { fprintf(stderr, "FATAL: flag %s needs a value\n", argv[i]); abort(); }
+        return argv[++i];
+      };
+      if (eq && is("--arch-interaction-op")) { config.arch_interaction_op = std::string(next()); continue; }
+      if (is("--dcn-num-layers")) { config.dcn_num_layers = atoi(next()); continue; }
+      if (is("--dcn-low-rank-dim")) { config.dcn_low_rank_dim = atoi(next()); continue; }
+    }
     if (!strcmp(argv[i], "--arch-sparse-feature-size")) { config.sparse_feature_size = atoi(argv[++i]); continue; }
     if (!strcmp(argv[i], "--arch-embedding-size")) { config.embedding_size = split(argv[++i]); continue; }
     if (!strcmp(argv[i], "--embedding-bag-size")) { config.embedding_bag_size = atoi(argv[++i]); continue; }
@@ -93,11 +106,13 @@ Tensor create_emb(FFModel* model, const Tensor& input, int input_dim, int output
 // for 26 tables; width D + C (C - 1) / 2 = 479) -- through FFModel::dot_interaction, the whole interaction as one
 // MFMA kernel each way (csrc/interaction.hip); "dot-tril-ops" spells the same thing as the operator chain with
 // FFModel::tril (neither operator exists in the reference).
-Tensor interact_features(FFModel* model, const Tensor& x, const std::vector<Tensor>& ly, std::string interaction) {
+// "dcn" is MLPerf DLRM-DCNv2's interaction: torchrec's LowRankCrossNet on the concat (FFModel::cross_net).
+Tensor interact_features(FFModel* model, const Tensor& x, const std::vector<Tensor>& ly, std::string interaction, int dcn_num_layers, int dcn_low_rank_dim) {
   std::vector<Tensor> inputs;
   inputs.push_back(x);
   for (size_t i = 0; i < ly.size(); i++) inputs.push_back(ly[i]);
   if (interaction == "cat") return model->concat((int)inputs.size(), inputs.data(), 1 /*axis*/);
+  if (interaction == "dcn") return model->cross_net(model->concat((int)inputs.size(), inputs.data(), 1 /*axis*/), dcn_num_layers, dcn_low_rank_dim);
   if (interaction == "dot" || interaction == "dot-tril" || interaction == "dot-tril-ops") {
     const int batch = x.adim[1], d = x.adim[0], c = (int)inputs.size();
     for (const Tensor& t : inputs)
@@ -114,7 +129,7 @@ Tensor interact_features(FFModel* model, const Tensor& x, const std::vector<Tens
     Tensor both[2] = {x, pf};
     return model->concat(2, both, 1 /*axis*/);
   }
-  fprintf(stderr, "FATAL: --arch-interaction-op %s: 'cat', 'dot', 'dot-tril' or 'dot-tril-ops'\n", interaction.c_str());
+  fprintf(stderr, "FATAL: --arch-interaction-op %s: 'cat', 'dot', 'dot-tril' or 'dot-tril-ops', or 'dcn' (the DCNv2 low-rank cross network)\n", interaction.c_str());
   abort();
 }
 
@@ -380,6 +395,22 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
     print_vector("Embedding Vocab Sizes", dlrm.embedding_size);
     print_vector("MLP Top", dlrm.mlp_top);
     print_vector("MLP Bot", dlrm.mlp_bot);
+    if (dlrm.arch_interaction_op == "dcn") {      // (flushed: a refusal below aborts, and a pipe would lose what says which model was asked for)
+      printf("[DLRM] interaction: dcn layers %d rank %d\n", dlrm.dcn_num_layers, dlrm.dcn_low_rank_dim);
+      fflush(stdout);
+    }
+  }
+  if (dlrm.arch_interaction_op == "dcn") {
+    if (dlrm.dcn_num_layers < 1) { fprintf(stderr, "FATAL: --dcn-num-layers %d: must be >= 1\n", dlrm.dcn_num_layers); abort(); }
+    if (dlrm.dcn_low_rank_dim < 1) { fprintf(stderr, "FATAL: --dcn-low-rank-dim %d: must be >= 1\n", dlrm.dcn_low_rank_dim); abort(); }
+    // the cross network keeps the width of its input: the concat of the bottom-MLP output and one vector per table
+    const long long D = (long long)dlrm.mlp_bot.back() + (long long)dlrm.embedding_size.size() * dlrm.sparse_feature_size;
+    if (dlrm.mlp_top.empty() || dlrm.mlp_top[0] != D) {
+      fprintf(stderr, "FATAL: --arch-interaction-op dcn: --arch-mlp-top must start with the interaction's width %lld (bottom-MLP output %d + %zu tables x "
+                      "--arch-sparse-feature-size %d), not %d\n", D, dlrm.mlp_bot.back(), dlrm.embedding_size.size(), dlrm.sparse_feature_size,
+              dlrm.mlp_top.empty() ? 0 : dlrm.mlp_top[0]);
+      abort();
+    }
   }
   if (dlrm.embedding_size.size() > MAX_NUM_EMB) { fprintf(stderr, "FATAL: more than %d tables\n", MAX_NUM_EMB); abort(); }
   ff = new FFModel(ffconfig);
@@ -397,7 +428,7 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
   std::vector<Tensor> ly;
   for (size_t i = 0; i < dlrm.embedding_size.size(); i++)
     ly.push_back(create_emb(ff, sparse_inputs[i], dlrm.embedding_size[i], dlrm.sparse_feature_size, (int)i));
-  Tensor z = interact_features(ff, x, ly, dlrm.arch_interaction_op);
+  Tensor z = interact_features(ff, x, ly, dlrm.arch_interaction_op, dlrm.dcn_num_layers, dlrm.dcn_low_rank_dim);
   create_mlp(ff, z, dlrm.mlp_top, (int)dlrm.mlp_top.size() - 2);
   if (dlrm.loss_threshold > 0.0f && dlrm.loss_threshold < 1.0f) {
     fprintf(stderr, "FATAL: --loss-threshold clamp is not implemented (the reference asserts here, dlrm.cc:125-128)\n");

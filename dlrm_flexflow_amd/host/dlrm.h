@@ -20,13 +20,15 @@ struct DLRMConfig {
   int data_size;
   std::string optimizer;   // --optimizer sgd (default, the reference driver's) | sgd-momentum | adam (not a reference flag)
   double zipf_alpha;   // > 0: synthetic ids follow a power law instead of the reference's uniform draw (not a reference flag)
+  int dcn_num_layers, dcn_low_rank_dim;   // --arch-interaction-op dcn: --dcn-num-layers L (3), --dcn-low-rank-dim R (512) (not reference flags)
 };
 
 void parse_input_args(char** argv, int argc, DLRMConfig& config);
 
 Tensor create_mlp(FFModel* model, const Tensor& input, std::vector<int> ln, int sigmoid_layer);
 Tensor create_emb(FFModel* model, const Tensor& input, int input_dim, int output_dim, int idx);
-Tensor interact_features(FFModel* model, const Tensor& x, const std::vector<Tensor>& ly, std::string interaction);
+Tensor interact_features(FFModel* model, const Tensor& x, const std::vector<Tensor>& ly, std::string interaction, int dcn_num_layers = 3,
+                         int dcn_low_rank_dim = 512);
 
 // Dataset (synthetic, or the reference's HDF5 Criteo file with --dataset) resident on the device (the reference keeps it in zero-copy host memory and
 // gathers + copies H2D every batch, [ref: examples/cpp/DLRM/dlrm.cc:357-377, dlrm.cu:19-122]).

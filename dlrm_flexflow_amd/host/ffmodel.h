@@ -28,6 +28,7 @@
 #include "../../include/ff_hip_bf16.h"
 #include "../../include/ff_hip_ctr.h"
 #include "../../include/ff_hip_lr.h"
+#include "../../include/ff_hip_cross.h"
 #include "ffcomm.h"
 
 // ---- enums: identical values to [ref: include/ffconst.h:4-57] -------------------------------
@@ -55,7 +56,7 @@ enum MetricsType {
   METRICS_AUC = 2002,                   // a marker: the run will call eval_batch() / get_eval_metrics() (the AUC is never a training-batch figure).  compile() checks what
                                         // evaluation needs (final sigmoid column, the CTR extension, held-out data in a training run) and allocates the device histograms
 };
-enum OperatorType { OP_INPUT, OP_LINEAR, OP_EMBEDDING, OP_CONCAT, OP_BATCHMATMUL, OP_TRANSPOSE, OP_RESHAPE, OP_FLAT, OP_TRIL, OP_DOT_INTERACTION };
+enum OperatorType { OP_INPUT, OP_LINEAR, OP_EMBEDDING, OP_CONCAT, OP_BATCHMATMUL, OP_TRANSPOSE, OP_RESHAPE, OP_FLAT, OP_TRIL, OP_DOT_INTERACTION, OP_CROSS_COMBINE };
 
 #define MAX_TENSOR_DIM 4
 #define MAX_NUM_INPUTS 256
@@ -473,6 +474,19 @@ class DotInteraction : public Op {
   bool bwd_overwrite;           // the input has no other consumer: its gradient is stored, not accumulated
 };
 
+// The third line of a DCNv2 low-rank cross layer (torchrec's LowRankCrossNet; include/ff_hip_cross.h):
+// y = x0 (.) v + xl, all [batch][D].  No weights: the two products of the layer, u = V xl and v = W u + b, are Linear ops.  In layer 0
+// xl IS x0 (one tensor in both slots).
+class CrossCombine : public Op {
+ public:
+  CrossCombine(FFModel& model, const Tensor& x0, const Tensor& v, const Tensor& xl, const char* name);
+  void create_output_and_partition(FFModel&) override {}
+  void forward(const FFModel&) override;
+  void backward(const FFModel&) override;
+  void print_layer(const FFModel&) const override;
+  int mode_x0, mode_xl;         // FFH_CROSS_STORE where the input has no other consumer, FFH_CROSS_ADD otherwise, FFH_CROSS_SKIP for a model input (allocate() step 4b)
+};
+
 // ---------------------------------------------------------------------------------------------
 // A host thread that issues the launches of one auxiliary HIP stream.  The training step is bound by
 // the host's launch rate (~7 us per launch, ~35 launches per Kaggle step); the weight-gradient GEMMs
@@ -515,6 +529,9 @@ class FFModel {
   Tensor flat(const Tensor& input, const char* name = NULL);
   Tensor tril(const Tensor& input, const char* name = NULL);
   Tensor dot_interaction(const Tensor& input, int d, const char* name = NULL);   // fused pairwise-dot interaction (this build's addition)   // strict lower triangle of [batch][n][n] (this build's addition)
+  Tensor cross_combine(const Tensor& x0, const Tensor& v, const Tensor& xl, const char* name = NULL);   // x0 (.) v + xl (this build's addition)
+  // num_layers low-rank cross layers on x0 [batch][D]: per layer dense(D -> low_rank, no bias), dense(low_rank -> D), cross_combine
+  Tensor cross_net(const Tensor& x0, int num_layers, int low_rank, const char* name = NULL);
   Tensor transpose(const Tensor& input, const std::vector<int>& perm, const char* name = NULL);
   Tensor reshape(const Tensor& input, const std::vector<int>& shape, const char* name = NULL);
   template <int NDIM>

@@ -83,6 +83,12 @@ flexflow_tensor_t flexflow_model_add_concat(flexflow_model_t m, int n, const fle
 }
 flexflow_tensor_t flexflow_model_add_flat(flexflow_model_t m, flexflow_tensor_t in, const char* name) { return wrap(M(m)->flat(*T(in), name)); }
 flexflow_tensor_t flexflow_model_add_dot_interaction(flexflow_model_t m, flexflow_tensor_t in, int d, const char* name) { return wrap(M(m)->dot_interaction(*T(in), d, name)); }
+flexflow_tensor_t flexflow_model_add_cross_combine(flexflow_model_t m, flexflow_tensor_t x0, flexflow_tensor_t v, flexflow_tensor_t xl, const char* name) {
+  return wrap(M(m)->cross_combine(*T(x0), *T(v), *T(xl), name));
+}
+flexflow_tensor_t flexflow_model_add_cross_net(flexflow_model_t m, flexflow_tensor_t x0, int num_layers, int low_rank, const char* name) {
+  return wrap(M(m)->cross_net(*T(x0), num_layers, low_rank, name));
+}
 flexflow_tensor_t flexflow_model_add_tril(flexflow_model_t m, flexflow_tensor_t in, const char* name) { return wrap(M(m)->tril(*T(in), name)); }
 flexflow_tensor_t flexflow_model_add_transpose(flexflow_model_t m, flexflow_tensor_t in, int n, const int* perm, const char* name) {
   return wrap(M(m)->transpose(*T(in), dims_vec(perm, n), name));

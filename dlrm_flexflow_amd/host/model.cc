@@ -284,6 +284,7 @@ std::string FFModel::get_operator_type_name(OperatorType type) const {
     case OP_FLAT: return "Flat";
     case OP_TRIL: return "Tril";
     case OP_DOT_INTERACTION: return "DotInteraction";
+    case OP_CROSS_COMBINE: return "CrossCombine";
     default: return "Unknown";
   }
 }
@@ -1085,6 +1086,60 @@ Tensor FFModel::dot_interaction(const Tensor& input, int d, const char* name) {
   t->layer_index = (int)layers.size();
   layers.push_back(t);
   return t->outputs[0];
+}
+
+// =============================================================================================
+// CrossCombine: x0 (.) v + xl of a DCNv2 low-rank cross layer (include/ff_hip_cross.h; no reference operator, parity is against torch)
+// =============================================================================================
+CrossCombine::CrossCombine(FFModel& model, const Tensor& x0, const Tensor& v, const Tensor& xl, const char* name)
+    : Op(model, OP_CROSS_COMBINE, name, 3, std::vector<Tensor>{x0, v, xl}.data()), mode_x0(FFH_CROSS_ADD), mode_xl(FFH_CROSS_ADD) {
+  for (int i = 0; i < 3; i++) {
+    if (inputs[i].data_type != DT_FLOAT) die("%s: inputs must be DT_FLOAT", this->name);
+    if (inputs[i].numDim != 2 || inputs[i].adim[0] != x0.adim[0] || inputs[i].adim[1] != x0.adim[1])
+      die("%s: x0, v and xl must be [batch][D] tensors of one shape", this->name);
+  }
+  outputs[0].numDim = 2;
+  outputs[0].adim[0] = x0.adim[0];
+  outputs[0].adim[1] = x0.adim[1];
+}
+void CrossCombine::print_layer(const FFModel&) const {
+  printf("%s: x0 (.) v + xl, [%d][%d]%s\n", name, outputs[0].adim[1], outputs[0].adim[0], inputs[0].impl == inputs[2].impl ? " (xl is x0)" : "");
+}
+void CrossCombine::forward(const FFModel& ff) {
+  const Tensor &x0 = inputs[0], &v = inputs[1], &xl = inputs[2], &y = outputs[0];
+  for (const Tensor* t : {&x0, &v, &xl, &y})
+    if (!t->impl->pieces.empty() || !t->impl->ptr) die("%s: operands must be single buffers", name);
+  ff.check(ff.api->cross->ffh_cross_fwd(ff.ctx, (float*)y.impl->ptr, y.impl->ld, (const float*)x0.impl->ptr, x0.impl->ld, (const float*)v.impl->ptr, v.impl->ld,
+                                        (const float*)xl.impl->ptr, xl.impl->ld, y.impl->rows_local, y.adim[0], ff.stream), name);
+}
+void CrossCombine::backward(const FFModel& ff) {
+  const Tensor &x0 = inputs[0], &v = inputs[1], &xl = inputs[2], &y = outputs[0];
+  if (!v.impl->grad) die("%s: v has no gradient buffer", name);
+  ff.check(ff.api->cross->ffh_cross_bwd(ff.ctx, y.impl->grad, y.impl->grad_ld, (const float*)x0.impl->ptr, x0.impl->ld, (const float*)v.impl->ptr, v.impl->ld,
+                                        v.impl->grad, v.impl->grad_ld, x0.impl->grad, x0.impl->grad_ld, x0.impl->grad ? mode_x0 : FFH_CROSS_SKIP,
+                                        xl.impl->grad, xl.impl->grad_ld, xl.impl->grad ? mode_xl : FFH_CROSS_SKIP, y.impl->rows_local, y.adim[0], ff.stream),
+           name);
+}
+Tensor FFModel::cross_combine(const Tensor& x0, const Tensor& v, const Tensor& xl, const char* name) {
+  CrossCombine* t = new CrossCombine(*this, x0, v, xl, name);
+  t->layer_index = (int)layers.size();
+  layers.push_back(t);
+  return t->outputs[0];
+}
+// LowRankCrossNet: V_l and W_l take the Linear default initialisers (Glorot uniform; torchrec: Xavier normal -- a stated divergence, DESIGN
+// section 14), b_l is zero
+Tensor FFModel::cross_net(const Tensor& x0, int num_layers, int low_rank, const char* name) {
+  if (x0.numDim != 2) die("cross_net: the input must be [batch][D]");
+  if (num_layers < 1) die("cross_net: %d layers, at least 1", num_layers);
+  if (low_rank < 1) die("cross_net: low-rank dimension %d, at least 1", low_rank);
+  (void)name;
+  Tensor xl = x0;
+  for (int l = 0; l < num_layers; l++) {
+    Tensor u = dense(xl, low_rank, AC_MODE_NONE, false /*bias*/);
+    Tensor v = dense(u, x0.adim[0], AC_MODE_NONE, true /*bias*/);
+    xl = cross_combine(x0, v, xl);
+  }
+  return xl;
 }
 Tensor FFModel::transpose(const Tensor& input, const std::vector<int>& perm, const char* name) {
   Transpose* t = new Transpose(*this, input, perm, name);

@@ -166,6 +166,11 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
   if (config.data_randomize && !api->data)
     die("--data-randomize total: %s (%s) is a kernel library without the data extension (include/ff_hip_data.h); use --data-randomize none",
         api->path.c_str(), api->ffh_backend_name());
+  // the DCNv2 cross interaction (include/ff_hip_cross.h): its combine is a kernel only a library with the extension has
+  for (const Op* op : layers)
+    if (op->op_type == OP_CROSS_COMBINE && !api->cross)
+      die("--arch-interaction-op dcn (%s): %s (%s) is a kernel library without the cross extension (include/ff_hip_cross.h); use --arch-interaction-op cat, "
+          "dot or dot-tril", op->name, api->path.c_str(), api->ffh_backend_name());
   for (Op* op : layers) {
     op->create_output_and_partition(*this);
     op->create_weights(*this);
@@ -517,6 +522,15 @@ void FFModel::allocate() {
       di->bwd_overwrite = consumers[di->inputs[0].impl] == 1;
       if (!di->bwd_overwrite) need_zero_act_grads = true;
     }
+    if (CrossCombine* cc = dynamic_cast<CrossCombine*>(op)) {
+      // the same consumer-count rule per input (a tensor in two slots of one op counts twice: layer 0, where xl is x0, accumulates its one
+      // write): x_0 feeds V_0 and every combine, an intermediate x_l feeds V_l and its own combine -- all accumulated, behind the memset.
+      // dv is always stored: a v_l with another reader than its combine would lose that reader's gradient
+      cc->mode_x0 = consumers[cc->inputs[0].impl] == 1 ? FFH_CROSS_STORE : FFH_CROSS_ADD;
+      cc->mode_xl = consumers[cc->inputs[2].impl] == 1 ? FFH_CROSS_STORE : FFH_CROSS_ADD;
+      if (consumers[cc->inputs[1].impl] != 1) die("%s: its v input is read by another operator as well (its gradient is stored, not accumulated)", cc->name);
+      if (cc->mode_x0 == FFH_CROSS_ADD || cc->mode_xl == FFH_CROSS_ADD) need_zero_act_grads = true;
+    }
     if (Concat* c = dynamic_cast<Concat*>(op)) {
       // inputs that nothing else reads take their gradient slice as a plain store (FFH_CONCAT_BWD_OVERWRITE)
       c->bwd_overwrite = true;
@@ -848,13 +862,16 @@ void FFModel::allocate() {
       if (!x3_images) return (char*)twin_base + off / 2;
       return off % 128 ? nullptr : (char*)twin_base + off / 128 * 192;
     };
-    auto reg = [&](const void* base, size_t bytes, void* twin) {
-      if (bytes == 0 || !twin || n_twin_regions >= 30) return;
+    // (false: not registered -- the cap; a layer that would convert into this twin / image by a pass of its own must then not be told to.  The
+    //  cross layers of --arch-interaction-op dcn add two Linear ops each)
+    auto reg = [&](const void* base, size_t bytes, void* twin) -> bool {
+      if (bytes == 0 || !twin || n_twin_regions >= 30) return false;
       auto set = x3_images ? api->ffh_ctx_bf16x3_mirror_set : api->ffh_ctx_bf16_mirror_set;
       check(set(ctx, base, bytes, twin), "bf16 twin");
       if (dw_worker) check(set(dw_worker->ctx(), base, bytes, twin), "bf16 twin");
       if (side_worker) check(set(side_worker->ctx(), base, bytes, twin), "bf16 twin");
       n_twin_regions++;
+      return true;
     };
     reg(mlp_weights, (size_t)mlp_count * 4, w_twin);
     w_twin_dirty = true;
@@ -906,7 +923,10 @@ void FFModel::allocate() {
           act_ok = li->out_twin != nullptr;
         }
       }
-      if (act_ok) reg(im->ptr, im->bytes, twin_at(act_twin, (size_t)((const char*)im->ptr - act_slab)));
+      if (act_ok && !reg(im->ptr, im->bytes, twin_at(act_twin, (size_t)((const char*)im->ptr - act_slab)))) {
+        if (op->op_type == OP_LINEAR) { static_cast<Linear*>(op)->out_twin = nullptr; static_cast<Linear*>(op)->out_twin_x3 = false; }
+        if (Concat* c = dynamic_cast<Concat*>(op)) c->image_inputs.clear();
+      }
       // the gradient of this tensor: one consumer, a twin-writing Linear that stores its data gradient
       // (... or the one-launch backward of a layer with <= 4 outputs, which writes the twin of its data gradient too: the
       //  256 -> 1 layer on top of the Terabyte MLP, whose input gradient is the 512 -> 256 layer's dy)
@@ -919,8 +939,8 @@ void FFModel::allocate() {
       const Linear* prod = op->op_type == OP_LINEAR ? static_cast<const Linear*>(op) : nullptr;
       const bool twin_read = prod && twin_linear(prod) && (prod->dy_premasked || prod->activation == AC_MODE_NONE);
       if (ncons == 1 && twin_read && only && (twin_linear(only) || skinny_twin(only)) && only->dx_overwrite && !only->discard_input_grad && im->grad && !exchange) {
-        reg(im->grad, im->bytes, twin_at(grad_twin, (size_t)((const char*)im->grad - act_grad_slab)));
-        if (!x3_images) {      // (bwd_exact below)
+        const bool registered = reg(im->grad, im->bytes, twin_at(grad_twin, (size_t)((const char*)im->grad - act_grad_slab)));
+        if (!x3_images && registered) {      // (bwd_exact below)
           Linear* o = const_cast<Linear*>(only);
           o->dx_twin_registered = true;
           if (im->grad_ld == op->outputs[0].adim[0]) o->dx_twin = twin_at(grad_twin, (size_t)((const char*)im->grad - act_grad_slab));
@@ -931,8 +951,7 @@ void FFModel::allocate() {
       // (1024 -> 512) streams it: 60 us of conversion for 170 us of split-in-kernel GEMM at 32768 samples
       else if (x3_images && ncons == 1 && twin_read && only && only->dx_overwrite && !only->discard_input_grad && im->grad && !exchange && !use_workers() &&
                !only->pair_upper && !only->pair_lower && twin_at(grad_twin, (size_t)((const char*)im->grad - act_grad_slab))) {
-        reg(im->grad, im->bytes, twin_at(grad_twin, (size_t)((const char*)im->grad - act_grad_slab)));
-        const_cast<Linear*>(only)->dx_image = true;
+        if (reg(im->grad, im->bytes, twin_at(grad_twin, (size_t)((const char*)im->grad - act_grad_slab)))) const_cast<Linear*>(only)->dx_image = true;
       }
     }
   }
