@@ -661,6 +661,64 @@ def data_api(lib: FFHLib) -> DataApi:
     return DataApi(lib)
 
 
+# include/ff_hip_digest.h: the optional digest extension (a 64-bit digest of a strided device buffer); same rule
+DIGEST_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_digest.h")
+
+_SIGS_DIGEST = {
+    "ffh_digest_abi_version": (I, []),
+    "ffh_state_digest": (I, [P, P, L, L, L, C.c_uint64, C.c_uint64, P, P]),
+}
+
+
+def digest_header_symbols(header_path: str = DIGEST_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_DIGEST_API_LIST X-macro in include/ff_hip_digest.h."""
+    text = open(header_path).read()
+    m = re.search(r"#define FFH_DIGEST_API_LIST\(X\)(.*?)\n\n", text, re.S)
+    if not m:
+        raise RuntimeError("FFH_DIGEST_API_LIST not found in " + header_path)
+    return re.findall(r"X\((ffh_[a-z0-9_]+)\)", m.group(1))
+
+
+def digest_header_abi_version(header_path: str = DIGEST_HEADER_PATH) -> int:
+    """FFH_DIGEST_ABI_VERSION of include/ff_hip_digest.h."""
+    m = re.search(r"#define\s+FFH_DIGEST_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_DIGEST_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
+class DigestApi:
+    """The digest extension (include/ff_hip_digest.h) of a loaded FFHLib; `digest_api(lib)` builds it or raises."""
+
+    def __init__(self, lib: FFHLib):
+        self.base = lib
+        for name, (res, args) in _SIGS_DIGEST.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no digest extension ({name} missing; include/ff_hip_digest.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_digest_abi_version()
+        if got != digest_header_abi_version():
+            raise FFHError(f"{lib.path}: digest ABI version {got}, include/ff_hip_digest.h says {digest_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+    def state_digest_rc(self, base, rows, row_bytes, ld_bytes, seed, index_base, acc, stream=None) -> int:
+        """ffh_state_digest, returning its status code (FFH_OK, FFH_ERR_BAD_ARG, ...): *acc += the digest."""
+        m64 = 2 ** 64 - 1
+        return self.lib.ffh_state_digest(self.ctx, ptr(base), int(rows), int(row_bytes), int(ld_bytes), int(seed) & m64, int(index_base) & m64, ptr(acc),
+                                         ptr(stream))
+
+    def state_digest(self, base, rows, row_bytes, ld_bytes, seed, index_base, acc, stream=None):
+        self.base.check(self.state_digest_rc(base, rows, row_bytes, ld_bytes, seed, index_base, acc, stream), "ffh_state_digest")
+
+
+def digest_api(lib: FFHLib) -> DigestApi:
+    """The digest entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
+    return DigestApi(lib)
+
+
 class CrossApi:
     """The cross extension (include/ff_hip_cross.h) of a loaded FFHLib; `cross_api(lib)` builds it or raises."""
 

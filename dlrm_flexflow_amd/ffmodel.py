@@ -132,7 +132,7 @@ def lib() -> C.CDLL:
         "flexflow_tensor_get_data_type": (I, [H]),
         "flexflow_tensor_set_bf16": (None, [H, H, IP, I, P]), "flexflow_tensor_get_bf16": (None, [H, H, P]),
         "flexflow_dlrm_create": (H, [I, C.POINTER(C.c_char_p), C.POINTER(FFComm)]), "flexflow_dlrm_destroy": (None, [H]),
-        "flexflow_dlrm_get_model": (H, [H]), "flexflow_dlrm_get_num_samples": (I, [H]), "flexflow_dlrm_get_num_tables": (I, [H]),
+        "flexflow_dlrm_get_model": (H, [H]), "flexflow_dlrm_get_num_samples": (I, [H]), "flexflow_dlrm_get_num_tables": (I, [H]), "flexflow_dlrm_get_start_epoch": (I, [H]),
         "flexflow_dlrm_get_sparse_input": (H, [H, I]), "flexflow_dlrm_get_dense_input": (H, [H]),
         "flexflow_dlrm_warmup": (None, [H]), "flexflow_dlrm_train_steps": (None, [H, I, B]),
         "flexflow_dlrm_run_epochs": (D, [H]), "flexflow_dlrm_time_kernel": (F, [H, I, I]),
@@ -142,6 +142,11 @@ def lib() -> C.CDLL:
         "flexflow_model_get_eval_metrics": (None, [H, C.POINTER(EvalMetricsC), P, P]),
         "flexflow_auc_bins": (I, []), "flexflow_auc_from_histograms": (D, [P, P, I]),
         "flexflow_dlrm_evaluate": (D, [H, I, C.POINTER(EvalMetricsC)]),
+        "flexflow_model_save_checkpoint": (I, [H, C.c_char_p, C.c_int64]),
+        "flexflow_model_load_checkpoint": (I, [H, C.c_char_p, C.POINTER(C.c_int64)]),
+        "flexflow_model_state_digest": (C.c_uint64, [H]),
+        "flexflow_state_digest_host": (C.c_uint64, [P, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64]),
+        "flexflow_digest_record_seed": (C.c_uint64, [C.c_uint64]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -189,6 +194,122 @@ def shuffle_indices(seed: int, epoch: int, n: int, first: int = 0, count: int | 
     out = np.empty(count, np.uint64)
     lib().flexflow_shuffle_indices(int(seed) & (2**64 - 1), int(epoch), int(first), count, int(n), out.ctypes.data)
     return out.astype(np.int64)
+
+
+def _mix64(z: np.ndarray) -> np.ndarray:
+    """ffh_mix64 (include/ffh_rng.h) on a uint64 array; the arithmetic wraps as uint64 does"""
+    z = z + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def state_digest_reference(data, seed: int, index_base: int = 0, row_bytes: int | None = None) -> int:
+    """The digest of include/ff_hip_digest.h restated in numpy: `data` is a 2-D array (its rows are the rows, row_bytes their length in bytes:
+    whatever its strides are, only the elements count, so the result does not depend on a leading dimension), a 1-D array (one row), or
+    bytes / bytearray (rows of row_bytes bytes each; default one row).  W = ceil(row_bytes / 8) little-endian words per row, bytes past
+    row_bytes zero; word (r, w) has index i = index_base + r W + w; the result is sum ffh_mix64(ffh_hash(seed, i) ^ word) mod 2^64."""
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        raw = np.frombuffer(bytes(data), np.uint8)
+        rb = len(raw) if row_bytes is None else int(row_bytes)
+        if rb <= 0 or len(raw) % rb:
+            raise ValueError("state_digest_reference: the bytes are no whole number of rows")
+        rows2 = raw.reshape(-1, rb)
+    else:
+        a = np.asarray(data)
+        if a.ndim == 1:
+            a = a.reshape(1, -1)
+        if a.ndim != 2:
+            raise ValueError("state_digest_reference: a 1-D or 2-D array")
+        a = np.ascontiguousarray(a)
+        rows2 = a.view(np.uint8).reshape(a.shape[0], a.shape[1] * a.dtype.itemsize)
+        if row_bytes is not None and int(row_bytes) != rows2.shape[1]:
+            raise ValueError("state_digest_reference: row_bytes does not match the array's rows")
+        rb = rows2.shape[1]
+    if rb < 2 or rb % 2:
+        raise ValueError("state_digest_reference: row_bytes must be even and >= 2")
+    n, W = rows2.shape[0], (rb + 7) // 8
+    if n == 0:
+        return 0
+    total = 0
+    block = max(1, (1 << 17) // W)          # rows per pass: the temporaries stay in cache
+    with np.errstate(over="ignore"):
+        key = _mix64(np.array([int(seed) & (2 ** 64 - 1)], np.uint64))[0]
+        for r0 in range(0, n, block):
+            part = rows2[r0:r0 + block]
+            padded = np.zeros((part.shape[0], 8 * W), np.uint8)
+            padded[:, :rb] = part
+            words = padded.view("<u8").reshape(-1).astype(np.uint64)
+            i = np.arange(words.size, dtype=np.uint64) + np.uint64((int(index_base) + r0 * W) & (2 ** 64 - 1))
+            total += int(np.add.reduce(_mix64(_mix64(key + i) ^ words), dtype=np.uint64))
+    return total & (2 ** 64 - 1)
+
+
+def state_digest_host(data, seed: int, index_base: int = 0, row_bytes: int | None = None, ld_bytes: int | None = None) -> int:
+    """ffh_state_digest_host of include/ff_hip_digest.h -- the header's own inline function as the host layer compiles it -- on a contiguous
+    buffer of rows ld_bytes apart (default row_bytes)."""
+    raw = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+    rb = len(raw) if row_bytes is None else int(row_bytes)
+    ld = rb if ld_bytes is None else int(ld_bytes)
+    if rb < 2 or rb % 2 or ld < rb or ld % 2:
+        raise ValueError("state_digest_host: row_bytes even and >= 2, ld_bytes even and >= row_bytes")
+    rows = 0 if len(raw) < rb else (len(raw) - rb) // ld + 1
+    raw = np.ascontiguousarray(raw)
+    return int(lib().flexflow_state_digest_host(raw.ctypes.data, rows, rb, ld, int(seed) & (2 ** 64 - 1), int(index_base) & (2 ** 64 - 1)))
+
+
+def digest_record_seed(ordinal: int) -> int:
+    """ffh_digest_record_seed: the digest seed of record `ordinal` of a checkpoint."""
+    return int(lib().flexflow_digest_record_seed(int(ordinal)))
+
+
+CHECKPOINT_MAGIC = b"FFHCKPT\n"
+_CK_DTYPES = {"f32": np.dtype("<f4"), "bf16": np.dtype("<u2"), "u64": np.dtype("<u8"), "raw": np.dtype("u1")}
+
+
+def read_checkpoint(path: str) -> dict:
+    """One rank's checkpoint file (DIR/rank-R-of-N.ffck; `path` may also be the directory of a one-rank checkpoint) as a dict: "meta" holds the
+    manifest -- the run fields (epochs_done, steps, optimizer, table_optimizer, embedding_dtype, embedding_rounding, world_size, rank, lr_route,
+    lr_host_steps; on the device learning-rate route also lr_schedule {base, warmup_steps, decay_start, decay_steps}), "tables" {operator: placement}, "digest" and "records" {name: {type, rows, cols, offset, digest, ordinal}} -- and every record
+    name maps to its contents, memory-mapped read-only: [rows][cols] float32 / uint16 (bf16 bit patterns) / uint64 / uint8 (raw).  Raises ValueError on a
+    file that is no checkpoint or is cut short; digests are NOT verified here (state_digest_reference(record, digest_record_seed(ordinal)) does that)."""
+    if os.path.isdir(path):
+        path = os.path.join(path, "rank-0-of-1.ffck")
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        head = f.read(24)
+        if len(head) < 24 or head[:8] != CHECKPOINT_MAGIC:
+            raise ValueError(f"{path}: not a checkpoint file")
+        version, length = int.from_bytes(head[8:12], "little"), int.from_bytes(head[16:24], "little")
+        if version != 1:
+            raise ValueError(f"{path}: format version {version}")
+        text = f.read(length)
+    if len(text) != length:
+        raise ValueError(f"{path}: truncated manifest")
+    data_start = (24 + length + 4095) // 4096 * 4096
+    meta = {"version": version, "tables": {}, "records": {}, "path": path}
+    for line in text.decode().splitlines():
+        k, *v = line.split()
+        if k == "record":
+            meta["records"][v[1]] = {"ordinal": int(v[0]), "type": v[2], "rows": int(v[3]), "cols": int(v[4]), "offset": int(v[5]), "digest": int(v[6], 16)}
+        elif k == "table":
+            meta["tables"][v[0]] = v[1]
+        elif k == "digest":
+            meta["digest"] = int(v[0], 16)
+        elif k in ("epochs_done", "steps", "world_size", "rank", "lr_host_steps"):
+            meta[k] = int(v[0])
+        elif k == "lr_schedule":
+            meta[k] = {"base": float(v[0]), "warmup_steps": int(v[1]), "decay_start": int(v[2]), "decay_steps": int(v[3])}
+        elif k in ("optimizer", "table_optimizer", "embedding_dtype", "embedding_rounding", "lr_route"):
+            meta[k] = v[0]
+    out = {"meta": meta}
+    for name, r in meta["records"].items():
+        dt = _CK_DTYPES[r["type"]]
+        nbytes = r["rows"] * r["cols"] * dt.itemsize
+        if data_start + r["offset"] + nbytes > size:
+            raise ValueError(f"{path}: truncated inside record {name}")
+        out[name] = np.memmap(path, dtype=dt, mode="r", offset=data_start + r["offset"], shape=(r["rows"], r["cols"])) if nbytes else np.zeros((r["rows"], r["cols"]), dt)
+    return out
 
 
 def cross_reference(x0, v, xl) -> np.ndarray:
@@ -386,6 +507,23 @@ class FFModel:
         xl is x0.  Needs a kernel library with the cross extension: compile() refuses the model otherwise."""
         return Tensor(lib().flexflow_model_add_cross_combine(self.h, x0.h, v.h, xl.h, name.encode() if name else None), self)
 
+    def save_checkpoint(self, dir: str, epochs_done: int = 0) -> None:
+        """Writes this rank's file of a checkpoint, DIR/rank-R-of-N.ffck: every parameter this rank holds, the optimizer state, the
+        learning-rate position and the bf16 rounding counter, each record with its digest.  Between steps; synchronises; aborts with the reason on failure."""
+        lib().flexflow_model_save_checkpoint(self.h, os.fsencode(dir), int(epochs_done))
+
+    def load_checkpoint(self, dir: str) -> dict:
+        """Loads DIR/rank-R-of-N.ffck into this compiled model, verifying every record's digest after the copy; whatever does not fit (other shapes,
+        optimizer, element type, world size, placement, a damaged file) aborts with "FATAL: --load-checkpoint DIR: <reason>".  Returns {"epochs_done"}."""
+        e = C.c_int64(0)
+        lib().flexflow_model_load_checkpoint(self.h, os.fsencode(dir), C.byref(e))
+        return {"epochs_done": int(e.value)}
+
+    def state_digest(self) -> int:
+        """The fold (sum mod 2^64) of the digests of every record a checkpoint of this model would hold -- its "digest" line; on the device where the
+        kernel library has the digest extension (include/ff_hip_digest.h), nothing but one word is copied out.  Synchronises."""
+        return int(lib().flexflow_model_state_digest(self.h))
+
     def cross_net(self, x0: Tensor, num_layers: int = 3, low_rank: int = 512, name=None) -> Tensor:
         """torchrec's LowRankCrossNet on x0 [batch][D]: per layer u = dense(x_l, low_rank, no bias), v = dense(u, D), x_{l+1} =
         cross_combine(x0, v, x_l) -- 3 * num_layers operators; returns x_L."""
@@ -512,6 +650,7 @@ class DLRM:
 
     num_samples = property(lambda s: lib().flexflow_dlrm_get_num_samples(s.h))
     num_tables = property(lambda s: lib().flexflow_dlrm_get_num_tables(s.h))
+    start_epoch = property(lambda s: lib().flexflow_dlrm_get_start_epoch(s.h))      # --load-checkpoint: the epochs the checkpoint had completed
     def sparse_input(self, t) -> Tensor: return Tensor(lib().flexflow_dlrm_get_sparse_input(self.h, t), self.model)
     def dense_input(self) -> Tensor: return Tensor(lib().flexflow_dlrm_get_dense_input(self.h), self.model)
     def label_input(self) -> Tensor:

@@ -137,6 +137,23 @@ const KernelApi* load_kernel_api(const std::string& path_in) {
     }
     api->cross = b;
   }
+  // the digest extension (include/ff_hip_digest.h): the same rule
+  if (dlsym(h, "ffh_digest_abi_version")) {
+    KernelApiDigest* b = new KernelApiDigest();
+#define FFH_LOAD(name)                                                        \
+  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
+  if (!b->name) {                                                             \
+    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_digest.h: %s is missing\n", path.c_str(), #name);   \
+    abort();                                                                  \
+  }
+    FFH_DIGEST_API_LIST(FFH_LOAD)
+#undef FFH_LOAD
+    if (b->ffh_digest_abi_version() != FFH_DIGEST_ABI_VERSION) {
+      fprintf(stderr, "FATAL: %s has digest ABI version %d, expected %d\n", path.c_str(), b->ffh_digest_abi_version(), FFH_DIGEST_ABI_VERSION);
+      abort();
+    }
+    api->digest = b;
+  }
   if (path_in.empty() && g_env_override)
     fprintf(stderr, "[DLRM] FFH_BACKEND_LIB: kernel library %s (%s)\n", path.c_str(), api->ffh_backend_name());
   cache[path] = api;

@@ -9,6 +9,7 @@
 #include "../../include/ff_hip_lr.h"
 #include "../../include/ff_hip_data.h"
 #include "../../include/ff_hip_cross.h"
+#include "../../include/ff_hip_digest.h"
 
 // The optional bf16-table extension (include/ff_hip_bf16.h): all of its list or none of it.
 struct KernelApiBf16 {
@@ -45,6 +46,13 @@ struct KernelApiCross {
 #undef FFH_DECL
 };
 
+// The optional digest extension (include/ff_hip_digest.h: a 64-bit digest of a strided device buffer).
+struct KernelApiDigest {
+#define FFH_DECL(name) decltype(&::name) name;
+  FFH_DIGEST_API_LIST(FFH_DECL)
+#undef FFH_DECL
+};
+
 struct KernelApi {
 #define FFH_DECL(name) decltype(&::name) name;
   FFH_API_LIST(FFH_DECL)
@@ -54,6 +62,7 @@ struct KernelApi {
   const KernelApiLr* lr = nullptr;       // likewise for include/ff_hip_lr.h
   const KernelApiData* data = nullptr;   // likewise for include/ff_hip_data.h
   const KernelApiCross* cross = nullptr; // likewise for include/ff_hip_cross.h
+  const KernelApiDigest* digest = nullptr;   // likewise for include/ff_hip_digest.h (absent: the host layer computes the same digest from the bytes it copies)
   void* handle;
   std::string path;
   bool overridden = false;      // chosen by --backend or $FFH_BACKEND_LIB rather than the product default: the driver says so on its THROUGHPUT line

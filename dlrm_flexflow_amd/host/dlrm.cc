@@ -484,6 +484,29 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
   }
   loader = new DataLoader(*ff, dlrm, sparse_inputs, dense_input, ff->label_tensor);
   ff->init_layers();
+  // checkpoint / resume; silent without the flags
+  if (ffconfig.checkpoint_every_epochs > 0 && ffconfig.save_checkpoint_dir.empty()) {
+    fprintf(stderr, "FATAL: --checkpoint-every-epochs %d: needs --save-checkpoint DIR to say where\n", ffconfig.checkpoint_every_epochs);
+    abort();
+  }
+  if (!ffconfig.load_checkpoint_dir.empty()) {
+    const FFModel::CheckpointInfo info = ff->load_checkpoint(ffconfig.load_checkpoint_dir);
+    start_epoch = (int)info.epochs_done;
+    if (chatty)
+      printf("[DLRM] checkpoint: loaded %s (epoch %lld, step %lld, digest 0x%016llx)\n", ffconfig.load_checkpoint_dir.c_str(), (long long)info.epochs_done,
+             (long long)info.steps, (unsigned long long)info.digest);
+  } else if (chatty && !ffconfig.save_checkpoint_dir.empty()) {
+    printf("[DLRM] checkpoint: none\n");
+  }
+  if (chatty) fflush(stdout);
+}
+
+double DLRMApp::save_checkpoint(int epochs_done) {
+  ff->sync();
+  const double t0 = now_us();
+  ff->save_checkpoint(ffconfig.save_checkpoint_dir, epochs_done);
+  if (ffconfig.comm.world_size > 1 && ffconfig.comm.barrier) ffconfig.comm.barrier(ffconfig.comm.user);      // a checkpoint is complete once every rank's file is
+  return 1e-6 * (now_us() - t0);
 }
 
 DLRMApp::~DLRMApp() {
@@ -541,7 +564,11 @@ void DLRMApp::train_steps(int n, bool trace) {
 }
 
 double DLRMApp::run_epochs() {
-  if (!warmed_up && !ffconfig.eval_only) warmup();      // (--eval-only: no training step at all)
+  const bool resumed = !ffconfig.load_checkpoint_dir.empty();
+  // (--eval-only: no training step at all.  --load-checkpoint: the warm-up step is part of what the checkpoint holds; the inputs get the batch
+  //  the warm-up would have left in them, which a plain synthetic run trains on without ever loading another)
+  if (resumed && !warmed_up) { loader->reset(0); loader->load_batch(*ff, 0); warmed_up = true; }
+  if (!warmed_up && !ffconfig.eval_only) warmup();
   if (ff->config.trace_mode < 0) ff->config.trace_mode = 0;     // the driver's loop: a step is replayed only where the replay is not slower (FFConfig::trace_mode)
   const bool chatty = ff->rank == 0;
   ff->sync();   // issue_execution_fence + timing measurement
@@ -554,25 +581,36 @@ double DLRMApp::run_epochs() {
   }
   double eval_secs = 0.0;                // evaluation is outside the timed region: its wall time is taken out again below
   const double ts_start = now_us();
-  if (ffconfig.eval_only) eval_secs += evaluate(0);
-  for (int epoch = 0; epoch < ffconfig.epochs && !ffconfig.eval_only; epoch++) {
+  double save_secs = 0.0;                // ... and so is saving a checkpoint
+  int epochs_run = 0;
+  if (ffconfig.eval_only) eval_secs += evaluate(start_epoch);      // (a loaded model: under the epoch number its last evaluation had)
+  for (int epoch = start_epoch; epoch < ffconfig.epochs && !ffconfig.eval_only; epoch++) {
     loader->reset(epoch);
     ff->reset_metrics();
     const int iterations = loader->num_train / ffconfig.batchSize;
     train_steps(iterations, epoch > 0 /* the reference traces from the second epoch on */);
     if (ffconfig.eval_batches > 0) eval_secs += evaluate(epoch + 1);
+    epochs_run++;
+    // epoch boundaries only: the data cursor is 0 and the next epoch's order follows from (--seed, epoch) alone
+    const bool last = epoch + 1 == ffconfig.epochs;
+    if (!ffconfig.save_checkpoint_dir.empty() && (last || (ffconfig.checkpoint_every_epochs > 0 && (epoch + 1) % ffconfig.checkpoint_every_epochs == 0)))
+      save_secs += save_checkpoint(epoch + 1);
   }
+  // (nothing left to train -- a checkpoint that had already completed --epochs -- or --eval-only: the state is saved as it is)
+  if (!ffconfig.save_checkpoint_dir.empty() && epochs_run == 0) save_secs += save_checkpoint(start_epoch);
   ff->sync();
   if (ffconfig.comm.world_size > 1 && ffconfig.comm.barrier) ffconfig.comm.barrier(ffconfig.comm.user);
   const double ts_end = now_us();
-  const double run_time = 1e-6 * (ts_end - ts_start) - eval_secs;
+  const double run_time = 1e-6 * (ts_end - ts_start) - eval_secs - save_secs;
   if (chatty && !ffconfig.eval_only) {      // (--eval-only trained nothing: no training metrics, no throughput)
     PerfMetrics pm = ff->get_perf_metrics();
     pm.print(ff->metrics_flags);
     // [ref: examples/cpp/DLRM/dlrm.cc:193-194] -- the reference's line as it is; a kernel library other than the product's own
     // (--backend / FFH_BACKEND_LIB: the CPU oracle in tests, an A/B build) is named on it, so a number can never be mistaken
-    printf("ELAPSED TIME = %.4fs, THROUGHPUT = %.2f samples/s", run_time, loader->num_train * (double)ffconfig.epochs / run_time);
+    printf("ELAPSED TIME = %.4fs, THROUGHPUT = %.2f samples/s", run_time, loader->num_train * (double)(resumed ? epochs_run : ffconfig.epochs) / run_time);
     if (ffconfig.eval_batches > 0) printf("  [wall time minus %.4fs of evaluation]", eval_secs);
+    if (!ffconfig.save_checkpoint_dir.empty()) printf("  [wall time minus %.4fs of checkpoint saving]", save_secs);
+    if (resumed) printf("  [resumed: epochs %d to %d]", start_epoch, start_epoch + epochs_run);
     if (ff->api->overridden) printf("  [kernel library: %s, %s]", ff->api->ffh_backend_name(), ff->api->path.c_str());
     printf("\n");
   }

@@ -72,6 +72,8 @@ struct DLRMApp {
   std::vector<Tensor> sparse_inputs;
   Tensor dense_input;
   bool warmed_up;
+  int start_epoch = 0;           // --load-checkpoint: the epochs the checkpoint had completed; run_epochs() goes on from there
+  double save_checkpoint(int epochs_done);   // --save-checkpoint: every rank writes its file; returns the wall time in seconds (outside the timed region)
   DLRMApp(int argc, char** argv, const ffcomm* comm);
   ~DLRMApp();
   void warmup();                 // the reference's single warm-up iteration

@@ -104,6 +104,8 @@ class FFConfig {
   static MappingTagID get_hash_id(const std::string& pcname);
   bool find_parallel_config(int ndims, const std::string& pcname, ParallelConfig& config) const;   // false: not in the file
   // this build
+  std::string save_checkpoint_dir, load_checkpoint_dir;   // --save-checkpoint DIR / --load-checkpoint DIR (the DLRM driver)
+  int checkpoint_every_epochs;                             // --checkpoint-every-epochs K: also after every K-th epoch (0: only after the last)
   std::string backend_lib;     // library exporting include/ff_hip.h; default: libffhip.so next to libffmodel.so
   int device;                  // HIP device ordinal of this process
   uint64_t seed;               // counter-based RNG seed (reference: unseeded std::rand)
@@ -673,6 +675,15 @@ class FFModel {
   double current_lr();                        // the scheduled rate of the next optimizer step (base rate: --lr / alpha), as the float the kernels get
   int64_t lr_steps();                         // optimizer steps taken (kLrDevice: read back from lr_block[0]; synchronises)
   std::string lr_schedule_line() const;       // "W=.. S=.. N=.. route=..": the driver's start-up line
+  // checkpoint save / exact resume (host/checkpoint.cc).  Between steps only (never inside begin/end_trace); both synchronise.
+  // save_checkpoint writes DIR/rank-R-of-N.ffck (temporary name + rename); load_checkpoint refuses with "FATAL: --load-checkpoint DIR: ..." whatever
+  // does not fit this model; state_digest is the fold of every record's digest (include/ff_hip_digest.h), on the device where the library has the extension
+  struct CheckpointInfo { int64_t epochs_done = 0, steps = 0; uint64_t digest = 0; size_t bytes = 0; };
+  CheckpointInfo save_checkpoint(const std::string& dir, int64_t epochs_done);
+  CheckpointInfo load_checkpoint(const std::string& dir);
+  uint64_t state_digest();
+  int64_t n_update_calls = 0;                 // optimizer steps taken (update() calls, replayed ones included): a checkpoint's "steps"
+  uint64_t* digest_acc = nullptr;             // the digest's accumulator word in device memory (allocated by the first use)
   mutable int64_t n_graph_replays = 0;        // hipGraph launches of an already captured trace (tests: flexflow_model_get_counter "graph_replays")
   mutable int64_t n_early_sorts = 0;          // sort-only launches issued behind the gather (tests: flexflow_model_get_counter "early_sorts")
   bool fused_embedding_update() const;        // the tables are updated on the sorted segments (plain SGD, or any optimizer with --sparse-embedding-optimizer)

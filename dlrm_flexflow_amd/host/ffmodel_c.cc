@@ -174,6 +174,18 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   return -1;
 }
 
+int flexflow_model_save_checkpoint(flexflow_model_t m, const char* dir, int64_t epochs_done) { M(m)->save_checkpoint(dir ? dir : "", epochs_done); return 0; }
+int flexflow_model_load_checkpoint(flexflow_model_t m, const char* dir, int64_t* epochs_done) {
+  const FFModel::CheckpointInfo info = M(m)->load_checkpoint(dir ? dir : "");
+  if (epochs_done) *epochs_done = info.epochs_done;
+  return 0;
+}
+uint64_t flexflow_model_state_digest(flexflow_model_t m) { return M(m)->state_digest(); }
+uint64_t flexflow_state_digest_host(const void* base, int64_t rows, int64_t row_bytes, int64_t ld_bytes, uint64_t seed, uint64_t index_base) {
+  return ffh_state_digest_host(base, rows, row_bytes, ld_bytes, seed, index_base);
+}
+uint64_t flexflow_digest_record_seed(uint64_t ordinal) { return ffh_digest_record_seed(ordinal); }
+
 int flexflow_tensor_get_num_dims(flexflow_tensor_t t) { return T(t)->numDim; }
 void flexflow_tensor_get_dims(flexflow_tensor_t t, int* dims) { for (int i = 0; i < T(t)->numDim; i++) dims[i] = T(t)->adim[T(t)->numDim - 1 - i]; }
 int64_t flexflow_tensor_get_local_rows(flexflow_tensor_t t) { return T(t)->impl ? T(t)->impl->rows_local : 0; }
@@ -197,6 +209,7 @@ void flexflow_tensor_get_bf16(flexflow_tensor_t t, flexflow_model_t m, uint16_t*
 
 flexflow_dlrm_t flexflow_dlrm_create(int argc, char** argv, const ffcomm* comm) { flexflow_dlrm_t h; h.impl = new DLRMApp(argc, argv, comm); return h; }
 void flexflow_dlrm_destroy(flexflow_dlrm_t h) { delete A(h); }
+int flexflow_dlrm_get_start_epoch(flexflow_dlrm_t h) { return A(h)->start_epoch; }
 flexflow_model_t flexflow_dlrm_get_model(flexflow_dlrm_t h) { flexflow_model_t m; m.impl = A(h)->ff; return m; }
 int flexflow_dlrm_get_num_samples(flexflow_dlrm_t h) { return A(h)->loader->num_samples; }
 int flexflow_dlrm_get_num_tables(flexflow_dlrm_t h) { return (int)A(h)->sparse_inputs.size(); }

@@ -125,6 +125,17 @@ int  flexflow_model_trace_replays(flexflow_model_t, int trace_id);   /* 0 once t
 int64_t flexflow_model_get_counter(flexflow_model_t, const char* name);   /* diagnostics for tests: "mlp_chain_fwd_calls", "mlp_chain_bwd_calls", "fused_loss_calls",
                                                                             "bf16_updates" (the bf16 tables' update counter, synchronises); -1: unknown */
 
+/* Checkpoint save / exact resume (host/checkpoint.cc).  Both return 0, or print "FATAL: ..." and abort like compile(); both synchronise
+ * and are called between steps.  save writes dir/rank-R-of-N.ffck; load writes the epochs the file had completed into *epochs_done (may be NULL). */
+int flexflow_model_save_checkpoint(flexflow_model_t, const char* dir, int64_t epochs_done);
+int flexflow_model_load_checkpoint(flexflow_model_t, const char* dir, int64_t* epochs_done);
+/* the fold (wrapping sum) of every checkpoint record's digest (include/ff_hip_digest.h): equal for two models iff a checkpoint of one would equal a
+ * checkpoint of the other record by record (up to a 2^-64 collision); on the device where the kernel library has the extension; synchronises */
+uint64_t flexflow_model_state_digest(flexflow_model_t);
+/* ffh_state_digest_host of include/ff_hip_digest.h on host memory: the definition as the host layer compiles it */
+uint64_t flexflow_state_digest_host(const void* base, int64_t rows, int64_t row_bytes, int64_t ld_bytes, uint64_t seed, uint64_t index_base);
+uint64_t flexflow_digest_record_seed(uint64_t ordinal);   /* ffh_digest_record_seed: the digest seed of a checkpoint's record */
+
 /* Tensor / Parameter host<->device [ref: flexflow_parameter_set_weights_float, python/flexflow_c.h:498-546] */
 int  flexflow_tensor_get_num_dims(flexflow_tensor_t);
 void flexflow_tensor_get_dims(flexflow_tensor_t, int* dims);            /* natural order: dims[0] = batch */
@@ -150,6 +161,7 @@ void flexflow_dlrm_destroy(flexflow_dlrm_t);
 flexflow_model_t flexflow_dlrm_get_model(flexflow_dlrm_t);
 int  flexflow_dlrm_get_num_samples(flexflow_dlrm_t);
 int  flexflow_dlrm_get_num_tables(flexflow_dlrm_t);
+int  flexflow_dlrm_get_start_epoch(flexflow_dlrm_t);   /* --load-checkpoint: the epochs the checkpoint had completed (0 without it) */
 flexflow_tensor_t flexflow_dlrm_get_sparse_input(flexflow_dlrm_t, int table);
 flexflow_tensor_t flexflow_dlrm_get_dense_input(flexflow_dlrm_t);
 void flexflow_dlrm_warmup(flexflow_dlrm_t);

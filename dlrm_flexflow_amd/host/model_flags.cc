@@ -76,6 +76,7 @@ FFConfig::FFConfig() {
   lr_warmup_steps = lr_decay_start_step = lr_num_decay_steps = 0;
   device_lr = false;
   host_lr_schedule = false;
+  checkpoint_every_epochs = 0;
   memset(&comm, 0, sizeof comm);
   comm.rank = 0;
   comm.world_size = 1;
@@ -190,6 +191,13 @@ void FFConfig::parse_args(char** argv, int argc) {
     if (is("--lr-num-warmup-steps")) { lr_warmup_steps = atoll(next()); continue; }
     if (is("--lr-decay-start-step")) { lr_decay_start_step = atoll(next()); continue; }
     if (is("--lr-num-decay-steps")) { lr_num_decay_steps = atoll(next()); continue; }
+    if (is("--save-checkpoint")) { save_checkpoint_dir = next(); if (save_checkpoint_dir.empty()) die("--save-checkpoint: needs a directory"); continue; }
+    if (is("--load-checkpoint")) { load_checkpoint_dir = next(); if (load_checkpoint_dir.empty()) die("--load-checkpoint: needs a directory"); continue; }
+    if (is("--checkpoint-every-epochs")) {
+      checkpoint_every_epochs = atoi(next());
+      if (checkpoint_every_epochs < 1) die("--checkpoint-every-epochs %d: must be >= 1", checkpoint_every_epochs);
+      continue;
+    }
     if (is("--device-lr")) { device_lr = true; continue; }
     if (is("--host-lr-schedule")) { host_lr_schedule = true; continue; }
     if (is("--embedding-rounding")) {

@@ -4,6 +4,7 @@
 //   model_flags.cc     FFConfig: defaults and the command line [ref: src/runtime/model.cc:2212-2403]
 //   model_allocate.cc  compile() / allocate(): storage, aliasing, shards, buckets, twins and images
 //   model_exchange.cc  the embedding group (gather, exchange, fused update) and the MLP gradients' all-reduce (buckets, ring / direct)
+//   checkpoint.cc      save_checkpoint / load_checkpoint / state_digest
 //   model_step.cc      forward / zero_gradients / backward / update, traces, sync [ref: src/runtime/model.cc:1410-1477]
 #pragma once
 #include "ffmodel.h"

@@ -300,6 +300,7 @@ void FFModel::backward(int _seq_length) {
 }
 
 void FFModel::update() {
+  n_update_calls++;              // (a replayed step counts: its update is in the graph)
   if (replaying_trace >= 0) return;
   optimizer->next();
   opt_next_done = true;
