@@ -57,6 +57,7 @@ class SparseOpt(C.Structure):
 
 
 SPARSE_OPT_SGD, SPARSE_OPT_SGD_MOMENTUM, SPARSE_OPT_ADAM = 0, 1, 2
+SPARSE_OPT_ADAGRAD = 3      # include/ff_hip_adagrad.h: accepted by a library with the Adagrad extension
 
 
 class PerfMetrics(C.Structure):
@@ -298,6 +299,33 @@ def cross_header_abi_version(header_path: str = CROSS_HEADER_PATH) -> int:
     m = re.search(r"#define\s+FFH_CROSS_ABI_VERSION\s+(\d+)", open(header_path).read())
     if not m:
         raise RuntimeError("FFH_CROSS_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
+# include/ff_hip_adagrad.h: the optional Adagrad extension (the dense launch; FFH_SPARSE_OPT_ADAGRAD in the table update); same rule
+ADAGRAD_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_adagrad.h")
+
+_SIGS_ADAGRAD = {
+    "ffh_adagrad_abi_version": (I, []),
+    "ffh_adagrad_update": (I, [P, P, P, P, L, F, F, F, I, P]),
+    "ffh_adagrad_update_lr": (I, [P, P, P, P, L, P, F, F, I, P]),
+}
+
+
+def adagrad_header_symbols(header_path: str = ADAGRAD_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_ADAGRAD_API_LIST X-macro in include/ff_hip_adagrad.h."""
+    text = open(header_path).read()
+    m = re.search(r"#define FFH_ADAGRAD_API_LIST\(X\)(.*?)\n\n", text, re.S)
+    if not m:
+        raise RuntimeError("FFH_ADAGRAD_API_LIST not found in " + header_path)
+    return re.findall(r"X\((\w+)\)", m.group(1))
+
+
+def adagrad_header_abi_version(header_path: str = ADAGRAD_HEADER_PATH) -> int:
+    """FFH_ADAGRAD_ABI_VERSION of include/ff_hip_adagrad.h."""
+    m = re.search(r"#define\s+FFH_ADAGRAD_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_ADAGRAD_ABI_VERSION not found in " + header_path)
     return int(m.group(1))
 
 
@@ -752,6 +780,41 @@ class CrossApi:
 def cross_api(lib: FFHLib) -> CrossApi:
     """The cross entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
     return CrossApi(lib)
+
+
+class AdagradApi:
+    """The Adagrad extension (include/ff_hip_adagrad.h) of a loaded FFHLib; `adagrad_api(lib)` builds it or raises."""
+
+    def __init__(self, lib: FFHLib):
+        self.base = lib
+        for name, (res, args) in _SIGS_ADAGRAD.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no Adagrad extension ({name} missing; include/ff_hip_adagrad.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_adagrad_abi_version()
+        if got != adagrad_header_abi_version():
+            raise FFHError(f"{lib.path}: Adagrad ABI version {got}, include/ff_hip_adagrad.h says {adagrad_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+    def rc(self, name: str, *args) -> int:
+        """`name(ctx, *args)` of the extension, returning its status code (FFH_OK, FFH_ERR_BAD_ARG, ...)."""
+        sig = _SIGS_ADAGRAD[name][1][1:]
+        if len(args) != len(sig):
+            raise TypeError(f"{name}: expected {len(sig)} args, got {len(args)}")
+        conv = [ptr(a) if t is P else a for a, t in zip(args, sig)]
+        return getattr(self.lib, name)(self.ctx, *conv)
+
+    def call(self, name: str, *args):
+        """Call `name(ctx, *args)` of the extension; pointers may be tensors/arrays/ints/None."""
+        self.base.check(self.rc(name, *args), name)
+
+
+def adagrad_api(lib: FFHLib) -> AdagradApi:
+    """The Adagrad entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
+    return AdagradApi(lib)
 
 
 _hip_singleton: FFHLib | None = None

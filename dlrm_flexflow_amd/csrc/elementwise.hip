@@ -4,6 +4,7 @@
 // [ref: src/ops/concat.cu:243-248,353-357]).
 #include "ffh_common.h"
 #include "lr_state.h"
+#include "../../include/ff_hip_adagrad.h"
 
 namespace {
 
@@ -396,6 +397,63 @@ __global__ __launch_bounds__(256) void adam_lr_kernel(float* __restrict__ w, flo
   adam_body<VEC>(w, g, m, v, n, *alpha_src, b1, b2, wd, eps, zero_grad, twin, planes, e0);
 }
 
+// Adagrad, torch.optim.Adagrad's element-wise rule with the canonical rounding of include/ff_hip_adagrad.h: every operation rounded on its
+// own (no contraction), sqrtf and / correctly rounded as in adam_body.  WD is a template parameter: without weight decay gt IS g (not
+// g + 0 * w, which would turn a NaN / Inf weight's g == 0 element into NaN and cost a multiply on the common path).
+// (adagrad_kernel / adagrad_lr_kernel: as sgd_kernel / sgd_lr_kernel)
+template <bool WD>
+__device__ __forceinline__ void adagrad_element(float& w, const float g, float& S, float lr, float eps, float wd) {
+#pragma clang fp contract(off)
+  float gt = g;
+  if (WD) { const float t0 = wd * w; gt = g + t0; }
+  const float t1 = gt * gt;
+  S = S + t1;
+  const float d = sqrtf(S) + eps;
+  const float q = gt / d;
+  const float t2 = lr * q;
+  w = w - t2;
+}
+template <int VEC, bool WD>
+__device__ __forceinline__ void adagrad_body(float* __restrict__ w, float* __restrict__ g, float* __restrict__ S, int64_t n, float lr, float eps, float wd,
+                                             int zero_grad, unsigned short* __restrict__ twin, char* __restrict__ planes, int64_t e0) {
+  ffh_kernel_prio();
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t nv = n / VEC;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += stride) {
+    float wv[VEC], gv[VEC], sv[VEC];
+    if (VEC == 4) {
+      const float4 a = reinterpret_cast<const float4*>(w)[i], b = reinterpret_cast<const float4*>(g)[i], c = reinterpret_cast<const float4*>(S)[i];
+      wv[0] = a.x; wv[1] = a.y; wv[2] = a.z; wv[3] = a.w;
+      gv[0] = b.x; gv[1] = b.y; gv[2] = b.z; gv[3] = b.w;
+      sv[0] = c.x; sv[1] = c.y; sv[2] = c.z; sv[3] = c.w;
+    } else {
+      wv[0] = w[i]; gv[0] = g[i]; sv[0] = S[i];
+    }
+#pragma unroll
+    for (int k = 0; k < VEC; k++) adagrad_element<WD>(wv[k], gv[k], sv[k], lr, eps, wd);
+    if (VEC == 4) {
+      reinterpret_cast<float4*>(w)[i] = make_float4(wv[0], wv[1], wv[2], wv[3]);
+      store_mirrors(make_float4(wv[0], wv[1], wv[2], wv[3]), twin, planes, e0, i);
+      reinterpret_cast<float4*>(S)[i] = make_float4(sv[0], sv[1], sv[2], sv[3]);
+      if (zero_grad) reinterpret_cast<float4*>(g)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      w[i] = wv[0]; S[i] = sv[0];
+      if (zero_grad) g[i] = 0.f;
+    }
+  }
+}
+template <int VEC, bool WD>
+__global__ __launch_bounds__(256) void adagrad_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ S, int64_t n, float lr, float eps, float wd,
+                                                      int zero_grad, unsigned short* __restrict__ twin, char* __restrict__ planes, int64_t e0) {
+  adagrad_body<VEC, WD>(w, g, S, n, lr, eps, wd, zero_grad, twin, planes, e0);
+}
+template <int VEC, bool WD>
+__global__ __launch_bounds__(256) void adagrad_lr_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ S, int64_t n,
+                                                         const float* __restrict__ lr_src, float eps, float wd, int zero_grad,
+                                                         unsigned short* __restrict__ twin, char* __restrict__ planes, int64_t e0) {
+  adagrad_body<VEC, WD>(w, g, S, n, *lr_src, eps, wd, zero_grad, twin, planes, e0);      // one wave-uniform load
+}
+
 __global__ __launch_bounds__(256) void add_scaled_kernel(float* __restrict__ d, const float* __restrict__ src, int64_t n, float scale) {
   ffh_kernel_prio();
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -599,6 +657,48 @@ int ffh_adam_update_lr(ffh_ctx* c, float* w, float* g, float* m, float* v, int64
                        float eps, int flags, ffh_stream s) {
   FFH_REQUIRE(c, block != nullptr, "adam_update_lr: null ffh_lr_state");
   return adam_update_impl(c, w, g, m, v, n, 0.0f, ffh_lr_rate_ptr(block, true), b1, b2, wd, eps, flags, s);
+}
+
+}  // extern "C"
+
+// include/ff_hip_adagrad.h (lr_src: as in sgd_update_impl)
+static int adagrad_update_impl(ffh_ctx* c, float* w, float* g, float* S, int64_t n, float lr, const float* lr_src, float eps, float wd, int flags, ffh_stream s) {
+  FFH_REQUIRE(c, n >= 0 && ((w && g && S) || n == 0), "adagrad_update: bad args");
+  FFH_REQUIRE(c, (flags & ~FFH_OPT_ZERO_GRAD) == 0, "adagrad_update: unknown flags");
+  if (n == 0) return FFH_OK;
+  const int zg = (flags & FFH_OPT_ZERO_GRAD) ? 1 : 0;
+  const bool vec = al16(w) && al16(g) && al16(S) && (n % 4 == 0);
+  unsigned short* tw = ffh_mirror_of(c, w, (size_t)n * 4);      // (the mirrors: as in ffh_sgd_update_ex)
+  int col0 = 0;
+  char* pl = const_cast<char*>(ffh_planes_of(c, w, (size_t)n * 4, &col0));
+  const bool fused = vec && (!tw || ((uintptr_t)tw & 7) == 0) && (!pl || col0 % 4 == 0);
+  unsigned short* const ktw = fused ? tw : nullptr;
+  char* const kpl = fused ? pl : nullptr;
+  const int64_t ke0 = vec ? (int64_t)col0 : 0;
+  const dim3 grid(ffh_grid(vec ? n / 4 : n, 256));
+#define FFH_ADAGRAD(VECV, WDV)                                                                                                                         \
+  { if (lr_src) hipLaunchKernelGGL((adagrad_lr_kernel<VECV, WDV>), grid, dim3(256), 0, as_stream(s), w, g, S, n, lr_src, eps, wd, zg, ktw, kpl, ke0);     \
+    else hipLaunchKernelGGL((adagrad_kernel<VECV, WDV>), grid, dim3(256), 0, as_stream(s), w, g, S, n, lr, eps, wd, zg, ktw, kpl, ke0); }
+  if (vec) { if (wd != 0.0f) FFH_ADAGRAD(4, true) else FFH_ADAGRAD(4, false) }
+  else { if (wd != 0.0f) FFH_ADAGRAD(1, true) else FFH_ADAGRAD(1, false) }
+#undef FFH_ADAGRAD
+  FFH_LAUNCH_CHECK(c, "adagrad_kernel");
+  if (!fused && tw) return ffh_convert_f32_to_bf16(c, tw, w, n, s);
+  if (!fused && pl) return ffh_convert_f32_to_bf16x3(c, w, 1, n, n, s);
+  return FFH_OK;
+}
+
+extern "C" {
+
+int ffh_adagrad_abi_version(void) { return FFH_ADAGRAD_ABI_VERSION; }
+
+int ffh_adagrad_update(ffh_ctx* c, float* w, float* g, float* S, int64_t n, float lr, float eps, float wd, int flags, ffh_stream s) {
+  return adagrad_update_impl(c, w, g, S, n, lr, nullptr, eps, wd, flags, s);
+}
+
+int ffh_adagrad_update_lr(ffh_ctx* c, float* w, float* g, float* S, int64_t n, const ffh_lr_state* block, float eps, float wd, int flags, ffh_stream s) {
+  FFH_REQUIRE(c, block != nullptr, "adagrad_update_lr: null ffh_lr_state");
+  return adagrad_update_impl(c, w, g, S, n, 0.0f, ffh_lr_rate_ptr(block, false), eps, wd, flags, s);
 }
 
 int ffh_add_scaled(ffh_ctx* c, float* d, const float* src, int64_t n, float scale, ffh_stream s) {

@@ -18,6 +18,7 @@
 #include "../../include/ff_hip_bf16.h"
 #include "../../include/ffh_bf16.h"
 #include "lr_state.h"
+#include "../../include/ff_hip_adagrad.h"
 #ifdef FFH_MSD_TIMING
 #include <vector>
 #endif
@@ -435,8 +436,18 @@ constexpr int kOptSgdBf16 = 3;
 constexpr int kOptMomentumBf16 = 4;
 constexpr int kOptAdamBf16 = 5;
 
-constexpr bool opt_bf16(int OPT) { return OPT >= kOptSgdBf16; }                // 16-bit weight rows
-constexpr int opt_base(int OPT) { return opt_bf16(OPT) ? OPT - kOptSgdBf16 : OPT; }   // the fp32 row rule: 0 plain SGD, 1 momentum / wd SGD, 2 Adam
+// OPT 6 / 7 (kOptAdagrad, kOptAdagradBf16): Adagrad (include/ff_hip_adagrad.h), the element arithmetic of adagrad_element (elementwise.hip) statement
+// by statement (the same rounded operations; weight decay is chosen by a uniform branch instead of a template parameter); s0 = S, no s1, so the bf16 form rides the Bf16Keys layout like kOptMomentumBf16.  Numbered behind the bf16 constants: 0 .. 5 keep
+// their values, and the helpers below map both to the row rule 3
+constexpr int kOptAdagrad = 6;
+constexpr int kOptAdagradBf16 = 7;
+constexpr int kBaseAdagrad = 3;
+
+constexpr bool opt_bf16(int OPT) { return (OPT >= kOptSgdBf16 && OPT <= kOptAdamBf16) || OPT == kOptAdagradBf16; }                // 16-bit weight rows
+constexpr int opt_base(int OPT) {      // the fp32 row rule: 0 plain SGD, 1 momentum / wd SGD, 2 Adam, 3 Adagrad
+  return (OPT == kOptAdagrad || OPT == kOptAdagradBf16) ? kBaseAdagrad : (opt_bf16(OPT) ? OPT - kOptSgdBf16 : OPT);
+}
+static_assert(opt_base(kOptAdamBf16) == 2 && opt_base(kOptAdagradBf16) == kBaseAdagrad && opt_bf16(kOptAdagradBf16) && !opt_bf16(kOptAdagrad), "row rule numbering");
 constexpr bool opt_plain(int OPT) { return opt_base(OPT) == 0; }                // no optimizer state
 constexpr bool opt_state(int OPT) { return opt_base(OPT) != 0; }
 struct Bf16Keys { int32_t table[FFH_MAX_TABLES]; int32_t col0[FFH_MAX_TABLES]; };   // kOptSgdBf16 / kOptMomentumBf16: in place of the (unused) s1 pointers
@@ -531,7 +542,7 @@ __device__ __forceinline__ void apply_row(const OptP& o, float* wrow, float* s0r
   }
   constexpr int BASE = opt_base(OPT);
   float wv[VEC], av[VEC], bv[VEC];
-  const bool has0 = BASE == 2 || o.mom > 0.f;
+  const bool has0 = BASE == 2 || BASE == kBaseAdagrad || o.mom > 0.f;
   uint16_t* const w16 = reinterpret_cast<uint16_t*>(wrow);
   if (VEC == 4) {
     if (opt_bf16(OPT)) {
@@ -558,6 +569,16 @@ __device__ __forceinline__ void apply_row(const OptP& o, float* wrow, float* s0r
         gt = o.nesterov ? __fmaf_rn(o.mom, av[k], gt) : av[k];
       }
       wv[k] = __fmaf_rn(-o.lr, gt, wv[k]);
+    } else if (BASE == kBaseAdagrad) {      // include/ff_hip_adagrad.h: the statements of adagrad_element (elementwise.hip), av = S; weight decay is a wave-uniform branch here, a template parameter there
+#pragma clang fp contract(off)
+      float gt = acc[k];
+      if (o.wd != 0.f) { const float t0 = o.wd * wv[k]; gt = acc[k] + t0; }
+      const float t1 = gt * gt;
+      av[k] = av[k] + t1;
+      const float den = sqrtf(av[k]) + o.eps;
+      const float q = gt / den;
+      const float t2 = o.lr * q;
+      wv[k] = wv[k] - t2;
     } else {                   // adam_update [ref: src/runtime/optimizer_kernel.cu:206-226], as adam_kernel spells it (lr = alpha_t)
 #pragma clang fp contract(off)
       const float gt = fmaf(o.wd, wv[k], acc[k]);
@@ -1742,15 +1763,15 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   int kind = FFH_SPARSE_OPT_SGD;
   if (opt && do_apply) {
     kind = opt->kind;
-    if (kind != FFH_SPARSE_OPT_SGD && kind != FFH_SPARSE_OPT_SGD_MOMENTUM && kind != FFH_SPARSE_OPT_ADAM)
+    if (kind != FFH_SPARSE_OPT_SGD && kind != FFH_SPARSE_OPT_SGD_MOMENTUM && kind != FFH_SPARSE_OPT_ADAM && kind != FFH_SPARSE_OPT_ADAGRAD)
       return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt: unknown ffh_sparse_opt.kind");
-    if (b16 && kind != FFH_SPARSE_OPT_SGD && nt > FFH_BF16_MAX_STATEFUL_TABLES)
+    if (b16 && (kind == FFH_SPARSE_OPT_SGD_MOMENTUM || kind == FFH_SPARSE_OPT_ADAM) && nt > FFH_BF16_MAX_STATEFUL_TABLES)      // (Adagrad: one state pointer, the Bf16Keys layout)
       return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt_multi_bf16: momentum / Adam take at most FFH_BF16_MAX_STATEFUL_TABLES (32) tables per call");
     op.lr = opt->lr; op.wd = opt->weight_decay; op.mom = opt->momentum; op.nesterov = opt->nesterov ? 1 : 0;
     op.b1 = opt->beta1; op.b2 = opt->beta2; op.eps = opt->epsilon; op.omb1 = 1.0f - opt->beta1; op.omb2 = 1.0f - opt->beta2;
     if (kind == FFH_SPARSE_OPT_SGD && (op.wd != 0.0f || op.mom != 0.0f)) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt: FFH_SPARSE_OPT_SGD takes no weight decay / momentum (use FFH_SPARSE_OPT_SGD_MOMENTUM)");
     if (lr_block) { op.lr = 0.0f; opt_set_lr_src(op, ffh_lr_rate_ptr(lr_block, kind == FFH_SPARSE_OPT_ADAM)); }      // (include/ff_hip_lr.h: opt->lr is ignored)
-    const bool need0 = kind == FFH_SPARSE_OPT_ADAM || (kind == FFH_SPARSE_OPT_SGD_MOMENTUM && op.mom > 0.0f);
+    const bool need0 = kind == FFH_SPARSE_OPT_ADAM || kind == FFH_SPARSE_OPT_ADAGRAD || (kind == FFH_SPARSE_OPT_SGD_MOMENTUM && op.mom > 0.0f);
     for (int i = 0; i < nt && batch > 0; i++) {
       if (need0 && (!states || !states[i].s0)) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt: optimizer state (s0) missing");
       if (kind == FFH_SPARSE_OPT_ADAM && !states[i].s1) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt: optimizer state (s1) missing");
@@ -1764,7 +1785,7 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   if (maxR > (1LL << 32)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_sgd_fused: num_entries > 2^32");
   bool v4 = can_vec4(tables, nt, D);
   for (int i = 0; i < nt && v4 && kind != FFH_SPARSE_OPT_SGD; i++)
-    v4 = (!states[i].s0 || aligned16(states[i].s0)) && (!states[i].s1 || aligned16(states[i].s1));
+    v4 = (!states[i].s0 || aligned16(states[i].s0)) && (kind == FFH_SPARSE_OPT_ADAGRAD || !states[i].s1 || aligned16(states[i].s1));      // (Adagrad: s1 is unused)
   const int nvec = v4 ? D / 4 : D;
   if ((nvec + 63) / 64 > kMaxChunks * 64) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_sgd_fused: out_dim too large");
   const BwdLayout lay = bwd_layout(nt, L, D, batch);
@@ -1819,7 +1840,8 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
     { if (v4) hipLaunchKernelGGL((emb_sgd_small_kernel<4, OPTV, LRPV>), dim3(nt), dim3(kSmallThreads), 0, as_stream(s), sm);  \
       else hipLaunchKernelGGL((emb_sgd_small_kernel<1, OPTV, LRPV>), dim3(nt), dim3(kSmallThreads), 0, as_stream(s), sm); }
 #define FFH_SMALL(OPTV) { if (lr_block) FFH_SMALL_L(OPTV, true) else FFH_SMALL_L(OPTV, false) }
-    if (b16) { if (kind == FFH_SPARSE_OPT_SGD) FFH_SMALL(kOptSgdBf16) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_SMALL(kOptMomentumBf16) else FFH_SMALL(kOptAdamBf16) }
+    if (kind == FFH_SPARSE_OPT_ADAGRAD) { if (b16) FFH_SMALL(kOptAdagradBf16) else FFH_SMALL(kOptAdagrad) }
+    else if (b16) { if (kind == FFH_SPARSE_OPT_SGD) FFH_SMALL(kOptSgdBf16) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_SMALL(kOptMomentumBf16) else FFH_SMALL(kOptAdamBf16) }
     else if (kind == FFH_SPARSE_OPT_SGD) FFH_SMALL(0) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_SMALL(1) else FFH_SMALL(2)
 #undef FFH_SMALL
 #undef FFH_SMALL_L
@@ -1911,7 +1933,11 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   if (!dbg_buf) hipMalloc(&dbg_buf, 8 * 8 * 65536);
   ra.dbg = dbg_buf;
 #endif
-  if (b16 && kind == FFH_SPARSE_OPT_SGD) { if (msd) FFH_RED(kOptSgdBf16, true) else FFH_RED(kOptSgdBf16, false) }
+  if (kind == FFH_SPARSE_OPT_ADAGRAD) {
+    if (b16) { if (msd) FFH_RED(kOptAdagradBf16, true) else FFH_RED(kOptAdagradBf16, false) }
+    else { if (msd) FFH_RED(kOptAdagrad, true) else FFH_RED(kOptAdagrad, false) }
+  }
+  else if (b16 && kind == FFH_SPARSE_OPT_SGD) { if (msd) FFH_RED(kOptSgdBf16, true) else FFH_RED(kOptSgdBf16, false) }
   else if (b16 && kind == FFH_SPARSE_OPT_SGD_MOMENTUM) { if (msd) FFH_RED(kOptMomentumBf16, true) else FFH_RED(kOptMomentumBf16, false) }
   else if (b16) { if (msd) FFH_RED(kOptAdamBf16, true) else FFH_RED(kOptAdamBf16, false) }
   else if (msd) { if (kind == FFH_SPARSE_OPT_SGD) FFH_RED(0, true) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_RED(1, true) else FFH_RED(2, true) }

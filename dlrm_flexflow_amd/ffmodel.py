@@ -111,6 +111,9 @@ def lib() -> C.CDLL:
         "flexflow_sgd_optimizer_create": (H, [H, D, D, B, D]), "flexflow_model_set_sgd_optimizer": (None, [H, H]),
         "flexflow_adam_optimizer_create": (H, [H, D, D, D, D, D]), "flexflow_model_set_adam_optimizer": (None, [H, H]),
         "flexflow_adam_optimizer_set_lr": (None, [H, D]),
+        "flexflow_config_set_adagrad": (None, [H, D, D]),
+        "flexflow_model_weight_mirror_stale_bytes": (C.c_int64, [H]),
+        "flexflow_adagrad_optimizer_create": (H, [H, D, D, D, D]), "flexflow_model_set_adagrad_optimizer": (None, [H, H]),
         "flexflow_model_compile": (None, [H, I, IP, I, I]),
         "flexflow_model_init_layers": (None, [H]), "flexflow_model_reset_metrics": (None, [H]),
         "flexflow_model_forward": (None, [H, I]), "flexflow_model_zero_gradients": (None, [H]),
@@ -312,6 +315,22 @@ def read_checkpoint(path: str) -> dict:
     return out
 
 
+def adagrad_reference(w, g, S, lr, eps, wd=0.0):
+    """One Adagrad step as include/ff_hip_adagrad.h states it (torch.optim.Adagrad's element-wise rule, no lr_decay), restated with one numpy operation
+    per rounded operation in the dtype of `w` (float32: the bits the kernels give; float64: the same statements for a comparison with torch).
+    Returns (w_new, S_new); the inputs are left alone."""
+    dt = np.asarray(w).dtype
+    w, g, S = np.asarray(w, dt), np.asarray(g, dt), np.asarray(S, dt)
+    lr, eps, wd = dt.type(lr), dt.type(eps), dt.type(wd)
+    with np.errstate(all="ignore"):
+        gt = g if wd == 0 else g + wd * w
+        S = S + gt * gt
+        d = np.sqrt(S) + eps
+        q = gt / d
+        w = w - lr * q
+    return w, S
+
+
 def cross_reference(x0, v, xl) -> np.ndarray:
     """The combine of a DCNv2 low-rank cross layer as include/ff_hip_cross.h states it, in float32 numpy: fadd_rn(fmul_rn(x0, v), xl) -- two
     separately rounded float32 operations per element (numpy never contracts them), which ffh_cross_fwd equals bit for bit."""
@@ -435,10 +454,16 @@ class FFConfig:
 
     def set(self, seed=None, device=None, enable_graph=None, overlap_embedding=None, dense_embedding_update=None,
             embedding_dtype=None, embedding_rounding=None, lr_warmup_steps=None, lr_decay_start_step=None, lr_num_decay_steps=None,
-            device_lr=None):
+            device_lr=None, adagrad_eps=None, adagrad_initial_accumulator=None):
         """embedding_dtype: "fp32" | "bf16"; embedding_rounding: "stochastic" | "nearest" (the --embedding-* flags).
         lr_*: the schedule of --lr-num-warmup-steps / --lr-decay-start-step / --lr-num-decay-steps; device_lr: True = --device-lr,
-        False = --host-lr-schedule, None = compile() chooses the route."""
+        False = --host-lr-schedule, None = compile() chooses the route.
+        adagrad_eps / adagrad_initial_accumulator: --adagrad-eps / --adagrad-initial-accumulator, what an AdagradOptimizer without its own takes.
+        FFModel(config) copies the config: call set() before the model is built (as for every other field)."""
+        if adagrad_eps is not None or adagrad_initial_accumulator is not None:
+            self._adagrad = tuple(old if new is None else float(new) for old, new in zip(getattr(self, "_adagrad", (1e-10, 0.0)),
+                                                                                       (adagrad_eps, adagrad_initial_accumulator)))
+            lib().flexflow_config_set_adagrad(self.h, *self._adagrad)
         if any(v is not None for v in (lr_warmup_steps, lr_decay_start_step, lr_num_decay_steps, device_lr)):
             self._lr = tuple(old if new is None else int(new) for old, new in zip(getattr(self, "_lr", (0, 0, 0)),
                                                                                (lr_warmup_steps, lr_decay_start_step, lr_num_decay_steps)))
@@ -562,6 +587,10 @@ class FFModel:
         self._opt = lib().flexflow_adam_optimizer_create(self.h, alpha, beta1, beta2, weight_decay, epsilon)
         lib().flexflow_model_set_adam_optimizer(self.h, self._opt)
 
+    def set_adagrad_optimizer(self, lr=0.01, weight_decay=0.0, epsilon=None, initial_accumulator=None):
+        """AdagradOptimizer(self, ...) as this model's optimizer."""
+        AdagradOptimizer(self, lr, weight_decay, epsilon, initial_accumulator)
+
     def compile(self, loss_type=LOSS_MSE_AVG, metrics=(METRICS_ACCURACY, METRICS_MSE), comp_mode=COMP_MODE_TRAINING):
         m = (C.c_int * len(metrics))(*metrics)
         lib().flexflow_model_compile(self.h, loss_type, m, len(metrics), comp_mode)
@@ -591,6 +620,11 @@ class FFModel:
     def layer_output(self, layer) -> Tensor: return Tensor(lib().flexflow_model_get_layer_output(self.h, layer), self)
     @property
     def stream(self) -> int: return lib().flexflow_model_get_stream(self.h) or 0
+    def weight_mirror_stale_bytes(self) -> int:
+        """Bytes of the weight slab's bf16 twin (tensor-op mode) / three-plane image (--fp32-split-bf16x3) that differ from a fresh conversion of
+        the fp32 weights: 0 where the optimizer kept it current; -1: the model keeps none; -2: a host write is pending.  Synchronises."""
+        return int(lib().flexflow_model_weight_mirror_stale_bytes(self.h))
+
     def current_lr(self) -> float:
         """The scheduled rate of the next optimizer step (base: the optimizer's lr / alpha), as the float the kernels receive."""
         return float(lib().flexflow_model_get_current_lr(self.h))
@@ -637,6 +671,20 @@ class FFModel:
         if self._owned and self.h is not None:
             lib().flexflow_model_destroy(self.h)
             self.h = None
+
+
+class AdagradOptimizer:
+    """Adagrad with torch.optim.Adagrad's element-wise rule (include/ff_hip_adagrad.h; adagrad_reference restates it) as the optimizer of `model`:
+    MLPs, cross layers and replicated tables in one dense launch, the other tables on the fused sorted-segments update (weight_decay == 0) or the dense
+    table path.  epsilon / initial_accumulator None: the config's (--adagrad-eps, default 1e-10; --adagrad-initial-accumulator, default 0).  Needs a
+    kernel library with the Adagrad extension: compile() refuses the model otherwise."""
+
+    def __init__(self, model: "FFModel", lr=0.01, weight_decay=0.0, epsilon=None, initial_accumulator=None):
+        nan = float("nan")
+        self.h = lib().flexflow_adagrad_optimizer_create(model.h, lr, weight_decay, nan if epsilon is None else float(epsilon),
+                                                         nan if initial_accumulator is None else float(initial_accumulator))
+        lib().flexflow_model_set_adagrad_optimizer(model.h, self.h)
+        model._opt = self
 
 
 class DLRM:

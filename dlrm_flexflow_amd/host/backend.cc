@@ -154,6 +154,23 @@ const KernelApi* load_kernel_api(const std::string& path_in) {
     }
     api->digest = b;
   }
+  // the Adagrad extension (include/ff_hip_adagrad.h): the same rule
+  if (dlsym(h, "ffh_adagrad_abi_version")) {
+    KernelApiAdagrad* b = new KernelApiAdagrad();
+#define FFH_LOAD(name)                                                        \
+  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
+  if (!b->name) {                                                             \
+    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_adagrad.h: %s is missing\n", path.c_str(), #name);   \
+    abort();                                                                  \
+  }
+    FFH_ADAGRAD_API_LIST(FFH_LOAD)
+#undef FFH_LOAD
+    if (b->ffh_adagrad_abi_version() != FFH_ADAGRAD_ABI_VERSION) {
+      fprintf(stderr, "FATAL: %s has Adagrad ABI version %d, expected %d\n", path.c_str(), b->ffh_adagrad_abi_version(), FFH_ADAGRAD_ABI_VERSION);
+      abort();
+    }
+    api->adagrad = b;
+  }
   if (path_in.empty() && g_env_override)
     fprintf(stderr, "[DLRM] FFH_BACKEND_LIB: kernel library %s (%s)\n", path.c_str(), api->ffh_backend_name());
   cache[path] = api;

@@ -10,6 +10,7 @@
 #include "../../include/ff_hip_data.h"
 #include "../../include/ff_hip_cross.h"
 #include "../../include/ff_hip_digest.h"
+#include "../../include/ff_hip_adagrad.h"
 
 // The optional bf16-table extension (include/ff_hip_bf16.h): all of its list or none of it.
 struct KernelApiBf16 {
@@ -53,6 +54,13 @@ struct KernelApiDigest {
 #undef FFH_DECL
 };
 
+// The optional Adagrad extension (include/ff_hip_adagrad.h: the dense launch; the library then also takes FFH_SPARSE_OPT_ADAGRAD in the table update).
+struct KernelApiAdagrad {
+#define FFH_DECL(name) decltype(&::name) name;
+  FFH_ADAGRAD_API_LIST(FFH_DECL)
+#undef FFH_DECL
+};
+
 struct KernelApi {
 #define FFH_DECL(name) decltype(&::name) name;
   FFH_API_LIST(FFH_DECL)
@@ -63,6 +71,7 @@ struct KernelApi {
   const KernelApiData* data = nullptr;   // likewise for include/ff_hip_data.h
   const KernelApiCross* cross = nullptr; // likewise for include/ff_hip_cross.h
   const KernelApiDigest* digest = nullptr;   // likewise for include/ff_hip_digest.h (absent: the host layer computes the same digest from the bytes it copies)
+  const KernelApiAdagrad* adagrad = nullptr; // likewise for include/ff_hip_adagrad.h
   void* handle;
   std::string path;
   bool overridden = false;      // chosen by --backend or $FFH_BACKEND_LIB rather than the product default: the driver says so on its THROUGHPUT line

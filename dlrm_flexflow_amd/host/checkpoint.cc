@@ -50,6 +50,7 @@ struct CkRecord {
 const char* optimizer_kind(const FFModel* ff) {
   if (const SGDOptimizer* s = dynamic_cast<const SGDOptimizer*>(ff->optimizer)) return s->momentum > 0.0 ? "sgd-momentum" : "sgd";
   if (dynamic_cast<const AdamOptimizer*>(ff->optimizer)) return "adam";
+  if (dynamic_cast<const AdagradOptimizer*>(ff->optimizer)) return "adagrad";
   return "none";
 }
 // how the tables are updated: what --sparse-embedding-optimizer / --dense-embedding-update select for this optimizer
@@ -86,6 +87,7 @@ std::vector<CkRecord> collect_records(FFModel* ff) {
   std::vector<CkRecord> out;
   SGDOptimizer* sgd = dynamic_cast<SGDOptimizer*>(ff->optimizer);
   AdamOptimizer* adam = dynamic_cast<AdamOptimizer*>(ff->optimizer);
+  AdagradOptimizer* adagrad = dynamic_cast<AdagradOptimizer*>(ff->optimizer);
   for (Op* op : ff->layers) {
     for (int i = 0; i < op->numWeights; i++) {
       const Parameter& p = op->weights[i];
@@ -118,7 +120,17 @@ std::vector<CkRecord> collect_records(FFModel* ff) {
           out.push_back(device_record("adam_v/" + id, "f32", 4, v, rows, cols, im->ld));
         }
       }
-      // per-row state of --sparse-embedding-optimizer: fp32 whatever the table's storage, contiguous
+      if (adagrad && im->grad && !bf16) {
+        float* S = nullptr;
+        if (in_dense_slab(p)) {
+          if (adagrad->mlp_s) S = adagrad->mlp_s + (size_t)((float*)im->ptr - ff->mlp_weights);
+        } else {
+          auto it = adagrad->s_values.find(im->ptr);
+          if (it != adagrad->s_values.end()) S = it->second;
+        }
+        if (S) out.push_back(device_record("adagrad_s/" + id, "f32", 4, S, rows, cols, im->ld));
+      }
+      // per-row state of --sparse-embedding-optimizer (Adagrad without weight decay: of its default table route): fp32 whatever the table's storage, contiguous
       if (e && i == 0)
         for (int k = 0; k < 2; k++)
           if (e->opt_state[k]) {

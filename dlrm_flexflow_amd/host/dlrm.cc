@@ -56,6 +56,7 @@ void parse_input_args(char** argv, int argc, DLRMConfig& config) {
         return argv[++i];
       };
       if (eq && is("--arch-interaction-op")) { config.arch_interaction_op = std::string(next()); continue; }
+      if (eq && is("--optimizer")) { config.optimizer = std::string(next()); continue; }
       if (is("--dcn-num-layers")) { config.dcn_num_layers = atoi(next()); continue; }
       if (is("--dcn-low-rank-dim")) { config.dcn_low_rank_dim = atoi(next()); continue; }
     }
@@ -441,7 +442,9 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
   if (dlrm.optimizer == "sgd") optimizer = new SGDOptimizer(ff, ffconfig.learningRate);
   else if (dlrm.optimizer == "sgd-momentum") optimizer = new SGDOptimizer(ff, ffconfig.learningRate, 0.9f);
   else if (dlrm.optimizer == "adam") optimizer = new AdamOptimizer(ff);
-  else { fprintf(stderr, "FATAL: --optimizer %s: 'sgd', 'sgd-momentum' or 'adam'\n", dlrm.optimizer.c_str()); abort(); }
+  // "adagrad" (DESIGN section 16): torch.optim.Adagrad's element-wise rule at rate --lr, no weight decay -- the MLPerf DLRM-DCNv2 recipe's
+  else if (dlrm.optimizer == "adagrad") optimizer = new AdagradOptimizer(ff, ffconfig.learningRate, 0.0, ffconfig.adagrad_eps, ffconfig.adagrad_initial_accumulator);
+  else { fprintf(stderr, "FATAL: --optimizer %s: 'sgd', 'sgd-momentum', 'adam' or 'adagrad'\n", dlrm.optimizer.c_str()); abort(); }
   std::vector<MetricsType> metrics;
   metrics.push_back(METRICS_ACCURACY);
   metrics.push_back(METRICS_MEAN_SQUARED_ERROR);
@@ -465,6 +468,15 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
                 ffconfig.comm.world_size > 1 ? ", per-rank stripes" : "");
   }
   ff->compile(optimizer, (LossType)ffconfig.driver_loss, metrics);
+  if (const AdagradOptimizer* ag = dynamic_cast<const AdagradOptimizer*>(optimizer)) {
+    // what --optimizer adagrad allocated on this rank: S beside every fp32 weight it updates, fp32 beside bf16 tables too (on fp32 tables it doubles their HBM)
+    size_t bytes = ag->state_bytes;
+    for (const Embedding* e : ff->embeddings)
+      if (e->opt_state[0]) bytes += e->weights[0].get_volume() * 4 + (e->row_sharded ? (size_t)e->out_channels * 4 : 0);
+    if (chatty)
+      printf("[DLRM] optimizer: adagrad eps=%g A=%g lr=%g, tables: %s, accumulator %zu bytes (%.3f GB) on rank %d\n", ag->epsilon, ag->initial_accumulator, ag->lr,
+             ff->embeddings.empty() ? "none" : (ff->fused_embedding_update() ? "fused" : "dense"), bytes, bytes / 1e9, ff->rank);
+  }
   // which learning-rate route runs, and why; silent without the flags
   if (chatty && (ffconfig.lr_warmup_steps || ffconfig.lr_num_decay_steps || ffconfig.lr_decay_start_step || ffconfig.device_lr || ffconfig.host_lr_schedule))
     printf("[DLRM] lr schedule: %s\n", ff->lr_schedule_line().c_str());

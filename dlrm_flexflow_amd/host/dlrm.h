@@ -18,7 +18,7 @@ struct DLRMConfig {
   std::vector<int> embedding_size, mlp_bot, mlp_top;
   std::string arch_interaction_op, dataset_path;
   int data_size;
-  std::string optimizer;   // --optimizer sgd (default, the reference driver's) | sgd-momentum | adam (not a reference flag)
+  std::string optimizer;   // --optimizer sgd (default, the reference driver's) | sgd-momentum | adam | adagrad (not a reference flag)
   double zipf_alpha;   // > 0: synthetic ids follow a power law instead of the reference's uniform draw (not a reference flag)
   int dcn_num_layers, dcn_low_rank_dim;   // --arch-interaction-op dcn: --dcn-num-layers L (3), --dcn-low-rank-dim R (512) (not reference flags)
 };

@@ -29,6 +29,7 @@
 #include "../../include/ff_hip_ctr.h"
 #include "../../include/ff_hip_lr.h"
 #include "../../include/ff_hip_cross.h"
+#include "../../include/ff_hip_adagrad.h"
 #include "ffcomm.h"
 
 // ---- enums: identical values to [ref: include/ffconst.h:4-57] -------------------------------
@@ -169,6 +170,8 @@ class FFConfig {
   int64_t lr_warmup_steps, lr_decay_start_step, lr_num_decay_steps;   // --lr-num-warmup-steps / --lr-decay-start-step / --lr-num-decay-steps
   bool device_lr;              // --device-lr: the rate lives in device memory even when it is constant (a captured step can then replay Adam)
   bool host_lr_schedule;       // --host-lr-schedule: the scheduled value is a launch argument computed on the host each step (A/B; never captured)
+  double adagrad_eps;                  // --adagrad-eps E: the eps of --optimizer adagrad (default 1e-10, torch.optim.Adagrad's)
+  double adagrad_initial_accumulator;  // --adagrad-initial-accumulator A: what its accumulator S starts at (default 0)
   ffcomm comm;                 // rank / world_size / collectives supplied by the launcher (ffcomm.h)
 };
 
@@ -294,6 +297,22 @@ class AdamOptimizer : public Optimizer {
   double alpha_t, beta1_t, beta2_t;
   float *mlp_m, *mlp_v;                                        // moments of the MLP slab
   std::map<const void*, std::pair<float*, float*>> mv_values;  // (m, v) of every other parameter, keyed by weight pointer
+};
+
+// AdagradOptimizer: torch.optim.Adagrad's element-wise rule (include/ff_hip_adagrad.h; no reference class).  S lives in one slab laid
+// out like the MLP parameter slab (one launch for every Linear / cross parameter and replicated table) plus one buffer per table on the dense
+// table path; tables on the fused path keep S in Embedding::opt_state[0].  Every S starts at initial_accumulator.
+class AdagradOptimizer : public Optimizer {
+ public:
+  AdagradOptimizer(const FFModel* _model, double _lr = 0.01f, double _weight_decay = 0.0f, double _epsilon = 1e-10, double _initial_accumulator = 0.0);
+  void init(void) override;
+  void next(void) override;
+  void update(const Parameter* p) override;
+  void set_weight_decay(double wd) { weight_decay = wd; }
+  double lr, weight_decay, epsilon, initial_accumulator;
+  float* mlp_s;                                // S of the MLP slab
+  std::map<const void*, float*> s_values;      // S of every other parameter, keyed by weight pointer
+  size_t state_bytes = 0;                      // what init() allocated
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -707,6 +726,9 @@ class FFModel {
   void* w_twin = nullptr; void* act_twin = nullptr; void* grad_twin = nullptr;
   mutable bool w_twin_dirty = false;      // a host write / initializer touched the weights: reconvert before the next step
   void refresh_weight_twin() const;
+  // how many bytes of the weight slab's bf16 twin / three-plane image differ from a fresh conversion of the fp32 weights (which it then holds):
+  // 0 where every writer kept it current.  -1: this model keeps none; -2: a host write is pending (the next step reconverts).  Synchronises.
+  int64_t weight_mirror_stale_bytes();
   void note_weight_write(const void* p) const;
   mutable bool bwd_alltoall_issued = false;   // this step's backward all-to-all has been enqueued (FFModel::issue_grad_buckets: a shared channel holds the buckets until then)
   int n_twin_regions = 0;

@@ -112,6 +112,14 @@ flexflow_adam_optimizer_t flexflow_adam_optimizer_create(flexflow_model_t m, dou
 }
 void flexflow_adam_optimizer_set_lr(flexflow_adam_optimizer_t o, double lr) { ((AdamOptimizer*)o.impl)->alpha = lr; }
 void flexflow_model_set_adam_optimizer(flexflow_model_t m, flexflow_adam_optimizer_t o) { M(m)->optimizer = (AdamOptimizer*)o.impl; }
+int64_t flexflow_model_weight_mirror_stale_bytes(flexflow_model_t m) { return M(m)->weight_mirror_stale_bytes(); }
+void flexflow_config_set_adagrad(flexflow_config_t h, double eps, double acc) { C(h)->adagrad_eps = eps; C(h)->adagrad_initial_accumulator = acc; }
+flexflow_adagrad_optimizer_t flexflow_adagrad_optimizer_create(flexflow_model_t m, double lr, double wd, double eps, double acc) {
+  flexflow_adagrad_optimizer_t h;
+  h.impl = new AdagradOptimizer(M(m), lr, wd, eps != eps ? M(m)->config.adagrad_eps : eps, acc != acc ? M(m)->config.adagrad_initial_accumulator : acc);
+  return h;
+}
+void flexflow_model_set_adagrad_optimizer(flexflow_model_t m, flexflow_adagrad_optimizer_t o) { M(m)->optimizer = (AdagradOptimizer*)o.impl; }
 void flexflow_model_compile(flexflow_model_t m, int loss, const int* metrics, int nb, int comp_mode) {
   std::vector<MetricsType> v;
   for (int i = 0; i < nb; i++) v.push_back((MetricsType)metrics[i]);

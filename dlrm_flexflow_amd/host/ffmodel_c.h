@@ -18,6 +18,7 @@ FF_NEW_OPAQUE_TYPE(flexflow_tensor_t);
 FF_NEW_OPAQUE_TYPE(flexflow_initializer_t);
 FF_NEW_OPAQUE_TYPE(flexflow_sgd_optimizer_t);
 FF_NEW_OPAQUE_TYPE(flexflow_adam_optimizer_t);
+FF_NEW_OPAQUE_TYPE(flexflow_adagrad_optimizer_t);
 FF_NEW_OPAQUE_TYPE(flexflow_dlrm_t);
 #undef FF_NEW_OPAQUE_TYPE
 
@@ -91,6 +92,13 @@ void flexflow_model_set_sgd_optimizer(flexflow_model_t, flexflow_sgd_optimizer_t
 flexflow_adam_optimizer_t flexflow_adam_optimizer_create(flexflow_model_t, double alpha, double beta1, double beta2, double weight_decay, double epsilon);
 void flexflow_adam_optimizer_set_lr(flexflow_adam_optimizer_t, double lr);
 void flexflow_model_set_adam_optimizer(flexflow_model_t, flexflow_adam_optimizer_t);
+/* Adagrad, torch.optim.Adagrad's element-wise rule (include/ff_hip_adagrad.h; no reference class).  epsilon / initial_accumulator given as NaN: the
+   config's --adagrad-eps / --adagrad-initial-accumulator */
+/* FFModel::weight_mirror_stale_bytes: bytes of the weight slab's bf16 twin / three-plane image that a fresh conversion changes (0: current; -1: none kept) */
+int64_t flexflow_model_weight_mirror_stale_bytes(flexflow_model_t);
+void flexflow_config_set_adagrad(flexflow_config_t, double epsilon, double initial_accumulator);
+flexflow_adagrad_optimizer_t flexflow_adagrad_optimizer_create(flexflow_model_t, double lr, double weight_decay, double epsilon, double initial_accumulator);
+void flexflow_model_set_adagrad_optimizer(flexflow_model_t, flexflow_adagrad_optimizer_t);
 void flexflow_model_compile(flexflow_model_t, int loss_type, const int* metrics, int nb_metrics, int comp_mode);
 void flexflow_model_init_layers(flexflow_model_t);
 void flexflow_model_reset_metrics(flexflow_model_t);

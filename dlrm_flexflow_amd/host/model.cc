@@ -1232,3 +1232,42 @@ void AdamOptimizer::update(const Parameter* p) {
   model->check(model->api->ffh_adam_update(model->ctx, (float*)p->impl->ptr, p->impl->grad, m, v, (int64_t)(p->impl->bytes / sizeof(float)), (float)alpha_t,
                                            (float)beta1, (float)beta2, (float)weight_decay, (float)epsilon, 0, model->stream), "adam_update");
 }
+
+// =============================================================================================
+// AdagradOptimizer (include/ff_hip_adagrad.h; compile() has checked that the library has the extension)
+// =============================================================================================
+AdagradOptimizer::AdagradOptimizer(const FFModel* _model, double _lr, double _wd, double _eps, double _acc)
+    : Optimizer(_model), lr(_lr), weight_decay(_wd), epsilon(_eps), initial_accumulator(_acc), mlp_s(nullptr) {}
+void AdagradOptimizer::init(void) {
+  auto filled = [&](size_t count) {
+    float* p = (float*)model->dmalloc(count * sizeof(float));
+    model->check(model->api->ffh_fill_f32(model->ctx, p, (int64_t)count, (float)initial_accumulator, model->stream), "adagrad accumulator");
+    state_bytes += count * sizeof(float);
+    return p;
+  };
+  if (model->mlp_count) mlp_s = filled(model->mlp_count);
+  for (const Parameter& p : model->parameters) {
+    if (in_dense_slab(p) || !p.impl->grad) continue;
+    s_values[p.impl->ptr] = filled(p.impl->bytes / sizeof(float));
+  }
+}
+void AdagradOptimizer::next(void) {}
+void AdagradOptimizer::update(const Parameter* p) {
+  if (!p->impl->grad) return;   // embedding tables on the fused path have no dense gradient
+  float* S;
+  if (in_dense_slab(*p)) {
+    S = mlp_s + (size_t)((float*)p->impl->ptr - model->mlp_weights);
+  } else {
+    auto it = s_values.find(p->impl->ptr);
+    if (it == s_values.end()) die("AdagradOptimizer::update: parameter without accumulator");
+    S = it->second;
+  }
+  const int64_t n = (int64_t)(p->impl->bytes / sizeof(float));
+  if (model->lr_route == FFModel::kLrDevice) {      // (as SGDOptimizer::update)
+    model->check(model->api->adagrad->ffh_adagrad_update_lr(model->ctx, (float*)p->impl->ptr, p->impl->grad, S, n, model->lr_block[0], (float)epsilon,
+                                                            (float)weight_decay, 0, model->stream), "adagrad_update_lr");
+    return;
+  }
+  model->check(model->api->adagrad->ffh_adagrad_update(model->ctx, (float*)p->impl->ptr, p->impl->grad, S, n, (float)lr, (float)epsilon, (float)weight_decay, 0,
+                                                       model->stream), "adagrad_update");
+}

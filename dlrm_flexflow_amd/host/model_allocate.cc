@@ -20,9 +20,13 @@ bool FFModel::fused_embedding_update() const {
   const SGDOptimizer* sgd = dynamic_cast<const SGDOptimizer*>(optimizer);
   // the fused sparse update equals the reference's dense sweep only for plain SGD ...
   if (sgd && sgd->momentum == 0.0 && sgd->weight_decay == 0.0) return true;
+  // ... and for Adagrad without weight decay: an element whose gradient is zero keeps w and S bit for bit, so the touched-rows rule IS the dense
+  // sweep, not a divergence to opt into
+  const AdagradOptimizer* adagrad = dynamic_cast<const AdagradOptimizer*>(optimizer);
+  if (adagrad && adagrad->weight_decay == 0.0) return true;
   // ... every other optimizer takes the reference's dense path (zero + scatter-add + whole-table sweep: reference semantics on
   // every row) unless the user opts into the touched-rows rule (--sparse-embedding-optimizer; stated divergence: ffh_sparse_opt)
-  return config.sparse_embedding_optimizer && (sgd || dynamic_cast<const AdamOptimizer*>(optimizer));
+  return config.sparse_embedding_optimizer && (sgd || adagrad || dynamic_cast<const AdamOptimizer*>(optimizer));
 }
 
 // the row rule of the sorted-segments update for the optimizer in force; false: plain SGD (the lr-only entry points)
@@ -32,6 +36,10 @@ bool FFModel::sparse_rule(ffh_sparse_opt& o) const {
     o.lr = (float)sgd->lr;
     if (sgd->momentum == 0.0 && sgd->weight_decay == 0.0) { o.kind = FFH_SPARSE_OPT_SGD; return false; }
     o.kind = FFH_SPARSE_OPT_SGD_MOMENTUM; o.weight_decay = (float)sgd->weight_decay; o.momentum = (float)sgd->momentum; o.nesterov = sgd->nesterov ? 1 : 0;
+    return true;
+  }
+  if (const AdagradOptimizer* ag = dynamic_cast<const AdagradOptimizer*>(optimizer)) {
+    o.kind = FFH_SPARSE_OPT_ADAGRAD; o.lr = (float)ag->lr; o.weight_decay = (float)ag->weight_decay; o.epsilon = (float)ag->epsilon;
     return true;
   }
   const AdamOptimizer* adam = dynamic_cast<const AdamOptimizer*>(optimizer);
@@ -162,6 +170,16 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
     if (bce) last->dy_premasked = true;
   }
   want_eval = want_auc;
+  // Adagrad (include/ff_hip_adagrad.h): its parameters, then the library -- the dense launch and the row rule exist only in one with the extension
+  if (const AdagradOptimizer* ag = dynamic_cast<const AdagradOptimizer*>(optimizer)) {
+    if (!(ag->epsilon > 0.0) && ag->initial_accumulator == 0.0)
+      die("--adagrad-eps %g with --adagrad-initial-accumulator 0: an element that has seen no gradient would be updated by 0 / (sqrt(0) + eps) = 0 / 0; "
+          "give --adagrad-eps a positive value or --adagrad-initial-accumulator one", ag->epsilon);
+    if (ag->initial_accumulator < 0.0) die("--adagrad-initial-accumulator %g: must be >= 0 (its square root is taken)", ag->initial_accumulator);
+    if (!api->adagrad)
+      die("--optimizer adagrad: %s (%s) is a kernel library without the Adagrad extension (include/ff_hip_adagrad.h); use --optimizer sgd, sgd-momentum "
+          "or adam, or another --backend", api->path.c_str(), api->ffh_backend_name());
+  }
   // a shuffled data order (include/ff_hip_data.h): its batches are one gather launch that only a library with the extension has
   if (config.data_randomize && !api->data)
     die("--data-randomize total: %s (%s) is a kernel library without the data extension (include/ff_hip_data.h); use --data-randomize none",
@@ -259,13 +277,15 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
   {   // per-row optimizer state of the touched-rows rule: the shape of the local table (+ the zero row of a row block)
     ffh_sparse_opt rule;
     if (fused_embedding_update() && sparse_rule(rule)) {
-      const int nstate = rule.kind == FFH_SPARSE_OPT_ADAM ? 2 : (rule.momentum > 0.0f ? 1 : 0);
+      const AdagradOptimizer* ag = dynamic_cast<const AdagradOptimizer*>(optimizer);      // S starts at the initial accumulator, every other state at zero
+      const int nstate = rule.kind == FFH_SPARSE_OPT_ADAM ? 2 : ((ag || rule.momentum > 0.0f) ? 1 : 0);
       for (Embedding* e : embeddings) {
         if (!e->held_here(rank) || e->replicated) continue;
         const size_t bytes = e->weights[0].get_volume() * 4 + (e->row_sharded ? (size_t)e->out_channels * 4 : 0);   // fp32 state, whatever the table's storage
         for (int k = 0; k < nstate; k++) {
           e->opt_state[k] = (float*)dmalloc(bytes);
-          check(api->ffh_zero(ctx, e->opt_state[k], bytes, stream), "sparse optimizer state");
+          if (ag) check(api->ffh_fill_f32(ctx, e->opt_state[k], (int64_t)(bytes / 4), (float)ag->initial_accumulator, stream), "sparse optimizer state");
+          else check(api->ffh_zero(ctx, e->opt_state[k], bytes, stream), "sparse optimizer state");
         }
       }
     }

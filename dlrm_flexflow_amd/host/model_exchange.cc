@@ -112,7 +112,8 @@ size_t FFModel::bf16_tables_per_launch() const {
   ffh_sparse_opt rule;
   bool any16 = false;
   for (const Embedding* e : embeddings) any16 = any16 || e->bf16_weights();
-  return any16 && fused_embedding_update() && sparse_rule(rule) ? FFH_BF16_MAX_STATEFUL_TABLES : FFH_MAX_TABLES;
+  // (Adagrad has one state pointer per table and rides the plain update's layout: include/ff_hip_adagrad.h)
+  return any16 && fused_embedding_update() && sparse_rule(rule) && rule.kind != FFH_SPARSE_OPT_ADAGRAD ? FFH_BF16_MAX_STATEFUL_TABLES : FFH_MAX_TABLES;
 }
 uint64_t FFModel::read_bf16_counter() const {
   if (!bf16_counter) return 0;

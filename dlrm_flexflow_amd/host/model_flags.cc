@@ -77,6 +77,8 @@ FFConfig::FFConfig() {
   device_lr = false;
   host_lr_schedule = false;
   checkpoint_every_epochs = 0;
+  adagrad_eps = 1e-10;
+  adagrad_initial_accumulator = 0.0;
   memset(&comm, 0, sizeof comm);
   comm.rank = 0;
   comm.world_size = 1;
@@ -198,6 +200,8 @@ void FFConfig::parse_args(char** argv, int argc) {
       if (checkpoint_every_epochs < 1) die("--checkpoint-every-epochs %d: must be >= 1", checkpoint_every_epochs);
       continue;
     }
+    if (is("--adagrad-eps")) { adagrad_eps = atof(next()); continue; }
+    if (is("--adagrad-initial-accumulator")) { adagrad_initial_accumulator = atof(next()); continue; }
     if (is("--device-lr")) { device_lr = true; continue; }
     if (is("--host-lr-schedule")) { host_lr_schedule = true; continue; }
     if (is("--embedding-rounding")) {

@@ -20,6 +20,22 @@ void FFModel::refresh_weight_twin() const {
   else check(api->ffh_convert_f32_to_bf16(ctx, w_twin, mlp_weights, (int64_t)mlp_count, stream), "weight twin");
   w_twin_dirty = false;
 }
+int64_t FFModel::weight_mirror_stale_bytes() {
+  if (!w_twin) return -1;
+  if (w_twin_dirty) return -2;
+  sync();
+  const bool x3 = config.fp32_split_bf16x3 && !config.allow_tensor_op_math_conversion;
+  const size_t bytes = x3 ? FFH_BF16X3_IMAGE_BYTES((size_t)mlp_count * 4) : (size_t)mlp_count * 2;
+  std::vector<char> kept(bytes), fresh(bytes);
+  check(api->ffh_memcpy_d2h(ctx, kept.data(), w_twin, bytes, stream), "weight mirror d2h");
+  w_twin_dirty = true;
+  refresh_weight_twin();
+  check(api->ffh_memcpy_d2h(ctx, fresh.data(), w_twin, bytes, stream), "weight mirror d2h");
+  check(api->ffh_stream_sync(ctx, stream), "weight mirror sync");
+  int64_t n = 0;
+  for (size_t i = 0; i < bytes; i++) n += kept[i] != fresh[i];
+  return n;
+}
 void FFModel::note_weight_write(const void* p) const {
   if (w_twin && (const char*)p >= (const char*)mlp_weights && (const char*)p < (const char*)(mlp_weights + mlp_count)) w_twin_dirty = true;
 }
@@ -306,7 +322,8 @@ void FFModel::update() {
   opt_next_done = true;
   SGDOptimizer* sgd = dynamic_cast<SGDOptimizer*>(optimizer);
   AdamOptimizer* adam = dynamic_cast<AdamOptimizer*>(optimizer);
-  if (!sgd && !adam) die("update(): unknown optimizer");
+  AdagradOptimizer* adagrad = dynamic_cast<AdagradOptimizer*>(optimizer);
+  if (!sgd && !adam && !adagrad) die("update(): unknown optimizer");
   // every rank must issue its collectives in the same order: the side thread's all-to-all (backward) first
   if (side_worker) side_worker->drain();
   if (dw_forked && !dw_worker && !api->ffh_second_stream_used(ctx, 1) && !dw_stream_used_directly) { dw_forked = false; dw1_used = false; }   // the library kept everything on `stream`
@@ -364,6 +381,16 @@ void FFModel::update() {
       check(api->ffh_adam_update(ctx, mlp_weights, mlp_grads, adam->mlp_m, adam->mlp_v, (int64_t)opt_count, (float)adam->alpha_t,
                                  (float)adam->beta1, (float)adam->beta2, (float)adam->weight_decay, (float)adam->epsilon,
                                  FFH_OPT_ZERO_GRAD, stream), "adam_update (MLP slab)");
+      mlp_grads_clean = true;
+    }
+  } else if (adagrad) {
+    if (mlp_count && lrb) {
+      check(api->adagrad->ffh_adagrad_update_lr(ctx, mlp_weights, mlp_grads, adagrad->mlp_s, (int64_t)opt_count, lrb, (float)adagrad->epsilon,
+                                                (float)adagrad->weight_decay, FFH_OPT_ZERO_GRAD, stream), "adagrad_update_lr (MLP slab)");
+      mlp_grads_clean = true;
+    } else if (mlp_count) {
+      check(api->adagrad->ffh_adagrad_update(ctx, mlp_weights, mlp_grads, adagrad->mlp_s, (int64_t)opt_count, (float)adagrad->lr, (float)adagrad->epsilon,
+                                             (float)adagrad->weight_decay, FFH_OPT_ZERO_GRAD, stream), "adagrad_update (MLP slab)");
       mlp_grads_clean = true;
     }
   } else if (sgd->momentum > 0.0) {
@@ -594,7 +621,8 @@ void FFModel::lr_choose_route() {
   const bool scheduled = W > 0 || N > 0;
   SGDOptimizer* sgd = dynamic_cast<SGDOptimizer*>(optimizer);
   AdamOptimizer* adam = dynamic_cast<AdamOptimizer*>(optimizer);
-  lr_base = sgd ? sgd->lr : (adam ? adam->alpha : 0.0);
+  AdagradOptimizer* adagrad = dynamic_cast<AdagradOptimizer*>(optimizer);
+  lr_base = sgd ? sgd->lr : (adam ? adam->alpha : (adagrad ? adagrad->lr : 0.0));
   lr_route = kLrOff;
   lr_route_why = "constant rate";
   if (config.device_lr && !api->lr)
@@ -606,7 +634,7 @@ void FFModel::lr_choose_route() {
   const char* no = nullptr;
   if (config.host_lr_schedule) no = "--host-lr-schedule";
   else if (!api->lr) no = "the kernel library has no learning-rate extension";
-  else if (!sgd && !adam) no = "unknown optimizer";
+  else if (!sgd && !adam && !adagrad) no = "unknown optimizer";
   else if (!embeddings.empty() && !fused_embedding_update()) no = "the tables take the owner-local dense update";
   else if (config.profiling) no = "--profiling times the table update as the embedding group's backward";
   else {
@@ -640,6 +668,7 @@ void FFModel::lr_host_set(int64_t k) {
   const double v = ffh_lr_schedule_value(k, lr_base, config.lr_warmup_steps, config.lr_decay_start_step, config.lr_num_decay_steps);
   if (SGDOptimizer* sgd = dynamic_cast<SGDOptimizer*>(optimizer)) sgd->lr = v;
   else if (AdamOptimizer* adam = dynamic_cast<AdamOptimizer*>(optimizer)) adam->alpha = v;
+  else if (AdagradOptimizer* adagrad = dynamic_cast<AdagradOptimizer*>(optimizer)) adagrad->lr = v;
 }
 
 void FFModel::advance_lr(int which, ffh_stream s, ffh_ctx* cx) const {
@@ -666,6 +695,7 @@ double FFModel::current_lr() {
   if (lr_route == kLrOff) {
     if (SGDOptimizer* sgd = dynamic_cast<SGDOptimizer*>(optimizer)) return (double)(float)sgd->lr;
     if (AdamOptimizer* adam = dynamic_cast<AdamOptimizer*>(optimizer)) return (double)(float)adam->alpha;
+    if (AdagradOptimizer* adagrad = dynamic_cast<AdagradOptimizer*>(optimizer)) return (double)(float)adagrad->lr;
     return 0.0;
   }
   return (double)(float)ffh_lr_schedule_value(k, lr_base, config.lr_warmup_steps, config.lr_decay_start_step, config.lr_num_decay_steps);

@@ -6,7 +6,8 @@
   python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 dlrm_flexflow_amd/run_dlrm.py <flags>
 
 Every flag goes to the C++ driver as it is, this build's own included (--loss mse|bce, --eval-batches N, --eval-only,
---data-randomize none|total, --arch-interaction-op dcn with --dcn-num-layers L and --dcn-low-rank-dim R: README.md).
+--data-randomize none|total, --arch-interaction-op dcn with --dcn-num-layers L and --dcn-low-rank-dim R,
+--optimizer adagrad with --adagrad-eps E and --adagrad-initial-accumulator A: README.md).
 
 [ref: examples/cpp/DLRM/run_random.sh:3 -- one command, `-ll:gpu N`; src/runtime/cpp_driver.cc:22-44]
 
