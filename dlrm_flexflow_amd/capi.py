@@ -58,6 +58,7 @@ class SparseOpt(C.Structure):
 
 SPARSE_OPT_SGD, SPARSE_OPT_SGD_MOMENTUM, SPARSE_OPT_ADAM = 0, 1, 2
 SPARSE_OPT_ADAGRAD = 3      # include/ff_hip_adagrad.h: accepted by a library with the Adagrad extension
+SPARSE_OPT_ROWWISE_ADAGRAD = 8      # include/ff_hip_rowwise.h: accepted by a library with the row-wise Adagrad extension (s0 = one float per row)
 
 
 class PerfMetrics(C.Structure):
@@ -326,6 +327,31 @@ def adagrad_header_abi_version(header_path: str = ADAGRAD_HEADER_PATH) -> int:
     m = re.search(r"#define\s+FFH_ADAGRAD_ABI_VERSION\s+(\d+)", open(header_path).read())
     if not m:
         raise RuntimeError("FFH_ADAGRAD_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
+# include/ff_hip_rowwise.h: the optional row-wise Adagrad extension (FFH_SPARSE_OPT_ROWWISE_ADAGRAD in the table update; no launch of its own)
+ROWWISE_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_rowwise.h")
+
+_SIGS_ROWWISE = {
+    "ffh_rowwise_abi_version": (I, []),
+}
+
+
+def rowwise_header_symbols(header_path: str = ROWWISE_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_ROWWISE_API_LIST X-macro in include/ff_hip_rowwise.h."""
+    text = open(header_path).read()
+    m = re.search(r"#define FFH_ROWWISE_API_LIST\(X\)(.*?)\n\n", text, re.S)
+    if not m:
+        raise RuntimeError("FFH_ROWWISE_API_LIST not found in " + header_path)
+    return re.findall(r"X\((\w+)\)", m.group(1))
+
+
+def rowwise_header_abi_version(header_path: str = ROWWISE_HEADER_PATH) -> int:
+    """FFH_ROWWISE_ABI_VERSION of include/ff_hip_rowwise.h."""
+    m = re.search(r"#define\s+FFH_ROWWISE_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_ROWWISE_ABI_VERSION not found in " + header_path)
     return int(m.group(1))
 
 
@@ -815,6 +841,30 @@ class AdagradApi:
 def adagrad_api(lib: FFHLib) -> AdagradApi:
     """The Adagrad entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
     return AdagradApi(lib)
+
+
+class RowwiseApi:
+    """The row-wise Adagrad extension (include/ff_hip_rowwise.h) of a loaded FFHLib; `rowwise_api(lib)` builds it or raises.  The rule itself is
+    reached through the table update's entry points of `lib` with SparseOpt.kind = SPARSE_OPT_ROWWISE_ADAGRAD."""
+
+    def __init__(self, lib: FFHLib):
+        self.base = lib
+        for name, (res, args) in _SIGS_ROWWISE.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no row-wise Adagrad extension ({name} missing; include/ff_hip_rowwise.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_rowwise_abi_version()
+        if got != rowwise_header_abi_version():
+            raise FFHError(f"{lib.path}: row-wise Adagrad ABI version {got}, include/ff_hip_rowwise.h says {rowwise_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+
+def rowwise_api(lib: FFHLib) -> RowwiseApi:
+    """The row-wise Adagrad extension of `lib`; FFHError when the library does not export it (e.g. the CPU oracle)."""
+    return RowwiseApi(lib)
 
 
 _hip_singleton: FFHLib | None = None

@@ -19,6 +19,7 @@
 #include "../../include/ffh_bf16.h"
 #include "lr_state.h"
 #include "../../include/ff_hip_adagrad.h"
+#include "../../include/ff_hip_rowwise.h"
 #ifdef FFH_MSD_TIMING
 #include <vector>
 #endif
@@ -443,11 +444,21 @@ constexpr int kOptAdagrad = 6;
 constexpr int kOptAdagradBf16 = 7;
 constexpr int kBaseAdagrad = 3;
 
-constexpr bool opt_bf16(int OPT) { return (OPT >= kOptSgdBf16 && OPT <= kOptAdamBf16) || OPT == kOptAdagradBf16; }                // 16-bit weight rows
-constexpr int opt_base(int OPT) {      // the fp32 row rule: 0 plain SGD, 1 momentum / wd SGD, 2 Adam, 3 Adagrad
-  return (OPT == kOptAdagrad || OPT == kOptAdagradBf16) ? kBaseAdagrad : (opt_bf16(OPT) ? OPT - kOptSgdBf16 : OPT);
+// OPT 8 / 9 (kOptRowwise, kOptRowwiseBf16): row-wise Adagrad (include/ff_hip_rowwise.h): s0 = S, ONE float per row, no s1 (the bf16 form rides the Bf16Keys
+// layout like kOptAdagradBf16).  The rule needs the whole row before it can update any of it, so it is not a case of apply_row (one vector at a time) but
+// apply_row_rowwise below; row rule 4
+constexpr int kOptRowwise = 8;
+constexpr int kOptRowwiseBf16 = 9;
+constexpr int kBaseRowwise = 4;
+
+constexpr bool opt_bf16(int OPT) { return (OPT >= kOptSgdBf16 && OPT <= kOptAdamBf16) || OPT == kOptAdagradBf16 || OPT == kOptRowwiseBf16; }                // 16-bit weight rows
+constexpr int opt_base(int OPT) {      // the fp32 row rule: 0 plain SGD, 1 momentum / wd SGD, 2 Adam, 3 Adagrad, 4 row-wise Adagrad
+  return (OPT == kOptRowwise || OPT == kOptRowwiseBf16) ? kBaseRowwise
+         : (OPT == kOptAdagrad || OPT == kOptAdagradBf16) ? kBaseAdagrad : (opt_bf16(OPT) ? OPT - kOptSgdBf16 : OPT);
 }
-static_assert(opt_base(kOptAdamBf16) == 2 && opt_base(kOptAdagradBf16) == kBaseAdagrad && opt_bf16(kOptAdagradBf16) && !opt_bf16(kOptAdagrad), "row rule numbering");
+static_assert(opt_base(kOptAdamBf16) == 2 && opt_base(kOptAdagradBf16) == kBaseAdagrad && opt_bf16(kOptAdagradBf16) && !opt_bf16(kOptAdagrad) &&
+              opt_base(kOptRowwise) == kBaseRowwise && opt_base(kOptRowwiseBf16) == kBaseRowwise && opt_bf16(kOptRowwiseBf16) && !opt_bf16(kOptRowwise), "row rule numbering");
+constexpr bool opt_rowwise(int OPT) { return opt_base(OPT) == kBaseRowwise; }   // the row is applied whole (apply_row_rowwise), its state is one float
 constexpr bool opt_plain(int OPT) { return opt_base(OPT) == 0; }                // no optimizer state
 constexpr bool opt_state(int OPT) { return opt_base(OPT) != 0; }
 struct Bf16Keys { int32_t table[FFH_MAX_TABLES]; int32_t col0[FFH_MAX_TABLES]; };   // kOptSgdBf16 / kOptMomentumBf16: in place of the (unused) s1 pointers
@@ -487,6 +498,7 @@ __device__ __forceinline__ uint64_t sr_row_key(const OptP& o, const SrKey& sk, u
 template <int VEC, int OPT>
 __device__ __forceinline__ void apply_row(const OptP& o, float* wrow, float* s0row, float* s1row, int c, const float (&acc)[VEC], const bool nt = false,
                                           const SrKey& sk = SrKey{0, 0}, uint64_t rkey = 0) {
+  if (opt_rowwise(OPT)) return;      // (never reached: both apply sites hand such a row to apply_row_rowwise)
   if (OPT == kOptSgdBf16) {
     uint16_t* const w16 = reinterpret_cast<uint16_t*>(wrow);
     uint16_t h[VEC];
@@ -623,6 +635,114 @@ __device__ __forceinline__ void apply_row(const OptP& o, float* wrow, float* s0r
     if (BASE == 2) s1row[c] = bv[0];
   }
 }
+
+// vector c of a bf16 row from its fp32 value, for apply_row_rowwise: the one rounding of kOptSgdBf16 with its key, the statements of apply_row's own
+// (which stay where they are: the kernels that existed compile to the instructions of before)
+template <int VEC>
+__device__ __forceinline__ void round_store_bf16(const OptP& o, uint16_t* w16, int c, const float (&wv)[VEC], const SrKey& sk, uint64_t rkey) {
+  uint16_t h[VEC];
+  const int64_t g0 = sk.col0 + (int64_t)c * VEC;
+  const bool sr = o.sr_mode == FFH_BF16_ROUND_STOCHASTIC;
+  const uint64_t grp = (sr && VEC == 4 && (g0 & 3) == 0) ? ffh_bf16_sr_group(rkey, (uint64_t)g0) : 0;
+#pragma unroll
+  for (int k = 0; k < VEC; k++) {
+    uint32_t r = 0;
+    if (sr) {
+      const uint64_t gc = (uint64_t)(g0 + k);
+      r = ffh_bf16_sr_field((VEC == 4 && (g0 & 3) == 0) ? grp : ffh_bf16_sr_group(rkey, gc), gc);
+    }
+    h[k] = ffh_bf16_round(wv[k], o.sr_mode, r);
+  }
+  if (VEC == 4) reinterpret_cast<uint2*>(w16)[c] = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
+  else w16[c] = h[0];
+}
+
+// Row-wise Adagrad on one complete row (include/ff_hip_rowwise.h, statement by statement), by the row's lane group: `lpr` consecutive lanes of one
+// wave, this lane the c0-th of them; vector c = c0 + t * lpr of the row (VEC columns) is this lane's in trip t.  `sum_of(c, g)` gives the canonical
+// gradient sum of vector c.  Gradient and weights of up to kMaxChunks trips stay in registers between the sum and the update (the entry points refuse
+// wider rows for this rule), so no row is read twice.
+// TREE: level k adds the subtrees whose column indices differ in bit k -- the VEC columns of a vector in the lane; then, per trip, a butterfly over
+// the group's lane index c0 (the low bits of the vector index): each lane holds the sum of its aligned subtree of `s` lanes and reads the sibling
+// subtree's from that subtree's first lane (every lane of a subtree holds the same value), nothing where the sibling lies wholly at or past lpr
+// (padding: x + (+0) = x for the x >= +0 that occur); then the trips (the high bits of the vector index; only a group of 64 lanes makes several).
+// A trip's butterfly is walked by all lanes of the group, a vector that does not exist (c >= nvec: the last trip of D / VEC not a multiple of 64)
+// counting as +0.  A lane only ever reads lanes of its own group: they took the same branches to get here (sub-run / slot, `single` / `complete`
+// and nvec are the group's), so they are active together whatever iteration the wave's other groups are in.  __shfl is ds_bpermute_b32: groups are
+// neither a power of two wide (D = 48: 12 lanes) nor aligned to one, which rules out the DPP row operations; six dependent LDS-crossbar hops at most.
+// S: loaded by every lane of the group (one address: a broadcast), stored by the group's first lane behind the loads in program order.
+template <int VEC, int OPT, class F>
+__device__ __forceinline__ void apply_row_rowwise(const OptP& o, float* wrow, float* Sp, int D, int nvec, int lpr, int c0, int lane, F&& sum_of,
+                                                  const SrKey& sk, uint64_t rkey) {
+#pragma clang fp contract(off)
+  uint16_t* const w16 = reinterpret_cast<uint16_t*>(wrow);
+  const float S = *Sp;
+  float gt[kMaxChunks][VEC], wv[kMaxChunks][VEC], part[kMaxChunks];
+  uint2 w2[kMaxChunks];      // bf16 rows, 16-byte form: the packed words are what lives across the sum; wv[t] is widened from them again for the update
+#pragma unroll
+  for (int t = 0; t < kMaxChunks; t++) {
+    part[t] = 0.f;
+    if (t * 64 < nvec) {                  // (uniform over the wave; t > 0: nvec > 64, the group is the wave)
+      const int c = c0 + t * lpr;
+      float p = 0.f;
+      if (c < nvec) {
+        sum_of(c, gt[t]);
+        if (VEC == 4) {
+          if (opt_bf16(OPT)) {
+            w2[t] = reinterpret_cast<const uint2*>(w16)[c];
+            wv[t][0] = ffh_bf16_to_f32((uint16_t)w2[t].x); wv[t][1] = ffh_bf16_to_f32((uint16_t)(w2[t].x >> 16));
+            wv[t][2] = ffh_bf16_to_f32((uint16_t)w2[t].y); wv[t][3] = ffh_bf16_to_f32((uint16_t)(w2[t].y >> 16));
+          } else {
+            const float4 w = reinterpret_cast<const float4*>(wrow)[c];
+            wv[t][0] = w.x; wv[t][1] = w.y; wv[t][2] = w.z; wv[t][3] = w.w;
+          }
+        } else {
+          wv[t][0] = opt_bf16(OPT) ? ffh_bf16_to_f32(w16[c]) : wrow[c];
+        }
+        float sq[VEC];
+#pragma unroll
+        for (int k = 0; k < VEC; k++) {
+          if (o.wd != 0.f) { const float t0 = o.wd * wv[t][k]; gt[t][k] = gt[t][k] + t0; }
+          sq[k] = gt[t][k] * gt[t][k];
+        }
+        if (VEC == 4) { const float lo = sq[0] + sq[1], hi = sq[2] + sq[3]; p = lo + hi; }
+        else p = sq[0];
+      }
+      for (int s = 1; s < lpr; s <<= 1) {
+        const int sib = (c0 & ~(s - 1)) ^ s;                      // first lane (of the group) of the sibling subtree
+        const float other = __shfl(p, sib < lpr ? lane - c0 + sib : lane);
+        if (sib < lpr) p = p + other;
+      }
+      part[t] = p;
+    }
+  }
+  // the trips: absent ones are +0, and x + (+0) = x, so the one expression is TREE's for every number of trips
+  const float sum01 = part[0] + part[1], sum23 = part[2] + part[3];
+  const float sum = sum01 + sum23;
+  const float ms = sum / (float)D;
+  const float Sn = S + ms;
+  const float den = sqrtf(Sn) + o.eps;
+#pragma unroll
+  for (int t = 0; t < kMaxChunks; t++) {
+    const int c = c0 + t * lpr;
+    if (t * 64 < nvec && c < nvec) {
+      if (VEC == 4 && opt_bf16(OPT)) {      // widened again from the two packed words: exact, and half the registers across the sum
+        wv[t][0] = ffh_bf16_to_f32((uint16_t)w2[t].x); wv[t][1] = ffh_bf16_to_f32((uint16_t)(w2[t].x >> 16));
+        wv[t][2] = ffh_bf16_to_f32((uint16_t)w2[t].y); wv[t][3] = ffh_bf16_to_f32((uint16_t)(w2[t].y >> 16));
+      }
+#pragma unroll
+      for (int k = 0; k < VEC; k++) {
+        const float q = gt[t][k] / den;
+        const float t2 = o.lr * q;
+        wv[t][k] = wv[t][k] - t2;
+      }
+      if (opt_bf16(OPT)) round_store_bf16<VEC>(o, w16, c, wv[t], sk, rkey);
+      else if (VEC == 4) reinterpret_cast<float4*>(wrow)[c] = make_float4(wv[t][0], wv[t][1], wv[t][2], wv[t][3]);
+      else wrow[c] = wv[t][0];
+    }
+  }
+  if (c0 == 0) *Sp = Sn;
+}
+static_assert(kMaxChunks == 4, "apply_row_rowwise: the tree over the trips is written for four");
 
 struct RedArgs {
   ffh_emb_table t[FFH_MAX_TABLES];
@@ -816,6 +936,20 @@ __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const 
       float* wrow = weight_row<OPT>(tb.weight, key, D);
       const uint64_t rkey = single ? sr_row_key<OPT>(op, sk, key) : 0;
       float* prow = partial_t + (chunk * 2 + odd) * D;
+      if constexpr (opt_rowwise(OPT)) {
+        if (single) {      // the whole row at once; the sub-run's sum of vector c as the loop below forms it, in order
+          apply_row_rowwise<VEC, OPT>(op, wrow, st0 + key, D, nvec, lpr, c0, lane, [&](int c, float (&acc)[VEC]) {
+            load_grad<VEC>(acc, tb.io + (int64_t)s_pos[s] * tb.ld, c, Lf, avg);
+            for (int q = s + 1; q < e; q++) {
+              float v0[VEC];
+              load_grad<VEC>(v0, tb.io + (int64_t)s_pos[q] * tb.ld, c, Lf, avg);
+#pragma unroll
+              for (int v = 0; v < VEC; v++) acc[v] = acc[v] + v0[v];
+            }
+          }, sk, rkey);
+          continue;
+        }
+      }
       for (int c = c0; c < nvec; c += lpr) {
         float acc[VEC];
         load_grad<VEC>(acc, tb.io + (int64_t)s_pos[s] * tb.ld, c, Lf, avg);
@@ -920,6 +1054,20 @@ __device__ __forceinline__ void fold_table_body(const ffh_emb_table& tb, const f
     float* wrow = weight_row<OPT>(tb.weight, m.y, D);
     const uint64_t rkey = complete ? sr_row_key<OPT>(op, sk, m.y) : 0;
     float* orow = pout_t + oslot * D;
+    if constexpr (opt_rowwise(OPT)) {
+      if (complete) {      // the whole row at once; the walk's sum of vector c as the loop below forms it, left to right
+        apply_row_rowwise<VEC, OPT>(op, wrow, st0 + m.y, D, nvec, lpr, c0, lane, [&](int c, float (&acc)[VEC]) {
+          xwg_load_row<VEC, AGENT>(acc, part + slot * D, c);
+          for (int64_t q = b + 1; q < b2; q++) {
+            float v0[VEC];
+            xwg_load_row<VEC, AGENT>(v0, part + 2 * q * D, c);
+#pragma unroll
+            for (int v = 0; v < VEC; v++) acc[v] = acc[v] + v0[v];
+          }
+        }, sk, rkey);
+        continue;
+      }
+    }
     for (int c = c0; c < nvec; c += lpr) {
       float acc[VEC];
       xwg_load_row<VEC, AGENT>(acc, part + slot * D, c);
@@ -1304,13 +1452,15 @@ __device__ __forceinline__ void msd_window(const uint2* __restrict__ kp, const u
 // OPT != 0 (momentum / weight-decay SGD, Adam on the touched rows): the row rule holds up to three more rows' worth of registers;
 // those instantiations are compiled for 4 waves per SIMD instead of spilling.  OPT kOptSgdBf16 (bf16 rows, the rounding hash): 6 waves per
 // SIMD -- at 8 it spilled 30 VGPRs; 6 and 4 were measured 193 / 192 against 200 us at the Terabyte shape.
+// kOptRowwiseBf16 in the 16-byte form: 3 -- a row of up to four vectors per lane (gradient and packed weights) stays in registers across the sum
+// beside the rounding hash; at 4 (128 VGPRs) it spilled 49 dwords.
 // MSD: the bucket form above (the list is grouped by top digit only; six workgroups per CU: the window needs 25 KB of LDS).
 struct RedSmem { RedShared sh; uint2 fmeta[kFoldStage]; };
 union MsdSmem { RedSmem red; MsdShared ms; };          // the window is dead once the tile's entries sit in registers
 template <bool MSD> struct RedSmemOf { typedef RedSmem type; static __device__ __forceinline__ RedSmem& red(RedSmem& s) { return s; } };
 template <> struct RedSmemOf<true> { typedef MsdSmem type; static __device__ __forceinline__ RedSmem& red(MsdSmem& s) { return s.red; } };
 template <int VEC, int OPT, bool MSD = false, bool LRP = false>
-__global__ __launch_bounds__(kRedThreads, MSD ? (opt_plain(OPT) ? 6 : 4) : (OPT == 0 ? 8 : OPT == kOptSgdBf16 ? 6 : 4)) void emb_sgd_reduce_kernel(const RedArgs a) {
+__global__ __launch_bounds__(kRedThreads, (VEC == 4 && OPT == kOptRowwiseBf16) ? 3 : MSD ? (opt_plain(OPT) ? 6 : 4) : (OPT == 0 ? 8 : OPT == kOptSgdBf16 ? 6 : 4)) void emb_sgd_reduce_kernel(const RedArgs a) {
   ffh_kernel_prio();
   FFH_OPT_OF(LRP, op, a.op);
   __shared__ typename RedSmemOf<MSD>::type smem;
@@ -1763,7 +1913,8 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   int kind = FFH_SPARSE_OPT_SGD;
   if (opt && do_apply) {
     kind = opt->kind;
-    if (kind != FFH_SPARSE_OPT_SGD && kind != FFH_SPARSE_OPT_SGD_MOMENTUM && kind != FFH_SPARSE_OPT_ADAM && kind != FFH_SPARSE_OPT_ADAGRAD)
+    if (kind != FFH_SPARSE_OPT_SGD && kind != FFH_SPARSE_OPT_SGD_MOMENTUM && kind != FFH_SPARSE_OPT_ADAM && kind != FFH_SPARSE_OPT_ADAGRAD &&
+        kind != FFH_SPARSE_OPT_ROWWISE_ADAGRAD)
       return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt: unknown ffh_sparse_opt.kind");
     if (b16 && (kind == FFH_SPARSE_OPT_SGD_MOMENTUM || kind == FFH_SPARSE_OPT_ADAM) && nt > FFH_BF16_MAX_STATEFUL_TABLES)      // (Adagrad: one state pointer, the Bf16Keys layout)
       return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt_multi_bf16: momentum / Adam take at most FFH_BF16_MAX_STATEFUL_TABLES (32) tables per call");
@@ -1771,7 +1922,7 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
     op.b1 = opt->beta1; op.b2 = opt->beta2; op.eps = opt->epsilon; op.omb1 = 1.0f - opt->beta1; op.omb2 = 1.0f - opt->beta2;
     if (kind == FFH_SPARSE_OPT_SGD && (op.wd != 0.0f || op.mom != 0.0f)) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt: FFH_SPARSE_OPT_SGD takes no weight decay / momentum (use FFH_SPARSE_OPT_SGD_MOMENTUM)");
     if (lr_block) { op.lr = 0.0f; opt_set_lr_src(op, ffh_lr_rate_ptr(lr_block, kind == FFH_SPARSE_OPT_ADAM)); }      // (include/ff_hip_lr.h: opt->lr is ignored)
-    const bool need0 = kind == FFH_SPARSE_OPT_ADAM || kind == FFH_SPARSE_OPT_ADAGRAD || (kind == FFH_SPARSE_OPT_SGD_MOMENTUM && op.mom > 0.0f);
+    const bool need0 = kind == FFH_SPARSE_OPT_ADAM || kind == FFH_SPARSE_OPT_ADAGRAD || kind == FFH_SPARSE_OPT_ROWWISE_ADAGRAD || (kind == FFH_SPARSE_OPT_SGD_MOMENTUM && op.mom > 0.0f);
     for (int i = 0; i < nt && batch > 0; i++) {
       if (need0 && (!states || !states[i].s0)) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt: optimizer state (s0) missing");
       if (kind == FFH_SPARSE_OPT_ADAM && !states[i].s1) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt: optimizer state (s1) missing");
@@ -1784,10 +1935,12 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   for (int i = 0; i < nt; i++) maxR = tables[i].num_entries > maxR ? tables[i].num_entries : maxR;
   if (maxR > (1LL << 32)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_sgd_fused: num_entries > 2^32");
   bool v4 = can_vec4(tables, nt, D);
-  for (int i = 0; i < nt && v4 && kind != FFH_SPARSE_OPT_SGD; i++)
+  for (int i = 0; i < nt && v4 && kind != FFH_SPARSE_OPT_SGD && kind != FFH_SPARSE_OPT_ROWWISE_ADAGRAD; i++)      // (row-wise: s0 is one float per row, never read as a vector)
     v4 = (!states[i].s0 || aligned16(states[i].s0)) && (kind == FFH_SPARSE_OPT_ADAGRAD || !states[i].s1 || aligned16(states[i].s1));      // (Adagrad: s1 is unused)
   const int nvec = v4 ? D / 4 : D;
   if ((nvec + 63) / 64 > kMaxChunks * 64) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_sgd_fused: out_dim too large");
+  if (kind == FFH_SPARSE_OPT_ROWWISE_ADAGRAD && (nvec + 63) / 64 > kMaxChunks)      // (apply_row_rowwise keeps the row in registers)
+    return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_opt: FFH_SPARSE_OPT_ROWWISE_ADAGRAD takes out_dim <= 1024 (16-byte form) / 256 (include/ff_hip_rowwise.h)");
   const BwdLayout lay = bwd_layout(nt, L, D, batch);
   if (!c->ws || c->ws_bytes < lay.total) return ffh_fail(c, FFH_ERR_WORKSPACE, "embedding_bwd_sgd_fused: workspace too small (ffh_embedding_bwd_workspace_bytes)");
   char* ws = (char*)c->ws;
@@ -1841,6 +1994,7 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
       else hipLaunchKernelGGL((emb_sgd_small_kernel<1, OPTV, LRPV>), dim3(nt), dim3(kSmallThreads), 0, as_stream(s), sm); }
 #define FFH_SMALL(OPTV) { if (lr_block) FFH_SMALL_L(OPTV, true) else FFH_SMALL_L(OPTV, false) }
     if (kind == FFH_SPARSE_OPT_ADAGRAD) { if (b16) FFH_SMALL(kOptAdagradBf16) else FFH_SMALL(kOptAdagrad) }
+    else if (kind == FFH_SPARSE_OPT_ROWWISE_ADAGRAD) { if (b16) FFH_SMALL(kOptRowwiseBf16) else FFH_SMALL(kOptRowwise) }
     else if (b16) { if (kind == FFH_SPARSE_OPT_SGD) FFH_SMALL(kOptSgdBf16) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_SMALL(kOptMomentumBf16) else FFH_SMALL(kOptAdamBf16) }
     else if (kind == FFH_SPARSE_OPT_SGD) FFH_SMALL(0) else if (kind == FFH_SPARSE_OPT_SGD_MOMENTUM) FFH_SMALL(1) else FFH_SMALL(2)
 #undef FFH_SMALL
@@ -1936,6 +2090,10 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   if (kind == FFH_SPARSE_OPT_ADAGRAD) {
     if (b16) { if (msd) FFH_RED(kOptAdagradBf16, true) else FFH_RED(kOptAdagradBf16, false) }
     else { if (msd) FFH_RED(kOptAdagrad, true) else FFH_RED(kOptAdagrad, false) }
+  }
+  else if (kind == FFH_SPARSE_OPT_ROWWISE_ADAGRAD) {
+    if (b16) { if (msd) FFH_RED(kOptRowwiseBf16, true) else FFH_RED(kOptRowwiseBf16, false) }
+    else { if (msd) FFH_RED(kOptRowwise, true) else FFH_RED(kOptRowwise, false) }
   }
   else if (b16 && kind == FFH_SPARSE_OPT_SGD) { if (msd) FFH_RED(kOptSgdBf16, true) else FFH_RED(kOptSgdBf16, false) }
   else if (b16 && kind == FFH_SPARSE_OPT_SGD_MOMENTUM) { if (msd) FFH_RED(kOptMomentumBf16, true) else FFH_RED(kOptMomentumBf16, false) }
@@ -2111,6 +2269,8 @@ int ffh_bf16_counter_advance(ffh_ctx* c, uint64_t* counter, ffh_stream s) {
   FFH_LAUNCH_CHECK(c, "bf16_counter_advance");
   return FFH_OK;
 }
+
+int ffh_rowwise_abi_version(void) { return FFH_ROWWISE_ABI_VERSION; }      // include/ff_hip_rowwise.h: the row rule lives in this file
 
 }  // extern "C"
 static_assert(sizeof(RedArgs) <= 4096 && sizeof(SmallArgs) <= 4096 && sizeof(EmbArgs) <= 4096, "kernel arguments");

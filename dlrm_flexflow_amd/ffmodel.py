@@ -114,6 +114,7 @@ def lib() -> C.CDLL:
         "flexflow_config_set_adagrad": (None, [H, D, D]),
         "flexflow_model_weight_mirror_stale_bytes": (C.c_int64, [H]),
         "flexflow_adagrad_optimizer_create": (H, [H, D, D, D, D]), "flexflow_model_set_adagrad_optimizer": (None, [H, H]),
+        "flexflow_config_set_adagrad_rowwise": (None, [H, I]), "flexflow_adagrad_optimizer_set_rowwise": (None, [H, I]),
         "flexflow_model_compile": (None, [H, I, IP, I, I]),
         "flexflow_model_init_layers": (None, [H]), "flexflow_model_reset_metrics": (None, [H]),
         "flexflow_model_forward": (None, [H, I]), "flexflow_model_zero_gradients": (None, [H]),
@@ -331,6 +332,36 @@ def adagrad_reference(w, g, S, lr, eps, wd=0.0):
     return w, S
 
 
+def rowwise_tree_sum(t):
+    """TREE of include/ff_hip_rowwise.h over the last axis of the non-negative array `t`: zero-pad to the next power of two, then add neighbouring
+    subtrees level by level (level k adds the elements whose indices differ in bit k), each addition rounded in t's dtype."""
+    t = np.asarray(t)
+    P = 1 << max(t.shape[-1] - 1, 0).bit_length()
+    t = np.concatenate([t, np.zeros(t.shape[:-1] + (P - t.shape[-1],), t.dtype)], axis=-1)
+    while t.shape[-1] > 1:
+        t = t[..., 0::2] + t[..., 1::2]
+    return t[..., 0]
+
+
+def rowwise_adagrad_reference(w, g, S, lr, eps, wd=0.0):
+    """One row-wise Adagrad step as include/ff_hip_rowwise.h states it, restated with one numpy operation per rounded operation in the dtype of `w`
+    (float32: the bits the kernels give; float64: the same statements for a comparison).  w, g: [rows][D]; S: [rows], one accumulator per row.
+    Returns (w_new, S_new); the inputs are left alone."""
+    dt = np.asarray(w).dtype
+    w, g, S = np.asarray(w, dt), np.asarray(g, dt), np.asarray(S, dt)
+    lr, eps, wd = dt.type(lr), dt.type(eps), dt.type(wd)
+    with np.errstate(all="ignore"):
+        gt = g if wd == 0 else g + wd * w
+        t = gt * gt
+        total = rowwise_tree_sum(t)
+        ms = total / dt.type(w.shape[-1])
+        S = S + ms
+        d = np.sqrt(S) + eps
+        q = gt / d[..., None]
+        w = w - lr * q
+    return w, S
+
+
 def cross_reference(x0, v, xl) -> np.ndarray:
     """The combine of a DCNv2 low-rank cross layer as include/ff_hip_cross.h states it, in float32 numpy: fadd_rn(fmul_rn(x0, v), xl) -- two
     separately rounded float32 operations per element (numpy never contracts them), which ffh_cross_fwd equals bit for bit."""
@@ -454,12 +485,15 @@ class FFConfig:
 
     def set(self, seed=None, device=None, enable_graph=None, overlap_embedding=None, dense_embedding_update=None,
             embedding_dtype=None, embedding_rounding=None, lr_warmup_steps=None, lr_decay_start_step=None, lr_num_decay_steps=None,
-            device_lr=None, adagrad_eps=None, adagrad_initial_accumulator=None):
+            device_lr=None, adagrad_eps=None, adagrad_initial_accumulator=None, adagrad_rowwise=None):
         """embedding_dtype: "fp32" | "bf16"; embedding_rounding: "stochastic" | "nearest" (the --embedding-* flags).
         lr_*: the schedule of --lr-num-warmup-steps / --lr-decay-start-step / --lr-num-decay-steps; device_lr: True = --device-lr,
         False = --host-lr-schedule, None = compile() chooses the route.
         adagrad_eps / adagrad_initial_accumulator: --adagrad-eps / --adagrad-initial-accumulator, what an AdagradOptimizer without its own takes.
+        adagrad_rowwise: --adagrad-rowwise, the tables of an AdagradOptimizer keep one accumulator per row (include/ff_hip_rowwise.h).
         FFModel(config) copies the config: call set() before the model is built (as for every other field)."""
+        if adagrad_rowwise is not None:
+            lib().flexflow_config_set_adagrad_rowwise(self.h, 1 if adagrad_rowwise else 0)
         if adagrad_eps is not None or adagrad_initial_accumulator is not None:
             self._adagrad = tuple(old if new is None else float(new) for old, new in zip(getattr(self, "_adagrad", (1e-10, 0.0)),
                                                                                        (adagrad_eps, adagrad_initial_accumulator)))
@@ -587,9 +621,9 @@ class FFModel:
         self._opt = lib().flexflow_adam_optimizer_create(self.h, alpha, beta1, beta2, weight_decay, epsilon)
         lib().flexflow_model_set_adam_optimizer(self.h, self._opt)
 
-    def set_adagrad_optimizer(self, lr=0.01, weight_decay=0.0, epsilon=None, initial_accumulator=None):
+    def set_adagrad_optimizer(self, lr=0.01, weight_decay=0.0, epsilon=None, initial_accumulator=None, rowwise=False):
         """AdagradOptimizer(self, ...) as this model's optimizer."""
-        AdagradOptimizer(self, lr, weight_decay, epsilon, initial_accumulator)
+        AdagradOptimizer(self, lr, weight_decay, epsilon, initial_accumulator, rowwise)
 
     def compile(self, loss_type=LOSS_MSE_AVG, metrics=(METRICS_ACCURACY, METRICS_MSE), comp_mode=COMP_MODE_TRAINING):
         m = (C.c_int * len(metrics))(*metrics)
@@ -677,12 +711,16 @@ class AdagradOptimizer:
     """Adagrad with torch.optim.Adagrad's element-wise rule (include/ff_hip_adagrad.h; adagrad_reference restates it) as the optimizer of `model`:
     MLPs, cross layers and replicated tables in one dense launch, the other tables on the fused sorted-segments update (weight_decay == 0) or the dense
     table path.  epsilon / initial_accumulator None: the config's (--adagrad-eps, default 1e-10; --adagrad-initial-accumulator, default 0).  Needs a
-    kernel library with the Adagrad extension: compile() refuses the model otherwise."""
+    kernel library with the Adagrad extension: compile() refuses the model otherwise.
+    rowwise=True (or the config's adagrad_rowwise / --adagrad-rowwise): the tables keep ONE accumulator per row, the running sum of the row's mean
+    squared gradient (include/ff_hip_rowwise.h; rowwise_adagrad_reference restates it), on the fused update only; the dense slab stays element-wise."""
 
-    def __init__(self, model: "FFModel", lr=0.01, weight_decay=0.0, epsilon=None, initial_accumulator=None):
+    def __init__(self, model: "FFModel", lr=0.01, weight_decay=0.0, epsilon=None, initial_accumulator=None, rowwise=False):
         nan = float("nan")
         self.h = lib().flexflow_adagrad_optimizer_create(model.h, lr, weight_decay, nan if epsilon is None else float(epsilon),
                                                          nan if initial_accumulator is None else float(initial_accumulator))
+        if rowwise:
+            lib().flexflow_adagrad_optimizer_set_rowwise(self.h, 1)
         lib().flexflow_model_set_adagrad_optimizer(model.h, self.h)
         model._opt = self
 

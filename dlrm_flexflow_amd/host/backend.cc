@@ -171,6 +171,23 @@ const KernelApi* load_kernel_api(const std::string& path_in) {
     }
     api->adagrad = b;
   }
+  // the row-wise Adagrad extension (include/ff_hip_rowwise.h): the same rule
+  if (dlsym(h, "ffh_rowwise_abi_version")) {
+    KernelApiRowwise* b = new KernelApiRowwise();
+#define FFH_LOAD(name)                                                        \
+  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
+  if (!b->name) {                                                             \
+    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_rowwise.h: %s is missing\n", path.c_str(), #name);   \
+    abort();                                                                  \
+  }
+    FFH_ROWWISE_API_LIST(FFH_LOAD)
+#undef FFH_LOAD
+    if (b->ffh_rowwise_abi_version() != FFH_ROWWISE_ABI_VERSION) {
+      fprintf(stderr, "FATAL: %s has row-wise Adagrad ABI version %d, expected %d\n", path.c_str(), b->ffh_rowwise_abi_version(), FFH_ROWWISE_ABI_VERSION);
+      abort();
+    }
+    api->rowwise = b;
+  }
   if (path_in.empty() && g_env_override)
     fprintf(stderr, "[DLRM] FFH_BACKEND_LIB: kernel library %s (%s)\n", path.c_str(), api->ffh_backend_name());
   cache[path] = api;

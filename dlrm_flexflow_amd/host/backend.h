@@ -11,6 +11,7 @@
 #include "../../include/ff_hip_cross.h"
 #include "../../include/ff_hip_digest.h"
 #include "../../include/ff_hip_adagrad.h"
+#include "../../include/ff_hip_rowwise.h"
 
 // The optional bf16-table extension (include/ff_hip_bf16.h): all of its list or none of it.
 struct KernelApiBf16 {
@@ -61,6 +62,13 @@ struct KernelApiAdagrad {
 #undef FFH_DECL
 };
 
+// The optional row-wise Adagrad extension (include/ff_hip_rowwise.h: the library takes FFH_SPARSE_OPT_ROWWISE_ADAGRAD in the table update).
+struct KernelApiRowwise {
+#define FFH_DECL(name) decltype(&::name) name;
+  FFH_ROWWISE_API_LIST(FFH_DECL)
+#undef FFH_DECL
+};
+
 struct KernelApi {
 #define FFH_DECL(name) decltype(&::name) name;
   FFH_API_LIST(FFH_DECL)
@@ -72,6 +80,7 @@ struct KernelApi {
   const KernelApiCross* cross = nullptr; // likewise for include/ff_hip_cross.h
   const KernelApiDigest* digest = nullptr;   // likewise for include/ff_hip_digest.h (absent: the host layer computes the same digest from the bytes it copies)
   const KernelApiAdagrad* adagrad = nullptr; // likewise for include/ff_hip_adagrad.h
+  const KernelApiRowwise* rowwise = nullptr; // likewise for include/ff_hip_rowwise.h
   void* handle;
   std::string path;
   bool overridden = false;      // chosen by --backend or $FFH_BACKEND_LIB rather than the product default: the driver says so on its THROUGHPUT line

@@ -50,7 +50,7 @@ struct CkRecord {
 const char* optimizer_kind(const FFModel* ff) {
   if (const SGDOptimizer* s = dynamic_cast<const SGDOptimizer*>(ff->optimizer)) return s->momentum > 0.0 ? "sgd-momentum" : "sgd";
   if (dynamic_cast<const AdamOptimizer*>(ff->optimizer)) return "adam";
-  if (dynamic_cast<const AdagradOptimizer*>(ff->optimizer)) return "adagrad";
+  if (const AdagradOptimizer* a = dynamic_cast<const AdagradOptimizer*>(ff->optimizer)) return a->rowwise ? "adagrad-rowwise" : "adagrad";
   return "none";
 }
 // how the tables are updated: what --sparse-embedding-optimizer / --dense-embedding-update select for this optimizer
@@ -134,7 +134,8 @@ std::vector<CkRecord> collect_records(FFModel* ff) {
       if (e && i == 0)
         for (int k = 0; k < 2; k++)
           if (e->opt_state[k]) {
-            CkRecord s = device_record("sparse_state" + std::to_string(k) + "/" + id, "f32", 4, e->opt_state[k], rows, cols, cols);
+            const int64_t scols = adagrad && adagrad->rowwise ? 1 : cols;      // (--adagrad-rowwise: one float per row)
+            CkRecord s = device_record("sparse_state" + std::to_string(k) + "/" + id, "f32", 4, e->opt_state[k], rows, scols, scols);
             if (e->row_sharded) { s.zero_tail = (char*)e->opt_state[k] + (size_t)rows * cols * 4; s.zero_tail_bytes = (size_t)e->out_channels * 4; }
             out.push_back(s);
           }
@@ -436,6 +437,9 @@ FFModel::CheckpointInfo FFModel::load_checkpoint(const std::string& dir) {
   if (m.world_size != mine.world_size || m.rank != mine.rank)
     refuse(dir, "%s was saved by rank %d of %d, this is rank %d of %d; a checkpoint loads into the world size that saved it: launch %d rank%s", path.c_str(),
            m.rank, m.world_size, mine.rank, mine.world_size, m.world_size, m.world_size == 1 ? "" : "s");
+  if ((m.optimizer == "adagrad-rowwise" && mine.optimizer == "adagrad") || (m.optimizer == "adagrad" && mine.optimizer == "adagrad-rowwise"))
+    refuse(dir, "it was saved %s --adagrad-rowwise, this run is %s it; an element-wise accumulator and a row-wise one do not convert: %s --adagrad-rowwise",
+           m.optimizer == "adagrad" ? "without" : "with", m.optimizer == "adagrad" ? "with" : "without", m.optimizer == "adagrad" ? "drop" : "add");
   if (m.optimizer != mine.optimizer)
     refuse(dir, "it was saved with --optimizer %s, this run has --optimizer %s; the optimizer state does not convert: use --optimizer %s", m.optimizer.c_str(),
            mine.optimizer.c_str(), m.optimizer.c_str());

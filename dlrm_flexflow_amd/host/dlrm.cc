@@ -472,8 +472,12 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
     // what --optimizer adagrad allocated on this rank: S beside every fp32 weight it updates, fp32 beside bf16 tables too (on fp32 tables it doubles their HBM)
     size_t bytes = ag->state_bytes;
     for (const Embedding* e : ff->embeddings)
-      if (e->opt_state[0]) bytes += e->weights[0].get_volume() * 4 + (e->row_sharded ? (size_t)e->out_channels * 4 : 0);
-    if (chatty)
+      if (e->opt_state[0]) bytes += ag->rowwise ? e->weights[0].get_volume() / (size_t)e->out_channels * 4
+                                                : e->weights[0].get_volume() * 4 + (e->row_sharded ? (size_t)e->out_channels * 4 : 0);
+    if (chatty && ag->rowwise)      // --adagrad-rowwise: one float per table row
+      printf("[DLRM] optimizer: adagrad eps=%g A=%g lr=%g, tables: %s, accumulator %zu bytes (%.3f GB) on rank %d\n", ag->epsilon, ag->initial_accumulator, ag->lr,
+             ff->embeddings.empty() ? "none" : "fused row-wise", bytes, bytes / 1e9, ff->rank);
+    else if (chatty)
       printf("[DLRM] optimizer: adagrad eps=%g A=%g lr=%g, tables: %s, accumulator %zu bytes (%.3f GB) on rank %d\n", ag->epsilon, ag->initial_accumulator, ag->lr,
              ff->embeddings.empty() ? "none" : (ff->fused_embedding_update() ? "fused" : "dense"), bytes, bytes / 1e9, ff->rank);
   }

@@ -30,6 +30,7 @@
 #include "../../include/ff_hip_lr.h"
 #include "../../include/ff_hip_cross.h"
 #include "../../include/ff_hip_adagrad.h"
+#include "../../include/ff_hip_rowwise.h"
 #include "ffcomm.h"
 
 // ---- enums: identical values to [ref: include/ffconst.h:4-57] -------------------------------
@@ -172,6 +173,7 @@ class FFConfig {
   bool host_lr_schedule;       // --host-lr-schedule: the scheduled value is a launch argument computed on the host each step (A/B; never captured)
   double adagrad_eps;                  // --adagrad-eps E: the eps of --optimizer adagrad (default 1e-10, torch.optim.Adagrad's)
   double adagrad_initial_accumulator;  // --adagrad-initial-accumulator A: what its accumulator S starts at (default 0)
+  bool adagrad_rowwise;                // --adagrad-rowwise: with --optimizer adagrad, the tables keep ONE accumulator per row (include/ff_hip_rowwise.h)
   ffcomm comm;                 // rank / world_size / collectives supplied by the launcher (ffcomm.h)
 };
 
@@ -310,6 +312,9 @@ class AdagradOptimizer : public Optimizer {
   void update(const Parameter* p) override;
   void set_weight_decay(double wd) { weight_decay = wd; }
   double lr, weight_decay, epsilon, initial_accumulator;
+  // row-wise on the tables (include/ff_hip_rowwise.h): the fused update keeps one float per row in Embedding::opt_state[0]; the dense
+  // slab stays element-wise.  Starts as the config's --adagrad-rowwise
+  bool rowwise;
   float* mlp_s;                                // S of the MLP slab
   std::map<const void*, float*> s_values;      // S of every other parameter, keyed by weight pointer
   size_t state_bytes = 0;                      // what init() allocated

@@ -120,6 +120,8 @@ flexflow_adagrad_optimizer_t flexflow_adagrad_optimizer_create(flexflow_model_t 
   return h;
 }
 void flexflow_model_set_adagrad_optimizer(flexflow_model_t m, flexflow_adagrad_optimizer_t o) { M(m)->optimizer = (AdagradOptimizer*)o.impl; }
+void flexflow_config_set_adagrad_rowwise(flexflow_config_t h, int on) { C(h)->adagrad_rowwise = on != 0; }
+void flexflow_adagrad_optimizer_set_rowwise(flexflow_adagrad_optimizer_t o, int on) { ((AdagradOptimizer*)o.impl)->rowwise = on != 0; }
 void flexflow_model_compile(flexflow_model_t m, int loss, const int* metrics, int nb, int comp_mode) {
   std::vector<MetricsType> v;
   for (int i = 0; i < nb; i++) v.push_back((MetricsType)metrics[i]);

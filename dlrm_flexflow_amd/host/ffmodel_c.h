@@ -99,6 +99,9 @@ int64_t flexflow_model_weight_mirror_stale_bytes(flexflow_model_t);
 void flexflow_config_set_adagrad(flexflow_config_t, double epsilon, double initial_accumulator);
 flexflow_adagrad_optimizer_t flexflow_adagrad_optimizer_create(flexflow_model_t, double lr, double weight_decay, double epsilon, double initial_accumulator);
 void flexflow_model_set_adagrad_optimizer(flexflow_model_t, flexflow_adagrad_optimizer_t);
+/* row-wise Adagrad on the tables (include/ff_hip_rowwise.h): --adagrad-rowwise for the optimizers created afterwards / for this optimizer (before compile) */
+void flexflow_config_set_adagrad_rowwise(flexflow_config_t, int on);
+void flexflow_adagrad_optimizer_set_rowwise(flexflow_adagrad_optimizer_t, int on);
 void flexflow_model_compile(flexflow_model_t, int loss_type, const int* metrics, int nb_metrics, int comp_mode);
 void flexflow_model_init_layers(flexflow_model_t);
 void flexflow_model_reset_metrics(flexflow_model_t);

@@ -1237,7 +1237,7 @@ void AdamOptimizer::update(const Parameter* p) {
 // AdagradOptimizer (include/ff_hip_adagrad.h; compile() has checked that the library has the extension)
 // =============================================================================================
 AdagradOptimizer::AdagradOptimizer(const FFModel* _model, double _lr, double _wd, double _eps, double _acc)
-    : Optimizer(_model), lr(_lr), weight_decay(_wd), epsilon(_eps), initial_accumulator(_acc), mlp_s(nullptr) {}
+    : Optimizer(_model), lr(_lr), weight_decay(_wd), epsilon(_eps), initial_accumulator(_acc), rowwise(_model->config.adagrad_rowwise), mlp_s(nullptr) {}
 void AdagradOptimizer::init(void) {
   auto filled = [&](size_t count) {
     float* p = (float*)model->dmalloc(count * sizeof(float));

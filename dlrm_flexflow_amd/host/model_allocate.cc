@@ -23,7 +23,7 @@ bool FFModel::fused_embedding_update() const {
   // ... and for Adagrad without weight decay: an element whose gradient is zero keeps w and S bit for bit, so the touched-rows rule IS the dense
   // sweep, not a divergence to opt into
   const AdagradOptimizer* adagrad = dynamic_cast<const AdagradOptimizer*>(optimizer);
-  if (adagrad && adagrad->weight_decay == 0.0) return true;
+  if (adagrad && adagrad->weight_decay == 0.0) return true;      // (row-wise too: a row without gradient keeps w and its S, include/ff_hip_rowwise.h)
   // ... every other optimizer takes the reference's dense path (zero + scatter-add + whole-table sweep: reference semantics on
   // every row) unless the user opts into the touched-rows rule (--sparse-embedding-optimizer; stated divergence: ffh_sparse_opt)
   return config.sparse_embedding_optimizer && (sgd || adagrad || dynamic_cast<const AdamOptimizer*>(optimizer));
@@ -39,7 +39,7 @@ bool FFModel::sparse_rule(ffh_sparse_opt& o) const {
     return true;
   }
   if (const AdagradOptimizer* ag = dynamic_cast<const AdagradOptimizer*>(optimizer)) {
-    o.kind = FFH_SPARSE_OPT_ADAGRAD; o.lr = (float)ag->lr; o.weight_decay = (float)ag->weight_decay; o.epsilon = (float)ag->epsilon;
+    o.kind = ag->rowwise ? FFH_SPARSE_OPT_ROWWISE_ADAGRAD : FFH_SPARSE_OPT_ADAGRAD; o.lr = (float)ag->lr; o.weight_decay = (float)ag->weight_decay; o.epsilon = (float)ag->epsilon;
     return true;
   }
   const AdamOptimizer* adam = dynamic_cast<const AdamOptimizer*>(optimizer);
@@ -170,6 +170,29 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
     if (bce) last->dy_premasked = true;
   }
   want_eval = want_auc;
+  // --adagrad-rowwise (include/ff_hip_rowwise.h): only the fused table update has the rule, so every placement and route it does not
+  // cover is refused here, each with the flag to change -- before the library checks: a library without the extensions shows them too
+  {
+    const AdagradOptimizer* ag = dynamic_cast<const AdagradOptimizer*>(optimizer);
+    if (config.adagrad_rowwise && !ag) die("--adagrad-rowwise is a form of Adagrad: add --optimizer adagrad, or drop --adagrad-rowwise");
+    if (ag && ag->rowwise && !embeddings.empty()) {
+      if (config.dense_embedding_update)
+        die("--adagrad-rowwise needs the fused sparse table update (no dense row-wise sweep is built): drop --dense-embedding-update or drop --adagrad-rowwise");
+      for (const Embedding* e : embeddings) {
+        if (e->row_sharded)
+          die("--adagrad-rowwise: %s is row-sharded; row-wise Adagrad is built for table-wise tables: drop --row-shard-rows or drop --adagrad-rowwise", e->name);
+        if (e->column_sharded)
+          die("--adagrad-rowwise: %s is column-sharded (a rank would hold part of every row, and the rule needs the mean over the whole row): drop "
+              "--column-shard-rows or drop --adagrad-rowwise", e->name);
+        if (e->replicated)
+          die("--adagrad-rowwise: %s is replicated (data-parallel tables are updated with the dense slab, and no dense row-wise sweep is built): drop "
+              "--replicate-embedding-rows or drop --adagrad-rowwise", e->name);
+      }
+      if (ag->weight_decay != 0.0 && !config.sparse_embedding_optimizer)
+        die("--adagrad-rowwise with weight decay %g updates only the rows a batch touched, which is not the dense sweep: add --sparse-embedding-optimizer to "
+            "accept that, or drop the weight decay or --adagrad-rowwise", ag->weight_decay);
+    }
+  }
   // Adagrad (include/ff_hip_adagrad.h): its parameters, then the library -- the dense launch and the row rule exist only in one with the extension
   if (const AdagradOptimizer* ag = dynamic_cast<const AdagradOptimizer*>(optimizer)) {
     if (!(ag->epsilon > 0.0) && ag->initial_accumulator == 0.0)
@@ -179,6 +202,9 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
     if (!api->adagrad)
       die("--optimizer adagrad: %s (%s) is a kernel library without the Adagrad extension (include/ff_hip_adagrad.h); use --optimizer sgd, sgd-momentum "
           "or adam, or another --backend", api->path.c_str(), api->ffh_backend_name());
+    if (ag->rowwise && !embeddings.empty() && !api->rowwise)
+      die("--adagrad-rowwise: %s (%s) is a kernel library without the row-wise Adagrad extension (include/ff_hip_rowwise.h); drop --adagrad-rowwise, "
+          "or use another --backend", api->path.c_str(), api->ffh_backend_name());
   }
   // a shuffled data order (include/ff_hip_data.h): its batches are one gather launch that only a library with the extension has
   if (config.data_randomize && !api->data)
@@ -281,7 +307,8 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
       const int nstate = rule.kind == FFH_SPARSE_OPT_ADAM ? 2 : ((ag || rule.momentum > 0.0f) ? 1 : 0);
       for (Embedding* e : embeddings) {
         if (!e->held_here(rank) || e->replicated) continue;
-        const size_t bytes = e->weights[0].get_volume() * 4 + (e->row_sharded ? (size_t)e->out_channels * 4 : 0);   // fp32 state, whatever the table's storage
+        size_t bytes = e->weights[0].get_volume() * 4 + (e->row_sharded ? (size_t)e->out_channels * 4 : 0);   // fp32 state, whatever the table's storage
+        if (rule.kind == FFH_SPARSE_OPT_ROWWISE_ADAGRAD) bytes = e->weights[0].get_volume() / (size_t)e->out_channels * 4;      // one float per row (table-wise: compile() refused the rest)
         for (int k = 0; k < nstate; k++) {
           e->opt_state[k] = (float*)dmalloc(bytes);
           if (ag) check(api->ffh_fill_f32(ctx, e->opt_state[k], (int64_t)(bytes / 4), (float)ag->initial_accumulator, stream), "sparse optimizer state");

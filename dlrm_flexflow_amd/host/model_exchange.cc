@@ -113,7 +113,7 @@ size_t FFModel::bf16_tables_per_launch() const {
   bool any16 = false;
   for (const Embedding* e : embeddings) any16 = any16 || e->bf16_weights();
   // (Adagrad has one state pointer per table and rides the plain update's layout: include/ff_hip_adagrad.h)
-  return any16 && fused_embedding_update() && sparse_rule(rule) && rule.kind != FFH_SPARSE_OPT_ADAGRAD ? FFH_BF16_MAX_STATEFUL_TABLES : FFH_MAX_TABLES;
+  return any16 && fused_embedding_update() && sparse_rule(rule) && rule.kind != FFH_SPARSE_OPT_ADAGRAD && rule.kind != FFH_SPARSE_OPT_ROWWISE_ADAGRAD ? FFH_BF16_MAX_STATEFUL_TABLES : FFH_MAX_TABLES;
 }
 uint64_t FFModel::read_bf16_counter() const {
   if (!bf16_counter) return 0;

@@ -79,6 +79,7 @@ FFConfig::FFConfig() {
   checkpoint_every_epochs = 0;
   adagrad_eps = 1e-10;
   adagrad_initial_accumulator = 0.0;
+  adagrad_rowwise = false;
   memset(&comm, 0, sizeof comm);
   comm.rank = 0;
   comm.world_size = 1;
@@ -202,6 +203,7 @@ void FFConfig::parse_args(char** argv, int argc) {
     }
     if (is("--adagrad-eps")) { adagrad_eps = atof(next()); continue; }
     if (is("--adagrad-initial-accumulator")) { adagrad_initial_accumulator = atof(next()); continue; }
+    if (is("--adagrad-rowwise")) { adagrad_rowwise = eq ? atoi(eq + 1) != 0 : true; continue; }      // (a switch: --adagrad-rowwise or --adagrad-rowwise=1)
     if (is("--device-lr")) { device_lr = true; continue; }
     if (is("--host-lr-schedule")) { host_lr_schedule = true; continue; }
     if (is("--embedding-rounding")) {

@@ -7,7 +7,7 @@
 
 Every flag goes to the C++ driver as it is, this build's own included (--loss mse|bce, --eval-batches N, --eval-only,
 --data-randomize none|total, --arch-interaction-op dcn with --dcn-num-layers L and --dcn-low-rank-dim R,
---optimizer adagrad with --adagrad-eps E and --adagrad-initial-accumulator A: README.md).
+--optimizer adagrad with --adagrad-eps E, --adagrad-initial-accumulator A and --adagrad-rowwise: README.md).
 
 [ref: examples/cpp/DLRM/run_random.sh:3 -- one command, `-ll:gpu N`; src/runtime/cpp_driver.cc:22-44]
 
