@@ -43,7 +43,8 @@ def _run(cmd: list[str]) -> None:
 
 def build_hip(force: bool = False, verbose: bool = False) -> str:
     out = os.path.join(CSRC, "libffhip.so")
-    srcs = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip"))
+    # largest source first: the longest compile (linear_bf16.hip, about as long as everything else on four workers) starts at once
+    srcs = sorted((os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hip")), key=lambda s: (-os.path.getsize(s), s))
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")] + \
            [os.path.join(INCLUDE, f) for f in os.listdir(INCLUDE)]
     if not force and not _newer(out, srcs + hdrs):
