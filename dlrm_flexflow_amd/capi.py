@@ -867,6 +867,97 @@ def rowwise_api(lib: FFHLib) -> RowwiseApi:
     return RowwiseApi(lib)
 
 
+# ---- the fold extension (include/ff_hip_fold.h): small embedding tables folded out of the first top layer's forward GEMM --------------------
+FOLD_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_fold.h")
+
+
+class FoldGroup(C.Structure):
+    """struct ffh_fold_group"""
+    _fields_ = [("e", P), ("lde", L), ("col0", L), ("p", P), ("rows", L)]
+
+
+class FoldSeg(C.Structure):
+    """struct ffh_fold_seg"""
+    _fields_ = [("k0", C.c_int32), ("len", C.c_int32)]
+
+
+_SIGS_FOLD = {
+    "ffh_fold_abi_version": (I, []),
+    "ffh_fold_product": (I, [P, C.POINTER(FoldGroup), I, P, L, I, I, P]),
+    "ffh_fold_gather_add": (I, [P, C.POINTER(EmbTable), I, I, I, L, I, P, L, P]),
+    "ffh_fold_linear_fwd": (I, [P, P, L, P, L, P, P, I, I, L, I, C.POINTER(FoldSeg), I, P, L, P]),
+    "ffh_fold_linear_fwd_plan": (I, [P, P, L, P, L, P, P, I, I, L, C.POINTER(FoldSeg), I, P, L]),
+}
+
+
+def fold_header_symbols(header_path: str = FOLD_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_FOLD_API_LIST X-macro in include/ff_hip_fold.h."""
+    m = re.search(r"#define FFH_FOLD_API_LIST\(X\)(.*?)\n\n", open(header_path).read(), re.S)
+    if not m:
+        raise RuntimeError("FFH_FOLD_API_LIST not found in " + header_path)
+    return re.findall(r"X\((\w+)\)", m.group(1))
+
+
+def fold_header_abi_version(header_path: str = FOLD_HEADER_PATH) -> int:
+    """FFH_FOLD_ABI_VERSION of include/ff_hip_fold.h."""
+    m = re.search(r"#define\s+FFH_FOLD_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_FOLD_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
+class FoldApi:
+    """The fold extension (include/ff_hip_fold.h) of a loaded FFHLib; `fold_api(lib)` builds it or raises."""
+
+    def __init__(self, lib: "FFHLib"):
+        self.base = lib
+        for name, (res, args) in _SIGS_FOLD.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no fold extension ({name} missing; include/ff_hip_fold.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_fold_abi_version()
+        if got != fold_header_abi_version():
+            raise FFHError(f"{lib.path}: fold ABI version {got}, include/ff_hip_fold.h says {fold_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+    @staticmethod
+    def groups(entries) -> "C.Array":
+        """entries: iterable of (e, lde, col0, p, rows)."""
+        entries = list(entries)
+        arr = (FoldGroup * len(entries))()
+        for k, (e, lde, col0, p, rows) in enumerate(entries):
+            arr[k] = FoldGroup(ptr(e), int(lde), int(col0), ptr(p), int(rows))
+        return arr
+
+    @staticmethod
+    def segs(entries) -> "C.Array":
+        """entries: iterable of (k0, len); an empty list gives a one-element array nobody reads (pass nkeep = 0)."""
+        entries = list(entries)
+        arr = (FoldSeg * max(1, len(entries)))()
+        for k, (k0, n) in enumerate(entries):
+            arr[k] = FoldSeg(int(k0), int(n))
+        return arr
+
+    def rc(self, name: str, *args) -> int:
+        """`name(ctx, *args)` of the extension, returning its status code; pointers may be tensors / arrays / ints / None, struct arrays as built above."""
+        sig = _SIGS_FOLD[name][1][1:]
+        if len(args) != len(sig):
+            raise TypeError(f"{name}: expected {len(sig)} args, got {len(args)}")
+        conv = [ptr(a) if t is P else a for a, t in zip(args, sig)]
+        return getattr(self.lib, name)(self.ctx, *conv)
+
+    def call(self, name: str, *args):
+        self.base.check(self.rc(name, *args), name)
+
+
+def fold_api(lib: "FFHLib") -> FoldApi:
+    """The fold entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
+    return FoldApi(lib)
+
+
 _hip_singleton: FFHLib | None = None
 
 

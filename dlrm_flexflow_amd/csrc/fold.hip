@@ -1,0 +1,270 @@
+// fold.hip -- small embedding tables folded out of the forward GEMM of the layer that reads them (include/ff_hip_fold.h).
+//
+// The first top layer of a `cat` DLRM multiplies [batch][in] by [out][in]; the column block of a table with R rows holds copies of at
+// most R distinct rows, so its share of the product is (E W_t^T)[ids]: one small GEMM per table (fold_gemm_kernel, all tables in one
+// launch), one gather-add of rows of the products per sample (fold_gather_add_kernel), and the big GEMM over the columns that are left
+// with the gathered sum as an addend in its epilogue (linear_sk.hip's FOLD instantiation; fold_gemm_kernel where that does not serve).
+//
+// fold_gemm_kernel: C[r][n] = sum over the kept k of A[r][k] W[n][wcol0 + k], both operands k-contiguous, v_mfma_f32_16x16x4_f32 straight
+// from global memory (the operands of the products are a few MB that live in L2; the big layers never come here).  One wave owns 32 rows
+// x 64 columns: W is the MFMA's row operand, A its column operand, so a lane ends up with four consecutive columns of one row and stores
+// 16 bytes.  Lane (c, q) loads 16 bytes at k = 16 j + 4 q of its rows; component e of both operands feeds MFMA e of the group -- any
+// assignment of k to the MFMA's four k-slots is legal as long as both operands agree (the trick of linear_sk.hip's k-contiguous image).
+// Order of the sum per element: segments in list order, groups of 16 ascending, e = 0..3, the MFMA's own order over q: fixed.
+#include "linear_gemm.h"
+
+#include "../../include/ff_hip_fold.h"
+
+using namespace ffh_gemm;
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct FoldGemmGroup { const float* a; int64_t lda; int64_t wcol0; float* c; int64_t ldc; int rows; int tile0; };   // tile0: the group's first wave tile in the launch
+struct FoldGemmArgs {
+  FoldGemmGroup grp[FFH_FOLD_MAX_GROUPS];
+  ffh_fold_seg  seg[FFH_FOLD_MAX_SEGS];
+  const float*  w; int64_t ldw;
+  const float*  bias;            // EPI: per-column bias or null
+  const float*  addend; int64_t ldadd;   // EPI: addend[r][n] or null (one group)
+  int ngroups, nseg, N, act, ntiles;
+};
+static_assert(sizeof(FoldGemmArgs) <= 4096, "kernel arguments");
+
+template <bool EPI>
+__global__ __launch_bounds__(256) void fold_gemm_kernel(const FoldGemmArgs g) {
+  ffh_kernel_prio();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int c = lane & 15, q = lane >> 4;
+  const int wt = (int)blockIdx.x * 4 + wave;
+  if (wt >= g.ntiles) return;
+  int gi = 0;
+  while (gi + 1 < g.ngroups && g.grp[gi + 1].tile0 <= wt) gi++;       // uniform
+  const FoldGemmGroup G = g.grp[gi];
+  const int ct = g.N / 64, local = wt - G.tile0;
+  const int r0 = (local / ct) * 32, n0 = (local % ct) * 64;
+  const float* ap[2];
+  const float* wp[4];
+#pragma unroll
+  for (int mt = 0; mt < 2; mt++) {
+    int r = r0 + 16 * mt + c;
+    if (r > G.rows - 1) r = G.rows - 1;                                // rows behind the table: any valid row, never stored
+    ap[mt] = G.a + (int64_t)r * G.lda + 4 * q;
+  }
+#pragma unroll
+  for (int nt = 0; nt < 4; nt++) wp[nt] = g.w + (int64_t)(n0 + 16 * nt + c) * g.ldw + G.wcol0 + 4 * q;
+  f32x4 acc[4][2];
+#pragma unroll
+  for (int nt = 0; nt < 4; nt++)
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++) acc[nt][mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int si = 0; si < g.nseg; si++) {
+    const int k0 = g.seg[si].k0, k1 = k0 + g.seg[si].len;
+    for (int k = k0; k < k1; k += 16) {
+      f32x4 a[2], b[4];
+#pragma unroll
+      for (int mt = 0; mt < 2; mt++) a[mt] = *reinterpret_cast<const f32x4*>(ap[mt] + k);
+#pragma unroll
+      for (int nt = 0; nt < 4; nt++) b[nt] = *reinterpret_cast<const f32x4*>(wp[nt] + k);
+#pragma unroll
+      for (int e = 0; e < 4; e++)
+#pragma unroll
+        for (int nt = 0; nt < 4; nt++)
+#pragma unroll
+          for (int mt = 0; mt < 2; mt++) acc[nt][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[nt][e], a[mt][e], acc[nt][mt], 0, 0, 0);
+    }
+  }
+  // lane (c, q): columns n0 + 16 nt + 4 q + {0..3} of row r0 + 16 mt + c
+#pragma unroll
+  for (int mt = 0; mt < 2; mt++) {
+    const int r = r0 + 16 * mt + c;
+    if (r >= G.rows) continue;
+#pragma unroll
+    for (int nt = 0; nt < 4; nt++) {
+      const int n = n0 + 16 * nt + 4 * q;
+      f32x4 v = acc[nt][mt];
+      if constexpr (EPI) {
+        if (g.addend) v += *reinterpret_cast<const f32x4*>(g.addend + (int64_t)r * g.ldadd + n);
+        if (g.bias) v += f32x4{g.bias[n], g.bias[n + 1], g.bias[n + 2], g.bias[n + 3]};
+        if (g.act != FFH_AC_MODE_NONE) { v.x = act_apply(v.x, g.act); v.y = act_apply(v.y, g.act); v.z = act_apply(v.z, g.act); v.w = act_apply(v.w, g.act); }
+      }
+      *reinterpret_cast<f32x4*>(G.c + (int64_t)r * G.ldc + n) = v;
+    }
+  }
+}
+
+// fold_gather_add_kernel: one lane per 16 bytes of S.  The (table, position) pairs are walked four at a time: four ids, then four rows in flight, then
+// the adds in list order.  The rows come out of L2 / the Infinity Cache (the products of all folded tables are a few tens of MB).
+struct FoldGatherTable { const int64_t* idx; const float* p; };
+struct FoldGatherArgs {
+  FoldGatherTable t[FFH_MAX_TABLES];
+  float* S; int64_t ldS;
+  int64_t batch;
+  int ntables, L, out;
+};
+
+__global__ __launch_bounds__(256) void fold_gather_add_kernel(const FoldGatherArgs g) {
+  ffh_kernel_prio();
+  const int nvec = g.out / 4;
+  const int64_t total = g.batch * nvec;
+  const int n = g.ntables * g.L;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+    const int64_t b = i / nvec;
+    const int cv = (int)(i - b * nvec) * 4;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j0 = 0; j0 < n; j0 += 4) {
+      f32x4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int j = j0 + u;
+        if (j < n) {        // uniform
+          const int t = j / g.L, l = j - t * g.L;
+          const int64_t id = g.t[t].idx[b * g.L + l];
+          v[u] = *reinterpret_cast<const f32x4*>(g.t[t].p + id * g.out + cv);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++)
+        if (j0 + u < n) acc = (j0 + u == 0) ? v[u] : acc + v[u];
+    }
+    *reinterpret_cast<f32x4*>(g.S + b * g.ldS + cv) = acc;
+  }
+}
+
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// the checks ffh_fold_linear_fwd and its plan query share; FFH_OK, or the error left in the ctx
+int fold_fwd_check(ffh_ctx* c, const float* x, int64_t ldx, const float* y, int64_t ldy, const float* w, int in, int out, int64_t batch,
+                   const ffh_fold_seg* keep, int nkeep, const float* addend, int64_t ldadd) {
+  FFH_REQUIRE(c, in > 0 && out > 0 && batch >= 0 && ldx >= in && ldy >= out, "fold_linear_fwd: bad dims");
+  FFH_REQUIRE(c, batch == 0 || (x && y && w), "fold_linear_fwd: null pointer");
+  FFH_REQUIRE(c, batch < (1LL << 31), "fold_linear_fwd: batch too large");
+  FFH_REQUIRE(c, nkeep >= 0 && (nkeep == 0 || keep), "fold_linear_fwd: bad segment list");
+  FFH_REQUIRE(c, !addend || ldadd >= out, "fold_linear_fwd: bad addend");
+  int prev = 0;
+  for (int i = 0; i < nkeep; i++) {
+    FFH_REQUIRE(c, keep[i].k0 >= prev && keep[i].len > 0 && (int64_t)keep[i].k0 + keep[i].len <= in, "fold_linear_fwd: segments must ascend inside [0, in_dim)");
+    prev = keep[i].k0 + keep[i].len;
+  }
+  return FFH_OK;
+}
+bool fold_fwd_served(const ffh_ctx* c, const float* x, int64_t ldx, const float* y, int64_t ldy, const float* w, int in, int out,
+                     const ffh_fold_seg* keep, int nkeep, const float* addend, int64_t ldadd) {
+  if (c->math_mode != FFH_MATH_DEFAULT) return false;
+  if (in % FFH_FOLD_KTILE || out % FFH_FOLD_NTILE || nkeep > FFH_FOLD_MAX_SEGS) return false;
+  if (!al16(x) || !al16(y) || !al16(w) || ldx % 4 || ldy % 4 || (addend && (!al16(addend) || ldadd % 4))) return false;
+  for (int i = 0; i < nkeep; i++)
+    if (keep[i].k0 % FFH_FOLD_KTILE || keep[i].len % FFH_FOLD_KTILE) return false;
+  return true;
+}
+// the kept k-tiles as the persistent kernel takes them; false: not whole 64-deep k-tiles / too deep
+bool fold_keep_mask(int in, const ffh_fold_seg* keep, int nkeep, unsigned long long mask[2], int* nk_kept) {
+  mask[0] = mask[1] = 0;
+  *nk_kept = 0;
+  if (in % 64 || in > 128 * 64) return false;
+  const ffh_fold_seg all{0, in};
+  if (nkeep == 0) { keep = &all; nkeep = 1; }
+  for (int i = 0; i < nkeep; i++) {
+    if (keep[i].k0 % 64 || keep[i].len % 64) return false;
+    for (int kt = keep[i].k0 / 64; kt < (keep[i].k0 + keep[i].len) / 64; kt++) { mask[kt >> 6] |= 1ull << (kt & 63); (*nk_kept)++; }
+  }
+  return *nk_kept > 0;
+}
+GemmArgs fold_fwd_gemm(const float* x, int64_t ldx, float* y, int64_t ldy, const float* w, const float* bias, int in, int out, int64_t batch, int act) {
+  GemmArgs g{};
+  g.A = x; g.sAm = ldx; g.sAk = 1;
+  g.B = w; g.sBn = in; g.sBk = 1;
+  g.C = y; g.ldc = ldy; g.bias = bias;
+  g.M = (int)batch; g.N = out; g.K = in;
+  g.epi = EPI_STORE; g.act = act;
+  return g;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ffh_fold_abi_version(void) { return FFH_FOLD_ABI_VERSION; }
+
+int ffh_fold_product(ffh_ctx* c, const ffh_fold_group* groups, int ngroups, const float* w, int64_t ldw, int d, int out, ffh_stream s) {
+  FFH_REQUIRE(c, groups && w && ngroups >= 1 && d > 0 && out > 0 && ldw >= d, "fold_product: bad arguments");
+  if (ngroups > FFH_FOLD_MAX_GROUPS || d % FFH_FOLD_KTILE || out % FFH_FOLD_NTILE || !al16(w) || ldw % 4)
+    return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_product: d a multiple of 16, out_dim a multiple of 64, at most 64 tables, aligned weight");
+  FoldGemmArgs a{};
+  int64_t tiles = 0;
+  for (int i = 0; i < ngroups; i++) {
+    const ffh_fold_group& gr = groups[i];
+    FFH_REQUIRE(c, gr.e && gr.p && gr.rows >= 1 && gr.rows < (1LL << 31) && gr.lde >= d && gr.col0 >= 0 && gr.col0 + d <= ldw, "fold_product: bad group");
+    if (!al16(gr.e) || !al16(gr.p) || gr.lde % 4 || gr.col0 % FFH_FOLD_KTILE) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_product: group not aligned");
+    a.grp[i] = FoldGemmGroup{gr.e, gr.lde, gr.col0, gr.p, (int64_t)out, (int)gr.rows, (int)tiles};
+    tiles += ((gr.rows + 31) / 32) * (out / 64);
+    FFH_REQUIRE(c, tiles < (1LL << 30), "fold_product: too many rows");
+  }
+  a.seg[0] = ffh_fold_seg{0, d};
+  a.w = w; a.ldw = ldw; a.ngroups = ngroups; a.nseg = 1; a.N = out; a.act = FFH_AC_MODE_NONE; a.ntiles = (int)tiles;
+  hipLaunchKernelGGL(fold_gemm_kernel<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, as_stream(s), a);
+  FFH_LAUNCH_CHECK(c, "fold_gemm_kernel (products)");
+  return FFH_OK;
+}
+
+int ffh_fold_gather_add(ffh_ctx* c, const ffh_emb_table* tables, int ntables, int in_dim, int out, int64_t batch, int aggr, float* S, int64_t ldS,
+                        ffh_stream s) {
+  FFH_REQUIRE(c, tables && ntables >= 1 && in_dim >= 1 && out > 0 && batch >= 0 && S && ldS >= out, "fold_gather_add: bad arguments");
+  if (aggr != FFH_AGGR_MODE_SUM) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_gather_add: sum aggregation only");
+  if (ntables > FFH_MAX_TABLES || out % 4 || ldS % 4 || !al16(S)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_gather_add: out_dim and ldS multiples of 4, aligned S, at most 64 tables");
+  FoldGatherArgs a{};
+  for (int t = 0; t < ntables; t++) {
+    FFH_REQUIRE(c, tables[t].idx && tables[t].weight && tables[t].num_entries >= 1, "fold_gather_add: bad table");
+    if (!al16(tables[t].weight)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_gather_add: product not aligned");
+    a.t[t] = FoldGatherTable{tables[t].idx, tables[t].weight};
+  }
+  if (batch == 0) return FFH_OK;
+  a.S = S; a.ldS = ldS; a.batch = batch; a.ntables = ntables; a.L = in_dim; a.out = out;
+  hipLaunchKernelGGL(fold_gather_add_kernel, dim3(ffh_grid(batch * (out / 4), 256, 4096)), dim3(256), 0, as_stream(s), a);
+  FFH_LAUNCH_CHECK(c, "fold_gather_add_kernel");
+  return FFH_OK;
+}
+
+int ffh_fold_linear_fwd_plan(ffh_ctx* c, const float* x, int64_t ldx, const float* y, int64_t ldy, const float* w, const float* bias, int in, int out,
+                             int64_t batch, const ffh_fold_seg* keep, int nkeep, const float* addend, int64_t ldadd) {
+  const int rc = fold_fwd_check(c, x, ldx, y, ldy, w, in, out, batch, keep, nkeep, addend, ldadd);
+  if (rc != FFH_OK) return rc;
+  if (!fold_fwd_served(c, x, ldx, y, ldy, w, in, out, keep, nkeep, addend, ldadd)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_linear_fwd: shape / alignment / math mode not served");
+  const GemmArgs g = fold_fwd_gemm(x, ldx, const_cast<float*>(y), ldy, w, bias, in, out, batch, FFH_AC_MODE_NONE);
+  unsigned long long mask[2]; int nk = 0;
+  if (batch > 0 && fold_keep_mask(in, keep, nkeep, mask, &nk) && launch_gemm_sk_fold(c, g, mask, nk, addend, ldadd, true, nullptr, "") == 1) return 2;
+  return (batch > 0 && gemm_sk_serves(c, g, SK_FORM_FWD)) ? 0 : 1;
+}
+
+int ffh_fold_linear_fwd(ffh_ctx* c, const float* x, int64_t ldx, float* y, int64_t ldy, const float* w, const float* bias, int in, int out, int64_t batch,
+                        int act, const ffh_fold_seg* keep, int nkeep, const float* addend, int64_t ldadd, ffh_stream s) {
+  if (nkeep == 0 && !addend) return ffh_linear_fwd(c, x, ldx, y, ldy, w, bias, in, out, batch, act, s);
+  const int rc = fold_fwd_check(c, x, ldx, y, ldy, w, in, out, batch, keep, nkeep, addend, ldadd);
+  if (rc != FFH_OK) return rc;
+  if (act != FFH_AC_MODE_NONE && act != FFH_AC_MODE_RELU && act != FFH_AC_MODE_SIGMOID && act != FFH_AC_MODE_GELU)
+    return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_linear_fwd: activation not supported (NONE, RELU, SIGMOID, GELU)");
+  if (!fold_fwd_served(c, x, ldx, y, ldy, w, in, out, keep, nkeep, addend, ldadd)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_linear_fwd: shape / alignment / math mode not served");
+  ffh_route_clear(c);
+  if (batch == 0) return FFH_OK;
+  const GemmArgs g = fold_fwd_gemm(x, ldx, y, ldy, w, bias, in, out, batch, act);
+  unsigned long long mask[2]; int nk = 0;
+  if (fold_keep_mask(in, keep, nkeep, mask, &nk) && (!bias || al16(bias))) {
+    const int r = launch_gemm_sk_fold(c, g, mask, nk, addend, ldadd, false, s, "fold_linear_fwd gemm");
+    if (r != 0) return r < 0 ? r : FFH_OK;
+  }
+  FoldGemmArgs a{};
+  a.grp[0] = FoldGemmGroup{x, ldx, 0, y, ldy, (int)batch, 0};
+  if (nkeep == 0) { a.seg[0] = ffh_fold_seg{0, in}; a.nseg = 1; }
+  else { for (int i = 0; i < nkeep; i++) a.seg[i] = keep[i]; a.nseg = nkeep; }
+  const int64_t tiles = ((batch + 31) / 32) * (out / 64);
+  FFH_REQUIRE(c, tiles < (1LL << 30), "fold_linear_fwd: too many tiles");
+  a.w = w; a.ldw = in; a.bias = bias; a.addend = addend; a.ldadd = ldadd; a.ngroups = 1; a.N = out; a.act = act; a.ntiles = (int)tiles;
+  hipLaunchKernelGGL(fold_gemm_kernel<true>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, as_stream(s), a);
+  FFH_LAUNCH_CHECK(c, "fold_gemm_kernel (forward)");
+  ffh_route_add(c, "fold_linear_fwd gemm|mfma_32x64x16");
+  return FFH_OK;
+}
+
+}  // extern "C"

@@ -107,5 +107,9 @@ void launch_dw_tile_reduce(const float* slots, float* C, int64_t ldc, int M, int
 enum { SK_FORM_FWD = 0, SK_FORM_DX = 1, SK_FORM_DW = 2 };
 bool gemm_sk_serves(const ffh_ctx* c, const GemmArgs& g, int form);                                   // shape / alignment / mode check only
 int launch_gemm_sk(ffh_ctx* c, const GemmArgs& g, int form, ffh_stream s, const char* name);           // 1 launched, 0 not served, < 0 error
+// ... the forward form over the kept 64-deep k-tiles of x and w only (bit kt of keep[kt / 64]; nk_kept of them) with an optional addend
+// read in the epilogue (include/ff_hip_fold.h); g describes the whole layer.  dry: decide only (1: would launch)
+int launch_gemm_sk_fold(ffh_ctx* c, const GemmArgs& g, const unsigned long long keep[2], int nk_kept, const float* addend, int64_t ldadd, bool dry,
+                        ffh_stream s, const char* name);
 
 }  // namespace ffh_gemm

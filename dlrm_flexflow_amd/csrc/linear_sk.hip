@@ -80,6 +80,17 @@ struct SkArgs {
   unsigned* sk_cnt;
 };
 
+// FOLD (include/ff_hip_fold.h, ffh_fold_linear_fwd): the forward form over the KEPT k-tiles only -- bit kt of keep[kt / 64] says that the
+// k-tile at columns [64 kt, 64 kt + 64) of x and w takes part; the operand stream steps from one kept k-tile to the next (scalar bit
+// scans: no memory, nothing per lane), the loop runs nk_kept k-tiles per output tile -- and an optional addend[m][n], read in the
+// epilogue in front of the bias (the way the data gradient reads its mask).  Its own argument block: the other instantiations keep theirs.
+struct SkArgsFold : SkArgs {
+  unsigned long long keep[2];
+  unsigned           nk_kept;
+  const float*       addend;
+  int64_t            ldadd;
+};
+
 template <int... I, class F>
 __device__ __forceinline__ void sk_static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N_, class F>
@@ -108,8 +119,9 @@ constexpr int SK_EP_WAVE = SK_EP_ROWS * SK_EP_LD * 4;     // bytes per wave
 // of the next tile) last, so the head usually is the last to arrive and its own part never leaves its registers.  Cross-workgroup
 // values travel as agent-scope relaxed atomics (sc1: written through / read behind the per-XCD L2s), ordered by completion (vmcnt
 // + barrier before the counter add; the loads behind the returned add + a barrier), as in embedding.hip's folds.
-template <bool AKR, bool BKR, int EPI, bool DB = false, bool SPLIT = false, int TMW = 4>
-__global__ __launch_bounds__(256, 1) void gemm_sk_kernel(const SkArgs g) {
+template <bool AKR, bool BKR, int EPI, bool DB = false, bool SPLIT = false, int TMW = 4, bool FOLD = false>
+__global__ __launch_bounds__(256, 1) void gemm_sk_kernel(const std::conditional_t<FOLD, SkArgsFold, SkArgs> g) {
+  static_assert(!FOLD || (EPI == SK_EPI_FWD && !SPLIT && !DB && TMW == 4), "kept k-tiles + addend: the whole-tile forward form");
   static_assert(!DB || (EPI == SK_EPI_DW_ATOMIC && AKR), "the bias gradient rides on the weight-gradient form");
   static_assert(!SPLIT || EPI != SK_EPI_DW_ATOMIC, "the weight gradient meets by atomics");
   static_assert(TMW == 4 || (TMW == 2 && !AKR && EPI != SK_EPI_DW_ATOMIC), "64-row tiles: forward and data gradient (A k-contiguous)");
@@ -146,7 +158,25 @@ __global__ __launch_bounds__(256, 1) void gemm_sk_kernel(const SkArgs g) {
 
   // ---- this workgroup's share of the (tile, k-tile) iteration space ----
   const unsigned nbx = (unsigned)(g.N / SK_BN), nby = (unsigned)(g.M / BM), ntiles = nbx * nby;
-  const unsigned nk = (unsigned)(g.K / SK_BK);
+  unsigned nk = (unsigned)(g.K / SK_BK);
+  if constexpr (FOLD) nk = g.nk_kept;
+  // FOLD: the first kept k-tile, and the kept k-tile behind p (behind the last one: p + 1 -- never loaded, place() comes first)
+  auto first_kept = [&]() -> unsigned {
+    if constexpr (FOLD) return g.keep[0] ? (unsigned)__builtin_ctzll(g.keep[0]) : 64u + (unsigned)__builtin_ctzll(g.keep[1]);
+    else return 0u;
+  };
+  auto next_kept = [&](unsigned p) -> unsigned {
+    if constexpr (FOLD) {
+      p++;
+      if (p < 64u) {
+        const unsigned long long m = g.keep[0] >> p;
+        if (m) return p + (unsigned)__builtin_ctzll(m);
+        p = 64u;
+      }
+      const unsigned long long m = p < 128u ? g.keep[1] >> (p - 64u) : 0ull;
+      return m ? p + (unsigned)__builtin_ctzll(m) : p;
+    } else return p + 1u;
+  };
   const unsigned G = gridDim.x, w = blockIdx.x;
   const unsigned total_it = ntiles * nk;                  // < 2^32 (the host checks)
   const unsigned wperm = (w & 7u) * (G >> 3) + (w >> 3);  // G is a multiple of 8
@@ -163,7 +193,7 @@ __global__ __launch_bounds__(256, 1) void gemm_sk_kernel(const SkArgs g) {
   const unsigned n_it = it_e - it_b;
   if (n_it == 0) return;
 
-  struct Cursor { unsigned seq, kt, m0, n0, offA, offB; };   // seq: index of the tile in this workgroup's sequence
+  struct Cursor { unsigned seq, kt, m0, n0, offA, offB, kp; };   // seq: index of the tile in this workgroup's sequence; kp (FOLD): the k-tile's place in the operands
   auto place = [&](Cursor& c) {      // tile coordinates and operand offsets of (c.seq, c.kt)
     unsigned lin;
     if (STREAMK) lin = it_b / nk + c.seq;
@@ -171,15 +201,17 @@ __global__ __launch_bounds__(256, 1) void gemm_sk_kernel(const SkArgs g) {
     if (lin >= ntiles) lin = ntiles - 1;                  // run-ahead loads past the end of the share: any valid tile
     const unsigned by = lin / nbx, bx = lin - by * nbx;
     c.m0 = by * BM; c.n0 = bx * SK_BN;
-    c.offA = (AKR ? c.m0 * 4u : (unsigned)(c.m0 * g.lda * 4)) + c.kt * kadvA;
-    c.offB = (BKR ? c.n0 * 4u : (unsigned)(c.n0 * g.ldb * 4)) + c.kt * kadvB;
+    c.kp = FOLD ? first_kept() : c.kt;                   // (FOLD: whole tiles, c.kt == 0 here)
+    c.offA = (AKR ? c.m0 * 4u : (unsigned)(c.m0 * g.lda * 4)) + c.kp * kadvA;
+    c.offB = (BKR ? c.n0 * 4u : (unsigned)(c.n0 * g.ldb * 4)) + c.kp * kadvB;
   };
   auto advance = [&](Cursor& c) {
     c.kt++;
     if (c.kt == nk) { c.kt = 0; c.seq++; place(c); }
+    else if constexpr (FOLD) { const unsigned np = next_kept(c.kp), d = np - c.kp; c.offA += d * kadvA; c.offB += d * kadvB; c.kp = np; }
     else { c.offA += kadvA; c.offB += kadvB; }
   };
-  Cursor ld{0, STREAMK ? it_b % nk : 0u, 0, 0, 0, 0}, cp = ld;
+  Cursor ld{0, STREAMK ? it_b % nk : 0u, 0, 0, 0, 0, 0}, cp = ld;
   place(ld); place(cp);
 
   u32x4 P[NP];
@@ -352,6 +384,21 @@ __global__ __launch_bounds__(256, 1) void gemm_sk_kernel(const SkArgs g) {
         if (!cvec) { cd1 = g.colmap[nn + 1]; cd2 = g.colmap[nn + 2]; }
       }
       f32x4 mk[TMW][4], cold[TMW][4];
+      f32x4 sadd[TMW][4];        // FOLD: the addend's 16 row groups, fetched before the first store like the mask below
+      bool has_add = false;
+      if constexpr (FOLD) {
+        has_add = g.addend != nullptr;      // uniform
+        if (has_add) {
+#pragma unroll
+          for (int tm = 0; tm < TMW; tm++)
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+              const int mm = (int)cp.m0 + 16 * TMW * wy + TMW * (4 * q + i) + tm;
+              sadd[tm][i] = *reinterpret_cast<const f32x4*>(g.addend + (int64_t)mm * g.ldadd + nn);
+            }
+        }
+      }
+      (void)sadd; (void)has_add;
       f32x4 csum = f32x4{0.f, 0.f, 0.f, 0.f};     // DX_STORE with g.colsum: this lane's four columns summed over its 16 rows
       (void)csum;
       if constexpr (EPI == SK_EPI_DX_STORE || EPI == SK_EPI_DX_ADD) {
@@ -376,6 +423,7 @@ __global__ __launch_bounds__(256, 1) void gemm_sk_kernel(const SkArgs g) {
             // which memory-side float atomics run at their full rate; 4-byte pieces 16 bytes apart run ~10x slower)
             (void)cptr; (void)v;          // below: 16 rows at a time
           } else if constexpr (EPI == SK_EPI_FWD) {
+            if constexpr (FOLD) { if (has_add) v += sadd[tm][i]; }
             v += bv;
             // ReLU / none without act_apply's chain of (uniform) branches per element: 64 elements x 3 branches per lane and tile were
             // ~2 us of every tile with nothing else to run on the SIMD; same values (v > 0 ? v : 0)
@@ -590,6 +638,43 @@ int launch_gemm_sk(ffh_ctx* c, const GemmArgs& g, int form, ffh_stream s, const 
     if (e != hipSuccess) return ffh_fail_hip(c, e, name);
   }
   { char tok[96]; snprintf(tok, sizeof tok, "%s|sk_%dx128x64%s%s%s|wgs=%d", name, 32 * p.tmw, g.colmap ? "|colmap" : "", p.split ? "|streamk" : "", a.colsum ? "|colsum" : "", G); ffh_route_add(c, tok); }
+  return 1;
+}
+
+// The forward form over kept k-tiles (+ addend): g describes the WHOLE layer (K = in_dim); keep / nk_kept as in SkArgsFold.  Served where the
+// plain forward of a layer of depth 64 nk_kept would run whole tiles on 128-row tiles.  dry: decide only.  1: launched (dry: would be),
+// 0: not this kernel's shape (nothing launched), < 0: error
+int launch_gemm_sk_fold(ffh_ctx* c, const GemmArgs& g, const unsigned long long keep[2], int nk_kept, const float* addend, int64_t ldadd, bool dry,
+                        ffh_stream s, const char* name) {
+  if (g.K % SK_BK || g.K > 128 * SK_BK || nk_kept < 1 || nk_kept > g.K / SK_BK) return 0;
+  if (addend && !sk_aligned(addend, ldadd)) return 0;
+  GemmArgs gk = g;
+  gk.K = nk_kept * SK_BK;
+  SkPlan p{};
+  if (!sk_plan(c, gk, SK_FORM_FWD, p) || p.split || p.tmw != 4) return 0;
+  const int64_t a_bytes = ((int64_t)(g.M - 1) * p.lda + g.K) * 4, b_bytes = ((int64_t)(g.N - 1) * p.ldb + g.K) * 4;
+  if (a_bytes >= (1LL << 32) || b_bytes >= (1LL << 32)) return 0;
+  if (dry) return 1;
+  SkArgsFold a{};
+  a.A = g.A; a.B = g.B; a.C = g.C; a.bias = g.bias;
+  a.lda = p.lda; a.ldb = p.ldb; a.ldc = g.ldc;
+  a.M = g.M; a.N = g.N; a.K = g.K; a.act = g.act;
+  a.a_bytes = (unsigned)a_bytes; a.b_bytes = (unsigned)b_bytes;
+  a.bias_bytes = g.bias ? (unsigned)g.N * 4u : 0u;
+  a.keep[0] = keep[0]; a.keep[1] = keep[1]; a.nk_kept = (unsigned)nk_kept; a.addend = addend; a.ldadd = ldadd;
+  {
+    auto kern = gemm_sk_kernel<false, false, SK_EPI_FWD, false, false, 4, true>;
+    constexpr int LDSB = 2 * SK_LDS_KC;
+    static std::atomic<signed char> ok[64];      // as in launch_gemm_sk: the LDS attribute once per (kernel, device)
+    const int dev = c->device & 63;
+    if (ok[dev].load(std::memory_order_acquire) == 0) ok[dev].store(sk_set_lds(kern, LDSB) ? 1 : -1, std::memory_order_release);
+    if (ok[dev].load(std::memory_order_acquire) < 0) return 0;
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.G), dim3(256), LDSB, as_stream(s), a);
+    const hipError_t e = hipGetLastError();
+    if (e == hipErrorInvalidValue || e == hipErrorInvalidConfiguration || e == hipErrorLaunchOutOfResources || e == hipErrorSharedObjectInitFailed) return 0;
+    if (e != hipSuccess) return ffh_fail_hip(c, e, name);
+  }
+  { char tok[96]; snprintf(tok, sizeof tok, "%s|sk_128x128x64|kept=%d/%d%s|wgs=%d", name, nk_kept, g.K / SK_BK, addend ? "|addend" : "", p.G); ffh_route_add(c, tok); }
   return 1;
 }
 

@@ -188,6 +188,23 @@ const KernelApi* load_kernel_api(const std::string& path_in) {
     }
     api->rowwise = b;
   }
+  // the fold extension (include/ff_hip_fold.h): the same rule
+  if (dlsym(h, "ffh_fold_abi_version")) {
+    KernelApiFold* b = new KernelApiFold();
+#define FFH_LOAD(name)                                                        \
+  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
+  if (!b->name) {                                                             \
+    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_fold.h: %s is missing\n", path.c_str(), #name);   \
+    abort();                                                                  \
+  }
+    FFH_FOLD_API_LIST(FFH_LOAD)
+#undef FFH_LOAD
+    if (b->ffh_fold_abi_version() != FFH_FOLD_ABI_VERSION) {
+      fprintf(stderr, "FATAL: %s has fold ABI version %d, expected %d\n", path.c_str(), b->ffh_fold_abi_version(), FFH_FOLD_ABI_VERSION);
+      abort();
+    }
+    api->fold = b;
+  }
   if (path_in.empty() && g_env_override)
     fprintf(stderr, "[DLRM] FFH_BACKEND_LIB: kernel library %s (%s)\n", path.c_str(), api->ffh_backend_name());
   cache[path] = api;

@@ -12,6 +12,7 @@
 #include "../../include/ff_hip_digest.h"
 #include "../../include/ff_hip_adagrad.h"
 #include "../../include/ff_hip_rowwise.h"
+#include "../../include/ff_hip_fold.h"
 
 // The optional bf16-table extension (include/ff_hip_bf16.h): all of its list or none of it.
 struct KernelApiBf16 {
@@ -69,6 +70,13 @@ struct KernelApiRowwise {
 #undef FFH_DECL
 };
 
+// The optional fold extension (include/ff_hip_fold.h: small embedding tables folded out of the first top layer's forward GEMM).
+struct KernelApiFold {
+#define FFH_DECL(name) decltype(&::name) name;
+  FFH_FOLD_API_LIST(FFH_DECL)
+#undef FFH_DECL
+};
+
 struct KernelApi {
 #define FFH_DECL(name) decltype(&::name) name;
   FFH_API_LIST(FFH_DECL)
@@ -81,6 +89,7 @@ struct KernelApi {
   const KernelApiDigest* digest = nullptr;   // likewise for include/ff_hip_digest.h (absent: the host layer computes the same digest from the bytes it copies)
   const KernelApiAdagrad* adagrad = nullptr; // likewise for include/ff_hip_adagrad.h
   const KernelApiRowwise* rowwise = nullptr; // likewise for include/ff_hip_rowwise.h
+  const KernelApiFold* fold = nullptr;       // likewise for include/ff_hip_fold.h (absent: no table is folded, the step is the one of before)
   void* handle;
   std::string path;
   bool overridden = false;      // chosen by --backend or $FFH_BACKEND_LIB rather than the product default: the driver says so on its THROUGHPUT line

@@ -31,6 +31,7 @@
 #include "../../include/ff_hip_cross.h"
 #include "../../include/ff_hip_adagrad.h"
 #include "../../include/ff_hip_rowwise.h"
+#include "../../include/ff_hip_fold.h"
 #include "ffcomm.h"
 
 // ---- enums: identical values to [ref: include/ffconst.h:4-57] -------------------------------
@@ -144,6 +145,8 @@ class FFConfig {
                                // measured on the trace's first calls, one GPU (--adaptive-replay): on this runtime the replay of a two-stream step costs a
                                // small model more than its launches (Kaggle shape: 210 vs 170 us).  -1 = not given: the FFModel API replays (1), the DLRM
                                // driver's timed loop adapts (0)
+  bool fold_small_tables;      // small embedding tables folded out of the first top layer's forward GEMM (include/ff_hip_fold.h; A/B: --no-fold-small-tables)
+  int64_t fold_max_rows;       // ... tables of at most this many rows (--fold-max-rows N)
   bool mlp_chain;              // a run of narrow Linear layers (every width <= 512) as one launch forward, two backward (ffh_mlp_chain_fwd / _bwd; A/B: --no-mlp-chain)
   int64_t mlp_chain_max_batch; // ... for at most this many samples per GPU (--mlp-chain-max-batch N)
   int64_t mlp_chain_fwd_max_batch;   // ... and up to this many (--mlp-chain-fwd-max-batch N)
@@ -737,6 +740,23 @@ class FFModel {
   void note_weight_write(const void* p) const;
   mutable bool bwd_alltoall_issued = false;   // this step's backward all-to-all has been enqueued (FFModel::issue_grad_buckets: a shared channel holds the buckets until then)
   int n_twin_regions = 0;
+  // Small tables folded out of the forward GEMM of the Linear that reads them through a feature Concat (include/ff_hip_fold.h; DESIGN
+  // section 18): that layer's forward is   products P_t = E_t W_t^T  ->  gather-add S = sum_t P_t[ids_t]  ->  GEMM over the kept columns + S.
+  struct FoldRoute {
+    Linear* layer = nullptr;               // null: nothing is folded (the step of before)
+    std::vector<Embedding*> tables;        // the folded tables, in the order of their columns
+    std::vector<ffh_fold_group> groups;    // ffh_fold_product's list
+    std::vector<ffh_emb_table> gather;     // ffh_fold_gather_add's list
+    std::vector<ffh_fold_seg> keep;        // the column runs of the layer's input the GEMM keeps
+    float* P = nullptr;                    // [sum of R_t][out] products
+    float* S = nullptr;                    // [local batch][out] gathered sum
+  } fold;
+  ffh_event ev_fold_w = nullptr;           // recorded on `stream` at the top of forward(): the optimizer of the step before has written W
+  ffh_event ev_fold_done = nullptr;        // recorded on the side stream behind the gather-add
+  mutable bool fold_w_recorded = false, fold_on_side = false;
+  void plan_fold();                        // allocate(): the route conditions and the buffers
+  void fold_products_and_sum(ffh_stream s, ffh_ctx* cx) const;
+  void fold_linear_forward(const Linear* li) const;
   int z_reader_layer;           // the lowest-index Linear that reads a Concat output the tables are gathered into (-1: unknown): behind ITS
                                 // backward no forked weight-gradient GEMM reads that buffer any more, so the next gather may overwrite it
   ffh_event ev_z_free;          // recorded on dw_stream behind that layer's backward

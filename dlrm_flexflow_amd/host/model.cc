@@ -405,6 +405,9 @@ FFModel::~FFModel() {
   api->ffh_event_destroy(ctx, ev_grad_ready); api->ffh_event_destroy(ctx, ev_update_done);
   api->ffh_event_destroy(ctx, ev_dw_done);
   api->ffh_event_destroy(ctx, ev_z_free);
+  if (ev_fold_w) api->ffh_event_destroy(ctx, ev_fold_w);
+  if (ev_fold_done) api->ffh_event_destroy(ctx, ev_fold_done);
+  for (void* p : {(void*)fold.P, (void*)fold.S}) if (p) api->ffh_free(ctx, p);
   for (auto& kv : trace_tune) for (ffh_event& e : kv.second.ev) if (e) { api->ffh_event_destroy(ctx, e); e = nullptr; }
   for (ffh_event& e : probe_ev) if (e) { api->ffh_event_destroy(ctx, e); e = nullptr; }
   api->ffh_stream_destroy(ctx, stream); api->ffh_stream_destroy(ctx, side_stream); api->ffh_stream_destroy(ctx, dw_stream); api->ffh_stream_destroy(ctx, ar_stream);
@@ -550,6 +553,7 @@ void Linear::forward(const FFModel& ff) {
     if (rc != FFH_ERR_UNSUPPORTED) ff.check(rc, name);
     pair_upper = nullptr;                                          // not a shape the pair launch serves
   }
+  if (ff.fold.layer == this) { ff.fold_linear_forward(this); return; }      // the small tables' columns as a gathered sum (allocate(), step 8)
   // (in_padded: the layer as the kernel library sees it -- see allocate(), step 4a; equal to in_channels unless the input was padded)
   ff.check(ff.api->ffh_linear_fwd(ff.ctx, (const float*)x.impl->ptr, x.impl->ld, (float*)y.impl->ptr, y.impl->ld,
                                   (const float*)weights[0].impl->ptr, use_bias ? (const float*)weights[1].impl->ptr : nullptr,

@@ -1028,7 +1028,85 @@ void FFModel::allocate() {
       if (converts(li->chain_fwd)) li->chain_fwd.clear();
       if (converts(li->chain_bwd)) li->chain_bwd.clear();
     }
+  plan_fold();
   check(api->ffh_stream_sync(ctx, stream), "allocate sync");
+}
+
+// ---- 8. small tables folded out of the first top layer's forward GEMM (include/ff_hip_fold.h) ----------------------
+// The layer reads [batch][in] through a feature Concat the tables are gathered into; a table of R rows contributes copies of at most R
+// distinct rows to its column block, so its share of the product is (E W_t^T)[ids].  A table is folded when: it feeds that Concat
+// directly and in place, sum aggregation, fp32 rows held whole on this rank with no exchange path, exact fp32 math, its column offset
+// and width whole k-tiles of the library, R <= --fold-max-rows and 4 R <= 3 batch (the product must stay cheaper than what it
+// replaces), and the library has the extension and serves the layer (ffh_fold_linear_fwd_plan).  Everything else -- the gather into
+// the Concat, the layer's backward, the table update -- is the step of before.
+void FFModel::plan_fold() {
+  fold = FoldRoute();
+  if (!config.fold_small_tables || !api->fold || exchange || world_size != 1 || embeddings.empty()) return;
+  if (config.allow_tensor_op_math_conversion || config.fp32_split_bf16x3) return;
+  for (Op* op : layers) {
+    Linear* li = dynamic_cast<Linear*>(op);
+    if (!li) continue;
+    const Tensor& x = li->inputs[0];
+    Concat* c = x.owner_op ? dynamic_cast<Concat*>(const_cast<Op*>(x.owner_op)) : nullptr;
+    if (!c || c->axis != 0 || !x.impl->pieces.empty() || !x.impl->ptr) continue;
+    if (li->in_padded != li->in_channels || li->pair_upper || li->out_channels % FFH_FOLD_NTILE || li->in_channels % FFH_FOLD_KTILE) continue;
+    if (!li->chain_fwd.empty() && mlp_chain_usable(local_rows(li->outputs[0], this), true)) continue;      // the chain launch runs this layer
+    FoldRoute r;
+    int64_t off = 0, prows = 0;
+    int32_t kept_from = 0;
+    for (int i = 0; i < c->numInputs; i++) {
+      const Tensor& in = c->inputs[i];
+      const int64_t w = in.adim[0];
+      Embedding* e = in.owner_op && in.owner_op->op_type == OP_EMBEDDING ? static_cast<Embedding*>(const_cast<Op*>(in.owner_op)) : nullptr;
+      const bool in_place = in.impl->pieces.empty() && in.impl->ptr == (float*)x.impl->ptr + off && in.impl->ld == x.impl->ld;
+      const bool ok = e && in_place && e->aggr == AGGR_MODE_SUM && !e->replicated && !e->row_sharded && !e->column_sharded && !e->bf16_weights() &&
+                      e->held_here(rank) && e->out_channels == w && w % FFH_FOLD_KTILE == 0 && off % FFH_FOLD_KTILE == 0 &&
+                      e->num_entries <= config.fold_max_rows && 4 * (int64_t)e->num_entries <= 3 * local_batch &&
+                      (r.tables.empty() || (e->out_channels == r.tables[0]->out_channels && e->inputs[0].adim[0] == r.tables[0]->inputs[0].adim[0])) &&
+                      (int)r.tables.size() < FFH_FOLD_MAX_GROUPS;
+      if (ok) {
+        if (off > kept_from) r.keep.push_back(ffh_fold_seg{kept_from, (int32_t)(off - kept_from)});
+        kept_from = (int32_t)(off + w);
+        r.tables.push_back(e);
+        prows += e->num_entries;
+      }
+      off += w;
+    }
+    if (off != li->in_channels || r.tables.empty()) continue;
+    if (off > kept_from) r.keep.push_back(ffh_fold_seg{kept_from, (int32_t)(off - kept_from)});
+    if (r.keep.empty() || r.keep.size() > (size_t)FFH_FOLD_MAX_SEGS) continue;      // (every column folded: the bottom MLP's block always stays in a DLRM)
+    const int out = li->out_channels;
+    r.P = (float*)dmalloc((size_t)prows * out * 4);
+    r.S = (float*)dmalloc((size_t)local_batch * out * 4);
+    const int plan = api->fold->ffh_fold_linear_fwd_plan(ctx, (const float*)x.impl->ptr, x.impl->ld, (const float*)li->outputs[0].impl->ptr, li->outputs[0].impl->ld,
+                                                         (const float*)li->weights[0].impl->ptr, li->use_bias ? (const float*)li->weights[1].impl->ptr : nullptr,
+                                                         li->in_padded, out, local_rows(li->outputs[0], this), r.keep.data(), (int)r.keep.size(), r.S, out);
+    if (plan < 1) { api->ffh_free(ctx, r.P); api->ffh_free(ctx, r.S); continue; }      // not served, or the whole layer runs a faster kernel than the kept columns would
+    int64_t prow = 0, col = 0;
+    size_t k = 0;
+    for (int i = 0; i < c->numInputs; i++) {
+      const Tensor& in = c->inputs[i];
+      if (k < r.tables.size() && in.owner_op == r.tables[k]) {
+        Embedding* e = r.tables[k++];
+        float* p = r.P + (size_t)prow * out;
+        r.groups.push_back(ffh_fold_group{(const float*)e->weights[0].impl->ptr, (int64_t)e->out_channels, col, p, (int64_t)e->num_entries});
+        ffh_emb_table t;
+        t.idx = (const int64_t*)e->inputs[0].impl->ptr;
+        t.weight = p;
+        t.num_entries = e->num_entries;
+        t.io = nullptr;
+        t.ld = out;
+        r.gather.push_back(t);
+        prow += e->num_entries;
+      }
+      col += in.adim[0];
+    }
+    r.layer = li;
+    fold = r;
+    if (!ev_fold_w) check((config.timing_events ? api->ffh_event_create : api->ffh_event_create_sync)(ctx, &ev_fold_w), "event create");
+    if (!ev_fold_done) check((config.timing_events ? api->ffh_event_create : api->ffh_event_create_sync)(ctx, &ev_fold_done), "event create");
+    return;
+  }
 }
 
 void FFModel::init_layers() {

@@ -40,6 +40,8 @@ FFConfig::FFConfig() {
   attach_events = true;
   fuse_pair = true;
   mlp_chain = true;
+  fold_small_tables = true;
+  fold_max_rows = 7420;      // the measured threshold (2208 and 7420 tried)
   trace_mode = -1;
   bucket_allreduce = -1;
   allreduce_bucket_floats = 1 << 20;
@@ -161,6 +163,8 @@ void FFConfig::parse_args(char** argv, int argc) {
     if (is("--no-attach-event")) { attach_events = false; continue; }
     if (is("--no-fused-pair")) { fuse_pair = false; continue; }
     if (is("--no-mlp-chain")) { mlp_chain = false; continue; }
+    if (is("--no-fold-small-tables")) { fold_small_tables = false; continue; }
+    if (is("--fold-max-rows")) { fold_max_rows = atoll(next()); continue; }
     if (is("--always-replay")) { trace_mode = 1; continue; }
     if (is("--adaptive-replay")) { trace_mode = 0; continue; }
     if (is("--bucket-allreduce")) { bucket_allreduce = 1; continue; }

@@ -45,6 +45,7 @@ void FFModel::forward(int _seq_length) {
   seq_length = _seq_length;
   if (capturing_trace < 0) refresh_weight_twin();      // (a capture: begin_trace() did it on the stream, outside the graph)
   emb_forward_issued = emb_forward_joined = false;
+  fold_w_recorded = fold_on_side = false;
   // gather (+ all-to-all) go to the side stream beside the bottom MLP: the fork point is here (inputs ready)
   if (config.overlap_embedding && !embeddings.empty()) {
     // The side stream already runs behind everything it depends on from earlier steps (the table update is on it);
@@ -57,6 +58,12 @@ void FFModel::forward(int _seq_length) {
     if (fork_recorded) check(api->ffh_event_record(ctx, ev_fork, stream), "fork");
     inputs_dirty = false;
     // start the gather right now unless a host-side collective would stall THIS thread's launches
+    // folded tables: their products read the weights the optimizer of the step before wrote on `stream`.  The gather deliberately does
+    // not wait for that launch (fork_recorded above), so the products get a dependency of their own
+    if (fold.layer && !use_workers()) {
+      check(api->ffh_event_record(ctx, ev_fold_w, stream), "fold: weights ready");
+      fold_w_recorded = true;
+    }
     if (!exchange || config.comm.nonblocking || use_workers()) issue_embedding_forward_on_side_stream();
   }
   for (Op* op : layers) {
@@ -109,6 +116,14 @@ void FFModel::issue_embedding_forward_on_side_stream() const {
     embedding_group_forward(side_stream);
     probe_record(1, side_stream, ctx);
     check(api->ffh_event_record(ctx, ev_join, side_stream), "join");
+    if (fold.layer && fold_w_recorded) {
+      // behind the gather: this stream already stands behind the table update of the step before (it ran here), ev_fold_w adds the
+      // optimizer.  The bottom MLP's forward is the window; what sticks out of it the first top layer waits for (ev_fold_done)
+      check(api->ffh_stream_wait_event(ctx, side_stream, ev_fold_w), "fold: weights ready");
+      fold_products_and_sum(side_stream, ctx);
+      check(api->ffh_event_record(ctx, ev_fold_done, side_stream), "fold: sum ready");
+      fold_on_side = true;
+    }
     if (early_sort_possible(1)) {       // behind the join: nothing waits for it until this step's update
       launch_shard_groups(this, kSortOnly, side_stream, ctx);
       emb_sorted_early = true;
@@ -116,6 +131,27 @@ void FFModel::issue_embedding_forward_on_side_stream() const {
   }
   emb_forward_issued = true;
   emb_forward_joined = false;
+}
+
+void FFModel::fold_products_and_sum(ffh_stream s, ffh_ctx* cx) const {
+  const Linear* li = fold.layer;
+  const Embedding* e0 = fold.tables[0];
+  check(api->fold->ffh_fold_product(cx, fold.groups.data(), (int)fold.groups.size(), (const float*)li->weights[0].impl->ptr, li->in_padded, e0->out_channels,
+                                    li->out_channels, s), "fold_product");
+  check(api->fold->ffh_fold_gather_add(cx, fold.gather.data(), (int)fold.gather.size(), e0->inputs[0].adim[0], li->out_channels, local_batch, FFH_AGGR_MODE_SUM,
+                                       fold.S, li->out_channels, s), "fold_gather_add");
+}
+
+// forward() of the layer the tables are folded out of.  The gather has been joined (the Concat below comes first), so `stream` stands behind
+// this step's tables either way: the sum is waited for where the side stream computed it, and computed right here otherwise
+void FFModel::fold_linear_forward(const Linear* li) const {
+  if (fold_on_side) check(api->ffh_stream_wait_event(ctx, stream, ev_fold_done), "fold: sum ready");
+  else fold_products_and_sum(stream, ctx);
+  const Tensor& x = li->inputs[0];
+  const Tensor& y = li->outputs[0];
+  check(api->fold->ffh_fold_linear_fwd(ctx, (const float*)x.impl->ptr, x.impl->ld, (float*)y.impl->ptr, y.impl->ld, (const float*)li->weights[0].impl->ptr,
+                                       li->use_bias ? (const float*)li->weights[1].impl->ptr : nullptr, li->in_padded, li->out_channels, local_rows(y, this),
+                                       (int)li->activation, fold.keep.data(), (int)fold.keep.size(), fold.S, li->out_channels, stream), li->name);
 }
 
 void FFModel::join_embedding_forward() const {
