@@ -164,10 +164,13 @@ int         ffh_ctx_set_math_mode(ffh_ctx* ctx, int mode);
  * the kernel is bound by bringing 4-byte elements on chip to use 2 of their bytes.  A caller may therefore give an fp32 buffer a
  * bfloat16 twin of the same element layout (same leading dimensions, 2 bytes per element):
  *   ffh_ctx_bf16_mirror_set(ctx, fp32_base, fp32_bytes, bf16_base)   registers [fp32_base, fp32_base + fp32_bytes) -> bf16_base
- *                                                                    (bf16_base NULL: removes the registration); <= 32 regions
+ *                                                                    (bf16_base NULL: removes the registration; an existing
+ *                                                                    fp32_base: replaces its twin); <= 64 regions, the next
+ *                                                                    one is refused with FFH_ERR_UNSUPPORTED
  * From then on, in tensor-op mode only,
  *   producers that write fp32 values into a registered region also write their bf16 roundings (nearest even) into the twin:
- *     ffh_linear_fwd (y), ffh_linear_bwd / _ex (dx), when they run on the bf16 pipe (in_dim, out_dim >= FFH_BF16_MIN_DIM);
+ *     ffh_linear_fwd (y), ffh_linear_bwd / _ex (dx), when they run on the bf16 pipe (in_dim, out_dim >= FFH_BF16_MIN_DIM), and the
+ *     one-launch backward of a narrow layer (out_dim <= 16; ffh_linear_bwd / _ex / _mse: dx) -- no other narrow layer writes a twin;
  *     ffh_embedding_fwd / _multi (out); ffh_sgd_update / _ex and ffh_adam_update (w); ffh_convert_f32_to_bf16 (explicit);
  *   the bf16-pipe GEMMs take an operand from its twin when BOTH operands of the GEMM lie in registered regions.
  * The twin of an element is by construction the value the kernel would have rounded it to, so results are bit-identical with and

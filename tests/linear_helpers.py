@@ -27,9 +27,24 @@ untouched.  The HIP library is held to the header: the map INSTEAD of dx.)
 One deviation from the letter of "ONLY_DX leaves dw and db untouched": with a live Sigmoid the header gives db to the ONLY_DX call ("in-place
 activation gradient + db first") and takes it from the ONLY_DW call; the checker follows the header.
 
+Tensor-op mode (Case.mode = 1, FFH_MATH_TENSOR_OP_BF16; tests/test_linear_bf16_sweep_cpu.py, tests/test_gpu_linear_bf16_sweep.py).  A layer with
+in_dim >= 128 and out_dim >= 128 has both operands of each GEMM rounded to bfloat16, nearest even (rne_bf16: numpy on the bits, written from
+include/ff_hip.h, not from the oracle or a kernel), widened to float64 and summed there: y vs act(rne(x) @ rne(w).T + b), dw vs dw0 + rne(dy').T @
+rne(x), dx vs [dx0 +] (rne(dy') @ rne(w)) [x > 0]; db, the bias, the activations and the dy transform stay fp32 quantities of unrounded values;
+the mass is taken on the rounded operands; the bound is the same one (the header: "against a twin that rounds the same operands the fp32
+summation-order bound of the fp32 mode applies").  A narrower layer keeps the fp32 reference.  Case.twins names the buffers among x w y dy dx
+that get a registered bfloat16 twin (TwinBuf: same layout at 2 bytes per element, SENTINEL16 in padding, offset and tail; an input's twin filled
+by ffh_convert_f32_to_bf16, as a model's producers would): an output's twin is untouched as a whole or, over the whole block and nowhere else,
+the nearest-even rounding of the floats the library stored -- written it must be where the route names the bf16 pipe; an input's twin is
+bit-identical after the call (Case.stale: dy's twin holds NaN and must not be read).  run_fwd / run_bwd set the mode and register the twins, and
+undo both in a finally.  Case.dist: "uniform", "integer" (exact), "ties" (every GEMM operand a bfloat16 plus half an ulp), "wide" (+-20 binades).
+
 Routes.  route_fwd / route_bwd restate the dispatch predicates of the HIP library (sk_plan, plan_glds, the launch_gemm tile choice, the skinny
 and thin conditions) as a function of the CU count; the GPU test asserts ffh_linear_last_route against them, and every edge case names the
-kernel family it is there for (Case.want), which the CPU test asserts of the model at 256 CUs.
+kernel family it is there for (Case.want), which the CPU test asserts of the model at 256 CUs.  In tensor-op mode bf16_gemm restates
+launch_gemm_bf16 (csrc/linear_bf16.hip: the tile, the split count, the twins' conditions) and launch_gemm_bf16_dma's serve conditions
+(csrc/linear_bf16_dma.hip); the split count is part of the expected token except for the LDS-DMA weight gradient, whose cost search is only held
+to its range.
 """
 import ctypes as C
 import re
@@ -42,7 +57,12 @@ from chain_helpers import Buf, HostBackend, TorchBackend, act64, LIPSCHITZ, num_
 NONE, RELU, SIG, GELU = capi.AC_MODE_NONE, capi.AC_MODE_RELU, capi.AC_MODE_SIGMOID, capi.AC_MODE_GELU
 OVERWRITE, ONLY_DW, ONLY_DX, PREMASKED, MASK_BY_X = (capi.LINEAR_DX_OVERWRITE, capi.LINEAR_ONLY_DW, capi.LINEAR_ONLY_DX, capi.LINEAR_DY_PREMASKED,
                                                      capi.LINEAR_DX_MASK_BY_X)
+MATH_BF16 = 1               # FFH_MATH_TENSOR_OP_BF16
 MATH_SPLIT_ALL = 3          # FFH_MATH_FP32_SPLIT_BF16X3_ALL
+BF16_MIN_DIM = 128          # FFH_BF16_MIN_DIM
+DISTS = ("uniform", "integer", "ties", "wide")
+TWIN_NAMES = ("x", "w", "y", "dy", "dx")
+SENTINEL16 = 0x7FDE         # a bfloat16 NaN: a twin's padding read into a GEMM poisons the result
 TABLE_CUS = 256             # the CU count the edge table's shapes were derived for (MI355X)
 
 
@@ -57,8 +77,13 @@ class Case:
 
     def __init__(self, name, kind, in_dim, out_dim, batch, act=NONE, flags=0, seed=0, ldx=None, x_off=0, ldy=None, y_off=0, lddy=None, dy_off=0,
                  lddx=None, dx_off=0, w_off=0, bias=True, bias_off=0, db=True, dx=True, forked=False, det=False, cmap=False, cmap_ncols=None,
-                 colsum=False, colsum_ncols=None, scratch=True, integer=False, want=()):
+                 colsum=False, colsum_ncols=None, scratch=True, integer=False, want=(), mode=0, twins=(), dist=None, stale=()):
         assert kind in ("fwd", "bwd")
+        self._kw = {k: v for k, v in locals().items() if k not in ("self", "__class__")}
+        dist = dist or ("integer" if integer else "uniform")
+        assert dist in DISTS and mode in (0, MATH_BF16) and set(twins) <= set(TWIN_NAMES) and set(stale) <= set(twins)
+        integer = dist == "integer"
+        self.mode, self.twins, self.dist, self.stale = mode, frozenset(twins), dist, frozenset(stale)
         self.name, self.kind, self.in_dim, self.out_dim, self.batch, self.act, self.flags, self.seed = name, kind, int(in_dim), int(out_dim), int(batch), act, flags, seed
         self.ldx, self.x_off = (in_dim if ldx is None else ldx), x_off
         self.ldy, self.y_off = (out_dim if ldy is None else ldy), y_off
@@ -73,11 +98,20 @@ class Case:
     def has(self, flag):
         return bool(self.flags & flag)
 
+    def replace(self, **kw):
+        """The same case with some constructor arguments changed."""
+        return Case(**{**self._kw, **kw})
+
+    @property
+    def bf16_layer(self):
+        """The layer rule of FFH_MATH_TENSOR_OP_BF16 (include/ff_hip.h): both widths >= FFH_BF16_MIN_DIM."""
+        return self.mode == MATH_BF16 and self.in_dim >= BF16_MIN_DIM and self.out_dim >= BF16_MIN_DIM
+
     def __repr__(self):
         return (f"Case({self.name}: {self.kind} B={self.batch} {self.in_dim}->{self.out_dim} act={self.act} flags={self.flags} ldx={self.ldx}+{self.x_off} "
                 f"ldy={self.ldy}+{self.y_off} lddy={self.lddy}+{self.dy_off} lddx={self.lddx}+{self.dx_off} w+{self.w_off} bias={self.bias}+{self.bias_off} "
                 f"db={self.db} dx={self.dx} forked={self.forked} det={self.det} cmap={self.cmap}/{self.cmap_ncols} colsum={self.colsum}/{self.colsum_ncols} "
-                f"scratch={self.scratch} integer={self.integer})")
+                f"scratch={self.scratch} dist={self.dist} mode={self.mode} twins={sorted(self.twins)} stale={sorted(self.stale)})")
 
 
 def make_inputs(case):
@@ -88,6 +122,18 @@ def make_inputs(case):
         assert case.act in (NONE, RELU)
         draw = lambda *shape: rng.integers(-2, 3, shape).astype(np.float64)
         w = draw(o, i)
+    elif case.dist == "ties":
+        # a bfloat16 value plus exactly half a bfloat16 ulp (low 16 bits 0x8000), random sign, exponent of order one: nearest-even, half-up
+        # and truncation give three different roundings (even / odd kept mantissas come equally often)
+        def draw(*shape, e0=126):
+            bits = (rng.integers(0, 2, shape).astype(np.uint32) << 31) | (rng.integers(e0 - 2, e0 + 1, shape).astype(np.uint32) << 23) \
+                | (rng.integers(0, 128, shape).astype(np.uint32) << 16) | np.uint32(0x8000)
+            return bits.view(np.float32).astype(np.float64)
+        w = draw(o, i, e0=126 - int(np.log2(i)) // 2)
+    elif case.dist == "wide":
+        assert case.act in (NONE, RELU)
+        draw = lambda *shape: rng.uniform(-1, 1, shape) * 2.0 ** rng.integers(-20, 21, shape)       # a rounding that carries into the exponent occurs
+        w = draw(o, i) * np.sqrt(3.0 / i)
     else:
         draw = lambda *shape: rng.uniform(-1, 1, shape)
         w = draw(o, i) * np.sqrt(3.0 / i)
@@ -127,12 +173,172 @@ class ColDest(C.Structure):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
+# bfloat16: the rounding of FFH_MATH_TENSOR_OP_BF16 (include/ff_hip.h: "round both operands to bfloat16 (nearest-even)") and the twins
+def rne_bf16_bits(a):
+    """float32 -> the 16 bits of the nearest bfloat16, ties to even, on the bits.  NaN stays NaN (quiet), what lies beyond the largest
+    bfloat16 becomes +-inf (the carry runs into the exponent), denormals and the sign of zero are kept."""
+    u = np.ascontiguousarray(a, np.float32).view(np.uint32)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    r = (u.astype(np.uint64) + 0x7FFF + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint64(16)
+    return np.where(nan, (u >> np.uint32(16)) | np.uint32(0x0040), r.astype(np.uint32)).astype(np.uint16).reshape(np.shape(a))
+
+
+def bf16_to_f32(bits):
+    return (np.asarray(bits, np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+def rne_bf16(a):
+    """float32 -> bfloat16 (nearest even) -> float32."""
+    return bf16_to_f32(rne_bf16_bits(a))
+
+
+def trunc_bf16(a):
+    """A WRONG rounding (the low 16 bits dropped): what the checker has to tell from rne_bf16."""
+    return (np.ascontiguousarray(a, np.float32).view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32).reshape(np.shape(a))
+
+
+def half_away_bf16(a):
+    """A WRONG rounding (ties away from zero)."""
+    u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
+    return ((u + 0x8000) & 0xFFFF0000).astype(np.uint32).view(np.float32).reshape(np.shape(a))
+
+
+# (float32 bits, bfloat16 bits) written by hand, and NaN patterns (quiet, signalling, payload in the low half only): what rne_bf16_bits and
+# ffh_convert_f32_to_bf16 are pinned to
+RNE_TABLE = [
+    (0x3F800000, 0x3F80), (0x3F807FFF, 0x3F80), (0x3F808001, 0x3F81),
+    (0x3F808000, 0x3F80),          # a tie, the kept mantissa even: down
+    (0x3F818000, 0x3F82),          # a tie, the kept mantissa odd: up
+    (0xBF808000, 0xBF80), (0xBF818000, 0xBF82),
+    (0x3FFF8000, 0x4000),          # a tie that carries into the exponent (1.99609375 + half an ulp -> 2.0)
+    (0x3FFFFFFF, 0x4000), (0x007F8000, 0x0080),          # the largest denormals round up to the smallest normal
+    (0x7F7FFFFF, 0x7F80), (0xFF7FFFFF, 0xFF80),          # the largest finite float: +-inf
+    (0x7F7F8000, 0x7F80), (0x7F7F7FFF, 0x7F7F),          # around the largest bfloat16
+    (0x7F800000, 0x7F80), (0xFF800000, 0xFF80),
+    (0x00000001, 0x0000), (0x80000001, 0x8000),          # the smallest denormals: to zero, the sign kept
+    (0x00008000, 0x0000), (0x00008001, 0x0001), (0x00018000, 0x0002), (0x00010000, 0x0001),
+    (0x00000000, 0x0000), (0x80000000, 0x8000)]
+NAN_PATTERNS = [0x7FC00000, 0xFFC00000, 0x7F800001, 0x7FA00000, 0x7F80FFFF, 0xFF800001, 0x7FFFFFFF]
+
+
+class TwinBuf:
+    """The bfloat16 twin of a Buf (ffh_ctx_bf16_mirror_set): the same element layout at 2 bytes per element, so that the twin of the float at p is
+    twin_base + (p - fp32_base) / 2, which is what the library computes from the registered region (the Buf's whole allocation).  Padding, offset
+    and tail hold SENTINEL16; an input's twin is filled over the valid block by ffh_convert_f32_to_bf16 (fill()), an output's stays sentinel."""
+
+    def __init__(self, be, buf):
+        self.be, self.buf, self.valid, self.idx = be, buf, buf.valid, buf.idx
+        flat = np.full(buf.valid.size, SENTINEL16, np.uint16)
+        self.before = flat.copy()
+        self.h = be.upload(flat.view(np.int16))
+        self.host = None
+
+    @property
+    def base(self):
+        return self.be.addr(self.h)
+
+    def fill(self, lib):
+        """What a model's producers leave in the twin of a buffer they wrote: the roundings of the valid block, row by row where it is strided."""
+        b = self.buf
+        runs = [(b.off, b.rows * b.cols)] if b.ld == b.cols or b.rows <= 1 else [(b.off + r * b.ld, b.cols) for r in range(b.rows)]
+        for at, n in runs:
+            if n:
+                lib.check(lib.lib.ffh_convert_f32_to_bf16(lib.ctx, self.base + 2 * at, b.ptr + 4 * (at - b.off), n, None), "ffh_convert_f32_to_bf16")
+        return self
+
+    def poison(self, bits=0x7FC0):
+        """A stale twin: the valid block replaced by bfloat16 NaN."""
+        flat = self.be.download(self.h).view(np.uint16).copy()
+        flat[self.idx] = bits
+        self.h = None
+        self.h = self.be.upload(flat.view(np.int16))
+        return self
+
+    def snapshot(self):
+        self.before = self.be.download(self.h).view(np.uint16).copy()
+        return self
+
+    def fetch(self):
+        self.host = self.be.download(self.h).view(np.uint16)
+        return self
+
+    def untouched(self):
+        return self.host.tobytes() == self.before.tobytes()
+
+    def problems(self, name, stored=None, must_write=False):
+        """An output's twin after the call (stored: the [rows][cols] floats the library left in the fp32 buffer): untouched as a whole, or the
+        nearest-even rounding of `stored` over the whole valid block and nothing else.  stored None: an input's twin, identical to before."""
+        out = []
+        if stored is None:
+            if not self.untouched():
+                out.append(f"{name} twin: an input's twin was modified ({int((self.host != self.before).sum())} elements)")
+            return out
+        if self.untouched():
+            if must_write:
+                out.append(f"{name} twin: not written by a launch on the bf16 pipe")
+            return out
+        pad = np.flatnonzero((self.host != SENTINEL16) & ~self.valid)
+        if pad.size:
+            out.append(f"{name} twin: {pad.size} padding element(s) overwritten, first at flat index {int(pad[0])} (ld {self.buf.ld}, offset {self.buf.off})")
+        want = rne_bf16_bits(stored).ravel()
+        got = self.host[self.idx]
+        isnan = lambda v: (v & 0x7FFF) > 0x7F80
+        bad = np.flatnonzero((got != want) & ~(isnan(got) & isnan(want)))
+        if bad.size:
+            r, c = divmod(int(bad[0]), self.buf.cols)
+            out.append(f"{name} twin: {bad.size} of {got.size} elements are not the nearest-even rounding of the stored float; first at ({r}, {c}): "
+                       f"0x{int(got[bad[0]]):04x}, expected 0x{int(want[bad[0]]):04x}")
+        return out
+
+
+class Twins:
+    """The registrations of one call: made before it, undone whatever happens (the ctx is the whole session's)."""
+
+    def __init__(self, lib, be, case, bufs, inputs):
+        self.lib, self.t, self.inputs, self.regs = lib, {}, set(inputs), []
+        try:
+            for name in TWIN_NAMES:
+                buf = bufs.get(name)
+                if name not in case.twins or buf is None:
+                    continue
+                tw = self.t[name] = TwinBuf(be, buf)
+                base = be.addr(buf.h)
+                assert base % 16 == 0 and tw.base % 16 == 0, "ffh_ctx_bf16_mirror_set wants 16-byte aligned bases"
+                lib.check(lib.lib.ffh_ctx_bf16_mirror_set(lib.ctx, base, 4 * buf.valid.size, tw.base), "ffh_ctx_bf16_mirror_set")
+                self.regs.append(base)
+                if name in self.inputs:
+                    tw.fill(lib)
+            be.sync()
+            for name, tw in self.t.items():
+                if name in case.stale:
+                    old = tw.base
+                    tw.poison()
+                    assert tw.base % 16 == 0
+                    if tw.base != old:
+                        lib.check(lib.lib.ffh_ctx_bf16_mirror_set(lib.ctx, be.addr(tw.buf.h), 4 * tw.buf.valid.size, tw.base), "ffh_ctx_bf16_mirror_set")
+                tw.snapshot()
+        except BaseException:
+            self.release()
+            raise
+
+    def release(self):
+        for base in self.regs:
+            self.lib.lib.ffh_ctx_bf16_mirror_set(self.lib.ctx, base, 4, None)
+        self.regs = []
+
+
+def _set_mode(lib, mode):
+    lib.check(lib.lib.ffh_ctx_set_math_mode(lib.ctx, mode), "ffh_ctx_set_math_mode")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
 # the calls
 class Result:
     def __init__(self, case, inp, rc, route, **kw):
         self.case, self.inp, self.rc, self.route = case, inp, rc, route
         self.scatter_used = self.colsum_used = 0
         self.is_hip = False
+        self.twins, self.twin_inputs = {}, ()
         self.__dict__.update(kw)
 
 
@@ -165,13 +371,21 @@ def run_fwd(lib, be, case, inp=None):
     Y = Buf(be, B, o, case.ldy, case.y_off)
     s = None if case.scratch else _stream(lib, "bare")
     be.sync()
-    rc = lib.lib.ffh_linear_fwd(lib.ctx, X.ptr, case.ldx, Y.ptr, case.ldy, W.ptr, Bi.ptr if Bi else None, i, o, B, case.act, s)
-    route = (lib.lib.ffh_linear_last_route(lib.ctx) or b"").decode()
-    _finish(lib, be, [s])
+    tw = None
+    try:
+        _set_mode(lib, case.mode)
+        tw = Twins(lib, be, case, dict(x=X, w=W, y=Y), ("x", "w"))
+        rc = lib.lib.ffh_linear_fwd(lib.ctx, X.ptr, case.ldx, Y.ptr, case.ldy, W.ptr, Bi.ptr if Bi else None, i, o, B, case.act, s)
+        route = (lib.lib.ffh_linear_last_route(lib.ctx) or b"").decode()
+        _finish(lib, be, [s])
+    finally:
+        if tw:
+            tw.release()
+        _set_mode(lib, 0)
     inputs = [("x", X), ("w", W)] + ([("bias", Bi)] if Bi else [])
-    for _, b in inputs + [("y", Y)]:
+    for _, b in inputs + [("y", Y)] + list(tw.t.items()):
         b.fetch()
-    return Result(case, inp, rc, route, Y=Y, outputs=[("y", Y)], inputs=inputs)
+    return Result(case, inp, rc, route, is_hip=be.is_hip, Y=Y, outputs=[("y", Y)], inputs=inputs, twins=tw.t, twin_inputs=("x", "w"))
 
 
 def run_bwd(lib, be, case, inp=None):
@@ -198,9 +412,12 @@ def run_bwd(lib, be, case, inp=None):
     s = None if case.scratch else _stream(lib, "bare")
     s_dw = _stream(lib, "dw") if case.forked else None
     be.sync()
-    if case.det:
-        lib.check(lib.lib.ffh_ctx_set_deterministic(lib.ctx, 1), "deterministic")
+    tw = None
     try:
+        _set_mode(lib, case.mode)
+        if case.det:
+            lib.check(lib.lib.ffh_ctx_set_deterministic(lib.ctx, 1), "deterministic")
+        tw = Twins(lib, be, case, dict(x=X, w=W, y=Y, dy=DY, dx=DX), ("x", "w", "y", "dy"))
         if case.cmap:
             lib.check(lib.lib.ffh_linear_bwd_set_dx_scatter(lib.ctx, be.addr(cmap_h), case.cmap_ncols, None), "set_dx_scatter")
         if case.colsum:
@@ -211,15 +428,18 @@ def run_bwd(lib, be, case, inp=None):
         su, cu = lib.lib.ffh_linear_dx_scatter_used(lib.ctx), lib.lib.ffh_linear_dx_colsum_used(lib.ctx)
         _finish(lib, be, [s, s_dw])
     finally:
+        if tw:
+            tw.release()
         if case.det:
             lib.check(lib.lib.ffh_ctx_set_deterministic(lib.ctx, 0), "deterministic")
+        _set_mode(lib, 0)
     inputs = [("x", X), ("w", W), ("y", Y)]
     outs = [("dy", DY), ("dw", DW)] + ([("db", DB)] if DB else []) + ([("dx", DX)] if DX else [])
     outs += [(f"dest{k}", d) for k, d in enumerate(dests)] + ([("colsum", CS)] if CS else [])
-    for _, b in inputs + outs:
+    for _, b in inputs + outs + list(tw.t.items()):
         b.fetch()
     return Result(case, inp, rc, route, is_hip=be.is_hip, DY=DY, DW=DW, DB=DB, DX=DX, dests=dests, CS=CS, outputs=outs, inputs=inputs, scatter_used=su, colsum_used=cu,
-                  keepalive=cmap_h)
+                  keepalive=cmap_h, twins=tw.t, twin_inputs=("x", "w", "y", "dy"))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -272,15 +492,37 @@ def _untouched(rep, name, buf, why):
         rep.violations.append(f"{name}: written although {why}")
 
 
-def check_fwd(res):
+def _twins(rep, res, written):
+    """written: output name -> (the floats the library stored, whether the route obliges the call to write the twin)."""
+    for name, tw in res.twins.items():
+        if name in written and res.is_hip:
+            stored, must = written[name]
+            rep.violations += tw.problems(name, stored, must)
+        elif name in written:       # the oracle library's ffh_ctx_bf16_mirror_set is a no-op: untouched is the expected outcome
+            rep.violations += tw.problems(name, written[name][0], False)
+        else:
+            rep.violations += tw.problems(name)
+
+
+def _operand_rounding(case, rnd):
+    """The rounding the GEMM operands of this case go through: the identity in fp32 mode and on a narrow layer, else nearest-even to bfloat16
+    (include/ff_hip.h, FFH_MATH_TENSOR_OP_BF16); `rnd` replaces nearest-even by a wrong rounding (the discrimination tests)."""
+    if not case.bf16_layer:
+        return _f64
+    return lambda a: _f64((rnd or rne_bf16)(np.asarray(a, np.float32)))
+
+
+def check_fwd(res, rnd=None):
     case, inp, rep = res.case, res.inp, Report()
     if res.rc != capi.FFH_OK:
         rep.violations.append(f"rc = {res.rc}")
         return rep
-    x, w = _f64(inp["x"]), _f64(inp["w"])
+    r = _operand_rounding(case, rnd)
+    x, w = r(inp["x"]), r(inp["w"])
     b = _f64(inp["b"]) if case.bias else np.zeros(case.out_dim)
     _compare(rep, "y", res.Y.get(), act64(x @ w.T + b, case.act), np.abs(x) @ np.abs(w).T + np.abs(b), LIPSCHITZ[case.act], case.integer)
     _buffers(rep, res)
+    _twins(rep, res, {"y": (res.Y.get(), "bf16" in res.route)})
     return rep
 
 
@@ -293,12 +535,14 @@ def must_decline_colsum(case):
     return not case.has(OVERWRITE) or case.colsum_ncols != case.in_dim or case.has(ONLY_DW) or not case.dx or case.cmap
 
 
-def check_bwd(res):
+def check_bwd(res, rnd=None):
     case, inp, rep = res.case, res.inp, Report()
     if res.rc != capi.FFH_OK:
         rep.violations.append(f"rc = {res.rc}")
         return rep
     x, w, y, g = _f64(inp["x"]), _f64(inp["w"]), _f64(inp["y"]), _f64(inp["g"])
+    r = _operand_rounding(case, rnd)
+    xr, wr = r(inp["x"]), r(inp["w"])          # the GEMMs' operands; the masks, db and the dy transform stay on the unrounded values
     only_dx, only_dw, ex = case.has(ONLY_DX), case.has(ONLY_DW), case.integer
     act = NONE if case.has(PREMASKED) else case.act
     dy_after = res.DY.get()
@@ -318,7 +562,8 @@ def check_bwd(res):
     if only_dx:
         _untouched(rep, "dw", res.DW, "ONLY_DX")
     else:
-        _compare(rep, "dw", res.DW.get(), _f64(inp["dw0"]) + eff.T @ x, np.abs(_f64(inp["dw0"])) + np.abs(eff).T @ np.abs(x), exact=ex)
+        effr = r(eff)
+        _compare(rep, "dw", res.DW.get(), _f64(inp["dw0"]) + effr.T @ xr, np.abs(_f64(inp["dw0"])) + np.abs(effr).T @ np.abs(xr), exact=ex)
     if res.DB is not None:
         if (only_dw if act == SIG else only_dx):
             _untouched(rep, "db", res.DB, "this half of the split call does not own the bias gradient")
@@ -337,7 +582,8 @@ def check_bwd(res):
         if only_dw:
             _untouched(rep, "dx", res.DX, "ONLY_DW")
         else:
-            ref, mass = eff @ w, np.abs(eff) @ np.abs(w)
+            effr = r(eff)
+            ref, mass = effr @ wr, np.abs(effr) @ np.abs(wr)
             if case.has(MASK_BY_X):
                 keep = x > 0
                 ref, mass = np.where(keep, ref, 0.0), np.where(keep, mass, 0.0)
@@ -365,6 +611,10 @@ def check_bwd(res):
         else:
             _untouched(rep, "colsum", res.CS, "the column sums were declined")
     _buffers(rep, res)
+    written = {}
+    if res.DX is not None and not only_dw:
+        written["dx"] = (res.DX.get(), any("dx" in t.split("|")[0] and "bf16" in t for t in res.route.split(";")) and not (res.scatter_used and case.cmap))
+    _twins(rep, res, written)
     return rep
 
 
@@ -453,12 +703,96 @@ def _sk_tok(name, p, split, colmap=False, colsum=False):
     return f"{name}|sk_{p['rows']}x128x64" + ("|colmap" if colmap else "") + ("|streamk" if split else "") + ("|colsum" if colsum else "")
 
 
+# --- FFH_MATH_TENSOR_OP_BF16: launch_gemm_bf16 (csrc/linear_bf16.hip) and launch_gemm_bf16_dma (csrc/linear_bf16_dma.hip), restated
+def bf16_dma_dw_split(cus, tiles, nk):
+    """The LDS-DMA weight gradient's cost search over the number of k-slices (the same double arithmetic), or None: no candidate."""
+    best, splitk = 1e30, None
+    for sp in range(1, 65):
+        if sp * 4 > nk:
+            break
+        nb = tiles * sp
+        if nb * 2 < cus:
+            continue
+        t = float(_cdiv(nb, cus)) * float(_cdiv(nk, sp)) * 1.0 + float(nb) * (256.0 * 256 * 4) / 1.3e6
+        if t < best:
+            best, splitk = t, sp
+    return splitk
+
+
+def bf16_gemm(c, cus, name, form, M, N, K, epi, lda, ldb, ldc, a, b, a_off, b_off, c_off, masking=False, a_stale=False, bias_off=None, mask=None):
+    """The token of one bf16-pipe GEMM.  form "fwd" / "dx" / "dw"; a, b: the operand buffers' names (their twins are looked up in c.twins) and
+    offsets; a_stale: a live activation derivative rewrote dy in place; mask: (offset, leading dimension) of the mask-by-x operand.  (A bias
+    gradient handed to the LDS-DMA weight gradient wants dy 16-byte aligned and out_dim % 4 == 0: both follow from the twins' own conditions.)"""
+    tiles_big = _cdiv(N, 256) * _cdiv(M, 256)
+    big = (form == "fwd" or (form == "dx" and K >= 1024)) and M >= 256 and N >= 256 and tiles_big >= cus
+    if form == "dw" and epi == "atomic" and not c.det and tiles_big >= 32 and K >= 8192:
+        big = True
+    bt = 256 if big else 128
+    tiles = _cdiv(N, bt) * _cdiv(M, bt)
+    splitk, kps = 1, K
+    if epi == "atomic" and c.det:
+        epi = "add"
+    if epi == "atomic":
+        want = _cdiv((1 if big else 2) * cus, tiles)
+        max_split = _cdiv(K, 256)                       # at least four k-tiles per workgroup
+        if big:                                         # the split whose workgroups fill whole rounds of one per CU best
+            best, best_u = want, 0.0
+            for w2 in range(want, min(2 * want + 2, max_split) + 1):
+                nb = tiles * w2
+                u = float(nb) / float(_cdiv(nb, cus) * cus)
+                if u > best_u + 1e-9:
+                    best_u, best = u, w2
+            want = best
+        want = max(1, min(want, max_split))
+        kps = _cdiv(_cdiv(K, want), 64) * 64
+        splitk = max(2, _cdiv(K, kps))                  # a search that ends at 1 launches two splits, the second one empty
+    twins = (not masking and not a_stale and M % 8 == 0 and N % 8 == 0 and M >= 8 and N >= 8 and K % 64 == 0 and kps % 64 == 0 and lda % 8 == 0
+             and ldb % 8 == 0 and a in c.twins and b in c.twins and a_off % 8 == 0 and b_off % 8 == 0)
+    if twins:
+        ok = ldc % 4 == 0 and c_off % 4 == 0 and (bias_off is None or bias_off % 4 == 0) and (mask is None or (mask[0] % 4 == 0 and mask[1] % 4 == 0))
+        t256 = _cdiv(M, 256) * _cdiv(N, 256)
+        if ok and form == "dw":
+            sp = bf16_dma_dw_split(cus, t256, K // 64) if epi == "atomic" and t256 >= 2 else None
+            if sp:
+                slots = sp > 1 and t256 * sp <= 512 and t256 * sp <= cus and c.scratch
+                return f"{name}|bf16_dma_256x256_twins" + ("|slots" if slots else "")
+        elif ok and (form == "dx" or epi == "store") and t256 * 100 >= cus * 50:
+            return f"{name}|bf16_dma_256x256_twins"
+    return f"{name}|bf16_{bt}x{bt}{'_twins' if twins else ''}|splitk={splitk}"
+
+
+def route_fwd_bf16(c, cus):
+    return [bf16_gemm(c, cus, "linear_fwd gemm (bf16)", "fwd", c.batch, c.out_dim, c.in_dim, "store", c.ldx, c.in_dim, c.ldy, "x", "w", c.x_off, c.w_off,
+                      c.y_off, bias_off=c.bias_off if c.bias else None)]
+
+
+def _bwd_bf16(st, c, cus, do_dw, do_dx):
+    """linear_bwd_impl's tensor-op branch (csrc/linear.hip): the activation gradient as its own pass (no token), the weight gradient, then the data
+    gradient; a column map or a column-sum request is not looked at in this mode (declined: ffh_linear_bwd_ex drops it after the call)."""
+    i, o, B, toks = c.in_dim, c.out_dim, c.batch, st["toks"]
+    act = NONE if c.has(PREMASKED) else c.act
+    relu = act == RELU
+    relu_done = relu and do_dw and do_dx and c.dx           # the mask is written to dy in front of the fork: both GEMMs read a final dy
+    if relu_done:
+        relu = False
+    forked = do_dw and do_dx and c.forked
+    if do_dw:
+        toks.append(bf16_gemm(c, cus, "linear_bwd dw gemm (bf16)", "dw", o, i, B, "atomic", c.lddy, c.ldx, i, "dy", "x", c.dy_off, c.x_off, 0, a_stale=act != NONE))
+    if c.dx and do_dx:
+        masking = (forked or not do_dw) and relu
+        toks.append(bf16_gemm(c, cus, "linear_bwd dx gemm (bf16, masking)" if masking else "linear_bwd dx gemm (bf16)", "dx", B, i, o,
+                              "store" if c.has(OVERWRITE) else "add", c.lddy, i, c.lddx, "dy", "w", c.dy_off, c.w_off, c.dx_off, masking=masking,
+                              a_stale=act != NONE, mask=(c.x_off, c.ldx) if c.has(MASK_BY_X) else None))
+
+
 def route_fwd(c, cus):
     i, o, B = c.in_dim, c.out_dim, c.batch
     if o <= 4:
         return ["linear_fwd|skinny"]
     if i <= 16 and o >= 64 and B < 16384:
         return ["linear_fwd|thin"]
+    if c.bf16_layer:
+        return route_fwd_bf16(c, cus)
     toks = []
     al = _al(c.x_off, c.ldx) and c.w_off % 4 == 0 and i % 4 == 0 and _al(c.y_off, c.ldy) and (not c.bias or c.bias_off % 4 == 0)
     p = sk_plan(cus, "fwd", B, o, i, al, "store")
@@ -489,6 +823,9 @@ def _bwd_impl(st, c, cus, do_dw, do_dx, has_dx, forked):
     x_al, dx_al, dy_al, w_al = _al(c.x_off, c.ldx), _al(c.dx_off, c.lddx), _al(c.dy_off, c.lddy), c.w_off % 4 == 0
     if ((o <= 4 and i <= 1024) or (o <= 16 and i <= 256)) and i % 4 == 0 and x_al and w_al and (not has_dx or dx_al) and not c.det:
         toks.append("linear_bwd|skinny")
+        return
+    if c.bf16_layer:
+        _bwd_bf16(st, c, cus, do_dw, do_dx)
         return
     want_dx = has_dx and do_dx
     epi = "store" if overwrite else "add"
@@ -547,8 +884,15 @@ def _bwd_impl(st, c, cus, do_dw, do_dx, has_dx, forked):
 
 
 def normalize_route(route):
-    """The library's tokens without their split and workgroup counts (route_fwd / route_bwd do not predict those)."""
-    return [re.sub(r"\|(splitk|wgs)=\d+", "", t) for t in route.split(";") if t]
+    """The library's tokens without the split and workgroup counts that route_fwd / route_bwd do not predict: every one except the split count of
+    the bf16-pipe kernels of csrc/linear_bf16.hip in tensor-op mode (the LDS-DMA kernel's comes from a cost search: dma_splits() checks its range)."""
+    keep = re.compile(r"\|bf16_(128x128|256x256)(_twins)?\|splitk=\d+$")
+    return [t if keep.search(t) else re.sub(r"\|(splitk|wgs)=\d+", "", t) for t in route.split(";") if t]
+
+
+def dma_splits(route):
+    """(token, splitk) of every LDS-DMA bf16 launch named in a route."""
+    return [(t, int(m.group(1))) for t in route.split(";") for m in [re.search(r"bf16_dma_256x256_twins\|splitk=(\d+)(\|slots)?$", t)] if m]
 
 
 def expected_route(case, cus):
@@ -569,6 +913,12 @@ def check_route(res, cus):
         if case.det:
             out += [f"deterministic mode: {t!r} is not an ordered route" for t in res.route.split(";")
                     if "skinny" in t or ("dw" in t.split("|")[0] and ("|sk_" in t or "glds" in t or not t.endswith("splitk=1")))]
+        for t, sp in dma_splits(res.route):
+            if "dw" in t.split("|")[0]:
+                if not (1 <= sp and 4 * sp <= case.batch // 64):
+                    out.append(f"{t!r}: a split of {sp} slices does not leave four k-tiles each at batch {case.batch}")
+            elif sp != 1:
+                out.append(f"{t!r}: only the weight gradient splits K")
     if cus == TABLE_CUS:
         joined = ";".join(got) + f";scatter_used={res.scatter_used};colsum_used={res.colsum_used}"
         out += [f"route {got} does not reach {w!r}, the kernel this case is in the table for" for w in case.want if w not in joined]
@@ -798,3 +1148,176 @@ def draw_case(rng, name="random"):
 def draw_cases(seed, count=6):
     rng = np.random.default_rng(1000 + seed)
     return [draw_case(rng, f"seed{seed}.{k}") for k in range(count)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# FFH_MATH_TENSOR_OP_BF16: the edge table (shapes derived for 256 CUs from bf16_gemm above) and the random cases
+def _bf16_table(t):
+    M1 = dict(mode=MATH_BF16)
+    F, DWT, DXT, DXM = "linear_fwd gemm (bf16)|", "linear_bwd dw gemm (bf16)|", "linear_bwd dx gemm (bf16)|", "linear_bwd dx gemm (bf16, masking)|"
+    S, BIG, ST, BIGT, DMA = "bf16_128x128|splitk=", "bf16_256x256|splitk=", "bf16_128x128_twins|splitk=", "bf16_256x256_twins|splitk=", "bf16_dma_256x256_twins"
+    # 128 x 128 tiles, fp32 operands rounded in the kernel: any wide layer below 256 tiles of 256 x 256.  Ragged in M, N and K (K neither a
+    # multiple of 64 nor of 4: the guarded loader), every offset, padded rows, no bias, the four activations.
+    t["bf16-128-fwd"] = [
+        Case("b-fwd-129->130", "fwd", 129, 130, 70, RELU, ldx=133, x_off=1, ldy=131, y_off=2, w_off=1, want=F + S + "1", **M1),
+        Case("b-fwd-136->257", "fwd", 136, 257, 300, SIG, bias=False, ldy=260, x_off=4, want=F + S + "1", **M1),
+        Case("b-fwd-192->128", "fwd", 192, 128, 257, GELU, bias_off=1, w_off=4, y_off=4, want=F + S + "1", **M1),
+        Case("b-fwd-130->192-int", "fwd", 130, 192, 129, NONE, integer=True, bias_off=2, want=F + S + "1", **M1),
+        Case("b-fwd-192->136-ties", "fwd", 192, 136, 200, RELU, dist="ties", want=F + S + "1", **M1),
+        Case("b-fwd-257->129-wide", "fwd", 257, 129, 130, NONE, dist="wide", w_off=2, ldx=260, want=F + S + "1", **M1)]
+    # dX: accumulating (EPI_ADD), storing (EPI_STORE), masked by x; a live ReLU with both gradients is applied to dy in front of the fork (plain
+    # form, forked or not), under ONLY_DX it is read through relu'(y) (the masking form).  The dW beside them splits K by atomics:
+    # tiles = cdiv(out, 128) * cdiv(in, 128), want = cdiv(512, tiles) capped at cdiv(batch, 256).
+    t["bf16-128-dx"] = [
+        Case("b-dx-add", "bwd", 129, 130, 700, NONE, 0, lddy=133, dy_off=1, lddx=131, dx_off=2, want=(DXT + S + "1", DWT + S + "3"), **M1),
+        Case("b-dx-store", "bwd", 136, 257, 300, SIG, OVERWRITE, w_off=1, ldx=137, x_off=4, db=False, want=(DXT + S + "1", DWT + S + "2"), **M1),
+        Case("b-dx-mask-by-x", "bwd", 192, 128, 257, RELU, OVERWRITE | MASK_BY_X | PREMASKED, ldx=195, x_off=1, want=(DXT + S + "1", DWT + S + "2"), **M1),
+        Case("b-dx-live-relu-forked", "bwd", 130, 192, 129, RELU, MASK_BY_X, forked=True, ldy=193, y_off=2, want=(DXT + S + "1", DWT + S + "2"), **M1),
+        Case("b-dx-live-relu", "bwd", 257, 129, 130, RELU, OVERWRITE, want=(DXT + S + "1", DWT + S + "2"), **M1),
+        Case("b-dx-masking-only-dx", "bwd", 129, 136, 200, RELU, ONLY_DX | OVERWRITE, lddy=137, ldy=139, dy_off=2, want=DXM + S + "1", **M1),
+        Case("b-dx-masking-only-dx-add-maskx", "bwd", 192, 257, 77, RELU, ONLY_DX | MASK_BY_X, dx_off=1, want=DXM + S + "1", **M1),
+        Case("b-dx-sigmoid-only-dx", "bwd", 130, 129, 131, SIG, ONLY_DX, want=DXT + S + "1", **M1),
+        Case("b-dx-int", "bwd", 130, 192, 129, RELU, OVERWRITE, integer=True, want=(DXT + S + "1", DWT + S + "2"), **M1),
+        Case("b-dx-masking-int", "bwd", 136, 129, 70, RELU, ONLY_DX | OVERWRITE, integer=True, want=DXM + S + "1", **M1),
+        Case("b-dx-ties", "bwd", 192, 136, 200, NONE, OVERWRITE, dist="ties", want=(DXT + S + "1", DWT + S + "2"), **M1),
+        Case("b-dx-masking-ties", "bwd", 192, 136, 200, RELU, ONLY_DX | OVERWRITE, dist="ties", want=DXM + S + "1", **M1),
+        Case("b-dx-masking-wide", "bwd", 257, 130, 131, RELU, ONLY_DX, dist="wide", lddy=131, want=DXM + S + "1", **M1),
+        Case("b-dx-wide", "bwd", 257, 129, 130, NONE, 0, dist="wide", want=(DXT + S + "1", DWT + S + "2"), **M1),
+        Case("b-dx-column-map-declined", "bwd", 129, 130, 70, NONE, OVERWRITE, cmap=True, colsum=True, want=(DXT + S + "1", "scatter_used=0", "colsum_used=0"), **M1)]
+    # dW alone: 700 x (130 -> 129): 4 tiles, want 128 capped at cdiv(700, 256) = 3 -> 256 samples per split, 3 splits; 1100 x (257 -> 136): 6 tiles,
+    # want 86 capped at 5 -> 256 per split, 5 splits, the last one 76 deep (not a multiple of 4); no dx, no db, the three activations
+    t["bf16-128-dw-splitk"] = [
+        Case("b-dw-3-splits", "bwd", 130, 129, 700, RELU, ONLY_DW, lddy=131, dy_off=1, ldx=133, x_off=2, want=DWT + S + "3", **M1),
+        Case("b-dw-5-splits-sigmoid", "bwd", 257, 136, 1100, SIG, ONLY_DW, db=False, want=DWT + S + "5", **M1),
+        Case("b-dw-no-dx", "bwd", 136, 130, 513, NONE, 0, dx=False, want=DWT + S + "3", **M1),
+        Case("b-dw-int", "bwd", 129, 192, 700, NONE, ONLY_DW, integer=True, want=DWT + S + "3", **M1),
+        Case("b-dw-ties", "bwd", 192, 136, 700, NONE, ONLY_DW, dist="ties", want=DWT + S + "3", **M1),
+        Case("b-dw-wide", "bwd", 130, 257, 700, RELU, ONLY_DW | PREMASKED, dist="wide", want=DWT + S + "3", **M1)]
+    # batch <= 256: cdiv(batch, 256) = 1 caps the search at one split, and the launch runs with two, the second one empty
+    t["bf16-128-dw-empty-second-split"] = [
+        Case("b-dw-empty-70", "bwd", 129, 130, 70, RELU, ONLY_DW, want=DWT + S + "2", **M1),
+        Case("b-dw-empty-256", "bwd", 192, 136, 256, NONE, OVERWRITE, want=DWT + S + "2", **M1),
+        Case("b-dw-empty-255-int", "bwd", 130, 129, 255, NONE, ONLY_DW, integer=True, want=DWT + S + "2", **M1)]
+    # deterministic mode: the same weight gradients as one ordered split adding into dw
+    t["bf16-deterministic"] = [
+        Case("b-det-700", "bwd", 130, 129, 700, RELU, ONLY_DW, det=True, lddy=131, dy_off=1, want=DWT + S + "1", **M1),
+        Case("b-det-1100-sigmoid", "bwd", 257, 136, 1100, SIG, 0, det=True, want=(DWT + S + "1", DXT + S + "1"), **M1),
+        Case("b-det-70", "bwd", 129, 130, 70, NONE, OVERWRITE, det=True, want=DWT + S + "1", **M1),
+        Case("b-det-twins", "bwd", 192, 192, 192, NONE, OVERWRITE, det=True, twins=("x", "w", "dy", "dx"), want=(DWT + ST + "1", DXT + ST + "1"), **M1)]
+    # 256 x 256 tiles: forward from 256 tiles on (both extents >= 256): 264 wide is 2 tile columns, so 128 tile rows: batch > 127 * 256 = 32512;
+    # dX the same with a reduction depth (out_dim) >= 1024; dW from 32 tiles and batch 8192 on: 1030 x 1540 is 5 x 7 = 35 tiles, want cdiv(256, 35) = 8,
+    # the search over 8 .. 18 splits takes the first fullest round
+    t["bf16-256-fwd"] = [Case("b-big-fwd", "fwd", 136, 264, 32520, RELU, ldx=137, x_off=1, y_off=2, want=F + BIG + "1", **M1)]
+    t["bf16-256-dx"] = [Case("b-big-dx", "bwd", 264, 1030, 32520, RELU, ONLY_DX | OVERWRITE | MASK_BY_X | PREMASKED, dx_off=1, want=DXT + BIG + "1", **M1)]
+    # ... and the masking form (a live ReLU under ONLY_DX: dy read through relu'(y), y the third operand, its rows ldy apart) takes the same tile by the
+    # same rule; the twins forms never serve it, so bf16_128x128 and bf16_256x256 are all it has.  Storing and accumulating, ragged in M, N and K
+    t["bf16-256-dx-masking"] = [
+        Case("b-big-dx-masking-store", "bwd", 264, 1030, 32520, RELU, ONLY_DX | OVERWRITE, lddy=1033, dy_off=1, ldy=1031, y_off=2, lddx=265, want=DXM + BIG + "1", **M1),
+        Case("b-big-dx-masking-add-maskx", "bwd", 264, 1030, 32520, RELU, ONLY_DX | MASK_BY_X, ldy=1032, dx_off=1, ldx=267, x_off=1, want=DXM + BIG + "1", **M1)]
+    t["bf16-256-dw"] = [Case("b-big-dw", "bwd", 1540, 1030, 8200, NONE, ONLY_DW, want=DWT + BIG, **M1)]
+    # one tile fewer: 127 tile rows x 2 = 254 tiles; 5 x 6 = 30 tiles; the masking dX at 254 tiles
+    t["bf16-256-tile-boundary"] = [
+        Case("b-big-fwd-254-tiles", "fwd", 136, 264, 32504, RELU, want=F + S + "1", **M1),
+        Case("b-big-dx-masking-254-tiles", "bwd", 264, 1030, 32504, RELU, ONLY_DX | OVERWRITE, ldy=1031, want=DXM + S + "1", **M1),
+        Case("b-big-dw-30-tiles", "bwd", 1536, 1030, 8200, NONE, ONLY_DW, db=False, want=DWT + S, **M1)]
+    # twins on both operands, whole 8-element pieces (M, N multiples of 8, K a multiple of 64, rows multiples of 8 apart, bases 16-byte aligned),
+    # fewer than 128 tiles of 256 x 256: the SRC16 form of the 128 x 128 kernel
+    XW, BW = ("x", "w", "y"), ("x", "w", "dy", "dx")
+    t["bf16-128-twins"] = [
+        Case("b-tw-fwd", "fwd", 192, 136, 200, RELU, ldx=200, x_off=8, ldy=137, y_off=1, twins=XW, want=F + ST + "1", **M1),
+        Case("b-tw-fwd-ties", "fwd", 192, 136, 200, NONE, twins=XW, dist="ties", want=F + ST + "1", **M1),
+        Case("b-tw-bwd", "bwd", 136, 192, 192, RELU, PREMASKED | OVERWRITE | MASK_BY_X, lddy=200, dy_off=8, twins=BW, want=(DWT + ST + "2", DXT + ST + "1"), **M1),
+        Case("b-tw-bwd-add-int", "bwd", 136, 192, 320, NONE, 0, twins=BW, integer=True, want=(DWT + ST + "2", DXT + ST + "1"), **M1),
+        Case("b-tw-bwd-wide", "bwd", 136, 192, 192, NONE, OVERWRITE, twins=BW, dist="wide", want=(DWT + ST + "2", DXT + ST + "1"), **M1)]
+    # the LDS-DMA kernel: twins, from 128 tiles of 256 x 256 on (half the CUs): 8200 rows are 33 tile rows (ragged, a multiple of 8) x 4 tile columns = 132
+    t["bf16-dma-fwd"] = [Case("b-dma-fwd", "fwd", 128, 1000, 8200, RELU, twins=XW, want=F + DMA, **M1),
+                         Case("b-dma-fwd-ties", "fwd", 128, 1000, 8200, SIG, twins=("x", "w"), dist="ties", bias=False, ldy=1004, want=F + DMA, **M1)]
+    t["bf16-dma-dx"] = [
+        Case("b-dma-dx-store", "bwd", 1000, 128, 8200, NONE, ONLY_DX | OVERWRITE, twins=BW, want=DXT + DMA, **M1),
+        Case("b-dma-dx-add", "bwd", 1000, 128, 8200, RELU, ONLY_DX | PREMASKED, twins=("w", "dy"), lddx=1004, want=DXT + DMA, **M1),
+        Case("b-dma-dx-mask-twin", "bwd", 1000, 128, 8200, NONE, ONLY_DX | OVERWRITE | MASK_BY_X, twins=BW, want=DXT + DMA, **M1),
+        Case("b-dma-dx-mask-fp32", "bwd", 1000, 128, 8200, NONE, ONLY_DX | OVERWRITE | MASK_BY_X, twins=("w", "dy", "dx"), want=DXT + DMA, **M1)]
+    # dW: 2 tiles (264 x 192) need 64 slices for 128 workgroups (half the CUs) and four k-tiles each: batch 64 * 4 * 64 = 16384; 6 tiles (520 x 320)
+    # need 22 slices: batch 22 * 4 * 64 = 5632.  128 and 132 workgroups fit one round: the slices meet in the stream's slots, without scratch by atomics
+    DW2 = dict(twins=("x", "dy"), **M1)
+    t["bf16-dma-dw"] = [
+        Case("b-dma-dw-2-tiles-db", "bwd", 192, 264, 16384, NONE, ONLY_DW, want=DWT + DMA + "|slots", **DW2),
+        Case("b-dma-dw-2-tiles-no-db", "bwd", 192, 264, 16384, RELU, ONLY_DW | PREMASKED, db=False, want=DWT + DMA + "|slots", **DW2),
+        Case("b-dma-dw-2-tiles-atomics", "bwd", 192, 264, 16384, NONE, ONLY_DW, scratch=False, want=DWT + DMA, **DW2),
+        Case("b-dma-dw-6-tiles", "bwd", 320, 520, 5632, NONE, ONLY_DW, want=DWT + DMA + "|slots", **DW2),
+        Case("b-dma-dw-6-tiles-atomics-int", "bwd", 320, 520, 5632, NONE, ONLY_DW, scratch=False, db=False, integer=True, want=DWT + DMA, **DW2)]
+    # one tile row fewer (31 x 4 = 124 tiles) stays on the 128 x 128 twins form; a batch one k-tile short of 16384 has no split with four k-tiles a slice
+    t["bf16-dma-boundary"] = [
+        Case("b-dma-fwd-124-tiles", "fwd", 128, 1000, 7936, RELU, twins=XW, want=F + ST + "1", **M1),
+        Case("b-dma-dw-declined", "bwd", 192, 264, 16320, NONE, ONLY_DW, want=DWT + ST + "64", **DW2)]
+    # 256 tiles and twins, but the LDS-DMA kernel declines: a bias, rows of y or a base of y that is not 16-byte aligned
+    t["bf16-256-twins-fwd"] = [
+        Case("b-bigtw-bias-off", "fwd", 128, 264, 32520, RELU, twins=XW, bias_off=1, want=F + BIGT + "1", **M1),
+        Case("b-bigtw-ldy", "fwd", 128, 264, 32520, NONE, twins=XW, ldy=266, want=F + BIGT + "1", **M1),
+        Case("b-bigtw-y-off", "fwd", 128, 264, 32520, GELU, twins=("x", "w"), y_off=2, want=F + BIGT + "1", **M1)]
+    t["bf16-256-twins-dx"] = [Case("b-bigtw-dx", "bwd", 264, 1088, 32520, NONE, ONLY_DX | OVERWRITE, twins=BW, dx_off=2, want=DXT + BIGT + "1", **M1)]
+    # twins registered and not usable: the fp32 operands are rounded in the kernel, the output's twin is written all the same
+    t["bf16-twins-not-usable"] = [
+        Case("b-nt-m", "fwd", 192, 136, 201, RELU, twins=XW, want=F + S + "1", **M1),
+        Case("b-nt-n", "fwd", 192, 130, 200, RELU, twins=XW, want=F + S + "1", **M1),
+        Case("b-nt-k", "fwd", 136, 192, 200, NONE, twins=XW, want=F + S + "1", **M1),
+        Case("b-nt-ldx", "fwd", 192, 136, 200, SIG, twins=XW, ldx=196, want=F + S + "1", **M1),
+        Case("b-nt-x-off", "fwd", 192, 136, 200, RELU, twins=XW, x_off=4, want=F + S + "1", **M1),
+        Case("b-nt-one-operand", "fwd", 192, 136, 200, RELU, twins=("x", "y"), want=F + S + "1", **M1),
+        Case("b-nt-bwd-k", "bwd", 192, 136, 200, NONE, OVERWRITE, twins=BW, want=(DWT + S + "2", DXT + S + "1"), **M1)]
+    # a live activation derivative rewrites dy in place and leaves its twin stale (NaN here): the twin must not be read
+    t["bf16-stale-twins"] = [
+        Case("b-stale-relu", "bwd", 136, 192, 192, RELU, OVERWRITE, twins=BW, stale=("dy",), want=(DWT + S + "2", DXT + S + "1"), **M1),
+        Case("b-stale-sigmoid", "bwd", 136, 192, 192, SIG, 0, twins=BW, stale=("dy",), want=(DWT + S + "2", DXT + S + "1"), **M1),
+        Case("b-stale-masking", "bwd", 136, 192, 192, RELU, ONLY_DX | OVERWRITE, twins=BW, stale=("dy",), want=DXM + S + "1", **M1),
+        Case("b-stale-sigmoid-only-dw", "bwd", 136, 192, 192, SIG, ONLY_DW, twins=BW, stale=("dy",), want=DWT + S + "2", **M1)]
+    # narrow layers keep the fp32 kernels and the fp32 reference (unrounded: a rounding kernel cannot meet the bound on uniform data)
+    t["bf16-narrow-layers"] = [
+        Case("b-narrow-in127", "fwd", 127, 256, 300, RELU, twins=XW, want="linear_fwd gemm|f32_", **M1),
+        Case("b-narrow-out127", "fwd", 256, 127, 300, SIG, twins=XW, want="linear_fwd gemm|f32_", **M1),
+        Case("b-narrow-bwd-in127", "bwd", 127, 256, 300, RELU, OVERWRITE, twins=BW, want=("linear_bwd dw gemm|f32_", "linear_bwd dx gemm|f32_"), **M1),
+        Case("b-narrow-bwd-out127", "bwd", 256, 127, 300, NONE, 0, twins=BW, want=("linear_bwd dw gemm|f32_", "linear_bwd dx gemm|f32_"), **M1),
+        Case("b-narrow-skinny-fwd", "fwd", 256, 4, 300, SIG, twins=XW, want="linear_fwd|skinny", **M1),
+        Case("b-narrow-thin-fwd", "fwd", 13, 512, 300, RELU, twins=XW, want="linear_fwd|thin", **M1),
+        Case("b-narrow-skinny-bwd", "bwd", 256, 1, 4100, SIG, OVERWRITE | MASK_BY_X, twins=BW, want="linear_bwd|skinny", **M1)]
+
+
+# calls that have to be refused before anything is written: name -> (case, the error)
+REFUSALS = {
+    "gelu-in-the-backward": (Case("r", "bwd", 70, 40, 33, GELU), capi.FFH_ERR_UNSUPPORTED),
+    "only-dx-and-only-dw": (Case("r", "bwd", 70, 40, 33, RELU, ONLY_DX | ONLY_DW), capi.FFH_ERR_BAD_ARG),
+    "ldx-below-in-dim": (Case("r", "bwd", 70, 40, 33, RELU, ldx=69), capi.FFH_ERR_BAD_ARG),
+    "ldy-below-out-dim": (Case("r", "bwd", 70, 40, 33, RELU, ldy=39), capi.FFH_ERR_BAD_ARG),
+    "lddy-below-out-dim": (Case("r", "bwd", 70, 40, 33, RELU, lddy=39), capi.FFH_ERR_BAD_ARG),
+    "lddx-below-in-dim": (Case("r", "bwd", 70, 40, 33, RELU, lddx=69), capi.FFH_ERR_BAD_ARG),
+    "fwd-ldx-below-in-dim": (Case("r", "fwd", 70, 40, 33, RELU, ldx=69), capi.FFH_ERR_BAD_ARG),
+    "fwd-ldy-below-out-dim": (Case("r", "fwd", 70, 40, 33, RELU, ldy=39), capi.FFH_ERR_BAD_ARG),
+    "fwd-tanh": (Case("r", "fwd", 70, 40, 33, capi.AC_MODE_TANH), capi.FFH_ERR_UNSUPPORTED),
+}
+
+
+def bf16_edge_table(cus=TABLE_CUS):
+    t = {}
+    _bf16_table(t)
+    return t
+
+
+BF16_EDGE_NAMES = list(bf16_edge_table())
+
+
+def draw_case_bf16(rng, name="random-bf16"):
+    """draw_case with each width raised to at least 128 with probability one half, in tensor-op mode, a random subset of twins, a random distribution."""
+    c = draw_case(rng, name)
+    i = max(c.in_dim, BF16_MIN_DIM) if rng.random() < 0.5 else c.in_dim
+    o = max(c.out_dim, BF16_MIN_DIM) if rng.random() < 0.5 else c.out_dim
+    twins = [n for n in TWIN_NAMES if rng.random() < 0.5]
+    dist = str(rng.choice(DISTS))
+    if dist in ("integer", "wide") and c.act not in (NONE, RELU):
+        dist = "uniform"
+    return c.replace(in_dim=i, out_dim=o, ldx=i + c.ldx - c.in_dim, lddx=i + c.lddx - c.in_dim, ldy=o + c.ldy - c.out_dim, lddy=o + c.lddy - c.out_dim,
+                     mode=MATH_BF16, twins=twins, dist=dist)
+
+
+def draw_cases_bf16(seed, count=6):
+    rng = np.random.default_rng(7000 + seed)
+    return [draw_case_bf16(rng, f"bf16-seed{seed}.{k}") for k in range(count)]

@@ -105,17 +105,7 @@ def test_linear_empty_batch_writes_nothing(hip, be):
 
 
 BAD_ARG, UNSUPPORTED = capi.FFH_ERR_BAD_ARG, capi.FFH_ERR_UNSUPPORTED
-REFUSALS = {
-    "gelu-in-the-backward": (Case("r", "bwd", 70, 40, 33, GELU), UNSUPPORTED),
-    "only-dx-and-only-dw": (Case("r", "bwd", 70, 40, 33, RELU, ONLY_DX | ONLY_DW), BAD_ARG),
-    "ldx-below-in-dim": (Case("r", "bwd", 70, 40, 33, RELU, ldx=69), BAD_ARG),
-    "ldy-below-out-dim": (Case("r", "bwd", 70, 40, 33, RELU, ldy=39), BAD_ARG),
-    "lddy-below-out-dim": (Case("r", "bwd", 70, 40, 33, RELU, lddy=39), BAD_ARG),
-    "lddx-below-in-dim": (Case("r", "bwd", 70, 40, 33, RELU, lddx=69), BAD_ARG),
-    "fwd-ldx-below-in-dim": (Case("r", "fwd", 70, 40, 33, RELU, ldx=69), BAD_ARG),
-    "fwd-ldy-below-out-dim": (Case("r", "fwd", 70, 40, 33, RELU, ldy=39), BAD_ARG),
-    "fwd-tanh": (Case("r", "fwd", 70, 40, 33, capi.AC_MODE_TANH), UNSUPPORTED),
-}
+REFUSALS = LH.REFUSALS          # (shared with the tensor-op sweep)
 
 
 @pytest.mark.parametrize("reason", list(REFUSALS))
