@@ -887,6 +887,10 @@ _SIGS_FOLD = {
     "ffh_fold_gather_add": (I, [P, C.POINTER(EmbTable), I, I, I, L, I, P, L, P]),
     "ffh_fold_linear_fwd": (I, [P, P, L, P, L, P, P, I, I, L, I, C.POINTER(FoldSeg), I, P, L, P]),
     "ffh_fold_linear_fwd_plan": (I, [P, P, L, P, L, P, P, I, I, L, C.POINTER(FoldSeg), I, P, L]),
+    "ffh_fold_segment_sum": (I, [P, C.POINTER(EmbTable), I, I, I, L, P]),
+    "ffh_fold_dw_product": (I, [P, C.POINTER(FoldGroup), I, P, L, I, I, P]),
+    "ffh_fold_linear_bwd_dw": (I, [P, P, L, P, L, P, P, I, I, L, C.POINTER(C.c_int32), I, P]),
+    "ffh_fold_linear_bwd_dw_plan": (I, [P, P, L, P, L, P, P, I, I, L, C.POINTER(C.c_int32), I]),
 }
 
 

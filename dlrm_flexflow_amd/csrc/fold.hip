@@ -11,6 +11,10 @@
 // 16 bytes.  Lane (c, q) loads 16 bytes at k = 16 j + 4 q of its rows; component e of both operands feeds MFMA e of the group -- any
 // assignment of k to the MFMA's four k-slots is legal as long as both operands agree (the trick of linear_sk.hip's k-contiguous image).
 // Order of the sum per element: segments in list order, groups of 16 ascending, e = 0..3, the MFMA's own order over q: fixed.
+//
+// The weight gradient of the same layer (ABI 2): dW[:, cols_t] = G_t^T E_t with G_t the segmented sum of dy over the table's rows -- the sum by
+// embedding.hip's fused update on zeroed rows (ffh_fold_segment_sum), the products by fold_dw_product_kernel, the GEMM over the column tiles
+// that are left by linear_sk.hip's KEPT instantiation (ffh_fold_linear_bwd_dw).
 #include "linear_gemm.h"
 
 #include "../../include/ff_hip_fold.h"
@@ -133,7 +137,109 @@ __global__ __launch_bounds__(256) void fold_gather_add_kernel(const FoldGatherAr
   }
 }
 
+// fold_dw_product_kernel: dW[o][col0 + d] += sum over a chunk of rows r of G[r][o] E[r][d] -- both operands rows-are-k.  One wave owns 64 outputs x
+// 64 columns of one chunk of FFH_FOLD_DW_CHUNK rows of one table; lane (c, q) loads 16 bytes of row k + q of either operand: ONE k-step of FOUR
+// 16-wide tiles (tile t holds outputs / columns 4 c + t -- linear_sk.hip's rows-are-k image, read from global memory instead of LDS).  Rows behind
+// the table's last contribute zeros (loaded from its last row, then cleared).  The next 16 rows are in flight while the MFMAs of these run.  The
+// chunks of a table meet in dW by float atomics, through a per-wave LDS image so that one atomic instruction covers 256 contiguous bytes of one
+// row of dW (the epilogue of the stream-K weight gradient, which writes the neighbouring columns under the same contract).
+constexpr int FOLD_DW_EP_LD = 68;      // floats per row of the wave's epilogue image: 64 + 4 of padding
+struct FoldDwGroup { const float* g; const float* e; int64_t lde; int64_t col0; int rows; int tile0; };   // tile0: the group's first wave tile in the launch
+struct FoldDwArgs {
+  FoldDwGroup grp[FFH_FOLD_MAX_GROUPS];
+  float* dw; int64_t lddw;
+  int ngroups, out, d, ntiles;
+};
+static_assert(sizeof(FoldDwArgs) <= 4096, "kernel arguments");
+
+__global__ __launch_bounds__(256) void fold_dw_product_kernel(const FoldDwArgs g) {
+  __shared__ __attribute__((aligned(16))) float ep_all[4][16 * FOLD_DW_EP_LD];
+  ffh_kernel_prio();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int c = lane & 15, q = lane >> 4;
+  const int wt = (int)blockIdx.x * 4 + wave;
+  if (wt >= g.ntiles) return;
+  int gi = 0;
+  while (gi + 1 < g.ngroups && g.grp[gi + 1].tile0 <= wt) gi++;       // uniform
+  const FoldDwGroup G = g.grp[gi];
+  const int ot = g.out / 64, dt = g.d / 64, local = wt - G.tile0;
+  const int chunk = local / (ot * dt), rem = local - chunk * (ot * dt);
+  const int o0 = (rem / dt) * 64, d0 = (rem % dt) * 64;
+  const int rb = chunk * FFH_FOLD_DW_CHUNK;
+  const int re = rb + FFH_FOLD_DW_CHUNK < G.rows ? rb + FFH_FOLD_DW_CHUNK : G.rows;      // rb < re <= G.rows
+  const float* gp = G.g + o0 + 4 * c;
+  const float* epn = G.e + d0 + 4 * c;
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int tm = 0; tm < 4; tm++)
+#pragma unroll
+    for (int tn = 0; tn < 4; tn++) acc[tm][tn] = f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 a[4], b[4], an[4], bn[4];
+  auto load16 = [&](int k, f32x4* av, f32x4* bv) {      // rows k + 4 u + q, u = 0..3
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int r = k + 4 * u + q;
+      const int rc = r < re ? r : re - 1;
+      av[u] = *reinterpret_cast<const f32x4*>(gp + (int64_t)rc * g.out);
+      bv[u] = *reinterpret_cast<const f32x4*>(epn + (int64_t)rc * G.lde);
+      if (r >= re) av[u] = f32x4{0.f, 0.f, 0.f, 0.f};     // (a zero times whatever the valid row holds: finite tables, as everywhere)
+    }
+  };
+  load16(rb, a, b);
+  for (int k = rb; k < re; k += 16) {
+    if (k + 16 < re) load16(k + 16, an, bn);      // uniform
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+#pragma unroll
+      for (int tm = 0; tm < 4; tm++)
+#pragma unroll
+        for (int tn = 0; tn < 4; tn++) acc[tm][tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][tm], b[u][tn], acc[tm][tn], 0, 0, 0);
+#pragma unroll
+    for (int u = 0; u < 4; u++) { a[u] = an[u]; b[u] = bn[u]; }
+  }
+  // lane (c, q) holds, for tm, tn, i in 0..3, output o0 + 16 q + 4 i + tm, column d0 + 4 c + tn: the layout of the stream-K weight gradient's wave
+  float* const ep = ep_all[wave];
+  float* crow = g.dw + (int64_t)o0 * g.lddw + G.col0 + d0 + lane;
+#pragma unroll
+  for (int p = 0; p < 4; p++) {            // outputs 16 p .. 16 p + 15 of the wave's result are held by the lanes with q == p
+    if (q == p) {
+#pragma unroll
+      for (int tm = 0; tm < 4; tm++)
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+          *reinterpret_cast<f32x4*>(ep + (4 * i + tm) * FOLD_DW_EP_LD + 4 * c) = f32x4{acc[tm][0][i], acc[tm][1][i], acc[tm][2][i], acc[tm][3][i]};
+    }
+    __builtin_amdgcn_wave_barrier();       // the wave's own image: no workgroup barrier (a wave's ds operations complete in order)
+#pragma unroll
+    for (int r = 0; r < 16; r++) atomicAdd(crow + (int64_t)(16 * p + r) * g.lddw, ep[r * FOLD_DW_EP_LD + lane]);
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// the checks ffh_fold_linear_bwd_dw and its plan query share; FFH_OK, or the error left in the ctx
+int fold_dw_check(ffh_ctx* c, const float* x, int64_t ldx, const float* dy, int64_t lddy, const float* dw, int in, int out, int64_t batch,
+                  const int32_t* kept, int nkept) {
+  FFH_REQUIRE(c, in > 0 && out > 0 && batch >= 0 && ldx >= in && lddy >= out, "fold_linear_bwd_dw: bad dims");
+  FFH_REQUIRE(c, batch == 0 || (x && dy && dw), "fold_linear_bwd_dw: null pointer");
+  FFH_REQUIRE(c, batch < (1LL << 31), "fold_linear_bwd_dw: batch too large");
+  FFH_REQUIRE(c, nkept >= 1 && kept, "fold_linear_bwd_dw: bad tile list");
+  for (int i = 0; i < nkept; i++)
+    FFH_REQUIRE(c, kept[i] >= 0 && ((int64_t)kept[i] + 1) * FFH_FOLD_DW_NTILE <= in && (i == 0 || kept[i] > kept[i - 1]), "fold_linear_bwd_dw: tiles must ascend inside [0, in_dim)");
+  return FFH_OK;
+}
+GemmArgs fold_dw_gemm(const float* x, int64_t ldx, const float* dy, int64_t lddy, float* dw, float* db, int in, int out, int64_t batch) {
+  GemmArgs g{};      // as linear.hip states the weight gradient of a layer whose dy is final
+  g.A = dy; g.sAm = 1; g.sAk = lddy;
+  g.B = x; g.sBn = 1; g.sBk = ldx;
+  g.C = dw; g.ldc = in;
+  g.M = out; g.N = in; g.K = (int)batch;
+  g.epi = EPI_ATOMIC; g.act = FFH_AC_MODE_NONE;
+  g.db = db;
+  return g;
+}
 
 // the checks ffh_fold_linear_fwd and its plan query share; FFH_OK, or the error left in the ctx
 int fold_fwd_check(ffh_ctx* c, const float* x, int64_t ldx, const float* y, int64_t ldy, const float* w, int in, int out, int64_t batch,
@@ -264,6 +370,69 @@ int ffh_fold_linear_fwd(ffh_ctx* c, const float* x, int64_t ldx, float* y, int64
   hipLaunchKernelGGL(fold_gemm_kernel<true>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, as_stream(s), a);
   FFH_LAUNCH_CHECK(c, "fold_gemm_kernel (forward)");
   ffh_route_add(c, "fold_linear_fwd gemm|mfma_32x64x16");
+  return FFH_OK;
+}
+
+// G_t = the segmented sum of dy over the hits of every row: the fused table update on zeroed rows with lr = -1 (w = fmaf(1, sum, 0) = sum), so the
+// sort, the ordered reduction and their summation order are embedding.hip's, launch for launch
+int ffh_fold_segment_sum(ffh_ctx* c, const ffh_emb_table* tables, int ntables, int in_dim, int width, int64_t batch, ffh_stream s) {
+  FFH_REQUIRE(c, tables && ntables >= 1 && in_dim >= 1 && width > 0 && batch >= 0, "fold_segment_sum: bad arguments");
+  if (ntables > FFH_MAX_TABLES || batch * in_dim >= (1LL << 31)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_segment_sum: at most 64 tables, batch * in_dim < 2^31");
+  for (int t = 0; t < ntables; t++)
+    FFH_REQUIRE(c, tables[t].weight && tables[t].num_entries >= 1 && (batch == 0 || (tables[t].idx && tables[t].io && tables[t].ld >= width)), "fold_segment_sum: bad table");
+  if (batch > 0 && (!c->ws || c->ws_bytes < ffh_embedding_bwd_workspace_bytes(ntables, in_dim, width, batch) || ((uintptr_t)c->ws & 15)))
+    return ffh_fail(c, FFH_ERR_WORKSPACE, "fold_segment_sum: workspace too small (ffh_embedding_bwd_workspace_bytes) or not 16-byte aligned");
+  for (int t = 0; t < ntables;) {      // tables that lie back to back (the usual case: one buffer) are cleared by one memset
+    char* p0 = (char*)tables[t].weight;
+    size_t bytes = 0;
+    for (; t < ntables && (char*)tables[t].weight == p0 + bytes; t++) bytes += (size_t)tables[t].num_entries * (size_t)width * 4;
+    const int rc = ffh_zero(c, p0, bytes, s);
+    if (rc != FFH_OK) return rc;
+  }
+  if (batch == 0) return FFH_OK;
+  return ffh_embedding_bwd_sgd_fused_multi(c, tables, ntables, in_dim, width, batch, FFH_AGGR_MODE_SUM, -1.0f, s);
+}
+
+int ffh_fold_dw_product(ffh_ctx* c, const ffh_fold_group* groups, int ngroups, float* dw, int64_t lddw, int d, int out, ffh_stream s) {
+  FFH_REQUIRE(c, groups && dw && ngroups >= 1 && d > 0 && out > 0 && lddw >= d, "fold_dw_product: bad arguments");
+  if (ngroups > FFH_FOLD_MAX_GROUPS || d % 64 || out % FFH_FOLD_NTILE) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_dw_product: d and out_dim multiples of 64, at most 64 tables");
+  FoldDwArgs a{};
+  int64_t tiles = 0;
+  for (int i = 0; i < ngroups; i++) {
+    const ffh_fold_group& gr = groups[i];
+    FFH_REQUIRE(c, gr.e && gr.p && gr.rows >= 1 && gr.rows < (1LL << 31) && gr.lde >= d && gr.col0 >= 0 && gr.col0 + d <= lddw, "fold_dw_product: bad group");
+    if (!al16(gr.e) || !al16(gr.p) || gr.lde % 4) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_dw_product: group not aligned");
+    a.grp[i] = FoldDwGroup{gr.p, gr.e, gr.lde, gr.col0, (int)gr.rows, (int)tiles};
+    tiles += ((gr.rows + FFH_FOLD_DW_CHUNK - 1) / FFH_FOLD_DW_CHUNK) * (out / 64) * (d / 64);
+    FFH_REQUIRE(c, tiles < (1LL << 30), "fold_dw_product: too many rows");
+  }
+  a.dw = dw; a.lddw = lddw; a.ngroups = ngroups; a.out = out; a.d = d; a.ntiles = (int)tiles;
+  hipLaunchKernelGGL(fold_dw_product_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, as_stream(s), a);
+  FFH_LAUNCH_CHECK(c, "fold_dw_product_kernel");
+  return FFH_OK;
+}
+
+int ffh_fold_linear_bwd_dw_plan(ffh_ctx* c, const float* x, int64_t ldx, const float* dy, int64_t lddy, const float* dw, const float* db, int in, int out,
+                                int64_t batch, const int32_t* kept, int nkept) {
+  const int rc = fold_dw_check(c, x, ldx, dy, lddy, dw, in, out, batch, kept, nkept);
+  if (rc != FFH_OK) return rc;
+  if (batch == 0 || c->math_mode != FFH_MATH_DEFAULT) return 0;
+  const GemmArgs g = fold_dw_gemm(x, ldx, dy, lddy, const_cast<float*>(dw), const_cast<float*>(db), in, out, batch);
+  if (!gemm_sk_serves(c, g, SK_FORM_DW)) return 0;      // the whole layer does not run the stream-K form: leave it where it is
+  return launch_gemm_sk_kept(c, g, kept, nkept, true, nullptr, "") == 1 ? 1 : 0;
+}
+
+int ffh_fold_linear_bwd_dw(ffh_ctx* c, const float* x, int64_t ldx, const float* dy, int64_t lddy, float* dw, float* db, int in, int out, int64_t batch,
+                           const int32_t* kept, int nkept, ffh_stream s) {
+  const int rc = fold_dw_check(c, x, ldx, dy, lddy, dw, in, out, batch, kept, nkept);
+  if (rc != FFH_OK) return rc;
+  ffh_route_clear(c);
+  if (batch == 0 || c->math_mode != FFH_MATH_DEFAULT) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_linear_bwd_dw: empty batch / math mode not served");
+  const GemmArgs g = fold_dw_gemm(x, ldx, dy, lddy, dw, db, in, out, batch);
+  if (!gemm_sk_serves(c, g, SK_FORM_DW)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_linear_bwd_dw: the layer's weight gradient does not run the stream-K form");
+  const int r = launch_gemm_sk_kept(c, g, kept, nkept, false, s, "fold_linear_bwd_dw gemm");
+  if (r < 0) return r;
+  if (r == 0) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_linear_bwd_dw: too few kept tiles for the stream-K form, deterministic mode, or a bias gradient without tile 0");
   return FFH_OK;
 }
 

@@ -111,5 +111,8 @@ int launch_gemm_sk(ffh_ctx* c, const GemmArgs& g, int form, ffh_stream s, const 
 // read in the epilogue (include/ff_hip_fold.h); g describes the whole layer.  dry: decide only (1: would launch)
 int launch_gemm_sk_fold(ffh_ctx* c, const GemmArgs& g, const unsigned long long keep[2], int nk_kept, const float* addend, int64_t ldadd, bool dry,
                         ffh_stream s, const char* name);
+// ... the weight-gradient form over the kept 128-column tiles of dW only (`tiles`: nkept ascending tile indices; include/ff_hip_fold.h); g describes
+// the whole layer's weight gradient.  dry: decide only (1: would launch)
+int launch_gemm_sk_kept(ffh_ctx* c, const GemmArgs& g, const int* tiles, int nkept, bool dry, ffh_stream s, const char* name);
 
 }  // namespace ffh_gemm

@@ -91,6 +91,15 @@ struct SkArgsFold : SkArgs {
   int64_t            ldadd;
 };
 
+// KEPT (include/ff_hip_fold.h, ffh_fold_linear_bwd_dw): the weight-gradient form over the KEPT 128-column tiles of dW only -- the columns of
+// the small tables folded out of the layer are OUTPUT tiles here, not k-tiles: the flat (tile, k-tile) space has nkept column tiles per
+// row of tiles, place() maps the column tile's index through the list to its place in x and dW, and nothing in the k-loop or its schedule
+// knows.  The bias gradient rides on the tiles with n0 == 0 as before, so tile[0] must be 0 where db is wanted (the host checks).
+struct SkArgsKept : SkArgs {
+  unsigned       nkept;
+  unsigned short tile[128];      // ascending indices of the kept 128-column tiles
+};
+
 template <int... I, class F>
 __device__ __forceinline__ void sk_static_for_impl(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N_, class F>
@@ -119,8 +128,9 @@ constexpr int SK_EP_WAVE = SK_EP_ROWS * SK_EP_LD * 4;     // bytes per wave
 // of the next tile) last, so the head usually is the last to arrive and its own part never leaves its registers.  Cross-workgroup
 // values travel as agent-scope relaxed atomics (sc1: written through / read behind the per-XCD L2s), ordered by completion (vmcnt
 // + barrier before the counter add; the loads behind the returned add + a barrier), as in embedding.hip's folds.
-template <bool AKR, bool BKR, int EPI, bool DB = false, bool SPLIT = false, int TMW = 4, bool FOLD = false>
-__global__ __launch_bounds__(256, 1) void gemm_sk_kernel(const std::conditional_t<FOLD, SkArgsFold, SkArgs> g) {
+template <bool AKR, bool BKR, int EPI, bool DB = false, bool SPLIT = false, int TMW = 4, bool FOLD = false, bool KEPT = false>
+__global__ __launch_bounds__(256, 1) void gemm_sk_kernel(const std::conditional_t<KEPT, SkArgsKept, std::conditional_t<FOLD, SkArgsFold, SkArgs>> g) {
+  static_assert(!KEPT || (EPI == SK_EPI_DW_ATOMIC && AKR && BKR && !FOLD), "kept column tiles: the weight-gradient form");
   static_assert(!FOLD || (EPI == SK_EPI_FWD && !SPLIT && !DB && TMW == 4), "kept k-tiles + addend: the whole-tile forward form");
   static_assert(!DB || (EPI == SK_EPI_DW_ATOMIC && AKR), "the bias gradient rides on the weight-gradient form");
   static_assert(!SPLIT || EPI != SK_EPI_DW_ATOMIC, "the weight gradient meets by atomics");
@@ -157,7 +167,9 @@ __global__ __launch_bounds__(256, 1) void gemm_sk_kernel(const std::conditional_
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(g.B), 0, g.b_bytes, 0x00020000);
 
   // ---- this workgroup's share of the (tile, k-tile) iteration space ----
-  const unsigned nbx = (unsigned)(g.N / SK_BN), nby = (unsigned)(g.M / BM), ntiles = nbx * nby;
+  unsigned nbx = (unsigned)(g.N / SK_BN);
+  if constexpr (KEPT) nbx = g.nkept;
+  const unsigned nby = (unsigned)(g.M / BM), ntiles = nbx * nby;
   unsigned nk = (unsigned)(g.K / SK_BK);
   if constexpr (FOLD) nk = g.nk_kept;
   // FOLD: the first kept k-tile, and the kept k-tile behind p (behind the last one: p + 1 -- never loaded, place() comes first)
@@ -200,7 +212,9 @@ __global__ __launch_bounds__(256, 1) void gemm_sk_kernel(const std::conditional_
     else lin = c.seq * G + wperm;
     if (lin >= ntiles) lin = ntiles - 1;                  // run-ahead loads past the end of the share: any valid tile
     const unsigned by = lin / nbx, bx = lin - by * nbx;
-    c.m0 = by * BM; c.n0 = bx * SK_BN;
+    c.m0 = by * BM;
+    if constexpr (KEPT) c.n0 = (unsigned)g.tile[bx] * SK_BN;      // (uniform: a scalar load from the argument block)
+    else c.n0 = bx * SK_BN;
     c.kp = FOLD ? first_kept() : c.kt;                   // (FOLD: whole tiles, c.kt == 0 here)
     c.offA = (AKR ? c.m0 * 4u : (unsigned)(c.m0 * g.lda * 4)) + c.kp * kadvA;
     c.offB = (BKR ? c.n0 * 4u : (unsigned)(c.n0 * g.ldb * 4)) + c.kp * kadvB;
@@ -675,6 +689,51 @@ int launch_gemm_sk_fold(ffh_ctx* c, const GemmArgs& g, const unsigned long long 
     if (e != hipSuccess) return ffh_fail_hip(c, e, name);
   }
   { char tok[96]; snprintf(tok, sizeof tok, "%s|sk_128x128x64|kept=%d/%d%s|wgs=%d", name, nk_kept, g.K / SK_BK, addend ? "|addend" : "", p.G); ffh_route_add(c, tok); }
+  return 1;
+}
+
+// The weight-gradient form over kept 128-column tiles of dW (include/ff_hip_fold.h): g describes the WHOLE layer's weight gradient (M = out_dim,
+// N = in_dim, K = batch, db as launch_gemm_sk takes it); tiles: nkept ascending indices below N / 128.  Served where the stream-K weight gradient
+// of a layer of nkept column tiles would run (sk_plan: nkept tiles * nk >= 8 workgroups' worth, not in deterministic mode).  dry: decide only.
+// 1: launched (dry: would be), 0: not this kernel's shape (nothing launched), < 0: error
+int launch_gemm_sk_kept(ffh_ctx* c, const GemmArgs& g, const int* tiles, int nkept, bool dry, ffh_stream s, const char* name) {
+  if (g.N % SK_BN || g.N / SK_BN > 128 || nkept < 1 || nkept > g.N / SK_BN) return 0;
+  for (int i = 0; i < nkept; i++)
+    if (tiles[i] < 0 || tiles[i] >= g.N / SK_BN || (i > 0 && tiles[i] <= tiles[i - 1])) return 0;
+  if (g.db && tiles[0] != 0) return 0;            // the bias gradient rides on the column tiles at n0 == 0
+  GemmArgs gk = g;
+  gk.N = nkept * SK_BN;
+  SkPlan p{};
+  if (!sk_plan(c, gk, SK_FORM_DW, p)) return 0;
+  const int64_t b_bytes = ((int64_t)(g.K - 1) * p.ldb + g.N) * 4;      // x over the whole width: the kept tiles lie anywhere in it
+  if (b_bytes >= (1LL << 32)) return 0;
+  if (dry) return 1;
+  SkArgsKept a{};
+  a.A = g.A; a.B = g.B; a.C = g.C; a.db = g.db;
+  a.lda = p.lda; a.ldb = p.ldb; a.ldc = g.ldc;
+  a.M = g.M; a.N = g.N; a.K = g.K; a.act = g.act;
+  a.a_bytes = (unsigned)p.a_bytes; a.b_bytes = (unsigned)b_bytes;
+  a.nkept = (unsigned)nkept;
+  for (int i = 0; i < nkept; i++) a.tile[i] = (unsigned short)tiles[i];
+  constexpr int LDSB = 2 * SK_LDS_KR + 4 * SK_EP_WAVE;
+#define FFH_SK_KEPT_LAUNCH(DBV)                                                                                  \
+  {                                                                                                              \
+    auto kern = gemm_sk_kernel<true, true, SK_EPI_DW_ATOMIC, DBV, false, 4, false, true>;                        \
+    static std::atomic<signed char> ok[64];      /* as in launch_gemm_sk: the LDS attribute once per (kernel, device) */ \
+    const int dev = c->device & 63;                                                                              \
+    if (ok[dev].load(std::memory_order_acquire) == 0) ok[dev].store(sk_set_lds(kern, LDSB) ? 1 : -1, std::memory_order_release); \
+    if (ok[dev].load(std::memory_order_acquire) < 0) return 0;                                                   \
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.G), dim3(256), LDSB, as_stream(s), a);                             \
+  }
+  if (g.db) FFH_SK_KEPT_LAUNCH(true)
+  else FFH_SK_KEPT_LAUNCH(false)
+#undef FFH_SK_KEPT_LAUNCH
+  {
+    const hipError_t e = hipGetLastError();
+    if (e == hipErrorInvalidValue || e == hipErrorInvalidConfiguration || e == hipErrorLaunchOutOfResources || e == hipErrorSharedObjectInitFailed) return 0;
+    if (e != hipSuccess) return ffh_fail_hip(c, e, name);
+  }
+  { char tok[96]; snprintf(tok, sizeof tok, "%s|sk_128x128x64|kept=%d/%d%s|wgs=%d", name, nkept, g.N / SK_BN, g.db ? "|db" : "", p.G); ffh_route_add(c, tok); }
   return 1;
 }
 

@@ -147,6 +147,7 @@ class FFConfig {
                                // driver's timed loop adapts (0)
   bool fold_small_tables;      // small embedding tables folded out of the first top layer's forward GEMM (include/ff_hip_fold.h; A/B: --no-fold-small-tables)
   int64_t fold_max_rows;       // ... tables of at most this many rows (--fold-max-rows N)
+  bool fold_dw;                // ... and out of its weight-gradient GEMM (A/B: --no-fold-dw)
   bool mlp_chain;              // a run of narrow Linear layers (every width <= 512) as one launch forward, two backward (ffh_mlp_chain_fwd / _bwd; A/B: --no-mlp-chain)
   int64_t mlp_chain_max_batch; // ... for at most this many samples per GPU (--mlp-chain-max-batch N)
   int64_t mlp_chain_fwd_max_batch;   // ... and up to this many (--mlp-chain-fwd-max-batch N)
@@ -750,11 +751,24 @@ class FFModel {
     std::vector<ffh_fold_seg> keep;        // the column runs of the layer's input the GEMM keeps
     float* P = nullptr;                    // [sum of R_t][out] products
     float* S = nullptr;                    // [local batch][out] gathered sum
+    // ... and out of the same layer's weight-gradient GEMM ("the weight gradient"): the forward-folded tables whose column blocks
+    // are whole 128-column tiles of dW.   G_t = segmented sum of dy over the table's rows  ->  GEMM over the kept column tiles  ->  dW[:, cols_t] += G_t^T E_t
+    std::vector<Embedding*> dw_tables;     // empty: the layer's weight gradient is the GEMM of before
+    std::vector<ffh_emb_table> dw_sum;     // ffh_fold_segment_sum's list (weight = G_t, io = the layer's dy)
+    std::vector<ffh_fold_group> dw_groups; // ffh_fold_dw_product's list (p = G_t)
+    std::vector<int32_t> dw_kept;          // the 128-column tiles of dW the GEMM keeps
+    float* G = nullptr;                    // [sum of R_t][out]
+    ffh_ctx* sum_ctx = nullptr;            // the segmented sum's own ctx and workspace: the model's ctx keeps its workspace and its one-shot sort note
+    void* sum_ws = nullptr;                // for the table update, which runs on another stream in the same step
   } fold;
+  ffh_event ev_fold_e_read = nullptr;      // recorded on the weight-gradient stream behind the products G_t^T E_t: the table update may overwrite E_t
+  mutable bool fold_e_read_recorded = false;
+  void fold_weight_gradient(const Linear* li, float* dbp, ffh_stream dws) const;   // the three launches above; the segmented sum first
   ffh_event ev_fold_w = nullptr;           // recorded on `stream` at the top of forward(): the optimizer of the step before has written W
   ffh_event ev_fold_done = nullptr;        // recorded on the side stream behind the gather-add
   mutable bool fold_w_recorded = false, fold_on_side = false;
   void plan_fold();                        // allocate(): the route conditions and the buffers
+  void plan_fold_dw(FoldRoute& r);         // ... of the weight-gradient half
   void fold_products_and_sum(ffh_stream s, ffh_ctx* cx) const;
   void fold_linear_forward(const Linear* li) const;
   int z_reader_layer;           // the lowest-index Linear that reads a Concat output the tables are gathered into (-1: unknown): behind ITS

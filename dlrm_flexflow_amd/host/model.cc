@@ -407,7 +407,9 @@ FFModel::~FFModel() {
   api->ffh_event_destroy(ctx, ev_z_free);
   if (ev_fold_w) api->ffh_event_destroy(ctx, ev_fold_w);
   if (ev_fold_done) api->ffh_event_destroy(ctx, ev_fold_done);
-  for (void* p : {(void*)fold.P, (void*)fold.S}) if (p) api->ffh_free(ctx, p);
+  if (ev_fold_e_read) api->ffh_event_destroy(ctx, ev_fold_e_read);
+  for (void* p : {(void*)fold.P, (void*)fold.S, (void*)fold.G, fold.sum_ws}) if (p) api->ffh_free(ctx, p);
+  if (fold.sum_ctx) api->ffh_ctx_destroy(fold.sum_ctx);
   for (auto& kv : trace_tune) for (ffh_event& e : kv.second.ev) if (e) { api->ffh_event_destroy(ctx, e); e = nullptr; }
   for (ffh_event& e : probe_ev) if (e) { api->ffh_event_destroy(ctx, e); e = nullptr; }
   api->ffh_stream_destroy(ctx, stream); api->ffh_stream_destroy(ctx, side_stream); api->ffh_stream_destroy(ctx, dw_stream); api->ffh_stream_destroy(ctx, ar_stream);
@@ -649,6 +651,24 @@ void Linear::backward_part(const FFModel& ff, int part) {
     return;
   }
   ffh_stream dws = ff.dw_stream;
+  if (part == 0 && ff.fold.layer == this && !ff.fold.dw_tables.empty()) {
+    // small tables folded out of the weight gradient (allocate(), step 8): the data gradient as the ONLY_DX call on `stream`, and behind the event
+    // that says dy is ready the segmented sum, the GEMM over the kept column tiles and the products on the weight-gradient stream -- the sum
+    // first, memory-bound beside the data-gradient GEMM.  --serial-dw: all of it on `stream`
+    if (fork) {
+      ffh_event ev = ff.layer_events[layer_index];
+      ff.check(ff.api->ffh_event_record(ff.ctx, ev, ff.stream), "event");
+      ff.check(ff.api->ffh_stream_wait_event(ff.ctx, dws, ev), "event");
+    }
+    if (dx) {
+      ff.check(ff.api->ffh_linear_bwd_ex(ff.ctx, xp, ldx, dx, lddx, yp, ldy, dyp, lddy, wp, dwp, dbp, in_padded, out_channels, b, (int)activation,
+                                         flags | FFH_LINEAR_ONLY_DX, ff.stream, nullptr), name);
+      image_dx();
+    }
+    ff.fold_weight_gradient(this, dbp, fork ? dws : ff.stream);
+    if (fork) { ff.dw_forked = true; ff.dw1_used = true; ff.dw_stream_used_directly = true; }
+    return;
+  }
   ff.check(ff.api->ffh_linear_bwd_ex(ff.ctx, xp, ldx, dx, lddx, yp, ldy, dyp, lddy, wp, dwp, dbp, in_padded, out_channels, b, (int)activation,
                                      flags, ff.stream, fork ? dws : nullptr), name);
   image_dx();

@@ -1102,11 +1102,66 @@ void FFModel::plan_fold() {
       col += in.adim[0];
     }
     r.layer = li;
+    plan_fold_dw(r);
     fold = r;
     if (!ev_fold_w) check((config.timing_events ? api->ffh_event_create : api->ffh_event_create_sync)(ctx, &ev_fold_w), "event create");
     if (!ev_fold_done) check((config.timing_events ? api->ffh_event_create : api->ffh_event_create_sync)(ctx, &ev_fold_done), "event create");
     return;
   }
+}
+
+// ... and out of the same layer's weight-gradient GEMM ("the weight gradient").  A forward-folded table is folded here as well when
+// its column block is whole 128-column tiles of dW, the layer's dy arrives final (premasked, or no activation), the step runs without launch workers,
+// profiling or the deterministic mode, the layer's backward is its own call (no chain, no pair launch), and the library runs the GEMM over the tiles
+// that are left on the stream-K kernel (ffh_fold_linear_bwd_dw_plan).  Otherwise every column stays in the GEMM; the forward fold is unaffected.
+void FFModel::plan_fold_dw(FoldRoute& r) {
+  Linear* li = r.layer;
+  if (!config.fold_dw || config.deterministic || config.profiling || dw_worker || side_worker) return;
+  if (!(li->dy_premasked || li->activation == AC_MODE_NONE) || li->pair_lower || li->bwd_exact || li->dx_image || li->dx_map) return;
+  const int64_t rows = local_rows(li->outputs[0], this);
+  if (!li->chain_bwd.empty() && mlp_chain_usable(rows, false)) return;
+  if (li->in_padded % FFH_FOLD_DW_NTILE || li->weights[0].impl->ld != li->in_padded) return;
+  const int out = li->out_channels, ntile = li->in_padded / FFH_FOLD_DW_NTILE;
+  std::vector<char> folded(ntile, 0);
+  std::vector<size_t> pick;
+  int64_t grows = 0;
+  for (size_t k = 0; k < r.tables.size(); k++) {
+    const int64_t col0 = r.groups[k].col0, d = r.tables[k]->out_channels;
+    if (col0 % FFH_FOLD_DW_NTILE || d % FFH_FOLD_DW_NTILE) continue;
+    for (int64_t t = col0 / FFH_FOLD_DW_NTILE; t < (col0 + d) / FFH_FOLD_DW_NTILE; t++) folded[t] = 1;
+    pick.push_back(k);
+    grows += r.tables[k]->num_entries;
+  }
+  if (pick.empty()) return;
+  for (int t = 0; t < ntile; t++) if (!folded[t]) r.dw_kept.push_back(t);
+  const Tensor &x = li->inputs[0], &y = li->outputs[0];
+  const int plan = r.dw_kept.empty() ? 0 : api->fold->ffh_fold_linear_bwd_dw_plan(ctx, (const float*)x.impl->ptr, x.impl->ld, y.impl->grad, y.impl->grad_ld, li->weights[0].impl->grad,
+                                                                                  li->use_bias ? li->weights[1].impl->grad : nullptr, li->in_padded, out, rows,
+                                                                                  r.dw_kept.data(), (int)r.dw_kept.size());
+  if (plan != 1) { r.dw_kept.clear(); return; }
+  const Embedding* e0 = r.tables[pick[0]];
+  const int L = (int)e0->inputs[0].adim[0];
+  r.G = (float*)dmalloc((size_t)grows * out * 4);
+  const size_t ws_bytes = api->ffh_embedding_bwd_workspace_bytes((int)pick.size(), L, out, local_batch) + 256;
+  r.sum_ws = dmalloc(ws_bytes);
+  if (api->ffh_ctx_create(&r.sum_ctx, config.device) != FFH_OK || !r.sum_ctx) die("fold: ffh_ctx_create(device %d) failed", config.device);
+  check(api->ffh_ctx_set_workspace(r.sum_ctx, r.sum_ws, ws_bytes), "set workspace");
+  int64_t grow = 0;
+  for (size_t k : pick) {
+    Embedding* e = r.tables[k];
+    float* g = r.G + (size_t)grow * out;
+    r.dw_tables.push_back(e);
+    r.dw_groups.push_back(ffh_fold_group{(const float*)e->weights[0].impl->ptr, (int64_t)e->out_channels, r.groups[k].col0, g, (int64_t)e->num_entries});
+    ffh_emb_table t;
+    t.idx = (const int64_t*)e->inputs[0].impl->ptr;
+    t.weight = g;
+    t.num_entries = e->num_entries;
+    t.io = y.impl->grad;
+    t.ld = y.impl->grad_ld;
+    r.dw_sum.push_back(t);
+    grow += e->num_entries;
+  }
+  if (!ev_fold_e_read) check((config.timing_events ? api->ffh_event_create : api->ffh_event_create_sync)(ctx, &ev_fold_e_read), "event create");
 }
 
 void FFModel::init_layers() {

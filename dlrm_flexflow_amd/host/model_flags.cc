@@ -42,6 +42,7 @@ FFConfig::FFConfig() {
   mlp_chain = true;
   fold_small_tables = true;
   fold_max_rows = 7420;      // the measured threshold (2208 and 7420 tried)
+  fold_dw = true;
   trace_mode = -1;
   bucket_allreduce = -1;
   allreduce_bucket_floats = 1 << 20;
@@ -164,6 +165,7 @@ void FFConfig::parse_args(char** argv, int argc) {
     if (is("--no-fused-pair")) { fuse_pair = false; continue; }
     if (is("--no-mlp-chain")) { mlp_chain = false; continue; }
     if (is("--no-fold-small-tables")) { fold_small_tables = false; continue; }
+    if (is("--no-fold-dw")) { fold_dw = false; continue; }
     if (is("--fold-max-rows")) { fold_max_rows = atoll(next()); continue; }
     if (is("--always-replay")) { trace_mode = 1; continue; }
     if (is("--adaptive-replay")) { trace_mode = 0; continue; }

@@ -142,6 +142,27 @@ void FFModel::fold_products_and_sum(ffh_stream s, ffh_ctx* cx) const {
                                        fold.S, li->out_channels, s), "fold_gather_add");
 }
 
+// The weight gradient of the layer the tables are folded out of, on `dws` (which stands behind "dy is ready"): G_t = the segmented sum of dy over
+// table t's rows, the layer's weight-gradient GEMM over the column tiles that are left (with the bias gradient), dW[:, cols_t] += G_t^T E_t.
+// The same launches with the same arguments every step: a captured step holds them as they are.
+void FFModel::fold_weight_gradient(const Linear* li, float* dbp, ffh_stream dws) const {
+  const Tensor &x = li->inputs[0], &y = li->outputs[0];
+  const Embedding* e0 = fold.dw_tables[0];
+  const int64_t b = local_rows(y, this);
+  const int out = li->out_channels, ng = (int)fold.dw_groups.size();
+  if (api->fold->ffh_fold_segment_sum(fold.sum_ctx, fold.dw_sum.data(), ng, e0->inputs[0].adim[0], out, b, dws) != FFH_OK)
+    die("%s: fold_segment_sum failed: %s", li->name, api->ffh_last_error_string(fold.sum_ctx));
+  // The products in FRONT of the GEMM (both only add into dW, disjoint columns): they read the tables' rows, which this step's table update
+  // overwrites on the side stream as soon as the data gradients are complete -- long before the GEMM ends.  The update waits for ev_fold_e_read.
+  check(api->fold->ffh_fold_dw_product(ctx, fold.dw_groups.data(), ng, li->weights[0].impl->grad, li->in_padded, e0->out_channels, out, dws), "fold_dw_product");
+  // (--serial-dw as well: "gradients ready" is recorded behind the data-gradient kernel, in front of these launches)
+  check(api->ffh_event_record(ctx, ev_fold_e_read, dws), "fold: table rows read");
+  fold_e_read_recorded = true;
+  // (dbp: null where the layer above has produced this layer's bias gradient already -- Linear::backward_part consumed db_from_upper)
+  check(api->fold->ffh_fold_linear_bwd_dw(ctx, (const float*)x.impl->ptr, x.impl->ld, y.impl->grad, y.impl->grad_ld, li->weights[0].impl->grad, dbp, li->in_padded, out, b,
+                                          fold.dw_kept.data(), (int)fold.dw_kept.size(), dws), li->name);
+}
+
 // forward() of the layer the tables are folded out of.  The gather has been joined (the Concat below comes first), so `stream` stands behind
 // this step's tables either way: the sum is waited for where the side stream computed it, and computed right here otherwise
 void FFModel::fold_linear_forward(const Linear* li) const {
@@ -172,6 +193,7 @@ void FFModel::issue_embedding_update_on_side_stream() const {
     });
   } else {
     check(api->ffh_stream_wait_event(ctx, side_stream, ev_grad_ready), "event");
+    if (fold_e_read_recorded) check(api->ffh_stream_wait_event(ctx, side_stream, ev_fold_e_read), "fold: table rows read");      // (fold_weight_gradient)
     probe_record(2, side_stream, ctx);
     embedding_group_update(side_stream);
     probe_record(3, side_stream, ctx);
@@ -223,6 +245,7 @@ void FFModel::backward(int _seq_length) {
   const float scale = (bce || loss_type == LOSS_MEAN_SQUARED_ERROR_AVG_REDUCE) ? 1.0f / (float)fin.adim[fin.numDim - 1] : 1.0f;
   if (fin.impl->grad_ld != fin.adim[0] || fin.impl->ld != fin.adim[0]) die("final layer output must be contiguous");
   dw_forked = false;
+  fold_e_read_recorded = false;
   opt_next_done = false;
   // the click-probability layer (out = 1): loss step + metrics + the layer's whole backward in ONE launch; any other last
   // layer: the loss kernel, then the layer's own backward

@@ -1,5 +1,5 @@
 /* ff_hip_fold.h -- optional extension of the kernel C-ABI (include/ff_hip.h): small embedding tables folded out of the forward
- * GEMM of the Linear layer that reads their rows through a Concat.
+ * GEMM, and (ABI 2, further down) out of the weight-gradient GEMM, of the Linear layer that reads their rows through a Concat.
  *
  * A library may export this list or not; include/ff_hip.h and its symbol list are unchanged by it.  libffhip.so exports it,
  * the CPU oracle does not.  Callers load it separately (host/backend: KernelApi::fold, null when absent).
@@ -34,12 +34,14 @@
 extern "C" {
 #endif
 
-#define FFH_FOLD_ABI_VERSION 1
+#define FFH_FOLD_ABI_VERSION 2
 
 #define FFH_FOLD_KTILE      16    /* granularity of every reduction-depth segment and of D, in floats          */
 #define FFH_FOLD_NTILE      64    /* out_dim of the folded layer is a multiple of this                           */
 #define FFH_FOLD_MAX_GROUPS 64    /* tables per ffh_fold_product launch (= FFH_MAX_TABLES)                       */
 #define FFH_FOLD_MAX_SEGS   32    /* kept segments per ffh_fold_linear_fwd call                                  */
+#define FFH_FOLD_DW_NTILE   128   /* width of a column tile of dW in ffh_fold_linear_bwd_dw                      */
+#define FFH_FOLD_DW_CHUNK   256   /* rows of a table per partial product of ffh_fold_dw_product                  */
 
 /* one table of ffh_fold_product */
 typedef struct ffh_fold_group {
@@ -85,11 +87,52 @@ int ffh_fold_linear_fwd(ffh_ctx* ctx, const float* x, int64_t ldx, float* y, int
 int ffh_fold_linear_fwd_plan(ffh_ctx* ctx, const float* x, int64_t ldx, const float* y, int64_t ldy, const float* w, const float* bias,
                              int in_dim, int out_dim, int64_t batch, const ffh_fold_seg* keep, int nkeep, const float* addend, int64_t ldadd);
 
+/* ---- the weight gradient of the same layer (ABI 2) --------------------------------------------------------------------------------------
+ * The column block of dW that faces a folded table is dy^T X_t, and X_t holds copies of the table's rows:
+ *
+ *     dW[:, cols_t] = dy^T X_t = G_t^T E_t,      G_t[r][:] = sum over the hits (b, l) of row r, id_t[b][l] == r, of dy[b][:]      (G_t: [R_t][out_dim])
+ *
+ * ffh_fold_segment_sum forms G, ffh_fold_dw_product adds G_t^T E_t into dW, ffh_fold_linear_bwd_dw is the layer's weight gradient over the column
+ * tiles that are left.  dy is FINAL in all three (the activation derivative applied by whoever produced it, FFH_LINEAR_DY_PREMASKED's meaning).
+ * Orders: G in the canonical order of the fused table update (below); the other two add partial sums into dW by float atomics, as the weight
+ * gradient of ffh_linear_bwd does on this shape: not the same bits from run to run.  Each meets the bound above against float64. */
+
+/* G_t[r][0 .. width) = sum over the hits of row r of dy[b][0 .. width); rows not hit: exactly 0.  `tables` as ffh_embedding_bwd_sgd_fused_multi takes
+ * them: idx = [batch][in_dim] ids, weight = G_t ([num_entries][width] contiguous, overwritten), num_entries = R_t, io = dy, ld = its leading dimension.
+ * THE ORDER OF THE SUM IS THE CONTRACT: the one include/ff_hip.h documents for the fused table update ("Canonical (deterministic) summation order":
+ * hits sorted by (row, position), added left to right inside blocks of 32, the blocks' partials inside blocks of 1024, then those) -- the entry zeroes G
+ * and runs that update's own sort and ordered reduction with lr = -1, w = fmaf(1, sum, 0): the same bits on every run and stream.  Needs
+ * ffh_embedding_bwd_workspace_bytes(ntables, in_dim, width, batch) of workspace attached to ctx, and spoils a pending ffh_embedding_bwd_sort_multi
+ * note on that workspace like any fused update: give it a ctx and a workspace of its own beside a table update in flight.  Width limits as the update's. */
+int ffh_fold_segment_sum(ffh_ctx* ctx, const ffh_emb_table* tables, int ntables, int in_dim, int width, int64_t batch, ffh_stream s);
+
+/* dw[o][col0_t + j] += sum_r G_t[r][o] E_t[r][j], j < d, for ngroups tables in ONE launch.  groups[t]: e = E_t, lde, col0 = col0_t, p = G_t ([rows][out_dim]
+ * contiguous, read), rows = R_t.  dw is the layer's [out_dim][lddw] weight gradient, pre-zeroed or accumulating: the entry ADDS.  The rows of a table are
+ * cut into chunks of FFH_FOLD_DW_CHUNK whose partial products meet in dw by float atomics.  d % 64 == 0, out_dim % FFH_FOLD_NTILE == 0, 16-byte aligned e
+ * and p, lde % 4 == 0, 1 <= ngroups <= FFH_FOLD_MAX_GROUPS; anything else: FFH_ERR_UNSUPPORTED. */
+int ffh_fold_dw_product(ffh_ctx* ctx, const ffh_fold_group* groups, int ngroups, float* dw, int64_t lddw, int d, int out_dim, ffh_stream s);
+
+/* The weight gradient of ffh_linear_bwd over the KEPT column tiles only:
+ *     dw[o][k] += sum_b dy[b][o] x[b][k]   for k in the tiles [FFH_FOLD_DW_NTILE kept[i], FFH_FOLD_DW_NTILE (kept[i] + 1)), i < nkept (ascending);
+ *     db[o]    += sum_b dy[b][o]           when db != NULL, which needs kept[0] == 0 (the bias gradient rides on the first column of tiles)
+ * dw is [out_dim][in_dim] contiguous.  Every other column of dw is left as it is.  Served only on the stream-K weight-gradient kernel, and only where
+ * the whole layer's weight gradient runs on it too: exact fp32 math mode, not the deterministic mode, out_dim and in_dim multiples of 128, batch a
+ * multiple of 64, aligned operands, and nkept column tiles that still fill the chip (nkept * (out_dim / 128) * (batch / 64) >= 8 per workgroup).
+ * Anything else: FFH_ERR_UNSUPPORTED, nothing launched, nothing written.  ffh_linear_last_route names the form: "...|kept=a/b|...". */
+int ffh_fold_linear_bwd_dw(ffh_ctx* ctx, const float* x, int64_t ldx, const float* dy, int64_t lddy, float* dw, float* db, int in_dim, int out_dim,
+                           int64_t batch, const int32_t* kept, int nkept, ffh_stream s);
+
+/* Whether the call above would be served for these arguments (nothing is launched): 1 = yes; 0 = no (it would return FFH_ERR_UNSUPPORTED);
+ * negative: bad arguments. */
+int ffh_fold_linear_bwd_dw_plan(ffh_ctx* ctx, const float* x, int64_t ldx, const float* dy, int64_t lddy, const float* dw, const float* db, int in_dim,
+                                int out_dim, int64_t batch, const int32_t* kept, int nkept);
+
 #ifdef __cplusplus
 }
 #endif
 
 #define FFH_FOLD_API_LIST(X) \
-  X(ffh_fold_abi_version) X(ffh_fold_product) X(ffh_fold_gather_add) X(ffh_fold_linear_fwd) X(ffh_fold_linear_fwd_plan)
+  X(ffh_fold_abi_version) X(ffh_fold_product) X(ffh_fold_gather_add) X(ffh_fold_linear_fwd) X(ffh_fold_linear_fwd_plan) \
+  X(ffh_fold_segment_sum) X(ffh_fold_dw_product) X(ffh_fold_linear_bwd_dw) X(ffh_fold_linear_bwd_dw_plan)
 
 #endif /* FF_HIP_FOLD_H_ */
