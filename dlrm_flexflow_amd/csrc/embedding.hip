@@ -18,6 +18,7 @@
 // kernels are emb_sort.h; the apply phase's kernels (emb_reduce.h) and the row rules (emb_row_rules.h) are compiled per weight type in
 // embedding_update_f32.hip / embedding_update_bf16.hip and reached through emb_update_launch_f32 / _bf16.
 #include "emb_reduce.h"
+#include "fold_sum.h"
 #include "lr_state.h"
 
 #include <type_traits>
@@ -355,6 +356,25 @@ static void set_bf16_keys(Bf16Keys& keys, Bf16AdamKeys& adam, const Bf16Cfg& b16
   for (int i = 0; i < nt; i++) { k.s1[i] = states[i].s1; k.table[i] = b16.keys.table[i]; k.col0[i] = b16.keys.col0[i]; }
   adam = k;
 }
+// the stable passes of the sort, one digit of rb bits each: pass p reads buffer p % 2 (pass 0: the int64 ids) and writes buffer (p + 1) % 2
+static void launch_sort_passes(SortArgs& sa, uint2* const kbuf[2], int passes, int rb, int E, dim3 sgrid, ffh_stream s) {
+  for (int p = 0; p < passes; p++) {
+    sa.shift = p * rb;
+    sa.pass = p;
+    sa.src = kbuf[p & 1];
+    sa.dst = kbuf[(p + 1) & 1];
+#define FFH_SORT_PASS(FIRSTV, EV)                                                                              \
+    hipLaunchKernelGGL((radix_hist_kernel<FIRSTV, EV>), sgrid, dim3(kSortThreads), 0, as_stream(s), sa);      \
+    hipLaunchKernelGGL((radix_scatter_kernel<FIRSTV, EV>), sgrid, dim3(kSortThreads), 0, as_stream(s), sa);
+    if (p == 0) {
+      switch (E) { case 1: FFH_SORT_PASS(true, 1) break; case 2: FFH_SORT_PASS(true, 2) break; case 4: FFH_SORT_PASS(true, 4) break; default: FFH_SORT_PASS(true, 8) break; }
+    } else {
+      switch (E) { case 1: FFH_SORT_PASS(false, 1) break; case 2: FFH_SORT_PASS(false, 2) break; case 4: FFH_SORT_PASS(false, 4) break; default: FFH_SORT_PASS(false, 8) break; }
+    }
+#undef FFH_SORT_PASS
+  }
+}
+
 static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L, int D, int64_t batch,
                           int aggr, float lr, ffh_stream s, const bool do_sort, const bool do_apply,
                           const ffh_sparse_opt* opt = nullptr, const ffh_emb_state* states = nullptr, const Bf16Cfg* b16 = nullptr,
@@ -495,22 +515,7 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   uint2* kbuf[2] = {(uint2*)(ws + lay.kp_a), (uint2*)(ws + lay.kp_b)};
   dim3 sgrid((unsigned)lay.nblk, (unsigned)nt);
   const int E = sort_per_thread(nt, N);
-  for (int p = 0; p < passes && do_sort; p++) {
-    sa.shift = p * rb;
-    sa.pass = p;
-    // pass p reads buffer p%2 (pass 0: the int64 ids) and writes buffer (p+1)%2
-    sa.src = kbuf[p & 1];
-    sa.dst = kbuf[(p + 1) & 1];
-#define FFH_SORT_PASS(FIRSTV, EV)                                                                              \
-    hipLaunchKernelGGL((radix_hist_kernel<FIRSTV, EV>), sgrid, dim3(kSortThreads), 0, as_stream(s), sa);      \
-    hipLaunchKernelGGL((radix_scatter_kernel<FIRSTV, EV>), sgrid, dim3(kSortThreads), 0, as_stream(s), sa);
-    if (p == 0) {
-      switch (E) { case 1: FFH_SORT_PASS(true, 1) break; case 2: FFH_SORT_PASS(true, 2) break; case 4: FFH_SORT_PASS(true, 4) break; default: FFH_SORT_PASS(true, 8) break; }
-    } else {
-      switch (E) { case 1: FFH_SORT_PASS(false, 1) break; case 2: FFH_SORT_PASS(false, 2) break; case 4: FFH_SORT_PASS(false, 4) break; default: FFH_SORT_PASS(false, 8) break; }
-    }
-#undef FFH_SORT_PASS
-  }
+  if (do_sort) launch_sort_passes(sa, kbuf, passes, rb, E, sgrid, s);
   FFH_LAUNCH_CHECK(c, "radix sort");
   if (!do_apply) return FFH_OK;
 
@@ -585,6 +590,43 @@ int ffh_embedding_bwd_sgd_fused(ffh_ctx* c, const int64_t* idx, const float* g, 
 }
 
 }  // extern "C"
+
+// fold_sum.h: the sort alone, complete (no bucket form, no one-launch form), for a caller that reduces the list itself.  Every table runs
+// the passes its own ids need; its result lies in buffer (passes % 2).
+int ffh_emb::emb_sort_full(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L, int D, int64_t batch, ffh_stream s, FullSort* out) {
+  const int64_t N = batch * L;
+  const BwdLayout lay = bwd_layout(nt, L, D, batch);
+  char* ws = (char*)c->ws;
+  if (c->emb_sorted_ws == c->ws) c->emb_sorted_ws = nullptr;
+  int64_t maxR = 1;
+  for (int i = 0; i < nt; i++) maxR = tables[i].num_entries > maxR ? tables[i].num_entries : maxR;
+  if (maxR > (1LL << 32)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_segment_sum: num_entries > 2^32");
+  int bits = 1;
+  while (bits < 32 && ((maxR - 1) >> bits) != 0) bits++;
+  const int passes = (bits + kMaxRadixBits - 1) / kMaxRadixBits;
+  const int rb = (bits + passes - 1) / passes;
+  SortArgs sa;
+  memset(&sa, 0, sizeof sa);
+  uint2* kbuf[2] = {(uint2*)(ws + lay.kp_a), (uint2*)(ws + lay.kp_b)};
+  for (int i = 0; i < nt; i++) {
+    sa.idx[i] = tables[i].idx;
+    int tb = 1;
+    while (tb < 32 && ((tables[i].num_entries - 1) >> tb) != 0) tb++;
+    const int np = (tb + rb - 1) / rb;
+    sa.npass[i] = (uint8_t)np;
+    out->kp[i] = kbuf[np & 1] + (int64_t)i * N;
+  }
+  sa.bstart = (uint32_t*)(ws + lay.bstart);
+  sa.hist = (uint32_t*)(ws + lay.hist);
+  sa.N = N; sa.nblk = lay.nblk; sa.bits = rb;
+  sa.clear[0] = (uint32_t*)(ws + lay.meta1); sa.clear[1] = (uint32_t*)(ws + lay.arrive);      // (nclear = 0: this caller has no counters to clear)
+  launch_sort_passes(sa, kbuf, passes, rb, sort_per_thread(nt, N), dim3((unsigned)lay.nblk, (unsigned)nt), s);
+  FFH_LAUNCH_CHECK(c, "radix sort");
+  out->partial0 = (float*)(ws + lay.partial);
+  out->partial1 = (float*)(ws + lay.partial1);
+  out->passes = passes;
+  return FFH_OK;
+}
 
 // ---------------------------------------------------------------------------
 // bf16 tables (include/ff_hip_bf16.h): the fp32 launchers with 16-bit weight rows, the numerics of include/ffh_bf16.h

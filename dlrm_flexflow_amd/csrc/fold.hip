@@ -13,8 +13,10 @@
 // Order of the sum per element: segments in list order, groups of 16 ascending, e = 0..3, the MFMA's own order over q: fixed.
 //
 // The weight gradient of the same layer (ABI 2): dW[:, cols_t] = G_t^T E_t with G_t the segmented sum of dy over the table's rows -- the sum by
-// embedding.hip's fused update on zeroed rows (ffh_fold_segment_sum), the products by fold_dw_product_kernel, the GEMM over the column tiles
-// that are left by linear_sk.hip's KEPT instantiation (ffh_fold_linear_bwd_dw).
+// fold_sum.hip's wide-row kernels behind embedding.hip's sort, or by embedding.hip's fused update on zeroed rows where those do not serve
+// (ffh_fold_segment_sum), the products by fold_dw_product_kernel, the GEMM over the column tiles that are left by linear_sk.hip's KEPT
+// instantiation (ffh_fold_linear_bwd_dw).
+#include "fold_sum.h"
 #include "linear_gemm.h"
 
 #include "../../include/ff_hip_fold.h"
@@ -373,8 +375,9 @@ int ffh_fold_linear_fwd(ffh_ctx* c, const float* x, int64_t ldx, float* y, int64
   return FFH_OK;
 }
 
-// G_t = the segmented sum of dy over the hits of every row: the fused table update on zeroed rows with lr = -1 (w = fmaf(1, sum, 0) = sum), so the
-// sort, the ordered reduction and their summation order are embedding.hip's, launch for launch
+// G_t = the segmented sum of dy over the hits of every row, in the fused table update's canonical order.  Wide aligned rows: that update's sort run to
+// completion + fold_sum.hip's two launches.  Anything else: the fused table update itself on zeroed rows with lr = -1 (w = fmaf(1, sum, 0) = sum), so
+// the sort, the ordered reduction and their summation order are embedding.hip's, launch for launch
 int ffh_fold_segment_sum(ffh_ctx* c, const ffh_emb_table* tables, int ntables, int in_dim, int width, int64_t batch, ffh_stream s) {
   FFH_REQUIRE(c, tables && ntables >= 1 && in_dim >= 1 && width > 0 && batch >= 0, "fold_segment_sum: bad arguments");
   if (ntables > FFH_MAX_TABLES || batch * in_dim >= (1LL << 31)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_segment_sum: at most 64 tables, batch * in_dim < 2^31");
@@ -382,6 +385,10 @@ int ffh_fold_segment_sum(ffh_ctx* c, const ffh_emb_table* tables, int ntables, i
     FFH_REQUIRE(c, tables[t].weight && tables[t].num_entries >= 1 && (batch == 0 || (tables[t].idx && tables[t].io && tables[t].ld >= width)), "fold_segment_sum: bad table");
   if (batch > 0 && (!c->ws || c->ws_bytes < ffh_embedding_bwd_workspace_bytes(ntables, in_dim, width, batch) || ((uintptr_t)c->ws & 15)))
     return ffh_fail(c, FFH_ERR_WORKSPACE, "fold_segment_sum: workspace too small (ffh_embedding_bwd_workspace_bytes) or not 16-byte aligned");
+  if (batch > 0) {      // wide aligned rows: fold_sum.hip, which writes every row of G itself
+    const int wide = ffh_emb::fold_sum_wide(c, tables, ntables, in_dim, width, batch, s);
+    if (wide != 0) return wide < 0 ? wide : FFH_OK;
+  }
   for (int t = 0; t < ntables;) {      // tables that lie back to back (the usual case: one buffer) are cleared by one memset
     char* p0 = (char*)tables[t].weight;
     size_t bytes = 0;

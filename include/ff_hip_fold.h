@@ -100,8 +100,14 @@ int ffh_fold_linear_fwd_plan(ffh_ctx* ctx, const float* x, int64_t ldx, const fl
 /* G_t[r][0 .. width) = sum over the hits of row r of dy[b][0 .. width); rows not hit: exactly 0.  `tables` as ffh_embedding_bwd_sgd_fused_multi takes
  * them: idx = [batch][in_dim] ids, weight = G_t ([num_entries][width] contiguous, overwritten), num_entries = R_t, io = dy, ld = its leading dimension.
  * THE ORDER OF THE SUM IS THE CONTRACT: the one include/ff_hip.h documents for the fused table update ("Canonical (deterministic) summation order":
- * hits sorted by (row, position), added left to right inside blocks of 32, the blocks' partials inside blocks of 1024, then those) -- the entry zeroes G
- * and runs that update's own sort and ordered reduction with lr = -1, w = fmaf(1, sum, 0): the same bits on every run and stream.  Needs
+ * hits sorted by (row, position), added left to right inside blocks of 32, the blocks' partials inside blocks of 1024, then those): the same bits on
+ * every run and stream, whichever of the two forms below produces them.  The entry zeroes G, then
+ *   wide rows (fp32 dy, width % 256 == 0, dy and every G_t 16-byte aligned, ld % 4 == 0): the update's index-only LSD sort run to completion (no bucket
+ *     form, no one-launch form), then two launches of their own (csrc/fold_sum.hip): one workgroup per (table, 1024-block of the sorted list, 256
+ *     columns) adds the runs of its 32-blocks and their partials in list order and stores every row that lies inside the block; a second, small launch
+ *     adds the rows that cross 1024-block boundaries, block by block.  No arrival counters, no atomics; plain stores only.
+ *   every other call: that update's own sort and ordered reduction with lr = -1, w = fmaf(1, sum, 0), launch for launch.
+ * ffh_embedding_last_route(ctx) names the form: "fold_sum:wide|slice=256|lsd:passes=P", or the update's own token.  Needs
  * ffh_embedding_bwd_workspace_bytes(ntables, in_dim, width, batch) of workspace attached to ctx, and spoils a pending ffh_embedding_bwd_sort_multi
  * note on that workspace like any fused update: give it a ctx and a workspace of its own beside a table update in flight.  Width limits as the update's. */
 int ffh_fold_segment_sum(ffh_ctx* ctx, const ffh_emb_table* tables, int ntables, int in_dim, int width, int64_t batch, ffh_stream s);
