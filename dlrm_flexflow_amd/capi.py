@@ -891,6 +891,11 @@ _SIGS_FOLD = {
     "ffh_fold_dw_product": (I, [P, C.POINTER(FoldGroup), I, P, L, I, I, P]),
     "ffh_fold_linear_bwd_dw": (I, [P, P, L, P, L, P, P, I, I, L, C.POINTER(C.c_int32), I, P]),
     "ffh_fold_linear_bwd_dw_plan": (I, [P, P, L, P, L, P, P, I, I, L, C.POINTER(C.c_int32), I]),
+    # ABI 3: the data gradient over kept column tiles (x, ldx, dx, lddx, dy, lddy, w, in, out, batch, flags, kept, nkept, colsum, event, stream)
+    "ffh_fold_linear_bwd_dx": (I, [P, P, L, P, L, P, L, P, I, I, L, I, C.POINTER(C.c_int32), I, P, P, P]),
+    "ffh_fold_linear_bwd_dx_plan": (I, [P, P, L, P, L, P, L, P, I, I, L, I, C.POINTER(C.c_int32), I, P]),
+    "ffh_fold_table_update": (I, [P, C.POINTER(FoldGroup), I, P, L, I, I, C.c_float, P]),
+    "ffh_fold_table_update_lr": (I, [P, C.POINTER(FoldGroup), I, P, L, I, I, P, P]),
 }
 
 

@@ -16,8 +16,13 @@
 // fold_sum.hip's wide-row kernels behind embedding.hip's sort, or by embedding.hip's fused update on zeroed rows where those do not serve
 // (ffh_fold_segment_sum), the products by fold_dw_product_kernel, the GEMM over the column tiles that are left by linear_sk.hip's KEPT
 // instantiation (ffh_fold_linear_bwd_dw).
+//
+// The data gradient (ABI 3): the only reader of dX[:, cols_t] is table t's update, and sum_hits dX[b][cols_t] = G_t W[:, cols_t] -- the GEMM over the
+// column tiles that are left by linear_sk.hip's KEPT data-gradient instantiations (ffh_fold_linear_bwd_dx), the tables' plain-SGD step as one dense
+// product from the G the weight gradient has formed already (fold_table_update_kernel).
 #include "fold_sum.h"
 #include "linear_gemm.h"
+#include "lr_state.h"
 
 #include "../../include/ff_hip_fold.h"
 
@@ -219,7 +224,133 @@ __global__ __launch_bounds__(256) void fold_dw_product_kernel(const FoldDwArgs g
   }
 }
 
+// fold_table_update_kernel (ABI 3): E[r][d] = fmaf(-lr, sum_o G[r][o] W[o][col0 + d], E[r][d]) -- G k-contiguous, W rows-are-k.  One wave owns 32 rows x 64
+// columns of one table over the whole depth `out`: a 16-deep group is 16 bytes of G per lane (lane (c, q): o = 16 j + 4 q + {0..3} of rows r0 + 16 mt + c,
+// fold_gemm_kernel's image) and four 16-byte loads of W (rows o = 16 j + 4 q + e, e = 0..3, columns d0 + 4 c + {0..3}: fold_dw_product_kernel's image, ONE
+// depth step of FOUR 16-wide column tiles, tile tn holding columns 4 c + tn); component e of G meets row e of W in MFMA e.  W is the MFMA's row operand, so
+// lane (c, q) ends up with columns d0 + 4 (4 q + i) + tn of row r0 + 16 mt + c: for every i four consecutive columns, 16 bytes of E read, updated and stored.
+// The next group's operands are in flight while the MFMAs of this one run.  Order per element: j ascending, e = 0..3, the MFMA's own order over q; one fmaf.
+// Rows behind the table's last: loaded from its last row, never stored.  Nothing is shared between waves: no LDS, no atomics.
+struct FoldUpdGroup { const float* g; float* e; int64_t lde; int64_t col0; int rows; int tile0; };   // tile0: the group's first wave tile in the launch
+struct FoldUpdArgs {
+  FoldUpdGroup grp[FFH_FOLD_MAX_GROUPS];
+  const float* w; int64_t ldw;
+  const float* lr_ptr; float lr;      // the rate: *lr_ptr where given (include/ff_hip_lr.h), else lr
+  int ngroups, out, d, ntiles;
+};
+static_assert(sizeof(FoldUpdArgs) <= 4096, "kernel arguments");
+
+__global__ __launch_bounds__(256) void fold_table_update_kernel(const FoldUpdArgs g) {
+  ffh_kernel_prio();
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int c = lane & 15, q = lane >> 4;
+  const int wt = (int)blockIdx.x * 4 + wave;
+  if (wt >= g.ntiles) return;
+  int gi = 0;
+  while (gi + 1 < g.ngroups && g.grp[gi + 1].tile0 <= wt) gi++;       // uniform
+  const FoldUpdGroup G = g.grp[gi];
+  const int dt = g.d / 64, local = wt - G.tile0;
+  const int r0 = (local / dt) * 32, d0 = (local % dt) * 64;
+  const float nlr = -(g.lr_ptr ? *g.lr_ptr : g.lr);
+  const float* gp[2];
+#pragma unroll
+  for (int mt = 0; mt < 2; mt++) {
+    int r = r0 + 16 * mt + c;
+    if (r > G.rows - 1) r = G.rows - 1;                                // rows behind the table: any valid row, never stored
+    gp[mt] = G.g + (int64_t)r * g.out + 4 * q;
+  }
+  const float* wp = g.w + (int64_t)(4 * q) * g.ldw + G.col0 + d0 + 4 * c;
+  f32x4 acc[2][4];
+#pragma unroll
+  for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+    for (int tn = 0; tn < 4; tn++) acc[mt][tn] = f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 a[2], b[4], an[2], bn[4];
+  auto load16 = [&](int k, f32x4* av, f32x4* bv) {      // depth k .. k + 15
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++) av[mt] = *reinterpret_cast<const f32x4*>(gp[mt] + k);
+#pragma unroll
+    for (int e = 0; e < 4; e++) bv[e] = *reinterpret_cast<const f32x4*>(wp + (int64_t)(k + e) * g.ldw);
+  };
+  load16(0, a, b);
+  for (int k = 0; k < g.out; k += 16) {
+    if (k + 16 < g.out) load16(k + 16, an, bn);         // uniform
+#pragma unroll
+    for (int e = 0; e < 4; e++)
+#pragma unroll
+      for (int tn = 0; tn < 4; tn++)
+#pragma unroll
+        for (int mt = 0; mt < 2; mt++) acc[mt][tn] = __builtin_amdgcn_mfma_f32_16x16x4f32(b[e][tn], a[mt][e], acc[mt][tn], 0, 0, 0);
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++) a[mt] = an[mt];
+#pragma unroll
+    for (int e = 0; e < 4; e++) b[e] = bn[e];
+  }
+#pragma unroll
+  for (int mt = 0; mt < 2; mt++) {
+    const int r = r0 + 16 * mt + c;
+    if (r >= G.rows) continue;
+    float* erow = G.e + (int64_t)r * G.lde + d0 + 16 * q;
+    f32x4 old[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) old[i] = *reinterpret_cast<const f32x4*>(erow + 4 * i);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      f32x4 v;
+      v.x = fmaf(nlr, acc[mt][0][i], old[i].x); v.y = fmaf(nlr, acc[mt][1][i], old[i].y);
+      v.z = fmaf(nlr, acc[mt][2][i], old[i].z); v.w = fmaf(nlr, acc[mt][3][i], old[i].w);
+      *reinterpret_cast<f32x4*>(erow + 4 * i) = v;
+    }
+  }
+}
+
 inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int fold_table_update_launch(ffh_ctx* c, const ffh_fold_group* groups, int ngroups, const float* w, int64_t ldw, int d, int out, const float* lr_ptr, float lr,
+                             ffh_stream s) {
+  FFH_REQUIRE(c, groups && w && ngroups >= 1 && d > 0 && out > 0 && ldw >= d, "fold_table_update: bad arguments");
+  if (ngroups > FFH_FOLD_MAX_GROUPS || d % 64 || out % FFH_FOLD_NTILE || !al16(w) || ldw % 4)
+    return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_table_update: d and out_dim multiples of 64, at most 64 tables, aligned weight");
+  FoldUpdArgs a{};
+  int64_t tiles = 0;
+  for (int i = 0; i < ngroups; i++) {
+    const ffh_fold_group& gr = groups[i];
+    FFH_REQUIRE(c, gr.e && gr.p && gr.rows >= 1 && gr.rows < (1LL << 31) && gr.lde >= d && gr.col0 >= 0 && gr.col0 + d <= ldw, "fold_table_update: bad group");
+    if (!al16(gr.e) || !al16(gr.p) || gr.lde % 4 || gr.col0 % 4) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_table_update: group not aligned");
+    a.grp[i] = FoldUpdGroup{gr.p, const_cast<float*>(gr.e), gr.lde, gr.col0, (int)gr.rows, (int)tiles};
+    tiles += ((gr.rows + 31) / 32) * (d / 64);
+    FFH_REQUIRE(c, tiles < (1LL << 30), "fold_table_update: too many rows");
+  }
+  a.w = w; a.ldw = ldw; a.lr_ptr = lr_ptr; a.lr = lr; a.ngroups = ngroups; a.out = out; a.d = d; a.ntiles = (int)tiles;
+  hipLaunchKernelGGL(fold_table_update_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, as_stream(s), a);
+  FFH_LAUNCH_CHECK(c, "fold_table_update_kernel");
+  return FFH_OK;
+}
+
+// the checks ffh_fold_linear_bwd_dx and its plan query share; FFH_OK, or the error left in the ctx
+int fold_dx_check(ffh_ctx* c, const float* x, int64_t ldx, const float* dx, int64_t lddx, const float* dy, int64_t lddy, const float* w, int in, int out,
+                  int64_t batch, int flags, const int32_t* kept, int nkept) {
+  FFH_REQUIRE(c, in > 0 && out > 0 && batch >= 0 && lddx >= in && lddy >= out, "fold_linear_bwd_dx: bad dims");
+  FFH_REQUIRE(c, !(flags & ~(FFH_LINEAR_DX_OVERWRITE | FFH_LINEAR_DX_MASK_BY_X)), "fold_linear_bwd_dx: flags are DX_OVERWRITE and DX_MASK_BY_X");
+  FFH_REQUIRE(c, !(flags & FFH_LINEAR_DX_MASK_BY_X) || (x && ldx >= in), "fold_linear_bwd_dx: the mask needs x");
+  FFH_REQUIRE(c, batch == 0 || (dx && dy && w), "fold_linear_bwd_dx: null pointer");
+  FFH_REQUIRE(c, batch < (1LL << 31), "fold_linear_bwd_dx: batch too large");
+  FFH_REQUIRE(c, nkept >= 1 && kept, "fold_linear_bwd_dx: bad tile list");
+  for (int i = 0; i < nkept; i++)
+    FFH_REQUIRE(c, kept[i] >= 0 && ((int64_t)kept[i] + 1) * FFH_FOLD_DW_NTILE <= in && (i == 0 || kept[i] > kept[i - 1]), "fold_linear_bwd_dx: tiles must ascend inside [0, in_dim)");
+  return FFH_OK;
+}
+GemmArgs fold_dx_gemm(const float* x, int64_t ldx, float* dx, int64_t lddx, const float* dy, int64_t lddy, const float* w, int in, int out, int64_t batch, int flags) {
+  GemmArgs g{};      // as linear.hip states the data gradient of a layer whose dy is final
+  g.A = dy; g.sAm = lddy; g.sAk = 1;
+  g.B = w; g.sBn = 1; g.sBk = in;
+  g.C = dx; g.ldc = lddx;
+  g.M = (int)batch; g.N = in; g.K = out;
+  g.epi = (flags & FFH_LINEAR_DX_OVERWRITE) ? EPI_STORE : EPI_ADD; g.act = FFH_AC_MODE_NONE;
+  if (flags & FFH_LINEAR_DX_MASK_BY_X) { g.mask = x; g.ldmask = ldx; }
+  return g;
+}
 
 // the checks ffh_fold_linear_bwd_dw and its plan query share; FFH_OK, or the error left in the ctx
 int fold_dw_check(ffh_ctx* c, const float* x, int64_t ldx, const float* dy, int64_t lddy, const float* dw, int in, int out, int64_t batch,
@@ -441,6 +572,41 @@ int ffh_fold_linear_bwd_dw(ffh_ctx* c, const float* x, int64_t ldx, const float*
   if (r < 0) return r;
   if (r == 0) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_linear_bwd_dw: too few kept tiles for the stream-K form, deterministic mode, or a bias gradient without tile 0");
   return FFH_OK;
+}
+
+int ffh_fold_linear_bwd_dx_plan(ffh_ctx* c, const float* x, int64_t ldx, const float* dx, int64_t lddx, const float* dy, int64_t lddy, const float* w, int in,
+                                int out, int64_t batch, int flags, const int32_t* kept, int nkept, const float* colsum) {
+  const int rc = fold_dx_check(c, x, ldx, dx, lddx, dy, lddy, w, in, out, batch, flags, kept, nkept);
+  if (rc != FFH_OK) return rc;
+  if (batch == 0 || c->math_mode != FFH_MATH_DEFAULT) return 0;
+  const GemmArgs g = fold_dx_gemm(x, ldx, const_cast<float*>(dx), lddx, dy, lddy, w, in, out, batch, flags);
+  return launch_gemm_sk_kept_dx(c, g, kept, nkept, const_cast<float*>(colsum), true, nullptr, "") == 1 ? 1 : 0;
+}
+
+int ffh_fold_linear_bwd_dx(ffh_ctx* c, const float* x, int64_t ldx, float* dx, int64_t lddx, const float* dy, int64_t lddy, const float* w, int in, int out,
+                           int64_t batch, int flags, const int32_t* kept, int nkept, float* colsum, ffh_event record_behind, ffh_stream s) {
+  const int rc = fold_dx_check(c, x, ldx, dx, lddx, dy, lddy, w, in, out, batch, flags, kept, nkept);
+  if (rc != FFH_OK) return rc;
+  ffh_route_clear(c);
+  if (batch == 0 || c->math_mode != FFH_MATH_DEFAULT) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_linear_bwd_dx: empty batch / math mode not served");
+  const GemmArgs g = fold_dx_gemm(x, ldx, dx, lddx, dy, lddy, w, in, out, batch, flags);
+  const int r = launch_gemm_sk_kept_dx(c, g, kept, nkept, colsum, false, s, "fold_linear_bwd_dx gemm");
+  if (r < 0) return r;
+  if (r == 0)
+    return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_linear_bwd_dx: the layer's data gradient does not run whole tiles on the persistent kernel, too few kept tiles, "
+                                            "deterministic mode, or column sums without tile 0 / without DX_OVERWRITE");
+  if (record_behind) FFH_HIP_TRY(c, hipEventRecord((hipEvent_t)record_behind, as_stream(s)));
+  return FFH_OK;
+}
+
+int ffh_fold_table_update(ffh_ctx* c, const ffh_fold_group* groups, int ngroups, const float* w, int64_t ldw, int d, int out, float lr, ffh_stream s) {
+  return fold_table_update_launch(c, groups, ngroups, w, ldw, d, out, nullptr, lr, s);
+}
+
+int ffh_fold_table_update_lr(ffh_ctx* c, const ffh_fold_group* groups, int ngroups, const float* w, int64_t ldw, int d, int out, const ffh_lr_state* block,
+                             ffh_stream s) {
+  FFH_REQUIRE(c, block, "fold_table_update_lr: null rate block");
+  return fold_table_update_launch(c, groups, ngroups, w, ldw, d, out, ffh_lr_rate_ptr(block, false), 0.0f, s);
 }
 
 }  // extern "C"

@@ -114,5 +114,8 @@ int launch_gemm_sk_fold(ffh_ctx* c, const GemmArgs& g, const unsigned long long 
 // ... the weight-gradient form over the kept 128-column tiles of dW only (`tiles`: nkept ascending tile indices; include/ff_hip_fold.h); g describes
 // the whole layer's weight gradient.  dry: decide only (1: would launch)
 int launch_gemm_sk_kept(ffh_ctx* c, const GemmArgs& g, const int* tiles, int nkept, bool dry, ffh_stream s, const char* name);
+// ... the whole-tile data-gradient form over the kept 128-column tiles of dX only; g describes the whole layer's data gradient (store / add, mask);
+// colsum ([in_dim], or null): the store epilogue's column sums, this call's own argument (g.colsum is not read).  dry: decide only (1: would launch)
+int launch_gemm_sk_kept_dx(ffh_ctx* c, const GemmArgs& g, const int* tiles, int nkept, float* colsum, bool dry, ffh_stream s, const char* name);
 
 }  // namespace ffh_gemm

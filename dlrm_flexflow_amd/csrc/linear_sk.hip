@@ -95,6 +95,8 @@ struct SkArgsFold : SkArgs {
 // the small tables folded out of the layer are OUTPUT tiles here, not k-tiles: the flat (tile, k-tile) space has nkept column tiles per
 // row of tiles, place() maps the column tile's index through the list to its place in x and dW, and nothing in the k-loop or its schedule
 // knows.  The bias gradient rides on the tiles with n0 == 0 as before, so tile[0] must be 0 where db is wanted (the host checks).
+// ... and (ffh_fold_linear_bwd_dx) the whole-tile data-gradient forms over the KEPT 128-column tiles of dX: the same mapping, the column
+// tile's place in w, dX, the mask and colsum; every other column of dX is never touched.
 struct SkArgsKept : SkArgs {
   unsigned       nkept;
   unsigned short tile[128];      // ascending indices of the kept 128-column tiles
@@ -130,7 +132,8 @@ constexpr int SK_EP_WAVE = SK_EP_ROWS * SK_EP_LD * 4;     // bytes per wave
 // + barrier before the counter add; the loads behind the returned add + a barrier), as in embedding.hip's folds.
 template <bool AKR, bool BKR, int EPI, bool DB = false, bool SPLIT = false, int TMW = 4, bool FOLD = false, bool KEPT = false>
 __global__ __launch_bounds__(256, 1) void gemm_sk_kernel(const std::conditional_t<KEPT, SkArgsKept, std::conditional_t<FOLD, SkArgsFold, SkArgs>> g) {
-  static_assert(!KEPT || (EPI == SK_EPI_DW_ATOMIC && AKR && BKR && !FOLD), "kept column tiles: the weight-gradient form");
+  static_assert(!KEPT || (!FOLD && ((EPI == SK_EPI_DW_ATOMIC && AKR && BKR) || ((EPI == SK_EPI_DX_STORE || EPI == SK_EPI_DX_ADD) && !AKR && BKR && !DB && !SPLIT && TMW == 4))),
+                "kept column tiles: the weight-gradient form and the whole-tile data-gradient forms");
   static_assert(!FOLD || (EPI == SK_EPI_FWD && !SPLIT && !DB && TMW == 4), "kept k-tiles + addend: the whole-tile forward form");
   static_assert(!DB || (EPI == SK_EPI_DW_ATOMIC && AKR), "the bias gradient rides on the weight-gradient form");
   static_assert(!SPLIT || EPI != SK_EPI_DW_ATOMIC, "the weight gradient meets by atomics");
@@ -734,6 +737,52 @@ int launch_gemm_sk_kept(ffh_ctx* c, const GemmArgs& g, const int* tiles, int nke
     if (e != hipSuccess) return ffh_fail_hip(c, e, name);
   }
   { char tok[96]; snprintf(tok, sizeof tok, "%s|sk_128x128x64|kept=%d/%d%s|wgs=%d", name, nkept, g.N / SK_BN, g.db ? "|db" : "", p.G); ffh_route_add(c, tok); }
+  return 1;
+}
+
+// The data-gradient form over kept 128-column tiles of dX (include/ff_hip_fold.h): g describes the WHOLE layer's data gradient (M = batch, N = in_dim,
+// K = out_dim, epi, mask as launch_gemm_sk takes them; g.colsum is ignored: `colsum` is this call's own argument, [in_dim], store epilogue only).
+// Served where the whole layer runs whole 128-row tiles (sk_plan: not the stream-K split, not the 64-row tiles) and the kept tiles still fill whole
+// rounds of workgroups by the rule sk_plan holds whole tiles to (at least one round, the last one 80 % full); never in deterministic mode (colsum
+// meets by atomics; the host keeps that mode on the plain call).  dry: decide only.  1: launched (dry: would be), 0: not served (nothing launched), < 0: error
+int launch_gemm_sk_kept_dx(ffh_ctx* c, const GemmArgs& g, const int* tiles, int nkept, float* colsum, bool dry, ffh_stream s, const char* name) {
+  if (g.N % SK_BN || g.N / SK_BN > 128 || nkept < 1 || nkept > g.N / SK_BN) return 0;
+  for (int i = 0; i < nkept; i++)
+    if (tiles[i] < 0 || tiles[i] >= g.N / SK_BN || (i > 0 && tiles[i] <= tiles[i - 1])) return 0;
+  if (colsum && (tiles[0] != 0 || g.epi != EPI_STORE)) return 0;      // the bias gradient of the layer below rides on the column tile at n0 == 0
+  if (c->deterministic || g.colmap) return 0;
+  SkPlan p{};
+  if (!sk_plan(c, g, SK_FORM_DX, p) || p.split || p.tmw != 4) return 0;
+  const int64_t ntk = (int64_t)(g.M / SK_BM) * nkept, rounds = (ntk + p.G - 1) / p.G;
+  if (ntk < p.G || ntk * 100 < rounds * p.G * 80) return 0;
+  if (dry) return 1;
+  SkArgsKept a{};
+  a.A = g.A; a.B = g.B; a.C = g.C; a.mask = g.mask; a.colsum = colsum;
+  a.lda = p.lda; a.ldb = p.ldb; a.ldc = g.ldc; a.ldmask = g.ldmask;
+  a.M = g.M; a.N = g.N; a.K = g.K; a.act = g.act;
+  a.a_bytes = (unsigned)p.a_bytes; a.b_bytes = (unsigned)p.b_bytes;      // w over the whole width: the kept tiles lie anywhere in it
+  a.mask_bytes = g.mask ? 1u : 0u;
+  a.nkept = (unsigned)nkept;
+  for (int i = 0; i < nkept; i++) a.tile[i] = (unsigned short)tiles[i];
+  constexpr int LDSB = SK_LDS_KC + SK_LDS_KR;
+#define FFH_SK_KEPT_DX_LAUNCH(EPI)                                                                               \
+  {                                                                                                              \
+    auto kern = gemm_sk_kernel<false, true, EPI, false, false, 4, false, true>;                                  \
+    static std::atomic<signed char> ok[64];      /* as in launch_gemm_sk: the LDS attribute once per (kernel, device) */ \
+    const int dev = c->device & 63;                                                                              \
+    if (ok[dev].load(std::memory_order_acquire) == 0) ok[dev].store(sk_set_lds(kern, LDSB) ? 1 : -1, std::memory_order_release); \
+    if (ok[dev].load(std::memory_order_acquire) < 0) return 0;                                                   \
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.G), dim3(256), LDSB, as_stream(s), a);                             \
+  }
+  if (g.epi == EPI_STORE) FFH_SK_KEPT_DX_LAUNCH(SK_EPI_DX_STORE)
+  else FFH_SK_KEPT_DX_LAUNCH(SK_EPI_DX_ADD)
+#undef FFH_SK_KEPT_DX_LAUNCH
+  {
+    const hipError_t e = hipGetLastError();
+    if (e == hipErrorInvalidValue || e == hipErrorInvalidConfiguration || e == hipErrorLaunchOutOfResources || e == hipErrorSharedObjectInitFailed) return 0;
+    if (e != hipSuccess) return ffh_fail_hip(c, e, name);
+  }
+  { char tok[96]; snprintf(tok, sizeof tok, "%s|sk_128x128x64|kept=%d/%d%s|wgs=%d", name, nkept, g.N / SK_BN, colsum ? "|colsum" : "", p.G); ffh_route_add(c, tok); }
   return 1;
 }
 

@@ -3,6 +3,7 @@
 #include <dlfcn.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <map>
 #include <mutex>
 
@@ -189,17 +190,20 @@ const KernelApi* load_kernel_api(const std::string& path_in) {
     api->rowwise = b;
   }
   // the fold extension (include/ff_hip_fold.h): the same rule
+  // ... except that a library of ABI 2 is taken as it is: the entries ABI 3 added (the data-gradient half) stay null and that half of the route is off
   if (dlsym(h, "ffh_fold_abi_version")) {
     KernelApiFold* b = new KernelApiFold();
+    const int fold_abi = reinterpret_cast<int (*)(void)>(dlsym(h, "ffh_fold_abi_version"))();
+    auto abi3_entry = [](const char* n) { return !strncmp(n, "ffh_fold_linear_bwd_dx", 22) || !strncmp(n, "ffh_fold_table_update", 21); };
 #define FFH_LOAD(name)                                                        \
   b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
+  if (!b->name && !(fold_abi == 2 && abi3_entry(#name))) {                    \
     fprintf(stderr, "FATAL: %s exports part of include/ff_hip_fold.h: %s is missing\n", path.c_str(), #name);   \
     abort();                                                                  \
   }
     FFH_FOLD_API_LIST(FFH_LOAD)
 #undef FFH_LOAD
-    if (b->ffh_fold_abi_version() != FFH_FOLD_ABI_VERSION) {
+    if (b->ffh_fold_abi_version() != FFH_FOLD_ABI_VERSION && fold_abi != 2) {
       fprintf(stderr, "FATAL: %s has fold ABI version %d, expected %d\n", path.c_str(), b->ffh_fold_abi_version(), FFH_FOLD_ABI_VERSION);
       abort();
     }

@@ -148,6 +148,7 @@ class FFConfig {
   bool fold_small_tables;      // small embedding tables folded out of the first top layer's forward GEMM (include/ff_hip_fold.h; A/B: --no-fold-small-tables)
   int64_t fold_max_rows;       // ... tables of at most this many rows (--fold-max-rows N)
   bool fold_dw;                // ... and out of its weight-gradient GEMM (A/B: --no-fold-dw)
+  bool fold_dx;                // ... and out of its data-gradient GEMM, their update one dense product (A/B: --no-fold-dx; needs fold_dw)
   bool mlp_chain;              // a run of narrow Linear layers (every width <= 512) as one launch forward, two backward (ffh_mlp_chain_fwd / _bwd; A/B: --no-mlp-chain)
   int64_t mlp_chain_max_batch; // ... for at most this many samples per GPU (--mlp-chain-max-batch N)
   int64_t mlp_chain_fwd_max_batch;   // ... and up to this many (--mlp-chain-fwd-max-batch N)
@@ -760,7 +761,16 @@ class FFModel {
     float* G = nullptr;                    // [sum of R_t][out]
     ffh_ctx* sum_ctx = nullptr;            // the segmented sum's own ctx and workspace: the model's ctx keeps its workspace and its one-shot sort note
     void* sum_ws = nullptr;                // for the table update, which runs on another stream in the same step
+    // ... and out of its data-gradient GEMM ("the data gradient"): all of dw_tables or none.  The layer's data gradient runs over dw_kept
+    // only, the rows of dx that face these tables are not produced, and their plain-SGD step is E_t -= lr G_t W[:, cols_t] (ffh_fold_table_update, dw_groups)
+    // on the side stream in front of the sparse update of the tables that are left
+    bool dx = false;
   } fold;
+  bool fold_dx_table(const Embedding* e) const;      // e's update is the dense product above: the sparse update skips it
+  void fold_table_update(ffh_stream s, ffh_ctx* cx) const;
+  ffh_event ev_fold_w_read = nullptr;      // recorded on the side stream behind that product, which reads W: the slab optimizer in update() waits for it
+  mutable bool fold_w_read_recorded = false;
+  mutable ffh_event fold_dx_event = nullptr;   // backward() -> Linear::backward_part: "gradients ready", to be recorded behind the kept data gradient (one call)
   ffh_event ev_fold_e_read = nullptr;      // recorded on the weight-gradient stream behind the products G_t^T E_t: the table update may overwrite E_t
   mutable bool fold_e_read_recorded = false;
   void fold_weight_gradient(const Linear* li, float* dbp, ffh_stream dws) const;   // the three launches above; the segmented sum first
@@ -769,6 +779,7 @@ class FFModel {
   mutable bool fold_w_recorded = false, fold_on_side = false;
   void plan_fold();                        // allocate(): the route conditions and the buffers
   void plan_fold_dw(FoldRoute& r);         // ... of the weight-gradient half
+  void plan_fold_dx(FoldRoute& r);         // ... of the data-gradient half
   void fold_products_and_sum(ffh_stream s, ffh_ctx* cx) const;
   void fold_linear_forward(const Linear* li) const;
   int z_reader_layer;           // the lowest-index Linear that reads a Concat output the tables are gathered into (-1: unknown): behind ITS

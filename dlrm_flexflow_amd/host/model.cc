@@ -408,6 +408,7 @@ FFModel::~FFModel() {
   if (ev_fold_w) api->ffh_event_destroy(ctx, ev_fold_w);
   if (ev_fold_done) api->ffh_event_destroy(ctx, ev_fold_done);
   if (ev_fold_e_read) api->ffh_event_destroy(ctx, ev_fold_e_read);
+  if (ev_fold_w_read) api->ffh_event_destroy(ctx, ev_fold_w_read);
   for (void* p : {(void*)fold.P, (void*)fold.S, (void*)fold.G, fold.sum_ws}) if (p) api->ffh_free(ctx, p);
   if (fold.sum_ctx) api->ffh_ctx_destroy(fold.sum_ctx);
   for (auto& kv : trace_tune) for (ffh_event& e : kv.second.ev) if (e) { api->ffh_event_destroy(ctx, e); e = nullptr; }
@@ -613,7 +614,7 @@ void Linear::backward_part(const FFModel& ff, int part) {
       if (lo) ff.check(ff.api->ffh_linear_bwd_set_dx_colsum(ff.ctx, lo->weights[1].impl->grad, lo->out_channels), "dx colsum");
     }
     ~ColsumScope() { if (lo) lo->db_from_upper = ff.api->ffh_linear_dx_colsum_used(ff.ctx) != 0; }
-  } colsum_scope(ff, colsum_lower, dx != nullptr && (part == 0 || part == 1) && !ff.use_workers() && !ff.config.profiling);
+  } colsum_scope(ff, colsum_lower, dx != nullptr && (part == 0 || part == 1) && !ff.use_workers() && !ff.config.profiling && !(ff.fold.layer == this && ff.fold.dx));
   // split mode, this layer on the fp32 kernels under one that streams images: the image of the data gradient just stored (allocate(), step 7)
   // tensor-op mode, bwd_exact: the twin of the data gradient the exact kernels stored
   auto image_dx = [&] {
@@ -660,7 +661,16 @@ void Linear::backward_part(const FFModel& ff, int part) {
       ff.check(ff.api->ffh_event_record(ff.ctx, ev, ff.stream), "event");
       ff.check(ff.api->ffh_stream_wait_event(ff.ctx, dws, ev), "event");
     }
-    if (dx) {
+    if (dx && ff.fold.dx) {
+      // ... and out of the data gradient: the kept column tiles only (the rows of dx that face the folded tables are not produced: their update is
+      // FFModel::fold_table_update).  Column sums and "gradients ready" are this call's own arguments: nothing was armed in the ctx for it (no Linear
+      // below: plan_fold_dx; backward() hands the event over through fold_dx_event), so nothing is left pending for the next layer's call
+      ffh_event ev = ff.fold_dx_event;
+      ff.fold_dx_event = nullptr;
+      ff.check(ff.api->fold->ffh_fold_linear_bwd_dx(ff.ctx, xp, ldx, dx, lddx, dyp, lddy, wp, in_padded, out_channels, b,
+                                                    flags & (FFH_LINEAR_DX_OVERWRITE | FFH_LINEAR_DX_MASK_BY_X), ff.fold.dw_kept.data(), (int)ff.fold.dw_kept.size(),
+                                                    nullptr, ev, ff.stream), name);
+    } else if (dx) {
       ff.check(ff.api->ffh_linear_bwd_ex(ff.ctx, xp, ldx, dx, lddx, yp, ldy, dyp, lddy, wp, dwp, dbp, in_padded, out_channels, b, (int)activation,
                                          flags | FFH_LINEAR_ONLY_DX, ff.stream, nullptr), name);
       image_dx();

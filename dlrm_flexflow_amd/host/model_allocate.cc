@@ -1162,6 +1162,33 @@ void FFModel::plan_fold_dw(FoldRoute& r) {
     grow += e->num_entries;
   }
   if (!ev_fold_e_read) check((config.timing_events ? api->ffh_event_create : api->ffh_event_create_sync)(ctx, &ev_fold_e_read), "event create");
+  plan_fold_dx(r);
+}
+
+// ... and out of the same layer's data-gradient GEMM ("the data gradient").  The only reader of dx[:, cols_t] is table t's update, which
+// sums those rows per table row: G_t W[:, cols_t], with the G_t the weight-gradient half forms anyway.  The dw-folded tables are folded here as well -- all of
+// them or none -- when the library has ABI 3 of the extension, the layer's dx is stored by the ONLY_DX call of backward_part's fold branch (plan_fold_dw's
+// conditions) with no Linear below whose bias gradient would ride on it, the tables' update is the fused plain-SGD one (no momentum, no weight decay; fp32
+// rows and sum aggregation come with the forward fold) issued on the side stream from backward() (--no-overlap runs it behind the slab optimizer, which has
+// rewritten W by then), and the library runs the data gradient over the tiles that are left on whole tiles of the persistent kernel
+// (ffh_fold_linear_bwd_dx_plan).  Otherwise the data gradient and the tables' update are those of before.
+void FFModel::plan_fold_dx(FoldRoute& r) {
+  Linear* li = r.layer;
+  if (!config.fold_dx || r.dw_tables.empty() || !api->fold->ffh_fold_linear_bwd_dx || !api->fold->ffh_fold_linear_bwd_dx_plan || !api->fold->ffh_fold_table_update) return;
+  ffh_sparse_opt rule;
+  if (!fused_embedding_update() || sparse_rule(rule) || !config.overlap_embedding || use_workers()) return;
+  if (lr_route == kLrDevice && !api->fold->ffh_fold_table_update_lr) return;      // the rate lives in device memory: only its twin can read it
+  if (li->discard_input_grad || li->colsum_lower || li->inputs[0].impl->grad == nullptr) return;
+  const Embedding* e0 = r.dw_tables[0];
+  if (e0->out_channels % 64) return;
+  const Tensor &x = li->inputs[0], &y = li->outputs[0];
+  const int flags = (li->dx_overwrite ? FFH_LINEAR_DX_OVERWRITE : 0) | (li->dx_mask_by_x ? FFH_LINEAR_DX_MASK_BY_X : 0);
+  const int plan = api->fold->ffh_fold_linear_bwd_dx_plan(ctx, (const float*)x.impl->ptr, x.impl->ld, x.impl->grad, x.impl->grad_ld, y.impl->grad, y.impl->grad_ld,
+                                                          (const float*)li->weights[0].impl->ptr, li->in_padded, li->out_channels, local_rows(y, this), flags,
+                                                          r.dw_kept.data(), (int)r.dw_kept.size(), nullptr);
+  if (plan != 1) return;
+  r.dx = true;
+  if (!ev_fold_w_read) check((config.timing_events ? api->ffh_event_create : api->ffh_event_create_sync)(ctx, &ev_fold_w_read), "event create");
 }
 
 void FFModel::init_layers() {

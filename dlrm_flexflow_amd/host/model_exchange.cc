@@ -7,7 +7,7 @@
 // =============================================================================================
 // launches one batched kernel per distinct shard width (all table-wise tables share one; column blocks of
 // giant tables another); FWD: gather, else fused backward + SGD
-void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_ctx* cx, const std::vector<const int64_t*>* idx_override) {
+void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_ctx* cx, const std::vector<const int64_t*>* idx_override, bool all_tables) {
   const bool fwd = what == kGather;
   ffh_sparse_opt rule;
   const bool ruled = (what == kFusedUpdate || what == kApplyOnly) && ff->sparse_rule(rule);     // momentum / wd SGD, Adam on the touched rows
@@ -27,6 +27,7 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
     t.idx = (const int64_t*)e->inputs[0].impl->ptr;
     if (idx_override && owned_i < idx_override->size()) t.idx = (*idx_override)[owned_i];
     owned_i++;
+    if (!fwd && !all_tables && ff->fold_dx_table(e)) continue;      // its update is FFModel::fold_table_update (its rows of the data gradient are not produced)
     t.weight = (float*)e->weights[0].impl->ptr;      // column-sharded: the local [R][cols] slice
     t.num_entries = e->num_entries;
     if (!ff->exchange) {
@@ -131,7 +132,7 @@ uint64_t FFModel::read_bf16_counter() const {
 // roofline kernels of a multi-rank job
 void FFModel::embedding_kernels_only(bool fwd, ffh_stream s, const std::vector<const int64_t*>* idx_override) const {
   if (embeddings.empty() || (!fwd && !fused_embedding_update())) return;
-  launch_shard_groups(this, fwd ? kGather : kFusedUpdate, s, ctx, idx_override);
+  launch_shard_groups(this, fwd ? kGather : kFusedUpdate, s, ctx, idx_override, true);      // (a roofline probe: every table, dx-folded or not)
   if (!fwd) advance_bf16_counter(s, ctx);
 }
 

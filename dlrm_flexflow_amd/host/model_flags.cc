@@ -43,6 +43,7 @@ FFConfig::FFConfig() {
   fold_small_tables = true;
   fold_max_rows = 7420;      // the measured threshold (2208 and 7420 tried)
   fold_dw = true;
+  fold_dx = true;
   trace_mode = -1;
   bucket_allreduce = -1;
   allreduce_bucket_floats = 1 << 20;
@@ -166,6 +167,7 @@ void FFConfig::parse_args(char** argv, int argc) {
     if (is("--no-mlp-chain")) { mlp_chain = false; continue; }
     if (is("--no-fold-small-tables")) { fold_small_tables = false; continue; }
     if (is("--no-fold-dw")) { fold_dw = false; continue; }
+    if (is("--no-fold-dx")) { fold_dx = false; continue; }
     if (is("--fold-max-rows")) { fold_max_rows = atoll(next()); continue; }
     if (is("--always-replay")) { trace_mode = 1; continue; }
     if (is("--adaptive-replay")) { trace_mode = 0; continue; }

@@ -70,4 +70,6 @@ inline bool in_dense_slab(const Parameter& p) {
 // one batched kernel per distinct shard width of this rank's tables (model_exchange.cc): the gather, the fused backward + optimizer, or its
 // two phases
 enum ShardLaunch { kGather, kFusedUpdate, kSortOnly, kApplyOnly };
-void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_ctx* cx, const std::vector<const int64_t*>* idx_override = nullptr);
+// all_tables: kFusedUpdate / kSortOnly / kApplyOnly normally leave out the dx-folded tables (FFModel::fold_dx_table), whose update is a dense product
+void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_ctx* cx, const std::vector<const int64_t*>* idx_override = nullptr,
+                         bool all_tables = false);

@@ -163,6 +163,27 @@ void FFModel::fold_weight_gradient(const Linear* li, float* dbp, ffh_stream dws)
                                           fold.dw_kept.data(), (int)fold.dw_kept.size(), dws), li->name);
 }
 
+// The plain-SGD step of the dx-folded tables as one dense product (include/ff_hip_fold.h, ABI 3): E_t[r] = fmaf(-lr, G_t[r] W[:, cols_t], E_t[r]).  The rate
+// as the sparse update of the other tables takes it: from the table update's block in device memory, or the optimizer's scalar.
+void FFModel::fold_table_update(ffh_stream s, ffh_ctx* cx) const {
+  const Linear* li = fold.layer;
+  const Embedding* e0 = fold.dw_tables[0];
+  const int ng = (int)fold.dw_groups.size();
+  const float* w = (const float*)li->weights[0].impl->ptr;
+  if (lr_route == kLrDevice) {
+    check(api->fold->ffh_fold_table_update_lr(cx, fold.dw_groups.data(), ng, w, li->in_padded, e0->out_channels, li->out_channels, lr_block[1], s), "fold_table_update_lr");
+  } else {
+    ffh_sparse_opt rule;
+    sparse_rule(rule);      // (plain SGD: plan_fold_dx)
+    check(api->fold->ffh_fold_table_update(cx, fold.dw_groups.data(), ng, w, li->in_padded, e0->out_channels, li->out_channels, rule.lr, s), "fold_table_update");
+  }
+}
+bool FFModel::fold_dx_table(const Embedding* e) const {
+  if (!fold.dx) return false;
+  for (const Embedding* t : fold.dw_tables) if (t == e) return true;
+  return false;
+}
+
 // forward() of the layer the tables are folded out of.  The gather has been joined (the Concat below comes first), so `stream` stands behind
 // this step's tables either way: the sum is waited for where the side stream computed it, and computed right here otherwise
 void FFModel::fold_linear_forward(const Linear* li) const {
@@ -195,6 +216,14 @@ void FFModel::issue_embedding_update_on_side_stream() const {
     check(api->ffh_stream_wait_event(ctx, side_stream, ev_grad_ready), "event");
     if (fold_e_read_recorded) check(api->ffh_stream_wait_event(ctx, side_stream, ev_fold_e_read), "fold: table rows read");      // (fold_weight_gradient)
     probe_record(2, side_stream, ctx);
+    if (fold.dx) {
+      // the dx-folded tables first: E_t -= lr G_t W[:, cols_t].  Behind ev_fold_e_read the products G_t^T E_t have read E_t and (the same stream, in front
+      // of them) the segmented sum has completed G.  It reads W, which the slab optimizer rewrites on `stream`: update() waits for ev_fold_w_read
+      if (!fold_e_read_recorded) die("fold: the dx-folded tables' update without this step's segmented sum");
+      fold_table_update(side_stream, ctx);
+      check(api->ffh_event_record(ctx, ev_fold_w_read, side_stream), "fold: weights read");
+      fold_w_read_recorded = true;
+    }
     embedding_group_update(side_stream);
     probe_record(3, side_stream, ctx);
     check(api->ffh_event_record(ctx, ev_update_done, side_stream), "event");
@@ -246,6 +275,8 @@ void FFModel::backward(int _seq_length) {
   if (fin.impl->grad_ld != fin.adim[0] || fin.impl->ld != fin.adim[0]) die("final layer output must be contiguous");
   dw_forked = false;
   fold_e_read_recorded = false;
+  fold_w_read_recorded = false;
+  fold_dx_event = nullptr;
   opt_next_done = false;
   // the click-probability layer (out = 1): loss step + metrics + the layer's whole backward in ONE launch; any other last
   // layer: the loss kernel, then the layer's own backward
@@ -312,7 +343,9 @@ void FFModel::backward(int _seq_length) {
   for (int l = first; l >= 0; l--) {
     if (bucketed_now()) issue_grad_buckets(l);     // the buckets every layer above l has completed
     if (l == grad_attach_layer) {
-      check(api->ffh_event_record_with_next_linear_bwd(ctx, ev_grad_ready), "attach event");
+      // (the dx-folded layer takes the event as an argument of its data-gradient call: nothing armed in the ctx)
+      if (fold.dx && layers[l] == fold.layer) fold_dx_event = ev_grad_ready;
+      else check(api->ffh_event_record_with_next_linear_bwd(ctx, ev_grad_ready), "attach event");
       grad_ready_attached = true;
     }
     Linear* up = layers[l]->op_type == OP_LINEAR ? static_cast<Linear*>(layers[l]) : nullptr;
@@ -426,6 +459,8 @@ void FFModel::update() {
       probe_record(9, stream, ctx);
     }
   }
+  // the dx-folded tables' update (side stream, issued from backward()) reads the first top layer's weight: the optimizer goes behind it
+  if (fold_w_read_recorded) { check(api->ffh_stream_wait_event(ctx, stream, ev_fold_w_read), "fold: weights read"); fold_w_read_recorded = false; }
   // one launch over the whole MLP slab; it also clears the gradients it consumed, so the next zero_gradients()
   // has nothing to sweep [ref: one update task per parameter, src/runtime/optimizer.cc:93-189,256-330]
   const size_t opt_count = mlp_count;

@@ -1,5 +1,6 @@
 /* ff_hip_fold.h -- optional extension of the kernel C-ABI (include/ff_hip.h): small embedding tables folded out of the forward
- * GEMM, and (ABI 2, further down) out of the weight-gradient GEMM, of the Linear layer that reads their rows through a Concat.
+ * GEMM, (ABI 2, further down) out of the weight-gradient GEMM, and (ABI 3, at the end) out of the data-gradient GEMM, of the Linear
+ * layer that reads their rows through a Concat.
  *
  * A library may export this list or not; include/ff_hip.h and its symbol list are unchanged by it.  libffhip.so exports it,
  * the CPU oracle does not.  Callers load it separately (host/backend: KernelApi::fold, null when absent).
@@ -34,7 +35,7 @@
 extern "C" {
 #endif
 
-#define FFH_FOLD_ABI_VERSION 2
+#define FFH_FOLD_ABI_VERSION 3
 
 #define FFH_FOLD_KTILE      16    /* granularity of every reduction-depth segment and of D, in floats          */
 #define FFH_FOLD_NTILE      64    /* out_dim of the folded layer is a multiple of this                           */
@@ -133,12 +134,57 @@ int ffh_fold_linear_bwd_dw(ffh_ctx* ctx, const float* x, int64_t ldx, const floa
 int ffh_fold_linear_bwd_dw_plan(ffh_ctx* ctx, const float* x, int64_t ldx, const float* dy, int64_t lddy, const float* dw, const float* db, int in_dim,
                                 int out_dim, int64_t batch, const int32_t* kept, int nkept);
 
+/* ---- the data gradient of the same layer (ABI 3) -------------------------------------------------------------------------------------------
+ * The only reader of dx[:, cols_t] of a folded table is that table's update, which sums those rows per table row:
+ *
+ *     dE_t[r] = sum over the hits (b, l) of r of dx[b][cols_t] = sum_hits dy[b] W[:, cols_t] = G_t[r] W[:, cols_t]       (G_t as above)
+ *
+ * ffh_fold_linear_bwd_dx is the layer's data gradient over the column tiles that are left; ffh_fold_table_update applies G_t W[:, cols_t] to the
+ * tables as one dense product.  The rows of dx that face a folded table are then NOT PRODUCED: whoever reads the gradient of such a table's output
+ * (a caller's own probe of the embedding output gradient) finds what the buffer held before.
+ * Orders: the kept columns of dx are those of ffh_linear_bwd_ex(FFH_LINEAR_ONLY_DX) bit for bit (the same kernel, the same k order, whole tiles).
+ * ffh_fold_table_update: one fp32 chain per element, the order of ffh_fold_product over the depth o (groups j of 16 ascending, in a group four MFMAs
+ * e = 0..3, MFMA e adding o = 16 j + 4 q + e, q = 0..3), then ONE fmaf(-lr, sum, E): no atomics, no split over o.  With the canonical order of G
+ * (ffh_fold_segment_sum) the tables' bits are the same from run to run and from stream to stream.  Bound: 1e-5 lr (term mass of the unfolded
+ * sum over hits and o) + 2 ulp(E) against float64. */
+
+/* The data gradient of ffh_linear_bwd_ex(..., FFH_LINEAR_ONLY_DX ...) of a layer whose dy is FINAL, over the KEPT column tiles only:
+ *     dx[b][k] (+)= mask(sum_o dy[b][o] w[o][k])   for k in the tiles [FFH_FOLD_DW_NTILE kept[i], FFH_FOLD_DW_NTILE (kept[i] + 1)), i < nkept (ascending)
+ * flags: FFH_LINEAR_DX_OVERWRITE (store; otherwise add to what dx holds) and FFH_LINEAR_DX_MASK_BY_X (dx = x > 0 ? v : 0, x the layer's input);
+ * x may be NULL without the mask.  w is [out_dim][in_dim] contiguous.  Every other column of dx is left as it is.
+ * colsum (or NULL): [in_dim] floats; colsum[k] += sum_b dx[b][k] as stored, for the kept k -- the bias gradient of the layer below, which rides on the
+ *   tile at column 0: needs kept[0] == 0 and FFH_LINEAR_DX_OVERWRITE.  When the call returns FFH_OK the sums have been added.
+ * record_behind (or NULL): recorded on `s` behind the kernel.
+ * Both are THIS call's arguments: the entry neither reads nor clears what ffh_linear_bwd_set_dx_colsum / ffh_event_record_with_next_linear_bwd armed.
+ * Served only where the whole layer's ONLY_DX call runs the persistent kernel on whole 128 x 128 tiles and the kept tiles still fill whole rounds of
+ * workgroups by that kernel's own rule (at least one round, the last one 80 % full); exact fp32 math mode, not the deterministic mode.  Anything else:
+ * FFH_ERR_UNSUPPORTED, nothing launched, nothing written, nothing recorded.  ffh_linear_last_route: "fold_linear_bwd_dx gemm|sk_128x128x64|kept=a/b|...". */
+int ffh_fold_linear_bwd_dx(ffh_ctx* ctx, const float* x, int64_t ldx, float* dx, int64_t lddx, const float* dy, int64_t lddy, const float* w, int in_dim,
+                           int out_dim, int64_t batch, int flags, const int32_t* kept, int nkept, float* colsum, ffh_event record_behind, ffh_stream s);
+
+/* Whether the call above would be served for these arguments (nothing is launched): 1 = yes; 0 = no; negative: bad arguments. */
+int ffh_fold_linear_bwd_dx_plan(ffh_ctx* ctx, const float* x, int64_t ldx, const float* dx, int64_t lddx, const float* dy, int64_t lddy, const float* w,
+                                int in_dim, int out_dim, int64_t batch, int flags, const int32_t* kept, int nkept, const float* colsum);
+
+/* E_t[r][j] = fmaf(-lr, sum_o G_t[r][o] w[o][col0_t + j], E_t[r][j]), j < d, for ngroups tables in ONE launch: plain SGD on the folded tables (no
+ * state, no weight decay).  groups[t]: e = E_t (WRITTEN here, unlike the other entries), lde, col0 = col0_t, p = G_t ([rows][out_dim] contiguous, read),
+ * rows = R_t.  w is the layer's [out_dim][ldw] weight.  A row nobody hit has G = 0 and keeps its bits.  Order: see above.  d % 64 == 0,
+ * out_dim % FFH_FOLD_NTILE == 0, 16-byte aligned e, p and w, lde % 4 == 0, ldw % 4 == 0, col0 % 4 == 0, 1 <= ngroups <= FFH_FOLD_MAX_GROUPS;
+ * anything else: FFH_ERR_UNSUPPORTED. */
+int ffh_fold_table_update(ffh_ctx* ctx, const ffh_fold_group* groups, int ngroups, const float* w, int64_t ldw, int d, int out_dim, float lr, ffh_stream s);
+/* ... with the rate read from `block` at run time (include/ff_hip_lr.h: the lr of ffh_lr_state, one uniform 4-byte load): the same bits as the
+ * entry above given that value. */
+struct ffh_lr_state;
+int ffh_fold_table_update_lr(ffh_ctx* ctx, const ffh_fold_group* groups, int ngroups, const float* w, int64_t ldw, int d, int out_dim,
+                             const struct ffh_lr_state* block, ffh_stream s);
+
 #ifdef __cplusplus
 }
 #endif
 
 #define FFH_FOLD_API_LIST(X) \
   X(ffh_fold_abi_version) X(ffh_fold_product) X(ffh_fold_gather_add) X(ffh_fold_linear_fwd) X(ffh_fold_linear_fwd_plan) \
-  X(ffh_fold_segment_sum) X(ffh_fold_dw_product) X(ffh_fold_linear_bwd_dw) X(ffh_fold_linear_bwd_dw_plan)
+  X(ffh_fold_segment_sum) X(ffh_fold_dw_product) X(ffh_fold_linear_bwd_dw) X(ffh_fold_linear_bwd_dw_plan) \
+  X(ffh_fold_linear_bwd_dx) X(ffh_fold_linear_bwd_dx_plan) X(ffh_fold_table_update) X(ffh_fold_table_update_lr)
 
 #endif /* FF_HIP_FOLD_H_ */
