@@ -149,6 +149,10 @@ class FFConfig {
   int64_t fold_max_rows;       // ... tables of at most this many rows (--fold-max-rows N)
   bool fold_dw;                // ... and out of its weight-gradient GEMM (A/B: --no-fold-dw)
   bool fold_dx;                // ... and out of its data-gradient GEMM, their update one dense product (A/B: --no-fold-dx; needs fold_dw)
+  bool fold_dw_behind_sum;     // A/B: that layer's kept-tile weight-gradient GEMM on the weight-gradient stream behind the segmented sum and the products, as it was
+                               // (--fold-dw-behind-sum); default: on the compute stream behind the backward of the layers below ("The schedule of the fold's backward")
+  bool fold_update_behind_products;   // A/B: the sparse update of the tables that are not dx-folded waits for the products G_t^T E_t, as it did
+                               // (--fold-update-behind-products); default: it starts at "gradients ready", the dense update of the folded tables follows it
   bool mlp_chain;              // a run of narrow Linear layers (every width <= 512) as one launch forward, two backward (ffh_mlp_chain_fwd / _bwd; A/B: --no-mlp-chain)
   int64_t mlp_chain_max_batch; // ... for at most this many samples per GPU (--mlp-chain-max-batch N)
   int64_t mlp_chain_fwd_max_batch;   // ... and up to this many (--mlp-chain-fwd-max-batch N)
@@ -377,6 +381,7 @@ class Linear : public Op {
   void forward(const FFModel&) override;
   void backward(const FFModel&) override;
   void backward_part(const FFModel&, int part);   // 0: all; 1: data gradient only
+  bool forks_dw(const FFModel&) const;            // backward_part gives this layer's weight gradient the weight-gradient stream (parallel_dw and a GEMM long enough to pay for the fork)
   void backward_dw_rows(const FFModel&, int row0, int nrows);   // the weight (+ bias) gradient of output rows [row0, row0 + nrows) on the weight-gradient stream (dy final: premasked / no activation)
   int in_channels, out_channels;
   int in_padded;                // what the kernel library is told: in_channels, or that rounded up to 64 when the input tensor and the kernel were
@@ -668,7 +673,8 @@ class FFModel {
   std::vector<Embedding*> embeddings;
   void embedding_group_forward(ffh_stream s, ffh_ctx* on_ctx = nullptr) const;   // on_ctx: the issuing thread's ctx
   void replicated_embedding_grads() const;                     // dense gradient of the data-parallel tables into the slab (compute stream)
-  void embedding_group_update(ffh_stream s, ffh_ctx* on_ctx = nullptr) const;
+  // advance_rate = false: the caller has another reader of the table update's rate block to issue (fold_table_update) and calls advance_lr(1, ..) behind it
+  void embedding_group_update(ffh_stream s, ffh_ctx* on_ctx = nullptr, bool advance_rate = true) const;
   // this rank's gather / fused update kernels, no exchange.  idx_override (bench probes): one id buffer per owned shard, in shard
   // order, used instead of the model's own -- back-to-back probe launches rotate over several id sets so that no launch finds the
   // rows of the launch before in the 256 MiB Infinity Cache
@@ -773,7 +779,20 @@ class FFModel {
   mutable ffh_event fold_dx_event = nullptr;   // backward() -> Linear::backward_part: "gradients ready", to be recorded behind the kept data gradient (one call)
   ffh_event ev_fold_e_read = nullptr;      // recorded on the weight-gradient stream behind the products G_t^T E_t: the table update may overwrite E_t
   mutable bool fold_e_read_recorded = false;
-  void fold_weight_gradient(const Linear* li, float* dbp, ffh_stream dws) const;   // the three launches above; the segmented sum first
+  // the three launches above: the segmented sum and the products on `dws`, the GEMM over the kept tiles on `gemm_stream` (`dws`, or the compute stream)
+  void fold_weight_gradient(const Linear* li, float* dbp, ffh_stream dws, ffh_stream gemm_stream) const;
+  // The schedule of the fold's backward ("The schedule").  Both apply only where the layer's weight gradient is forked to the weight-gradient
+  // stream and the table update runs on the side stream (no launch workers, no --profiling: plan_fold_dw); everywhere else the launches keep their order.
+  void fold_kept_dw_gemm(const Linear* li, float* dbp, ffh_stream s, bool off_dw_stream) const;   // that GEMM; off the weight-gradient stream it records ev_fold_x_read behind itself
+  mutable bool fold_dw_defer = false;      // backward() is walking the layers: on the compute stream the GEMM waits until the layers below have issued their backward
+  mutable const Linear* fold_dw_pending = nullptr;
+  mutable float* fold_dw_pending_db = nullptr;
+  bool fold_schedule_route() const;        // that route
+  bool fold_dw_on_compute() const;         // the kept-tile weight-gradient GEMM goes on the compute stream, behind the backward of the layers below
+  bool fold_update_early() const;          // the sparse update of the tables that are left starts at ev_grad_ready, in front of the dx-folded tables' dense update
+  ffh_event ev_fold_x_read = nullptr;      // recorded on the compute stream behind that GEMM, the last reader of the Concat output: the next gather (side stream) waits for it
+  mutable bool fold_x_read_recorded = false;
+  mutable int64_t n_fold_dw_on_compute = 0, n_fold_update_early = 0;   // steps issued that way (tests: flexflow_model_get_counter)
   ffh_event ev_fold_w = nullptr;           // recorded on `stream` at the top of forward(): the optimizer of the step before has written W
   ffh_event ev_fold_done = nullptr;        // recorded on the side stream behind the gather-add
   mutable bool fold_w_recorded = false, fold_on_side = false;

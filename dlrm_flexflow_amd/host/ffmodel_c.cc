@@ -179,6 +179,8 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   if (n == "folded_tables") return (int64_t)M(m)->fold.tables.size();      // tables folded out of the first top layer's forward GEMM (include/ff_hip_fold.h)
   if (n == "folded_dw_tables") return (int64_t)M(m)->fold.dw_tables.size();   // ... and out of its weight-gradient GEMM
   if (n == "folded_dx_tables") return (int64_t)(M(m)->fold.dx ? M(m)->fold.dw_tables.size() : 0);   // ... and out of its data-gradient GEMM
+  if (n == "fold_dw_on_compute_steps") return M(m)->n_fold_dw_on_compute;      // backward() calls that put the kept-tile weight-gradient GEMM on the compute stream
+  if (n == "fold_update_early_steps") return M(m)->n_fold_update_early;        // ... and that started the sparse table update at "gradients ready"
   if (n == "tensor_op_exact_backward_layers") {      // Linear layers whose backward runs in exact mode under --allow-tensor-op-math-conversion (allocate() step 7)
     int64_t k = 0;
     for (Op* op : M(m)->layers) if (op->op_type == OP_LINEAR && static_cast<Linear*>(op)->bwd_exact) k++;

@@ -409,6 +409,7 @@ FFModel::~FFModel() {
   if (ev_fold_done) api->ffh_event_destroy(ctx, ev_fold_done);
   if (ev_fold_e_read) api->ffh_event_destroy(ctx, ev_fold_e_read);
   if (ev_fold_w_read) api->ffh_event_destroy(ctx, ev_fold_w_read);
+  if (ev_fold_x_read) api->ffh_event_destroy(ctx, ev_fold_x_read);
   for (void* p : {(void*)fold.P, (void*)fold.S, (void*)fold.G, fold.sum_ws}) if (p) api->ffh_free(ctx, p);
   if (fold.sum_ctx) api->ffh_ctx_destroy(fold.sum_ctx);
   for (auto& kv : trace_tune) for (ffh_event& e : kv.second.ev) if (e) { api->ffh_event_destroy(ctx, e); e = nullptr; }
@@ -588,6 +589,14 @@ int Linear::backward_pair(const FFModel& ff) {
 }
 void Linear::backward(const FFModel& ff) { backward_part(ff, 0); }
 
+// the weight-gradient GEMM gets its own stream only where it is long enough to pay for the fork and the join
+// (two event records + two waits, each a packet the command processor has to retire): measured on the Kaggle shape,
+// forking the 432x512 / 512x256 layers gains 22 us per step, forking the 256x64 / 64x16 / 13x512 ones loses 6
+bool Linear::forks_dw(const FFModel& ff) const {
+  const double macs = (double)in_channels * out_channels * (double)local_rows(outputs[0], &ff);
+  return ff.config.parallel_dw && macs >= 1.0e8;
+}
+
 // part 0: the whole backward; 1: the data gradient only (FFH_LINEAR_ONLY_DX on the compute stream) -- for FFModel::backward's row-block
 // weight gradient of the biggest layer (backward_dw_rows), which follows it.
 void Linear::backward_part(const FFModel& ff, int part) {
@@ -597,11 +606,7 @@ void Linear::backward_part(const FFModel& ff, int part) {
   const Tensor& y = outputs[0];
   const int64_t b = local_rows(y, &ff);
   float* dx = discard_input_grad ? nullptr : x.impl->grad;
-  // the weight-gradient GEMM gets its own stream only where it is long enough to pay for the fork and the join
-  // (two event records + two waits, each a packet the command processor has to retire): measured on the Kaggle shape,
-  // forking the 432x512 / 512x256 layers gains 22 us per step, forking the 256x64 / 64x16 / 13x512 ones loses 6
-  const double macs = (double)in_channels * out_channels * (double)b;
-  const bool fork = ff.config.parallel_dw && macs >= 1.0e8;
+  const bool fork = forks_dw(ff);
   const int flags = (dx_overwrite ? FFH_LINEAR_DX_OVERWRITE : 0) | (dx_mask_by_x ? FFH_LINEAR_DX_MASK_BY_X : 0) | (dy_premasked ? FFH_LINEAR_DY_PREMASKED : 0);
   const float *xp = (const float*)x.impl->ptr, *yp = (const float*)y.impl->ptr, *wp = (const float*)weights[0].impl->ptr;
   float *dyp = y.impl->grad, *dwp = weights[0].impl->grad, *dbp = (use_bias && !db_from_upper) ? weights[1].impl->grad : nullptr;
@@ -654,8 +659,11 @@ void Linear::backward_part(const FFModel& ff, int part) {
   ffh_stream dws = ff.dw_stream;
   if (part == 0 && ff.fold.layer == this && !ff.fold.dw_tables.empty()) {
     // small tables folded out of the weight gradient (allocate(), step 8): the data gradient as the ONLY_DX call on `stream`, and behind the event
-    // that says dy is ready the segmented sum, the GEMM over the kept column tiles and the products on the weight-gradient stream -- the sum
-    // first, memory-bound beside the data-gradient GEMM.  --serial-dw: all of it on `stream`
+    // that says dy is ready the segmented sum and the products on the weight-gradient stream -- the sum first, memory-bound beside the data-gradient
+    // GEMM.  The GEMM over the kept column tiles goes on `stream` behind the backward of the layers below (FFModel::fold_dw_on_compute: it reads x
+    // and dy only; backward() issues it when it has walked them, so their forked weight gradients follow the products on the weight-gradient stream,
+    // not a 0.9 ms GEMM), or behind the products on the weight-gradient stream (--fold-dw-behind-sum, and every configuration outside that route).
+    // --serial-dw: all of it on `stream`
     if (fork) {
       ffh_event ev = ff.layer_events[layer_index];
       ff.check(ff.api->ffh_event_record(ff.ctx, ev, ff.stream), "event");
@@ -675,7 +683,8 @@ void Linear::backward_part(const FFModel& ff, int part) {
                                          flags | FFH_LINEAR_ONLY_DX, ff.stream, nullptr), name);
       image_dx();
     }
-    ff.fold_weight_gradient(this, dbp, fork ? dws : ff.stream);
+    // (forked either way: the sum and the products stay on the weight-gradient stream, so the join in update() is still due)
+    ff.fold_weight_gradient(this, dbp, fork ? dws : ff.stream, fork && !ff.fold_dw_on_compute() ? dws : ff.stream);
     if (fork) { ff.dw_forked = true; ff.dw1_used = true; ff.dw_stream_used_directly = true; }
     return;
   }

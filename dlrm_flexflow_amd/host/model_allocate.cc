@@ -1162,6 +1162,7 @@ void FFModel::plan_fold_dw(FoldRoute& r) {
     grow += e->num_entries;
   }
   if (!ev_fold_e_read) check((config.timing_events ? api->ffh_event_create : api->ffh_event_create_sync)(ctx, &ev_fold_e_read), "event create");
+  if (!ev_fold_x_read) check((config.timing_events ? api->ffh_event_create : api->ffh_event_create_sync)(ctx, &ev_fold_x_read), "event create");
   plan_fold_dx(r);
 }
 

@@ -245,7 +245,7 @@ void FFModel::replicated_embedding_grads() const {
   check(api->ffh_ctx_set_workspace(ctx, workspace, workspace_bytes), "set workspace");
 }
 
-void FFModel::embedding_group_update(ffh_stream s, ffh_ctx* on_ctx) const {
+void FFModel::embedding_group_update(ffh_stream s, ffh_ctx* on_ctx, bool advance_rate) const {
   if (embeddings.empty()) return;
   if (exchange) {
     // gradients of the rows go back to the owners (transposed exchange)
@@ -278,7 +278,7 @@ void FFModel::embedding_group_update(ffh_stream s, ffh_ctx* on_ctx) const {
     check(api->ffh_zero(cx, w + e->rows_local * (int64_t)D, (size_t)D * 4, s), "zero row");   // (its optimizer state is never read for a row of the block)
   }
   advance_bf16_counter(s, cx);
-  advance_lr(1, s, cx);      // behind this step's last reader of the table update's block, on its stream
+  if (advance_rate) advance_lr(1, s, cx);      // behind this step's last reader of the table update's block, on its stream
 }
 
 // The reference's own table update on the rank(s) that hold a table, for optimizers the fused update does not cover (default for

@@ -44,6 +44,8 @@ FFConfig::FFConfig() {
   fold_max_rows = 7420;      // the measured threshold (2208 and 7420 tried)
   fold_dw = true;
   fold_dx = true;
+  fold_dw_behind_sum = false;
+  fold_update_behind_products = false;
   trace_mode = -1;
   bucket_allreduce = -1;
   allreduce_bucket_floats = 1 << 20;
@@ -168,6 +170,8 @@ void FFConfig::parse_args(char** argv, int argc) {
     if (is("--no-fold-small-tables")) { fold_small_tables = false; continue; }
     if (is("--no-fold-dw")) { fold_dw = false; continue; }
     if (is("--no-fold-dx")) { fold_dx = false; continue; }
+    if (is("--fold-dw-behind-sum")) { fold_dw_behind_sum = true; continue; }
+    if (is("--fold-update-behind-products")) { fold_update_behind_products = true; continue; }
     if (is("--fold-max-rows")) { fold_max_rows = atoll(next()); continue; }
     if (is("--always-replay")) { trace_mode = 1; continue; }
     if (is("--adaptive-replay")) { trace_mode = 0; continue; }

@@ -145,8 +145,12 @@ void FFModel::fold_products_and_sum(ffh_stream s, ffh_ctx* cx) const {
 // The weight gradient of the layer the tables are folded out of, on `dws` (which stands behind "dy is ready"): G_t = the segmented sum of dy over
 // table t's rows, the layer's weight-gradient GEMM over the column tiles that are left (with the bias gradient), dW[:, cols_t] += G_t^T E_t.
 // The same launches with the same arguments every step: a captured step holds them as they are.
-void FFModel::fold_weight_gradient(const Linear* li, float* dbp, ffh_stream dws) const {
-  const Tensor &x = li->inputs[0], &y = li->outputs[0];
+// `gemm_stream` is `dws`, or the compute stream (fold_dw_on_compute): the GEMM reads x and dy, which are final there, and adds into columns of dW the
+// products do not touch, so nothing but stream order ever held it behind the sum.  Inside backward() it is then put off until the layers below have
+// issued their backward: right behind the data gradient it keeps the segmented sum from finishing (the sum crawls beside a persistent GEMM, and the
+// products, the dense table update and the optimizer wait for it) and only swaps places with the bottom MLP's data gradients.
+void FFModel::fold_weight_gradient(const Linear* li, float* dbp, ffh_stream dws, ffh_stream gemm_stream) const {
+  const Tensor& y = li->outputs[0];
   const Embedding* e0 = fold.dw_tables[0];
   const int64_t b = local_rows(y, this);
   const int out = li->out_channels, ng = (int)fold.dw_groups.size();
@@ -159,9 +163,26 @@ void FFModel::fold_weight_gradient(const Linear* li, float* dbp, ffh_stream dws)
   check(api->ffh_event_record(ctx, ev_fold_e_read, dws), "fold: table rows read");
   fold_e_read_recorded = true;
   // (dbp: null where the layer above has produced this layer's bias gradient already -- Linear::backward_part consumed db_from_upper)
-  check(api->fold->ffh_fold_linear_bwd_dw(ctx, (const float*)x.impl->ptr, x.impl->ld, y.impl->grad, y.impl->grad_ld, li->weights[0].impl->grad, dbp, li->in_padded, out, b,
-                                          fold.dw_kept.data(), (int)fold.dw_kept.size(), dws), li->name);
+  if (gemm_stream != dws && fold_dw_defer) { fold_dw_pending = li; fold_dw_pending_db = dbp; return; }      // backward() issues it behind the layers below
+  fold_kept_dw_gemm(li, dbp, gemm_stream, gemm_stream != dws);
 }
+void FFModel::fold_kept_dw_gemm(const Linear* li, float* dbp, ffh_stream s, bool off_dw_stream) const {
+  const Tensor &x = li->inputs[0], &y = li->outputs[0];
+  check(api->fold->ffh_fold_linear_bwd_dw(ctx, (const float*)x.impl->ptr, x.impl->ld, y.impl->grad, y.impl->grad_ld, li->weights[0].impl->grad, dbp, li->in_padded, li->out_channels,
+                                          local_rows(y, this), fold.dw_kept.data(), (int)fold.dw_kept.size(), s), li->name);
+  if (off_dw_stream) {
+    // off the weight-gradient stream, neither ev_z_free nor ev_dw_done says that this reader of the Concat output is done: an event of its own for the
+    // next gather (update() makes the side stream wait for it; in a captured step that wait is the graph edge)
+    check(api->ffh_event_record(ctx, ev_fold_x_read, s), "fold: layer input read");
+    fold_x_read_recorded = true;
+    n_fold_dw_on_compute++;
+  }
+}
+bool FFModel::fold_schedule_route() const {
+  return fold.layer && !fold.dw_tables.empty() && fold.layer->forks_dw(*this) && config.overlap_embedding && !use_workers() && !config.profiling;
+}
+bool FFModel::fold_dw_on_compute() const { return fold_schedule_route() && !config.fold_dw_behind_sum; }
+bool FFModel::fold_update_early() const { return fold_schedule_route() && fold.dx && !config.fold_update_behind_products; }
 
 // The plain-SGD step of the dx-folded tables as one dense product (include/ff_hip_fold.h, ABI 3): E_t[r] = fmaf(-lr, G_t[r] W[:, cols_t], E_t[r]).  The rate
 // as the sparse update of the other tables takes it: from the table update's block in device memory, or the optimizer's scalar.
@@ -214,6 +235,24 @@ void FFModel::issue_embedding_update_on_side_stream() const {
     });
   } else {
     check(api->ffh_stream_wait_event(ctx, side_stream, ev_grad_ready), "event");
+    if (fold_update_early()) {
+      // The sparse update of the tables that are left needs the kept data gradient only: with dx folding it writes no table of fold.dw_groups (launch_shard_groups
+      // skips them), and those are the only rows the products G_t^T E_t read, so it does not wait for ev_fold_e_read.  It runs on the model's ctx and workspace
+      // while the segmented sum may still run on fold.sum_ctx and its own.  The dense update of the folded tables follows it, behind ev_fold_e_read as before; the
+      // rate block both read advances behind the second reader.
+      if (!fold_e_read_recorded) die("fold: the dx-folded tables' update without this step's segmented sum");
+      probe_record(2, side_stream, ctx);
+      embedding_group_update(side_stream, nullptr, false);
+      check(api->ffh_stream_wait_event(ctx, side_stream, ev_fold_e_read), "fold: table rows read");
+      fold_table_update(side_stream, ctx);
+      check(api->ffh_event_record(ctx, ev_fold_w_read, side_stream), "fold: weights read");
+      fold_w_read_recorded = true;
+      advance_lr(1, side_stream, ctx);
+      probe_record(3, side_stream, ctx);
+      check(api->ffh_event_record(ctx, ev_update_done, side_stream), "event");
+      n_fold_update_early++;
+      return;
+    }
     if (fold_e_read_recorded) check(api->ffh_stream_wait_event(ctx, side_stream, ev_fold_e_read), "fold: table rows read");      // (fold_weight_gradient)
     probe_record(2, side_stream, ctx);
     if (fold.dx) {
@@ -276,6 +315,9 @@ void FFModel::backward(int _seq_length) {
   dw_forked = false;
   fold_e_read_recorded = false;
   fold_w_read_recorded = false;
+  fold_x_read_recorded = false;
+  fold_dw_pending = nullptr;
+  fold_dw_defer = true;      // (a layer's backward() called on its own -- time_kernel(7) -- issues the GEMM at once)
   fold_dx_event = nullptr;
   opt_next_done = false;
   // the click-probability layer (out = 1): loss step + metrics + the layer's whole backward in ONE launch; any other last
@@ -397,6 +439,12 @@ void FFModel::backward(int _seq_length) {
     layers[l]->backward(*this);
     mark_z_free(l);
   }
+  fold_dw_defer = false;
+  if (fold_dw_pending) {
+    // the fold layer's kept-tile weight-gradient GEMM, behind the backward of the layers below it on `stream` (fold_dw_on_compute)
+    fold_kept_dw_gemm(fold_dw_pending, fold_dw_pending_db, stream, true);
+    fold_dw_pending = nullptr;
+  }
   if (emb_update_pending) {
     // exchange of the row gradients + fused sparse update on the side stream, beside the bottom-MLP backward
     issue_embedding_update_on_side_stream();
@@ -437,6 +485,8 @@ void FFModel::update() {
     dw1_used = false;
     dw_forked = false;
   }
+  // ... and the kept-tile weight-gradient GEMM of the fold layer reads that buffer on `stream` (fold_dw_on_compute), where neither event above stands behind it
+  if (fold_x_read_recorded) { check(api->ffh_stream_wait_event(ctx, side_stream, ev_fold_x_read), "fold: layer input read (embedding stream)"); fold_x_read_recorded = false; }
   // data-parallel MLP gradients: ONE bucket [ref: one ncclAllReduce per tensor, src/runtime/optimizer_kernel.cu:170-171].
   // No 1/world_size: the loss already divides by the global batch.
   if (exchange && mlp_count) {
