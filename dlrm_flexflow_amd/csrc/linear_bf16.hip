@@ -759,17 +759,24 @@ int launch_gemm_bf16(ffh_ctx* c, GemmArgs& g, ffh_stream s, const char* name) {
       if (rc > 0) { if (g.db && !AKC && !BKC) g.db_done = 1; return FFH_OK; }
     }
   }
-  if (x3) { char tok[96]; snprintf(tok, sizeof tok, "%s|bf16x3_%s|splitk=%d", name, (big && g.epi == EPI_ATOMIC) ? "256x256" : "128x128", g.splitk); ffh_route_add(c, tok); }
+  // few tiles (at most ~one per CU: 4096 x 3456 -> 1024 forward has 256): the forward / data-gradient kernel runs the same tile on EIGHT waves of
+  // 32 x 64 instead of four of 64 x 64 -- a CU that holds one workgroup then has two waves per SIMD, one's loads and LDS passes under the other's
+  // MFMAs (same sums per accumulator, same bits)
+  static const int w8_pct = FFH_LAB_INT("FFH_X3V_W8_PCT", 150);      // A/B switch: eight waves up to this many tiles, in per cent of the CUs
+  const bool x3_v2 = AKC && x3 && g.epi != EPI_ATOMIC;
+  const bool x3_w8 = x3_v2 && (int64_t)((g.N + kBfBN - 1) / kBfBN) * ((g.M + kBfBM - 1) / kBfBM) * 100 <= (int64_t)c->num_cus * w8_pct;
+  if (x3) {      // the 128 x 128 token is three kernels' (v2 on four or eight waves, the 32x32x16 form): the suffix says which
+    const bool t256 = big && g.epi == EPI_ATOMIC;
+    char tok[112];
+    snprintf(tok, sizeof tok, "%s|bf16x3_%s|splitk=%d%s", name, t256 ? "256x256" : "128x128", g.splitk, t256 ? "" : (x3_v2 ? (x3_w8 ? "|v2w8" : "|v2w4") : "|mfma32"));
+    ffh_route_add(c, tok);
+  }
   if constexpr (AKC) {
-    if (x3 && g.epi != EPI_ATOMIC) {      // forward / data gradient: the arithmetic of the LDS-DMA form, bit for bit (gemm_bf16x3_v2_kernel)
+    if (x3_v2) {      // forward / data gradient: the arithmetic of the LDS-DMA form, bit for bit (gemm_bf16x3_v2_kernel)
       // (128 x 128 tiles only: with 128 x 64 per wave the 16 x 16 accumulators, two operands' fragments and the staging registers do not fit 256 VGPRs)
       const int vx = (g.N + kBfBN - 1) / kBfBN, vy = (g.M + kBfBM - 1) / kBfBM;
       if (vy > 65535) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "gemm (bf16x3): grid too large");
-      // few tiles (at most ~one per CU: 4096 x 3456 -> 1024 forward has 256): the same tile on EIGHT waves of 32 x 64 instead of four of 64 x 64 --
-      // a CU that holds one workgroup then has two waves per SIMD, one's loads and LDS passes under the other's MFMAs (same sums per
-      // accumulator, same bits)
-      static const int w8_pct = FFH_LAB_INT("FFH_X3V_W8_PCT", 150);      // A/B switch: eight waves up to this many tiles, in per cent of the CUs
-      if ((int64_t)vx * vy * 100 <= (int64_t)c->num_cus * w8_pct) {
+      if (x3_w8) {
         auto kv8 = gemm_bf16x3_v2_kernel<BKC, MASK_A, 128, 128, 32>;
         static const bool okv8 = glds_set_lds(kv8, kX3Lds);
         if (!okv8) return ffh_fail(c, FFH_ERR_HIP, "gemm (bf16x3): cannot reserve 48 KB of LDS");

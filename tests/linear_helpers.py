@@ -45,6 +45,24 @@ kernel family it is there for (Case.want), which the CPU test asserts of the mod
 launch_gemm_bf16 (csrc/linear_bf16.hip: the tile, the split count, the twins' conditions) and launch_gemm_bf16_dma's serve conditions
 (csrc/linear_bf16_dma.hip); the split count is part of the expected token except for the LDS-DMA weight gradient, whose cost search is only held
 to its range.
+
+Split mode (Case.mode = 3, FFH_MATH_FP32_SPLIT_BF16X3_ALL; tests/test_linear_x3_sweep_cpu.py, tests/test_gpu_linear_x3_sweep.py).  A layer with both
+widths >= 128 computes each product as the six bfloat16 plane products a3 b1, a1 b3, a2 b2, a2 b1, a1 b2, a1 b1 of x1 = bf16(x), x2 = bf16(x - x1),
+x3 = bf16(x - x1 - x2) (split3 / split_product: numpy, written from include/ff_hip.h).  On the distributions above the mode is held to the project's
+bound against the float64 product of the UNSPLIT operands, which cannot tell six products from four; Case.dist = "planes" is the family on which
+it can: every non-zero GEMM operand is s * (2^18 + t * 2^9 + r), s, t in {-1, +1}, r in {0, 1}, whose planes are exactly s 2^18, s t 2^9 and s r,
+so the six kept products are multiples of 2^18 and the three dropped ones are not zero; zeros are placed so that no output of any GEMM of the
+call has more than PLANES_MAX_TERMS = 48 reduction positions with both operands non-zero (asserted by the generator with a boolean product of
+the masks), spread over the whole reduction range.  Every partial sum in any order is then a multiple of 2^18 below 2^42, exact in fp32: y, dx
+and dw have to EQUAL the float64 sum of the six kept products, whatever the tile, split-K or atomics (db sums unsplit values and keeps the
+bound).  (t = -1 puts x on or just above a rounding tie of the first plane and x - x1 on one of the second: with t = +1 alone every remainder
+lies below half an ulp and a truncating split gives the same planes as nearest-even.)  Case.images names the buffers among x w y dy dx with a
+registered three-plane image (ImageBuf / Images: the region is the Buf's whole allocation, 128-byte aligned; the image holds SENTINEL16
+everywhere, an input's is filled by ffh_convert_f32_to_bf16x3 and compared with the numpy restatement before the call): after the call an input's
+image is bit-identical, an output's is untouched as a whole or exactly the image of the stored floats over the block and the sentinel elsewhere,
+and written it must be where the route names "bf16x3" or "x3_dma" for that GEMM.  x3_gemm restates the split branch of launch_gemm_bf16
+(csrc/linear_bf16.hip) and the serve conditions of launch_gemm_x3_dma (csrc/linear_x3_dma.hip).  NumpySplitLib is the same entry points in numpy
+with the arithmetic as a parameter: what the CPU test feeds the checker, right and wrong.
 """
 import ctypes as C
 import re
@@ -61,7 +79,11 @@ MATH_BF16 = 1               # FFH_MATH_TENSOR_OP_BF16
 MATH_SPLIT_ALL = 3          # FFH_MATH_FP32_SPLIT_BF16X3_ALL
 BF16_MIN_DIM = 128          # FFH_BF16_MIN_DIM
 DISTS = ("uniform", "integer", "ties", "wide")
+ALL_DISTS = DISTS + ("planes",)          # "planes": the split mode's own family
 TWIN_NAMES = ("x", "w", "y", "dy", "dx")
+IMAGE_NAMES = TWIN_NAMES
+PLANES_MAX_TERMS = 48       # "planes": reduction positions with both operands non-zero, per output element: 48 * (2^18 + 2^9 + 1)^2 < 2^42
+PLANE_UNIT = 2.0 ** 18
 SENTINEL16 = 0x7FDE         # a bfloat16 NaN: a twin's padding read into a GEMM poisons the result
 TABLE_CUS = 256             # the CU count the edge table's shapes were derived for (MI355X)
 
@@ -77,13 +99,15 @@ class Case:
 
     def __init__(self, name, kind, in_dim, out_dim, batch, act=NONE, flags=0, seed=0, ldx=None, x_off=0, ldy=None, y_off=0, lddy=None, dy_off=0,
                  lddx=None, dx_off=0, w_off=0, bias=True, bias_off=0, db=True, dx=True, forked=False, det=False, cmap=False, cmap_ncols=None,
-                 colsum=False, colsum_ncols=None, scratch=True, integer=False, want=(), mode=0, twins=(), dist=None, stale=()):
+                 colsum=False, colsum_ncols=None, scratch=True, integer=False, want=(), mode=0, twins=(), dist=None, stale=(), images=()):
         assert kind in ("fwd", "bwd")
         self._kw = {k: v for k, v in locals().items() if k not in ("self", "__class__")}
         dist = dist or ("integer" if integer else "uniform")
-        assert dist in DISTS and mode in (0, MATH_BF16) and set(twins) <= set(TWIN_NAMES) and set(stale) <= set(twins)
+        assert dist in ALL_DISTS and mode in (0, MATH_BF16, MATH_SPLIT_ALL) and set(twins) <= set(TWIN_NAMES) and set(images) <= set(IMAGE_NAMES)
+        assert set(stale) <= set(twins) | set(images) and not (twins and images)
+        assert dist != "planes" or act in (NONE, RELU)
         integer = dist == "integer"
-        self.mode, self.twins, self.dist, self.stale = mode, frozenset(twins), dist, frozenset(stale)
+        self.mode, self.twins, self.dist, self.stale, self.images = mode, frozenset(twins), dist, frozenset(stale), frozenset(images)
         self.name, self.kind, self.in_dim, self.out_dim, self.batch, self.act, self.flags, self.seed = name, kind, int(in_dim), int(out_dim), int(batch), act, flags, seed
         self.ldx, self.x_off = (in_dim if ldx is None else ldx), x_off
         self.ldy, self.y_off = (out_dim if ldy is None else ldy), y_off
@@ -107,17 +131,29 @@ class Case:
         """The layer rule of FFH_MATH_TENSOR_OP_BF16 (include/ff_hip.h): both widths >= FFH_BF16_MIN_DIM."""
         return self.mode == MATH_BF16 and self.in_dim >= BF16_MIN_DIM and self.out_dim >= BF16_MIN_DIM
 
+    @property
+    def x3_layer(self):
+        """The layer rule of FFH_MATH_FP32_SPLIT_BF16X3_ALL (include/ff_hip.h): both widths >= FFH_BF16_MIN_DIM, whatever the size."""
+        return self.mode == MATH_SPLIT_ALL and self.in_dim >= BF16_MIN_DIM and self.out_dim >= BF16_MIN_DIM
+
+    @property
+    def planes_exact(self):
+        """y, dx and dw have to equal the six-product sum: the "planes" family on a layer the split kernels take."""
+        return self.dist == "planes" and self.x3_layer
+
     def __repr__(self):
         return (f"Case({self.name}: {self.kind} B={self.batch} {self.in_dim}->{self.out_dim} act={self.act} flags={self.flags} ldx={self.ldx}+{self.x_off} "
                 f"ldy={self.ldy}+{self.y_off} lddy={self.lddy}+{self.dy_off} lddx={self.lddx}+{self.dx_off} w+{self.w_off} bias={self.bias}+{self.bias_off} "
                 f"db={self.db} dx={self.dx} forked={self.forked} det={self.det} cmap={self.cmap}/{self.cmap_ncols} colsum={self.colsum}/{self.colsum_ncols} "
-                f"scratch={self.scratch} dist={self.dist} mode={self.mode} twins={sorted(self.twins)} stale={sorted(self.stale)})")
+                f"scratch={self.scratch} dist={self.dist} mode={self.mode} twins={sorted(self.twins)} images={sorted(self.images)} stale={sorted(self.stale)})")
 
 
 def make_inputs(case):
     """Operands of order one (or small integers), the same for a given case on every backend."""
     rng = np.random.default_rng([case.seed, case.in_dim, case.out_dim, case.batch, case.flags])
     B, i, o = case.batch, case.in_dim, case.out_dim
+    if case.dist == "planes":
+        return _make_planes(case, rng)
     if case.integer:
         assert case.act in (NONE, RELU)
         draw = lambda *shape: rng.integers(-2, 3, shape).astype(np.float64)
@@ -150,6 +186,74 @@ def make_inputs(case):
             g = np.where(y > 0, g, 0.0)
         inp.update(y=y, g=g.astype(np.float32), dx0=draw(B, i).astype(np.float32), dw0=draw(o, i).astype(np.float32), db0=draw(o).astype(np.float32),
                    cs0=draw(case.colsum_ncols).astype(np.float32))
+    return inp
+
+
+def _band(rng, rows, cols, n):
+    """bool [rows][cols]: n non-zeros in every row, one in each of n equal stretches of the columns, the pattern moved on from row to row by a
+    step that takes the rows through a whole stretch (so every part of the range is used) and has no factor in common with cols: no column
+    holds more than n * ceil(rows / cols)."""
+    n = max(1, min(int(n), cols))
+    edges = (np.arange(n + 1) * cols) // n
+    pos = edges[:-1] + rng.integers(0, edges[1:] - edges[:-1])
+    step = max(1, _cdiv(_cdiv(cols, n), rows))
+    while np.gcd(step, cols) != 1:
+        step += 1
+    m = np.zeros((rows, cols), bool)
+    m[np.arange(rows)[:, None], (pos[None, :] + step * np.arange(rows)[:, None]) % cols] = True
+    return m
+
+
+def _plane_values(rng, shape):
+    """s * (2^18 + t * 2^9 + r): the planes are s 2^18, s t 2^9, s r exactly (t = -1: x1 by a tie to even or just above it, x2 = bf16(-511) a tie)."""
+    s, t = (np.where(rng.integers(0, 2, shape) == 1, 1.0, -1.0) for _ in range(2))
+    return s * (PLANE_UNIT + t * 2.0 ** 9 + rng.integers(0, 2, shape))
+
+
+def planes_terms(case, inp):
+    """GEMM name -> [M][N] count of the reduction positions at which both operands are non-zero, for every GEMM the call runs (a boolean product
+    of the non-zero masks; dy counted before any mask: an upper bound)."""
+    nz = lambda a: (np.asarray(a) != 0).astype(np.float32)
+    if case.kind == "fwd":
+        return {"fwd": nz(inp["x"]) @ nz(inp["w"]).T}
+    out = {}
+    if not case.has(ONLY_DX):
+        out["dw"] = nz(inp["g"]).T @ nz(inp["x"])
+    if case.dx and not case.has(ONLY_DW):
+        out["dx"] = nz(inp["g"]) @ nz(inp["w"])
+    return out
+
+
+def _make_planes(case, rng):
+    """The "planes" family (module docstring).  Forward: 48 non-zeros in every row of w, x dense.  Backward: x and w dense; with a weight gradient
+    every column of dy has 48 non-zero rows spread over the batch (fewer where out_dim > batch, so that a row of dy keeps to 48 as well), with the
+    data gradient alone every row of dy has 48 non-zeros spread over out_dim."""
+    B, i, o = case.batch, case.in_dim, case.out_dim
+    T = PLANES_MAX_TERMS
+    small = lambda *shape: rng.integers(-2, 3, shape) * PLANE_UNIT
+    w, x = _plane_values(rng, (o, i)), _plane_values(rng, (B, i))
+    if case.kind == "fwd":
+        w = np.where(_band(rng, o, i, T), w, 0.0)
+    elif case.has(MASK_BY_X):
+        x = np.maximum(x, 0)          # the output of a ReLU
+    inp = {"w": w.astype(np.float32), "b": small(o).astype(np.float32), "x": x.astype(np.float32)}
+    if case.kind == "bwd":
+        y = act64(_f64(inp["x"]) @ _f64(inp["w"]).T + _f64(inp["b"]), case.act).astype(np.float32)
+        g = _plane_values(rng, (B, o))
+        if B:
+            if not case.has(ONLY_DX):
+                keep = _band(rng, o, B, T // _cdiv(o, B)).T
+                if case.dx and not case.has(ONLY_DW) and keep.sum(1).max() > T:
+                    keep &= _band(rng, B, o, T)
+            else:
+                keep = _band(rng, B, o, T)
+            g = np.where(keep, g, 0.0)
+        if case.has(PREMASKED) and case.act == RELU:
+            g = np.where(y > 0, g, 0.0)
+        inp.update(y=y, g=g.astype(np.float32), dx0=small(B, i).astype(np.float32), dw0=small(o, i).astype(np.float32), db0=small(o).astype(np.float32),
+                   cs0=small(case.colsum_ncols).astype(np.float32))
+    for name, terms in planes_terms(case, inp).items():          # a condition on the inputs, not a tolerance
+        assert terms.size == 0 or terms.max() <= T, f"{case.name}: {name} has an output with {int(terms.max())} > {T} non-zero terms"
     return inp
 
 
@@ -327,6 +431,205 @@ class Twins:
         self.regs = []
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# the split of FFH_MATH_FP32_SPLIT_BF16X3 (include/ff_hip.h: x1 = bf16(x) nearest-even, x2 = bf16(x - x1), x3 = bf16(x - x1 - x2), both
+# differences exact in fp32; a * b = the fp32 sum of the six products a_i b_j with i + j <= 4) and the three-plane images
+SIX = ((3, 1), (1, 3), (2, 2), (2, 1), (1, 2), (1, 1))
+
+
+def _rne_bf16_finite(a):
+    """rne_bf16 for finite values below the largest bfloat16 (what a split meets), in 32-bit arithmetic: the same bits, a quarter of the time."""
+    u = np.ascontiguousarray(a, np.float32).view(np.uint32)
+    r = (u >> np.uint32(16)) & np.uint32(1)
+    r += np.uint32(0x7FFF)
+    r += u
+    r &= np.uint32(0xFFFF0000)
+    return r.view(np.float32).reshape(np.shape(a))
+
+
+def split3(a, rnd=None):
+    """float32 -> its three bfloat16 terms, as float32 arrays.  rnd replaces nearest-even by a wrong rounding."""
+    a = np.ascontiguousarray(a, np.float32)
+    if rnd is None:
+        rnd = _rne_bf16_finite if a.size == 0 or float(np.abs(a).max()) < 3.0e38 else rne_bf16          # (a NaN compares false: rne_bf16)
+    x1 = rnd(a)
+    r1 = a - x1
+    x2 = rnd(r1)
+    return x1, x2, rnd(r1 - x2)
+
+
+def split_product(a, b, pairs=SIX, rnd=None):
+    """a [M][K] @ b [K][N] as the float64 sum of the kept plane products a_i b_j, (i, j) in pairs."""
+    pa, pb = split3(a, rnd), split3(b, rnd)
+    out = np.zeros((np.shape(a)[0], np.shape(b)[1]))
+    for i in (1, 2, 3):
+        js = [j for ii, j in pairs if ii == i]
+        if js:
+            out += _f64(pa[i - 1]) @ sum(_f64(pb[j - 1]) for j in js)
+    return out
+
+
+def plane_bits(a, rnd=None):
+    """float32 [n] -> uint16 [3][n]: the bits of the three terms."""
+    return np.stack([(p.view(np.uint32) >> np.uint32(16)).astype(np.uint16) for p in split3(np.ravel(a), rnd)])
+
+
+def image_at(e):
+    """Element e of a region (counted from its 128-byte aligned base) -> the uint16 index of its term 0 in the image ("I32": 32 elements <-> 192
+    bytes [x1 of the 32 | x2 of the 32 | x3 of the 32]); term p lies 32 * p further on."""
+    e = np.asarray(e, np.int64)
+    return (e // 32) * 96 + e % 32
+
+
+def image_len(n):
+    """uint16 elements of the image of a region of n floats: FFH_BF16X3_IMAGE_BYTES(4 n) / 2."""
+    return (4 * n + 127) // 128 * 96
+
+
+def _aligned(be, flat, align=128):
+    """flat uploaded to an allocation whose base is `align`-byte aligned (over-allocated where the backend does not give that)."""
+    h = be.upload(flat)
+    if be.addr(h) % align == 0:
+        return h
+    assert isinstance(h, np.ndarray), "the device allocator is expected to give 128-byte aligned blocks"
+    raw = np.empty(flat.nbytes + align, np.uint8)
+    at = -raw.ctypes.data % align
+    v = raw[at:at + flat.nbytes].view(flat.dtype)
+    v[:] = flat
+    return v
+
+
+class ImageBuf:
+    """The three-plane image of a Buf (ffh_ctx_bf16x3_mirror_set): the region is the Buf's whole allocation.  Every position holds SENTINEL16; an
+    input's image is filled over the valid block by ffh_convert_f32_to_bf16x3 (fill()), an output's stays sentinel."""
+
+    def __init__(self, be, buf):
+        self.be, self.buf = be, buf
+        if be.addr(buf.h) % 128:
+            buf.h = _aligned(be, be.download(buf.h))
+        self.before = np.full(image_len(buf.valid.size), SENTINEL16, np.uint16)
+        self.at = image_at(buf.idx)[None, :] + 32 * np.arange(3)[:, None]          # [3][rows * cols]
+        self.valid = np.zeros(self.before.size, bool)
+        self.valid[self.at.ravel()] = True
+        self.h = _aligned(be, self.before.view(np.int16))
+        self.host = None
+
+    @property
+    def base(self):
+        return self.be.addr(self.h)
+
+    def register(self, lib):
+        base = self.be.addr(self.buf.h)
+        assert base % 128 == 0 and self.base % 128 == 0, "ffh_ctx_bf16x3_mirror_set wants 128-byte aligned bases"
+        lib.check(lib.lib.ffh_ctx_bf16x3_mirror_set(lib.ctx, base, 4 * self.buf.valid.size, self.base), "ffh_ctx_bf16x3_mirror_set")
+        return base
+
+    def fill(self, lib):
+        """What a model's producers leave in the image of a buffer they wrote: the planes of the valid block, row by row where it is strided."""
+        b = self.buf
+        runs = [(0, b.rows * b.cols)] if b.ld == b.cols or b.rows <= 1 else [(r * b.ld, b.cols) for r in range(b.rows)]
+        for at, n in runs:
+            if n:
+                lib.check(lib.lib.ffh_convert_f32_to_bf16x3(lib.ctx, b.ptr + 4 * at, 1, n, n, None), "ffh_convert_f32_to_bf16x3")
+        return self
+
+    def poison(self, bits=0x7FC0):
+        """A stale image: the three planes of the valid block replaced by bfloat16 NaN."""
+        flat = self.be.download(self.h).view(np.uint16).copy()
+        flat[self.valid] = bits
+        self.h = None
+        self.h = _aligned(self.be, flat.view(np.int16))
+        return self
+
+    def snapshot(self):
+        self.before = self.be.download(self.h).view(np.uint16).copy()
+        return self
+
+    def fetch(self):
+        self.host = self.be.download(self.h).view(np.uint16)
+        return self
+
+    def untouched(self):
+        return self.host.tobytes() == self.before.tobytes()
+
+    def problems(self, name, stored=None, must_write=False):
+        """An output's image after the call (stored: the [rows][cols] floats the library left in the fp32 buffer): untouched as a whole, or the three
+        terms of `stored` over the valid block and the sentinel everywhere else.  stored None: an input's image, identical to before."""
+        out = []
+        if stored is None:
+            if not self.untouched():
+                out.append(f"{name} image: an input's image was modified ({int((self.host != self.before).sum())} positions)")
+            return out
+        if self.untouched():
+            if must_write:
+                out.append(f"{name} image: not written by a launch of the split mode's kernels")
+            return out
+        pad = np.flatnonzero((self.host != SENTINEL16) & ~self.valid)
+        if pad.size:
+            out.append(f"{name} image: {pad.size} position(s) outside the valid block written, first at uint16 index {int(pad[0])} (group {int(pad[0]) // 96}, "
+                       f"term {int(pad[0]) % 96 // 32}, element {int(pad[0]) % 32}; ld {self.buf.ld}, offset {self.buf.off})")
+        want, got = plane_bits(stored), self.host[self.at]
+        bad = np.argwhere(got != want)
+        if bad.size:
+            p, k = (int(v) for v in bad[0])
+            r, c = divmod(k, self.buf.cols)
+            out.append(f"{name} image: {bad.shape[0]} of {got.size} terms are not the split of the stored float; first: term {p + 1} of ({r}, {c}): "
+                       f"0x{int(got[p, k]):04x}, expected 0x{int(want[p, k]):04x}")
+        return out
+
+
+class Images:
+    """The image registrations of one call: made before it, undone whatever happens (the ctx is the whole session's).  An input's image, once
+    filled, has to be what the numpy restatement says: ffh_convert_f32_to_bf16x3 is one of the passes under test."""
+
+    def __init__(self, lib, be, case, bufs, inputs):
+        self.lib, self.t, self.inputs, self.regs = lib, {}, set(inputs), []
+        try:
+            for name in IMAGE_NAMES:
+                buf = bufs.get(name)
+                if name not in case.images or buf is None:
+                    continue
+                im = self.t[name] = ImageBuf(be, buf)
+                self.regs.append((im.register(lib), 4 * buf.valid.size))
+                if name in self.inputs:
+                    im.fill(lib)
+            be.sync()
+            for name, im in self.t.items():
+                if name in self.inputs:
+                    bad = im.fetch().problems(name, im.buf.before[im.buf.idx].reshape(im.buf.rows, im.buf.cols), must_write=im.buf.idx.size > 0)
+                    assert not bad, f"{case.name}: ffh_convert_f32_to_bf16x3 left a wrong image: {bad}"
+                if name in case.stale:
+                    im.poison()
+                    im.register(lib)
+                im.snapshot()
+        except BaseException:
+            self.release()
+            raise
+
+    def release(self):
+        for base, nbytes in self.regs:
+            self.lib.lib.ffh_ctx_bf16x3_mirror_set(self.lib.ctx, base, nbytes, None)
+        self.regs = []
+
+
+class _Regs:
+    """Twins and Images of one call behind one release()."""
+
+    def __init__(self, lib, be, case, bufs, inputs):
+        self.parts = []
+        try:
+            self.parts.append(Twins(lib, be, case, bufs, inputs))
+            self.parts.append(Images(lib, be, case, bufs, inputs))
+        except BaseException:
+            self.release()
+            raise
+        self.t = {**self.parts[0].t, **self.parts[1].t}
+
+    def release(self):
+        for p in self.parts:
+            p.release()
+
+
 def _set_mode(lib, mode):
     lib.check(lib.lib.ffh_ctx_set_math_mode(lib.ctx, mode), "ffh_ctx_set_math_mode")
 
@@ -374,7 +677,7 @@ def run_fwd(lib, be, case, inp=None):
     tw = None
     try:
         _set_mode(lib, case.mode)
-        tw = Twins(lib, be, case, dict(x=X, w=W, y=Y), ("x", "w"))
+        tw = _Regs(lib, be, case, dict(x=X, w=W, y=Y), ("x", "w"))
         rc = lib.lib.ffh_linear_fwd(lib.ctx, X.ptr, case.ldx, Y.ptr, case.ldy, W.ptr, Bi.ptr if Bi else None, i, o, B, case.act, s)
         route = (lib.lib.ffh_linear_last_route(lib.ctx) or b"").decode()
         _finish(lib, be, [s])
@@ -417,7 +720,7 @@ def run_bwd(lib, be, case, inp=None):
         _set_mode(lib, case.mode)
         if case.det:
             lib.check(lib.lib.ffh_ctx_set_deterministic(lib.ctx, 1), "deterministic")
-        tw = Twins(lib, be, case, dict(x=X, w=W, y=Y, dy=DY, dx=DX), ("x", "w", "y", "dy"))
+        tw = _Regs(lib, be, case, dict(x=X, w=W, y=Y, dy=DY, dx=DX), ("x", "w", "y", "dy"))
         if case.cmap:
             lib.check(lib.lib.ffh_linear_bwd_set_dx_scatter(lib.ctx, be.addr(cmap_h), case.cmap_ncols, None), "set_dx_scatter")
         if case.colsum:
@@ -512,6 +815,19 @@ def _operand_rounding(case, rnd):
     return lambda a: _f64((rnd or rne_bf16)(np.asarray(a, np.float32)))
 
 
+def _product(case):
+    """a @ b as the reference of this case sums it: in float64 over the operands as they come, or, for the "planes" family on a layer of the split
+    mode, the six kept plane products (exact in float64: integers below 2^53)."""
+    if case.planes_exact:
+        return lambda a, b: split_product(np.asarray(a, np.float32), np.asarray(b, np.float32))
+    return lambda a, b: a @ b
+
+
+def _on_pipe(tok):
+    """The token names a launch that keeps the output's twin / image current (include/ff_hip.h)."""
+    return "bf16" in tok or "x3_dma" in tok
+
+
 def check_fwd(res, rnd=None):
     case, inp, rep = res.case, res.inp, Report()
     if res.rc != capi.FFH_OK:
@@ -520,9 +836,10 @@ def check_fwd(res, rnd=None):
     r = _operand_rounding(case, rnd)
     x, w = r(inp["x"]), r(inp["w"])
     b = _f64(inp["b"]) if case.bias else np.zeros(case.out_dim)
-    _compare(rep, "y", res.Y.get(), act64(x @ w.T + b, case.act), np.abs(x) @ np.abs(w).T + np.abs(b), LIPSCHITZ[case.act], case.integer)
+    _compare(rep, "y", res.Y.get(), act64(_product(case)(x, w.T) + b, case.act), np.abs(x) @ np.abs(w).T + np.abs(b), LIPSCHITZ[case.act],
+             case.integer or case.planes_exact)
     _buffers(rep, res)
-    _twins(rep, res, {"y": (res.Y.get(), "bf16" in res.route)})
+    _twins(rep, res, {"y": (res.Y.get(), _on_pipe(res.route))})
     return rep
 
 
@@ -544,6 +861,7 @@ def check_bwd(res, rnd=None):
     r = _operand_rounding(case, rnd)
     xr, wr = r(inp["x"]), r(inp["w"])          # the GEMMs' operands; the masks, db and the dy transform stay on the unrounded values
     only_dx, only_dw, ex = case.has(ONLY_DX), case.has(ONLY_DW), case.integer
+    prod, exg = _product(case), case.integer or case.planes_exact          # (db is a plain fp32 sum of unsplit values: exact on integers only)
     act = NONE if case.has(PREMASKED) else case.act
     dy_after = res.DY.get()
     # dy
@@ -563,7 +881,7 @@ def check_bwd(res, rnd=None):
         _untouched(rep, "dw", res.DW, "ONLY_DX")
     else:
         effr = r(eff)
-        _compare(rep, "dw", res.DW.get(), _f64(inp["dw0"]) + effr.T @ xr, np.abs(_f64(inp["dw0"])) + np.abs(effr).T @ np.abs(xr), exact=ex)
+        _compare(rep, "dw", res.DW.get(), _f64(inp["dw0"]) + prod(effr.T, xr), np.abs(_f64(inp["dw0"])) + np.abs(effr).T @ np.abs(xr), exact=exg)
     if res.DB is not None:
         if (only_dw if act == SIG else only_dx):
             _untouched(rep, "db", res.DB, "this half of the split call does not own the bias gradient")
@@ -583,7 +901,7 @@ def check_bwd(res, rnd=None):
             _untouched(rep, "dx", res.DX, "ONLY_DW")
         else:
             effr = r(eff)
-            ref, mass = effr @ wr, np.abs(effr) @ np.abs(wr)
+            ref, mass = prod(effr, wr), np.abs(effr) @ np.abs(wr)
             if case.has(MASK_BY_X):
                 keep = x > 0
                 ref, mass = np.where(keep, ref, 0.0), np.where(keep, mass, 0.0)
@@ -600,7 +918,7 @@ def check_bwd(res, rnd=None):
                     order = sel[np.argsort(col[sel])]
                     _compare(rep, f"dest{k}", d.get(), ref[:, order], mass[:, order], exact=ex)
             else:
-                _compare(rep, "dx", res.DX.get(), ref, mass, exact=ex)
+                _compare(rep, "dx", res.DX.get(), ref, mass, exact=exg)
     if not (res.scatter_used and case.cmap):
         for k, d in enumerate(res.dests):
             _untouched(rep, f"dest{k}", d, "the column map was declined")
@@ -613,7 +931,7 @@ def check_bwd(res, rnd=None):
     _buffers(rep, res)
     written = {}
     if res.DX is not None and not only_dw:
-        written["dx"] = (res.DX.get(), any("dx" in t.split("|")[0] and "bf16" in t for t in res.route.split(";")) and not (res.scatter_used and case.cmap))
+        written["dx"] = (res.DX.get(), any("dx" in t.split("|")[0] and _on_pipe(t) for t in res.route.split(";")) and not (res.scatter_used and case.cmap))
     _twins(rep, res, written)
     return rep
 
@@ -761,9 +1079,73 @@ def bf16_gemm(c, cus, name, form, M, N, K, epi, lda, ldb, ldc, a, b, a_off, b_of
     return f"{name}|bf16_{bt}x{bt}{'_twins' if twins else ''}|splitk={splitk}"
 
 
+# --- FFH_MATH_FP32_SPLIT_BF16X3_ALL: the split branch of launch_gemm_bf16 (csrc/linear_bf16.hip) and launch_gemm_x3_dma (csrc/linear_x3_dma.hip), restated
+def x3_dma_dw_split(cus, tiles, nk):
+    """The LDS-DMA weight gradient's cost search over the number of k-slices (nk k-tiles of 32; at least eight a slice), or None: no candidate."""
+    best, splitk = 1e30, None
+    for sp in range(1, 65):
+        if sp * 8 > nk:
+            break
+        nb = tiles * sp
+        if nb * 2 < cus:
+            continue
+        t = float(_cdiv(nb, cus)) * float(_cdiv(nk, sp)) * 3.0 + float(nb) * (256.0 * 256 * 4) / 1.3e6
+        if t < best:
+            best, splitk = t, sp
+    return splitk
+
+
+def x3_gemm(c, cus, name, form, M, N, K, epi, lda, ldb, ldc, a, b, a_off, b_off, c_off, masking=False, a_stale=False, bias_off=None, mask=None, cname=None,
+            db=False):
+    """The token of one split-mode GEMM; the arguments of bf16_gemm, the images looked up in c.images; cname: the output's buffer (its image in
+    place: "+image"); db: the bias gradient is handed to the weight-gradient GEMM.  The kernel behind bf16x3_128x128 is part of the token: v2w8 /
+    v2w4 (gemm_bf16x3_v2_kernel on eight or four waves: forward and data gradient) or mfma32 (gemm_bf16x3_kernel: the weight gradient)."""
+    tiles_big = _cdiv(N, 256) * _cdiv(M, 256)
+    big = (form == "fwd" or (form == "dx" and K >= 1024)) and M >= 256 and N >= 256 and tiles_big >= cus
+    if form == "dw" and epi == "atomic" and not c.det and tiles_big >= 32 and K >= 8192:
+        big = True
+    bt = 256 if big else 128
+    tiles = _cdiv(N, bt) * _cdiv(M, bt)
+    splitk = 1
+    if epi == "atomic" and c.det:
+        epi = "add"
+    if epi == "atomic":
+        want = _cdiv((1 if big else 2) * cus, tiles)
+        max_split = _cdiv(K, 256)
+        if big:
+            best, best_u = want, 0.0
+            for w2 in range(want, min(2 * want + 2, max_split) + 1):
+                nb = tiles * w2
+                u = float(nb) / float(_cdiv(nb, cus) * cus)
+                if u > best_u + 1e-9:
+                    best_u, best = u, w2
+            want = best
+        want = max(1, min(want, max_split))
+        kps = _cdiv(_cdiv(K, want), 64) * 64
+        splitk = max(2, _cdiv(K, kps))
+    served = (not masking and not a_stale and K % 32 == 0 and N % 8 == 0 and lda % 32 == 0 and ldb % 32 == 0 and ldc % 4 == 0 and c_off % 4 == 0
+              and (bias_off is None or bias_off % 4 == 0) and (mask is None or (mask[0] % 4 == 0 and mask[1] % 4 == 0))
+              and not (form == "dw" and db and (a_off % 4 or M % 4)) and a in c.images and b in c.images and a_off % 32 == 0 and b_off % 32 == 0)
+    if served:
+        t256 = _cdiv(M, 256) * _cdiv(N, 256)
+        if form == "dw":
+            sp = x3_dma_dw_split(cus, t256, K // 32) if epi == "atomic" and t256 >= 2 else None
+            if sp:
+                slots = sp > 1 and t256 * sp <= 512 and t256 * sp <= cus and c.scratch
+                return f"{name}|x3_dma_256x256_planes" + ("|slots" if slots else "")
+        elif (form == "dx" or epi == "store") and t256 * 100 >= cus * 75:
+            return f"{name}|x3_dma_256x256_planes" + ("+image" if ldc % 32 == 0 and c_off % 32 == 0 and cname in c.images else "")
+    if big and epi == "atomic":
+        return f"{name}|bf16x3_256x256|splitk={splitk}"
+    if form in ("fwd", "dx") and epi != "atomic":
+        return f"{name}|bf16x3_128x128|splitk={splitk}|" + ("v2w8" if _cdiv(N, 128) * _cdiv(M, 128) * 100 <= cus * 150 else "v2w4")
+    return f"{name}|bf16x3_128x128|splitk={splitk}|mfma32"
+
+
 def route_fwd_bf16(c, cus):
-    return [bf16_gemm(c, cus, "linear_fwd gemm (bf16)", "fwd", c.batch, c.out_dim, c.in_dim, "store", c.ldx, c.in_dim, c.ldy, "x", "w", c.x_off, c.w_off,
-                      c.y_off, bias_off=c.bias_off if c.bias else None)]
+    gemm = x3_gemm if c.x3_layer else bf16_gemm
+    return [gemm(c, cus, "linear_fwd gemm (bf16)", "fwd", c.batch, c.out_dim, c.in_dim, "store", c.ldx, c.in_dim, c.ldy, "x", "w", c.x_off, c.w_off,
+                 c.y_off, bias_off=c.bias_off if c.bias else None, **(dict(cname="y") if c.x3_layer else {}))]
 
 
 def _bwd_bf16(st, c, cus, do_dw, do_dx):
@@ -776,13 +1158,16 @@ def _bwd_bf16(st, c, cus, do_dw, do_dx):
     if relu_done:
         relu = False
     forked = do_dw and do_dx and c.forked
+    gemm, kw_dw, kw_dx = bf16_gemm, {}, {}
+    if c.x3_layer:          # the same call sites in the split mode; the bias gradient rides on the weight-gradient GEMM where no activation pass runs
+        gemm, kw_dw, kw_dx = x3_gemm, dict(db=c.db and act == NONE), dict(cname="dx")
     if do_dw:
-        toks.append(bf16_gemm(c, cus, "linear_bwd dw gemm (bf16)", "dw", o, i, B, "atomic", c.lddy, c.ldx, i, "dy", "x", c.dy_off, c.x_off, 0, a_stale=act != NONE))
+        toks.append(gemm(c, cus, "linear_bwd dw gemm (bf16)", "dw", o, i, B, "atomic", c.lddy, c.ldx, i, "dy", "x", c.dy_off, c.x_off, 0, a_stale=act != NONE, **kw_dw))
     if c.dx and do_dx:
         masking = (forked or not do_dw) and relu
-        toks.append(bf16_gemm(c, cus, "linear_bwd dx gemm (bf16, masking)" if masking else "linear_bwd dx gemm (bf16)", "dx", B, i, o,
-                              "store" if c.has(OVERWRITE) else "add", c.lddy, i, c.lddx, "dy", "w", c.dy_off, c.w_off, c.dx_off, masking=masking,
-                              a_stale=act != NONE, mask=(c.x_off, c.ldx) if c.has(MASK_BY_X) else None))
+        toks.append(gemm(c, cus, "linear_bwd dx gemm (bf16, masking)" if masking else "linear_bwd dx gemm (bf16)", "dx", B, i, o,
+                         "store" if c.has(OVERWRITE) else "add", c.lddy, i, c.lddx, "dy", "w", c.dy_off, c.w_off, c.dx_off, masking=masking,
+                         a_stale=act != NONE, mask=(c.x_off, c.ldx) if c.has(MASK_BY_X) else None, **kw_dx))
 
 
 def route_fwd(c, cus):
@@ -791,7 +1176,7 @@ def route_fwd(c, cus):
         return ["linear_fwd|skinny"]
     if i <= 16 and o >= 64 and B < 16384:
         return ["linear_fwd|thin"]
-    if c.bf16_layer:
+    if c.bf16_layer or c.x3_layer:
         return route_fwd_bf16(c, cus)
     toks = []
     al = _al(c.x_off, c.ldx) and c.w_off % 4 == 0 and i % 4 == 0 and _al(c.y_off, c.ldy) and (not c.bias or c.bias_off % 4 == 0)
@@ -824,7 +1209,7 @@ def _bwd_impl(st, c, cus, do_dw, do_dx, has_dx, forked):
     if ((o <= 4 and i <= 1024) or (o <= 16 and i <= 256)) and i % 4 == 0 and x_al and w_al and (not has_dx or dx_al) and not c.det:
         toks.append("linear_bwd|skinny")
         return
-    if c.bf16_layer:
+    if c.bf16_layer or c.x3_layer:
         _bwd_bf16(st, c, cus, do_dw, do_dx)
         return
     want_dx = has_dx and do_dx
@@ -886,13 +1271,18 @@ def _bwd_impl(st, c, cus, do_dw, do_dx, has_dx, forked):
 def normalize_route(route):
     """The library's tokens without the split and workgroup counts that route_fwd / route_bwd do not predict: every one except the split count of
     the bf16-pipe kernels of csrc/linear_bf16.hip in tensor-op mode (the LDS-DMA kernel's comes from a cost search: dma_splits() checks its range)."""
-    keep = re.compile(r"\|bf16_(128x128|256x256)(_twins)?\|splitk=\d+$")
+    keep = re.compile(r"\|bf16(_(128x128|256x256)(_twins)?\|splitk=\d+|x3_(128x128|256x256)\|splitk=\d+(\|\w+)?)$")
     return [t if keep.search(t) else re.sub(r"\|(splitk|wgs)=\d+", "", t) for t in route.split(";") if t]
 
 
 def dma_splits(route):
     """(token, splitk) of every LDS-DMA bf16 launch named in a route."""
     return [(t, int(m.group(1))) for t in route.split(";") for m in [re.search(r"bf16_dma_256x256_twins\|splitk=(\d+)(\|slots)?$", t)] if m]
+
+
+def x3_dma_splits(route):
+    """(token, splitk) of every launch of the split mode's LDS-DMA kernel named in a route."""
+    return [(t, int(m.group(1))) for t in route.split(";") for m in [re.search(r"x3_dma_256x256_planes(?:\+image)?\|splitk=(\d+)(\|slots)?$", t)] if m]
 
 
 def expected_route(case, cus):
@@ -912,11 +1302,17 @@ def check_route(res, cus):
             out.append(f"ffh_linear_dx_colsum_used = {res.colsum_used}, expected {colsum}")
         if case.det:
             out += [f"deterministic mode: {t!r} is not an ordered route" for t in res.route.split(";")
-                    if "skinny" in t or ("dw" in t.split("|")[0] and ("|sk_" in t or "glds" in t or not t.endswith("splitk=1")))]
+                    if "skinny" in t or ("dw" in t.split("|")[0] and ("|sk_" in t or "glds" in t or not re.search(r"splitk=1(\|\w+)?$", t)))]
         for t, sp in dma_splits(res.route):
             if "dw" in t.split("|")[0]:
                 if not (1 <= sp and 4 * sp <= case.batch // 64):
                     out.append(f"{t!r}: a split of {sp} slices does not leave four k-tiles each at batch {case.batch}")
+            elif sp != 1:
+                out.append(f"{t!r}: only the weight gradient splits K")
+        for t, sp in x3_dma_splits(res.route):
+            if "dw" in t.split("|")[0]:
+                if not (1 <= sp and 8 * sp <= case.batch // 32):
+                    out.append(f"{t!r}: a split of {sp} slices does not leave eight k-tiles of 32 each at batch {case.batch}")
             elif sp != 1:
                 out.append(f"{t!r}: only the weight gradient splits K")
     if cus == TABLE_CUS:
@@ -1321,3 +1717,296 @@ def draw_case_bf16(rng, name="random-bf16"):
 def draw_cases_bf16(seed, count=6):
     rng = np.random.default_rng(7000 + seed)
     return [draw_case_bf16(rng, f"bf16-seed{seed}.{k}") for k in range(count)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# FFH_MATH_FP32_SPLIT_BF16X3_ALL: the edge table (shapes derived for 256 CUs from x3_gemm above), the random cases, the run with and without images
+def _x3_table(t):
+    M3 = dict(mode=MATH_SPLIT_ALL)
+    P, U, WD = dict(dist="planes", **M3), dict(dist="uniform", **M3), dict(dist="wide", **M3)
+    F, DWT, DXT, DXM = "linear_fwd gemm (bf16)|", "linear_bwd dw gemm (bf16)|", "linear_bwd dx gemm (bf16)|", "linear_bwd dx gemm (bf16, masking)|"
+    W8, W4, S = "bf16x3_128x128|splitk=1|v2w8", "bf16x3_128x128|splitk=1|v2w4", "bf16x3_128x128|splitk="
+    DMA, DMAI = "x3_dma_256x256_planes", "x3_dma_256x256_planes+image"
+    DXO = ONLY_DX | OVERWRITE
+    # gemm_bf16x3_v2_kernel on eight waves: at most 384 tiles of 128 x 128 (150 % of the CUs); batch 200 is two tile rows.  K = 136 and 200 are no
+    # multiples of 32 (the guarded k-tile), 192 is; ragged M and N, every offset, padded rows
+    t["x3-v2w8-fwd"] = [
+        Case("x-w8-fwd-136->192", "fwd", 136, 192, 200, NONE, ldx=137, x_off=1, bias_off=1, want=F + W8, **P),
+        Case("x-w8-fwd-192->200-relu", "fwd", 192, 200, 200, RELU, w_off=4, ldy=203, y_off=2, want=F + W8, **P),
+        Case("x-w8-fwd-200->136-no-bias", "fwd", 200, 136, 200, RELU, bias=False, ldy=139, y_off=1, w_off=1, want=F + W8, **U),
+        Case("x-w8-fwd-136->200-wide", "fwd", 136, 200, 129, NONE, bias_off=2, ldx=140, want=F + W8, **WD),
+        Case("x-w8-fwd-192->136-int", "fwd", 192, 136, 200, NONE, dist="integer", want=F + W8, **M3)]
+    # the data gradient stored, accumulated, masked by x; the masking form (a live ReLU under ONLY_DX reads dy through relu'(y)); beside a
+    # weight gradient of batch <= 256 the search ends at one split and the launch runs two, the second one empty
+    t["x3-v2w8-dx"] = [
+        Case("x-w8-dx-store", "bwd", 192, 136, 200, NONE, DXO, lddy=137, dy_off=1, want=DXT + W8, **P),
+        Case("x-w8-dx-add", "bwd", 200, 192, 200, NONE, ONLY_DX, lddx=203, dx_off=1, w_off=1, want=DXT + W8, **P),
+        Case("x-w8-dx-mask-by-x", "bwd", 136, 200, 200, RELU, DXO | MASK_BY_X | PREMASKED, ldx=139, x_off=2, want=DXT + W8, **P),
+        Case("x-w8-dx-add-mask-by-x", "bwd", 192, 136, 129, NONE, ONLY_DX | MASK_BY_X, want=DXT + W8, **U),
+        Case("x-w8-dx-masking", "bwd", 136, 192, 200, RELU, DXO, ldy=195, y_off=2, want=DXM + W8, **P),
+        Case("x-w8-dx-masking-add-maskx", "bwd", 200, 136, 77, RELU, ONLY_DX | MASK_BY_X, dx_off=1, want=DXM + W8, **U),
+        Case("x-w8-both", "bwd", 192, 200, 200, NONE, OVERWRITE, want=(DWT + S + "2|mfma32", DXT + W8), **P),
+        Case("x-w8-both-live-relu-forked", "bwd", 136, 192, 200, RELU, MASK_BY_X, forked=True, want=(DWT + S + "2|mfma32", DXT + W8), **P),
+        Case("x-w8-both-sigmoid", "bwd", 200, 136, 131, SIG, 0, db=False, want=(DWT + S + "2|mfma32", DXT + W8), **U),
+        Case("x-w8-dx-wide", "bwd", 257, 129, 130, NONE, 0, want=(DWT + S + "2|mfma32", DXT + W8), **WD)]
+    # ... on four waves: more than 384 tiles: 384 wide is three tile columns, 16400 rows are 129 tile rows = 387 tiles; 16256 rows are 127 = 381
+    t["x3-v2w4"] = [
+        Case("x-w4-fwd-128->384", "fwd", 128, 384, 16400, RELU, bias_off=1, want=F + W4, **P),
+        Case("x-w4-fwd-136->380", "fwd", 136, 380, 16400, NONE, bias=False, ldy=381, y_off=1, x_off=1, want=F + W4, **U),
+        Case("x-w4-dx-store", "bwd", 384, 136, 16400, NONE, DXO, want=DXT + W4, **P),
+        Case("x-w4-dx-add-mask-by-x", "bwd", 380, 128, 16400, RELU, ONLY_DX | MASK_BY_X | PREMASKED, lddx=381, dx_off=1, want=DXT + W4, **P),
+        Case("x-w4-dx-masking", "bwd", 384, 136, 16400, RELU, DXO, want=DXM + W4, **U),
+        Case("x-w4-fwd-381-tiles", "fwd", 128, 384, 16256, RELU, want=F + W8, **P)]
+    # gemm_bf16x3_kernel, 128 x 128: 700 x (130 -> 129): 4 tiles, want 128 capped at cdiv(700, 256) = 3 splits of 256; 1100 x (257 -> 136): 6 tiles, 5
+    # splits, the last one 76 deep; batch <= 256: the forced empty second split; with and without db
+    t["x3-dw-128"] = [
+        Case("x-dw-3-splits-db", "bwd", 130, 129, 700, NONE, ONLY_DW, lddy=131, dy_off=1, ldx=133, x_off=2, want=DWT + S + "3|mfma32", **P),
+        Case("x-dw-3-splits-no-db", "bwd", 130, 129, 700, RELU, ONLY_DW | PREMASKED, db=False, want=DWT + S + "3|mfma32", **P),
+        Case("x-dw-5-splits", "bwd", 257, 136, 1100, RELU, ONLY_DW, want=DWT + S + "5|mfma32", **U),
+        Case("x-dw-no-dx", "bwd", 136, 130, 513, NONE, 0, dx=False, want=DWT + S + "3|mfma32", **WD),
+        Case("x-dw-empty-second-split", "bwd", 129, 130, 70, NONE, ONLY_DW, want=DWT + S + "2|mfma32", **P),
+        Case("x-dw-empty-second-split-256", "bwd", 192, 136, 256, NONE, ONLY_DW, db=False, want=DWT + S + "2|mfma32", **U),
+        Case("x-dw-int", "bwd", 129, 192, 700, NONE, ONLY_DW, dist="integer", want=DWT + S + "3|mfma32", **M3)]
+    # deterministic mode: one ordered split adding into dw
+    t["x3-deterministic"] = [
+        Case("x-det-700", "bwd", 130, 129, 700, NONE, ONLY_DW, det=True, lddy=131, dy_off=1, want=DWT + S + "1|mfma32", **P),
+        Case("x-det-1100", "bwd", 257, 136, 1100, RELU, 0, det=True, want=(DWT + S + "1|mfma32", DXT + W8), **U),
+        Case("x-det-images", "bwd", 192, 256, 16416, NONE, ONLY_DW, det=True, lddy=256, images=("x", "dy"), want=DWT + S + "1|mfma32", **P)]
+    # ... 256 x 256 from 32 tiles and batch 8192 on: 770 x 1800 is 4 x 8 = 32 tiles, 8 splits fill one round; 770 x 1792 is 28 tiles; batch 8190
+    t["x3-dw-256"] = [
+        Case("x-dw-big", "bwd", 1800, 770, 8200, NONE, ONLY_DW, want=DWT + "bf16x3_256x256|splitk=8", **P),
+        Case("x-dw-big-uniform", "bwd", 1800, 770, 8200, RELU, ONLY_DW | PREMASKED, db=False, want=DWT + "bf16x3_256x256|splitk=8", **U),
+        Case("x-dw-big-28-tiles", "bwd", 1792, 770, 8200, NONE, ONLY_DW, db=False, want=DWT + S + "6|mfma32", **U)]
+    # gemm_x3_dma_kernel, forward: images on x and w, from 192 tiles of 256 x 256 on (75 % of the CUs): 1000 wide is 4 tile columns, 12200 rows
+    # are 48 tile rows (ragged); the image of y in place where its rows are a multiple of 32 apart, else by the conversion pass
+    XW = ("x", "w", "y")
+    t["x3-dma-fwd"] = [
+        Case("x-dma-fwd-image", "fwd", 128, 1000, 12200, RELU, ldy=1024, images=XW, want=F + DMAI, **P),
+        Case("x-dma-fwd-convert-pass", "fwd", 128, 1000, 12200, NONE, bias_off=4, images=XW, want=F + DMA + ";", **U),
+        Case("x-dma-fwd-no-bias-no-y-image", "fwd", 160, 1000, 12200, NONE, bias=False, ldx=192, x_off=32, images=("x", "w"), want=F + DMA + ";", **P),
+        Case("x-dma-fwd-188-tiles", "fwd", 128, 1000, 12032, RELU, ldy=1024, images=XW, want=F + W4, **P)]
+    # ... data gradient: dy and w from their images (w's rows are in_dim apart: a multiple of 32), stored and accumulated, masked by x from x's
+    # image and from the fp32 x
+    BW = ("w", "dy", "dx")
+    t["x3-dma-dx"] = [
+        Case("x-dma-dx-store", "bwd", 992, 128, 12200, NONE, DXO, images=BW, want=DXT + DMAI, **P),
+        Case("x-dma-dx-add-convert-pass", "bwd", 992, 128, 12200, RELU, ONLY_DX | PREMASKED, lddx=996, images=BW, want=DXT + DMA + ";", **U),
+        Case("x-dma-dx-188-tiles", "bwd", 992, 128, 12032, NONE, DXO, images=BW, want=DXT + W4, **U)]
+    t["x3-dma-dx-masked"] = [
+        Case("x-dma-dx-mask-image", "bwd", 992, 128, 12200, NONE, DXO | MASK_BY_X, images=("x",) + BW, want=DXT + DMAI, **P),
+        Case("x-dma-dx-mask-fp32", "bwd", 992, 128, 12200, NONE, ONLY_DX | MASK_BY_X, ldx=996, images=BW, want=DXT + DMAI, **U)]
+    # ... weight gradient: 2 tiles (264 x 192) need 64 slices for 128 workgroups (half the CUs) of eight k-tiles of 32: batch 16384 (16416: nine
+    # in some); 6 tiles (520 x 320) need 22 slices: batch 5632.  One round: through the stream's slots; without scratch by atomics
+    DW2 = dict(images=("x", "dy"))
+    t["x3-dma-dw"] = [
+        Case("x-dma-dw-2-tiles-db", "bwd", 192, 264, 16416, NONE, ONLY_DW, lddy=288, want=DWT + DMA + "|slots", **DW2, **P),
+        Case("x-dma-dw-2-tiles-no-db", "bwd", 192, 264, 16384, RELU, ONLY_DW | PREMASKED, lddy=288, db=False, want=DWT + DMA + "|slots", **DW2, **U),
+        Case("x-dma-dw-2-tiles-atomics", "bwd", 192, 264, 16416, NONE, ONLY_DW, lddy=288, scratch=False, want=DWT + DMA + ";", **DW2, **P),
+        Case("x-dma-dw-6-tiles", "bwd", 320, 520, 5632, NONE, ONLY_DW, lddy=544, db=False, want=DWT + DMA + "|slots", **DW2, **P),
+        Case("x-dma-dw-6-tiles-atomics", "bwd", 320, 520, 5632, NONE, ONLY_DW, lddy=544, scratch=False, want=DWT + DMA + ";", **DW2, **U),
+        Case("x-dma-dw-no-split-fits", "bwd", 192, 264, 16352, NONE, ONLY_DW, lddy=288, want=DWT + S + "64|mfma32", **DW2, **P),
+        Case("x-dma-dw-one-tile", "bwd", 192, 192, 16416, NONE, ONLY_DW, db=False, want=DWT + S, **DW2, **U)]
+    # images registered, the LDS-DMA kernel declines (every shape is one it serves otherwise): the split-in-kernel form runs and the output's
+    # image is written all the same; y off the group grid is served, its image written by the conversion pass
+    t["x3-dma-declined-operands"] = [
+        Case("x-nd-x-off", "fwd", 128, 1000, 12200, RELU, ldx=160, x_off=8, ldy=1024, images=XW, want=F + W4, **P),
+        Case("x-nd-ldx", "fwd", 128, 1000, 12200, NONE, ldx=132, images=XW, want=F + W4, **U),
+        Case("x-nd-one-operand", "fwd", 128, 1000, 12200, NONE, ldy=1024, images=("x", "y"), want=F + W4, **U)]
+    t["x3-dma-declined-shape"] = [
+        Case("x-nd-k", "fwd", 136, 1000, 12200, NONE, ldx=160, ldy=1024, images=XW, want=F + W4, **P),
+        Case("x-nd-n", "fwd", 128, 1004, 12200, RELU, ldy=1024, images=XW, want=F + W4, **U)]
+    t["x3-dma-image-by-the-conversion-pass"] = [
+        Case("x-nd-y-off-grid", "fwd", 128, 1000, 12200, RELU, ldy=1024, y_off=4, images=XW, want=F + DMA + ";", **P),
+        Case("x-nd-ldy", "fwd", 128, 1000, 12200, NONE, ldy=1004, y_off=32, images=XW, want=F + DMA + ";", **U)]
+    t["x3-dma-declined-live-activation"] = [
+        Case("x-nd-live-relu-masking", "bwd", 992, 128, 12200, RELU, DXO, images=BW, stale=("dy",), want=DXM + W4, **P),
+        Case("x-nd-live-sigmoid", "bwd", 992, 128, 12200, SIG, DXO, images=BW, stale=("dy",), want=DXT + W4, **U),
+        Case("x-nd-live-relu-dw", "bwd", 192, 264, 16416, RELU, OVERWRITE, lddy=288, images=("x", "w", "dy", "dx"), stale=("dy",), want=(DWT + S + "65|mfma32", DXT + W8), **P)]
+    # narrow layers keep the fp32 kernels: no image is written (the one-launch backward of out_dim <= 16 refreshes dx's by the conversion pass:
+    # allowed, not required), and "planes" is held to the bound against the unsplit product there
+    t["x3-narrow-layers"] = [
+        Case("x-narrow-in127", "fwd", 127, 256, 300, RELU, images=XW, want="linear_fwd gemm|f32_", **U),
+        Case("x-narrow-out127", "fwd", 256, 127, 300, NONE, images=XW, want="linear_fwd gemm|f32_", **P),
+        Case("x-narrow-bwd-in127", "bwd", 127, 256, 300, RELU, OVERWRITE, images=("x", "w", "dy", "dx"), want=("linear_bwd dw gemm|f32_", "linear_bwd dx gemm|f32_"), **U),
+        Case("x-narrow-bwd-out127", "bwd", 256, 127, 300, NONE, 0, images=("x", "w", "dy", "dx"), want=("linear_bwd dw gemm|f32_", "linear_bwd dx gemm|f32_"), **WD),
+        Case("x-narrow-skinny-fwd", "fwd", 256, 4, 300, SIG, images=XW, want="linear_fwd|skinny", **U),
+        Case("x-narrow-skinny-bwd", "bwd", 256, 1, 4100, SIG, OVERWRITE | MASK_BY_X, images=("x", "w", "dy", "dx"), want="linear_bwd|skinny", **U)]
+
+
+def x3_edge_table(cus=TABLE_CUS):
+    t = {}
+    _x3_table(t)
+    return t
+
+
+X3_EDGE_NAMES = list(x3_edge_table())
+# kernel (as the issue lists them) -> a substring of the tokens that name it
+X3_KERNELS = {"gemm_bf16x3_kernel 128 x 128": "|mfma32", "gemm_bf16x3_kernel 256 x 256": "bf16x3_256x256", "gemm_bf16x3_v2_kernel, four waves": "|v2w4",
+              "gemm_bf16x3_v2_kernel, eight waves": "|v2w8", "gemm_x3_dma_kernel forward": "linear_fwd gemm (bf16)|x3_dma_256x256_planes",
+              "gemm_x3_dma_kernel data gradient": "linear_bwd dx gemm (bf16)|x3_dma_256x256_planes",
+              "gemm_x3_dma_kernel weight gradient": "linear_bwd dw gemm (bf16)|x3_dma_256x256_planes", "x3_dw_reduce_kernel": "x3_dma_256x256_planes|slots"}
+
+
+def draw_case_x3(rng, name="random-x3"):
+    """draw_case with each width raised to at least 128 with probability three quarters, in the split mode, a random subset of images, a random
+    distribution."""
+    c = draw_case(rng, name)
+    i = max(c.in_dim, BF16_MIN_DIM) if rng.random() < 0.75 else c.in_dim
+    o = max(c.out_dim, BF16_MIN_DIM) if rng.random() < 0.75 else c.out_dim
+    images = [] if rng.random() < 0.2 else [n for n in IMAGE_NAMES if rng.random() < 0.5]
+    dist = str(rng.choice(["uniform", "integer", "wide", "planes", "planes"]))
+    if dist != "uniform" and c.act not in (NONE, RELU):
+        dist = "uniform"
+    return c.replace(in_dim=i, out_dim=o, ldx=i + c.ldx - c.in_dim, lddx=i + c.lddx - c.in_dim, ldy=o + c.ldy - c.out_dim, lddy=o + c.lddy - c.out_dim,
+                     mode=MATH_SPLIT_ALL, images=images, dist=dist)
+
+
+def draw_cases_x3(seed, count=6):
+    rng = np.random.default_rng(9000 + seed)
+    return [draw_case_x3(rng, f"x3-seed{seed}.{k}") for k in range(count)]
+
+
+def run_and_check_x3(lib, be, case, cus=None, routes=True):
+    """run_and_check; where the case has images and its y or dx came from a kernel of the split mode, the same case once more without images: the
+    header promises the same bits in y and dx (the weight gradient is held to its bound, or to equality, in both runs)."""
+    res, rep = run_and_check(lib, be, case, cus, routes)
+    split_out = [n for n, tok in (("y", res.route if case.kind == "fwd" else ""),) + tuple(("dx", t) for t in res.route.split(";") if "dx" in t.split("|")[0])
+                 if "bf16x3" in tok or "x3_dma" in tok]
+    if case.images and rep.ok() and split_out:
+        c2 = case.replace(images=(), stale=(), want=())
+        bare = (run_fwd if case.kind == "fwd" else run_bwd)(lib, be, c2, res.inp)
+        same = True
+        for name in split_out:
+            a, b = dict(res.outputs).get(name), dict(bare.outputs).get(name)
+            if a is not None and a.host.tobytes() != b.host.tobytes():
+                same = False
+                rep.violations.append(f"{name}: differs between the run with images ({res.route}) and the run without ({bare.route})")
+        # y and dx equal, whole buffers, to what was just checked: numbers and sentinels are checked with that; anything else the call writes
+        # (a weight or bias gradient, dy and db under a live activation) is checked again, and so is the route
+        final_dy = case.has(PREMASKED) or case.act == NONE
+        if same and (case.kind == "fwd" or (case.has(ONLY_DX) and final_dy)) and bare.rc == capi.FFH_OK:
+            rep2 = Report()
+            _buffers(rep2, bare)
+            if case.kind == "bwd" and not all(b.untouched() for n, b in bare.outputs if n in ("dw", "db")):
+                rep2.violations.append("dw / db: written under ONLY_DX")
+        else:
+            rep2 = check_fwd(bare) if case.kind == "fwd" else check_bwd(bare)
+        if be.is_hip and routes and bare.rc == capi.FFH_OK and case.batch > 0:
+            rep2.violations += check_route(bare, cus)
+        rep.violations += [f"without images: {v}" for v in rep2.violations]
+    return res, rep
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the entry points of the split mode in numpy, the arithmetic a parameter: what tests/test_linear_x3_sweep_cpu.py feeds the checker
+class NumpySplitLib:
+    """ffh_linear_fwd / ffh_linear_bwd_ex on host memory as include/ff_hip.h states them, a layer of the split mode summed by split_product(pairs,
+    rnd) and rounded to fp32 once, every other layer in float64; images registered with ffh_ctx_bf16x3_mirror_set are kept as the header says
+    (write_images False: an output's image is left alone).  Only what run_fwd / run_bwd call."""
+
+    def __init__(self, pairs=SIX, rnd=None, write_images=True):
+        self.lib, self.ctx, self.pairs, self.rnd, self.write_images = self, None, pairs, rnd, write_images
+        self.mode, self.regions = 0, {}
+
+    def check(self, rc, what=""):
+        assert rc == capi.FFH_OK, what
+
+    @staticmethod
+    def _view(ptr, rows, cols, ld):
+        if ptr is None or rows * cols == 0:
+            return None
+        flat = np.ctypeslib.as_array((C.c_float * ((rows - 1) * ld + cols)).from_address(int(ptr)))
+        return np.lib.stride_tricks.as_strided(flat, (rows, cols), (4 * ld, 4))
+
+    def _image(self, ptr, rows, cols, ld, rnd=None):
+        """Write the planes of the [rows][cols] block at ptr into the image of the region that holds it; False: no such region."""
+        ptr = int(ptr)
+        for base, (nbytes, img) in self.regions.items():
+            if base <= ptr and ptr + 4 * ((rows - 1) * ld + cols) <= base + nbytes:
+                e = ((ptr - base) // 4 + np.arange(rows)[:, None] * ld + np.arange(cols)[None, :]).ravel()
+                planes = np.ctypeslib.as_array((C.c_uint16 * image_len(nbytes // 4)).from_address(img))
+                planes[image_at(e)[None, :] + 32 * np.arange(3)[:, None]] = plane_bits(self._view(ptr, rows, cols, ld), rnd)
+                return True
+        return False
+
+    def _prod(self, a, b, split):
+        if split:
+            return split_product(np.asarray(a, np.float32), np.asarray(b, np.float32), self.pairs, self.rnd)
+        return _f64(a) @ _f64(b)
+
+    def ffh_ctx_set_math_mode(self, ctx, mode):
+        self.mode = mode
+        return 0
+
+    def ffh_ctx_set_deterministic(self, ctx, on):
+        return 0
+
+    def ffh_stream_create(self, ctx, ref):
+        return 0
+
+    def ffh_stream_sync(self, ctx, s):
+        return 0
+
+    def ffh_linear_last_route(self, ctx):
+        return b""
+
+    def ffh_linear_dx_scatter_used(self, ctx):
+        return 0
+
+    def ffh_linear_dx_colsum_used(self, ctx):
+        return 0
+
+    def ffh_ctx_bf16x3_mirror_set(self, ctx, base, nbytes, img):
+        if img is None:
+            self.regions.pop(int(base), None)
+        else:
+            self.regions[int(base)] = (int(nbytes), int(img))
+        return 0
+
+    def ffh_convert_f32_to_bf16x3(self, ctx, src, rows, cols, ld, s):
+        return 0 if self._image(src, rows, cols, ld) else capi.FFH_ERR_BAD_ARG          # (the explicit conversion is not the mutant)
+
+    def _split(self, i, o):
+        return self.mode == MATH_SPLIT_ALL and i >= BF16_MIN_DIM and o >= BF16_MIN_DIM
+
+    def ffh_linear_fwd(self, ctx, x, ldx, y, ldy, w, bias, i, o, B, act, s):
+        if B == 0:
+            return 0
+        X, W, Y = self._view(x, B, i, ldx), self._view(w, o, i, i), self._view(y, B, o, ldy)
+        b = _f64(self._view(bias, 1, o, o)[0]) if bias else 0.0
+        Y[:] = act64(self._prod(X, W.T, self._split(i, o)) + b, act).astype(np.float32)
+        if self._split(i, o) and self.write_images:
+            self._image(y, B, o, ldy, self.rnd)
+        return 0
+
+    def ffh_linear_bwd_ex(self, ctx, x, ldx, dx, lddx, y, ldy, dy, lddy, w, dw, db, i, o, B, act, flags, s, s_dw):
+        if B == 0:
+            return 0
+        X, W, Y, G = self._view(x, B, i, ldx), self._view(w, o, i, i), self._view(y, B, o, ldy), self._view(dy, B, o, lddy)
+        only_dx, only_dw, split = bool(flags & ONLY_DX), bool(flags & ONLY_DW), self._split(i, o)
+        act = NONE if flags & PREMASKED else act
+        eff = G
+        if act == RELU:
+            eff = np.where(Y > 0, G, np.float32(0))
+            if not only_dx:
+                G[:] = eff
+        elif act == SIG and not only_dw:
+            eff = (_f64(G) * _f64(Y) * (1.0 - _f64(Y))).astype(np.float32)
+            G[:] = eff
+        if not only_dx:
+            DW = self._view(dw, o, i, i)
+            DW[:] = (_f64(DW) + self._prod(eff.T, X, split)).astype(np.float32)
+        if db and not (only_dw if act == SIG else only_dx):
+            DB = self._view(db, 1, o, o)
+            DB[0] = (_f64(DB[0]) + _f64(eff).sum(0)).astype(np.float32)
+        if dx and not only_dw:
+            DX = self._view(dx, B, i, lddx)
+            v = self._prod(eff, W, split)
+            if flags & MASK_BY_X:
+                v = np.where(X > 0, v, 0.0)
+            if not flags & OVERWRITE:
+                v = v + _f64(DX)
+            DX[:] = v.astype(np.float32)
+            if split and self.write_images:
+                self._image(dx, B, i, lddx, self.rnd)
+        return 0
