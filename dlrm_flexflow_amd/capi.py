@@ -967,6 +967,71 @@ def fold_api(lib: "FFHLib") -> FoldApi:
     return FoldApi(lib)
 
 
+# ---- the bags extension (include/ff_hip_bags.h): the gather with a bag size per table, one launch ------------------------------------------
+BAGS_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_bags.h")
+BAGS_MAX_IN_DIM = 65535
+
+_SIGS_BAGS = {
+    "ffh_bags_abi_version": (I, []),
+    "ffh_bags_kernarg_bytes": (SZ, []),
+    "ffh_embedding_fwd_multi_bags": (I, [P, C.POINTER(EmbTable), C.POINTER(I), I, I, L, I, P]),
+    "ffh_embedding_fwd_multi_bags_bf16": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(I), I, I, L, I, P]),
+}
+
+
+def bags_header_symbols(header_path: str = BAGS_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_BAGS_API_LIST X-macro in include/ff_hip_bags.h."""
+    m = re.search(r"#define FFH_BAGS_API_LIST\(X\)(.*?)\n\n", open(header_path).read(), re.S)
+    if not m:
+        raise RuntimeError("FFH_BAGS_API_LIST not found in " + header_path)
+    return re.findall(r"X\((\w+)\)", m.group(1))
+
+
+def bags_header_abi_version(header_path: str = BAGS_HEADER_PATH) -> int:
+    """FFH_BAGS_ABI_VERSION of include/ff_hip_bags.h."""
+    m = re.search(r"#define\s+FFH_BAGS_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_BAGS_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
+class BagsApi:
+    """The bags extension (include/ff_hip_bags.h) of a loaded FFHLib; `bags_api(lib)` builds it or raises."""
+
+    def __init__(self, lib: "FFHLib"):
+        self.base = lib
+        for name, (res, args) in _SIGS_BAGS.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no bags extension ({name} missing; include/ff_hip_bags.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_bags_abi_version()
+        if got != bags_header_abi_version():
+            raise FFHError(f"{lib.path}: bags ABI version {got}, include/ff_hip_bags.h says {bags_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+    @staticmethod
+    def in_dims(sizes) -> "C.Array":
+        """The `in_dims` argument: one C int per table."""
+        sizes = [int(v) for v in sizes]
+        return (I * max(1, len(sizes)))(*sizes)
+
+    def rc(self, name: str, tables, in_dims, ntables: int, out_dim: int, batch: int, aggr: int, stream=None) -> int:
+        """`name(ctx, tables, in_dims, ...)`, returning its status code; `tables` from FFHLib.emb_tables / Bf16Api.tables, `in_dims` from
+        BagsApi.in_dims (or None: a null pointer)."""
+        return getattr(self.lib, name)(self.ctx, tables, in_dims, int(ntables), int(out_dim), int(batch), int(aggr), ptr(stream))
+
+    def call(self, name: str, *args, **kw):
+        self.base.check(self.rc(name, *args, **kw), name)
+
+
+def bags_api(lib: "FFHLib") -> BagsApi:
+    """The ragged-gather entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
+    return BagsApi(lib)
+
+
 _hip_singleton: FFHLib | None = None
 
 

@@ -20,6 +20,7 @@
 #include "emb_reduce.h"
 #include "fold_sum.h"
 #include "lr_state.h"
+#include "../../include/ff_hip_bags.h"
 
 #include <type_traits>
 
@@ -142,6 +143,175 @@ __global__ __launch_bounds__(256) void emb_fwd_kernel(const EmbArgs a) {
       }
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// forward with a bag size per table (include/ff_hip_bags.h): the same sums, per table, as emb_fwd_kernel -- acc = +0, then
+// acc = acc + W[idx[b][j]] for j ascending, AVG times the table's own 1 / L -- so a table's output is the bits of emb_fwd_kernel on
+// that table alone.  What differs is how the work is laid over the chip:
+//   * a FLAT grid.  Table t gets bag_blocks() workgroups, in proportion to its lookups batch * L_t (at least one, at most one per
+//     row block); workgroup -> (table, first row block) is a scan over the <= 64 bag sizes in the kernel arguments.  The scan is
+//     block-uniform (SGPRs), and host and kernel compute it with the one function below.
+//   * long bags (L >= kBagLong) keep JU consecutive j of a row in flight beside U rows: a bag's ids are contiguous, the loads of
+//     JU ids and then of JU table rows are issued together, and the adds follow in ascending j.  Short bags run U = 4 rows with one
+//     j each, as emb_fwd_kernel does.  Long bags take half the rows per workgroup, so a table of few rows and long bags still
+//     splits into enough row blocks.
+// Kernel arguments: 64 tables of 40 bytes plus two pointer arrays are 3584 bytes; a bag size in 16 bits and the image column (< 32)
+// in 8 bits per table keep the struct below EmbArgs' size, and the prefix of the workgroup map is derived, not passed.
+// ---------------------------------------------------------------------------
+constexpr int kBagLong = 4;        // bags of at least this many ids take the JU = 4 form
+constexpr int kBagMaxL = 65535;    // BagArgs::L is 16 bits (FFH_BAGS_MAX_IN_DIM)
+struct BagArgs {
+  ffh_emb_table t[FFH_MAX_TABLES];
+  unsigned short* out16[FFH_MAX_TABLES];   // as EmbArgs::out16
+  char* out3[FFH_MAX_TABLES];              // as EmbArgs::out3 ...
+  uint16_t L[FFH_MAX_TABLES];              // bag size of table i
+  uint8_t  out3c[FFH_MAX_TABLES];          // ... and EmbArgs::out3c (0 .. 31)
+  int64_t batch;
+  int64_t nrb[2];        // row blocks of the batch: [0] short bags (U = 4), [1] long bags (U = 2)
+  int     ntables;
+  int     D;
+  int     aggr;
+  int     shift;         // workgroups of table i = clamp((batch * L[i]) >> shift, 1, nrb)
+};
+static_assert(sizeof(BagArgs) <= sizeof(EmbArgs) && sizeof(BagArgs) <= 4096, "kernel arguments");
+
+__host__ __device__ inline int64_t bag_blocks(int64_t batch, int L, int shift, int64_t nrb) {
+  int64_t w = (batch * (int64_t)L) >> shift;
+  w = w < 1 ? 1 : w;
+  return w > nrb ? nrb : w;
+}
+
+// the rows [first, first + step, ...) x rows_per_block of table t; U rows x JU ids in flight per lane-group
+template <int VEC, int U, int JU, class WT>
+__device__ __forceinline__ void bag_rows(const BagArgs& a, const int t, const int64_t first, const int64_t step) {
+  using vec_t = typename RowVec<VEC, WT>::type;
+  constexpr int NQ = VEC / 4;
+  const ffh_emb_table tb = a.t[t];
+  const WT* const wt = reinterpret_cast<const WT*>(tb.weight);
+  unsigned short* const o16 = a.out16[t];
+  char* const o3 = a.out3[t];
+  const int o3c = a.out3c[t];
+  const int D = a.D, L = a.L[t];
+  const int nvec = D / VEC;
+  const int lpr = nvec < 64 ? nvec : 64;
+  const int rpw = 64 / lpr;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int rsub = lane / lpr;
+  const int c0 = lane - rsub * lpr;
+  const bool active = rsub < rpw;
+  const int64_t rows_per_block = 4LL * rpw * U;      // 256 threads
+  const float inv = 1.0f / (float)L;
+  const bool avg = a.aggr == FFH_AGGR_MODE_AVG;
+
+  for (int64_t base = first * rows_per_block; base < a.batch; base += step * rows_per_block) {
+    const int64_t b0 = base + (int64_t)wave * rpw * U + rsub;
+    bool ok[U];
+    const int64_t* ids[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const int64_t b = b0 + (int64_t)u * rpw;
+      ok[u] = active && b < a.batch;
+      ids[u] = tb.idx + b * L;
+    }
+    for (int c = c0; c < nvec; c += lpr) {
+      float acc[U][VEC];
+#pragma unroll
+      for (int u = 0; u < U; u++)
+#pragma unroll
+        for (int v = 0; v < VEC; v++) acc[u][v] = 0.0f;
+      int j = 0;
+      if constexpr (JU > 1) {
+        for (; j + JU <= L; j += JU) {
+          int64_t row[U][JU];
+#pragma unroll
+          for (int u = 0; u < U; u++)
+#pragma unroll
+            for (int k = 0; k < JU; k++) row[u][k] = ok[u] ? ids[u][j + k] : 0;
+          vec_t val[U][JU];
+#pragma unroll
+          for (int u = 0; u < U; u++)
+#pragma unroll
+            for (int k = 0; k < JU; k++)
+              if (ok[u]) val[u][k] = *(reinterpret_cast<const vec_t*>(wt + row[u][k] * (int64_t)D) + c);
+#pragma unroll
+          for (int u = 0; u < U; u++)
+            if (ok[u]) {
+#pragma unroll
+              for (int k = 0; k < JU; k++)           // ascending j: the order of emb_fwd_kernel
+#pragma unroll
+                for (int v = 0; v < VEC; v++) acc[u][v] = acc[u][v] + row_elem<VEC, WT>(val[u][k], v);
+            }
+        }
+      }
+      for (; j < L; j++) {
+        int64_t row[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) row[u] = ok[u] ? ids[u][j] : 0;
+        vec_t val[U];
+#pragma unroll
+        for (int u = 0; u < U; u++)
+          if (ok[u]) val[u] = *(reinterpret_cast<const vec_t*>(wt + row[u] * (int64_t)D) + c);
+#pragma unroll
+        for (int u = 0; u < U; u++)
+          if (ok[u]) {
+#pragma unroll
+            for (int v = 0; v < VEC; v++) acc[u][v] = acc[u][v] + row_elem<VEC, WT>(val[u], v);   // 0 + w first, as emb_fwd_kernel
+          }
+      }
+      // the stores of emb_fwd_kernel, statement by statement (that kernel is left as it compiles today)
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        const int64_t b = b0 + (int64_t)u * rpw;
+        if (ok[u]) {
+          float f[VEC];
+#pragma unroll
+          for (int v = 0; v < VEC; v++) f[v] = avg ? acc[u][v] * inv : acc[u][v];
+          if constexpr (NQ == 0) {
+            tb.io[b * tb.ld + c] = f[0];
+          } else {
+#pragma unroll
+            for (int h = 0; h < NQ; h++) {
+              const int q = c * NQ + h;
+              const float* g = f + 4 * h;
+              typedef float f4 __attribute__((ext_vector_type(4)));
+              const f4 o = {g[0], g[1], g[2], g[3]};
+              reinterpret_cast<f4*>(tb.io + b * tb.ld)[q] = o;
+              if (o16) {
+                typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+                const bf2 lo = {(__bf16)g[0], (__bf16)g[1]}, hi = {(__bf16)g[2], (__bf16)g[3]};
+                reinterpret_cast<uint2*>(o16 + b * tb.ld)[q] = make_uint2(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi));
+              }
+              if (o3) {
+                uint2 p1, p2, p3;
+                ffh_split_bf16x3(make_float4(g[0], g[1], g[2], g[3]), p1, p2, p3);
+                char* d = o3 + b * tb.ld * 6 + ffh_i32_off(o3c + 4 * q);
+                *reinterpret_cast<uint2*>(d) = p1; *reinterpret_cast<uint2*>(d + 64) = p2; *reinterpret_cast<uint2*>(d + 128) = p3;
+              }
+            }
+          }
+        }
+      }
+    }
+  }
+}
+
+template <int VEC, class WT>
+__global__ __launch_bounds__(256) void emb_fwd_bags_kernel(const BagArgs a) {
+  ffh_kernel_prio();
+  // workgroup -> (table, first row block of the table): block-uniform
+  int t = 0;
+  int64_t first = blockIdx.x, w = 0;
+  for (; t < a.ntables; t++) {
+    const int L = a.L[t];
+    w = bag_blocks(a.batch, L, a.shift, L >= kBagLong ? a.nrb[1] : a.nrb[0]);
+    if (first < w) break;
+    first -= w;
+  }
+  if (t >= a.ntables) return;
+  if (a.L[t] >= kBagLong) bag_rows<VEC, 2, 4, WT>(a, t, first, w);
+  else bag_rows<VEC, 4, 1, WT>(a, t, first, w);
 }
 
 // ---------------------------------------------------------------------------
@@ -300,9 +470,64 @@ static int emb_fwd_launch(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   return FFH_OK;
 }
 
+// include/ff_hip_bags.h.  WT as in emb_fwd_launch; the 16-byte form under the same conditions, so a table's bits are those of its own
+// ffh_embedding_fwd call wherever that call and this one take the same form (all tables aligned alike, or D % 4 != 0).
+template <class WT>
+static int emb_fwd_bags_launch(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, int nt, int D, int64_t batch, int aggr, ffh_stream s) {
+  int rc = validate_tables(c, tables, nt, 1, D, batch, aggr, "embedding_fwd_bags");
+  if (rc) return rc;
+  if (nt > 0 && !in_dims) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_fwd_multi_bags: null in_dims");
+  for (int i = 0; i < nt; i++) {
+    if (in_dims[i] < 1) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_fwd_multi_bags: in_dims[i] < 1");
+    if (in_dims[i] > kBagMaxL) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_fwd_multi_bags: in_dims[i] > FFH_BAGS_MAX_IN_DIM (65535)");
+  }
+  if (nt == 0 || batch == 0) return FFH_OK;
+  constexpr bool b16 = std::is_same<WT, uint16_t>::value;
+  int vec = can_vec4(tables, nt, D) ? 4 : 1;
+  if (b16) {
+    bool ok = D % 4 == 0;
+    for (int i = 0; i < nt; i++) ok = ok && ((uintptr_t)tables[i].weight & 7) == 0 && aligned16(tables[i].io) && tables[i].ld % 4 == 0;
+    vec = ok ? 4 : 1;
+  }
+  const int nvec = D / vec;
+  if ((nvec + 63) / 64 > kMaxChunks * 64) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_fwd_multi_bags: out_dim too large");
+  BagArgs a;
+  memset(&a, 0, sizeof a);
+  for (int i = 0; i < nt; i++) {
+    a.t[i] = tables[i];
+    a.L[i] = (uint16_t)in_dims[i];
+    // the twin / the image of the destination, under emb_fwd_launch's conditions
+    a.out16[i] = (vec >= 4 && tables[i].ld % 4 == 0) ? ffh_mirror_of(c, tables[i].io, (size_t)((batch - 1) * tables[i].ld + D) * 4) : nullptr;
+    int col0 = 0;
+    a.out3[i] = (vec >= 4 && tables[i].ld % 32 == 0) ? ffh_planes_of(c, tables[i].io, (size_t)((batch - 1) * tables[i].ld + D) * 4, &col0) : nullptr;
+    a.out3c[i] = (uint8_t)col0;
+    if (a.out3[i] && (col0 & 3)) a.out3[i] = nullptr;
+  }
+  a.batch = batch; a.ntables = nt; a.D = D; a.aggr = aggr;
+  const int lpr = nvec < 64 ? nvec : 64;
+  const int rpw = 64 / lpr;
+  const int64_t rpb_short = 4LL * rpw * 4, rpb_long = 4LL * rpw * 2;      // bag_rows<.., U = 4 / 2, ..> at 256 threads
+  a.nrb[0] = (batch + rpb_short - 1) / rpb_short;
+  a.nrb[1] = (batch + rpb_long - 1) / rpb_long;
+  // workgroups in proportion to the lookups: the smallest shift at which the tables' shares fit 256 CUs x 8 workgroups
+  static const int cap_env = FFH_LAB_INT("FFH_EMB_BAGS_CAP", 2048);      // A/B switch: workgroups over all tables (>= FFH_MAX_TABLES)
+  const int64_t cap = cap_env > FFH_MAX_TABLES ? cap_env : FFH_MAX_TABLES;
+  int64_t total = 0;
+  for (int sh = 0; sh < 63; sh++) {
+    total = 0;
+    for (int i = 0; i < nt; i++) total += bag_blocks(batch, in_dims[i], sh, a.nrb[in_dims[i] >= kBagLong ? 1 : 0]);
+    a.shift = sh;
+    if (total <= cap) break;
+  }
+  if (vec == 4) hipLaunchKernelGGL((emb_fwd_bags_kernel<4, WT>), dim3((unsigned)total), dim3(256), 0, as_stream(s), a);
+  else hipLaunchKernelGGL((emb_fwd_bags_kernel<1, WT>), dim3((unsigned)total), dim3(256), 0, as_stream(s), a);
+  FFH_LAUNCH_CHECK(c, "emb_fwd_bags_kernel");
+  return FFH_OK;
+}
+
 extern "C" {
 
-int ffh_embedding_fwd_multi(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L, int D, int64_t batch, int aggr, ffh_stream s) {
+int ffh_embedding_fwd_multi(ffh_ctx* c,const ffh_emb_table* tables, int nt, int L, int D, int64_t batch, int aggr, ffh_stream s) {
   return emb_fwd_launch<float>(c, tables, nt, L, D, batch, aggr, s);
 }
 
@@ -731,5 +956,21 @@ int ffh_bf16_counter_advance(ffh_ctx* c, uint64_t* counter, ffh_stream s) {
 
 int ffh_rowwise_abi_version(void) { return FFH_ROWWISE_ABI_VERSION; }      // include/ff_hip_rowwise.h: the row rule lives in this file
 
+// include/ff_hip_bags.h: the gather with a bag size per table
+int ffh_bags_abi_version(void) { return FFH_BAGS_ABI_VERSION; }
+size_t ffh_bags_kernarg_bytes(void) { return sizeof(BagArgs); }
+
+int ffh_embedding_fwd_multi_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, int nt, int D, int64_t batch, int aggr, ffh_stream s) {
+  return emb_fwd_bags_launch<float>(c, tables, in_dims, nt, D, batch, aggr, s);
+}
+
+int ffh_embedding_fwd_multi_bags_bf16(ffh_ctx* c, const ffh_emb_table_bf16* tables, const int* in_dims, int nt, int D, int64_t batch, int aggr, ffh_stream s) {
+  ffh_emb_table t[FFH_MAX_TABLES];
+  const int rc = bf16_tables(c, tables, nt, t, nullptr);
+  if (rc) return rc;
+  return emb_fwd_bags_launch<uint16_t>(c, t, in_dims, nt, D, batch, aggr, s);
+}
+
 }  // extern "C"
 static_assert(sizeof(EmbArgs) <= 4096, "kernel arguments");
+static_assert(kBagMaxL == FFH_BAGS_MAX_IN_DIM, "include/ff_hip_bags.h");

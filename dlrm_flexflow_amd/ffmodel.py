@@ -136,7 +136,7 @@ def lib() -> C.CDLL:
         "flexflow_tensor_get_data_type": (I, [H]),
         "flexflow_tensor_set_bf16": (None, [H, H, IP, I, P]), "flexflow_tensor_get_bf16": (None, [H, H, P]),
         "flexflow_dlrm_create": (H, [I, C.POINTER(C.c_char_p), C.POINTER(FFComm)]), "flexflow_dlrm_destroy": (None, [H]),
-        "flexflow_dlrm_get_model": (H, [H]), "flexflow_dlrm_get_num_samples": (I, [H]), "flexflow_dlrm_get_num_tables": (I, [H]), "flexflow_dlrm_get_start_epoch": (I, [H]),
+        "flexflow_dlrm_get_model": (H, [H]), "flexflow_dlrm_get_num_samples": (I, [H]), "flexflow_dlrm_get_num_tables": (I, [H]), "flexflow_dlrm_get_bag_size": (I, [H, I]), "flexflow_dlrm_get_start_epoch": (I, [H]),
         "flexflow_dlrm_get_sparse_input": (H, [H, I]), "flexflow_dlrm_get_dense_input": (H, [H]),
         "flexflow_dlrm_warmup": (None, [H]), "flexflow_dlrm_train_steps": (None, [H, I, B]),
         "flexflow_dlrm_run_epochs": (D, [H]), "flexflow_dlrm_time_kernel": (F, [H, I, I]),
@@ -736,6 +736,7 @@ class DLRM:
 
     num_samples = property(lambda s: lib().flexflow_dlrm_get_num_samples(s.h))
     num_tables = property(lambda s: lib().flexflow_dlrm_get_num_tables(s.h))
+    bag_sizes = property(lambda s: [lib().flexflow_dlrm_get_bag_size(s.h, t) for t in range(s.num_tables)])      # ids per sample, per table (--embedding-bag-size / --embedding-bag-sizes)
     start_epoch = property(lambda s: lib().flexflow_dlrm_get_start_epoch(s.h))      # --load-checkpoint: the epochs the checkpoint had completed
     def sparse_input(self, t) -> Tensor: return Tensor(lib().flexflow_dlrm_get_sparse_input(self.h, t), self.model)
     def dense_input(self) -> Tensor: return Tensor(lib().flexflow_dlrm_get_dense_input(self.h), self.model)

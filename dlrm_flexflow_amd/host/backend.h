@@ -13,6 +13,7 @@
 #include "../../include/ff_hip_adagrad.h"
 #include "../../include/ff_hip_rowwise.h"
 #include "../../include/ff_hip_fold.h"
+#include "../../include/ff_hip_bags.h"
 
 // The optional bf16-table extension (include/ff_hip_bf16.h): all of its list or none of it.
 struct KernelApiBf16 {
@@ -77,6 +78,13 @@ struct KernelApiFold {
 #undef FFH_DECL
 };
 
+// The optional bags extension (include/ff_hip_bags.h: the embedding gather with a bag size per table, one launch).
+struct KernelApiBags {
+#define FFH_DECL(name) decltype(&::name) name;
+  FFH_BAGS_API_LIST(FFH_DECL)
+#undef FFH_DECL
+};
+
 struct KernelApi {
 #define FFH_DECL(name) decltype(&::name) name;
   FFH_API_LIST(FFH_DECL)
@@ -90,6 +98,7 @@ struct KernelApi {
   const KernelApiAdagrad* adagrad = nullptr; // likewise for include/ff_hip_adagrad.h
   const KernelApiRowwise* rowwise = nullptr; // likewise for include/ff_hip_rowwise.h
   const KernelApiFold* fold = nullptr;       // likewise for include/ff_hip_fold.h (absent: no table is folded, the step is the one of before)
+  const KernelApiBags* bags = nullptr;       // likewise for include/ff_hip_bags.h (absent: a model of mixed bag sizes gathers once per bag size)
   void* handle;
   std::string path;
   bool overridden = false;      // chosen by --backend or $FFH_BACKEND_LIB rather than the product default: the driver says so on its THROUGHPUT line

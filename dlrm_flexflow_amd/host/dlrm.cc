@@ -29,7 +29,7 @@ void print_vector(const std::string& name, const std::vector<int>& v) {
 }  // namespace
 
 DLRMConfig::DLRMConfig(void)
-    : sparse_feature_size(2), sigmoid_bot(-1), sigmoid_top(-1), embedding_bag_size(1), loss_threshold(0.0f),
+    : sparse_feature_size(2), sigmoid_bot(-1), sigmoid_top(-1), embedding_bag_size(1), bag_size_given(false), loss_threshold(0.0f),
       arch_interaction_op("cat"), dataset_path(""), data_size(-1), optimizer("sgd"), zipf_alpha(0.0), dcn_num_layers(3), dcn_low_rank_dim(512) {
   embedding_size.push_back(4);
   mlp_bot.push_back(4); mlp_bot.push_back(2);
@@ -57,12 +57,13 @@ void parse_input_args(char** argv, int argc, DLRMConfig& config) {
       };
       if (eq && is("--arch-interaction-op")) { config.arch_interaction_op = std::string(next()); continue; }
       if (eq && is("--optimizer")) { config.optimizer = std::string(next()); continue; }
+      if (is("--embedding-bag-sizes")) { config.embedding_bag_sizes = split(next()); continue; }      // one per table, the format of --arch-embedding-size
       if (is("--dcn-num-layers")) { config.dcn_num_layers = atoi(next()); continue; }
       if (is("--dcn-low-rank-dim")) { config.dcn_low_rank_dim = atoi(next()); continue; }
     }
     if (!strcmp(argv[i], "--arch-sparse-feature-size")) { config.sparse_feature_size = atoi(argv[++i]); continue; }
     if (!strcmp(argv[i], "--arch-embedding-size")) { config.embedding_size = split(argv[++i]); continue; }
-    if (!strcmp(argv[i], "--embedding-bag-size")) { config.embedding_bag_size = atoi(argv[++i]); continue; }
+    if (!strcmp(argv[i], "--embedding-bag-size")) { config.embedding_bag_size = atoi(argv[++i]); config.bag_size_given = true; continue; }
     if (!strcmp(argv[i], "--arch-mlp-bot")) { config.mlp_bot = split(argv[++i]); continue; }
     if (!strcmp(argv[i], "--arch-mlp-top")) { config.mlp_top = split(argv[++i]); continue; }
     if (!strcmp(argv[i], "--loss-threshold")) { config.loss_threshold = (float)atof(argv[++i]); continue; }
@@ -141,7 +142,7 @@ DataLoader::DataLoader(FFModel& ff, const DLRMConfig& dlrm, const std::vector<Te
     : num_samples(0), next_index(0), epoch(0), batch_sparse_inputs(sparse_inputs), batch_dense_input(dense_input), batch_label(label),
       full_dense(nullptr), full_label(nullptr), model(&ff) {
   num_train = 0;
-  bag = dlrm.embedding_bag_size;
+  for (size_t t = 0; t < sparse_inputs.size(); t++) bags.push_back(dlrm.bag_of(t));
   dense_dim = dense_input.adim[0];
   full_sparse.assign(sparse_inputs.size(), nullptr);
   if (dlrm.dataset_path != "") load_hdf5(ff, dlrm);
@@ -151,7 +152,7 @@ DataLoader::DataLoader(FFModel& ff, const DLRMConfig& dlrm, const std::vector<Te
   num_train = num_samples - ff.config.eval_batches * ff.config.batchSize;
   if (ff.config.data_randomize) {
     for (size_t t = 0; t < batch_sparse_inputs.size(); t++)
-      segments.push_back({full_sparse[t], full_sparse[t] ? batch_sparse_inputs[t].impl->ptr : nullptr, 8 * bag, FFH_GATHER_GLOBAL_ROWS});
+      segments.push_back({full_sparse[t], full_sparse[t] ? batch_sparse_inputs[t].impl->ptr : nullptr, 8 * bags[t], FFH_GATHER_GLOBAL_ROWS});
     segments.push_back({full_dense, batch_dense_input.impl->ptr, 4 * dense_dim, FFH_GATHER_LOCAL_ROWS});
     segments.push_back({full_label, batch_label.impl->ptr, 4, FFH_GATHER_LOCAL_ROWS});
   }
@@ -184,7 +185,7 @@ void DataLoader::generate_random(FFModel& ff, const DLRMConfig& dlrm) {
   // sparse ids: owner of table t keeps ids of every sample (it gathers for the global batch)
   for (size_t t = 0; t < batch_sparse_inputs.size(); t++) {
     if (!batch_sparse_inputs[t].impl->ptr) continue;          // this rank neither owns the table nor holds a column block of it
-    const int64_t n = (int64_t)num_samples * bag;
+    const int64_t n = (int64_t)num_samples * bags[t];
     full_sparse[t] = (int64_t*)ff.dmalloc((size_t)n * sizeof(int64_t));
     if (dlrm.zipf_alpha > 0.0) generate_zipf(ff, full_sparse[t], n, s0 + 17 + t, dlrm.embedding_size[t], dlrm.zipf_alpha);
     else ff.check(ff.api->ffh_gen_indices(ff.ctx, full_sparse[t], n, s0 + 17 + t, 0, dlrm.embedding_size[t], ff.stream), "gen_indices");
@@ -249,7 +250,7 @@ void DataLoader::generate_zipf(FFModel& ff, int64_t* dst, int64_t n, uint64_t se
 
 // The Criteo file of the reference [ref: examples/cpp/DLRM/dlrm.cc:279-326 (shape checks), :421-479 (H5Dread of X_cat as
 // LLONG, X_int and y as FLOAT); written by preprocess_hdf.py:14-24]: X_int [N][dense] float (already log(x+1)),
-// X_cat [N][tables*bag] integer, y [N] or [N][1] float.  The whole set becomes device-resident in the same layout the
+// X_cat [N][sum of the tables' bag sizes] integer, y [N] or [N][1] float.  The whole set becomes device-resident in the same layout the
 // synthetic generator produces; the file is read in row chunks so that host memory stays bounded.
 void DataLoader::load_hdf5(FFModel& ff, const DLRMConfig& dlrm) {
   const bool chatty = ff.world_size <= 1 || ff.rank == 0;
@@ -265,7 +266,15 @@ void DataLoader::load_hdf5(FFModel& ff, const DLRMConfig& dlrm) {
   if ((int)xi.dims[1] != dense_dim) bad("X_int's second dimension must equal --arch-mlp-bot[0]");                 // [ref: dlrm.cc:292]
   if (xc.dims.size() != 2 || xc.type_class != 0) bad("X_cat must be a 2-D integer dataset");
   if (xc.dims[0] != xi.dims[0] || yy.dims[0] != xi.dims[0]) bad("X_int, X_cat and y must have the same number of samples");
-  if (xc.dims[1] != T * (size_t)bag) bad("X_cat's second dimension must equal (number of tables) x (bag size)");  // [ref: dlrm.cc:307]
+  size_t C = 0;                      // X_cat's columns: table t's ids in [sum of the bag sizes before it, ... + bags[t])
+  std::vector<size_t> col0(T);
+  int max_bag = 1;
+  for (size_t t = 0; t < T; t++) { col0[t] = C; C += (size_t)bags[t]; max_bag = std::max(max_bag, bags[t]); }
+  if (xc.dims[1] != C) {             // [ref: dlrm.cc:307]
+    char msg[192];
+    snprintf(msg, sizeof msg, "X_cat's second dimension must equal the sum of the tables' bag sizes, %zu (it is %llu)", C, (unsigned long long)xc.dims[1]);
+    bad(msg);
+  }
   if (yy.dims.size() == 2 && yy.dims[1] != 1) bad("y must be [N] or [N][1]");
   const int B = ff.config.batchSize;
   uint64_t n_file = xi.dims[0];
@@ -276,13 +285,12 @@ void DataLoader::load_hdf5(FFModel& ff, const DLRMConfig& dlrm) {
   const int nb = num_samples / B;
   const int64_t Bl = ff.local_batch;
   for (size_t t = 0; t < T; t++)
-    if (batch_sparse_inputs[t].impl->ptr) full_sparse[t] = (int64_t*)ff.dmalloc((size_t)num_samples * bag * sizeof(int64_t));
+    if (batch_sparse_inputs[t].impl->ptr) full_sparse[t] = (int64_t*)ff.dmalloc((size_t)num_samples * bags[t] * sizeof(int64_t));
   full_dense = (float*)ff.dmalloc((size_t)nb * Bl * dense_dim * sizeof(float));
   full_label = (float*)ff.dmalloc((size_t)nb * Bl * sizeof(float));
 
   const int batches_per_chunk = std::max(1, (1 << 18) / B);       // about 256k samples per pass over the file
-  const size_t C = T * (size_t)bag;
-  std::vector<int64_t> cat((size_t)batches_per_chunk * B * C), col((size_t)batches_per_chunk * B * bag);
+  std::vector<int64_t> cat((size_t)batches_per_chunk * B * C), col((size_t)batches_per_chunk * B * max_bag);
   std::vector<float> xint((size_t)batches_per_chunk * B * dense_dim), lab((size_t)batches_per_chunk * B);
   for (int k0 = 0; k0 < nb; k0 += batches_per_chunk) {
     const int kb = std::min(batches_per_chunk, nb - k0);
@@ -293,13 +301,14 @@ void DataLoader::load_hdf5(FFModel& ff, const DLRMConfig& dlrm) {
     for (size_t t = 0; t < T; t++) {
       if (!full_sparse[t]) continue;
       const int64_t R = dlrm.embedding_size[t];
+      const int bag = bags[t];
       for (uint64_t i = 0; i < rows; i++)
         for (int j = 0; j < bag; j++) {
-          const int64_t id = cat[i * C + t * bag + j];
+          const int64_t id = cat[i * C + col0[t] + j];
           // the reference gathers without a bounds check on the GPU and asserts on the CPU path (src/ops/embedding.cc:71-73)
           if (id < 0 || id >= R) {
             fprintf(stderr, "FATAL: --dataset %s: X_cat[%llu][%zu] = %lld is outside table %zu (%lld rows)\n", dlrm.dataset_path.c_str(),
-                    (unsigned long long)(row0 + i), t * bag + j, (long long)id, t, (long long)R);
+                    (unsigned long long)(row0 + i), col0[t] + j, (long long)id, t, (long long)R);
             abort();
           }
           col[i * bag + j] = id;
@@ -360,8 +369,8 @@ void DataLoader::load_batch(FFModel& ff, int k) {
   ff.order_input_writes_behind_update();       // eager steps: the last step's table update may still be reading the ids
   for (size_t t = 0; t < batch_sparse_inputs.size(); t++) {
     if (!full_sparse[t]) continue;
-    ff.check(ff.api->ffh_memcpy_d2d(ff.ctx, batch_sparse_inputs[t].impl->ptr, full_sparse[t] + first * bag,
-                                    (size_t)B * bag * sizeof(int64_t), ff.stream), "load sparse");
+    ff.check(ff.api->ffh_memcpy_d2d(ff.ctx, batch_sparse_inputs[t].impl->ptr, full_sparse[t] + first * bags[t],
+                                    (size_t)B * bags[t] * sizeof(int64_t), ff.stream), "load sparse");
   }
   ff.check(ff.api->ffh_memcpy_d2d(ff.ctx, batch_dense_input.impl->ptr, full_dense + (int64_t)k * Bl * dense_dim,
                                   (size_t)Bl * dense_dim * sizeof(float), ff.stream), "load dense");
@@ -392,7 +401,12 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
   const bool chatty = ffconfig.comm.world_size <= 1 || ffconfig.comm.rank == 0;
   if (chatty) {
     printf("[DLRM] batchSize(%d) workersPerNodes(%d) numNodes(%d)\n", ffconfig.batchSize, ffconfig.workersPerNode, ffconfig.numNodes);
-    printf("[DLRM] EmbeddingBagSize(%d)\n", dlrm.embedding_bag_size);
+    if (dlrm.embedding_bag_sizes.empty()) printf("[DLRM] EmbeddingBagSize(%d)\n", dlrm.embedding_bag_size);
+    else {
+      std::string list;
+      for (size_t i = 0; i < dlrm.embedding_bag_sizes.size(); i++) list += (i ? "-" : "") + std::to_string(dlrm.embedding_bag_sizes[i]);
+      printf("[DLRM] EmbeddingBagSizes(%s)\n", list.c_str());
+    }
     print_vector("Embedding Vocab Sizes", dlrm.embedding_size);
     print_vector("MLP Top", dlrm.mlp_top);
     print_vector("MLP Bot", dlrm.mlp_bot);
@@ -413,11 +427,28 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
       abort();
     }
   }
+  if (!dlrm.embedding_bag_sizes.empty()) {
+    // --embedding-bag-sizes: one entry >= 1 per table, instead of --embedding-bag-size
+    if (dlrm.bag_size_given) {
+      fprintf(stderr, "FATAL: --embedding-bag-sizes and --embedding-bag-size were both given: give the per-table list or the one size, not both\n");
+      abort();
+    }
+    if (dlrm.embedding_bag_sizes.size() != dlrm.embedding_size.size()) {
+      fprintf(stderr, "FATAL: --embedding-bag-sizes has %zu entries for %zu tables (--arch-embedding-size): give one bag size per table, or one for all with "
+                      "--embedding-bag-size\n", dlrm.embedding_bag_sizes.size(), dlrm.embedding_size.size());
+      abort();
+    }
+    for (size_t i = 0; i < dlrm.embedding_bag_sizes.size(); i++)
+      if (dlrm.embedding_bag_sizes[i] < 1) {
+        fprintf(stderr, "FATAL: --embedding-bag-sizes: entry %zu is %d, a bag size must be >= 1 (--embedding-bag-size has the same rule)\n", i, dlrm.embedding_bag_sizes[i]);
+        abort();
+      }
+  }
   if (dlrm.embedding_size.size() > MAX_NUM_EMB) { fprintf(stderr, "FATAL: more than %d tables\n", MAX_NUM_EMB); abort(); }
   ff = new FFModel(ffconfig);
 
   for (size_t i = 0; i < dlrm.embedding_size.size(); i++) {
-    const int dims[] = {ffconfig.batchSize, dlrm.embedding_bag_size};
+    const int dims[] = {ffconfig.batchSize, dlrm.bag_of(i)};
     sparse_inputs.push_back(ff->create_tensor<2>(dims, DT_INT64));
   }
   {
@@ -468,6 +499,7 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
                 ffconfig.comm.world_size > 1 ? ", per-rank stripes" : "");
   }
   ff->compile(optimizer, (LossType)ffconfig.driver_loss, metrics);
+  if (chatty && !dlrm.embedding_bag_sizes.empty()) printf("[DLRM] embedding gather: %s\n", ff->bag_gather_line().c_str());      // a per-table list: how the gather runs
   if (const AdagradOptimizer* ag = dynamic_cast<const AdagradOptimizer*>(optimizer)) {
     // what --optimizer adagrad allocated on this rank: S beside every fp32 weight it updates, fp32 beside bf16 tables too (on fp32 tables it doubles their HBM)
     size_t bytes = ag->state_bytes;

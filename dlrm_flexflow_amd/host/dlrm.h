@@ -14,6 +14,9 @@
 struct DLRMConfig {
   DLRMConfig(void);   // defaults of [ref: examples/cpp/DLRM/dlrm.h:25-36]
   int sparse_feature_size, sigmoid_bot, sigmoid_top, embedding_bag_size;
+  std::vector<int> embedding_bag_sizes;   // --embedding-bag-sizes a-b-c-...: one bag size per table (not a reference flag; empty: embedding_bag_size for all)
+  bool bag_size_given;                    // --embedding-bag-size was on the command line (refused beside --embedding-bag-sizes)
+  int bag_of(size_t table) const { return embedding_bag_sizes.empty() ? embedding_bag_size : embedding_bag_sizes[table]; }
   float loss_threshold;
   std::vector<int> embedding_size, mlp_bot, mlp_top;
   std::string arch_interaction_op, dataset_path;
@@ -56,9 +59,10 @@ class DataLoader {
   std::vector<ffh_gather_segment> segments;                 // ... its segments: one per table (null destination: not held by this rank), the dense features, the labels
   std::vector<Tensor> batch_sparse_inputs;
   Tensor batch_dense_input, batch_label;
-  std::vector<int64_t*> full_sparse;   // per owned table: [num_samples][bag]
+  std::vector<int64_t*> full_sparse;   // per owned table: [num_samples][bags[t]]
   float *full_dense, *full_label;      // this rank's samples of every batch: [num_samples/world][...]
-  int bag, dense_dim;
+  std::vector<int> bags;               // bag size per table
+  int dense_dim;
   FFModel* model;
 };
 

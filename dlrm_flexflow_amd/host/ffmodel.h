@@ -145,6 +145,7 @@ class FFConfig {
                                // measured on the trace's first calls, one GPU (--adaptive-replay): on this runtime the replay of a two-stream step costs a
                                // small model more than its launches (Kaggle shape: 210 vs 170 us).  -1 = not given: the FFModel API replays (1), the DLRM
                                // driver's timed loop adapts (0)
+  bool ragged_gather;          // tables of differing bag sizes are gathered in one launch per group (include/ff_hip_bags.h; A/B: --no-ragged-gather = one launch per bag size)
   bool fold_small_tables;      // small embedding tables folded out of the first top layer's forward GEMM (include/ff_hip_fold.h; A/B: --no-fold-small-tables)
   int64_t fold_max_rows;       // ... tables of at most this many rows (--fold-max-rows N)
   bool fold_dw;                // ... and out of its weight-gradient GEMM (A/B: --no-fold-dw)
@@ -721,6 +722,10 @@ class FFModel {
   uint64_t* digest_acc = nullptr;             // the digest's accumulator word in device memory (allocated by the first use)
   mutable int64_t n_graph_replays = 0;        // hipGraph launches of an already captured trace (tests: flexflow_model_get_counter "graph_replays")
   mutable int64_t n_early_sorts = 0;          // sort-only launches issued behind the gather (tests: flexflow_model_get_counter "early_sorts")
+  mutable int64_t n_ragged_gathers = 0;       // ffh_embedding_fwd_multi_bags[_bf16] launches (tests: flexflow_model_get_counter "ragged_gather_launches")
+  bool mixed_bags = false;                    // the tables' bag sizes differ (allocate()): DESIGN section 19
+  bool ragged_gather_on() const;              // ... and their gather is the one-launch ragged one (the library has it, no --no-ragged-gather)
+  std::string bag_gather_line() const;        // how a model of mixed bag sizes gathers, for the driver's transcript
   bool fused_embedding_update() const;        // the tables are updated on the sorted segments (plain SGD, or any optimizer with --sparse-embedding-optimizer)
   bool sparse_rule(ffh_sparse_opt& rule) const;   // the row rule in force; false: plain SGD
   mutable bool opt_next_done = false;          // Optimizer::next() has run for the step in flight (update() does it; backward() clears it)

@@ -173,6 +173,7 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   if (n == "direct_allreduces") return M(m)->n_direct_allreduces;
   if (n == "bf16_updates") return (int64_t)M(m)->read_bf16_counter();
   if (n == "early_sorts") return M(m)->n_early_sorts;
+  if (n == "ragged_gather_launches") return M(m)->n_ragged_gathers;      // ffh_embedding_fwd_multi_bags[_bf16] launches (mixed bag sizes; include/ff_hip_bags.h)
   if (n == "lr_steps") return M(m)->lr_steps();
   if (n == "lr_route") return M(m)->lr_route;          // 0 off (the scalar launches of before), 1 host, 2 device
   if (n == "graph_replays") return M(m)->n_graph_replays;
@@ -228,6 +229,7 @@ int flexflow_dlrm_get_start_epoch(flexflow_dlrm_t h) { return A(h)->start_epoch;
 flexflow_model_t flexflow_dlrm_get_model(flexflow_dlrm_t h) { flexflow_model_t m; m.impl = A(h)->ff; return m; }
 int flexflow_dlrm_get_num_samples(flexflow_dlrm_t h) { return A(h)->loader->num_samples; }
 int flexflow_dlrm_get_num_tables(flexflow_dlrm_t h) { return (int)A(h)->sparse_inputs.size(); }
+int flexflow_dlrm_get_bag_size(flexflow_dlrm_t h, int t) { return A(h)->dlrm.bag_of((size_t)t); }
 flexflow_tensor_t flexflow_dlrm_get_sparse_input(flexflow_dlrm_t h, int t) { return wrap(A(h)->sparse_inputs.at(t)); }
 flexflow_tensor_t flexflow_dlrm_get_dense_input(flexflow_dlrm_t h) { return wrap(A(h)->dense_input); }
 void flexflow_dlrm_warmup(flexflow_dlrm_t h) { A(h)->warmup(); }
@@ -311,12 +313,11 @@ float flexflow_dlrm_time_kernel(flexflow_dlrm_t h, int which, int iters) {
   std::vector<std::vector<const int64_t*>> probe_ids;
   std::vector<void*> probe_bufs;
   if (which == 8 || which == 9) {
-    const int L = ff->embeddings.empty() ? 1 : ff->embeddings[0]->inputs[0].adim[0];
     for (int set = 0; set < kProbeSets; set++) {
       std::vector<const int64_t*> ptrs;
       for (const FFModel::EmbShard& sh : ff->shards) {
         if (sh.owner != ff->rank) continue;
-        const int64_t n = (int64_t)ff->config.batchSize * L;
+        const int64_t n = (int64_t)ff->config.batchSize * sh.e->inputs[0].adim[0];
         void* buf = nullptr;
         ff->check(ff->api->ffh_malloc(ff->ctx, &buf, (size_t)n * sizeof(int64_t)), "probe ids");
         ff->check(ff->api->ffh_gen_indices(ff->ctx, (int64_t*)buf, n, 0x9e3779b97f4a7c15ull * (uint64_t)(set + 1) + (uint64_t)ptrs.size(), 0, sh.e->num_entries, ff->stream), "probe ids");

@@ -172,6 +172,7 @@ void flexflow_dlrm_destroy(flexflow_dlrm_t);
 flexflow_model_t flexflow_dlrm_get_model(flexflow_dlrm_t);
 int  flexflow_dlrm_get_num_samples(flexflow_dlrm_t);
 int  flexflow_dlrm_get_num_tables(flexflow_dlrm_t);
+int  flexflow_dlrm_get_bag_size(flexflow_dlrm_t, int table);      /* ids per sample of table `table` (--embedding-bag-size, or its entry of --embedding-bag-sizes) */
 int  flexflow_dlrm_get_start_epoch(flexflow_dlrm_t);   /* --load-checkpoint: the epochs the checkpoint had completed (0 without it) */
 flexflow_tensor_t flexflow_dlrm_get_sparse_input(flexflow_dlrm_t, int table);
 flexflow_tensor_t flexflow_dlrm_get_dense_input(flexflow_dlrm_t);

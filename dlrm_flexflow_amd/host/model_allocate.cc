@@ -356,10 +356,21 @@ void FFModel::allocate() {
   if (T) {
     D = embeddings[0]->out_channels;
     L = embeddings[0]->inputs[0].adim[0];
-    for (Embedding* e : embeddings)
-      if (e->out_channels != D || e->inputs[0].adim[0] != L || e->aggr != embeddings[0]->aggr)
-        die("all embedding tables must share out_dim, bag size and aggregation (DLRM)");
+    mixed_bags = false;
+    for (Embedding* e : embeddings) {
+      if (e->out_channels != D || e->aggr != embeddings[0]->aggr) die("all embedding tables must share out_dim and aggregation (DLRM)");
+      if (e->inputs[0].adim[0] != L) mixed_bags = true;
+    }
     if (T > FFH_MAX_TABLES * 8) die("too many embedding tables");
+    // Bag sizes may differ per table where a table lives whole on one rank: the row-sharded, column-sharded and replicated
+    // paths read one bag size for all their tables
+    if (mixed_bags)
+      for (Embedding* e : embeddings) {
+        const char* flag = e->row_sharded ? "--row-shard-rows" : e->column_sharded ? "--column-shard-rows" : e->replicated ? "--replicate-embedding-rows" : nullptr;
+        if (flag)
+          die("embedding tables with different bag sizes (--embedding-bag-sizes) are supported table-wise only: %s is %s here; drop %s (or give every table "
+              "one bag size with --embedding-bag-size)", e->name, e->row_sharded ? "row-sharded" : e->column_sharded ? "column-sharded" : "replicated", flag);
+      }
   }
   owned_tables.clear();
   for (Embedding* e : embeddings)
@@ -855,8 +866,12 @@ void FFModel::allocate() {
   // ---- 6. workspace + metrics -------------------------------------------------------------------
   workspace_bytes = 256;
   if (owned_shards && fused) {
-    const int chunk = std::min(owned_shards, FFH_MAX_TABLES);
-    workspace_bytes = api->ffh_embedding_bwd_workspace_bytes(chunk, L, D, config.batchSize) + 256;
+    // the update runs once per bag size (launch_shard_groups), the calls sharing the workspace: the largest of them
+    std::map<int, int> owned_by_bag;
+    for (const EmbShard& sh : shards)
+      if (sh.owner == rank) owned_by_bag[sh.e->inputs[0].adim[0]]++;
+    for (const auto& kv : owned_by_bag)
+      workspace_bytes = std::max(workspace_bytes, api->ffh_embedding_bwd_workspace_bytes(std::min(kv.second, FFH_MAX_TABLES), kv.first, D, config.batchSize) + 256);
   }
   for (Embedding* e : embeddings)
     if (e->row_sharded) workspace_bytes = std::max(workspace_bytes, api->ffh_embedding_bwd_workspace_bytes(1, L, D, config.batchSize) + 256);
@@ -1042,6 +1057,7 @@ void FFModel::allocate() {
 void FFModel::plan_fold() {
   fold = FoldRoute();
   if (!config.fold_small_tables || !api->fold || exchange || world_size != 1 || embeddings.empty()) return;
+  if (mixed_bags) return;      // the fold is planned on one bag size
   if (config.allow_tensor_op_math_conversion || config.fp32_split_bf16x3) return;
   for (Op* op : layers) {
     Linear* li = dynamic_cast<Linear*>(op);

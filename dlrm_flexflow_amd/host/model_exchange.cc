@@ -2,11 +2,15 @@
 // (one of the translation units of the host shim: model_internal.h lists them)
 #include "model_internal.h"
 
+#include <map>
+#include <tuple>
+
 // =============================================================================================
 // embedding group: batched gather (+ exchange) and batched fused update
 // =============================================================================================
 // launches one batched kernel per distinct shard width (all table-wise tables share one; column blocks of
-// giant tables another); FWD: gather, else fused backward + SGD
+// giant tables another) and, where the tables' bag sizes differ, per bag size (the gather: one ragged launch where the
+// library has it); FWD: gather, else fused backward + SGD
 void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_ctx* cx, const std::vector<const int64_t*>* idx_override, bool all_tables) {
   const bool fwd = what == kGather;
   ffh_sparse_opt rule;
@@ -14,11 +18,13 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
   // the rate from device memory (include/ff_hip_lr.h): the opt entries with the table update's own block; kind FFH_SPARSE_OPT_SGD = the plain update's bits
   const ffh_lr_state* lrb = ff->lr_route == FFModel::kLrDevice ? ff->lr_block[1] : nullptr;
   const KernelApiLr* lra = ff->api->lr;
-  const int L = ff->embeddings[0]->inputs[0].adim[0];
   const int aggr = (int)ff->embeddings[0]->aggr;
-  // by shard width, then storage (bf16 tables: include/ff_hip_bf16.h, keyed by global table index and global column)
-  struct Group { std::vector<ffh_emb_table> t; std::vector<ffh_emb_table_bf16> t16; std::vector<ffh_emb_state> st; };
-  std::map<std::pair<int, bool>, Group> groups;
+  // by shard width, then storage (bf16 tables: include/ff_hip_bf16.h, keyed by global table index and global column), then bag size.  The update's
+  // entry points take one bag size per call, so its groups are always split by bag size; the gather of a model of mixed bag sizes keeps a group
+  // whole (key 0) where the library has the one-launch ragged gather (include/ff_hip_bags.h) and --no-ragged-gather is not given
+  const bool ragged = fwd && ff->ragged_gather_on();
+  struct Group { std::vector<ffh_emb_table> t; std::vector<ffh_emb_table_bf16> t16; std::vector<ffh_emb_state> st; std::vector<int> bag; };
+  std::map<std::tuple<int, bool, int>, Group> groups;
   size_t owned_i = 0;
   for (const FFModel::EmbShard& sh : ff->shards) {
     if (sh.owner != ff->rank) continue;
@@ -37,16 +43,24 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
       t.io = (fwd ? ff->xsend : ff->grecv) + sh.off;
       t.ld = ff->rank_width[ff->rank];
     }
-    Group& g = groups[{sh.cols, e->bf16_weights()}];
+    const int bag = e->inputs[0].adim[0];
+    Group& g = groups[std::make_tuple(sh.cols, e->bf16_weights(), ragged ? 0 : bag)];
     if (e->bf16_weights()) g.t16.push_back(ffh_emb_table_bf16{t.idx, (uint16_t*)t.weight, t.io, t.num_entries, t.ld, e->table_index, sh.col0});
     else g.t.push_back(t);
     g.st.push_back(ffh_emb_state{e->opt_state[0], e->opt_state[1]});
+    g.bag.push_back(bag);
   }
   const int64_t B = ff->config.batchSize;
   for (auto& kv : groups) {
-    const int D = kv.first.first;
+    const int D = std::get<0>(kv.first);
     const Group& g = kv.second;
-    if (kv.first.second) {
+    const int L = g.bag[0];
+    // tables [b, b + n) of the group in one ragged launch: where their bag sizes differ (else the call stays the uniform one)
+    auto differ = [&](size_t b, int n) {
+      for (int i = 1; i < n; i++) if (g.bag[b + i] != g.bag[b]) return true;
+      return false;
+    };
+    if (std::get<1>(kv.first)) {
       const KernelApiBf16* b16 = ff->api->bf16;
       const ffh_bf16_rounding rnd = ff->bf16_rounding();
       const size_t per = ff->bf16_tables_per_launch();       // momentum / Adam: FFH_BF16_MAX_STATEFUL_TABLES (the sort of an early-sorted group matches it)
@@ -55,7 +69,12 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
         const ffh_emb_table_bf16* tb = g.t16.data() + b;
         const ffh_emb_state* st = g.st.data() + b;
         switch (what) {
-          case kGather: ff->check(b16->ffh_embedding_fwd_multi_bf16(cx, tb, n, L, D, B, aggr, s), "embedding_fwd_multi_bf16"); break;
+          case kGather:
+            if (ragged && differ(b, n)) {
+              ff->check(ff->api->bags->ffh_embedding_fwd_multi_bags_bf16(cx, tb, g.bag.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags_bf16");
+              ff->n_ragged_gathers++;
+            } else ff->check(b16->ffh_embedding_fwd_multi_bf16(cx, tb, n, g.bag[b], D, B, aggr, s), "embedding_fwd_multi_bf16");
+            break;
           case kFusedUpdate:
             if (lrb) ff->check(lra->ffh_embedding_bwd_opt_fused_multi_bf16_lr(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, lrb, s), "embedding_bwd_opt_fused_multi_bf16_lr");
             else if (ruled) ff->check(b16->ffh_embedding_bwd_opt_fused_multi_bf16(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, s), "embedding_bwd_opt_fused_multi_bf16");
@@ -76,7 +95,12 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
     for (size_t b = 0; b < tabs.size(); b += FFH_MAX_TABLES) {
       const int n = (int)std::min<size_t>(FFH_MAX_TABLES, tabs.size() - b);
       switch (what) {
-        case kGather: ff->check(ff->api->ffh_embedding_fwd_multi(cx, tabs.data() + b, n, L, D, B, aggr, s), "embedding_fwd_multi"); break;
+        case kGather:
+          if (ragged && differ(b, n)) {
+            ff->check(ff->api->bags->ffh_embedding_fwd_multi_bags(cx, tabs.data() + b, g.bag.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags");
+            ff->n_ragged_gathers++;
+          } else ff->check(ff->api->ffh_embedding_fwd_multi(cx, tabs.data() + b, n, g.bag[b], D, B, aggr, s), "embedding_fwd_multi");
+          break;
         case kFusedUpdate:
           if (lrb) ff->check(lra->ffh_embedding_bwd_opt_fused_multi_lr(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, lrb, s), "embedding_bwd_opt_fused_multi_lr");
           else if (ruled) ff->check(ff->api->ffh_embedding_bwd_opt_fused_multi(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, s), "embedding_bwd_opt_fused_multi");
@@ -91,6 +115,19 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
       }
     }
   }
+}
+
+bool FFModel::ragged_gather_on() const { return mixed_bags && config.ragged_gather && api->bags; }
+// how a model of mixed bag sizes gathers (the driver prints it): the launches of one gather over this rank's tables
+std::string FFModel::bag_gather_line() const {
+  std::set<std::tuple<int, bool, int>> keys;
+  for (const EmbShard& sh : shards)
+    if (sh.owner == rank) keys.insert(std::make_tuple(sh.cols, sh.e->bf16_weights(), ragged_gather_on() ? 0 : sh.e->inputs[0].adim[0]));
+  char buf[160];
+  if (!mixed_bags) { snprintf(buf, sizeof buf, "one bag size, %zu launch%s", keys.size(), keys.size() == 1 ? "" : "es"); return buf; }
+  if (ragged_gather_on()) snprintf(buf, sizeof buf, "ragged, one launch per group (%zu launch%s)", keys.size(), keys.size() == 1 ? "" : "es");
+  else snprintf(buf, sizeof buf, "per bag size, %zu launches%s", keys.size(), !api->bags ? " (the kernel library has no ragged gather)" : " (--no-ragged-gather)");
+  return buf;
 }
 
 // bf16 tables: the rounding of this model's table update.  The stochastic bits' seed is ffh_hash(FFConfig::seed, kBf16SeedSalt) --
@@ -153,11 +190,13 @@ bool FFModel::early_sort_possible(int where) const {
   const bool exact_gemms = !config.allow_tensor_op_math_conversion && !config.fp32_split_bf16x3;
   const int mode = config.early_sort > 0 ? config.early_sort : ((!exchange && local_batch >= 8192 && exact_gemms) ? early_sort_big_batch_mode : 1);
   if (mode != where) return false;
-  int n = 0, cols = -1;
+  int n = 0, cols = -1, bag = -1;
   for (const EmbShard& sh : shards) {
     if (sh.owner != rank) continue;
     if (cols >= 0 && sh.cols != cols) return false;
+    if (bag >= 0 && sh.e->inputs[0].adim[0] != bag) return false;      // one sort note per ctx: a model of mixed bag sizes sorts in front of its apply
     cols = sh.cols;
+    bag = sh.e->inputs[0].adim[0];
     n++;
   }
   for (const Embedding* e : embeddings)
@@ -288,7 +327,6 @@ void FFModel::embedding_group_update(ffh_stream s, ffh_ctx* on_ctx, bool advance
 // transposed all-to-all / the all-gather of a row-sharded table); a table has ONE holder per element, so nothing is all-reduced.
 void FFModel::embedding_dense_update() const {
   if (embeddings.empty()) return;
-  const int L = embeddings[0]->inputs[0].adim[0];
   const int aggr = (int)embeddings[0]->aggr;
   if (exchange) {
     if (!shards.empty() && config.comm.alltoall_f32(config.comm.user, gsend, fwd_recv_counts.data(), grecv, fwd_send_counts.data(), stream) != 0)
@@ -296,12 +334,13 @@ void FFModel::embedding_dense_update() const {
     for (const EmbShard& sh : shards) {
       if (sh.owner != rank) continue;
       const Embedding* e = sh.e;
+      const int L = e->inputs[0].adim[0];
       check(api->ffh_embedding_bwd_dense(ctx, (const int64_t*)e->inputs[0].impl->ptr, grecv + sh.off, e->weights[0].impl->grad, L, sh.cols,
                                          config.batchSize, e->num_entries, rank_width[rank], aggr, stream), e->name);
     }
     for (const Embedding* e : embeddings) {
       if (!e->row_sharded) continue;
-      const int D = e->out_channels;
+      const int D = e->out_channels, L = e->inputs[0].adim[0];
       if (config.comm.allgather_f32(config.comm.user, e->outputs[0].impl->grad, e->gfull, local_batch * D, stream) != 0)
         die("all-gather (row-sharded embedding backward) failed");
       check(api->ffh_embedding_bwd_dense(ctx, e->local_idx, e->gfull, e->weights[0].impl->grad, L, D, config.batchSize, e->rows_local + 1, D, aggr, stream), e->name);
