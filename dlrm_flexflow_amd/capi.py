@@ -1032,6 +1032,108 @@ def bags_api(lib: "FFHLib") -> BagsApi:
     return BagsApi(lib)
 
 
+# ---- the bags-update extension (include/ff_hip_bags_update.h): the fused table update with a bag size per table, one call -----------------
+BAGS_UPDATE_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_bags_update.h")
+BAGS_UPDATE_MAX_TABLES = MAX_TABLES
+
+
+class BagsUpdate(C.Structure):
+    """struct ffh_bags_update"""
+    _fields_ = [("tables", C.POINTER(EmbTable)), ("tables_bf16", C.POINTER(EmbTableBf16)), ("in_dims", C.POINTER(I)),
+                ("states", C.POINTER(EmbState)), ("ntables", I), ("out_dim", I), ("batch", L), ("aggr", I), ("lr", F),
+                ("opt", C.POINTER(SparseOpt)), ("rounding", C.POINTER(Bf16Rounding)), ("lr_block", P)]
+
+
+_SIGS_BAGS_UPDATE = {
+    "ffh_bags_update_abi_version": (I, []),
+    "ffh_bags_update_kernarg_bytes": (SZ, []),
+    "ffh_embedding_bwd_bags_workspace_bytes": (SZ, [C.POINTER(I), I, I, L]),
+    "ffh_embedding_bwd_fused_multi_bags": (I, [P, C.POINTER(BagsUpdate), P]),
+}
+
+
+def bags_update_header_symbols(header_path: str = BAGS_UPDATE_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_BAGS_UPDATE_API_LIST X-macro in include/ff_hip_bags_update.h."""
+    m = re.search(r"#define FFH_BAGS_UPDATE_API_LIST\(X\)(.*?)\n\n", open(header_path).read(), re.S)
+    if not m:
+        raise RuntimeError("FFH_BAGS_UPDATE_API_LIST not found in " + header_path)
+    return re.findall(r"X\((\w+)\)", m.group(1))
+
+
+def bags_update_header_abi_version(header_path: str = BAGS_UPDATE_HEADER_PATH) -> int:
+    """FFH_BAGS_UPDATE_ABI_VERSION of include/ff_hip_bags_update.h."""
+    m = re.search(r"#define\s+FFH_BAGS_UPDATE_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_BAGS_UPDATE_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
+class BagsUpdateApi:
+    """The bags-update extension (include/ff_hip_bags_update.h) of a loaded FFHLib; `bags_update_api(lib)` builds it or raises."""
+
+    def __init__(self, lib: "FFHLib"):
+        self.base = lib
+        for name, (res, args) in _SIGS_BAGS_UPDATE.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no bags-update extension ({name} missing; include/ff_hip_bags_update.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_bags_update_abi_version()
+        if got != bags_update_header_abi_version():
+            raise FFHError(f"{lib.path}: bags-update ABI version {got}, include/ff_hip_bags_update.h says {bags_update_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+    def kernarg_bytes(self) -> int:
+        return int(self.lib.ffh_bags_update_kernarg_bytes())
+
+    def workspace_bytes(self, in_dims, out_dim: int, batch: int, ntables: int | None = None) -> int:
+        """ffh_embedding_bwd_bags_workspace_bytes (host arithmetic); `in_dims`: a list of bag sizes, or None for a null pointer."""
+        arr = None if in_dims is None else BagsApi.in_dims(in_dims)
+        nt = len(in_dims) if ntables is None else ntables
+        return int(self.lib.ffh_embedding_bwd_bags_workspace_bytes(arr, int(nt), int(out_dim), int(batch)))
+
+    @staticmethod
+    def descriptor(*, in_dims, out_dim: int, batch: int, aggr: int, tables=None, tables_bf16=None, states=None, ntables: int | None = None,
+                   lr: float = 0.0, opt: SparseOpt | None = None, rounding: Bf16Rounding | None = None, lr_block=None) -> BagsUpdate:
+        """A struct ffh_bags_update.  `tables` from FFHLib.emb_tables, `tables_bf16` from Bf16Api.tables, `states` from FFHLib.emb_states,
+        `in_dims` a list of bag sizes (or None: a null pointer), `lr_block` a device buffer.  The descriptor keeps its arrays alive."""
+        u = BagsUpdate()
+        keep = [tables, tables_bf16, states, opt, rounding, lr_block]
+        if tables is not None:
+            u.tables = C.cast(tables, C.POINTER(EmbTable))
+        if tables_bf16 is not None:
+            u.tables_bf16 = C.cast(tables_bf16, C.POINTER(EmbTableBf16))
+        if in_dims is not None:
+            arr = BagsApi.in_dims(in_dims)
+            keep.append(arr)
+            u.in_dims = C.cast(arr, C.POINTER(I))
+        if states is not None:
+            u.states = C.cast(states, C.POINTER(EmbState))
+        u.ntables = int(len(in_dims) if ntables is None else ntables)
+        u.out_dim, u.batch, u.aggr, u.lr = int(out_dim), int(batch), int(aggr), float(lr)
+        if opt is not None:
+            u.opt = C.pointer(opt)
+        if rounding is not None:
+            u.rounding = C.pointer(rounding)
+        u.lr_block = ptr(lr_block)
+        u._keep = keep
+        return u
+
+    def rc(self, u: BagsUpdate | None, stream=None) -> int:
+        """ffh_embedding_bwd_fused_multi_bags, returning its status code."""
+        return self.lib.ffh_embedding_bwd_fused_multi_bags(self.ctx, C.byref(u) if u is not None else None, ptr(stream))
+
+    def call(self, u: BagsUpdate, stream=None):
+        self.base.check(self.rc(u, stream), "ffh_embedding_bwd_fused_multi_bags")
+
+
+def bags_update_api(lib: "FFHLib") -> BagsUpdateApi:
+    """The ragged-update entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
+    return BagsUpdateApi(lib)
+
+
 _hip_singleton: FFHLib | None = None
 
 

@@ -16,11 +16,15 @@
 //     read-modified-written exactly once.
 // This file: the gather, the dense backward, the sort launches, validation, the workspace layout and every entry point.  The sort
 // kernels are emb_sort.h; the apply phase's kernels (emb_reduce.h) and the row rules (emb_row_rules.h) are compiled per weight type in
-// embedding_update_f32.hip / embedding_update_bf16.hip and reached through emb_update_launch_f32 / _bf16.
+// embedding_update_f32.hip / embedding_update_bf16.hip and reached through emb_update_launch_f32 / _bf16.  The update of tables with a bag
+// size per table (include/ff_hip_bags_update.h): the entry and its layout are here, its kernels in emb_bags_update.h, compiled in
+// embedding_update_bags_f32.hip / _bf16.hip.
 #include "emb_reduce.h"
 #include "fold_sum.h"
 #include "lr_state.h"
 #include "../../include/ff_hip_bags.h"
+#include "../../include/ff_hip_bags_update.h"
+#include "emb_bags_update.h"
 
 #include <type_traits>
 
@@ -600,12 +604,11 @@ static void launch_sort_passes(SortArgs& sa, uint2* const kbuf[2], int passes, i
   }
 }
 
-static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L, int D, int64_t batch,
-                          int aggr, float lr, ffh_stream s, const bool do_sort, const bool do_apply,
-                          const ffh_sparse_opt* opt = nullptr, const ffh_emb_state* states = nullptr, const Bf16Cfg* b16 = nullptr,
-                          const ffh_lr_state* lr_block = nullptr) {
-  int rc = validate_tables(c, tables, nt, L, D, batch, aggr, "embedding_bwd_sgd_fused");
-  if (rc) return rc;
+// The row rule of an update call: its parameters (OptP), its kind and the argument checks that go with them.  Shared by the uniform entries
+// (emb_bwd_phases) and the ragged one (emb_bwd_bags).
+struct UpdatePlan { OptP op; int kind; RowRule rule; bool v4; int64_t maxR; };
+static int emb_update_rule(ffh_ctx* c, int nt, int D, int64_t batch, float lr, const bool do_apply, const ffh_sparse_opt* opt, const ffh_emb_state* states,
+                           const Bf16Cfg* b16, const ffh_lr_state* lr_block, UpdatePlan* plan) {
   OptP op{};
   op.lr = lr;
   if (b16 && do_apply) {
@@ -636,9 +639,12 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
       if (kind == FFH_SPARSE_OPT_ADAM && !states[i].s1) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_opt: optimizer state (s1) missing");
     }
   }
-  if (nt == 0 || batch == 0) return FFH_OK;
-  const int64_t N = batch * L;
-  if (N >= (1LL << 31)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_sgd_fused: batch*in_dim >= 2^31");
+  plan->op = op; plan->kind = kind; plan->rule = rule;
+  return FFH_OK;
+}
+// ... and what depends on the tables: the largest row count and whether every row and state row takes the 16-byte form
+static int emb_update_form(ffh_ctx* c, const ffh_emb_table* tables, int nt, int D, const ffh_emb_state* states, UpdatePlan* plan) {
+  const int kind = plan->kind;
   int64_t maxR = 1;
   for (int i = 0; i < nt; i++) maxR = tables[i].num_entries > maxR ? tables[i].num_entries : maxR;
   if (maxR > (1LL << 32)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_sgd_fused: num_entries > 2^32");
@@ -649,6 +655,29 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   if ((nvec + 63) / 64 > kMaxChunks * 64) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_sgd_fused: out_dim too large");
   if (kind == FFH_SPARSE_OPT_ROWWISE_ADAGRAD && (nvec + 63) / 64 > kMaxChunks)      // (apply_row_rowwise keeps the row in registers)
     return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_opt: FFH_SPARSE_OPT_ROWWISE_ADAGRAD takes out_dim <= 1024 (16-byte form) / 256 (include/ff_hip_rowwise.h)");
+  plan->v4 = v4; plan->maxR = maxR;
+  return FFH_OK;
+}
+
+static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L, int D, int64_t batch,
+                          int aggr, float lr, ffh_stream s, const bool do_sort, const bool do_apply,
+                          const ffh_sparse_opt* opt = nullptr, const ffh_emb_state* states = nullptr, const Bf16Cfg* b16 = nullptr,
+                          const ffh_lr_state* lr_block = nullptr) {
+  int rc = validate_tables(c, tables, nt, L, D, batch, aggr, "embedding_bwd_sgd_fused");
+  if (rc) return rc;
+  UpdatePlan plan;
+  rc = emb_update_rule(c, nt, D, batch, lr, do_apply, opt, states, b16, lr_block, &plan);
+  if (rc) return rc;
+  if (nt == 0 || batch == 0) return FFH_OK;
+  const int64_t N = batch * L;
+  if (N >= (1LL << 31)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_sgd_fused: batch*in_dim >= 2^31");
+  rc = emb_update_form(c, tables, nt, D, states, &plan);
+  if (rc) return rc;
+  const OptP& op = plan.op;
+  const int kind = plan.kind;
+  const RowRule rule = plan.rule;
+  const bool v4 = plan.v4;
+  const int64_t maxR = plan.maxR;
   const BwdLayout lay = bwd_layout(nt, L, D, batch);
   if (!c->ws || c->ws_bytes < lay.total) return ffh_fail(c, FFH_ERR_WORKSPACE, "embedding_bwd_sgd_fused: workspace too small (ffh_embedding_bwd_workspace_bytes)");
   char* ws = (char*)c->ws;
@@ -969,6 +998,192 @@ int ffh_embedding_fwd_multi_bags_bf16(ffh_ctx* c, const ffh_emb_table_bf16* tabl
   const int rc = bf16_tables(c, tables, nt, t, nullptr);
   if (rc) return rc;
   return emb_fwd_bags_launch<uint16_t>(c, t, in_dims, nt, D, batch, aggr, s);
+}
+
+}  // extern "C"
+// ---------------------------------------------------------------------------
+// include/ff_hip_bags_update.h: the fused update with a bag size per table.  One call, the kernels of emb_bags_update.h.
+// ---------------------------------------------------------------------------
+namespace {
+
+// The workspace: bwd_layout's arrays with every table's share sized by its own N_t = batch * L_t (with equal bag sizes: bwd_layout's bytes).
+// `bstart` keeps the place of the bucket form's array, which no ragged kernel uses yet.
+struct BagsLayout {
+  size_t kp_a, kp_b, hist, partial, meta, partial1, meta1, arrive, bstart, total;
+  BagsGeo g;           // (sort_sh and red_sh set: the tiles the call runs with)
+  BagsAt tot;          // totals over the tables; tot.local = reduce tiles
+  int64_t sort_tiles, maxN;
+  int E;
+};
+
+inline int log2_of(int v) { int s = 0; while ((1 << s) < v) s++; return s; }
+
+// in_dims checked by the caller: 1 .. kBagMaxL, batch * in_dims[i] < 2^31
+inline BagsLayout bags_layout(const int* in_dims, int nt, int D, int64_t batch) {
+  BagsLayout l;
+  memset(&l, 0, sizeof l);
+  int64_t total = 0, maxN = 0;
+  for (int i = 0; i < nt; i++) {
+    l.g.L[i] = (uint16_t)in_dims[i];
+    const int64_t N = batch * in_dims[i];
+    total += N;
+    maxN = N > maxN ? N : maxN;
+  }
+  l.g.batch = batch; l.g.nt = nt;
+  l.maxN = maxN;
+  // sort_per_thread / reduce_tile on the call's lookups: enough workgroups to cover the chip, tiles as large as that allows
+  int e = 1;
+  while (e * 2 <= total / (512LL * kSortThreads) && e < kSortMaxPerThread) e *= 2;
+  while ((maxN + (int64_t)kSortThreads * e - 1) / ((int64_t)kSortThreads * e) > 32 && e < kSortMaxPerThread) e *= 2;
+  l.E = e;
+  l.g.sort_sh = log2_of(kSortThreads * e);
+  int t = 128;
+  while (t * 2 <= total / 1024 && t < kRedTile) t *= 2;
+  l.g.red_sh = log2_of(t);
+  bags_locate(l.g, l.g.red_sh, INT64_MAX, &l.tot);
+  l.sort_tiles = l.tot.sblk0;
+  const size_t arr = align_up((size_t)l.tot.key0 * sizeof(uint2), 256);
+  size_t o = 0;
+  l.kp_a = o; o += arr;
+  l.kp_b = o; o += arr;
+  l.hist = o; o += align_up((size_t)l.tot.sblk0 * kMaxRadix * sizeof(uint32_t), 256);
+  l.partial = o; o += align_up(2 * (size_t)l.tot.ch0 * (size_t)D * sizeof(float), 256);
+  l.meta = o; o += align_up(2 * (size_t)l.tot.ch0 * sizeof(uint2), 256);
+  l.partial1 = o; o += align_up(2 * (size_t)l.tot.ch1 * (size_t)D * sizeof(float), 256);
+  l.meta1 = o; o += align_up(2 * (size_t)l.tot.ch1 * sizeof(uint2), 256);
+  l.arrive = o; o += align_up(((size_t)l.tot.ch1 + (size_t)nt) * sizeof(uint32_t), 256);
+  l.bstart = o; o += align_up((size_t)nt * (kMaxRadix + 1) * sizeof(uint32_t), 256);
+  l.total = o;
+  return l;
+}
+
+// FFH_OK, or the code the entry returns for these bag sizes (no message: the callers add their own)
+inline int bags_dims_check(const int* in_dims, int nt, int64_t batch) {
+  if (nt < 0 || nt > FFH_BAGS_UPDATE_MAX_TABLES || (nt > 0 && !in_dims) || batch < 0) return FFH_ERR_BAD_ARG;
+  for (int i = 0; i < nt; i++)
+    if (in_dims[i] < 1) return FFH_ERR_BAD_ARG;
+  for (int i = 0; i < nt; i++) {
+    if (in_dims[i] > kBagMaxL) return FFH_ERR_UNSUPPORTED;
+    if (batch * (int64_t)in_dims[i] >= (1LL << 31)) return FFH_ERR_UNSUPPORTED;
+  }
+  return FFH_OK;
+}
+
+typedef bool (*BagsUpdateOfFn)(const BagsUpdateLaunch&);
+constexpr BagsUpdateOfFn kBagsUpdateOf[2] = {emb_bags_update_launch_f32, emb_bags_update_launch_bf16};
+
+int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, int nt, int D, int64_t batch, int aggr, float lr, ffh_stream s,
+                 const ffh_sparse_opt* opt, const ffh_emb_state* states, const Bf16Cfg* b16, const ffh_lr_state* lr_block) {
+  int rc = bags_dims_check(in_dims, nt, batch);
+  if (rc == FFH_ERR_BAD_ARG) return ffh_fail(c, rc, "embedding_bwd_fused_multi_bags: ntables out of range, null in_dims or in_dims[i] < 1");
+  if (rc) return ffh_fail(c, rc, "embedding_bwd_fused_multi_bags: in_dims[i] > FFH_BAGS_MAX_IN_DIM (65535) or batch*in_dims[i] >= 2^31");
+  rc = validate_tables(c, tables, nt, 1, D, batch, aggr, "embedding_bwd_fused_multi_bags");
+  if (rc) return rc;
+  UpdatePlan plan;
+  rc = emb_update_rule(c, nt, D, batch, lr, true, opt, states, b16, lr_block, &plan);
+  if (rc) return rc;
+  if (nt == 0 || batch == 0) return FFH_OK;
+  rc = emb_update_form(c, tables, nt, D, states, &plan);
+  if (rc) return rc;
+  const int kind = plan.kind;
+  const BagsLayout lay = bags_layout(in_dims, nt, D, batch);
+  if (!c->ws || c->ws_bytes < lay.total) return ffh_fail(c, FFH_ERR_WORKSPACE, "embedding_bwd_fused_multi_bags: workspace too small (ffh_embedding_bwd_bags_workspace_bytes)");
+  char* ws = (char*)c->ws;
+  if (!aligned16(ws)) return ffh_fail(c, FFH_ERR_WORKSPACE, "embedding_bwd_fused_multi_bags: workspace must be 16-byte aligned");
+  if (c->emb_sorted_ws == c->ws) c->emb_sorted_ws = nullptr;      // (as the uniform fused call: a pending sort on this workspace is overwritten)
+
+  int bits = 1;
+  while (bits < 32 && ((plan.maxR - 1) >> bits) != 0) bits++;
+  const int passes = (bits + kMaxRadixBits - 1) / kMaxRadixBits;
+  const int rb = (bits + passes - 1) / passes;
+  const int avg = aggr == FFH_AGGR_MODE_AVG ? 1 : 0;
+
+  if (lay.maxN <= kSmallMax) {
+    snprintf(c->emb_route, sizeof c->emb_route, "bags:small");
+    BagsSmallArgs sm;
+    memset(&sm, 0, sizeof sm);
+    for (int i = 0; i < nt; i++) {
+      sm.t[i] = tables[i];
+      int tb = 1;
+      while (tb < 32 && ((tables[i].num_entries - 1) >> tb) != 0) tb++;
+      sm.npass[i] = (uint8_t)((tb + rb - 1) / rb);
+    }
+    sm.kp = (uint2*)(ws + lay.kp_a);
+    sm.partial0 = (float*)(ws + lay.partial); sm.meta0 = (uint2*)(ws + lay.meta);
+    sm.partial1 = (float*)(ws + lay.partial1); sm.meta1 = (uint2*)(ws + lay.meta1);
+    sm.rb = rb; sm.D = D; sm.avg = avg; sm.g = lay.g; sm.op = plan.op;
+    for (int i = 0; i < nt && kind != FFH_SPARSE_OPT_SGD; i++) { sm.s0[i] = states[i].s0; sm.s1[i] = states[i].s1; }
+    if (b16) set_bf16_keys(sm.b16, sm.b16a, *b16, states, nt, kind);
+    if (!kBagsUpdateOf[b16 ? 1 : 0](BagsUpdateLaunch{plan.rule, plan.v4, lr_block != nullptr, &sm, nullptr, dim3((unsigned)nt), as_stream(s)}))
+      return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags: no small-route kernel for this rule / weight type");
+    FFH_LAUNCH_CHECK(c, "emb_bags_small_kernel");
+    return FFH_OK;
+  }
+
+  snprintf(c->emb_route, sizeof c->emb_route, "bags:lsd:passes=%d", passes);
+  BagsSortArgs sa;
+  memset(&sa, 0, sizeof sa);
+  BagsRedArgs ra;
+  memset(&ra, 0, sizeof ra);
+  for (int i = 0; i < nt; i++) {
+    sa.idx[i] = tables[i].idx;
+    int tb = 1;
+    while (tb < 32 && ((tables[i].num_entries - 1) >> tb) != 0) tb++;
+    const int np = (tb + rb - 1) / rb;
+    sa.npass[i] = (uint8_t)np;
+    ra.parity[i] = (uint8_t)(np & 1);
+    ra.t[i] = tables[i];
+  }
+  sa.hist = (uint32_t*)(ws + lay.hist);
+  sa.bits = rb; sa.g = lay.g;
+  sa.clear[0] = (uint32_t*)(ws + lay.meta1); sa.nclear[0] = (int)(4 * lay.tot.ch1);      // uint2 slots, two per 1024-block
+  sa.clear[1] = (uint32_t*)(ws + lay.arrive); sa.nclear[1] = (int)(lay.tot.ch1 + nt);
+  uint2* kbuf[2] = {(uint2*)(ws + lay.kp_a), (uint2*)(ws + lay.kp_b)};
+  const dim3 sgrid((unsigned)lay.sort_tiles), rgrid((unsigned)lay.tot.local);      // the flat map: every table's own tiles
+  for (int p = 0; p < passes; p++) {
+    sa.shift = p * rb; sa.pass = p;
+    sa.src = kbuf[p & 1]; sa.dst = kbuf[(p + 1) & 1];
+    if (!emb_bags_sort_pass(sa, p == 0, lay.E, sgrid, as_stream(s))) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags: no sort kernel");
+  }
+  FFH_LAUNCH_CHECK(c, "bags radix sort");
+
+  ra.kp[0] = kbuf[0]; ra.kp[1] = kbuf[1];
+  ra.partial = (float*)(ws + lay.partial); ra.meta = (uint2*)(ws + lay.meta);
+  ra.partial1 = (float*)(ws + lay.partial1); ra.meta1 = (uint2*)(ws + lay.meta1);
+  ra.arrive = (uint32_t*)(ws + lay.arrive);
+  ra.D = D; ra.avg = avg; ra.g = lay.g; ra.op = plan.op;
+  for (int i = 0; i < nt && kind != FFH_SPARSE_OPT_SGD; i++) { ra.s0[i] = states[i].s0; ra.s1[i] = states[i].s1; }
+  if (b16) set_bf16_keys(ra.b16, ra.b16a, *b16, states, nt, kind);
+  if (!kBagsUpdateOf[b16 ? 1 : 0](BagsUpdateLaunch{plan.rule, plan.v4, lr_block != nullptr, nullptr, &ra, rgrid, as_stream(s)}))
+    return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags: no reduce kernel for this rule / weight type");
+  FFH_LAUNCH_CHECK(c, "emb_bags_reduce/fold");
+  return FFH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ffh_bags_update_abi_version(void) { return FFH_BAGS_UPDATE_ABI_VERSION; }
+size_t ffh_bags_update_kernarg_bytes(void) { return kBagsKernargBytes; }
+
+size_t ffh_embedding_bwd_bags_workspace_bytes(const int* in_dims, int nt, int D, int64_t batch) {
+  if (nt <= 0 || D <= 0 || batch <= 0 || bags_dims_check(in_dims, nt, batch) != FFH_OK) return 0;
+  return bags_layout(in_dims, nt, D, batch).total;
+}
+
+int ffh_embedding_bwd_fused_multi_bags(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) {
+  if (!u) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: null descriptor");
+  if ((u->tables != nullptr) == (u->tables_bf16 != nullptr)) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: exactly one of tables / tables_bf16");
+  if (u->lr_block && !u->opt) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: lr_block needs opt");
+  if (u->tables) return emb_bwd_bags(c, u->tables, u->in_dims, u->ntables, u->out_dim, u->batch, u->aggr, u->lr, s, u->opt, u->states, nullptr, u->lr_block);
+  ffh_emb_table t[FFH_MAX_TABLES];
+  Bf16Cfg cfg;
+  memset(&cfg, 0, sizeof cfg);
+  cfg.r = u->rounding;
+  const int rc = bf16_tables(c, u->tables_bf16, u->ntables, t, &cfg.keys);
+  if (rc) return rc;
+  return emb_bwd_bags(c, t, u->in_dims, u->ntables, u->out_dim, u->batch, u->aggr, u->lr, s, u->opt, u->states, &cfg, u->lr_block);
 }
 
 }  // extern "C"

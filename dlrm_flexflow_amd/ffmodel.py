@@ -87,6 +87,7 @@ def lib() -> C.CDLL:
         "flexflow_config_set_backend": (None, [H, C.c_char_p]), "flexflow_config_set_seed": (None, [H, C.c_uint64]),
         "flexflow_config_set_device": (None, [H, I]), "flexflow_config_set_enable_graph": (None, [H, B]),
         "flexflow_config_set_overlap_embedding": (None, [H, B]), "flexflow_config_set_dense_embedding_update": (None, [H, B]),
+        "flexflow_config_set_ragged_update": (None, [H, B]),
         "flexflow_config_set_embedding_dtype": (None, [H, I]), "flexflow_config_set_embedding_rounding": (None, [H, I]),
         "flexflow_config_set_lr_schedule": (None, [H, C.c_int64, C.c_int64, C.c_int64, I]),
         "flexflow_lr_schedule_value": (D, [C.c_int64, D, C.c_int64, C.c_int64, C.c_int64]),
@@ -485,7 +486,7 @@ class FFConfig:
 
     def set(self, seed=None, device=None, enable_graph=None, overlap_embedding=None, dense_embedding_update=None,
             embedding_dtype=None, embedding_rounding=None, lr_warmup_steps=None, lr_decay_start_step=None, lr_num_decay_steps=None,
-            device_lr=None, adagrad_eps=None, adagrad_initial_accumulator=None, adagrad_rowwise=None):
+            device_lr=None, adagrad_eps=None, adagrad_initial_accumulator=None, adagrad_rowwise=None, ragged_update=None):
         """embedding_dtype: "fp32" | "bf16"; embedding_rounding: "stochastic" | "nearest" (the --embedding-* flags).
         lr_*: the schedule of --lr-num-warmup-steps / --lr-decay-start-step / --lr-num-decay-steps; device_lr: True = --device-lr,
         False = --host-lr-schedule, None = compile() chooses the route.
@@ -509,6 +510,7 @@ class FFConfig:
         if enable_graph is not None: lib().flexflow_config_set_enable_graph(self.h, enable_graph)
         if overlap_embedding is not None: lib().flexflow_config_set_overlap_embedding(self.h, overlap_embedding)
         if dense_embedding_update is not None: lib().flexflow_config_set_dense_embedding_update(self.h, dense_embedding_update)
+        if ragged_update is not None: lib().flexflow_config_set_ragged_update(self.h, bool(ragged_update))      # (--ragged-update / --no-ragged-update)
         if embedding_dtype is not None:
             dt = {"fp32": DT_FLOAT, "bf16": DT_BF16}.get(embedding_dtype)
             if dt is None:

@@ -14,6 +14,7 @@
 #include "../../include/ff_hip_rowwise.h"
 #include "../../include/ff_hip_fold.h"
 #include "../../include/ff_hip_bags.h"
+#include "../../include/ff_hip_bags_update.h"
 
 // The optional bf16-table extension (include/ff_hip_bf16.h): all of its list or none of it.
 struct KernelApiBf16 {
@@ -85,6 +86,13 @@ struct KernelApiBags {
 #undef FFH_DECL
 };
 
+// The optional bags-update extension (include/ff_hip_bags_update.h: the fused table update with a bag size per table, one call).
+struct KernelApiBagsUpdate {
+#define FFH_DECL(name) decltype(&::name) name;
+  FFH_BAGS_UPDATE_API_LIST(FFH_DECL)
+#undef FFH_DECL
+};
+
 struct KernelApi {
 #define FFH_DECL(name) decltype(&::name) name;
   FFH_API_LIST(FFH_DECL)
@@ -99,6 +107,7 @@ struct KernelApi {
   const KernelApiRowwise* rowwise = nullptr; // likewise for include/ff_hip_rowwise.h
   const KernelApiFold* fold = nullptr;       // likewise for include/ff_hip_fold.h (absent: no table is folded, the step is the one of before)
   const KernelApiBags* bags = nullptr;       // likewise for include/ff_hip_bags.h (absent: a model of mixed bag sizes gathers once per bag size)
+  const KernelApiBagsUpdate* bags_update = nullptr;   // likewise for include/ff_hip_bags_update.h (absent: a model of mixed bag sizes updates once per bag size)
   void* handle;
   std::string path;
   bool overridden = false;      // chosen by --backend or $FFH_BACKEND_LIB rather than the product default: the driver says so on its THROUGHPUT line

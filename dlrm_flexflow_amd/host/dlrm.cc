@@ -500,6 +500,7 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
   }
   ff->compile(optimizer, (LossType)ffconfig.driver_loss, metrics);
   if (chatty && !dlrm.embedding_bag_sizes.empty()) printf("[DLRM] embedding gather: %s\n", ff->bag_gather_line().c_str());      // a per-table list: how the gather runs
+  if (chatty && ff->mixed_bags && ff->fused_embedding_update()) printf("[DLRM] embedding update: %s\n", ff->bag_update_line().c_str());      // ... and, where the sizes differ, the update
   if (const AdagradOptimizer* ag = dynamic_cast<const AdagradOptimizer*>(optimizer)) {
     // what --optimizer adagrad allocated on this rank: S beside every fp32 weight it updates, fp32 beside bf16 tables too (on fp32 tables it doubles their HBM)
     size_t bytes = ag->state_bytes;

@@ -145,6 +145,8 @@ class FFConfig {
                                // measured on the trace's first calls, one GPU (--adaptive-replay): on this runtime the replay of a two-stream step costs a
                                // small model more than its launches (Kaggle shape: 210 vs 170 us).  -1 = not given: the FFModel API replays (1), the DLRM
                                // driver's timed loop adapts (0)
+  bool ragged_update;          // the fused update of tables of differing bag sizes is one ragged call per group (include/ff_hip_bags_update.h; --ragged-update / --no-ragged-update,
+                               // the later one wins; off: one call per bag size)
   bool ragged_gather;          // tables of differing bag sizes are gathered in one launch per group (include/ff_hip_bags.h; A/B: --no-ragged-gather = one launch per bag size)
   bool fold_small_tables;      // small embedding tables folded out of the first top layer's forward GEMM (include/ff_hip_fold.h; A/B: --no-fold-small-tables)
   int64_t fold_max_rows;       // ... tables of at most this many rows (--fold-max-rows N)
@@ -724,6 +726,9 @@ class FFModel {
   mutable int64_t n_early_sorts = 0;          // sort-only launches issued behind the gather (tests: flexflow_model_get_counter "early_sorts")
   mutable int64_t n_ragged_gathers = 0;       // ffh_embedding_fwd_multi_bags[_bf16] launches (tests: flexflow_model_get_counter "ragged_gather_launches")
   bool mixed_bags = false;                    // the tables' bag sizes differ (allocate()): DESIGN section 19
+  mutable int64_t n_ragged_updates = 0;       // ffh_embedding_bwd_fused_multi_bags calls (tests: flexflow_model_get_counter "ragged_update_launches")
+  bool ragged_update_on() const;              // the tables' bag sizes differ and their fused update is the ragged call (the library has it, the flag allows it)
+  std::string bag_update_line() const;        // how a model of mixed bag sizes updates its tables, for the driver's transcript
   bool ragged_gather_on() const;              // ... and their gather is the one-launch ragged one (the library has it, no --no-ragged-gather)
   std::string bag_gather_line() const;        // how a model of mixed bag sizes gathers, for the driver's transcript
   bool fused_embedding_update() const;        // the tables are updated on the sorted segments (plain SGD, or any optimizer with --sparse-embedding-optimizer)

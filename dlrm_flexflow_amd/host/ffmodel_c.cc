@@ -37,6 +37,7 @@ void flexflow_config_set_device(flexflow_config_t h, int d) { C(h)->device = d; 
 void flexflow_config_set_enable_graph(flexflow_config_t h, bool v) { C(h)->enable_graph = v; }
 void flexflow_config_set_overlap_embedding(flexflow_config_t h, bool v) { C(h)->overlap_embedding = v; }
 void flexflow_config_set_dense_embedding_update(flexflow_config_t h, bool v) { C(h)->dense_embedding_update = v; }
+void flexflow_config_set_ragged_update(flexflow_config_t h, bool v) { C(h)->ragged_update = v; }
 void flexflow_config_set_embedding_dtype(flexflow_config_t h, int dt) {
   if (dt != DT_FLOAT && dt != DT_BF16) { fprintf(stderr, "FATAL: embedding data type %d: %d (fp32) or %d (bf16)\n", dt, (int)DT_FLOAT, (int)DT_BF16); abort(); }
   C(h)->embedding_dtype = (DataType)dt;
@@ -173,6 +174,7 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   if (n == "direct_allreduces") return M(m)->n_direct_allreduces;
   if (n == "bf16_updates") return (int64_t)M(m)->read_bf16_counter();
   if (n == "early_sorts") return M(m)->n_early_sorts;
+  if (n == "ragged_update_launches") return M(m)->n_ragged_updates;      // ffh_embedding_bwd_fused_multi_bags calls (mixed bag sizes; include/ff_hip_bags_update.h)
   if (n == "ragged_gather_launches") return M(m)->n_ragged_gathers;      // ffh_embedding_fwd_multi_bags[_bf16] launches (mixed bag sizes; include/ff_hip_bags.h)
   if (n == "lr_steps") return M(m)->lr_steps();
   if (n == "lr_route") return M(m)->lr_route;          // 0 off (the scalar launches of before), 1 host, 2 device

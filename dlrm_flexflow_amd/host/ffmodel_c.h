@@ -51,6 +51,8 @@ void flexflow_config_set_device(flexflow_config_t, int);
 void flexflow_config_set_enable_graph(flexflow_config_t, bool);
 void flexflow_config_set_overlap_embedding(flexflow_config_t, bool);
 void flexflow_config_set_dense_embedding_update(flexflow_config_t, bool);
+/* --ragged-update / --no-ragged-update: tables of differing bag sizes are updated in one ragged call per group (include/ff_hip_bags_update.h) */
+void flexflow_config_set_ragged_update(flexflow_config_t, bool);
 /* bf16 embedding tables (--embedding-dtype / --embedding-rounding): data_type 40 (DT_FLOAT, default) or 140 (DT_BF16);
  * mode 0 stochastic (default) or 1 nearest even (include/ffh_bf16.h).  Other values abort. */
 void flexflow_config_set_embedding_dtype(flexflow_config_t, int data_type);

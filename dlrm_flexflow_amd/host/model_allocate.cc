@@ -872,6 +872,20 @@ void FFModel::allocate() {
       if (sh.owner == rank) owned_by_bag[sh.e->inputs[0].adim[0]]++;
     for (const auto& kv : owned_by_bag)
       workspace_bytes = std::max(workspace_bytes, api->ffh_embedding_bwd_workspace_bytes(std::min(kv.second, FFH_MAX_TABLES), kv.first, D, config.batchSize) + 256);
+    // ... or once per group of mixed bag sizes (the ragged update, include/ff_hip_bags_update.h): a group's calls as launch_shard_groups cuts them.  The
+    // sizing above stays beside it: the roofline probe and --no-ragged-update run the calls per bag size
+    if (ragged_update_on()) {
+      std::map<std::pair<int, bool>, std::vector<int>> bags_of;
+      for (const EmbShard& sh : shards)
+        if (sh.owner == rank) bags_of[{sh.cols, sh.e->bf16_weights()}].push_back(sh.e->inputs[0].adim[0]);
+      for (const auto& kv : bags_of) {
+        const size_t per = kv.first.second ? bf16_tables_per_launch() : (size_t)FFH_MAX_TABLES;
+        for (size_t b = 0; b < kv.second.size(); b += per) {
+          const int n = (int)std::min(per, kv.second.size() - b);
+          workspace_bytes = std::max(workspace_bytes, api->bags_update->ffh_embedding_bwd_bags_workspace_bytes(kv.second.data() + b, n, kv.first.first, config.batchSize) + 256);
+        }
+      }
+    }
   }
   for (Embedding* e : embeddings)
     if (e->row_sharded) workspace_bytes = std::max(workspace_bytes, api->ffh_embedding_bwd_workspace_bytes(1, L, D, config.batchSize) + 256);

@@ -10,7 +10,8 @@
 // =============================================================================================
 // launches one batched kernel per distinct shard width (all table-wise tables share one; column blocks of
 // giant tables another) and, where the tables' bag sizes differ, per bag size (the gather: one ragged launch where the
-// library has it); FWD: gather, else fused backward + SGD
+// library has it; the fused update: one ragged call where the library has it and the flag allows it); FWD: gather, else fused
+// backward + SGD
 void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_ctx* cx, const std::vector<const int64_t*>* idx_override, bool all_tables) {
   const bool fwd = what == kGather;
   ffh_sparse_opt rule;
@@ -19,10 +20,11 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
   const ffh_lr_state* lrb = ff->lr_route == FFModel::kLrDevice ? ff->lr_block[1] : nullptr;
   const KernelApiLr* lra = ff->api->lr;
   const int aggr = (int)ff->embeddings[0]->aggr;
-  // by shard width, then storage (bf16 tables: include/ff_hip_bf16.h, keyed by global table index and global column), then bag size.  The update's
-  // entry points take one bag size per call, so its groups are always split by bag size; the gather of a model of mixed bag sizes keeps a group
-  // whole (key 0) where the library has the one-launch ragged gather (include/ff_hip_bags.h) and --no-ragged-gather is not given
-  const bool ragged = fwd && ff->ragged_gather_on();
+  // by shard width, then storage (bf16 tables: include/ff_hip_bf16.h, keyed by global table index and global column), then bag size.  The uniform
+  // update entries take one bag size per call, so their groups are split by bag size; a model of mixed bag sizes keeps a group whole (key 0) for the
+  // gather where the library has the one-launch ragged gather (include/ff_hip_bags.h) and --no-ragged-gather is not given, and for the fused update
+  // where it has the ragged update (include/ff_hip_bags_update.h) and --ragged-update allows it.  The sort-only / apply-only pair stays uniform.
+  const bool ragged = fwd ? ff->ragged_gather_on() : (what == kFusedUpdate && ff->ragged_update_on());
   struct Group { std::vector<ffh_emb_table> t; std::vector<ffh_emb_table_bf16> t16; std::vector<ffh_emb_state> st; std::vector<int> bag; };
   std::map<std::tuple<int, bool, int>, Group> groups;
   size_t owned_i = 0;
@@ -54,11 +56,20 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
   for (auto& kv : groups) {
     const int D = std::get<0>(kv.first);
     const Group& g = kv.second;
-    const int L = g.bag[0];
     // tables [b, b + n) of the group in one ragged launch: where their bag sizes differ (else the call stays the uniform one)
     auto differ = [&](size_t b, int n) {
       for (int i = 1; i < n; i++) if (g.bag[b + i] != g.bag[b]) return true;
       return false;
+    };
+    // the ragged fused update of tables [b, b + n): every rule and both rates through the one descriptor
+    auto ragged_update = [&](const ffh_emb_table* t32, const ffh_emb_table_bf16* t16, const ffh_emb_state* st, const ffh_bf16_rounding* rnd, size_t b, int n) {
+      ffh_bags_update u;
+      u.tables = t32; u.tables_bf16 = t16; u.in_dims = g.bag.data() + b; u.states = st;
+      u.ntables = n; u.out_dim = D; u.batch = B; u.aggr = aggr; u.lr = rule.lr;
+      u.opt = (ruled || lrb) ? &rule : nullptr;
+      u.rounding = rnd; u.lr_block = lrb;
+      ff->check(ff->api->bags_update->ffh_embedding_bwd_fused_multi_bags(cx, &u, s), "embedding_bwd_fused_multi_bags");
+      ff->n_ragged_updates++;
     };
     if (std::get<1>(kv.first)) {
       const KernelApiBf16* b16 = ff->api->bf16;
@@ -68,6 +79,7 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
         const int n = (int)std::min<size_t>(per, g.t16.size() - b);
         const ffh_emb_table_bf16* tb = g.t16.data() + b;
         const ffh_emb_state* st = g.st.data() + b;
+        const int L = g.bag[b];       // a uniform call's bag size is its own tables' (a whole group of mixed sizes holds several)
         switch (what) {
           case kGather:
             if (ragged && differ(b, n)) {
@@ -76,7 +88,8 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
             } else ff->check(b16->ffh_embedding_fwd_multi_bf16(cx, tb, n, g.bag[b], D, B, aggr, s), "embedding_fwd_multi_bf16");
             break;
           case kFusedUpdate:
-            if (lrb) ff->check(lra->ffh_embedding_bwd_opt_fused_multi_bf16_lr(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, lrb, s), "embedding_bwd_opt_fused_multi_bf16_lr");
+            if (ragged && differ(b, n)) ragged_update(nullptr, tb, st, &rnd, b, n);
+            else if (lrb) ff->check(lra->ffh_embedding_bwd_opt_fused_multi_bf16_lr(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, lrb, s), "embedding_bwd_opt_fused_multi_bf16_lr");
             else if (ruled) ff->check(b16->ffh_embedding_bwd_opt_fused_multi_bf16(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, s), "embedding_bwd_opt_fused_multi_bf16");
             else ff->check(b16->ffh_embedding_bwd_sgd_fused_multi_bf16(cx, tb, n, L, D, B, aggr, rule.lr, &rnd, s), "embedding_bwd_sgd_fused_multi_bf16");
             break;
@@ -94,6 +107,7 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
     const std::vector<ffh_emb_state>& sts = g.st;
     for (size_t b = 0; b < tabs.size(); b += FFH_MAX_TABLES) {
       const int n = (int)std::min<size_t>(FFH_MAX_TABLES, tabs.size() - b);
+      const int L = g.bag[b];
       switch (what) {
         case kGather:
           if (ragged && differ(b, n)) {
@@ -102,7 +116,8 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
           } else ff->check(ff->api->ffh_embedding_fwd_multi(cx, tabs.data() + b, n, g.bag[b], D, B, aggr, s), "embedding_fwd_multi");
           break;
         case kFusedUpdate:
-          if (lrb) ff->check(lra->ffh_embedding_bwd_opt_fused_multi_lr(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, lrb, s), "embedding_bwd_opt_fused_multi_lr");
+          if (ragged && differ(b, n)) ragged_update(tabs.data() + b, nullptr, sts.data() + b, nullptr, b, n);
+          else if (lrb) ff->check(lra->ffh_embedding_bwd_opt_fused_multi_lr(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, lrb, s), "embedding_bwd_opt_fused_multi_lr");
           else if (ruled) ff->check(ff->api->ffh_embedding_bwd_opt_fused_multi(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, s), "embedding_bwd_opt_fused_multi");
           else ff->check(ff->api->ffh_embedding_bwd_sgd_fused_multi(cx, tabs.data() + b, n, L, D, B, aggr, rule.lr, s), "embedding_bwd_sgd_fused_multi");
           break;
@@ -127,6 +142,27 @@ std::string FFModel::bag_gather_line() const {
   if (!mixed_bags) { snprintf(buf, sizeof buf, "one bag size, %zu launch%s", keys.size(), keys.size() == 1 ? "" : "es"); return buf; }
   if (ragged_gather_on()) snprintf(buf, sizeof buf, "ragged, one launch per group (%zu launch%s)", keys.size(), keys.size() == 1 ? "" : "es");
   else snprintf(buf, sizeof buf, "per bag size, %zu launches%s", keys.size(), !api->bags ? " (the kernel library has no ragged gather)" : " (--no-ragged-gather)");
+  return buf;
+}
+
+bool FFModel::ragged_update_on() const { return mixed_bags && config.ragged_update && api->bags_update; }
+// how a model of mixed bag sizes updates its tables (the driver prints it): the calls of one fused update over this rank's tables
+std::string FFModel::bag_update_line() const {
+  const bool on = ragged_update_on();
+  std::map<std::tuple<int, bool, int>, std::vector<int>> keys;      // the groups of launch_shard_groups, each with its tables' bag sizes in order
+  for (const EmbShard& sh : shards)
+    if (sh.owner == rank) keys[std::make_tuple(sh.cols, sh.e->bf16_weights(), on ? 0 : sh.e->inputs[0].adim[0])].push_back(sh.e->inputs[0].adim[0]);
+  size_t calls = 0, uniform = 0;      // (a chunk of a whole group whose bag sizes are equal makes the uniform call)
+  for (const auto& kv : keys) {
+    const std::vector<int>& bag = kv.second;
+    const size_t per = std::get<1>(kv.first) ? bf16_tables_per_launch() : (size_t)FFH_MAX_TABLES;
+    for (size_t b = 0; b < bag.size(); b += per, calls++)
+      uniform += std::all_of(bag.begin() + b, bag.begin() + std::min(bag.size(), b + per), [&](int L) { return L == bag[b]; });
+  }
+  char buf[160];
+  if (on && uniform) snprintf(buf, sizeof buf, "ragged, %zu call%s per step (%zu of them over one bag size)", calls, calls == 1 ? "" : "s", uniform);
+  else if (on) snprintf(buf, sizeof buf, "ragged, %zu call%s per step", calls, calls == 1 ? "" : "s");
+  else snprintf(buf, sizeof buf, "per bag size, %zu call%s per step%s", calls, calls == 1 ? "" : "s", !api->bags_update ? " (the kernel library has no ragged update)" : " (--no-ragged-update)");
   return buf;
 }
 

@@ -41,6 +41,7 @@ FFConfig::FFConfig() {
   fuse_pair = true;
   mlp_chain = true;
   ragged_gather = true;
+  ragged_update = true;
   fold_small_tables = true;
   fold_max_rows = 7420;      // the measured threshold (2208 and 7420 tried)
   fold_dw = true;
@@ -169,6 +170,8 @@ void FFConfig::parse_args(char** argv, int argc) {
     if (is("--no-fused-pair")) { fuse_pair = false; continue; }
     if (is("--no-mlp-chain")) { mlp_chain = false; continue; }
     if (is("--no-ragged-gather")) { ragged_gather = false; continue; }
+    if (is("--ragged-update")) { ragged_update = true; continue; }
+    if (is("--no-ragged-update")) { ragged_update = false; continue; }
     if (is("--no-fold-small-tables")) { fold_small_tables = false; continue; }
     if (is("--no-fold-dw")) { fold_dw = false; continue; }
     if (is("--no-fold-dx")) { fold_dx = false; continue; }

@@ -17,8 +17,8 @@
  * captured graph replays the launch without reading anything the host rewrites).  A null in_dims with ntables > 0 and ntables >
  * FFH_MAX_TABLES return FFH_ERR_BAD_ARG.  Nothing is launched on an error.  Row ids are not checked (as in ffh_embedding_fwd_multi).
  *
- * The update has no ragged form: a table's gradient touches at most batch * in_dims[i] rows whatever the other tables' bag sizes are, and the
- * sort and the segmented reduction of ffh_embedding_bwd_* are laid out on one N = batch * in_dim per call.  Call them once per bag size.
+ * The update's ragged form is an extension of its own, include/ff_hip_bags_update.h (ffh_embedding_bwd_fused_multi_bags): the sort and the
+ * segmented reduction of ffh_embedding_bwd_* are laid out on one N = batch * in_dim per call.  Without that extension, call them once per bag size.
  */
 #ifndef FF_HIP_BAGS_H_
 #define FF_HIP_BAGS_H_
