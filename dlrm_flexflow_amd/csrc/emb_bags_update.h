@@ -95,7 +95,7 @@ struct BagsSmallArgs {
   ffh_emb_table t[FFH_MAX_TABLES];
   uint8_t   npass[FFH_MAX_TABLES];
   uint2*    kp;                         // [sum N_t] sorted {row id, position}   (workspace)
-  float*    partial0; uint2* meta0;
+  float*    partial;  uint2* meta;
   float*    partial1; uint2* meta1;
   int       rb, D, avg, pad_;
   BagsGeo   g;
@@ -376,8 +376,8 @@ __global__ __launch_bounds__(kSmallThreads) void emb_bags_small_kernel(const Bag
   __syncthreads();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 
-  float* p0 = a.partial0 + at.ch0 * 2 * a.D;
-  uint2* m0 = a.meta0 + at.ch0 * 2;
+  float* p0 = a.partial + at.ch0 * 2 * a.D;
+  uint2* m0 = a.meta + at.ch0 * 2;
   const int team = threadIdx.x / kRedThreads, ttid = threadIdx.x % kRedThreads;
   const int ntiles = (int)((N + tile - 1) / tile);
   for (int t0 = 0; t0 < ntiles; t0 += kSmallRedParts) {

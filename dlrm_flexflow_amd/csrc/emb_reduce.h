@@ -54,7 +54,7 @@ struct SmallArgs {
   ffh_emb_table t[FFH_MAX_TABLES];
   uint8_t   npass[FFH_MAX_TABLES];
   uint2*    kp;        // [nt][N] sorted {row id, position}   (workspace)
-  float*    partial0;  uint2* meta0;   // level-0 slots [nt][2*nch0]
+  float*    partial;   uint2* meta;    // level-0 slots [nt][2*nch0]   (the slots' names are RedArgs': the host fills both alike)
   float*    partial1;  uint2* meta1;   // level-1 slots [nt][2*nch1]
   int64_t   N;
   int nch0, nch1, rb, L, D, avg;
@@ -954,8 +954,8 @@ __global__ __launch_bounds__(kSmallThreads) void emb_sgd_small_kernel(const Smal
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 
   // reduce: the 1024 threads act as four 256-thread teams, one tile of a.tile sorted entries each
-  float* p0 = a.partial0 + (int64_t)tix * 2 * a.nch0 * a.D;
-  uint2* m0 = a.meta0 + (int64_t)tix * 2 * a.nch0;
+  float* p0 = a.partial + (int64_t)tix * 2 * a.nch0 * a.D;
+  uint2* m0 = a.meta + (int64_t)tix * 2 * a.nch0;
   const int team = threadIdx.x / kRedThreads, ttid = threadIdx.x % kRedThreads;
   const int ntiles = (int)((N + a.tile - 1) / a.tile);
   for (int t0 = 0; t0 < ntiles; t0 += kSmallRedParts) {

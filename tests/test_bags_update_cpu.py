@@ -79,6 +79,27 @@ def test_workspace_grows_with_the_lookups_not_with_the_largest_bag():
     assert _bytes(lib, [100, 1, 1], D, batch) == mixed == _bytes(lib, [1, 1, 100], D, batch)
 
 
+# Workspace bytes as commit 8ec5655 ("Update tables of mixed bag sizes in one ragged sort-and-apply call") answers them, before the two layouts
+# were given one layout function and one set of tile choices.  Callers size their buffers once and keep them: the sizes do not move.
+_UNIFORM_BYTES = [      # ((nt, L, D, batch), bytes)
+    ((1, 1, 8, 64), 6656), ((3, 7, 16, 500), 310528), ((26, 1, 128, 8192), 12304896), ((5, 100, 6, 6000), 57210880),
+    ((26, 1, 128, 32768), 43946752),
+    ((1, 1, 4, 2048), 55296), ((1, 1, 4, 2049), 58368),      # the two sides of the small route's 2048-lookup limit
+    ((1, 1, 16, 300000), 6497280),                           # at most 32 sort tiles per table
+    ((64, 1, 4, 1), 270080),
+]
+_MLPERF_BAGS = [3, 2, 1, 2, 6, 1, 1, 1, 1, 7, 3, 8, 1, 6, 9, 5, 1, 1, 1, 12, 100, 27, 10, 3, 1, 1]      # tools/bags_bench.py
+_RAGGED_BYTES = [       # (bag sizes, D, batch, bytes)
+    ([1, 100, 1], 128, 8192, 42219776), (_MLPERF_BAGS, 128, 8192, 88619008), ([7] * 3, 128, 8192, 8697600), ([1, 2], 3, 5, 10240),
+]
+
+
+def test_workspace_sizes_are_pinned():
+    lib = _lib()
+    assert [lib.ffh_embedding_bwd_workspace_bytes(*shape) for shape, _ in _UNIFORM_BYTES] == [n for _, n in _UNIFORM_BYTES]
+    assert [_bytes(lib, bags, D, batch) for bags, D, batch, _ in _RAGGED_BYTES] == [n for _, _, _, n in _RAGGED_BYTES]
+
+
 def test_workspace_of_bad_arguments_is_zero():
     lib = _lib()
     assert _bytes(lib, [1, 0, 3], 8, 64) == 0 and _bytes(lib, [1, capi.BAGS_MAX_IN_DIM + 1], 8, 64) == 0
