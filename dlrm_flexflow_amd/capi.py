@@ -1134,6 +1134,70 @@ def bags_update_api(lib: "FFHLib") -> BagsUpdateApi:
     return BagsUpdateApi(lib)
 
 
+# ---- the bags-sort extension (include/ff_hip_bags_sort.h): the ragged update in two calls, sort (ids only) then apply ----------------------
+BAGS_SORT_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_bags_sort.h")
+
+_SIGS_BAGS_SORT = {
+    "ffh_bags_sort_abi_version": (I, []),
+    "ffh_embedding_bwd_sort_multi_bags": (I, [P, C.POINTER(BagsUpdate), P]),
+    "ffh_embedding_bwd_apply_multi_bags": (I, [P, C.POINTER(BagsUpdate), P]),
+}
+
+
+def bags_sort_header_symbols(header_path: str = BAGS_SORT_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_BAGS_SORT_API_LIST X-macro in include/ff_hip_bags_sort.h."""
+    m = re.search(r"#define FFH_BAGS_SORT_API_LIST\(X\)(.*?)\n\n", open(header_path).read(), re.S)
+    if not m:
+        raise RuntimeError("FFH_BAGS_SORT_API_LIST not found in " + header_path)
+    return re.findall(r"X\((\w+)\)", m.group(1))
+
+
+def bags_sort_header_abi_version(header_path: str = BAGS_SORT_HEADER_PATH) -> int:
+    """FFH_BAGS_SORT_ABI_VERSION of include/ff_hip_bags_sort.h."""
+    m = re.search(r"#define\s+FFH_BAGS_SORT_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_BAGS_SORT_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
+class BagsSortApi:
+    """The bags-sort extension (include/ff_hip_bags_sort.h) of a loaded FFHLib; `bags_sort_api(lib)` builds it or raises.  Both calls take
+    the descriptor of the fused ragged update (BagsUpdateApi.descriptor)."""
+
+    def __init__(self, lib: "FFHLib"):
+        self.base = lib
+        for name, (res, args) in _SIGS_BAGS_SORT.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no bags-sort extension ({name} missing; include/ff_hip_bags_sort.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_bags_sort_abi_version()
+        if got != bags_sort_header_abi_version():
+            raise FFHError(f"{lib.path}: bags-sort ABI version {got}, include/ff_hip_bags_sort.h says {bags_sort_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+    def sort_rc(self, u: BagsUpdate | None, stream=None) -> int:
+        """ffh_embedding_bwd_sort_multi_bags, returning its status code."""
+        return self.lib.ffh_embedding_bwd_sort_multi_bags(self.ctx, C.byref(u) if u is not None else None, ptr(stream))
+
+    def apply_rc(self, u: BagsUpdate | None, stream=None) -> int:
+        """ffh_embedding_bwd_apply_multi_bags, returning its status code."""
+        return self.lib.ffh_embedding_bwd_apply_multi_bags(self.ctx, C.byref(u) if u is not None else None, ptr(stream))
+
+    def sort(self, u: BagsUpdate, stream=None):
+        self.base.check(self.sort_rc(u, stream), "ffh_embedding_bwd_sort_multi_bags")
+
+    def apply(self, u: BagsUpdate, stream=None):
+        self.base.check(self.apply_rc(u, stream), "ffh_embedding_bwd_apply_multi_bags")
+
+
+def bags_sort_api(lib: "FFHLib") -> BagsSortApi:
+    """The ragged sort / apply entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
+    return BagsSortApi(lib)
+
+
 _hip_singleton: FFHLib | None = None
 
 

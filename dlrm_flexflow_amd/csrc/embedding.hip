@@ -8,7 +8,7 @@
 //   * the plan of a call, for both updates: radix_plan, fill_passes, sort_per_thread, reduce_tile,
 //     ws_layout (bwd_layout, bags_layout), UpdatePlan, set_rule_args, set_ws_slots;
 //   * emb_bwd_phases: the update with one bag size; emb_sort_full: its sort alone (fold_sum.hip);
-//   * emb_bwd_bags: the update with a bag size per table (include/ff_hip_bags_update.h);
+//   * emb_bwd_bags: the update with a bag size per table (include/ff_hip_bags_update.h), whole or in its two phases (include/ff_hip_bags_sort.h);
 //   * emb_bwd_dense_kernel, emb_localize_kernel, the bf16 init / counter kernels; every entry.
 // What is where:
 //   * the gather: embedding_fwd.hip; checks on a table list shared with it: emb_tables.h;
@@ -20,6 +20,7 @@
 #include "fold_sum.h"
 #include "lr_state.h"
 #include "../../include/ff_hip_bags_update.h"
+#include "../../include/ff_hip_bags_sort.h"
 #include "emb_bags_update.h"
 
 namespace {
@@ -287,6 +288,11 @@ static void set_ws_slots(Args& a, char* ws, const WsLayout& lay) {
   a.partial1 = (float*)(ws + lay.partial1); a.meta1 = (uint2*)(ws + lay.meta1);
 }
 
+// A call that overwrites the ctx's workspace spoils the ragged sort waiting there (include/ff_hip_bags_sort.h: the note of emb_bwd_bags)
+static inline void spoil_bags_sort_note(ffh_ctx* c) {
+  if (c->emb_bags_sorted.ws == c->ws) c->emb_bags_sorted.ws = nullptr;
+}
+
 // The sort of a call with one bag size, on its workspace.  Set for the LSD form (no bucket digit), every table running its own passes,
 // and to clear the apply phase's level-1 slots and arrival counters in pass 0.
 struct SortSetup { SortArgs sa; uint2* kbuf[2]; dim3 grid; };
@@ -348,6 +354,7 @@ static int emb_bwd_phases(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L
   // sort notes (workspace, shape) in the ctx, the apply requires and clears that note; the fused call needs no note but spoils one
   // that sits on the workspace it overwrites.
   const int64_t sig[4] = {nt, L, D, batch};
+  if (do_sort) spoil_bags_sort_note(c);      // (a ragged note never satisfies a uniform apply, and the reverse: emb_bwd_bags)
   if (do_sort && do_apply) {
     if (c->emb_sorted_ws == c->ws) c->emb_sorted_ws = nullptr;
   } else if (do_sort) {
@@ -486,6 +493,7 @@ int ffh_emb::emb_sort_full(ffh_ctx* c, const ffh_emb_table* tables, int nt, int 
   const BwdLayout lay = bwd_layout(nt, L, D, batch);
   char* ws = (char*)c->ws;
   if (c->emb_sorted_ws == c->ws) c->emb_sorted_ws = nullptr;
+  spoil_bags_sort_note(c);
   const int64_t maxR = max_rows(tables, nt);
   if (maxR > (1LL << 32)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_segment_sum: num_entries > 2^32");
   const RadixPlan rp = radix_plan(maxR);
@@ -608,29 +616,64 @@ inline int bags_dims_check(const int* in_dims, int nt, int64_t batch) {
 typedef bool (*BagsUpdateOfFn)(const BagsUpdateLaunch&);
 constexpr BagsUpdateOfFn kBagsUpdateOf[2] = {emb_bags_update_launch_f32, emb_bags_update_launch_bf16};
 
+// the sort phase alone reads idx and num_entries only (include/ff_hip_bags_sort.h): validate_tables without the weight / io / ld checks
+inline int validate_sort_tables(ffh_ctx* c, const ffh_emb_table* t, int nt, int D, int64_t batch) {
+  if (D <= 0) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding: bad dims");
+  for (int i = 0; i < nt; i++) {
+    if (batch > 0 && !t[i].idx) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding: null pointer");
+    if (t[i].num_entries <= 0) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding: ld < out_dim or num_entries <= 0");
+  }
+  return FFH_OK;
+}
+
+// The ragged update in the two phases of emb_bwd_phases: do_sort && do_apply is the fused entry, do_sort alone and do_apply alone are the pair of
+// include/ff_hip_bags_sort.h.  Same launches in the same order on the same workspace.
 int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, int nt, int D, int64_t batch, int aggr, float lr, ffh_stream s,
+                 const bool do_sort, const bool do_apply,
                  const ffh_sparse_opt* opt, const ffh_emb_state* states, const Bf16Cfg* b16, const ffh_lr_state* lr_block) {
   int rc = bags_dims_check(in_dims, nt, batch);
   if (rc == FFH_ERR_BAD_ARG) return ffh_fail(c, rc, "embedding_bwd_fused_multi_bags: ntables out of range, null in_dims or in_dims[i] < 1");
   if (rc) return ffh_fail(c, rc, "embedding_bwd_fused_multi_bags: in_dims[i] > FFH_BAGS_MAX_IN_DIM (65535) or batch*in_dims[i] >= 2^31");
-  rc = validate_tables(c, tables, nt, 1, D, batch, aggr);
+  rc = do_apply ? validate_tables(c, tables, nt, 1, D, batch, aggr) : validate_sort_tables(c, tables, nt, D, batch);
   if (rc) return rc;
   UpdatePlan plan;
-  rc = emb_update_rule(c, nt, D, batch, lr, true, opt, states, b16, lr_block, &plan);
+  rc = emb_update_rule(c, nt, D, batch, lr, do_apply, opt, states, b16, lr_block, &plan);
   if (rc) return rc;
   if (nt == 0 || batch == 0) return FFH_OK;
-  rc = emb_update_form(c, tables, nt, D, states, &plan);
+  rc = emb_update_form(c, tables, nt, D, states, &plan);      // (the sort phase: the plain rule, no state is looked at; it keeps maxR)
   if (rc) return rc;
   const BagsLayout lay = bags_layout(in_dims, nt, D, batch);
   if (!c->ws || c->ws_bytes < lay.total) return ffh_fail(c, FFH_ERR_WORKSPACE, "embedding_bwd_fused_multi_bags: workspace too small (ffh_embedding_bwd_bags_workspace_bytes)");
   char* ws = (char*)c->ws;
   if (!aligned16(ws)) return ffh_fail(c, FFH_ERR_WORKSPACE, "embedding_bwd_fused_multi_bags: workspace must be 16-byte aligned");
-  if (c->emb_sorted_ws == c->ws) c->emb_sorted_ws = nullptr;      // (as the uniform fused call: a pending sort on this workspace is overwritten)
+  // One-shot, as in emb_bwd_phases: the apply phase consumes the sorted lists, the level-1 slots and the arrival counters that only the sort's
+  // pass 0 clears.  The sort notes the workspace and everything the layout and the lists depend on; the apply requires that note and clears it.
+  // Either phase overwrites what a uniform sort left on this workspace, and a uniform fused call or sort spoils this note (spoil_bags_sort_note):
+  // a note of one kind never serves the other kind's apply.
+  if (do_sort) {
+    if (c->emb_sorted_ws == c->ws) c->emb_sorted_ws = nullptr;      // (as the uniform fused call: a pending sort on this workspace is overwritten)
+    spoil_bags_sort_note(c);
+  }
+  if (do_sort != do_apply) {
+    ffh_ctx::bags_sort_note note;
+    memset(&note, 0, sizeof note);
+    note.ws = c->ws; note.nt = nt; note.D = D; note.batch = batch;
+    for (int i = 0; i < nt; i++) { note.rows[i] = tables[i].num_entries; note.idx[i] = tables[i].idx; note.L[i] = (uint16_t)in_dims[i]; }
+    if (do_sort) {
+      c->emb_bags_sorted = note;
+    } else {
+      if (memcmp(&c->emb_bags_sorted, &note, sizeof note) != 0)
+        return ffh_fail(c, FFH_ERR_WORKSPACE, "embedding_bwd_apply_multi_bags: no fresh ffh_embedding_bwd_sort_multi_bags of the same tables / bag sizes / batch on this "
+                                             "ctx's workspace (the apply phase consumes the sort: one apply per sort)");
+      c->emb_bags_sorted.ws = nullptr;
+    }
+  }
   const RadixPlan rp = radix_plan(plan.maxR);
   const int avg = aggr == FFH_AGGR_MODE_AVG ? 1 : 0;
 
   if (lay.maxN <= kSmallMax) {
     snprintf(c->emb_route, sizeof c->emb_route, "bags:small");
+    if (!do_apply) return FFH_OK;      // (the sort lives inside the one launch: the sort call only leaves the note)
     BagsSmallArgs sm;
     memset(&sm, 0, sizeof sm);
     for (int i = 0; i < nt; i++) sm.t[i] = tables[i];
@@ -658,12 +701,13 @@ int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, in
   sa.clear[1] = (uint32_t*)(ws + lay.arrive); sa.nclear[1] = (int)(lay.tot.ch1 + nt);
   uint2* kbuf[2] = {(uint2*)(ws + lay.kp_a), (uint2*)(ws + lay.kp_b)};
   const dim3 sgrid((unsigned)lay.tot.sblk0), rgrid((unsigned)lay.tot.local);      // the flat map: every table's own tiles
-  for (int p = 0; p < rp.passes; p++) {
+  for (int p = 0; do_sort && p < rp.passes; p++) {
     sa.shift = p * rp.rb; sa.pass = p;
     sa.src = kbuf[p & 1]; sa.dst = kbuf[(p + 1) & 1];
     if (!emb_bags_sort_pass(sa, p == 0, lay.E, sgrid, as_stream(s))) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags: no sort kernel");
   }
   FFH_LAUNCH_CHECK(c, "bags radix sort");
+  if (!do_apply) return FFH_OK;
 
   ra.kp[0] = kbuf[0]; ra.kp[1] = kbuf[1];
   set_ws_slots(ra, ws, lay);
@@ -688,18 +732,32 @@ size_t ffh_embedding_bwd_bags_workspace_bytes(const int* in_dims, int nt, int D,
   return bags_layout(in_dims, nt, D, batch).total;
 }
 
-int ffh_embedding_bwd_fused_multi_bags(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) {
+// the descriptor of the three ragged entries: the fused call (do_sort && do_apply) and the pair of include/ff_hip_bags_sort.h.  The sort phase
+// takes the fields it reads (tables, in_dims, ntables, out_dim, batch) and nothing else.
+static int emb_bwd_bags_desc(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s, const bool do_sort, const bool do_apply) {
   if (!u) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: null descriptor");
   if ((u->tables != nullptr) == (u->tables_bf16 != nullptr)) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: exactly one of tables / tables_bf16");
-  if (u->lr_block && !u->opt) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: lr_block needs opt");
-  if (u->tables) return emb_bwd_bags(c, u->tables, u->in_dims, u->ntables, u->out_dim, u->batch, u->aggr, u->lr, s, u->opt, u->states, nullptr, u->lr_block);
+  if (do_apply && u->lr_block && !u->opt) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: lr_block needs opt");
+  const int aggr = do_apply ? u->aggr : FFH_AGGR_MODE_SUM;
+  const float lr = do_apply ? u->lr : 0.0f;
+  const ffh_sparse_opt* opt = do_apply ? u->opt : nullptr;
+  const ffh_emb_state* states = do_apply ? u->states : nullptr;
+  const ffh_lr_state* lr_block = do_apply ? u->lr_block : nullptr;
+  if (u->tables) return emb_bwd_bags(c, u->tables, u->in_dims, u->ntables, u->out_dim, u->batch, aggr, lr, s, do_sort, do_apply, opt, states, nullptr, lr_block);
   ffh_emb_table t[FFH_MAX_TABLES];
   Bf16Cfg cfg;
   memset(&cfg, 0, sizeof cfg);
-  cfg.r = u->rounding;
+  cfg.r = do_apply ? u->rounding : nullptr;
   const int rc = bf16_tables(c, u->tables_bf16, u->ntables, t, &cfg.keys);
   if (rc) return rc;
-  return emb_bwd_bags(c, t, u->in_dims, u->ntables, u->out_dim, u->batch, u->aggr, u->lr, s, u->opt, u->states, &cfg, u->lr_block);
+  return emb_bwd_bags(c, t, u->in_dims, u->ntables, u->out_dim, u->batch, aggr, lr, s, do_sort, do_apply, opt, states, &cfg, lr_block);
 }
+
+int ffh_embedding_bwd_fused_multi_bags(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, true, true); }
+
+// include/ff_hip_bags_sort.h
+int ffh_bags_sort_abi_version(void) { return FFH_BAGS_SORT_ABI_VERSION; }
+int ffh_embedding_bwd_sort_multi_bags(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, true, false); }
+int ffh_embedding_bwd_apply_multi_bags(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, false, true); }
 
 }  // extern "C"

@@ -243,6 +243,23 @@ const KernelApi* load_kernel_api(const std::string& path_in) {
     }
     api->bags_update = b;
   }
+  // the bags-sort extension (include/ff_hip_bags_sort.h): the same rule
+  if (dlsym(h, "ffh_bags_sort_abi_version")) {
+    KernelApiBagsSort* b = new KernelApiBagsSort();
+#define FFH_LOAD(name)                                                        \
+  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
+  if (!b->name) {                                                             \
+    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_bags_sort.h: %s is missing\n", path.c_str(), #name);   \
+    abort();                                                                  \
+  }
+    FFH_BAGS_SORT_API_LIST(FFH_LOAD)
+#undef FFH_LOAD
+    if (b->ffh_bags_sort_abi_version() != FFH_BAGS_SORT_ABI_VERSION) {
+      fprintf(stderr, "FATAL: %s has bags-sort ABI version %d, expected %d\n", path.c_str(), b->ffh_bags_sort_abi_version(), FFH_BAGS_SORT_ABI_VERSION);
+      abort();
+    }
+    api->bags_sort = b;
+  }
   if (path_in.empty() && g_env_override)
     fprintf(stderr, "[DLRM] FFH_BACKEND_LIB: kernel library %s (%s)\n", path.c_str(), api->ffh_backend_name());
   cache[path] = api;

@@ -15,6 +15,7 @@
 #include "../../include/ff_hip_fold.h"
 #include "../../include/ff_hip_bags.h"
 #include "../../include/ff_hip_bags_update.h"
+#include "../../include/ff_hip_bags_sort.h"
 
 // The optional bf16-table extension (include/ff_hip_bf16.h): all of its list or none of it.
 struct KernelApiBf16 {
@@ -93,6 +94,13 @@ struct KernelApiBagsUpdate {
 #undef FFH_DECL
 };
 
+// The optional bags-sort extension (include/ff_hip_bags_sort.h: the ragged update's sort call and apply call).
+struct KernelApiBagsSort {
+#define FFH_DECL(name) decltype(&::name) name;
+  FFH_BAGS_SORT_API_LIST(FFH_DECL)
+#undef FFH_DECL
+};
+
 struct KernelApi {
 #define FFH_DECL(name) decltype(&::name) name;
   FFH_API_LIST(FFH_DECL)
@@ -108,6 +116,7 @@ struct KernelApi {
   const KernelApiFold* fold = nullptr;       // likewise for include/ff_hip_fold.h (absent: no table is folded, the step is the one of before)
   const KernelApiBags* bags = nullptr;       // likewise for include/ff_hip_bags.h (absent: a model of mixed bag sizes gathers once per bag size)
   const KernelApiBagsUpdate* bags_update = nullptr;   // likewise for include/ff_hip_bags_update.h (absent: a model of mixed bag sizes updates once per bag size)
+  const KernelApiBagsSort* bags_sort = nullptr;       // likewise for include/ff_hip_bags_sort.h (absent: a model of mixed bag sizes sorts in front of its apply)
   void* handle;
   std::string path;
   bool overridden = false;      // chosen by --backend or $FFH_BACKEND_LIB rather than the product default: the driver says so on its THROUGHPUT line

@@ -724,10 +724,12 @@ class FFModel {
   uint64_t* digest_acc = nullptr;             // the digest's accumulator word in device memory (allocated by the first use)
   mutable int64_t n_graph_replays = 0;        // hipGraph launches of an already captured trace (tests: flexflow_model_get_counter "graph_replays")
   mutable int64_t n_early_sorts = 0;          // sort-only launches issued behind the gather (tests: flexflow_model_get_counter "early_sorts")
+  mutable int64_t n_ragged_early_sorts = 0;   // ... those of them that were ffh_embedding_bwd_sort_multi_bags calls ("ragged_early_sorts")
   mutable int64_t n_ragged_gathers = 0;       // ffh_embedding_fwd_multi_bags[_bf16] launches (tests: flexflow_model_get_counter "ragged_gather_launches")
   bool mixed_bags = false;                    // the tables' bag sizes differ (allocate()): DESIGN section 19
   mutable int64_t n_ragged_updates = 0;       // ffh_embedding_bwd_fused_multi_bags calls (tests: flexflow_model_get_counter "ragged_update_launches")
   bool ragged_update_on() const;              // the tables' bag sizes differ and their fused update is the ragged call (the library has it, the flag allows it)
+  bool ragged_early_sort_on() const;          // ... and --early-sort asks for its sort behind the gather, with a library that has the pair (include/ff_hip_bags_sort.h)
   std::string bag_update_line() const;        // how a model of mixed bag sizes updates its tables, for the driver's transcript
   bool ragged_gather_on() const;              // ... and their gather is the one-launch ragged one (the library has it, no --no-ragged-gather)
   std::string bag_gather_line() const;        // how a model of mixed bag sizes gathers, for the driver's transcript

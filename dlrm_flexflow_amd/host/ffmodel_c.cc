@@ -174,6 +174,7 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   if (n == "direct_allreduces") return M(m)->n_direct_allreduces;
   if (n == "bf16_updates") return (int64_t)M(m)->read_bf16_counter();
   if (n == "early_sorts") return M(m)->n_early_sorts;
+  if (n == "ragged_early_sorts") return M(m)->n_ragged_early_sorts;      // ffh_embedding_bwd_sort_multi_bags calls among them (include/ff_hip_bags_sort.h)
   if (n == "ragged_update_launches") return M(m)->n_ragged_updates;      // ffh_embedding_bwd_fused_multi_bags calls (mixed bag sizes; include/ff_hip_bags_update.h)
   if (n == "ragged_gather_launches") return M(m)->n_ragged_gathers;      // ffh_embedding_fwd_multi_bags[_bf16] launches (mixed bag sizes; include/ff_hip_bags.h)
   if (n == "lr_steps") return M(m)->lr_steps();

@@ -15,7 +15,7 @@
 void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_ctx* cx, const std::vector<const int64_t*>* idx_override, bool all_tables) {
   const bool fwd = what == kGather;
   ffh_sparse_opt rule;
-  const bool ruled = (what == kFusedUpdate || what == kApplyOnly) && ff->sparse_rule(rule);     // momentum / wd SGD, Adam on the touched rows
+  const bool ruled = !fwd && ff->sparse_rule(rule);     // momentum / wd SGD, Adam on the touched rows (the sort-only calls read none of it)
   // the rate from device memory (include/ff_hip_lr.h): the opt entries with the table update's own block; kind FFH_SPARSE_OPT_SGD = the plain update's bits
   const ffh_lr_state* lrb = ff->lr_route == FFModel::kLrDevice ? ff->lr_block[1] : nullptr;
   const KernelApiLr* lra = ff->api->lr;
@@ -23,8 +23,9 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
   // by shard width, then storage (bf16 tables: include/ff_hip_bf16.h, keyed by global table index and global column), then bag size.  The uniform
   // update entries take one bag size per call, so their groups are split by bag size; a model of mixed bag sizes keeps a group whole (key 0) for the
   // gather where the library has the one-launch ragged gather (include/ff_hip_bags.h) and --no-ragged-gather is not given, and for the fused update
-  // where it has the ragged update (include/ff_hip_bags_update.h) and --ragged-update allows it.  The sort-only / apply-only pair stays uniform.
-  const bool ragged = fwd ? ff->ragged_gather_on() : (what == kFusedUpdate && ff->ragged_update_on());
+  // where it has the ragged update (include/ff_hip_bags_update.h) and --ragged-update allows it, and for the sort-only / apply-only pair where the
+  // ragged early sort is on (include/ff_hip_bags_sort.h, FFModel::ragged_early_sort_on).
+  const bool ragged = fwd ? ff->ragged_gather_on() : (what == kFusedUpdate ? ff->ragged_update_on() : ff->ragged_early_sort_on());
   struct Group { std::vector<ffh_emb_table> t; std::vector<ffh_emb_table_bf16> t16; std::vector<ffh_emb_state> st; std::vector<int> bag; };
   std::map<std::tuple<int, bool, int>, Group> groups;
   size_t owned_i = 0;
@@ -61,14 +62,20 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
       for (int i = 1; i < n; i++) if (g.bag[b + i] != g.bag[b]) return true;
       return false;
     };
-    // the ragged fused update of tables [b, b + n): every rule and both rates through the one descriptor
+    // the ragged update of tables [b, b + n), fused or one call of the pair (`what`): every rule and both rates through the one descriptor
     auto ragged_update = [&](const ffh_emb_table* t32, const ffh_emb_table_bf16* t16, const ffh_emb_state* st, const ffh_bf16_rounding* rnd, size_t b, int n) {
       ffh_bags_update u;
       u.tables = t32; u.tables_bf16 = t16; u.in_dims = g.bag.data() + b; u.states = st;
       u.ntables = n; u.out_dim = D; u.batch = B; u.aggr = aggr; u.lr = rule.lr;
       u.opt = (ruled || lrb) ? &rule : nullptr;
       u.rounding = rnd; u.lr_block = lrb;
-      ff->check(ff->api->bags_update->ffh_embedding_bwd_fused_multi_bags(cx, &u, s), "embedding_bwd_fused_multi_bags");
+      if (what == kSortOnly) {
+        ff->check(ff->api->bags_sort->ffh_embedding_bwd_sort_multi_bags(cx, &u, s), "embedding_bwd_sort_multi_bags");
+        ff->n_early_sorts++; ff->n_ragged_early_sorts++;
+        return;
+      }
+      if (what == kApplyOnly) ff->check(ff->api->bags_sort->ffh_embedding_bwd_apply_multi_bags(cx, &u, s), "embedding_bwd_apply_multi_bags");
+      else ff->check(ff->api->bags_update->ffh_embedding_bwd_fused_multi_bags(cx, &u, s), "embedding_bwd_fused_multi_bags");
       ff->n_ragged_updates++;
     };
     if (std::get<1>(kv.first)) {
@@ -93,9 +100,12 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
             else if (ruled) ff->check(b16->ffh_embedding_bwd_opt_fused_multi_bf16(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, s), "embedding_bwd_opt_fused_multi_bf16");
             else ff->check(b16->ffh_embedding_bwd_sgd_fused_multi_bf16(cx, tb, n, L, D, B, aggr, rule.lr, &rnd, s), "embedding_bwd_sgd_fused_multi_bf16");
             break;
-          case kSortOnly: ff->check(b16->ffh_embedding_bwd_sort_multi_bf16(cx, tb, n, L, D, B, s), "embedding_bwd_sort_multi_bf16"); ff->n_early_sorts++; break;
+          case kSortOnly:
+            if (ragged && differ(b, n)) { ragged_update(nullptr, tb, st, &rnd, b, n); break; }
+            ff->check(b16->ffh_embedding_bwd_sort_multi_bf16(cx, tb, n, L, D, B, s), "embedding_bwd_sort_multi_bf16"); ff->n_early_sorts++; break;
           case kApplyOnly:
-            if (lrb) ff->check(lra->ffh_embedding_bwd_opt_apply_multi_bf16_lr(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, lrb, s), "embedding_bwd_opt_apply_multi_bf16_lr");
+            if (ragged && differ(b, n)) ragged_update(nullptr, tb, st, &rnd, b, n);
+            else if (lrb) ff->check(lra->ffh_embedding_bwd_opt_apply_multi_bf16_lr(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, lrb, s), "embedding_bwd_opt_apply_multi_bf16_lr");
             else if (ruled) ff->check(b16->ffh_embedding_bwd_opt_apply_multi_bf16(cx, tb, st, n, L, D, B, aggr, &rule, &rnd, s), "embedding_bwd_opt_apply_multi_bf16");
             else ff->check(b16->ffh_embedding_bwd_sgd_apply_multi_bf16(cx, tb, n, L, D, B, aggr, rule.lr, &rnd, s), "embedding_bwd_sgd_apply_multi_bf16");
             break;
@@ -121,9 +131,12 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
           else if (ruled) ff->check(ff->api->ffh_embedding_bwd_opt_fused_multi(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, s), "embedding_bwd_opt_fused_multi");
           else ff->check(ff->api->ffh_embedding_bwd_sgd_fused_multi(cx, tabs.data() + b, n, L, D, B, aggr, rule.lr, s), "embedding_bwd_sgd_fused_multi");
           break;
-        case kSortOnly: ff->check(ff->api->ffh_embedding_bwd_sort_multi(cx, tabs.data() + b, n, L, D, B, s), "embedding_bwd_sort_multi"); ff->n_early_sorts++; break;
+        case kSortOnly:
+          if (ragged && differ(b, n)) { ragged_update(tabs.data() + b, nullptr, sts.data() + b, nullptr, b, n); break; }
+          ff->check(ff->api->ffh_embedding_bwd_sort_multi(cx, tabs.data() + b, n, L, D, B, s), "embedding_bwd_sort_multi"); ff->n_early_sorts++; break;
         case kApplyOnly:
-          if (lrb) ff->check(lra->ffh_embedding_bwd_opt_apply_multi_lr(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, lrb, s), "embedding_bwd_opt_apply_multi_lr");
+          if (ragged && differ(b, n)) ragged_update(tabs.data() + b, nullptr, sts.data() + b, nullptr, b, n);
+          else if (lrb) ff->check(lra->ffh_embedding_bwd_opt_apply_multi_lr(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, lrb, s), "embedding_bwd_opt_apply_multi_lr");
           else if (ruled) ff->check(ff->api->ffh_embedding_bwd_opt_apply_multi(cx, tabs.data() + b, sts.data() + b, n, L, D, B, aggr, &rule, s), "embedding_bwd_opt_apply_multi");
           else ff->check(ff->api->ffh_embedding_bwd_sgd_apply_multi(cx, tabs.data() + b, n, L, D, B, aggr, rule.lr, s), "embedding_bwd_sgd_apply_multi");
           break;
@@ -146,6 +159,9 @@ std::string FFModel::bag_gather_line() const {
 }
 
 bool FFModel::ragged_update_on() const { return mixed_bags && config.ragged_update && api->bags_update; }
+// a model of mixed bag sizes may sort behind the gather (early_sort_possible): asked for by --early-sort (never by shape: that default is unmeasured),
+// with the ragged update on and a library that has its two-call form (include/ff_hip_bags_sort.h)
+bool FFModel::ragged_early_sort_on() const { return config.early_sort > 0 && ragged_update_on() && api->bags_sort; }
 // how a model of mixed bag sizes updates its tables (the driver prints it): the calls of one fused update over this rank's tables
 std::string FFModel::bag_update_line() const {
   const bool on = ragged_update_on();
@@ -163,6 +179,8 @@ std::string FFModel::bag_update_line() const {
   if (on && uniform) snprintf(buf, sizeof buf, "ragged, %zu call%s per step (%zu of them over one bag size)", calls, calls == 1 ? "" : "s", uniform);
   else if (on) snprintf(buf, sizeof buf, "ragged, %zu call%s per step", calls, calls == 1 ? "" : "s");
   else snprintf(buf, sizeof buf, "per bag size, %zu call%s per step%s", calls, calls == 1 ? "" : "s", !api->bags_update ? " (the kernel library has no ragged update)" : " (--no-ragged-update)");
+  // the sort of the one ragged call leaves the chain behind the gradients (ffh_embedding_bwd_sort_multi_bags behind the gather)
+  if (on && ragged_early_sort_on() && early_sort_possible(1)) snprintf(buf + strlen(buf), sizeof buf - strlen(buf), ", sorted behind the gather");
   return buf;
 }
 
@@ -230,7 +248,8 @@ bool FFModel::early_sort_possible(int where) const {
   for (const EmbShard& sh : shards) {
     if (sh.owner != rank) continue;
     if (cols >= 0 && sh.cols != cols) return false;
-    if (bag >= 0 && sh.e->inputs[0].adim[0] != bag) return false;      // one sort note per ctx: a model of mixed bag sizes sorts in front of its apply
+    // one sort note per ctx: a model of mixed bag sizes sorts in front of its apply, unless its one group has the ragged pair (ragged_early_sort_on)
+    if (bag >= 0 && sh.e->inputs[0].adim[0] != bag && !ragged_early_sort_on()) return false;
     cols = sh.cols;
     bag = sh.e->inputs[0].adim[0];
     n++;

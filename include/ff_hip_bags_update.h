@@ -27,7 +27,8 @@
  * launched on an error.  Row ids are not checked.
  *
  * Like the uniform fused call, this one spoils a pending ffh_embedding_bwd_sort_multi note on the workspace it overwrites: a later
- * ffh_embedding_bwd_*_apply_multi on that note returns FFH_ERR_WORKSPACE.  There is no ragged two-call (sort, then apply) form.
+ * ffh_embedding_bwd_*_apply_multi on that note returns FFH_ERR_WORKSPACE.  The ragged two-call form (sort, then apply) of this entry is an
+ * extension of its own, include/ff_hip_bags_sort.h, on this header's descriptor; this call spoils a pending ragged sort in the same way.
  */
 #ifndef FF_HIP_BAGS_UPDATE_H_
 #define FF_HIP_BAGS_UPDATE_H_

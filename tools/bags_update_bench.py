@@ -6,6 +6,7 @@
                   runs, the only way without the extension, and the baseline
 
   python tools/bags_update_bench.py [--bag-sizes a-b-c-...] [--batch B] [--dtype fp32|bf16|both] [--rule sgd|rowwise|both] [--rows r-r-...] [--dim D]
+                                    [--legs update|pair|both]
 
 Defaults: the MLPerf DLRM-DCNv2 shape -- the 26 pooling sizes 3-2-1-2-6-1-1-1-1-7-3-8-1-6-9-5-1-1-1-12-100-27-10-3-1-1, 8192 samples, D = 128, the
 table row counts of bench.py's MLPerf workload -- for fp32 and for bf16 tables (stochastic rounding, the update counter held still), plain SGD and
@@ -17,7 +18,16 @@ off the route every call reports (ffh_embedding_last_route: one-launch form 1, b
 
 Before any timing the two legs are compared bit for bit: from the same start (the tables are re-initialised from their seeds in between) each leg
 runs one update per id set; after each, the rows the update touched (and their optimizer state) are read back, and a wrapping 64-bit sum over
-every table's bits covers the rows it did not."""
+every table's bits covers the rows it did not.
+
+The pair leg (--legs pair | both; include/ff_hip_bags_sort.h) says how much of the ragged call an early sort can move off the step's serial chain:
+  (s) sort     ffh_embedding_bwd_sort_multi_bags alone: the index-only part
+  (p) apply    ffh_embedding_bwd_apply_multi_bags alone: what stays behind the output gradients
+  (f) fused    ffh_embedding_bwd_fused_multi_bags, timed the same way
+An apply needs a sort of its own (the pair is one-shot), so this leg cannot run applies back to back: every CALL sits between two HIP events of its
+own ([e0] sort [e1] apply [e2], and [e0] fused [e1]) and a window's figure is the mean over its calls.  Windows of sort + apply and windows of the
+fused call alternate; the pair is first compared with the fused call bit for bit, as above.  The per-call events leave the launch gaps in, so (f)
+here reads higher than (a) above; (s) + (p) against (f) is the comparison."""
 import argparse
 import ctypes as C
 import os
@@ -62,7 +72,7 @@ def window(fn, n):
     return e0.elapsed_time(e1) * 1e3 / n
 
 
-def bench(hip, bu, b16, rows, bags, D, batch, bf16, rule):
+def bench(hip, bu, b16, rows, bags, D, batch, bf16, rule, legs="update", bs=None):
     import torch
     from dlrm_flexflow_amd import capi
     dev, nt = "cuda:0", len(bags)
@@ -150,6 +160,54 @@ def bench(hip, bu, b16, rows, bags, D, batch, bf16, rule):
                 out.append(state[t].view(torch.int32).sum(dtype=torch.int64).reshape(1))
         torch.cuda.synchronize()
         return out
+    kind = ("bf16" if bf16 else "fp32") + " tables, " + ("row-wise Adagrad" if rowwise else "plain SGD")
+    nbytes = algorithmic_bytes(batch, bags, D, wbytes)
+    if legs != "update":
+        def leg_pair(s, note=False):
+            bs.sort(ragged[s])
+            bs.apply(ragged[s])
+        sa, sp = snapshot(leg_a), snapshot(leg_pair)
+        for k, (x, y) in enumerate(zip(sa, sp)):
+            if not torch.equal(x.view(torch.uint8), y.view(torch.uint8)):
+                sys.exit(f"record {k}: sort + apply and the fused ragged call differ")
+        del sa, sp
+
+        def timed(calls, n):
+            """n rounds of `calls` (each between two events of its own); the mean microseconds of every call"""
+            ev = [[torch.cuda.Event(enable_timing=True) for _ in range(len(calls) + 1)] for _ in range(n)]
+            for i in range(n):
+                ev[i][0].record()
+                for k, fn in enumerate(calls):
+                    fn(ragged[i % NSETS])
+                    ev[i][k + 1].record()
+            torch.cuda.synchronize()
+            return [sum(ev[i][k].elapsed_time(ev[i][k + 1]) for i in range(n)) * 1e3 / n for k in range(len(calls))]
+        n = 8
+        while True:
+            us = timed([bu.call], n)[0]
+            if us * n >= MIN_SECONDS * 1e6:
+                break
+            n = int(n * max(2.0, 1.2 * MIN_SECONDS * 1e6 / (us * n)))
+        t = {"s": [], "p": [], "f": []}
+        for _ in range(WINDOWS):
+            a, b = timed([bs.sort, bs.apply], n)
+            t["s"].append(a); t["p"].append(b)
+            t["f"].append(timed([bu.call], n)[0])
+        print(f"{kind}: {nt} tables, D {D}, batch {batch}, {sum(bags)} lookups per sample; the pair leg: {n} calls per window, {WINDOWS} interleaved windows, "
+              f"every call between two events of its own; sort + apply leave the fused call's bits; route {seen['a'][0]}")
+        t["s+p"] = [x + y for x, y in zip(t["s"], t["p"])]
+        for leg, what in (("s", "(s) sort call alone"), ("p", "(p) apply call alone"), ("s+p", "(s) + (p), window by window"), ("f", "(f) fused call")):
+            v = np.array(t[leg])
+            print(f"  {what:44s} us per call:   {' '.join(f'{u:7.1f}' for u in v)} | min {v.min():7.1f} median {np.median(v):7.1f} max {v.max():7.1f} "
+                  f"| spread {100 * (v.max() - v.min()) / np.median(v):4.1f} %", flush=True)
+        ms, mp, mf = (float(np.median(t[k])) for k in ("s", "p", "f"))
+        print(f"  the sort is {ms / mf:.3f} of the fused call at the medians: what an early sort can move; (s) + (p) - (f) = {ms + mp - mf:+.1f} us "
+              f"(the fused call's window spread: {max(t['f']) - min(t['f']):.1f} us)", flush=True)
+    if legs == "pair":
+        del tables, ids, g, ws, state
+        torch.cuda.empty_cache()
+        return None
+    seen["a"].clear()
     sa, sb = snapshot(leg_a), snapshot(leg_b)
     for k, (x, y) in enumerate(zip(sa, sb)):
         if not torch.equal(x.view(torch.uint8), y.view(torch.uint8)):
@@ -165,8 +223,6 @@ def bench(hip, bu, b16, rows, bags, D, batch, bf16, rule):
     for _ in range(WINDOWS):
         t["a"].append(window(leg_a, n))
         t["b"].append(window(leg_b, n))
-    nbytes = algorithmic_bytes(batch, bags, D, wbytes)
-    kind = ("bf16" if bf16 else "fp32") + " tables, " + ("row-wise Adagrad" if rowwise else "plain SGD")
     print(f"{kind}: {nt} tables, D {D}, batch {batch}, {sum(bags)} lookups per sample, {nbytes / 1e6:.1f} MB per update by the formula; "
           f"{n} updates per window, {WINDOWS} interleaved windows per leg; the two legs leave the same bits")
     la, lb = sum(map(launches_of, seen["a"])), sum(map(launches_of, seen["b"]))
@@ -190,6 +246,7 @@ def main():
     ap.add_argument("--rows", default=None, help="table row counts r-r-... (default: bench.py's MLPerf workload)")
     ap.add_argument("--dtype", default="both", choices=["fp32", "bf16", "both"])
     ap.add_argument("--rule", default="both", choices=["sgd", "rowwise", "both"])
+    ap.add_argument("--legs", default="update", choices=["update", "pair", "both"], help="update: ragged against per bag size; pair: the sort call and the apply call alone")
     a = ap.parse_args()
     bags = [int(x) for x in a.bag_sizes.split("-")]
     if a.rows is None:
@@ -203,10 +260,11 @@ def main():
     from dlrm_flexflow_amd import capi
     hip = _lab.load_hip(0)                      # FFH_TOOLS_LIB=<libffhip.so of another build> measures that build
     bu, b16 = capi.bags_update_api(hip), capi.bf16_api(hip)
+    bs = capi.bags_sort_api(hip) if a.legs != "update" else None
     print(f"device: {torch.cuda.get_device_name(0)}; calls on the null stream, HIP events around each window")
     for bf16 in ([False, True] if a.dtype == "both" else [a.dtype == "bf16"]):
         for rule in (["sgd", "rowwise"] if a.rule == "both" else [a.rule]):
-            bench(hip, bu, b16, rows, bags, a.dim, a.batch, bf16, rule)
+            bench(hip, bu, b16, rows, bags, a.dim, a.batch, bf16, rule, a.legs, bs)
 
 
 if __name__ == "__main__":
