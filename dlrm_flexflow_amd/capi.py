@@ -1198,6 +1198,121 @@ def bags_sort_api(lib: "FFHLib") -> BagsSortApi:
     return BagsSortApi(lib)
 
 
+# ---- the q8 extension (include/ff_hip_q8.h): tables as 8-bit rows with a scale and a bias each; a quantizer and the gathers that read them ----
+Q8_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_q8.h")
+
+
+class EmbTableQ8(C.Structure):
+    """struct ffh_emb_table_q8"""
+    _fields_ = [("idx", P), ("rows", P), ("io", P), ("num_entries", L), ("ld", L), ("row_bytes", L)]
+
+
+class Q8Source(C.Structure):
+    """struct ffh_q8_source"""
+    _fields_ = [("weight", P), ("rows", P), ("num_entries", L), ("row_bytes", L), ("bf16", C.c_int32), ("reserved_", C.c_int32)]
+
+
+_SIGS_Q8 = {
+    "ffh_q8_abi_version": (I, []),
+    "ffh_q8_row_bytes": (SZ, [I]),
+    "ffh_q8_quantize_max_workgroups": (I, []),
+    "ffh_embedding_quantize_q8": (I, [P, C.POINTER(Q8Source), I, I, P]),
+    "ffh_embedding_fwd_multi_q8": (I, [P, C.POINTER(EmbTableQ8), I, I, I, L, I, P]),
+    "ffh_embedding_fwd_multi_bags_q8": (I, [P, C.POINTER(EmbTableQ8), C.POINTER(I), I, I, L, I, P]),
+}
+
+
+def q8_header_symbols(header_path: str = Q8_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_Q8_API_LIST X-macro in include/ff_hip_q8.h."""
+    m = re.search(r"#define FFH_Q8_API_LIST\(X\)(.*?)\n\n", open(header_path).read(), re.S)
+    if not m:
+        raise RuntimeError("FFH_Q8_API_LIST not found in " + header_path)
+    return re.findall(r"X\((\w+)\)", m.group(1))
+
+
+def q8_header_abi_version(header_path: str = Q8_HEADER_PATH) -> int:
+    """FFH_Q8_ABI_VERSION of include/ff_hip_q8.h."""
+    m = re.search(r"#define\s+FFH_Q8_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_Q8_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
+class Q8Api:
+    """The q8 extension (include/ff_hip_q8.h) of a loaded FFHLib; `q8_api(lib)` builds it or raises."""
+
+    def __init__(self, lib: "FFHLib"):
+        self.base = lib
+        for name, (res, args) in _SIGS_Q8.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no q8 extension ({name} missing; include/ff_hip_q8.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_q8_abi_version()
+        if got != q8_header_abi_version():
+            raise FFHError(f"{lib.path}: q8 ABI version {got}, include/ff_hip_q8.h says {q8_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+    def row_bytes(self, out_dim: int) -> int:
+        return int(self.lib.ffh_q8_row_bytes(int(out_dim)))
+
+    def quantize_max_workgroups(self) -> int:
+        return int(self.lib.ffh_q8_quantize_max_workgroups())
+
+    @staticmethod
+    def quantize_rows_per_trip(out_dim: int) -> int:
+        """Rows of one table that a quantizer workgroup takes per trip (include/ff_hip_q8.h, QUANTIZER)."""
+        lanes = out_dim // 16 if out_dim % 16 == 0 else out_dim // 4
+        p = 1
+        while p < lanes and p < 64:
+            p <<= 1
+        return 4 * (64 // p)
+
+    @staticmethod
+    def tables(entries) -> "C.Array":
+        """entries: iterable of (idx, rows, io, num_entries, ld, row_bytes)."""
+        entries = list(entries)
+        arr = (EmbTableQ8 * max(1, len(entries)))()
+        for k, (idx, rows, io, n, ld, rb) in enumerate(entries):
+            arr[k] = EmbTableQ8(ptr(idx), ptr(rows), ptr(io), int(n), int(ld), int(rb))
+        return arr
+
+    @staticmethod
+    def sources(entries) -> "C.Array":
+        """entries: iterable of (weight, rows, num_entries, row_bytes, bf16)."""
+        entries = list(entries)
+        arr = (Q8Source * max(1, len(entries)))()
+        for k, (w, rows, n, rb, bf16) in enumerate(entries):
+            arr[k] = Q8Source(ptr(w), ptr(rows), int(n), int(rb), int(bf16), 0)
+        return arr
+
+    def quantize_rc(self, sources, ntables: int, out_dim: int, stream=None) -> int:
+        return self.lib.ffh_embedding_quantize_q8(self.ctx, sources, int(ntables), int(out_dim), ptr(stream))
+
+    def quantize(self, sources, ntables: int, out_dim: int, stream=None):
+        self.base.check(self.quantize_rc(sources, ntables, out_dim, stream), "ffh_embedding_quantize_q8")
+
+    def fwd_rc(self, tables, ntables: int, in_dim: int, out_dim: int, batch: int, aggr: int, stream=None) -> int:
+        return self.lib.ffh_embedding_fwd_multi_q8(self.ctx, tables, int(ntables), int(in_dim), int(out_dim), int(batch), int(aggr), ptr(stream))
+
+    def fwd(self, *args, **kw):
+        self.base.check(self.fwd_rc(*args, **kw), "ffh_embedding_fwd_multi_q8")
+
+    def fwd_bags_rc(self, tables, in_dims, ntables: int, out_dim: int, batch: int, aggr: int, stream=None) -> int:
+        """`in_dims` from BagsApi.in_dims (or None: a null pointer)."""
+        return self.lib.ffh_embedding_fwd_multi_bags_q8(self.ctx, tables, in_dims, int(ntables), int(out_dim), int(batch), int(aggr), ptr(stream))
+
+    def fwd_bags(self, *args, **kw):
+        self.base.check(self.fwd_bags_rc(*args, **kw), "ffh_embedding_fwd_multi_bags_q8")
+
+
+def q8_api(lib: "FFHLib") -> Q8Api:
+    """The 8-bit-row entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
+    return Q8Api(lib)
+
+
 _hip_singleton: FFHLib | None = None
 
 

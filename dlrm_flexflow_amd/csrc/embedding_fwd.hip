@@ -9,14 +9,16 @@
 //   * 64-bit addressing everywhere (a 200M x 256 table is 204.8 GB; the reference's
 //     `int outputSize` [ref: src/ops/embedding.cu:226,229] would overflow).
 // What is here:
-//   * RowLanes, store_row: the lane geometry and the store epilogue of both kernels;
 //   * emb_fwd_kernel: one bag size for all tables (grid.y = table);
 //   * emb_fwd_bags_kernel: a bag size per table (include/ff_hip_bags.h), a flat grid;
-//   * gather_form, gather_dests: the 16-byte form and every destination's twin / image, on the
-//     host, for both launchers; the entries ffh_embedding_fwd*, fp32 and bf16 tables.
-// What is where: the table update, the dense backward and the bf16 helpers are
-// embedding.hip; the checks on a table list shared with them are emb_tables.h.
-#include "emb_tables.h"
+//   * gather_form: the 16-byte form, on the host, for both launchers; the entries
+//     ffh_embedding_fwd*, fp32 and bf16 tables.
+//   * RowLanes: the lane geometry of both kernels;
+// What is where: store_row (the store epilogue of both kernels), bag_blocks and gather_dests
+// (every destination's twin / image) are emb_gather.h, shared with the gather from 8-bit rows
+// (embedding_q8.hip); the table update, the dense backward and the
+// bf16 helpers are embedding.hip; the checks on a table list shared with them are emb_tables.h.
+#include "emb_gather.h"
 
 #include <type_traits>
 
@@ -55,40 +57,6 @@ struct RowLanes {
   // rows a 256-thread workgroup takes per trip with U rows in flight per lane-group
   __host__ __device__ int64_t block_rows(int U) const { return 4LL * rpw * U; }
 };
-
-// The store epilogue: vector `c` of output row `b` from one row's sums -- the fp32 row, and beside it the bf16 twin (o16) and the
-// three-plane image (o3, column o3c) where the destination has one.
-template <int VEC>
-__device__ __forceinline__ void store_row(const ffh_emb_table& tb, unsigned short* const o16, char* const o3, const int o3c,
-                                          const int64_t b, const int c, const float (&acc)[VEC], const bool avg, const float inv) {
-  constexpr int NQ = VEC / 4;                     // 16-B groups of output floats per lane-access (0: scalar)
-  float f[VEC];
-#pragma unroll
-  for (int v = 0; v < VEC; v++) f[v] = avg ? acc[v] * inv : acc[v];
-  if constexpr (NQ == 0) {
-    tb.io[b * tb.ld + c] = f[0];
-  } else {
-#pragma unroll
-    for (int h = 0; h < NQ; h++) {
-      const int q = c * NQ + h;                 // float4 index in the output row
-      const float* g = f + 4 * h;
-      typedef float f4 __attribute__((ext_vector_type(4)));
-      const f4 o = {g[0], g[1], g[2], g[3]};
-      reinterpret_cast<f4*>(tb.io + b * tb.ld)[q] = o;
-      if (o16) {      // the twin the first top-MLP GEMM reads its operand from (ffh_ctx_bf16_mirror_set)
-        typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-        const bf2 lo = {(__bf16)g[0], (__bf16)g[1]}, hi = {(__bf16)g[2], (__bf16)g[3]};
-        reinterpret_cast<uint2*>(o16 + b * tb.ld)[q] = make_uint2(__builtin_bit_cast(unsigned, lo), __builtin_bit_cast(unsigned, hi));
-      }
-      if (o3) {       // split mode: the three-plane image of the row piece (ffh_ctx_bf16x3_mirror_set; ld a multiple of 32)
-        uint2 p1, p2, p3;
-        ffh_split_bf16x3(make_float4(g[0], g[1], g[2], g[3]), p1, p2, p3);
-        char* d = o3 + b * tb.ld * 6 + ffh_i32_off(o3c + 4 * q);
-        *reinterpret_cast<uint2*>(d) = p1; *reinterpret_cast<uint2*>(d + 64) = p2; *reinterpret_cast<uint2*>(d + 128) = p3;
-      }
-    }
-  }
-}
 
 // ---------------------------------------------------------------------------
 // forward: out[b][:] = sum_j W[idx[b][j]][:]
@@ -173,7 +141,6 @@ __global__ __launch_bounds__(256) void emb_fwd_kernel(const EmbArgs a) {
 // Kernel arguments: 64 tables of 40 bytes plus two pointer arrays are 3584 bytes; a bag size in 16 bits and the image column (< 32)
 // in 8 bits per table keep the struct below EmbArgs' size, and the prefix of the workgroup map is derived, not passed.
 // ---------------------------------------------------------------------------
-constexpr int kBagLong = 4;        // bags of at least this many ids take the JU = 4 form
 struct BagArgs {
   ffh_emb_table t[FFH_MAX_TABLES];
   unsigned short* out16[FFH_MAX_TABLES];   // as EmbArgs::out16
@@ -186,12 +153,6 @@ struct BagArgs {
   int     shift;        // workgroups of table i = clamp((batch * L[i]) >> shift, 1, nrb)
 };
 static_assert(sizeof(BagArgs) <= sizeof(EmbArgs) && sizeof(BagArgs) <= 4096, "kernel arguments");
-
-__host__ __device__ inline int64_t bag_blocks(int64_t batch, int L, int shift, int64_t nrb) {
-  int64_t w = (batch * (int64_t)L) >> shift;
-  w = w < 1 ? 1 : w;
-  return w > nrb ? nrb : w;
-}
 
 // the rows [first, first + step, ...) x rows_per_block of table t; U rows x JU ids in flight per lane-group
 template <int VEC, int U, int JU, class WT>
@@ -304,22 +265,6 @@ int gather_form(ffh_ctx* c, const ffh_emb_table* tables, int nt, int D, const ch
   *vec = v4 ? 4 : 1;
   if ((D / *vec + 63) / 64 > kMaxChunks * 64) return ffh_fail(c, FFH_ERR_UNSUPPORTED, too_large);
   return FFH_OK;
-}
-
-// The tables into the kernel arguments (EmbArgs / BagArgs), each with the registered twin and image of its destination.
-template <class Args>
-void gather_dests(const ffh_ctx* c, const ffh_emb_table* tables, int nt, int D, int64_t batch, int vec, Args& a) {
-  for (int i = 0; i < nt; i++) {
-    a.t[i] = tables[i];
-    const size_t span = (size_t)((batch - 1) * tables[i].ld + D) * 4;
-    // tensor-op mode with a registered twin of the destination: the gather writes the bf16 roundings beside the fp32 rows
-    a.out16[i] = (vec >= 4 && tables[i].ld % 4 == 0) ? ffh_mirror_of(c, tables[i].io, span) : nullptr;
-    // split mode with a registered image of the destination (rows a whole number of 32-element groups apart): the three terms beside the fp32 rows
-    int col0 = 0;
-    a.out3[i] = (vec >= 4 && tables[i].ld % 32 == 0) ? ffh_planes_of(c, tables[i].io, span, &col0) : nullptr;
-    a.out3c[i] = col0;      // (0 .. 31: BagArgs keeps it in 8 bits)
-    if (a.out3[i] && (col0 & 3)) a.out3[i] = nullptr;
-  }
 }
 
 template <class WT>

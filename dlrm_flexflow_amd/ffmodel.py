@@ -89,6 +89,7 @@ def lib() -> C.CDLL:
         "flexflow_config_set_overlap_embedding": (None, [H, B]), "flexflow_config_set_dense_embedding_update": (None, [H, B]),
         "flexflow_config_set_ragged_update": (None, [H, B]),
         "flexflow_config_set_embedding_dtype": (None, [H, I]), "flexflow_config_set_embedding_rounding": (None, [H, I]),
+        "flexflow_config_set_eval_embedding_dtype": (None, [H, I]),
         "flexflow_config_set_lr_schedule": (None, [H, C.c_int64, C.c_int64, C.c_int64, I]),
         "flexflow_lr_schedule_value": (D, [C.c_int64, D, C.c_int64, C.c_int64, C.c_int64]),
         "flexflow_model_get_current_lr": (D, [H]),
@@ -384,6 +385,53 @@ def cross_reference_backward(dy, x0, v, aliased=False):
         return dv, g0, dy.copy()
 
 
+def q8_quantize_reference(w):
+    """Rows of a [rows][D] float32 table as 8-bit codes with a scale and a bias per row, as include/ff_hip_q8.h states the rule: float32
+    throughout, every operation rounded on its own.  Returns (codes uint8 [rows][D], scale float32 [rows], bias float32 [rows])."""
+    w = np.asarray(w, dtype=np.float32)
+    f = np.float32
+    with np.errstate(all="ignore"):
+        mn = w.min(axis=-1) + f(0.0)             # a zero minimum is +0 whatever the order of the min
+        mx = w.max(axis=-1)
+        rng = (mx - mn).astype(f)
+        scale = (rng / f(255.0)).astype(f)
+        inv = (f(255.0) / (rng + f(1e-8)).astype(f)).astype(f)
+        q = np.rint(((w - mn[..., None]).astype(f) * inv[..., None]).astype(f))      # round half to even
+    return q.astype(np.uint8), scale, mn.astype(f)
+
+
+def q8_dequantize_reference(codes, scale, bias) -> np.ndarray:
+    """w[d] = (float)code[d] * scale + bias: a float32 multiply, then a float32 add (two roundings, not an fma)."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    scale, bias = (np.asarray(a, dtype=np.float32) for a in (scale, bias))
+    with np.errstate(all="ignore"):
+        return (codes.astype(np.float32) * scale[..., None]).astype(np.float32) + bias[..., None]
+
+
+def q8_pack_rows(codes, scale, bias, row_bytes: int | None = None) -> np.ndarray:
+    """The byte layout of include/ff_hip_q8.h: uint8 [rows][row_bytes] = D codes, fp32 scale, fp32 bias, zeros.  row_bytes defaults to D + 8."""
+    codes = np.ascontiguousarray(codes, dtype=np.uint8)
+    rows, D = codes.shape
+    row_bytes = D + 8 if row_bytes is None else int(row_bytes)
+    if D % 4 or row_bytes < D + 8 or row_bytes % 4:
+        raise ValueError(f"q8_pack_rows: D = {D} must be a multiple of 4 and row_bytes = {row_bytes} a multiple of 4 that is >= D + 8")
+    out = np.zeros((rows, row_bytes), np.uint8)
+    out[:, :D] = codes
+    out[:, D:D + 4] = np.ascontiguousarray(scale, dtype="<f4").reshape(rows, 1).view(np.uint8)
+    out[:, D + 4:D + 8] = np.ascontiguousarray(bias, dtype="<f4").reshape(rows, 1).view(np.uint8)
+    return out
+
+
+def q8_unpack_rows(rows, D: int):
+    """(codes, scale, bias) of uint8 [rows][row_bytes] in the layout of q8_pack_rows."""
+    rows = np.ascontiguousarray(rows, dtype=np.uint8)
+    if rows.ndim != 2 or rows.shape[1] < D + 8:
+        raise ValueError("q8_unpack_rows: rows must be [rows][row_bytes >= D + 8]")
+    scale = np.ascontiguousarray(rows[:, D:D + 4]).view("<f4").reshape(-1).astype(np.float32)
+    bias = np.ascontiguousarray(rows[:, D + 4:D + 8]).view("<f4").reshape(-1).astype(np.float32)
+    return rows[:, :D].copy(), scale, bias
+
+
 def _argv(args):
     arr = (C.c_char_p * len(args))(*[a.encode() for a in args])
     return arr
@@ -486,12 +534,14 @@ class FFConfig:
 
     def set(self, seed=None, device=None, enable_graph=None, overlap_embedding=None, dense_embedding_update=None,
             embedding_dtype=None, embedding_rounding=None, lr_warmup_steps=None, lr_decay_start_step=None, lr_num_decay_steps=None,
-            device_lr=None, adagrad_eps=None, adagrad_initial_accumulator=None, adagrad_rowwise=None, ragged_update=None):
+            device_lr=None, adagrad_eps=None, adagrad_initial_accumulator=None, adagrad_rowwise=None, ragged_update=None,
+            eval_embedding_dtype=None):
         """embedding_dtype: "fp32" | "bf16"; embedding_rounding: "stochastic" | "nearest" (the --embedding-* flags).
         lr_*: the schedule of --lr-num-warmup-steps / --lr-decay-start-step / --lr-num-decay-steps; device_lr: True = --device-lr,
         False = --host-lr-schedule, None = compile() chooses the route.
         adagrad_eps / adagrad_initial_accumulator: --adagrad-eps / --adagrad-initial-accumulator, what an AdagradOptimizer without its own takes.
         adagrad_rowwise: --adagrad-rowwise, the tables of an AdagradOptimizer keep one accumulator per row (include/ff_hip_rowwise.h).
+        eval_embedding_dtype: "fp32" | "int8" (--eval-embedding-dtype): eval_batch() gathers from 8-bit row images of the tables (include/ff_hip_q8.h).
         FFModel(config) copies the config: call set() before the model is built (as for every other field)."""
         if adagrad_rowwise is not None:
             lib().flexflow_config_set_adagrad_rowwise(self.h, 1 if adagrad_rowwise else 0)
@@ -516,6 +566,11 @@ class FFConfig:
             if dt is None:
                 raise ValueError(f"embedding_dtype {embedding_dtype!r}: 'fp32' or 'bf16'")
             lib().flexflow_config_set_embedding_dtype(self.h, dt)
+        if eval_embedding_dtype is not None:
+            q = {"fp32": 0, "int8": 1}.get(eval_embedding_dtype)
+            if q is None:
+                raise ValueError(f"eval_embedding_dtype {eval_embedding_dtype!r}: 'fp32' or 'int8'")
+            lib().flexflow_config_set_eval_embedding_dtype(self.h, q)
         if embedding_rounding is not None:
             mode = {"stochastic": ROUND_STOCHASTIC, "nearest": ROUND_NEAREST}.get(embedding_rounding)
             if mode is None:

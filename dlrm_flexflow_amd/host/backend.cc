@@ -260,6 +260,23 @@ const KernelApi* load_kernel_api(const std::string& path_in) {
     }
     api->bags_sort = b;
   }
+  // the q8 extension (include/ff_hip_q8.h): the same rule
+  if (dlsym(h, "ffh_q8_abi_version")) {
+    KernelApiQ8* b = new KernelApiQ8();
+#define FFH_LOAD(name)                                                        \
+  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
+  if (!b->name) {                                                             \
+    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_q8.h: %s is missing\n", path.c_str(), #name);   \
+    abort();                                                                  \
+  }
+    FFH_Q8_API_LIST(FFH_LOAD)
+#undef FFH_LOAD
+    if (b->ffh_q8_abi_version() != FFH_Q8_ABI_VERSION) {
+      fprintf(stderr, "FATAL: %s has q8 ABI version %d, expected %d\n", path.c_str(), b->ffh_q8_abi_version(), FFH_Q8_ABI_VERSION);
+      abort();
+    }
+    api->q8 = b;
+  }
   if (path_in.empty() && g_env_override)
     fprintf(stderr, "[DLRM] FFH_BACKEND_LIB: kernel library %s (%s)\n", path.c_str(), api->ffh_backend_name());
   cache[path] = api;

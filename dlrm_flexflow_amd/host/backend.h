@@ -16,6 +16,7 @@
 #include "../../include/ff_hip_bags.h"
 #include "../../include/ff_hip_bags_update.h"
 #include "../../include/ff_hip_bags_sort.h"
+#include "../../include/ff_hip_q8.h"
 
 // The optional bf16-table extension (include/ff_hip_bf16.h): all of its list or none of it.
 struct KernelApiBf16 {
@@ -101,6 +102,13 @@ struct KernelApiBagsSort {
 #undef FFH_DECL
 };
 
+// The optional q8 extension (include/ff_hip_q8.h: tables as 8-bit rows for held-out evaluation, their quantizer and gathers).
+struct KernelApiQ8 {
+#define FFH_DECL(name) decltype(&::name) name;
+  FFH_Q8_API_LIST(FFH_DECL)
+#undef FFH_DECL
+};
+
 struct KernelApi {
 #define FFH_DECL(name) decltype(&::name) name;
   FFH_API_LIST(FFH_DECL)
@@ -117,6 +125,7 @@ struct KernelApi {
   const KernelApiBags* bags = nullptr;       // likewise for include/ff_hip_bags.h (absent: a model of mixed bag sizes gathers once per bag size)
   const KernelApiBagsUpdate* bags_update = nullptr;   // likewise for include/ff_hip_bags_update.h (absent: a model of mixed bag sizes updates once per bag size)
   const KernelApiBagsSort* bags_sort = nullptr;       // likewise for include/ff_hip_bags_sort.h (absent: a model of mixed bag sizes sorts in front of its apply)
+  const KernelApiQ8* q8 = nullptr;                    // likewise for include/ff_hip_q8.h (absent: compile() refuses --eval-embedding-dtype int8)
   void* handle;
   std::string path;
   bool overridden = false;      // chosen by --backend or $FFH_BACKEND_LIB rather than the product default: the driver says so on its THROUGHPUT line

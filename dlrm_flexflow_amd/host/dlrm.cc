@@ -517,6 +517,7 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
   // which learning-rate route runs, and why; silent without the flags
   if (chatty && (ffconfig.lr_warmup_steps || ffconfig.lr_num_decay_steps || ffconfig.lr_decay_start_step || ffconfig.device_lr || ffconfig.host_lr_schedule))
     printf("[DLRM] lr schedule: %s\n", ff->lr_schedule_line().c_str());
+  if (chatty && ff->q8_on() && !ff->embeddings.empty()) printf("[DLRM] eval tables: %s\n", ff->q8_line().c_str());      // what --eval-embedding-dtype int8 allocated on this rank
   if (chatty && ffconfig.embedding_dtype == DT_BF16) {
     // what --embedding-dtype bf16 did: data-parallel (replicated) tables live in the dense slab and stay fp32
     size_t bytes = 0;

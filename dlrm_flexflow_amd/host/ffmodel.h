@@ -178,6 +178,7 @@ class FFConfig {
   bool force_exchange;         // run the all-to-all / all-reduce path even with one rank (tests the collectives on 1 GPU)
   DataType embedding_dtype;    // --embedding-dtype fp32|bf16: storage of the tables the fused update owns (table-wise; compile() refuses sharded ones); DT_FLOAT or DT_BF16
   int embedding_rounding;      // --embedding-rounding stochastic|nearest: FFH_BF16_ROUND_STOCHASTIC / _NEAREST (include/ffh_bf16.h) of the bf16 table update
+  int eval_embedding_dtype;    // --eval-embedding-dtype fp32|int8: 0 (the bits of before) or 1: eval_batch() gathers from 8-bit row images of the tables (include/ff_hip_q8.h)
   // learning-rate schedule (include/ff_hip_lr.h): linear warm-up over lr_warmup_steps, then the optimizer's rate, then a quadratic
   // decay over lr_num_decay_steps from lr_decay_start_step on; all 0: the constant rate of before
   int64_t lr_warmup_steps, lr_decay_start_step, lr_num_decay_steps;   // --lr-num-warmup-steps / --lr-decay-start-step / --lr-num-decay-steps
@@ -449,6 +450,8 @@ class Embedding : public Op {
   float* opt_state[2] = {nullptr, nullptr};   // --sparse-embedding-optimizer: per-row state of this rank's slice (SGD momentum: V; Adam: M, V)
   bool held_here(int rank) const { return owner_rank == rank || column_sharded || row_sharded || replicated; }
   bool bf16_weights() const { return weights[0].data_type == DT_BF16; }   // --embedding-dtype bf16: 16-bit storage (include/ff_hip_bf16.h)
+  uint8_t* q8_rows = nullptr;   // --eval-embedding-dtype int8: [num_entries][q8_row_bytes] image of the table for evaluation (include/ff_hip_q8.h), or null
+  int64_t q8_row_bytes = 0;
 };
 
 class Concat : public Op {
@@ -727,6 +730,19 @@ class FFModel {
   mutable int64_t n_ragged_early_sorts = 0;   // ... those of them that were ffh_embedding_bwd_sort_multi_bags calls ("ragged_early_sorts")
   mutable int64_t n_ragged_gathers = 0;       // ffh_embedding_fwd_multi_bags[_bf16] launches (tests: flexflow_model_get_counter "ragged_gather_launches")
   bool mixed_bags = false;                    // the tables' bag sizes differ (allocate()): DESIGN section 19
+  // --eval-embedding-dtype int8 (include/ff_hip_q8.h): one 8-bit row image per table this rank gathers (Embedding::q8_rows; the
+  // tables folded into the first top layer keep their fp32 path).  Derived state: stale after compile() and after whatever writes a table (a step, a
+  // replayed trace, or a host-side write of a table that has an image -- an initializer, Tensor::set, load_checkpoint: note_weight_write); the first eval_batch() that finds them stale re-quantizes before its forward pass.
+  // Written on the model's calling thread only (backward / update / eval_batch / note_weight_write); the launch workers never touch it.
+  mutable bool q8_stale = true;
+  mutable int64_t n_q8_quantize = 0, n_q8_gathers = 0;      // tests: flexflow_model_get_counter "q8_quantize_launches" / "q8_gather_launches"
+  size_t q8_bytes = 0, q8_table_bytes = 0;    // bytes of the images, and of the tables they were made from
+  int q8_folded = 0;                          // tables left out because the fold reads them
+  bool q8_on() const { return config.eval_embedding_dtype == 1; }
+  void q8_check_destinations() const;         // compile(), before anything is allocated: every gather destination is in the 16-byte form, from the layer structure
+  void q8_allocate();                         // compile(), behind allocate(): the images
+  void q8_quantize(ffh_stream s, ffh_ctx* cx) const;      // every image from its table: one launch per group of <= FFH_MAX_TABLES tables of one width and storage
+  std::string q8_line() const;                // the driver's start-up line
   mutable int64_t n_ragged_updates = 0;       // ffh_embedding_bwd_fused_multi_bags calls (tests: flexflow_model_get_counter "ragged_update_launches")
   bool ragged_update_on() const;              // the tables' bag sizes differ and their fused update is the ragged call (the library has it, the flag allows it)
   bool ragged_early_sort_on() const;          // ... and --early-sort asks for its sort behind the gather, with a library that has the pair (include/ff_hip_bags_sort.h)

@@ -46,6 +46,10 @@ void flexflow_config_set_embedding_rounding(flexflow_config_t h, int mode) {
   if (mode != 0 && mode != 1) { fprintf(stderr, "FATAL: embedding rounding %d: 0 (stochastic) or 1 (nearest)\n", mode); abort(); }
   C(h)->embedding_rounding = mode;
 }
+void flexflow_config_set_eval_embedding_dtype(flexflow_config_t h, int int8) {
+  if (int8 != 0 && int8 != 1) { fprintf(stderr, "FATAL: evaluation embedding type %d: 0 (fp32) or 1 (int8)\n", int8); abort(); }
+  C(h)->eval_embedding_dtype = int8;
+}
 void flexflow_config_set_lr_schedule(flexflow_config_t h, int64_t warmup_steps, int64_t decay_start_step, int64_t num_decay_steps, int device_lr) {
   C(h)->lr_warmup_steps = warmup_steps; C(h)->lr_decay_start_step = decay_start_step; C(h)->lr_num_decay_steps = num_decay_steps;
   C(h)->device_lr = device_lr == 1;
@@ -176,7 +180,9 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   if (n == "early_sorts") return M(m)->n_early_sorts;
   if (n == "ragged_early_sorts") return M(m)->n_ragged_early_sorts;      // ffh_embedding_bwd_sort_multi_bags calls among them (include/ff_hip_bags_sort.h)
   if (n == "ragged_update_launches") return M(m)->n_ragged_updates;      // ffh_embedding_bwd_fused_multi_bags calls (mixed bag sizes; include/ff_hip_bags_update.h)
-  if (n == "ragged_gather_launches") return M(m)->n_ragged_gathers;      // ffh_embedding_fwd_multi_bags[_bf16] launches (mixed bag sizes; include/ff_hip_bags.h)
+  if (n == "q8_quantize_launches") return M(m)->n_q8_quantize;      // ffh_embedding_quantize_q8 launches (--eval-embedding-dtype int8; include/ff_hip_q8.h)
+  if (n == "q8_gather_launches") return M(m)->n_q8_gathers;         // ffh_embedding_fwd_multi[_bags]_q8 launches
+  if (n == "ragged_gather_launches") return M(m)->n_ragged_gathers;     // ffh_embedding_fwd_multi_bags[_bf16] launches (mixed bag sizes; include/ff_hip_bags.h)
   if (n == "lr_steps") return M(m)->lr_steps();
   if (n == "lr_route") return M(m)->lr_route;          // 0 off (the scalar launches of before), 1 host, 2 device
   if (n == "graph_replays") return M(m)->n_graph_replays;

@@ -57,6 +57,8 @@ void flexflow_config_set_ragged_update(flexflow_config_t, bool);
  * mode 0 stochastic (default) or 1 nearest even (include/ffh_bf16.h).  Other values abort. */
 void flexflow_config_set_embedding_dtype(flexflow_config_t, int data_type);
 void flexflow_config_set_embedding_rounding(flexflow_config_t, int mode);
+/* --eval-embedding-dtype: 0 fp32 (default), 1 int8: eval_batch() gathers from 8-bit row images of the tables (include/ff_hip_q8.h).  Other values abort. */
+void flexflow_config_set_eval_embedding_dtype(flexflow_config_t, int int8);
 /* learning-rate schedule (include/ff_hip_lr.h): warm-up steps W, decay start step S, decay steps N (all 0: the constant rate); device_lr: 1 = the rate lives
  * in device memory (--device-lr), -1 = force the host route (--host-lr-schedule), 0 = compile() chooses.  compile() refuses bad values, naming the flag. */
 void flexflow_config_set_lr_schedule(flexflow_config_t, int64_t warmup_steps, int64_t decay_start_step, int64_t num_decay_steps, int device_lr);

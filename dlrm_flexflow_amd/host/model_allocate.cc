@@ -153,6 +153,36 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
       default: die("metrics type %d is not on the DLRM path", (int)m);
     }
   }
+  // --eval-embedding-dtype int8 (include/ff_hip_q8.h): eval_batch() gathers table-wise tables from 8-bit row images; every case
+  // that does not cover is refused here, each with the flag to drop -- before the library checks: a library without the extensions shows them too.
+  // (The gather destinations' 16-byte form follows from the layer structure: q8_check_destinations().)
+  if (q8_on() && !embeddings.empty()) {
+    if (!want_auc && config.eval_batches <= 0)
+      die("--eval-embedding-dtype int8 is read by held-out evaluation only, and this run has none: add --eval-batches N (METRICS_AUC), or drop "
+          "--eval-embedding-dtype int8");
+    for (const Embedding* e : embeddings) {
+      if (e->row_sharded)
+        die("--eval-embedding-dtype int8: %s is row-sharded; the 8-bit row images are built for table-wise tables: drop --row-shard-rows or drop "
+            "--eval-embedding-dtype int8", e->name);
+      if (e->column_sharded)
+        die("--eval-embedding-dtype int8: %s is column-sharded (a rank would hold part of every row, and a row's scale is taken over the whole row): drop "
+            "--column-shard-rows or drop --eval-embedding-dtype int8", e->name);
+      if (e->replicated)
+        die("--eval-embedding-dtype int8: %s is replicated (data-parallel tables live in the dense slab and are gathered apart): drop "
+            "--replicate-embedding-rows or drop --eval-embedding-dtype int8", e->name);
+    }
+    if (config.dense_embedding_update)
+      die("--eval-embedding-dtype int8 follows the fused sparse table update (the dense path updates the tables on the compute stream): drop "
+          "--dense-embedding-update or drop --eval-embedding-dtype int8");
+    for (const Embedding* e : embeddings)
+      if (e->out_channels % 4)
+        die("--eval-embedding-dtype int8: %s is %d columns wide; a lane reads four 8-bit codes at a time, so the width must be a multiple of 4: change "
+            "--arch-sparse-feature-size or drop --eval-embedding-dtype int8", e->name, e->out_channels);
+    q8_check_destinations();
+    if (!api->q8)
+      die("--eval-embedding-dtype int8: %s (%s) is a kernel library without the q8 extension (include/ff_hip_q8.h); drop --eval-embedding-dtype int8, or "
+          "use another --backend", api->path.c_str(), api->ffh_backend_name());
+  }
   // binary cross-entropy and evaluation (include/ff_hip_ctr.h): refused here, before anything is allocated or launched
   if (bce || want_auc || (metrics_flags & FFH_METRIC_BCE)) {
     const char* what = bce ? "--loss bce" : (want_auc ? "METRICS_AUC" : "METRICS_BINARY_CROSSENTROPY");
@@ -268,6 +298,7 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
   // all-reduce) -- or, with --sparse-embedding-optimizer, the touched-rows rule on the sorted segments with per-row state
   // (ffh_sparse_opt).  Data-parallel (replicated) tables live in the dense slab and follow the MLP's optimizer launch either way.
   allocate();
+  if (q8_on() && !embeddings.empty()) q8_allocate();
   for (Op* op : layers) {
     if (Linear* li = dynamic_cast<Linear*>(op)) {
       if (li->in_padded != li->in_channels) {

@@ -26,7 +26,11 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
   // where it has the ragged update (include/ff_hip_bags_update.h) and --ragged-update allows it, and for the sort-only / apply-only pair where the
   // ragged early sort is on (include/ff_hip_bags_sort.h, FFModel::ragged_early_sort_on).
   const bool ragged = fwd ? ff->ragged_gather_on() : (what == kFusedUpdate ? ff->ragged_update_on() : ff->ragged_early_sort_on());
-  struct Group { std::vector<ffh_emb_table> t; std::vector<ffh_emb_table_bf16> t16; std::vector<ffh_emb_state> st; std::vector<int> bag; };
+  struct Group { std::vector<ffh_emb_table> t; std::vector<ffh_emb_table_bf16> t16; std::vector<ffh_emb_state> st; std::vector<int> bag;
+                 std::vector<ffh_emb_table_q8> tq; std::vector<int> bagq; };      // tq, bagq: the tables an evaluation gathers from their 8-bit row images
+  // --eval-embedding-dtype int8: the gather of eval_batch() reads the images (include/ff_hip_q8.h), in the same groups.  eval_batch() has made stale images
+  // again before it issued this forward pass (on the calling thread: this function may run on a launch worker, and reads the images' addresses only)
+  const bool q8 = fwd && ff->evaluating && ff->q8_on() && !idx_override && !all_tables;
   std::map<std::tuple<int, bool, int>, Group> groups;
   size_t owned_i = 0;
   for (const FFModel::EmbShard& sh : ff->shards) {
@@ -48,6 +52,11 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
     }
     const int bag = e->inputs[0].adim[0];
     Group& g = groups[std::make_tuple(sh.cols, e->bf16_weights(), ragged ? 0 : bag)];
+    if (q8 && e->q8_rows) {
+      g.tq.push_back(ffh_emb_table_q8{t.idx, e->q8_rows, t.io, t.num_entries, t.ld, e->q8_row_bytes});
+      g.bagq.push_back(bag);
+      continue;
+    }
     if (e->bf16_weights()) g.t16.push_back(ffh_emb_table_bf16{t.idx, (uint16_t*)t.weight, t.io, t.num_entries, t.ld, e->table_index, sh.col0});
     else g.t.push_back(t);
     g.st.push_back(ffh_emb_state{e->opt_state[0], e->opt_state[1]});
@@ -78,6 +87,14 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
       else ff->check(ff->api->bags_update->ffh_embedding_bwd_fused_multi_bags(cx, &u, s), "embedding_bwd_fused_multi_bags");
       ff->n_ragged_updates++;
     };
+    for (size_t b = 0; b < g.tq.size(); b += FFH_MAX_TABLES) {      // (evaluation with --eval-embedding-dtype int8 only)
+      const int n = (int)std::min<size_t>(FFH_MAX_TABLES, g.tq.size() - b);
+      bool mixed = false;
+      for (int i = 1; i < n; i++) mixed = mixed || g.bagq[b + i] != g.bagq[b];
+      if (ragged && mixed) ff->check(ff->api->q8->ffh_embedding_fwd_multi_bags_q8(cx, g.tq.data() + b, g.bagq.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags_q8");
+      else ff->check(ff->api->q8->ffh_embedding_fwd_multi_q8(cx, g.tq.data() + b, n, g.bagq[b], D, B, aggr, s), "embedding_fwd_multi_q8");
+      ff->n_q8_gathers++;
+    }
     if (std::get<1>(kv.first)) {
       const KernelApiBf16* b16 = ff->api->bf16;
       const ffh_bf16_rounding rnd = ff->bf16_rounding();
@@ -143,6 +160,92 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
       }
     }
   }
+}
+
+// =============================================================================================
+// --eval-embedding-dtype int8 (include/ff_hip_q8.h)
+// =============================================================================================
+// where this rank's gather of shard `sh` writes (launch_shard_groups, kGather)
+static void gather_dest(const FFModel* ff, const FFModel::EmbShard& sh, float** io, int64_t* ld) {
+  if (!ff->exchange) { *io = (float*)sh.e->outputs[0].impl->ptr; *ld = sh.e->outputs[0].impl->ld; }
+  else { *io = ff->xsend + sh.off; *ld = ff->rank_width[ff->rank]; }
+}
+
+// Where allocate() will put a table's gathered rows, from the layer structure alone (its step 4): a table whose output is read only by one feature-axis
+// Concat writes straight into the Concat's buffer, at the column where its input starts, with the Concat's width as leading dimension; any other table
+// owns rows of its own width.  Through the exchange buffers a rank's tables lie side by side, each at a multiple of the (checked) table widths.  Buffers
+// start 16-byte aligned, so the 16-byte form holds iff that column and that width are multiples of 4 floats.
+void FFModel::q8_check_destinations() const {
+  if (exchange) return;
+  std::map<const TensorImpl*, int> consumers;
+  for (const Op* op : layers)
+    for (int i = 0; i < op->numInputs; i++) consumers[op->inputs[i].impl]++;
+  std::set<const TensorImpl*> placed;
+  for (const Op* op : layers) {
+    const Concat* c = dynamic_cast<const Concat*>(op);
+    if (!c || c->axis != 0) continue;
+    int64_t width = 0;
+    for (int i = 0; i < c->numInputs; i++) width += c->inputs[i].adim[0];
+    int64_t off = 0;
+    for (int i = 0; i < c->numInputs; i++) {
+      const Tensor& in = c->inputs[i];
+      if (in.owner_op && in.owner_op->op_type == OP_EMBEDDING && consumers[in.impl] == 1 && placed.insert(in.impl).second && (off % 4 || width % 4))
+        die("--eval-embedding-dtype int8: the gather of %s writes columns %lld.. of a %lld-column Concat, rows that are not 16-byte aligned, and the 8-bit "
+            "gather has no scalar form: make the widths in front of it and the Concat's width multiples of 4 (--arch-mlp-bot, --arch-sparse-feature-size), or "
+            "drop --eval-embedding-dtype int8", in.owner_op->name, (long long)off, (long long)width);
+      off += in.adim[0];
+    }
+  }
+}
+
+void FFModel::q8_allocate() {
+  q8_bytes = q8_table_bytes = 0;
+  q8_folded = 0;
+  for (const EmbShard& sh : shards) {
+    if (sh.owner != rank) continue;
+    Embedding* e = sh.e;
+    if (std::find(fold.tables.begin(), fold.tables.end(), e) != fold.tables.end()) { q8_folded++; continue; }      // read as products of the fp32 table: its path is kept
+    float* io; int64_t ld;
+    gather_dest(this, sh, &io, &ld);
+    if (((uintptr_t)io & 15) || ld % 4)
+      die("--eval-embedding-dtype int8: the gather of %s writes rows that are not 16-byte aligned (leading dimension %lld floats), which q8_check_destinations() "
+          "did not foresee: drop --eval-embedding-dtype int8", e->name, (long long)ld);
+  }
+  for (const EmbShard& sh : shards) {
+    if (sh.owner != rank) continue;
+    Embedding* e = sh.e;
+    if (std::find(fold.tables.begin(), fold.tables.end(), e) != fold.tables.end()) continue;
+    e->q8_row_bytes = (int64_t)api->q8->ffh_q8_row_bytes(e->out_channels);
+    const size_t bytes = (size_t)e->num_entries * (size_t)e->q8_row_bytes;
+    e->q8_rows = (uint8_t*)dmalloc(bytes);
+    q8_bytes += bytes;
+    q8_table_bytes += (size_t)e->num_entries * e->out_channels * (e->bf16_weights() ? 2 : 4);
+  }
+  q8_stale = true;
+}
+
+void FFModel::q8_quantize(ffh_stream s, ffh_ctx* cx) const {
+  std::map<std::pair<int, bool>, std::vector<ffh_q8_source>> groups;      // by width and storage
+  for (const EmbShard& sh : shards) {
+    const Embedding* e = sh.e;
+    if (sh.owner != rank || !e->q8_rows) continue;
+    groups[{e->out_channels, e->bf16_weights()}].push_back(ffh_q8_source{e->weights[0].impl->ptr, e->q8_rows, e->num_entries, e->q8_row_bytes, e->bf16_weights() ? 1 : 0, 0});
+  }
+  for (const auto& kv : groups)
+    for (size_t b = 0; b < kv.second.size(); b += FFH_MAX_TABLES) {
+      const int n = (int)std::min<size_t>(FFH_MAX_TABLES, kv.second.size() - b);
+      check(api->q8->ffh_embedding_quantize_q8(cx, kv.second.data() + b, n, kv.first.first, s), "embedding_quantize_q8");
+      n_q8_quantize++;
+    }
+  q8_stale = false;
+}
+
+std::string FFModel::q8_line() const {
+  int64_t rb = 0;
+  for (const Embedding* e : embeddings) if (e->q8_rows) { rb = e->q8_row_bytes; break; }
+  char buf[200];
+  snprintf(buf, sizeof buf, "int8 rows (row_bytes %lld), %zu bytes beside %zu bytes of tables, %d folded tables keep fp32", (long long)rb, q8_bytes, q8_table_bytes, q8_folded);
+  return buf;
 }
 
 bool FFModel::ragged_gather_on() const { return mixed_bags && config.ragged_gather && api->bags; }
@@ -224,6 +327,7 @@ uint64_t FFModel::read_bf16_counter() const {
 void FFModel::embedding_kernels_only(bool fwd, ffh_stream s, const std::vector<const int64_t*>* idx_override) const {
   if (embeddings.empty() || (!fwd && !fused_embedding_update())) return;
   launch_shard_groups(this, fwd ? kGather : kFusedUpdate, s, ctx, idx_override, true);      // (a roofline probe: every table, dx-folded or not)
+  if (!fwd) q8_stale = true;      // (the probe's update writes the tables)
   if (!fwd) advance_bf16_counter(s, ctx);
 }
 

@@ -80,6 +80,7 @@ FFConfig::FFConfig() {
   fp32_split_bf16x3 = false;
   deterministic = false;
   embedding_dtype = DT_FLOAT;
+  eval_embedding_dtype = 0;
   embedding_rounding = FFH_BF16_ROUND_STOCHASTIC;
   lr_warmup_steps = lr_decay_start_step = lr_num_decay_steps = 0;
   device_lr = false;
@@ -206,6 +207,13 @@ void FFConfig::parse_args(char** argv, int argc) {
       if (!strcmp(v, "fp32")) embedding_dtype = DT_FLOAT;
       else if (!strcmp(v, "bf16")) embedding_dtype = DT_BF16;
       else die("--embedding-dtype %s: 'fp32' or 'bf16'", v);
+      continue;
+    }
+    if (is("--eval-embedding-dtype")) {
+      const char* v = next();
+      if (!strcmp(v, "fp32")) eval_embedding_dtype = 0;
+      else if (!strcmp(v, "int8")) eval_embedding_dtype = 1;
+      else die("--eval-embedding-dtype %s: 'fp32' or 'int8'", v);
       continue;
     }
     if (is("--lr-num-warmup-steps")) { lr_warmup_steps = atoll(next()); continue; }

@@ -37,6 +37,11 @@ int64_t FFModel::weight_mirror_stale_bytes() {
   return n;
 }
 void FFModel::note_weight_write(const void* p) const {
+  // --eval-embedding-dtype int8: every host-side write of a tensor (initializers, set(), the checkpoint loader) passes here.  Only a write of a table
+  // that has an image leaves the images behind: set() on an input or a label between eval_batch() calls must not cost a quantizer pass per batch
+  // (before compile() has allocated the images they are stale anyway)
+  for (const Embedding* e : embeddings)
+    if (e->q8_rows && e->weights[0].impl && p == e->weights[0].impl->ptr) { q8_stale = true; break; }
   if (w_twin && (const char*)p >= (const char*)mlp_weights && (const char*)p < (const char*)(mlp_weights + mlp_count)) w_twin_dirty = true;
 }
 
@@ -303,6 +308,7 @@ void FFModel::compute_metrics() {
 }
 
 void FFModel::backward(int _seq_length) {
+  q8_stale = true;               // the table update may start from here (a replayed step: the graph holds it)
   if (replaying_trace >= 0) return;
   seq_length = _seq_length;
   if (config.computationMode != COMP_MODE_TRAINING) die("backward() in inference mode");
@@ -457,6 +463,7 @@ void FFModel::backward(int _seq_length) {
 
 void FFModel::update() {
   n_update_calls++;              // (a replayed step counts: its update is in the graph)
+  q8_stale = true;               // ... and so the 8-bit row images of the tables are behind (--eval-embedding-dtype int8)
   if (replaying_trace >= 0) return;
   optimizer->next();
   opt_next_done = true;
@@ -697,6 +704,13 @@ void FFModel::eval_batch() {
   // batch was just written there, and a replayed step joins its table update into `stream`), and no early sort is issued (it would
   // leave a sorted list of THESE ids in the workspace for the next training step's apply phase).  Nothing else a step carries across its
   // boundary is touched: gradients, the optimizer's step count, the bf16 rounding counter, the captured graphs.
+  // --eval-embedding-dtype int8: images that a step, a set() or a load has left behind their tables are made again here, on the calling thread.  sync()
+  // drains the launch workers and every stream, so `stream` stands behind the last write of every table; the gather (this stream, or the side stream
+  // behind the fork event that inputs_dirty makes forward() record) stands behind the quantizer.  Once per evaluation after training, not per batch.
+  if (q8_on() && q8_stale && !embeddings.empty()) {
+    sync();
+    q8_quantize(stream, ctx);
+  }
   evaluating = true;
   inputs_dirty = true;
   forward();
