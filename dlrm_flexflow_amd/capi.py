@@ -1198,6 +1198,97 @@ def bags_sort_api(lib: "FFHLib") -> BagsSortApi:
     return BagsSortApi(lib)
 
 
+# ---- the pad extension (include/ff_hip_pad.h): variable-length bags, the id EMB_PAD_ID being "no lookup" ---------------------------------
+PAD_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_pad.h")
+EMB_PAD_ID = -1
+
+_SIGS_PAD = {
+    "ffh_pad_abi_version": (I, []),
+    "ffh_embedding_fwd_multi_bags_pad": (I, [P, C.POINTER(EmbTable), C.POINTER(I), I, I, L, I, P]),
+    "ffh_embedding_fwd_multi_bags_pad_bf16": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(I), I, I, L, I, P]),
+    "ffh_embedding_bwd_fused_multi_bags_pad": (I, [P, C.POINTER(BagsUpdate), P]),
+    "ffh_embedding_bwd_sort_multi_bags_pad": (I, [P, C.POINTER(BagsUpdate), P]),
+    "ffh_embedding_bwd_apply_multi_bags_pad": (I, [P, C.POINTER(BagsUpdate), P]),
+    "ffh_pad_mask_indices": (I, [P, P, L, C.c_uint64, L, F, P]),
+}
+
+
+def pad_header_symbols(header_path: str = PAD_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_PAD_API_LIST X-macro in include/ff_hip_pad.h."""
+    m = re.search(r"#define FFH_PAD_API_LIST\(X\)(.*?)\n\n", open(header_path).read(), re.S)
+    if not m:
+        raise RuntimeError("FFH_PAD_API_LIST not found in " + header_path)
+    return re.findall(r"X\((\w+)\)", m.group(1))
+
+
+def pad_header_abi_version(header_path: str = PAD_HEADER_PATH) -> int:
+    """FFH_PAD_ABI_VERSION of include/ff_hip_pad.h."""
+    m = re.search(r"#define\s+FFH_PAD_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_PAD_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
+class PadApi:
+    """The pad extension (include/ff_hip_pad.h) of a loaded FFHLib; `pad_api(lib)` builds it or raises.  The gathers take the arguments of
+    BagsApi.rc, the update entries the descriptor of the ragged update (BagsUpdateApi.descriptor)."""
+
+    def __init__(self, lib: "FFHLib"):
+        self.base = lib
+        for name, (res, args) in _SIGS_PAD.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no pad extension ({name} missing; include/ff_hip_pad.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_pad_abi_version()
+        if got != pad_header_abi_version():
+            raise FFHError(f"{lib.path}: pad ABI version {got}, include/ff_hip_pad.h says {pad_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+    def fwd_rc(self, tables, in_dims, ntables: int, out_dim: int, batch: int, aggr: int, bf16: bool = False, stream=None) -> int:
+        """ffh_embedding_fwd_multi_bags_pad[_bf16], returning its status code; `in_dims` from BagsApi.in_dims (or None: a null pointer)."""
+        fn = self.lib.ffh_embedding_fwd_multi_bags_pad_bf16 if bf16 else self.lib.ffh_embedding_fwd_multi_bags_pad
+        return fn(self.ctx, tables, in_dims, int(ntables), int(out_dim), int(batch), int(aggr), ptr(stream))
+
+    def fwd(self, *args, **kw):
+        self.base.check(self.fwd_rc(*args, **kw), "ffh_embedding_fwd_multi_bags_pad")
+
+    def _u(self, name: str, u: BagsUpdate | None, stream) -> int:
+        return getattr(self.lib, name)(self.ctx, C.byref(u) if u is not None else None, ptr(stream))
+
+    def fused_rc(self, u: BagsUpdate | None, stream=None) -> int:
+        return self._u("ffh_embedding_bwd_fused_multi_bags_pad", u, stream)
+
+    def sort_rc(self, u: BagsUpdate | None, stream=None) -> int:
+        return self._u("ffh_embedding_bwd_sort_multi_bags_pad", u, stream)
+
+    def apply_rc(self, u: BagsUpdate | None, stream=None) -> int:
+        return self._u("ffh_embedding_bwd_apply_multi_bags_pad", u, stream)
+
+    def fused(self, u: BagsUpdate, stream=None):
+        self.base.check(self.fused_rc(u, stream), "ffh_embedding_bwd_fused_multi_bags_pad")
+
+    def sort(self, u: BagsUpdate, stream=None):
+        self.base.check(self.sort_rc(u, stream), "ffh_embedding_bwd_sort_multi_bags_pad")
+
+    def apply(self, u: BagsUpdate, stream=None):
+        self.base.check(self.apply_rc(u, stream), "ffh_embedding_bwd_apply_multi_bags_pad")
+
+    def mask_rc(self, idx, count: int, seed: int, first: int, fill: float, stream=None) -> int:
+        """ffh_pad_mask_indices on a device buffer of int64 ids, returning its status code."""
+        return self.lib.ffh_pad_mask_indices(self.ctx, ptr(idx), int(count), int(seed) & (2**64 - 1), int(first), float(fill), ptr(stream))
+
+    def mask(self, *args, **kw):
+        self.base.check(self.mask_rc(*args, **kw), "ffh_pad_mask_indices")
+
+
+def pad_api(lib: "FFHLib") -> PadApi:
+    """The pad entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
+    return PadApi(lib)
+
+
 # ---- the q8 extension (include/ff_hip_q8.h): tables as 8-bit rows with a scale and a bias each; a quantizer and the gathers that read them ----
 Q8_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_q8.h")
 

@@ -2,7 +2,8 @@
 // of the sort kernels (emb_sort.h) and of the apply phase's kernels (emb_reduce.h).  Every table keeps its own geometry -- N_t = batch * L_t
 // entries, its own share of the key buffers, histogram matrix, level-0 / level-1 slots and arrival counters, its own nchunks / nchunks1 --
 // and the arithmetic is the uniform kernels' device bodies (reduce_tile_body, fold_table_body, sort_scan_offsets, sort_rank_and_scatter, the
-// row rules), so a table ends with the bits of its own uniform call.  Nothing here is reached by the uniform entries.
+// row rules), so a table ends with the bits of its own uniform call.  Nothing here is reached by the uniform entries.  The kernels' PAD forms
+// (include/ff_hip_pad.h: an id < 0 is no lookup) are instantiated only for the pad entries; with PAD = false a kernel is what it was.
 // Included by the two translation units that instantiate the kernels (embedding_update_bags_f32.hip / _bf16.hip) and by embedding.hip for the
 // argument structs and the geometry.
 #pragma once
@@ -75,6 +76,7 @@ struct BagsSortArgs {
   uint32_t* clear[2];
   uint8_t   npass[FFH_MAX_TABLES];      // digits table t really has
   BagsGeo   g;
+  uint32_t  padkey[FFH_MAX_TABLES];     // the pad forms' pass 0 (include/ff_hip_pad.h): an id < 0 sorts as this key, the table's num_entries
 };
 
 struct BagsRedArgs {
@@ -115,7 +117,14 @@ namespace {
 // ---------------------------------------------------------------------------
 // sort: radix_hist_kernel / radix_scatter_kernel (emb_sort.h) on the flat map
 // ---------------------------------------------------------------------------
-template <bool FIRST, int E>
+// PAD (pass 0 only; include/ff_hip_pad.h): an id < 0 is no lookup and sorts as the table's largest key, padkey[t] = num_entries
+template <bool PAD>
+__device__ __forceinline__ uint32_t bags_first_key(const int64_t id, const uint32_t padkey) {
+  if (PAD) return id < 0 ? padkey : (uint32_t)id;
+  return (uint32_t)id;
+}
+
+template <bool FIRST, int E, bool PAD = false>
 __global__ __launch_bounds__(kSortThreads) void bags_radix_hist_kernel(const BagsSortArgs a) {
   ffh_kernel_prio();
   constexpr int kSortTile = kSortThreads * E;
@@ -140,14 +149,14 @@ __global__ __launch_bounds__(kSortThreads) void bags_radix_hist_kernel(const Bag
 #pragma unroll
   for (int e = 0; e < E; e++) {
     const int64_t i = tile0 + e * kSortThreads + threadIdx.x;
-    if (i < at.N) atomicAdd(&s_hist[((FIRST ? (uint32_t)idx[i] : src[i].x) >> a.shift) & mask], 1u);
+    if (i < at.N) atomicAdd(&s_hist[((FIRST ? bags_first_key<PAD>(idx[i], a.padkey[t]) : src[i].x) >> a.shift) & mask], 1u);
   }
   __syncthreads();
   uint32_t* out = a.hist + (at.sblk0 + at.local) * radix;
   for (int d = threadIdx.x; d < radix; d += kSortThreads) out[d] = s_hist[d];
 }
 
-template <bool FIRST, int E>
+template <bool FIRST, int E, bool PAD = false>
 __global__ __launch_bounds__(kSortThreads) void bags_radix_scatter_kernel(const BagsSortArgs a) {
   ffh_kernel_prio();
   constexpr int kSortTile = kSortThreads * E;
@@ -178,7 +187,7 @@ __global__ __launch_bounds__(kSortThreads) void bags_radix_scatter_kernel(const 
     const int64_t i = tile0 + wave * (kSortTile / 4) + e * 64 + lane;
     valid[e] = i < at.N;
     if (FIRST) {
-      key[e] = valid[e] ? (uint32_t)idx[i] : 0u;
+      key[e] = valid[e] ? bags_first_key<PAD>(idx[i], a.padkey[t]) : 0u;
       pos[e] = (uint32_t)i;
     } else {
       const uint2 kp = valid[e] ? src[i] : make_uint2(0u, 0u);
@@ -221,7 +230,7 @@ __global__ __launch_bounds__(kSortThreads) void bags_radix_scatter_kernel(const 
 // records go out written through and completed before it counts itself in; the last tile of a 1024-block folds the block, the last folded
 // block of a table folds the table.  No workgroup waits for another.
 // ---------------------------------------------------------------------------
-template <int VEC, RowRule R, class WT, bool LRP>
+template <int VEC, RowRule R, class WT, bool LRP, bool PAD = false>
 __global__ __launch_bounds__(kRedThreads, (red_waves_per_simd<VEC, R, WT, false>())) void emb_bags_reduce_kernel(const BagsRedArgs a) {
   ffh_kernel_prio();
   FFH_OPT_OF(LRP, op, a.op);
@@ -243,7 +252,7 @@ __global__ __launch_bounds__(kRedThreads, (red_waves_per_simd<VEC, R, WT, false>
   float* const st0 = opt_state(R) ? a.s0[tix] : nullptr;
   float* const st1 = state1_of<R, WT>(a, tix);
   const SrKey sk = sr_key<R, WT>(a, tix);
-  reduce_tile_body<VEC, true, R, WT>(tb, keys, p0, m0, N, nchunks, tile, (int)at.local, L, a.D, a.avg != 0, op, st0, st1, sk, sh, threadIdx.x, false);
+  reduce_tile_body<VEC, true, R, WT, PAD>(tb, keys, p0, m0, N, nchunks, tile, (int)at.local, L, a.D, a.avg != 0, op, st0, st1, sk, sh, threadIdx.x, false);
 
   const int nvec = a.D / VEC;
   const int lpr = nvec < 64 ? nvec : 64;
@@ -301,7 +310,7 @@ __global__ __launch_bounds__(kRedThreads, (red_waves_per_simd<VEC, R, WT, false>
 // apply, small route (every N_t <= kSmallMax): emb_sgd_small_kernel with the table's own N_t -- sort, reduce and folds of a table in its
 // one workgroup
 // ---------------------------------------------------------------------------
-template <int VEC, RowRule R, class WT, bool LRP>
+template <int VEC, RowRule R, class WT, bool LRP, bool PAD = false>
 __global__ __launch_bounds__(kSmallThreads) void emb_bags_small_kernel(const BagsSmallArgs a) {
   ffh_kernel_prio();
   FFH_OPT_OF(LRP, op, a.op);
@@ -334,7 +343,7 @@ __global__ __launch_bounds__(kSmallThreads) void emb_bags_small_kernel(const Bag
   for (int e = 0; e < E; e++) {
     const int i = wave * (kSmallMax / NW) + e * 64 + lane;
     valid[e] = i < N;
-    key[e] = valid[e] ? (uint32_t)tb.idx[i] : 0u;
+    key[e] = valid[e] ? bags_first_key<PAD>(tb.idx[i], (uint32_t)tb.num_entries) : 0u;
     pos[e] = (uint32_t)i;
   }
   const int npass = a.npass[tix];
@@ -381,7 +390,7 @@ __global__ __launch_bounds__(kSmallThreads) void emb_bags_small_kernel(const Bag
   const int team = threadIdx.x / kRedThreads, ttid = threadIdx.x % kRedThreads;
   const int ntiles = (int)((N + tile - 1) / tile);
   for (int t0 = 0; t0 < ntiles; t0 += kSmallRedParts) {
-    reduce_tile_body<VEC, false, R, WT>(tb, keys, p0, m0, N, nch0, tile, t0 + team, L, a.D, a.avg != 0, op, st0, st1, sk, sm.red[team], ttid);
+    reduce_tile_body<VEC, false, R, WT, PAD>(tb, keys, p0, m0, N, nch0, tile, t0 + team, L, a.D, a.avg != 0, op, st0, st1, sk, sm.red[team], ttid);
     __syncthreads();
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -419,16 +428,17 @@ struct BagsUpdateLaunch {
 };
 typedef void (*BagsUpdateFn)(const BagsUpdateLaunch&);
 namespace {
-template <class WT, int I> void launch_bags_small(const BagsUpdateLaunch& u) {
-  hipLaunchKernelGGL((emb_bags_small_kernel<(I >> 1 & 1) ? 4 : 1, (RowRule)(I >> 2), WT, (I & 1) != 0>), u.grid, dim3(kSmallThreads), 0, u.stream, *u.small);
+template <class WT, bool PAD, int I> void launch_bags_small(const BagsUpdateLaunch& u) {
+  hipLaunchKernelGGL((emb_bags_small_kernel<(I >> 1 & 1) ? 4 : 1, (RowRule)(I >> 2), WT, (I & 1) != 0, PAD>), u.grid, dim3(kSmallThreads), 0, u.stream, *u.small);
 }
-template <class WT, int I> void launch_bags_reduce(const BagsUpdateLaunch& u) {
-  hipLaunchKernelGGL((emb_bags_reduce_kernel<(I >> 1 & 1) ? 4 : 1, (RowRule)(I >> 2), WT, (I & 1) != 0>), u.grid, dim3(kRedThreads), 0, u.stream, *u.red);
+template <class WT, bool PAD, int I> void launch_bags_reduce(const BagsUpdateLaunch& u) {
+  hipLaunchKernelGGL((emb_bags_reduce_kernel<(I >> 1 & 1) ? 4 : 1, (RowRule)(I >> 2), WT, (I & 1) != 0, PAD>), u.grid, dim3(kRedThreads), 0, u.stream, *u.red);
 }
-template <class WT, int... I>
+// PAD: the pad forms (include/ff_hip_pad.h), compiled in translation units of their own (embedding_update_pad_f32.hip / _bf16.hip)
+template <class WT, bool PAD, int... I>
 bool emb_bags_update_launch(const BagsUpdateLaunch& u, std::integer_sequence<int, I...>) {
-  static constexpr BagsUpdateFn kSmall[] = {launch_bags_small<WT, I>...};
-  static constexpr BagsUpdateFn kReduce[] = {launch_bags_reduce<WT, I>...};
+  static constexpr BagsUpdateFn kSmall[] = {launch_bags_small<WT, PAD, I>...};
+  static constexpr BagsUpdateFn kReduce[] = {launch_bags_reduce<WT, PAD, I>...};
   const int i = update_index(u.rule, u.v4, u.lrp);
   if (i < 0 || i >= (int)sizeof...(I) || (u.small != nullptr) == (u.red != nullptr)) return false;
   if (u.small) kSmall[i](u); else kReduce[i](u);
@@ -440,5 +450,9 @@ __attribute__((visibility("hidden"))) bool emb_bags_update_launch_f32(const Bags
 __attribute__((visibility("hidden"))) bool emb_bags_update_launch_bf16(const BagsUpdateLaunch& u);     // embedding_update_bags_bf16.hip
 // one pass of the ragged sort (histogram + scatter; `first`: pass 0, which reads the int64 ids), E = entries per thread; embedding_update_bags_f32.hip
 __attribute__((visibility("hidden"))) bool emb_bags_sort_pass(const BagsSortArgs& a, bool first, int E, dim3 grid, hipStream_t stream);
+// the pad forms (include/ff_hip_pad.h): the apply kernels that drop the pad key's segment, and pass 0 of the sort, which loads a pad as that key
+__attribute__((visibility("hidden"))) bool emb_pad_update_launch_f32(const BagsUpdateLaunch& u);       // embedding_update_pad_f32.hip
+__attribute__((visibility("hidden"))) bool emb_pad_update_launch_bf16(const BagsUpdateLaunch& u);      // embedding_update_pad_bf16.hip
+__attribute__((visibility("hidden"))) bool emb_pad_sort_first_pass(const BagsSortArgs& a, int E, dim3 grid, hipStream_t stream);      // embedding_update_pad_f32.hip
 
 }  // namespace ffh_emb

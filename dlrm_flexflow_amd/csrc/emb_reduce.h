@@ -144,7 +144,9 @@ struct RedShared {
 };
 
 // one tile of one table; `partial_t` / `meta_t` are the table's level-0 slot arrays
-template <int VEC, bool AGENT, RowRule R, class WT>
+// PAD (include/ff_hip_pad.h; the ragged kernels' pad forms only): the sort loaded "no lookup" as key tb.num_entries, the largest key.  Its
+// sub-runs are dropped here: no sum, no row, no partial row and no slot record -- the folds walk slot records, so they never see the segment.
+template <int VEC, bool AGENT, RowRule R, class WT, bool PAD = false>
 __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const uint2* kp,
                                                  float* partial_t, uint2* meta_t, int64_t N, int nchunks, int tile, int tile_index,
                                                  int L, int D_, bool avg_, const OptP& op, float* st0, float* st1, const SrKey& sk, RedShared& sh, const int tid = threadIdx.x,
@@ -223,6 +225,9 @@ __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const 
     for (int k = gid; k < S; k += groups) {
       const int s = s_start[k], e = s_start[k + 1];
       const uint32_t key = s_key[1 + s];
+      if constexpr (PAD) {
+        if (key == (uint32_t)tb.num_entries) continue;
+      }
       const bool head = (s_key[s] != key) || (s == 0 && at_table_start);
       const bool tail = (s_key[1 + e] != key) || (tile0 + e >= N);
       const int64_t chunk = (tile0 + s) / FFH_EMB_CHUNK;

@@ -8,7 +8,8 @@
 //   * the plan of a call, for both updates: radix_plan, fill_passes, sort_per_thread, reduce_tile,
 //     ws_layout (bwd_layout, bags_layout), UpdatePlan, set_rule_args, set_ws_slots;
 //   * emb_bwd_phases: the update with one bag size; emb_sort_full: its sort alone (fold_sum.hip);
-//   * emb_bwd_bags: the update with a bag size per table (include/ff_hip_bags_update.h), whole or in its two phases (include/ff_hip_bags_sort.h);
+//   * emb_bwd_bags: the update with a bag size per table (include/ff_hip_bags_update.h), whole or in its two phases (include/ff_hip_bags_sort.h),
+//     and its pad form, in which an id < 0 is no lookup (include/ff_hip_pad.h);
 //   * emb_bwd_dense_kernel, emb_localize_kernel, the bf16 init / counter kernels; every entry.
 // What is where:
 //   * the gather: embedding_fwd.hip; checks on a table list shared with it: emb_tables.h;
@@ -22,6 +23,7 @@
 #include "../../include/ff_hip_bags_update.h"
 #include "../../include/ff_hip_bags_sort.h"
 #include "emb_bags_update.h"
+#include "../../include/ff_hip_pad.h"
 
 namespace {
 
@@ -71,9 +73,10 @@ inline RadixPlan radix_plan(int64_t maxR) {
   return RadixPlan{bits, passes, (bits + passes - 1) / passes};
 }
 // a table only runs the passes its own ids need; its sorted list ends in key buffer parity[i]
-inline void fill_passes(const ffh_emb_table* tables, int nt, int rb, uint8_t* npass, uint8_t* parity = nullptr) {
+// (more_keys = 1: the pad form, whose largest key is num_entries itself)
+inline void fill_passes(const ffh_emb_table* tables, int nt, int rb, uint8_t* npass, uint8_t* parity = nullptr, int more_keys = 0) {
   for (int i = 0; i < nt; i++) {
-    const int np = (bit_length(tables[i].num_entries) + rb - 1) / rb;
+    const int np = (bit_length(tables[i].num_entries + more_keys) + rb - 1) / rb;
     npass[i] = (uint8_t)np;
     if (parity) parity[i] = (uint8_t)(np & 1);
   }
@@ -614,7 +617,8 @@ inline int bags_dims_check(const int* in_dims, int nt, int64_t batch) {
 }
 
 typedef bool (*BagsUpdateOfFn)(const BagsUpdateLaunch&);
-constexpr BagsUpdateOfFn kBagsUpdateOf[2] = {emb_bags_update_launch_f32, emb_bags_update_launch_bf16};
+constexpr BagsUpdateOfFn kBagsUpdateOf[2][2] = {{emb_bags_update_launch_f32, emb_bags_update_launch_bf16},      // [pad form][bf16 rows]
+                                                {emb_pad_update_launch_f32, emb_pad_update_launch_bf16}};
 
 // the sort phase alone reads idx and num_entries only (include/ff_hip_bags_sort.h): validate_tables without the weight / io / ld checks
 inline int validate_sort_tables(ffh_ctx* c, const ffh_emb_table* t, int nt, int D, int64_t batch) {
@@ -628,20 +632,26 @@ inline int validate_sort_tables(ffh_ctx* c, const ffh_emb_table* t, int nt, int 
 
 // The ragged update in the two phases of emb_bwd_phases: do_sort && do_apply is the fused entry, do_sort alone and do_apply alone are the pair of
 // include/ff_hip_bags_sort.h.  Same launches in the same order on the same workspace.
+// `pad` (include/ff_hip_pad.h): an id < 0 is no lookup.  Pass 0 of the sort loads it as key num_entries, so the radix plan covers one more key
+// per table, and the apply kernels drop that key's segment; the layout, the grids and the workspace are those of the call without pads.
 int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, int nt, int D, int64_t batch, int aggr, float lr, ffh_stream s,
                  const bool do_sort, const bool do_apply,
-                 const ffh_sparse_opt* opt, const ffh_emb_state* states, const Bf16Cfg* b16, const ffh_lr_state* lr_block) {
+                 const ffh_sparse_opt* opt, const ffh_emb_state* states, const Bf16Cfg* b16, const ffh_lr_state* lr_block, const bool pad) {
   int rc = bags_dims_check(in_dims, nt, batch);
   if (rc == FFH_ERR_BAD_ARG) return ffh_fail(c, rc, "embedding_bwd_fused_multi_bags: ntables out of range, null in_dims or in_dims[i] < 1");
   if (rc) return ffh_fail(c, rc, "embedding_bwd_fused_multi_bags: in_dims[i] > FFH_BAGS_MAX_IN_DIM (65535) or batch*in_dims[i] >= 2^31");
   rc = do_apply ? validate_tables(c, tables, nt, 1, D, batch, aggr) : validate_sort_tables(c, tables, nt, D, batch);
   if (rc) return rc;
+  if (pad && aggr == FFH_AGGR_MODE_AVG)      // (a mean over the lookups that are there needs each bag's count in the apply phase)
+    return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags_pad: FFH_AGGR_MODE_AVG is not supported with pad ids");
   UpdatePlan plan;
   rc = emb_update_rule(c, nt, D, batch, lr, do_apply, opt, states, b16, lr_block, &plan);
   if (rc) return rc;
   if (nt == 0 || batch == 0) return FFH_OK;
   rc = emb_update_form(c, tables, nt, D, states, &plan);      // (the sort phase: the plain rule, no state is looked at; it keeps maxR)
   if (rc) return rc;
+  if (pad && plan.maxR > 0xFFFFFFFELL)      // (the pad key is num_entries; 0xFFFFFFFF is the reduce kernel's "no key")
+    return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags_pad: num_entries > 2^32 - 2");
   const BagsLayout lay = bags_layout(in_dims, nt, D, batch);
   if (!c->ws || c->ws_bytes < lay.total) return ffh_fail(c, FFH_ERR_WORKSPACE, "embedding_bwd_fused_multi_bags: workspace too small (ffh_embedding_bwd_bags_workspace_bytes)");
   char* ws = (char*)c->ws;
@@ -657,7 +667,7 @@ int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, in
   if (do_sort != do_apply) {
     ffh_ctx::bags_sort_note note;
     memset(&note, 0, sizeof note);
-    note.ws = c->ws; note.nt = nt; note.D = D; note.batch = batch;
+    note.ws = c->ws; note.nt = nt; note.D = D; note.batch = batch; note.pad = pad ? 1 : 0;      // (a pad sort serves a pad apply only, and the reverse)
     for (int i = 0; i < nt; i++) { note.rows[i] = tables[i].num_entries; note.idx[i] = tables[i].idx; note.L[i] = (uint16_t)in_dims[i]; }
     if (do_sort) {
       c->emb_bags_sorted = note;
@@ -668,33 +678,34 @@ int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, in
       c->emb_bags_sorted.ws = nullptr;
     }
   }
-  const RadixPlan rp = radix_plan(plan.maxR);
+  const int more_keys = pad ? 1 : 0;
+  const RadixPlan rp = radix_plan(plan.maxR + more_keys);
   const int avg = aggr == FFH_AGGR_MODE_AVG ? 1 : 0;
 
   if (lay.maxN <= kSmallMax) {
-    snprintf(c->emb_route, sizeof c->emb_route, "bags:small");
+    snprintf(c->emb_route, sizeof c->emb_route, pad ? "bags:small:pad" : "bags:small");
     if (!do_apply) return FFH_OK;      // (the sort lives inside the one launch: the sort call only leaves the note)
     BagsSmallArgs sm;
     memset(&sm, 0, sizeof sm);
     for (int i = 0; i < nt; i++) sm.t[i] = tables[i];
-    fill_passes(tables, nt, rp.rb, sm.npass);
+    fill_passes(tables, nt, rp.rb, sm.npass, nullptr, more_keys);
     sm.kp = (uint2*)(ws + lay.kp_a);
     set_ws_slots(sm, ws, lay);
     sm.rb = rp.rb; sm.D = D; sm.avg = avg; sm.g = lay.g;
     set_rule_args(sm, plan, states, nt, b16);
-    if (!kBagsUpdateOf[b16 ? 1 : 0](BagsUpdateLaunch{plan.rule, plan.v4, lr_block != nullptr, &sm, nullptr, dim3((unsigned)nt), as_stream(s)}))
+    if (!kBagsUpdateOf[more_keys][b16 ? 1 : 0](BagsUpdateLaunch{plan.rule, plan.v4, lr_block != nullptr, &sm, nullptr, dim3((unsigned)nt), as_stream(s)}))
       return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags: no small-route kernel for this rule / weight type");
     FFH_LAUNCH_CHECK(c, "emb_bags_small_kernel");
     return FFH_OK;
   }
 
-  snprintf(c->emb_route, sizeof c->emb_route, "bags:lsd:passes=%d", rp.passes);
+  snprintf(c->emb_route, sizeof c->emb_route, pad ? "bags:lsd:passes=%d:pad" : "bags:lsd:passes=%d", rp.passes);
   BagsSortArgs sa;
   memset(&sa, 0, sizeof sa);
   BagsRedArgs ra;
   memset(&ra, 0, sizeof ra);
-  for (int i = 0; i < nt; i++) { sa.idx[i] = tables[i].idx; ra.t[i] = tables[i]; }
-  fill_passes(tables, nt, rp.rb, sa.npass, ra.parity);
+  for (int i = 0; i < nt; i++) { sa.idx[i] = tables[i].idx; ra.t[i] = tables[i]; sa.padkey[i] = (uint32_t)tables[i].num_entries; }
+  fill_passes(tables, nt, rp.rb, sa.npass, ra.parity, more_keys);
   sa.hist = (uint32_t*)(ws + lay.hist);
   sa.bits = rp.rb; sa.g = lay.g;
   sa.clear[0] = (uint32_t*)(ws + lay.meta1); sa.nclear[0] = (int)(4 * lay.tot.ch1);      // uint2 slots, two per 1024-block
@@ -704,7 +715,7 @@ int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, in
   for (int p = 0; do_sort && p < rp.passes; p++) {
     sa.shift = p * rp.rb; sa.pass = p;
     sa.src = kbuf[p & 1]; sa.dst = kbuf[(p + 1) & 1];
-    if (!emb_bags_sort_pass(sa, p == 0, lay.E, sgrid, as_stream(s))) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags: no sort kernel");
+    if (!(pad && p == 0 ? emb_pad_sort_first_pass(sa, lay.E, sgrid, as_stream(s)) : emb_bags_sort_pass(sa, p == 0, lay.E, sgrid, as_stream(s)))) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags: no sort kernel");
   }
   FFH_LAUNCH_CHECK(c, "bags radix sort");
   if (!do_apply) return FFH_OK;
@@ -714,7 +725,7 @@ int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, in
   ra.arrive = (uint32_t*)(ws + lay.arrive);
   ra.D = D; ra.avg = avg; ra.g = lay.g;
   set_rule_args(ra, plan, states, nt, b16);
-  if (!kBagsUpdateOf[b16 ? 1 : 0](BagsUpdateLaunch{plan.rule, plan.v4, lr_block != nullptr, nullptr, &ra, rgrid, as_stream(s)}))
+  if (!kBagsUpdateOf[more_keys][b16 ? 1 : 0](BagsUpdateLaunch{plan.rule, plan.v4, lr_block != nullptr, nullptr, &ra, rgrid, as_stream(s)}))
     return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags: no reduce kernel for this rule / weight type");
   FFH_LAUNCH_CHECK(c, "emb_bags_reduce/fold");
   return FFH_OK;
@@ -734,7 +745,7 @@ size_t ffh_embedding_bwd_bags_workspace_bytes(const int* in_dims, int nt, int D,
 
 // the descriptor of the three ragged entries: the fused call (do_sort && do_apply) and the pair of include/ff_hip_bags_sort.h.  The sort phase
 // takes the fields it reads (tables, in_dims, ntables, out_dim, batch) and nothing else.
-static int emb_bwd_bags_desc(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s, const bool do_sort, const bool do_apply) {
+static int emb_bwd_bags_desc(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s, const bool do_sort, const bool do_apply, const bool pad = false) {
   if (!u) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: null descriptor");
   if ((u->tables != nullptr) == (u->tables_bf16 != nullptr)) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: exactly one of tables / tables_bf16");
   if (do_apply && u->lr_block && !u->opt) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: lr_block needs opt");
@@ -743,14 +754,14 @@ static int emb_bwd_bags_desc(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s,
   const ffh_sparse_opt* opt = do_apply ? u->opt : nullptr;
   const ffh_emb_state* states = do_apply ? u->states : nullptr;
   const ffh_lr_state* lr_block = do_apply ? u->lr_block : nullptr;
-  if (u->tables) return emb_bwd_bags(c, u->tables, u->in_dims, u->ntables, u->out_dim, u->batch, aggr, lr, s, do_sort, do_apply, opt, states, nullptr, lr_block);
+  if (u->tables) return emb_bwd_bags(c, u->tables, u->in_dims, u->ntables, u->out_dim, u->batch, aggr, lr, s, do_sort, do_apply, opt, states, nullptr, lr_block, pad);
   ffh_emb_table t[FFH_MAX_TABLES];
   Bf16Cfg cfg;
   memset(&cfg, 0, sizeof cfg);
   cfg.r = do_apply ? u->rounding : nullptr;
   const int rc = bf16_tables(c, u->tables_bf16, u->ntables, t, &cfg.keys);
   if (rc) return rc;
-  return emb_bwd_bags(c, t, u->in_dims, u->ntables, u->out_dim, u->batch, aggr, lr, s, do_sort, do_apply, opt, states, &cfg, lr_block);
+  return emb_bwd_bags(c, t, u->in_dims, u->ntables, u->out_dim, u->batch, aggr, lr, s, do_sort, do_apply, opt, states, &cfg, lr_block, pad);
 }
 
 int ffh_embedding_bwd_fused_multi_bags(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, true, true); }
@@ -759,5 +770,10 @@ int ffh_embedding_bwd_fused_multi_bags(ffh_ctx* c, const ffh_bags_update* u, ffh
 int ffh_bags_sort_abi_version(void) { return FFH_BAGS_SORT_ABI_VERSION; }
 int ffh_embedding_bwd_sort_multi_bags(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, true, false); }
 int ffh_embedding_bwd_apply_multi_bags(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, false, true); }
+
+// include/ff_hip_pad.h: the three entries above with an id < 0 as no lookup
+int ffh_embedding_bwd_fused_multi_bags_pad(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, true, true, true); }
+int ffh_embedding_bwd_sort_multi_bags_pad(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, true, false, true); }
+int ffh_embedding_bwd_apply_multi_bags_pad(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, false, true, true); }
 
 }  // extern "C"

@@ -4,6 +4,6 @@
 
 namespace ffh_emb {
 
-bool emb_bags_update_launch_bf16(const BagsUpdateLaunch& u) { return emb_bags_update_launch<uint16_t>(u, std::make_integer_sequence<int, kUpdateEntries>()); }
+bool emb_bags_update_launch_bf16(const BagsUpdateLaunch& u) { return emb_bags_update_launch<uint16_t, false>(u, std::make_integer_sequence<int, kUpdateEntries>()); }
 
 }  // namespace ffh_emb

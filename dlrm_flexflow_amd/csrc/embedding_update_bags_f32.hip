@@ -4,7 +4,7 @@
 
 namespace ffh_emb {
 
-bool emb_bags_update_launch_f32(const BagsUpdateLaunch& u) { return emb_bags_update_launch<float>(u, std::make_integer_sequence<int, kUpdateEntries>()); }
+bool emb_bags_update_launch_f32(const BagsUpdateLaunch& u) { return emb_bags_update_launch<float, false>(u, std::make_integer_sequence<int, kUpdateEntries>()); }
 
 namespace {
 template <bool FIRST, int E> void bags_sort_pass(const BagsSortArgs& a, dim3 grid, hipStream_t stream) {

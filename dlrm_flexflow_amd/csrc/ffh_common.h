@@ -43,7 +43,8 @@ struct ffh_ctx {
   int64_t     emb_sorted_sig[4]; // ... for this (ntables, in_dim, out_dim, batch): ffh_embedding_bwd_sgd_apply_multi consumes it, once
   // the latest ragged sort (include/ff_hip_bags_sort.h): ffh_embedding_bwd_sort_multi_bags left every table's sorted list in workspace `ws` for
   // these tables; ffh_embedding_bwd_apply_multi_bags consumes it, once.  ws == nullptr: no note.  Compared as bytes (set from a zeroed copy).
-  struct bags_sort_note { const void* ws; int nt, D; int64_t batch; int64_t rows[FFH_MAX_TABLES]; const int64_t* idx[FFH_MAX_TABLES]; uint16_t L[FFH_MAX_TABLES]; } emb_bags_sorted;
+  // pad != 0: the sort of include/ff_hip_pad.h, which only that header's apply consumes.
+  struct bags_sort_note { const void* ws; int nt, D; int64_t batch; int64_t rows[FFH_MAX_TABLES]; const int64_t* idx[FFH_MAX_TABLES]; uint16_t L[FFH_MAX_TABLES]; int pad; } emb_bags_sorted;
   char        route[256]; // ffh_linear_last_route(): kernel families of the latest ffh_linear_* call
   char        emb_route[64]; // ffh_embedding_last_route(): the form the latest fused table update took
   char        err[512];

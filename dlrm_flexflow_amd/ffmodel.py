@@ -87,7 +87,7 @@ def lib() -> C.CDLL:
         "flexflow_config_set_backend": (None, [H, C.c_char_p]), "flexflow_config_set_seed": (None, [H, C.c_uint64]),
         "flexflow_config_set_device": (None, [H, I]), "flexflow_config_set_enable_graph": (None, [H, B]),
         "flexflow_config_set_overlap_embedding": (None, [H, B]), "flexflow_config_set_dense_embedding_update": (None, [H, B]),
-        "flexflow_config_set_ragged_update": (None, [H, B]),
+        "flexflow_config_set_ragged_update": (None, [H, B]), "flexflow_config_set_embedding_padding": (None, [H, B]),
         "flexflow_config_set_embedding_dtype": (None, [H, I]), "flexflow_config_set_embedding_rounding": (None, [H, I]),
         "flexflow_config_set_eval_embedding_dtype": (None, [H, I]),
         "flexflow_config_set_lr_schedule": (None, [H, C.c_int64, C.c_int64, C.c_int64, I]),
@@ -138,7 +138,7 @@ def lib() -> C.CDLL:
         "flexflow_tensor_get_data_type": (I, [H]),
         "flexflow_tensor_set_bf16": (None, [H, H, IP, I, P]), "flexflow_tensor_get_bf16": (None, [H, H, P]),
         "flexflow_dlrm_create": (H, [I, C.POINTER(C.c_char_p), C.POINTER(FFComm)]), "flexflow_dlrm_destroy": (None, [H]),
-        "flexflow_dlrm_get_model": (H, [H]), "flexflow_dlrm_get_num_samples": (I, [H]), "flexflow_dlrm_get_num_tables": (I, [H]), "flexflow_dlrm_get_bag_size": (I, [H, I]), "flexflow_dlrm_get_start_epoch": (I, [H]),
+        "flexflow_dlrm_get_model": (H, [H]), "flexflow_dlrm_get_num_samples": (I, [H]), "flexflow_dlrm_get_num_tables": (I, [H]), "flexflow_dlrm_get_bag_size": (I, [H, I]), "flexflow_dlrm_get_bag_fill": (D, [H]), "flexflow_dlrm_get_start_epoch": (I, [H]),
         "flexflow_dlrm_get_sparse_input": (H, [H, I]), "flexflow_dlrm_get_dense_input": (H, [H]),
         "flexflow_dlrm_warmup": (None, [H]), "flexflow_dlrm_train_steps": (None, [H, I, B]),
         "flexflow_dlrm_run_epochs": (D, [H]), "flexflow_dlrm_time_kernel": (F, [H, I, I]),
@@ -208,6 +208,27 @@ def _mix64(z: np.ndarray) -> np.ndarray:
     z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
     z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
     return z ^ (z >> np.uint64(31))
+
+
+def pad_mask_reference(seed: int, first: int, count: int, fill: float) -> np.ndarray:
+    """ffh_pad_mask_indices (include/ff_hip_pad.h) restated in numpy: a bool array, True where slot first + i KEEPS its id, that is where
+    ffh_u24(ffh_hash(seed, first + i)) < fill in fp32 (False: the slot becomes the pad id -1)."""
+    i = np.arange(int(first), int(first) + int(count), dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        h = _mix64(_mix64(np.array([int(seed) & (2 ** 64 - 1)], np.uint64)) + i)
+    u = (h >> np.uint64(40)).astype(np.float32) * np.float32(1.0 / 16777216.0)      # 24 bits: exact in fp32
+    return u < np.float32(fill)
+
+
+def padded_bag_reference(W, idx) -> np.ndarray:
+    """The pad gather of include/ff_hip_pad.h in numpy: out[b] = sum of W[idx[b][j]] over the j, ascending, whose id is not negative, in
+    fp32 starting from +0.  `W` is [rows][D] float32, `idx` [batch][L] integers; a bag of only pads gives a row of +0."""
+    W, idx = np.asarray(W, np.float32), np.asarray(idx, np.int64)
+    out = np.zeros((idx.shape[0], W.shape[1]), np.float32)
+    for j in range(idx.shape[1]):
+        live = idx[:, j] >= 0
+        out[live] = out[live] + W[idx[live, j]]
+    return out
 
 
 def state_digest_reference(data, seed: int, index_base: int = 0, row_bytes: int | None = None) -> int:
@@ -535,14 +556,16 @@ class FFConfig:
     def set(self, seed=None, device=None, enable_graph=None, overlap_embedding=None, dense_embedding_update=None,
             embedding_dtype=None, embedding_rounding=None, lr_warmup_steps=None, lr_decay_start_step=None, lr_num_decay_steps=None,
             device_lr=None, adagrad_eps=None, adagrad_initial_accumulator=None, adagrad_rowwise=None, ragged_update=None,
-            eval_embedding_dtype=None):
+            eval_embedding_dtype=None, embedding_padding=None):
         """embedding_dtype: "fp32" | "bf16"; embedding_rounding: "stochastic" | "nearest" (the --embedding-* flags).
         lr_*: the schedule of --lr-num-warmup-steps / --lr-decay-start-step / --lr-num-decay-steps; device_lr: True = --device-lr,
         False = --host-lr-schedule, None = compile() chooses the route.
         adagrad_eps / adagrad_initial_accumulator: --adagrad-eps / --adagrad-initial-accumulator, what an AdagradOptimizer without its own takes.
         adagrad_rowwise: --adagrad-rowwise, the tables of an AdagradOptimizer keep one accumulator per row (include/ff_hip_rowwise.h).
         eval_embedding_dtype: "fp32" | "int8" (--eval-embedding-dtype): eval_batch() gathers from 8-bit row images of the tables (include/ff_hip_q8.h).
+        embedding_padding: --embedding-padding, the id -1 in a sparse input is "no lookup" (variable-length bags; include/ff_hip_pad.h).
         FFModel(config) copies the config: call set() before the model is built (as for every other field)."""
+        if embedding_padding is not None: lib().flexflow_config_set_embedding_padding(self.h, bool(embedding_padding))
         if adagrad_rowwise is not None:
             lib().flexflow_config_set_adagrad_rowwise(self.h, 1 if adagrad_rowwise else 0)
         if adagrad_eps is not None or adagrad_initial_accumulator is not None:
@@ -793,6 +816,7 @@ class DLRM:
 
     num_samples = property(lambda s: lib().flexflow_dlrm_get_num_samples(s.h))
     num_tables = property(lambda s: lib().flexflow_dlrm_get_num_tables(s.h))
+    bag_fill = property(lambda s: float(lib().flexflow_dlrm_get_bag_fill(s.h)))      # --synthetic-bag-fill: the share of a synthetic bag's slots that hold a lookup (1: every slot)
     bag_sizes = property(lambda s: [lib().flexflow_dlrm_get_bag_size(s.h, t) for t in range(s.num_tables)])      # ids per sample, per table (--embedding-bag-size / --embedding-bag-sizes)
     start_epoch = property(lambda s: lib().flexflow_dlrm_get_start_epoch(s.h))      # --load-checkpoint: the epochs the checkpoint had completed
     def sparse_input(self, t) -> Tensor: return Tensor(lib().flexflow_dlrm_get_sparse_input(self.h, t), self.model)

@@ -16,6 +16,7 @@
 #include "../../include/ff_hip_bags.h"
 #include "../../include/ff_hip_bags_update.h"
 #include "../../include/ff_hip_bags_sort.h"
+#include "../../include/ff_hip_pad.h"
 #include "../../include/ff_hip_q8.h"
 
 // The optional bf16-table extension (include/ff_hip_bf16.h): all of its list or none of it.
@@ -102,6 +103,13 @@ struct KernelApiBagsSort {
 #undef FFH_DECL
 };
 
+// The optional pad extension (include/ff_hip_pad.h: variable-length bags, the id -1 being "no lookup").
+struct KernelApiPad {
+#define FFH_DECL(name) decltype(&::name) name;
+  FFH_PAD_API_LIST(FFH_DECL)
+#undef FFH_DECL
+};
+
 // The optional q8 extension (include/ff_hip_q8.h: tables as 8-bit rows for held-out evaluation, their quantizer and gathers).
 struct KernelApiQ8 {
 #define FFH_DECL(name) decltype(&::name) name;
@@ -125,6 +133,7 @@ struct KernelApi {
   const KernelApiBags* bags = nullptr;       // likewise for include/ff_hip_bags.h (absent: a model of mixed bag sizes gathers once per bag size)
   const KernelApiBagsUpdate* bags_update = nullptr;   // likewise for include/ff_hip_bags_update.h (absent: a model of mixed bag sizes updates once per bag size)
   const KernelApiBagsSort* bags_sort = nullptr;       // likewise for include/ff_hip_bags_sort.h (absent: a model of mixed bag sizes sorts in front of its apply)
+  const KernelApiPad* pad = nullptr;                  // likewise for include/ff_hip_pad.h (absent: compile() refuses --embedding-padding)
   const KernelApiQ8* q8 = nullptr;                    // likewise for include/ff_hip_q8.h (absent: compile() refuses --eval-embedding-dtype int8)
   void* handle;
   std::string path;

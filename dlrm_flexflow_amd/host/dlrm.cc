@@ -58,6 +58,15 @@ void parse_input_args(char** argv, int argc, DLRMConfig& config) {
       if (eq && is("--arch-interaction-op")) { config.arch_interaction_op = std::string(next()); continue; }
       if (eq && is("--optimizer")) { config.optimizer = std::string(next()); continue; }
       if (is("--embedding-bag-sizes")) { config.embedding_bag_sizes = split(next()); continue; }      // one per table, the format of --arch-embedding-size
+      if (is("--synthetic-bag-fill")) {      // with --embedding-padding: the share of a synthetic bag's slots that hold a lookup, the rest are the pad id
+        config.synthetic_bag_fill = atof(next());
+        if (!(config.synthetic_bag_fill > 0.0 && config.synthetic_bag_fill <= 1.0)) {
+          fprintf(stderr, "FATAL: --synthetic-bag-fill %g: must be in (0, 1]\n", config.synthetic_bag_fill);
+          abort();
+        }
+        config.bag_fill_given = true;
+        continue;
+      }
       if (is("--dcn-num-layers")) { config.dcn_num_layers = atoi(next()); continue; }
       if (is("--dcn-low-rank-dim")) { config.dcn_low_rank_dim = atoi(next()); continue; }
     }
@@ -189,6 +198,10 @@ void DataLoader::generate_random(FFModel& ff, const DLRMConfig& dlrm) {
     full_sparse[t] = (int64_t*)ff.dmalloc((size_t)n * sizeof(int64_t));
     if (dlrm.zipf_alpha > 0.0) generate_zipf(ff, full_sparse[t], n, s0 + 17 + t, dlrm.embedding_size[t], dlrm.zipf_alpha);
     else ff.check(ff.api->ffh_gen_indices(ff.ctx, full_sparse[t], n, s0 + 17 + t, 0, dlrm.embedding_size[t], ff.stream), "gen_indices");
+    // --synthetic-bag-fill F < 1 (with --embedding-padding): a slot keeps its id with probability F, else it becomes the pad id; a stream per table,
+    // indexed by the slot's global position, so every rank that holds the table's ids masks them alike
+    if (ff.config.embedding_padding && dlrm.synthetic_bag_fill < 1.0)
+      ff.check(ff.api->pad->ffh_pad_mask_indices(ff.ctx, full_sparse[t], n, s0 + 0x9AD + 31 * t, 0, (float)dlrm.synthetic_bag_fill, ff.stream), "pad_mask_indices");
   }
   // dense features and labels: this rank's slice [rank*Bl, (rank+1)*Bl) of every batch
   full_dense = (float*)ff.dmalloc((size_t)nb * Bl * dense_dim * sizeof(float));
@@ -306,9 +319,11 @@ void DataLoader::load_hdf5(FFModel& ff, const DLRMConfig& dlrm) {
         for (int j = 0; j < bag; j++) {
           const int64_t id = cat[i * C + col0[t] + j];
           // the reference gathers without a bounds check on the GPU and asserts on the CPU path (src/ops/embedding.cc:71-73)
-          if (id < 0 || id >= R) {
-            fprintf(stderr, "FATAL: --dataset %s: X_cat[%llu][%zu] = %lld is outside table %zu (%lld rows)\n", dlrm.dataset_path.c_str(),
-                    (unsigned long long)(row0 + i), col0[t] + j, (long long)id, t, (long long)R);
+          // ... but for the pad id -1, "no lookup", under --embedding-padding (include/ff_hip_pad.h)
+          if ((id < 0 || id >= R) && !(id == FFH_EMB_PAD_ID && ff.config.embedding_padding)) {
+            fprintf(stderr, "FATAL: --dataset %s: X_cat[%llu][%zu] = %lld is outside table %zu (%lld rows)%s\n", dlrm.dataset_path.c_str(),
+                    (unsigned long long)(row0 + i), col0[t] + j, (long long)id, t, (long long)R,
+                    id == FFH_EMB_PAD_ID ? "; if -1 means \"no lookup\" in this file, add --embedding-padding" : "");
             abort();
           }
           col[i * bag + j] = id;
@@ -498,7 +513,13 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
     else printf("[DLRM] data order: total (seed %llu, a new order every epoch%s)\n", (unsigned long long)ffconfig.seed,
                 ffconfig.comm.world_size > 1 ? ", per-rank stripes" : "");
   }
+  if (dlrm.bag_fill_given && !ffconfig.embedding_padding) {
+    fprintf(stderr, "FATAL: --synthetic-bag-fill %g leaves slots of a bag without a lookup, which only --embedding-padding trains on: add --embedding-padding, "
+                    "or drop --synthetic-bag-fill\n", dlrm.synthetic_bag_fill);
+    abort();
+  }
   ff->compile(optimizer, (LossType)ffconfig.driver_loss, metrics);
+  if (chatty && ffconfig.embedding_padding) printf("[DLRM] embedding padding: id -1 is no lookup (synthetic fill %g)\n", dlrm.synthetic_bag_fill);
   if (chatty && !dlrm.embedding_bag_sizes.empty()) printf("[DLRM] embedding gather: %s\n", ff->bag_gather_line().c_str());      // a per-table list: how the gather runs
   if (chatty && ff->mixed_bags && ff->fused_embedding_update()) printf("[DLRM] embedding update: %s\n", ff->bag_update_line().c_str());      // ... and, where the sizes differ, the update
   if (const AdagradOptimizer* ag = dynamic_cast<const AdagradOptimizer*>(optimizer)) {

@@ -22,6 +22,8 @@ struct DLRMConfig {
   std::string arch_interaction_op, dataset_path;
   int data_size;
   std::string optimizer;   // --optimizer sgd (default, the reference driver's) | sgd-momentum | adam | adagrad (not a reference flag)
+  double synthetic_bag_fill = 1.0;   // --synthetic-bag-fill F, 0 < F <= 1 (with --embedding-padding): a synthetic slot holds a lookup with probability F (not a reference flag)
+  bool bag_fill_given = false;
   double zipf_alpha;   // > 0: synthetic ids follow a power law instead of the reference's uniform draw (not a reference flag)
   int dcn_num_layers, dcn_low_rank_dim;   // --arch-interaction-op dcn: --dcn-num-layers L (3), --dcn-low-rank-dim R (512) (not reference flags)
 };

@@ -148,6 +148,8 @@ class FFConfig {
   bool ragged_update;          // the fused update of tables of differing bag sizes is one ragged call per group (include/ff_hip_bags_update.h; --ragged-update / --no-ragged-update,
                                // the later one wins; off: one call per bag size)
   bool ragged_gather;          // tables of differing bag sizes are gathered in one launch per group (include/ff_hip_bags.h; A/B: --no-ragged-gather = one launch per bag size)
+  bool embedding_padding;      // variable-length bags: the id -1 in a sparse input is "no lookup" (include/ff_hip_pad.h; --embedding-padding).  The
+                               // gather and the fused update then run on the pad forms of the ragged entries, whether or not the bag sizes differ
   bool fold_small_tables;      // small embedding tables folded out of the first top layer's forward GEMM (include/ff_hip_fold.h; A/B: --no-fold-small-tables)
   int64_t fold_max_rows;       // ... tables of at most this many rows (--fold-max-rows N)
   bool fold_dw;                // ... and out of its weight-gradient GEMM (A/B: --no-fold-dw)
@@ -743,6 +745,9 @@ class FFModel {
   void q8_allocate();                         // compile(), behind allocate(): the images
   void q8_quantize(ffh_stream s, ffh_ctx* cx) const;      // every image from its table: one launch per group of <= FFH_MAX_TABLES tables of one width and storage
   std::string q8_line() const;                // the driver's start-up line
+  mutable int64_t n_pad_gathers = 0;          // ffh_embedding_fwd_multi_bags_pad[_bf16] launches (--embedding-padding; "pad_gather_launches")
+  mutable int64_t n_pad_updates = 0;          // ffh_embedding_bwd_fused_multi_bags_pad / ffh_embedding_bwd_apply_multi_bags_pad calls ("pad_update_launches")
+  bool bags_path() const { return mixed_bags || config.embedding_padding; }      // the tables go through the ragged entries: their bag sizes differ, or an id may be a pad
   mutable int64_t n_ragged_updates = 0;       // ffh_embedding_bwd_fused_multi_bags calls (tests: flexflow_model_get_counter "ragged_update_launches")
   bool ragged_update_on() const;              // the tables' bag sizes differ and their fused update is the ragged call (the library has it, the flag allows it)
   bool ragged_early_sort_on() const;          // ... and --early-sort asks for its sort behind the gather, with a library that has the pair (include/ff_hip_bags_sort.h)

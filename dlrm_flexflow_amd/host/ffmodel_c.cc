@@ -38,6 +38,7 @@ void flexflow_config_set_enable_graph(flexflow_config_t h, bool v) { C(h)->enabl
 void flexflow_config_set_overlap_embedding(flexflow_config_t h, bool v) { C(h)->overlap_embedding = v; }
 void flexflow_config_set_dense_embedding_update(flexflow_config_t h, bool v) { C(h)->dense_embedding_update = v; }
 void flexflow_config_set_ragged_update(flexflow_config_t h, bool v) { C(h)->ragged_update = v; }
+void flexflow_config_set_embedding_padding(flexflow_config_t h, bool v) { C(h)->embedding_padding = v; }
 void flexflow_config_set_embedding_dtype(flexflow_config_t h, int dt) {
   if (dt != DT_FLOAT && dt != DT_BF16) { fprintf(stderr, "FATAL: embedding data type %d: %d (fp32) or %d (bf16)\n", dt, (int)DT_FLOAT, (int)DT_BF16); abort(); }
   C(h)->embedding_dtype = (DataType)dt;
@@ -180,6 +181,8 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   if (n == "early_sorts") return M(m)->n_early_sorts;
   if (n == "ragged_early_sorts") return M(m)->n_ragged_early_sorts;      // ffh_embedding_bwd_sort_multi_bags calls among them (include/ff_hip_bags_sort.h)
   if (n == "ragged_update_launches") return M(m)->n_ragged_updates;      // ffh_embedding_bwd_fused_multi_bags calls (mixed bag sizes; include/ff_hip_bags_update.h)
+  if (n == "pad_gather_launches") return M(m)->n_pad_gathers;      // ffh_embedding_fwd_multi_bags_pad[_bf16] launches (--embedding-padding; include/ff_hip_pad.h)
+  if (n == "pad_update_launches") return M(m)->n_pad_updates;      // ffh_embedding_bwd_{fused,apply}_multi_bags_pad calls
   if (n == "q8_quantize_launches") return M(m)->n_q8_quantize;      // ffh_embedding_quantize_q8 launches (--eval-embedding-dtype int8; include/ff_hip_q8.h)
   if (n == "q8_gather_launches") return M(m)->n_q8_gathers;         // ffh_embedding_fwd_multi[_bags]_q8 launches
   if (n == "ragged_gather_launches") return M(m)->n_ragged_gathers;     // ffh_embedding_fwd_multi_bags[_bf16] launches (mixed bag sizes; include/ff_hip_bags.h)
@@ -239,6 +242,7 @@ flexflow_model_t flexflow_dlrm_get_model(flexflow_dlrm_t h) { flexflow_model_t m
 int flexflow_dlrm_get_num_samples(flexflow_dlrm_t h) { return A(h)->loader->num_samples; }
 int flexflow_dlrm_get_num_tables(flexflow_dlrm_t h) { return (int)A(h)->sparse_inputs.size(); }
 int flexflow_dlrm_get_bag_size(flexflow_dlrm_t h, int t) { return A(h)->dlrm.bag_of((size_t)t); }
+double flexflow_dlrm_get_bag_fill(flexflow_dlrm_t h) { return A(h)->dlrm.synthetic_bag_fill; }
 flexflow_tensor_t flexflow_dlrm_get_sparse_input(flexflow_dlrm_t h, int t) { return wrap(A(h)->sparse_inputs.at(t)); }
 flexflow_tensor_t flexflow_dlrm_get_dense_input(flexflow_dlrm_t h) { return wrap(A(h)->dense_input); }
 void flexflow_dlrm_warmup(flexflow_dlrm_t h) { A(h)->warmup(); }

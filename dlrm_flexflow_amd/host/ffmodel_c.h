@@ -53,6 +53,8 @@ void flexflow_config_set_overlap_embedding(flexflow_config_t, bool);
 void flexflow_config_set_dense_embedding_update(flexflow_config_t, bool);
 /* --ragged-update / --no-ragged-update: tables of differing bag sizes are updated in one ragged call per group (include/ff_hip_bags_update.h) */
 void flexflow_config_set_ragged_update(flexflow_config_t, bool);
+/* --embedding-padding: the id -1 in a sparse input is "no lookup" (variable-length bags; include/ff_hip_pad.h) */
+void flexflow_config_set_embedding_padding(flexflow_config_t, bool);
 /* bf16 embedding tables (--embedding-dtype / --embedding-rounding): data_type 40 (DT_FLOAT, default) or 140 (DT_BF16);
  * mode 0 stochastic (default) or 1 nearest even (include/ffh_bf16.h).  Other values abort. */
 void flexflow_config_set_embedding_dtype(flexflow_config_t, int data_type);
@@ -177,6 +179,7 @@ flexflow_model_t flexflow_dlrm_get_model(flexflow_dlrm_t);
 int  flexflow_dlrm_get_num_samples(flexflow_dlrm_t);
 int  flexflow_dlrm_get_num_tables(flexflow_dlrm_t);
 int  flexflow_dlrm_get_bag_size(flexflow_dlrm_t, int table);      /* ids per sample of table `table` (--embedding-bag-size, or its entry of --embedding-bag-sizes) */
+double flexflow_dlrm_get_bag_fill(flexflow_dlrm_t);             /* --synthetic-bag-fill: the share of a synthetic bag's slots that hold a lookup (with --embedding-padding; 1: all) */
 int  flexflow_dlrm_get_start_epoch(flexflow_dlrm_t);   /* --load-checkpoint: the epochs the checkpoint had completed (0 without it) */
 flexflow_tensor_t flexflow_dlrm_get_sparse_input(flexflow_dlrm_t, int table);
 flexflow_tensor_t flexflow_dlrm_get_dense_input(flexflow_dlrm_t);

@@ -153,6 +153,37 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
       default: die("metrics type %d is not on the DLRM path", (int)m);
     }
   }
+  // --embedding-padding (include/ff_hip_pad.h): the id -1 is "no lookup" in the pad forms of the ragged gather and the ragged fused
+  // update, and nowhere else.  Every path that would hand such an id to another kernel is refused here, each with the flag to drop -- before the library checks, as below.
+  if (config.embedding_padding && !embeddings.empty()) {
+    for (const Embedding* e : embeddings) {
+      if (e->aggr == AGGR_MODE_AVG)
+        die("--embedding-padding: %s pools with AGGR_MODE_AVG; a mean over the lookups that are there needs each bag's count, which the pad kernels do not "
+            "keep: use AGGR_MODE_SUM or drop --embedding-padding", e->name);
+      if (e->row_sharded)
+        die("--embedding-padding: %s is row-sharded (its ids are localized onto a zero row, a path that takes no pad id); padded tables are table-wise: drop "
+            "--row-shard-rows or drop --embedding-padding", e->name);
+      if (e->column_sharded)
+        die("--embedding-padding: %s is column-sharded; padded tables are table-wise: drop --column-shard-rows or drop --embedding-padding", e->name);
+      if (e->replicated)
+        die("--embedding-padding: %s is replicated (data-parallel tables are gathered and updated apart, by kernels that take no pad id): drop "
+            "--replicate-embedding-rows or drop --embedding-padding", e->name);
+    }
+    if (config.dense_embedding_update)
+      die("--embedding-padding needs the fused sparse table update (the dense backward adds into the row an id names, and -1 names none): drop "
+          "--dense-embedding-update or drop --embedding-padding");
+    if (!fused_embedding_update())
+      die("--embedding-padding needs the fused sparse table update: add --sparse-embedding-optimizer or drop --embedding-padding");
+    if (!config.ragged_gather)
+      die("--embedding-padding gathers through the ragged entries' pad forms: drop --no-ragged-gather or drop --embedding-padding");
+    if (!config.ragged_update)
+      die("--embedding-padding updates through the ragged entries' pad forms: drop --no-ragged-update or drop --embedding-padding");
+    if (q8_on())
+      die("--embedding-padding: the 8-bit gathers have no pad form; drop --eval-embedding-dtype int8 or drop --embedding-padding");
+    if (!api->pad || !api->bags || !api->bags_update)
+      die("--embedding-padding: %s (%s) is a kernel library without the pad extension (include/ff_hip_pad.h); drop --embedding-padding, or use another "
+          "--backend", api->path.c_str(), api->ffh_backend_name());
+  }
   // --eval-embedding-dtype int8 (include/ff_hip_q8.h): eval_batch() gathers table-wise tables from 8-bit row images; every case
   // that does not cover is refused here, each with the flag to drop -- before the library checks: a library without the extensions shows them too.
   // (The gather destinations' 16-byte form follows from the layer structure: q8_check_destinations().)
@@ -1103,6 +1134,7 @@ void FFModel::plan_fold() {
   fold = FoldRoute();
   if (!config.fold_small_tables || !api->fold || exchange || world_size != 1 || embeddings.empty()) return;
   if (mixed_bags) return;      // the fold is planned on one bag size
+  if (config.embedding_padding) return;      // ... and on ids that are all rows: a folded table's gather-add and segmented sum take no pad
   if (config.allow_tensor_op_math_conversion || config.fp32_split_bf16x3) return;
   for (Op* op : layers) {
     Linear* li = dynamic_cast<Linear*>(op);

@@ -25,7 +25,11 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
   // gather where the library has the one-launch ragged gather (include/ff_hip_bags.h) and --no-ragged-gather is not given, and for the fused update
   // where it has the ragged update (include/ff_hip_bags_update.h) and --ragged-update allows it, and for the sort-only / apply-only pair where the
   // ragged early sort is on (include/ff_hip_bags_sort.h, FFModel::ragged_early_sort_on).
+  // --embedding-padding (include/ff_hip_pad.h): an id may be -1, which only the pad forms of the ragged entries take -- every chunk of every group
+  // goes through them, whether or not its bag sizes differ (compile() has refused every configuration in which one of the three is off).
   const bool ragged = fwd ? ff->ragged_gather_on() : (what == kFusedUpdate ? ff->ragged_update_on() : ff->ragged_early_sort_on());
+  const bool pad = ff->config.embedding_padding;
+  const KernelApiPad* pda = ff->api->pad;
   struct Group { std::vector<ffh_emb_table> t; std::vector<ffh_emb_table_bf16> t16; std::vector<ffh_emb_state> st; std::vector<int> bag;
                  std::vector<ffh_emb_table_q8> tq; std::vector<int> bagq; };      // tq, bagq: the tables an evaluation gathers from their 8-bit row images
   // --eval-embedding-dtype int8: the gather of eval_batch() reads the images (include/ff_hip_q8.h), in the same groups.  eval_batch() has made stale images
@@ -68,6 +72,7 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
     const Group& g = kv.second;
     // tables [b, b + n) of the group in one ragged launch: where their bag sizes differ (else the call stays the uniform one)
     auto differ = [&](size_t b, int n) {
+      if (pad) return true;
       for (int i = 1; i < n; i++) if (g.bag[b + i] != g.bag[b]) return true;
       return false;
     };
@@ -79,8 +84,15 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
       u.opt = (ruled || lrb) ? &rule : nullptr;
       u.rounding = rnd; u.lr_block = lrb;
       if (what == kSortOnly) {
-        ff->check(ff->api->bags_sort->ffh_embedding_bwd_sort_multi_bags(cx, &u, s), "embedding_bwd_sort_multi_bags");
+        if (pad) ff->check(pda->ffh_embedding_bwd_sort_multi_bags_pad(cx, &u, s), "embedding_bwd_sort_multi_bags_pad");
+        else ff->check(ff->api->bags_sort->ffh_embedding_bwd_sort_multi_bags(cx, &u, s), "embedding_bwd_sort_multi_bags");
         ff->n_early_sorts++; ff->n_ragged_early_sorts++;
+        return;
+      }
+      if (pad) {
+        if (what == kApplyOnly) ff->check(pda->ffh_embedding_bwd_apply_multi_bags_pad(cx, &u, s), "embedding_bwd_apply_multi_bags_pad");
+        else ff->check(pda->ffh_embedding_bwd_fused_multi_bags_pad(cx, &u, s), "embedding_bwd_fused_multi_bags_pad");
+        ff->n_pad_updates++;
         return;
       }
       if (what == kApplyOnly) ff->check(ff->api->bags_sort->ffh_embedding_bwd_apply_multi_bags(cx, &u, s), "embedding_bwd_apply_multi_bags");
@@ -106,7 +118,10 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
         const int L = g.bag[b];       // a uniform call's bag size is its own tables' (a whole group of mixed sizes holds several)
         switch (what) {
           case kGather:
-            if (ragged && differ(b, n)) {
+            if (pad) {
+              ff->check(pda->ffh_embedding_fwd_multi_bags_pad_bf16(cx, tb, g.bag.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags_pad_bf16");
+              ff->n_pad_gathers++;
+            } else if (ragged && differ(b, n)) {
               ff->check(ff->api->bags->ffh_embedding_fwd_multi_bags_bf16(cx, tb, g.bag.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags_bf16");
               ff->n_ragged_gathers++;
             } else ff->check(b16->ffh_embedding_fwd_multi_bf16(cx, tb, n, g.bag[b], D, B, aggr, s), "embedding_fwd_multi_bf16");
@@ -137,7 +152,10 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
       const int L = g.bag[b];
       switch (what) {
         case kGather:
-          if (ragged && differ(b, n)) {
+          if (pad) {
+            ff->check(pda->ffh_embedding_fwd_multi_bags_pad(cx, tabs.data() + b, g.bag.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags_pad");
+            ff->n_pad_gathers++;
+          } else if (ragged && differ(b, n)) {
             ff->check(ff->api->bags->ffh_embedding_fwd_multi_bags(cx, tabs.data() + b, g.bag.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags");
             ff->n_ragged_gathers++;
           } else ff->check(ff->api->ffh_embedding_fwd_multi(cx, tabs.data() + b, n, g.bag[b], D, B, aggr, s), "embedding_fwd_multi");
@@ -248,7 +266,7 @@ std::string FFModel::q8_line() const {
   return buf;
 }
 
-bool FFModel::ragged_gather_on() const { return mixed_bags && config.ragged_gather && api->bags; }
+bool FFModel::ragged_gather_on() const { return bags_path() && config.ragged_gather && api->bags; }
 // how a model of mixed bag sizes gathers (the driver prints it): the launches of one gather over this rank's tables
 std::string FFModel::bag_gather_line() const {
   std::set<std::tuple<int, bool, int>> keys;
@@ -261,7 +279,7 @@ std::string FFModel::bag_gather_line() const {
   return buf;
 }
 
-bool FFModel::ragged_update_on() const { return mixed_bags && config.ragged_update && api->bags_update; }
+bool FFModel::ragged_update_on() const { return bags_path() && config.ragged_update && api->bags_update; }
 // a model of mixed bag sizes may sort behind the gather (early_sort_possible): asked for by --early-sort (never by shape: that default is unmeasured),
 // with the ragged update on and a library that has its two-call form (include/ff_hip_bags_sort.h)
 bool FFModel::ragged_early_sort_on() const { return config.early_sort > 0 && ragged_update_on() && api->bags_sort; }
@@ -348,6 +366,7 @@ bool FFModel::early_sort_possible(int where) const {
   const bool exact_gemms = !config.allow_tensor_op_math_conversion && !config.fp32_split_bf16x3;
   const int mode = config.early_sort > 0 ? config.early_sort : ((!exchange && local_batch >= 8192 && exact_gemms) ? early_sort_big_batch_mode : 1);
   if (mode != where) return false;
+  if (config.embedding_padding && !ragged_early_sort_on()) return false;      // (the uniform sort takes no pad id: only the pad pair sorts early, on --early-sort)
   int n = 0, cols = -1, bag = -1;
   for (const EmbShard& sh : shards) {
     if (sh.owner != rank) continue;

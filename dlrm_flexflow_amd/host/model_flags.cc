@@ -42,6 +42,7 @@ FFConfig::FFConfig() {
   mlp_chain = true;
   ragged_gather = true;
   ragged_update = true;
+  embedding_padding = false;
   fold_small_tables = true;
   fold_max_rows = 7420;      // the measured threshold (2208 and 7420 tried)
   fold_dw = true;
@@ -173,6 +174,7 @@ void FFConfig::parse_args(char** argv, int argc) {
     if (is("--no-ragged-gather")) { ragged_gather = false; continue; }
     if (is("--ragged-update")) { ragged_update = true; continue; }
     if (is("--no-ragged-update")) { ragged_update = false; continue; }
+    if (is("--embedding-padding")) { embedding_padding = eq ? atoi(eq + 1) != 0 : true; continue; }      // (a switch: --embedding-padding or --embedding-padding=1)
     if (is("--no-fold-small-tables")) { fold_small_tables = false; continue; }
     if (is("--no-fold-dw")) { fold_dw = false; continue; }
     if (is("--no-fold-dx")) { fold_dx = false; continue; }
