@@ -1289,6 +1289,89 @@ def pad_api(lib: "FFHLib") -> PadApi:
     return PadApi(lib)
 
 
+# ---- the pad-mean extension (include/ff_hip_pad_mean.h): the pad entries with a mean over the lookups that are there ---------------------
+PAD_MEAN_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_pad_mean.h")
+
+_SIGS_PAD_MEAN = {
+    "ffh_pad_mean_abi_version": (I, []),
+    "ffh_embedding_fwd_multi_bags_pad_mean": (I, [P, C.POINTER(EmbTable), C.POINTER(I), I, I, L, I, P]),
+    "ffh_embedding_fwd_multi_bags_pad_mean_bf16": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(I), I, I, L, I, P]),
+    "ffh_embedding_bwd_bags_pad_mean_workspace_bytes": (SZ, [C.POINTER(I), I, I, L]),
+    "ffh_embedding_bwd_fused_multi_bags_pad_mean": (I, [P, C.POINTER(BagsUpdate), P]),
+    "ffh_embedding_bwd_apply_multi_bags_pad_mean": (I, [P, C.POINTER(BagsUpdate), P]),
+}
+
+
+def pad_mean_header_symbols(header_path: str = PAD_MEAN_HEADER_PATH) -> list[str]:
+    """Every symbol of the FFH_PAD_MEAN_API_LIST X-macro in include/ff_hip_pad_mean.h."""
+    m = re.search(r"#define FFH_PAD_MEAN_API_LIST\(X\)(.*?)\n\n", open(header_path).read(), re.S)
+    if not m:
+        raise RuntimeError("FFH_PAD_MEAN_API_LIST not found in " + header_path)
+    return re.findall(r"X\((\w+)\)", m.group(1))
+
+
+def pad_mean_header_abi_version(header_path: str = PAD_MEAN_HEADER_PATH) -> int:
+    """FFH_PAD_MEAN_ABI_VERSION of include/ff_hip_pad_mean.h."""
+    m = re.search(r"#define\s+FFH_PAD_MEAN_ABI_VERSION\s+(\d+)", open(header_path).read())
+    if not m:
+        raise RuntimeError("FFH_PAD_MEAN_ABI_VERSION not found in " + header_path)
+    return int(m.group(1))
+
+
+class PadMeanApi:
+    """The pad-mean extension (include/ff_hip_pad_mean.h) of a loaded FFHLib; `pad_mean_api(lib)` builds it or raises.  PadApi's methods without
+    the sort (the pad sort serves either apply), and the workspace query of the update."""
+
+    def __init__(self, lib: "FFHLib"):
+        self.base = lib
+        for name, (res, args) in _SIGS_PAD_MEAN.items():
+            fn = getattr(lib.lib, name, None)
+            if fn is None:
+                raise FFHError(f"{lib.path}: no pad-mean extension ({name} missing; include/ff_hip_pad_mean.h)")
+            fn.restype = res
+            fn.argtypes = args
+        got = lib.lib.ffh_pad_mean_abi_version()
+        if got != pad_mean_header_abi_version():
+            raise FFHError(f"{lib.path}: pad-mean ABI version {got}, include/ff_hip_pad_mean.h says {pad_mean_header_abi_version()} (rebuild)")
+        self.lib = lib.lib
+        self.ctx = lib.ctx
+
+    def fwd_rc(self, tables, in_dims, ntables: int, out_dim: int, batch: int, aggr: int, bf16: bool = False, stream=None) -> int:
+        """ffh_embedding_fwd_multi_bags_pad_mean[_bf16], returning its status code; `in_dims` from BagsApi.in_dims (or None: a null pointer)."""
+        fn = self.lib.ffh_embedding_fwd_multi_bags_pad_mean_bf16 if bf16 else self.lib.ffh_embedding_fwd_multi_bags_pad_mean
+        return fn(self.ctx, tables, in_dims, int(ntables), int(out_dim), int(batch), int(aggr), ptr(stream))
+
+    def fwd(self, *args, **kw):
+        self.base.check(self.fwd_rc(*args, **kw), "ffh_embedding_fwd_multi_bags_pad_mean")
+
+    def workspace_bytes(self, in_dims, out_dim: int, batch: int) -> int:
+        """ffh_embedding_bwd_bags_pad_mean_workspace_bytes of a list of bag sizes (None: a null pointer with ntables 1); 0 on a bad argument."""
+        if in_dims is None:
+            return int(self.lib.ffh_embedding_bwd_bags_pad_mean_workspace_bytes(None, 1, int(out_dim), int(batch)))
+        arr = (I * max(len(in_dims), 1))(*[int(v) for v in in_dims])
+        return int(self.lib.ffh_embedding_bwd_bags_pad_mean_workspace_bytes(arr, len(in_dims), int(out_dim), int(batch)))
+
+    def _u(self, name: str, u: BagsUpdate | None, stream) -> int:
+        return getattr(self.lib, name)(self.ctx, C.byref(u) if u is not None else None, ptr(stream))
+
+    def fused_rc(self, u: BagsUpdate | None, stream=None) -> int:
+        return self._u("ffh_embedding_bwd_fused_multi_bags_pad_mean", u, stream)
+
+    def apply_rc(self, u: BagsUpdate | None, stream=None) -> int:
+        return self._u("ffh_embedding_bwd_apply_multi_bags_pad_mean", u, stream)
+
+    def fused(self, u: BagsUpdate, stream=None):
+        self.base.check(self.fused_rc(u, stream), "ffh_embedding_bwd_fused_multi_bags_pad_mean")
+
+    def apply(self, u: BagsUpdate, stream=None):
+        self.base.check(self.apply_rc(u, stream), "ffh_embedding_bwd_apply_multi_bags_pad_mean")
+
+
+def pad_mean_api(lib: "FFHLib") -> PadMeanApi:
+    """The pad-mean entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
+    return PadMeanApi(lib)
+
+
 # ---- the q8 extension (include/ff_hip_q8.h): tables as 8-bit rows with a scale and a bias each; a quantizer and the gathers that read them ----
 Q8_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_q8.h")
 

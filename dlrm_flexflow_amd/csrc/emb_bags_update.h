@@ -91,6 +91,7 @@ struct BagsRedArgs {
   OptP      op;
   float*    s0[FFH_MAX_TABLES];
   union { float* s1[FFH_MAX_TABLES]; Bf16Keys b16; Bf16AdamKeys b16a; };     // as in RedArgs
+  const uint16_t* cnt;                  // the mean forms (include/ff_hip_pad_mean.h): real lookups per bag, [table][batch]; else null and never read
 };
 
 struct BagsSmallArgs {
@@ -104,13 +105,29 @@ struct BagsSmallArgs {
   OptP      op;
   float*    s0[FFH_MAX_TABLES];
   union { float* s1[FFH_MAX_TABLES]; Bf16Keys b16; Bf16AdamKeys b16a; };
+  const uint16_t* cnt;                  // as BagsRedArgs::cnt
 };
+
+// the count kernel of the mean forms (include/ff_hip_pad_mean.h): cnt[t][b] = ids >= 0 in bag b of table t
+struct BagsCountArgs {
+  const int64_t* idx[FFH_MAX_TABLES];
+  uint16_t  L[FFH_MAX_TABLES];
+  uint16_t* cnt;                        // [nt][batch]
+  int64_t   batch;
+  int       nt;
+};
+constexpr int kCountThreads = 256;
+constexpr int kCountSlots = 1024;       // id slots a workgroup takes at most, in whole bags; a longer bag has a workgroup to itself
+// the bags of a table with bag size L that one workgroup counts, and the table's workgroups: host and kernel compute the flat map with these
+__host__ __device__ inline int count_bags_per_wg(int L) { return L >= kCountSlots ? 1 : kCountSlots / L; }
+__host__ __device__ inline int64_t count_wgs(int64_t batch, int L) { const int b = count_bags_per_wg(L); return (batch + b - 1) / b; }
 
 constexpr size_t kBagsKernargBytes = sizeof(BagsRedArgs) > sizeof(BagsSmallArgs)
                                          ? (sizeof(BagsRedArgs) > sizeof(BagsSortArgs) ? sizeof(BagsRedArgs) : sizeof(BagsSortArgs))
                                          : (sizeof(BagsSmallArgs) > sizeof(BagsSortArgs) ? sizeof(BagsSmallArgs) : sizeof(BagsSortArgs));
 static_assert(sizeof(BagsGeo) == 2 * FFH_MAX_TABLES + 24, "BagsGeo: 16-bit bag sizes");
-static_assert(sizeof(BagsRedArgs) == 3936 && sizeof(BagsSmallArgs) == 3928 && kBagsKernargBytes <= 4096, "kernel arguments: 64 tables inside 4 KB");
+static_assert(sizeof(BagsRedArgs) == 3944 && sizeof(BagsSmallArgs) == 3936 && kBagsKernargBytes <= 4096 && sizeof(BagsCountArgs) <= 4096, "kernel arguments: 64 tables inside 4 KB");
+static_assert(offsetof(BagsRedArgs, cnt) == 3936 && offsetof(BagsSmallArgs, cnt) == 3928, "the counts lie behind the members the existing kernels read");
 
 namespace {
 
@@ -230,7 +247,7 @@ __global__ __launch_bounds__(kSortThreads) void bags_radix_scatter_kernel(const 
 // records go out written through and completed before it counts itself in; the last tile of a 1024-block folds the block, the last folded
 // block of a table folds the table.  No workgroup waits for another.
 // ---------------------------------------------------------------------------
-template <int VEC, RowRule R, class WT, bool LRP, bool PAD = false>
+template <int VEC, RowRule R, class WT, bool LRP, bool PAD = false, bool MEAN = false>
 __global__ __launch_bounds__(kRedThreads, (red_waves_per_simd<VEC, R, WT, false>())) void emb_bags_reduce_kernel(const BagsRedArgs a) {
   ffh_kernel_prio();
   FFH_OPT_OF(LRP, op, a.op);
@@ -252,7 +269,8 @@ __global__ __launch_bounds__(kRedThreads, (red_waves_per_simd<VEC, R, WT, false>
   float* const st0 = opt_state(R) ? a.s0[tix] : nullptr;
   float* const st1 = state1_of<R, WT>(a, tix);
   const SrKey sk = sr_key<R, WT>(a, tix);
-  reduce_tile_body<VEC, true, R, WT, PAD>(tb, keys, p0, m0, N, nchunks, tile, (int)at.local, L, a.D, a.avg != 0, op, st0, st1, sk, sh, threadIdx.x, false);
+  reduce_tile_body<VEC, true, R, WT, PAD, MEAN>(tb, keys, p0, m0, N, nchunks, tile, (int)at.local, L, a.D, a.avg != 0, op, st0, st1, sk, sh, threadIdx.x, false,
+                                                MEAN ? a.cnt + (int64_t)tix * a.g.batch : nullptr);
 
   const int nvec = a.D / VEC;
   const int lpr = nvec < 64 ? nvec : 64;
@@ -310,7 +328,7 @@ __global__ __launch_bounds__(kRedThreads, (red_waves_per_simd<VEC, R, WT, false>
 // apply, small route (every N_t <= kSmallMax): emb_sgd_small_kernel with the table's own N_t -- sort, reduce and folds of a table in its
 // one workgroup
 // ---------------------------------------------------------------------------
-template <int VEC, RowRule R, class WT, bool LRP, bool PAD = false>
+template <int VEC, RowRule R, class WT, bool LRP, bool PAD = false, bool MEAN = false>
 __global__ __launch_bounds__(kSmallThreads) void emb_bags_small_kernel(const BagsSmallArgs a) {
   ffh_kernel_prio();
   FFH_OPT_OF(LRP, op, a.op);
@@ -390,7 +408,8 @@ __global__ __launch_bounds__(kSmallThreads) void emb_bags_small_kernel(const Bag
   const int team = threadIdx.x / kRedThreads, ttid = threadIdx.x % kRedThreads;
   const int ntiles = (int)((N + tile - 1) / tile);
   for (int t0 = 0; t0 < ntiles; t0 += kSmallRedParts) {
-    reduce_tile_body<VEC, false, R, WT, PAD>(tb, keys, p0, m0, N, nch0, tile, t0 + team, L, a.D, a.avg != 0, op, st0, st1, sk, sm.red[team], ttid);
+    reduce_tile_body<VEC, false, R, WT, PAD, MEAN>(tb, keys, p0, m0, N, nch0, tile, t0 + team, L, a.D, a.avg != 0, op, st0, st1, sk, sm.red[team], ttid, false,
+                                                   MEAN ? a.cnt + (int64_t)tix * a.g.batch : nullptr);
     __syncthreads();
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -428,17 +447,18 @@ struct BagsUpdateLaunch {
 };
 typedef void (*BagsUpdateFn)(const BagsUpdateLaunch&);
 namespace {
-template <class WT, bool PAD, int I> void launch_bags_small(const BagsUpdateLaunch& u) {
-  hipLaunchKernelGGL((emb_bags_small_kernel<(I >> 1 & 1) ? 4 : 1, (RowRule)(I >> 2), WT, (I & 1) != 0, PAD>), u.grid, dim3(kSmallThreads), 0, u.stream, *u.small);
+template <class WT, bool PAD, bool MEAN, int I> void launch_bags_small(const BagsUpdateLaunch& u) {
+  hipLaunchKernelGGL((emb_bags_small_kernel<(I >> 1 & 1) ? 4 : 1, (RowRule)(I >> 2), WT, (I & 1) != 0, PAD, MEAN>), u.grid, dim3(kSmallThreads), 0, u.stream, *u.small);
 }
-template <class WT, bool PAD, int I> void launch_bags_reduce(const BagsUpdateLaunch& u) {
-  hipLaunchKernelGGL((emb_bags_reduce_kernel<(I >> 1 & 1) ? 4 : 1, (RowRule)(I >> 2), WT, (I & 1) != 0, PAD>), u.grid, dim3(kRedThreads), 0, u.stream, *u.red);
+template <class WT, bool PAD, bool MEAN, int I> void launch_bags_reduce(const BagsUpdateLaunch& u) {
+  hipLaunchKernelGGL((emb_bags_reduce_kernel<(I >> 1 & 1) ? 4 : 1, (RowRule)(I >> 2), WT, (I & 1) != 0, PAD, MEAN>), u.grid, dim3(kRedThreads), 0, u.stream, *u.red);
 }
 // PAD: the pad forms (include/ff_hip_pad.h), compiled in translation units of their own (embedding_update_pad_f32.hip / _bf16.hip)
-template <class WT, bool PAD, int... I>
+// MEAN: their mean forms (include/ff_hip_pad_mean.h), likewise (embedding_update_padmean_f32.hip / _bf16.hip)
+template <class WT, bool PAD, bool MEAN = false, int... I>
 bool emb_bags_update_launch(const BagsUpdateLaunch& u, std::integer_sequence<int, I...>) {
-  static constexpr BagsUpdateFn kSmall[] = {launch_bags_small<WT, PAD, I>...};
-  static constexpr BagsUpdateFn kReduce[] = {launch_bags_reduce<WT, PAD, I>...};
+  static constexpr BagsUpdateFn kSmall[] = {launch_bags_small<WT, PAD, MEAN, I>...};
+  static constexpr BagsUpdateFn kReduce[] = {launch_bags_reduce<WT, PAD, MEAN, I>...};
   const int i = update_index(u.rule, u.v4, u.lrp);
   if (i < 0 || i >= (int)sizeof...(I) || (u.small != nullptr) == (u.red != nullptr)) return false;
   if (u.small) kSmall[i](u); else kReduce[i](u);
@@ -454,5 +474,9 @@ __attribute__((visibility("hidden"))) bool emb_bags_sort_pass(const BagsSortArgs
 __attribute__((visibility("hidden"))) bool emb_pad_update_launch_f32(const BagsUpdateLaunch& u);       // embedding_update_pad_f32.hip
 __attribute__((visibility("hidden"))) bool emb_pad_update_launch_bf16(const BagsUpdateLaunch& u);      // embedding_update_pad_bf16.hip
 __attribute__((visibility("hidden"))) bool emb_pad_sort_first_pass(const BagsSortArgs& a, int E, dim3 grid, hipStream_t stream);      // embedding_update_pad_f32.hip
+// the mean forms (include/ff_hip_pad_mean.h): the apply kernels that divide a gradient row by its bag's count of real lookups, and the kernel that counts
+__attribute__((visibility("hidden"))) bool emb_padmean_update_launch_f32(const BagsUpdateLaunch& u);   // embedding_update_padmean_f32.hip
+__attribute__((visibility("hidden"))) bool emb_padmean_update_launch_bf16(const BagsUpdateLaunch& u);  // embedding_update_padmean_bf16.hip
+__attribute__((visibility("hidden"))) void emb_padmean_count(const BagsCountArgs& a, hipStream_t stream);      // embedding_update_padmean_f32.hip
 
 }  // namespace ffh_emb

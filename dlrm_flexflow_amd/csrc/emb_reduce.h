@@ -146,11 +146,14 @@ struct RedShared {
 // one tile of one table; `partial_t` / `meta_t` are the table's level-0 slot arrays
 // PAD (include/ff_hip_pad.h; the ragged kernels' pad forms only): the sort loaded "no lookup" as key tb.num_entries, the largest key.  Its
 // sub-runs are dropped here: no sum, no row, no partial row and no slot record -- the folds walk slot records, so they never see the segment.
-template <int VEC, bool AGENT, RowRule R, class WT, bool PAD = false>
+// MEAN (include/ff_hip_pad_mean.h; PAD forms only): the divisor of entry i is the count of real lookups of its sample, cnt[s_pos[i]] (the
+// table's 16-bit counts, [batch]), read where the gradient row is loaded, in place of (float)L.  An entry that is summed is a real lookup, so
+// its count is at least 1.  With MEAN false the body is what it was.
+template <int VEC, bool AGENT, RowRule R, class WT, bool PAD = false, bool MEAN = false>
 __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const uint2* kp,
                                                  float* partial_t, uint2* meta_t, int64_t N, int nchunks, int tile, int tile_index,
                                                  int L, int D_, bool avg_, const OptP& op, float* st0, float* st1, const SrKey& sk, RedShared& sh, const int tid = threadIdx.x,
-                                                 const bool preloaded = false) {
+                                                 const bool preloaded = false, const uint16_t* __restrict__ cnt = nullptr) {
   uint32_t* s_key = sh.key;
   uint32_t* s_pos = sh.pos;
   uint16_t* s_start = sh.start;
@@ -217,6 +220,10 @@ __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const 
   const int gid = wave * rpw + rsub;
   const float Lf = (float)a.L;
   const bool avg = a.avg != 0;
+  auto div_of = [&](const int q) -> float {      // the divisor of sorted entry q of the tile
+    if constexpr (MEAN) return (float)cnt[s_pos[q]];
+    else return Lf;
+  };
 
   // (Several sub-runs per lane-group in flight at once were tried -- 2 and 4, with and without the registers capped for eight
   //  waves per SIMD -- and changed nothing: with every tile resident the kernel runs at the rate the memory system takes random
@@ -240,10 +247,10 @@ __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const 
       if constexpr (opt_rowwise(R)) {
         if (single) {      // the whole row at once; the sub-run's sum of vector c as the loop below forms it, in order
           apply_row_rowwise<VEC, WT>(op, wrow, st0 + key, D, nvec, lpr, c0, lane, [&](int c, float (&acc)[VEC]) {
-            load_grad<VEC>(acc, tb.io + (int64_t)s_pos[s] * tb.ld, c, Lf, avg);
+            load_grad<VEC>(acc, tb.io + (int64_t)s_pos[s] * tb.ld, c, div_of(s), avg);
             for (int q = s + 1; q < e; q++) {
               float v0[VEC];
-              load_grad<VEC>(v0, tb.io + (int64_t)s_pos[q] * tb.ld, c, Lf, avg);
+              load_grad<VEC>(v0, tb.io + (int64_t)s_pos[q] * tb.ld, c, div_of(q), avg);
 #pragma unroll
               for (int v = 0; v < VEC; v++) acc[v] = acc[v] + v0[v];
             }
@@ -253,21 +260,21 @@ __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const 
       }
       for (int c = c0; c < nvec; c += lpr) {
         float acc[VEC];
-        load_grad<VEC>(acc, tb.io + (int64_t)s_pos[s] * tb.ld, c, Lf, avg);
+        load_grad<VEC>(acc, tb.io + (int64_t)s_pos[s] * tb.ld, c, div_of(s), avg);
         int q = s + 1;
         // four independent row loads in flight, summed in order
         for (; q + 4 <= e; q += 4) {
           float v0[VEC], v1[VEC], v2[VEC], v3[VEC];
-          load_grad<VEC>(v0, tb.io + (int64_t)s_pos[q] * tb.ld, c, Lf, avg);
-          load_grad<VEC>(v1, tb.io + (int64_t)s_pos[q + 1] * tb.ld, c, Lf, avg);
-          load_grad<VEC>(v2, tb.io + (int64_t)s_pos[q + 2] * tb.ld, c, Lf, avg);
-          load_grad<VEC>(v3, tb.io + (int64_t)s_pos[q + 3] * tb.ld, c, Lf, avg);
+          load_grad<VEC>(v0, tb.io + (int64_t)s_pos[q] * tb.ld, c, div_of(q), avg);
+          load_grad<VEC>(v1, tb.io + (int64_t)s_pos[q + 1] * tb.ld, c, div_of(q + 1), avg);
+          load_grad<VEC>(v2, tb.io + (int64_t)s_pos[q + 2] * tb.ld, c, div_of(q + 2), avg);
+          load_grad<VEC>(v3, tb.io + (int64_t)s_pos[q + 3] * tb.ld, c, div_of(q + 3), avg);
 #pragma unroll
           for (int v = 0; v < VEC; v++) acc[v] = (((acc[v] + v0[v]) + v1[v]) + v2[v]) + v3[v];
         }
         for (; q < e; q++) {
           float v0[VEC];
-          load_grad<VEC>(v0, tb.io + (int64_t)s_pos[q] * tb.ld, c, Lf, avg);
+          load_grad<VEC>(v0, tb.io + (int64_t)s_pos[q] * tb.ld, c, div_of(q), avg);
 #pragma unroll
           for (int v = 0; v < VEC; v++) acc[v] = acc[v] + v0[v];
         }

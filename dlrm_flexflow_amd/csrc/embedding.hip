@@ -23,7 +23,7 @@
 #include "../../include/ff_hip_bags_update.h"
 #include "../../include/ff_hip_bags_sort.h"
 #include "emb_bags_update.h"
-#include "../../include/ff_hip_pad.h"
+#include "../../include/ff_hip_pad_mean.h"
 
 namespace {
 
@@ -617,8 +617,17 @@ inline int bags_dims_check(const int* in_dims, int nt, int64_t batch) {
 }
 
 typedef bool (*BagsUpdateOfFn)(const BagsUpdateLaunch&);
-constexpr BagsUpdateOfFn kBagsUpdateOf[2][2] = {{emb_bags_update_launch_f32, emb_bags_update_launch_bf16},      // [pad form][bf16 rows]
-                                                {emb_pad_update_launch_f32, emb_pad_update_launch_bf16}};
+constexpr BagsUpdateOfFn kBagsUpdateOf[3][2] = {{emb_bags_update_launch_f32, emb_bags_update_launch_bf16},      // [BagsForm][bf16 rows]
+                                                {emb_pad_update_launch_f32, emb_pad_update_launch_bf16},
+                                                {emb_padmean_update_launch_f32, emb_padmean_update_launch_bf16}};
+// the form of a ragged update call: plain, the pad form (include/ff_hip_pad.h) or the pad form with a mean over the lookups that are there
+// (include/ff_hip_pad_mean.h)
+enum BagsForm { kBagsPlain = 0, kBagsPad = 1, kBagsPadMean = 2 };
+
+// The mean form's counts: one uint16 per (table, bag), [table][batch], in a region behind the ragged layout -- the sort phase, which sizes and
+// writes only that layout, never touches it.
+inline size_t padmean_cnt_offset(const BagsLayout& lay) { return (lay.total + 15) & ~(size_t)15; }
+inline size_t padmean_total(const BagsLayout& lay, int nt, int64_t batch) { return padmean_cnt_offset(lay) + (((size_t)nt * (size_t)batch * 2 + 15) & ~(size_t)15); }
 
 // the sort phase alone reads idx and num_entries only (include/ff_hip_bags_sort.h): validate_tables without the weight / io / ld checks
 inline int validate_sort_tables(ffh_ctx* c, const ffh_emb_table* t, int nt, int D, int64_t batch) {
@@ -634,16 +643,22 @@ inline int validate_sort_tables(ffh_ctx* c, const ffh_emb_table* t, int nt, int 
 // include/ff_hip_bags_sort.h.  Same launches in the same order on the same workspace.
 // `pad` (include/ff_hip_pad.h): an id < 0 is no lookup.  Pass 0 of the sort loads it as key num_entries, so the radix plan covers one more key
 // per table, and the apply kernels drop that key's segment; the layout, the grids and the workspace are those of the call without pads.
+// kBagsPadMean (include/ff_hip_pad_mean.h; apply and fused only -- the sort is the pad form's): the apply phase first counts every bag's real
+// lookups into the region behind the layout (one small launch), and its kernels divide each gradient row by its bag's count.
 int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, int nt, int D, int64_t batch, int aggr, float lr, ffh_stream s,
                  const bool do_sort, const bool do_apply,
-                 const ffh_sparse_opt* opt, const ffh_emb_state* states, const Bf16Cfg* b16, const ffh_lr_state* lr_block, const bool pad) {
+                 const ffh_sparse_opt* opt, const ffh_emb_state* states, const Bf16Cfg* b16, const ffh_lr_state* lr_block, const BagsForm form) {
+  const bool pad = form != kBagsPlain, mean = form == kBagsPadMean;
   int rc = bags_dims_check(in_dims, nt, batch);
   if (rc == FFH_ERR_BAD_ARG) return ffh_fail(c, rc, "embedding_bwd_fused_multi_bags: ntables out of range, null in_dims or in_dims[i] < 1");
   if (rc) return ffh_fail(c, rc, "embedding_bwd_fused_multi_bags: in_dims[i] > FFH_BAGS_MAX_IN_DIM (65535) or batch*in_dims[i] >= 2^31");
   rc = do_apply ? validate_tables(c, tables, nt, 1, D, batch, aggr) : validate_sort_tables(c, tables, nt, D, batch);
   if (rc) return rc;
-  if (pad && aggr == FFH_AGGR_MODE_AVG)      // (a mean over the lookups that are there needs each bag's count in the apply phase)
+  if (pad && !mean && aggr == FFH_AGGR_MODE_AVG)      // (a mean over the lookups that are there needs each bag's count in the apply phase: include/ff_hip_pad_mean.h)
     return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags_pad: FFH_AGGR_MODE_AVG is not supported with pad ids");
+  if (mean && aggr != FFH_AGGR_MODE_AVG)
+    return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags_pad_mean: aggr must be FFH_AGGR_MODE_AVG (for a sum call ffh_embedding_bwd_fused_multi_bags_pad / "
+                                        "ffh_embedding_bwd_apply_multi_bags_pad)");
   UpdatePlan plan;
   rc = emb_update_rule(c, nt, D, batch, lr, do_apply, opt, states, b16, lr_block, &plan);
   if (rc) return rc;
@@ -654,6 +669,8 @@ int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, in
     return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags_pad: num_entries > 2^32 - 2");
   const BagsLayout lay = bags_layout(in_dims, nt, D, batch);
   if (!c->ws || c->ws_bytes < lay.total) return ffh_fail(c, FFH_ERR_WORKSPACE, "embedding_bwd_fused_multi_bags: workspace too small (ffh_embedding_bwd_bags_workspace_bytes)");
+  if (mean && c->ws_bytes < padmean_total(lay, nt, batch))
+    return ffh_fail(c, FFH_ERR_WORKSPACE, "embedding_bwd_fused_multi_bags_pad_mean: workspace too small (ffh_embedding_bwd_bags_pad_mean_workspace_bytes)");
   char* ws = (char*)c->ws;
   if (!aligned16(ws)) return ffh_fail(c, FFH_ERR_WORKSPACE, "embedding_bwd_fused_multi_bags: workspace must be 16-byte aligned");
   // One-shot, as in emb_bwd_phases: the apply phase consumes the sorted lists, the level-1 slots and the arrival counters that only the sort's
@@ -681,25 +698,34 @@ int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, in
   const int more_keys = pad ? 1 : 0;
   const RadixPlan rp = radix_plan(plan.maxR + more_keys);
   const int avg = aggr == FFH_AGGR_MODE_AVG ? 1 : 0;
+  uint16_t* const cnt = mean ? (uint16_t*)(ws + padmean_cnt_offset(lay)) : nullptr;
+  auto count_bags = [&]() {      // (the mean form's apply phase, ahead of its kernels on the stream)
+    BagsCountArgs ca;
+    memset(&ca, 0, sizeof ca);
+    for (int i = 0; i < nt; i++) { ca.idx[i] = tables[i].idx; ca.L[i] = (uint16_t)in_dims[i]; }
+    ca.cnt = cnt; ca.batch = batch; ca.nt = nt;
+    emb_padmean_count(ca, as_stream(s));
+  };
 
   if (lay.maxN <= kSmallMax) {
-    snprintf(c->emb_route, sizeof c->emb_route, pad ? "bags:small:pad" : "bags:small");
+    snprintf(c->emb_route, sizeof c->emb_route, mean ? "bags:small:pad:mean" : pad ? "bags:small:pad" : "bags:small");
     if (!do_apply) return FFH_OK;      // (the sort lives inside the one launch: the sort call only leaves the note)
+    if (mean) count_bags();
     BagsSmallArgs sm;
     memset(&sm, 0, sizeof sm);
     for (int i = 0; i < nt; i++) sm.t[i] = tables[i];
     fill_passes(tables, nt, rp.rb, sm.npass, nullptr, more_keys);
     sm.kp = (uint2*)(ws + lay.kp_a);
     set_ws_slots(sm, ws, lay);
-    sm.rb = rp.rb; sm.D = D; sm.avg = avg; sm.g = lay.g;
+    sm.rb = rp.rb; sm.D = D; sm.avg = avg; sm.g = lay.g; sm.cnt = cnt;
     set_rule_args(sm, plan, states, nt, b16);
-    if (!kBagsUpdateOf[more_keys][b16 ? 1 : 0](BagsUpdateLaunch{plan.rule, plan.v4, lr_block != nullptr, &sm, nullptr, dim3((unsigned)nt), as_stream(s)}))
+    if (!kBagsUpdateOf[form][b16 ? 1 : 0](BagsUpdateLaunch{plan.rule, plan.v4, lr_block != nullptr, &sm, nullptr, dim3((unsigned)nt), as_stream(s)}))
       return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags: no small-route kernel for this rule / weight type");
     FFH_LAUNCH_CHECK(c, "emb_bags_small_kernel");
     return FFH_OK;
   }
 
-  snprintf(c->emb_route, sizeof c->emb_route, pad ? "bags:lsd:passes=%d:pad" : "bags:lsd:passes=%d", rp.passes);
+  snprintf(c->emb_route, sizeof c->emb_route, mean ? "bags:lsd:passes=%d:pad:mean" : pad ? "bags:lsd:passes=%d:pad" : "bags:lsd:passes=%d", rp.passes);
   BagsSortArgs sa;
   memset(&sa, 0, sizeof sa);
   BagsRedArgs ra;
@@ -720,12 +746,13 @@ int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, in
   FFH_LAUNCH_CHECK(c, "bags radix sort");
   if (!do_apply) return FFH_OK;
 
+  if (mean) count_bags();
   ra.kp[0] = kbuf[0]; ra.kp[1] = kbuf[1];
   set_ws_slots(ra, ws, lay);
   ra.arrive = (uint32_t*)(ws + lay.arrive);
-  ra.D = D; ra.avg = avg; ra.g = lay.g;
+  ra.D = D; ra.avg = avg; ra.g = lay.g; ra.cnt = cnt;
   set_rule_args(ra, plan, states, nt, b16);
-  if (!kBagsUpdateOf[more_keys][b16 ? 1 : 0](BagsUpdateLaunch{plan.rule, plan.v4, lr_block != nullptr, nullptr, &ra, rgrid, as_stream(s)}))
+  if (!kBagsUpdateOf[form][b16 ? 1 : 0](BagsUpdateLaunch{plan.rule, plan.v4, lr_block != nullptr, nullptr, &ra, rgrid, as_stream(s)}))
     return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags: no reduce kernel for this rule / weight type");
   FFH_LAUNCH_CHECK(c, "emb_bags_reduce/fold");
   return FFH_OK;
@@ -745,7 +772,7 @@ size_t ffh_embedding_bwd_bags_workspace_bytes(const int* in_dims, int nt, int D,
 
 // the descriptor of the three ragged entries: the fused call (do_sort && do_apply) and the pair of include/ff_hip_bags_sort.h.  The sort phase
 // takes the fields it reads (tables, in_dims, ntables, out_dim, batch) and nothing else.
-static int emb_bwd_bags_desc(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s, const bool do_sort, const bool do_apply, const bool pad = false) {
+static int emb_bwd_bags_desc(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s, const bool do_sort, const bool do_apply, const BagsForm pad = kBagsPlain) {
   if (!u) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: null descriptor");
   if ((u->tables != nullptr) == (u->tables_bf16 != nullptr)) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: exactly one of tables / tables_bf16");
   if (do_apply && u->lr_block && !u->opt) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: lr_block needs opt");
@@ -772,8 +799,16 @@ int ffh_embedding_bwd_sort_multi_bags(ffh_ctx* c, const ffh_bags_update* u, ffh_
 int ffh_embedding_bwd_apply_multi_bags(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, false, true); }
 
 // include/ff_hip_pad.h: the three entries above with an id < 0 as no lookup
-int ffh_embedding_bwd_fused_multi_bags_pad(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, true, true, true); }
-int ffh_embedding_bwd_sort_multi_bags_pad(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, true, false, true); }
-int ffh_embedding_bwd_apply_multi_bags_pad(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, false, true, true); }
+int ffh_embedding_bwd_fused_multi_bags_pad(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, true, true, kBagsPad); }
+int ffh_embedding_bwd_sort_multi_bags_pad(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, true, false, kBagsPad); }
+int ffh_embedding_bwd_apply_multi_bags_pad(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, false, true, kBagsPad); }
+
+// include/ff_hip_pad_mean.h: the fused call and the apply with a mean over the lookups that are there (the sort is the pad sort above)
+size_t ffh_embedding_bwd_bags_pad_mean_workspace_bytes(const int* in_dims, int nt, int D, int64_t batch) {
+  if (nt <= 0 || D <= 0 || batch <= 0 || bags_dims_check(in_dims, nt, batch) != FFH_OK) return 0;
+  return padmean_total(bags_layout(in_dims, nt, D, batch), nt, batch);
+}
+int ffh_embedding_bwd_fused_multi_bags_pad_mean(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, true, true, kBagsPadMean); }
+int ffh_embedding_bwd_apply_multi_bags_pad_mean(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, false, true, kBagsPadMean); }
 
 }  // extern "C"

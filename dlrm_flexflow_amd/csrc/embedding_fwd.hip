@@ -10,7 +10,8 @@
 //     `int outputSize` [ref: src/ops/embedding.cu:226,229] would overflow).
 // What is here:
 //   * emb_fwd_kernel: one bag size for all tables (grid.y = table);
-//   * emb_fwd_bags_kernel: a bag size per table (include/ff_hip_bags.h), a flat grid; its PAD form skips ids < 0 (include/ff_hip_pad.h);
+//   * emb_fwd_bags_kernel: a bag size per table (include/ff_hip_bags.h), a flat grid; its PAD form skips ids < 0 (include/ff_hip_pad.h), its
+//     MEAN form also divides by the count of the ids it did not skip (include/ff_hip_pad_mean.h);
 //   * gather_form: the 16-byte form, on the host, for both launchers; the entries
 //     ffh_embedding_fwd*, fp32 and bf16 tables.
 //   * RowLanes: the lane geometry of both kernels;
@@ -19,7 +20,7 @@
 // (embedding_q8.hip); the table update, the dense backward and the
 // bf16 helpers are embedding.hip; the checks on a table list shared with them are emb_tables.h.
 #include "emb_gather.h"
-#include "../../include/ff_hip_pad.h"
+#include "../../include/ff_hip_pad_mean.h"
 
 #include <type_traits>
 
@@ -158,7 +159,9 @@ static_assert(sizeof(BagArgs) <= sizeof(EmbArgs) && sizeof(BagArgs) <= 4096, "ke
 // the rows [first, first + step, ...) x rows_per_block of table t; U rows x JU ids in flight per lane-group
 // PAD (include/ff_hip_pad.h): an id < 0 is no lookup.  The id is the same in the lanes that share a row and differs between the row groups of a
 // wave, so the row load and the add are predicated on it beside ok[u], not branched around; acc keeps its +0 where nothing is added.
-template <int VEC, int U, int JU, class WT, bool PAD = false>
+// MEAN (include/ff_hip_pad_mean.h; PAD forms only): the lanes that share a row count its ids >= 0 where the add is predicated, and the row is
+// stored times 1 / max(count, 1) -- store_row's AVG epilogue with a divisor per row.  With PAD or MEAN false the kernel is what it was.
+template <int VEC, int U, int JU, class WT, bool PAD = false, bool MEAN = false>
 __device__ __forceinline__ void bag_rows(const BagArgs& a, const int t, const int64_t first, const int64_t step) {
   using vec_t = typename RowVec<VEC, WT>::type;
   const ffh_emb_table tb = a.t[t];
@@ -189,6 +192,9 @@ __device__ __forceinline__ void bag_rows(const BagArgs& a, const int t, const in
       for (int u = 0; u < U; u++)
 #pragma unroll
         for (int v = 0; v < VEC; v++) acc[u][v] = 0.0f;
+      int live[U];      // (MEAN: the row's lookups that are there)
+#pragma unroll
+      for (int u = 0; u < U; u++) live[u] = 0;
       int j = 0;
       if constexpr (JU > 1) {
         for (; j + JU <= L; j += JU) {
@@ -211,6 +217,7 @@ __device__ __forceinline__ void bag_rows(const BagArgs& a, const int t, const in
                 if (!PAD || row[u][k] >= 0) {
 #pragma unroll
                   for (int v = 0; v < VEC; v++) acc[u][v] = acc[u][v] + row_elem<VEC, WT>(val[u][k], v);
+                  if constexpr (MEAN) live[u]++;
                 }
             }
         }
@@ -228,16 +235,20 @@ __device__ __forceinline__ void bag_rows(const BagArgs& a, const int t, const in
           if (PAD ? ok[u] && row[u] >= 0 : ok[u]) {
 #pragma unroll
             for (int v = 0; v < VEC; v++) acc[u][v] = acc[u][v] + row_elem<VEC, WT>(val[u], v);   // 0 + w first, as emb_fwd_kernel
+            if constexpr (MEAN) live[u]++;
           }
       }
 #pragma unroll
       for (int u = 0; u < U; u++)
-        if (ok[u]) store_row<VEC>(tb, o16, o3, o3c, b0 + (int64_t)u * g.rpw, c, acc[u], avg, inv);
+        if (ok[u]) {
+          if constexpr (MEAN) store_row<VEC>(tb, o16, o3, o3c, b0 + (int64_t)u * g.rpw, c, acc[u], true, 1.0f / (float)(live[u] > 1 ? live[u] : 1));
+          else store_row<VEC>(tb, o16, o3, o3c, b0 + (int64_t)u * g.rpw, c, acc[u], avg, inv);
+        }
     }
   }
 }
 
-template <int VEC, class WT, bool PAD = false>
+template <int VEC, class WT, bool PAD = false, bool MEAN = false>
 __global__ __launch_bounds__(256) void emb_fwd_bags_kernel(const BagArgs a) {
   ffh_kernel_prio();
   // workgroup -> (table, first row block of the table): block-uniform
@@ -250,8 +261,8 @@ __global__ __launch_bounds__(256) void emb_fwd_bags_kernel(const BagArgs a) {
     first -= w;
   }
   if (t >= a.ntables) return;
-  if (a.L[t] >= kBagLong) bag_rows<VEC, 2, 4, WT, PAD>(a, t, first, w);
-  else bag_rows<VEC, 4, 1, WT, PAD>(a, t, first, w);
+  if (a.L[t] >= kBagLong) bag_rows<VEC, 2, 4, WT, PAD, MEAN>(a, t, first, w);
+  else bag_rows<VEC, 4, 1, WT, PAD, MEAN>(a, t, first, w);
 }
 
 // ---- host side, both launchers.  WT = float: fp32 tables; WT = uint16_t: `tables[i].weight` holds bf16 bits. ----
@@ -305,12 +316,14 @@ int emb_fwd_launch(ffh_ctx* c, const ffh_emb_table* tables, int nt, int L, int D
   return FFH_OK;
 }
 
-template <class WT, bool PAD = false>
+template <class WT, bool PAD = false, bool MEAN = false>
 int emb_fwd_bags_launch(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, int nt, int D, int64_t batch, int aggr, ffh_stream s) {
   int rc = validate_tables(c, tables, nt, 1, D, batch, aggr);
   if (rc) return rc;
-  if (PAD && aggr == FFH_AGGR_MODE_AVG)      // (a mean over the lookups that are there needs each bag's count: include/ff_hip_pad.h)
+  if (PAD && !MEAN && aggr == FFH_AGGR_MODE_AVG)      // (a mean over the lookups that are there needs each bag's count: include/ff_hip_pad_mean.h)
     return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_fwd_multi_bags_pad: FFH_AGGR_MODE_AVG is not supported with pad ids");
+  if (MEAN && aggr != FFH_AGGR_MODE_AVG)
+    return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_fwd_multi_bags_pad_mean: aggr must be FFH_AGGR_MODE_AVG (for a sum call ffh_embedding_fwd_multi_bags_pad)");
   if (nt > 0 && !in_dims) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_fwd_multi_bags: null in_dims");
   for (int i = 0; i < nt; i++) {
     if (in_dims[i] < 1) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_fwd_multi_bags: in_dims[i] < 1");
@@ -339,8 +352,8 @@ int emb_fwd_bags_launch(ffh_ctx* c, const ffh_emb_table* tables, const int* in_d
     a.shift = sh;
     if (total <= cap) break;
   }
-  if (vec == 4) hipLaunchKernelGGL((emb_fwd_bags_kernel<4, WT, PAD>), dim3((unsigned)total), dim3(256), 0, as_stream(s), a);
-  else hipLaunchKernelGGL((emb_fwd_bags_kernel<1, WT, PAD>), dim3((unsigned)total), dim3(256), 0, as_stream(s), a);
+  if (vec == 4) hipLaunchKernelGGL((emb_fwd_bags_kernel<4, WT, PAD, MEAN>), dim3((unsigned)total), dim3(256), 0, as_stream(s), a);
+  else hipLaunchKernelGGL((emb_fwd_bags_kernel<1, WT, PAD, MEAN>), dim3((unsigned)total), dim3(256), 0, as_stream(s), a);
   FFH_LAUNCH_CHECK(c, "emb_fwd_bags_kernel");
   return FFH_OK;
 }
@@ -393,6 +406,21 @@ int ffh_embedding_fwd_multi_bags_pad_bf16(ffh_ctx* c, const ffh_emb_table_bf16* 
   const int rc = bf16_tables(c, tables, nt, t, nullptr);
   if (rc) return rc;
   return emb_fwd_bags_launch<uint16_t, true>(c, t, in_dims, nt, D, batch, aggr, s);
+}
+
+// include/ff_hip_pad_mean.h: the pad gather with a mean over the lookups that are there
+int ffh_pad_mean_abi_version(void) { return FFH_PAD_MEAN_ABI_VERSION; }
+
+int ffh_embedding_fwd_multi_bags_pad_mean(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, int nt, int D, int64_t batch, int aggr, ffh_stream s) {
+  return emb_fwd_bags_launch<float, true, true>(c, tables, in_dims, nt, D, batch, aggr, s);
+}
+
+int ffh_embedding_fwd_multi_bags_pad_mean_bf16(ffh_ctx* c, const ffh_emb_table_bf16* tables, const int* in_dims, int nt, int D, int64_t batch, int aggr,
+                                               ffh_stream s) {
+  ffh_emb_table t[FFH_MAX_TABLES];
+  const int rc = bf16_tables(c, tables, nt, t, nullptr);
+  if (rc) return rc;
+  return emb_fwd_bags_launch<uint16_t, true, true>(c, t, in_dims, nt, D, batch, aggr, s);
 }
 
 }  // extern "C"

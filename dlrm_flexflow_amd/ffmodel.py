@@ -138,7 +138,7 @@ def lib() -> C.CDLL:
         "flexflow_tensor_get_data_type": (I, [H]),
         "flexflow_tensor_set_bf16": (None, [H, H, IP, I, P]), "flexflow_tensor_get_bf16": (None, [H, H, P]),
         "flexflow_dlrm_create": (H, [I, C.POINTER(C.c_char_p), C.POINTER(FFComm)]), "flexflow_dlrm_destroy": (None, [H]),
-        "flexflow_dlrm_get_model": (H, [H]), "flexflow_dlrm_get_num_samples": (I, [H]), "flexflow_dlrm_get_num_tables": (I, [H]), "flexflow_dlrm_get_bag_size": (I, [H, I]), "flexflow_dlrm_get_bag_fill": (D, [H]), "flexflow_dlrm_get_start_epoch": (I, [H]),
+        "flexflow_dlrm_get_model": (H, [H]), "flexflow_dlrm_get_num_samples": (I, [H]), "flexflow_dlrm_get_num_tables": (I, [H]), "flexflow_dlrm_get_bag_size": (I, [H, I]), "flexflow_dlrm_get_bag_fill": (D, [H]), "flexflow_dlrm_get_embedding_pooling": (C.c_char_p, [H]), "flexflow_dlrm_get_start_epoch": (I, [H]),
         "flexflow_dlrm_get_sparse_input": (H, [H, I]), "flexflow_dlrm_get_dense_input": (H, [H]),
         "flexflow_dlrm_warmup": (None, [H]), "flexflow_dlrm_train_steps": (None, [H, I, B]),
         "flexflow_dlrm_run_epochs": (D, [H]), "flexflow_dlrm_time_kernel": (F, [H, I, I]),
@@ -220,14 +220,24 @@ def pad_mask_reference(seed: int, first: int, count: int, fill: float) -> np.nda
     return u < np.float32(fill)
 
 
-def padded_bag_reference(W, idx) -> np.ndarray:
+def padded_bag_counts(idx) -> np.ndarray:
+    """count[b] of include/ff_hip_pad_mean.h: the ids >= 0 in bag b of `idx` [batch][L], as int64."""
+    return (np.asarray(idx, np.int64) >= 0).sum(axis=1).astype(np.int64)
+
+
+def padded_bag_reference(W, idx, mean: bool = False) -> np.ndarray:
     """The pad gather of include/ff_hip_pad.h in numpy: out[b] = sum of W[idx[b][j]] over the j, ascending, whose id is not negative, in
-    fp32 starting from +0.  `W` is [rows][D] float32, `idx` [batch][L] integers; a bag of only pads gives a row of +0."""
+    fp32 starting from +0.  `W` is [rows][D] float32, `idx` [batch][L] integers; a bag of only pads gives a row of +0.
+    `mean`: the mean gather of include/ff_hip_pad_mean.h -- that sum times float32(1) / float32(max(count, 1)), one fp32 reciprocal and one
+    fp32 multiply per element."""
     W, idx = np.asarray(W, np.float32), np.asarray(idx, np.int64)
     out = np.zeros((idx.shape[0], W.shape[1]), np.float32)
     for j in range(idx.shape[1]):
         live = idx[:, j] >= 0
         out[live] = out[live] + W[idx[live, j]]
+    if mean:
+        inv = np.float32(1) / np.maximum(padded_bag_counts(idx), 1).astype(np.float32)
+        out = out * inv[:, None]
     return out
 
 
@@ -816,6 +826,7 @@ class DLRM:
 
     num_samples = property(lambda s: lib().flexflow_dlrm_get_num_samples(s.h))
     num_tables = property(lambda s: lib().flexflow_dlrm_get_num_tables(s.h))
+    embedding_pooling = property(lambda s: lib().flexflow_dlrm_get_embedding_pooling(s.h).decode())      # --embedding-pooling: "sum" or "mean"
     bag_fill = property(lambda s: float(lib().flexflow_dlrm_get_bag_fill(s.h)))      # --synthetic-bag-fill: the share of a synthetic bag's slots that hold a lookup (1: every slot)
     bag_sizes = property(lambda s: [lib().flexflow_dlrm_get_bag_size(s.h, t) for t in range(s.num_tables)])      # ids per sample, per table (--embedding-bag-size / --embedding-bag-sizes)
     start_epoch = property(lambda s: lib().flexflow_dlrm_get_start_epoch(s.h))      # --load-checkpoint: the epochs the checkpoint had completed

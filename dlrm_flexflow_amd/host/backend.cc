@@ -277,6 +277,23 @@ const KernelApi* load_kernel_api(const std::string& path_in) {
     }
     api->pad = b;
   }
+  // the pad-mean extension (include/ff_hip_pad_mean.h): the same rule
+  if (dlsym(h, "ffh_pad_mean_abi_version")) {
+    KernelApiPadMean* b = new KernelApiPadMean();
+#define FFH_LOAD(name)                                                        \
+  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
+  if (!b->name) {                                                             \
+    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_pad_mean.h: %s is missing\n", path.c_str(), #name);   \
+    abort();                                                                  \
+  }
+    FFH_PAD_MEAN_API_LIST(FFH_LOAD)
+#undef FFH_LOAD
+    if (b->ffh_pad_mean_abi_version() != FFH_PAD_MEAN_ABI_VERSION) {
+      fprintf(stderr, "FATAL: %s has pad-mean ABI version %d, expected %d\n", path.c_str(), b->ffh_pad_mean_abi_version(), FFH_PAD_MEAN_ABI_VERSION);
+      abort();
+    }
+    api->pad_mean = b;
+  }
   // the q8 extension (include/ff_hip_q8.h): the same rule
   if (dlsym(h, "ffh_q8_abi_version")) {
     KernelApiQ8* b = new KernelApiQ8();

@@ -17,6 +17,7 @@
 #include "../../include/ff_hip_bags_update.h"
 #include "../../include/ff_hip_bags_sort.h"
 #include "../../include/ff_hip_pad.h"
+#include "../../include/ff_hip_pad_mean.h"
 #include "../../include/ff_hip_q8.h"
 
 // The optional bf16-table extension (include/ff_hip_bf16.h): all of its list or none of it.
@@ -110,6 +111,13 @@ struct KernelApiPad {
 #undef FFH_DECL
 };
 
+// The optional pad-mean extension (include/ff_hip_pad_mean.h: the pad entries' mean forms, the divisor being a bag's count of real lookups).
+struct KernelApiPadMean {
+#define FFH_DECL(name) decltype(&::name) name;
+  FFH_PAD_MEAN_API_LIST(FFH_DECL)
+#undef FFH_DECL
+};
+
 // The optional q8 extension (include/ff_hip_q8.h: tables as 8-bit rows for held-out evaluation, their quantizer and gathers).
 struct KernelApiQ8 {
 #define FFH_DECL(name) decltype(&::name) name;
@@ -134,6 +142,7 @@ struct KernelApi {
   const KernelApiBagsUpdate* bags_update = nullptr;   // likewise for include/ff_hip_bags_update.h (absent: a model of mixed bag sizes updates once per bag size)
   const KernelApiBagsSort* bags_sort = nullptr;       // likewise for include/ff_hip_bags_sort.h (absent: a model of mixed bag sizes sorts in front of its apply)
   const KernelApiPad* pad = nullptr;                  // likewise for include/ff_hip_pad.h (absent: compile() refuses --embedding-padding)
+  const KernelApiPadMean* pad_mean = nullptr;         // likewise for include/ff_hip_pad_mean.h (absent: compile() refuses AGGR_MODE_AVG on a padded table)
   const KernelApiQ8* q8 = nullptr;                    // likewise for include/ff_hip_q8.h (absent: compile() refuses --eval-embedding-dtype int8)
   void* handle;
   std::string path;

@@ -67,6 +67,16 @@ void parse_input_args(char** argv, int argc, DLRMConfig& config) {
         config.bag_fill_given = true;
         continue;
       }
+      if (is("--embedding-pooling")) {      // how a bag's rows become one: the sum (the default, the reference's), or the mean
+        const std::string v(next());
+        if (v != "sum" && v != "mean") {
+          fprintf(stderr, "FATAL: --embedding-pooling %s: 'sum' or 'mean'\n", v.c_str());
+          abort();
+        }
+        config.mean_pooling = v == "mean";
+        config.pooling_given = true;
+        continue;
+      }
       if (is("--dcn-num-layers")) { config.dcn_num_layers = atoi(next()); continue; }
       if (is("--dcn-low-rank-dim")) { config.dcn_low_rank_dim = atoi(next()); continue; }
     }
@@ -101,12 +111,12 @@ Tensor create_mlp(FFModel* model, const Tensor& input, std::vector<int> ln, int 
   return t;
 }
 
-// [ref: examples/cpp/DLRM/dlrm.cc:41-47]: U(-sqrt(1/R), sqrt(1/R)), AGGR_MODE_SUM
-Tensor create_emb(FFModel* model, const Tensor& input, int input_dim, int output_dim, int idx) {
+// [ref: examples/cpp/DLRM/dlrm.cc:41-47]: U(-sqrt(1/R), sqrt(1/R)), AGGR_MODE_SUM (`aggr`: --embedding-pooling mean gives AGGR_MODE_AVG)
+Tensor create_emb(FFModel* model, const Tensor& input, int input_dim, int output_dim, int idx, AggrMode aggr) {
   (void)idx;
   float range = std::sqrt(1.0f / input_dim);
   Initializer* embed_init = model->own(new UniformInitializer(model->next_seed(), -range, range));
-  return model->embedding(input, input_dim, output_dim, AGGR_MODE_SUM, NULL /*weight_sharing*/, embed_init);
+  return model->embedding(input, input_dim, output_dim, aggr, NULL /*weight_sharing*/, embed_init);
 }
 
 // [ref: examples/cpp/DLRM/dlrm.cc:49-65]: the reference implements "cat" and asserts on "dot" (a TODO).
@@ -474,7 +484,7 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
   Tensor x = create_mlp(ff, dense_input, dlrm.mlp_bot, dlrm.sigmoid_bot);
   std::vector<Tensor> ly;
   for (size_t i = 0; i < dlrm.embedding_size.size(); i++)
-    ly.push_back(create_emb(ff, sparse_inputs[i], dlrm.embedding_size[i], dlrm.sparse_feature_size, (int)i));
+    ly.push_back(create_emb(ff, sparse_inputs[i], dlrm.embedding_size[i], dlrm.sparse_feature_size, (int)i, dlrm.mean_pooling ? AGGR_MODE_AVG : AGGR_MODE_SUM));
   Tensor z = interact_features(ff, x, ly, dlrm.arch_interaction_op, dlrm.dcn_num_layers, dlrm.dcn_low_rank_dim);
   create_mlp(ff, z, dlrm.mlp_top, (int)dlrm.mlp_top.size() - 2);
   if (dlrm.loss_threshold > 0.0f && dlrm.loss_threshold < 1.0f) {
@@ -520,6 +530,9 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
   }
   ff->compile(optimizer, (LossType)ffconfig.driver_loss, metrics);
   if (chatty && ffconfig.embedding_padding) printf("[DLRM] embedding padding: id -1 is no lookup (synthetic fill %g)\n", dlrm.synthetic_bag_fill);
+  // --embedding-pooling, only when given: a mean divides by a table's bag size L_t, or under --embedding-padding by the lookups a bag really has
+  if (chatty && dlrm.pooling_given)
+    printf("[DLRM] embedding pooling: %s\n", !dlrm.mean_pooling ? "sum" : ffconfig.embedding_padding ? "mean (over the lookups that are there)" : "mean (over L_t slots)");
   if (chatty && !dlrm.embedding_bag_sizes.empty()) printf("[DLRM] embedding gather: %s\n", ff->bag_gather_line().c_str());      // a per-table list: how the gather runs
   if (chatty && ff->mixed_bags && ff->fused_embedding_update()) printf("[DLRM] embedding update: %s\n", ff->bag_update_line().c_str());      // ... and, where the sizes differ, the update
   if (const AdagradOptimizer* ag = dynamic_cast<const AdagradOptimizer*>(optimizer)) {

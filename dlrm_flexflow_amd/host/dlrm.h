@@ -24,6 +24,8 @@ struct DLRMConfig {
   std::string optimizer;   // --optimizer sgd (default, the reference driver's) | sgd-momentum | adam | adagrad (not a reference flag)
   double synthetic_bag_fill = 1.0;   // --synthetic-bag-fill F, 0 < F <= 1 (with --embedding-padding): a synthetic slot holds a lookup with probability F (not a reference flag)
   bool bag_fill_given = false;
+  bool mean_pooling = false;         // --embedding-pooling sum|mean: every table pools with AGGR_MODE_AVG instead of AGGR_MODE_SUM (not a reference flag)
+  bool pooling_given = false;
   double zipf_alpha;   // > 0: synthetic ids follow a power law instead of the reference's uniform draw (not a reference flag)
   int dcn_num_layers, dcn_low_rank_dim;   // --arch-interaction-op dcn: --dcn-num-layers L (3), --dcn-low-rank-dim R (512) (not reference flags)
 };
@@ -31,7 +33,7 @@ struct DLRMConfig {
 void parse_input_args(char** argv, int argc, DLRMConfig& config);
 
 Tensor create_mlp(FFModel* model, const Tensor& input, std::vector<int> ln, int sigmoid_layer);
-Tensor create_emb(FFModel* model, const Tensor& input, int input_dim, int output_dim, int idx);
+Tensor create_emb(FFModel* model, const Tensor& input, int input_dim, int output_dim, int idx, AggrMode aggr = AGGR_MODE_SUM);
 Tensor interact_features(FFModel* model, const Tensor& x, const std::vector<Tensor>& ly, std::string interaction, int dcn_num_layers = 3,
                          int dcn_low_rank_dim = 512);
 

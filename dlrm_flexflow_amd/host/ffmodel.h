@@ -747,6 +747,8 @@ class FFModel {
   std::string q8_line() const;                // the driver's start-up line
   mutable int64_t n_pad_gathers = 0;          // ffh_embedding_fwd_multi_bags_pad[_bf16] launches (--embedding-padding; "pad_gather_launches")
   mutable int64_t n_pad_updates = 0;          // ffh_embedding_bwd_fused_multi_bags_pad / ffh_embedding_bwd_apply_multi_bags_pad calls ("pad_update_launches")
+  mutable int64_t n_pad_mean_gathers = 0;     // ffh_embedding_fwd_multi_bags_pad_mean[_bf16] launches (padded tables with AGGR_MODE_AVG; "pad_mean_gather_launches")
+  mutable int64_t n_pad_mean_updates = 0;     // ffh_embedding_bwd_fused_multi_bags_pad_mean / ffh_embedding_bwd_apply_multi_bags_pad_mean calls ("pad_mean_update_launches")
   bool bags_path() const { return mixed_bags || config.embedding_padding; }      // the tables go through the ragged entries: their bag sizes differ, or an id may be a pad
   mutable int64_t n_ragged_updates = 0;       // ffh_embedding_bwd_fused_multi_bags calls (tests: flexflow_model_get_counter "ragged_update_launches")
   bool ragged_update_on() const;              // the tables' bag sizes differ and their fused update is the ragged call (the library has it, the flag allows it)

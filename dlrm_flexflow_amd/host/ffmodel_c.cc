@@ -182,6 +182,8 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   if (n == "ragged_early_sorts") return M(m)->n_ragged_early_sorts;      // ffh_embedding_bwd_sort_multi_bags calls among them (include/ff_hip_bags_sort.h)
   if (n == "ragged_update_launches") return M(m)->n_ragged_updates;      // ffh_embedding_bwd_fused_multi_bags calls (mixed bag sizes; include/ff_hip_bags_update.h)
   if (n == "pad_gather_launches") return M(m)->n_pad_gathers;      // ffh_embedding_fwd_multi_bags_pad[_bf16] launches (--embedding-padding; include/ff_hip_pad.h)
+  if (n == "pad_mean_gather_launches") return M(m)->n_pad_mean_gathers;      // ffh_embedding_fwd_multi_bags_pad_mean[_bf16] launches (include/ff_hip_pad_mean.h)
+  if (n == "pad_mean_update_launches") return M(m)->n_pad_mean_updates;      // ffh_embedding_bwd_{fused,apply}_multi_bags_pad_mean calls
   if (n == "pad_update_launches") return M(m)->n_pad_updates;      // ffh_embedding_bwd_{fused,apply}_multi_bags_pad calls
   if (n == "q8_quantize_launches") return M(m)->n_q8_quantize;      // ffh_embedding_quantize_q8 launches (--eval-embedding-dtype int8; include/ff_hip_q8.h)
   if (n == "q8_gather_launches") return M(m)->n_q8_gathers;         // ffh_embedding_fwd_multi[_bags]_q8 launches
@@ -243,6 +245,7 @@ int flexflow_dlrm_get_num_samples(flexflow_dlrm_t h) { return A(h)->loader->num_
 int flexflow_dlrm_get_num_tables(flexflow_dlrm_t h) { return (int)A(h)->sparse_inputs.size(); }
 int flexflow_dlrm_get_bag_size(flexflow_dlrm_t h, int t) { return A(h)->dlrm.bag_of((size_t)t); }
 double flexflow_dlrm_get_bag_fill(flexflow_dlrm_t h) { return A(h)->dlrm.synthetic_bag_fill; }
+const char* flexflow_dlrm_get_embedding_pooling(flexflow_dlrm_t h) { return A(h)->dlrm.mean_pooling ? "mean" : "sum"; }
 flexflow_tensor_t flexflow_dlrm_get_sparse_input(flexflow_dlrm_t h, int t) { return wrap(A(h)->sparse_inputs.at(t)); }
 flexflow_tensor_t flexflow_dlrm_get_dense_input(flexflow_dlrm_t h) { return wrap(A(h)->dense_input); }
 void flexflow_dlrm_warmup(flexflow_dlrm_t h) { A(h)->warmup(); }

@@ -179,6 +179,7 @@ flexflow_model_t flexflow_dlrm_get_model(flexflow_dlrm_t);
 int  flexflow_dlrm_get_num_samples(flexflow_dlrm_t);
 int  flexflow_dlrm_get_num_tables(flexflow_dlrm_t);
 int  flexflow_dlrm_get_bag_size(flexflow_dlrm_t, int table);      /* ids per sample of table `table` (--embedding-bag-size, or its entry of --embedding-bag-sizes) */
+const char* flexflow_dlrm_get_embedding_pooling(flexflow_dlrm_t);   /* --embedding-pooling: "sum" (the default) or "mean" (every table pools with AGGR_MODE_AVG) */
 double flexflow_dlrm_get_bag_fill(flexflow_dlrm_t);             /* --synthetic-bag-fill: the share of a synthetic bag's slots that hold a lookup (with --embedding-padding; 1: all) */
 int  flexflow_dlrm_get_start_epoch(flexflow_dlrm_t);   /* --load-checkpoint: the epochs the checkpoint had completed (0 without it) */
 flexflow_tensor_t flexflow_dlrm_get_sparse_input(flexflow_dlrm_t, int table);

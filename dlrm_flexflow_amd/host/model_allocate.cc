@@ -157,9 +157,10 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
   // update, and nowhere else.  Every path that would hand such an id to another kernel is refused here, each with the flag to drop -- before the library checks, as below.
   if (config.embedding_padding && !embeddings.empty()) {
     for (const Embedding* e : embeddings) {
-      if (e->aggr == AGGR_MODE_AVG)
-        die("--embedding-padding: %s pools with AGGR_MODE_AVG; a mean over the lookups that are there needs each bag's count, which the pad kernels do not "
-            "keep: use AGGR_MODE_SUM or drop --embedding-padding", e->name);
+      if (e->aggr == AGGR_MODE_AVG && !api->pad_mean)      // (the mean forms of the pad entries: launch_shard_groups takes them where they are there)
+        die("--embedding-padding: %s pools with AGGR_MODE_AVG; a mean over the lookups that are there needs each bag's count, which the pad kernels of %s "
+            "(%s) do not keep (include/ff_hip_pad_mean.h is missing): use AGGR_MODE_SUM or drop --embedding-padding", e->name, api->path.c_str(),
+            api->ffh_backend_name());
       if (e->row_sharded)
         die("--embedding-padding: %s is row-sharded (its ids are localized onto a zero row, a path that takes no pad id); padded tables are table-wise: drop "
             "--row-shard-rows or drop --embedding-padding", e->name);
@@ -945,6 +946,9 @@ void FFModel::allocate() {
         for (size_t b = 0; b < kv.second.size(); b += per) {
           const int n = (int)std::min(per, kv.second.size() - b);
           workspace_bytes = std::max(workspace_bytes, api->bags_update->ffh_embedding_bwd_bags_workspace_bytes(kv.second.data() + b, n, kv.first.first, config.batchSize) + 256);
+          // (a padded table that pools with AGGR_MODE_AVG: the mean update keeps its bags' counts behind that layout, include/ff_hip_pad_mean.h)
+          if (config.embedding_padding && api->pad_mean && embeddings[0]->aggr == AGGR_MODE_AVG)
+            workspace_bytes = std::max(workspace_bytes, api->pad_mean->ffh_embedding_bwd_bags_pad_mean_workspace_bytes(kv.second.data() + b, n, kv.first.first, config.batchSize) + 256);
         }
       }
     }

@@ -30,6 +30,10 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
   const bool ragged = fwd ? ff->ragged_gather_on() : (what == kFusedUpdate ? ff->ragged_update_on() : ff->ragged_early_sort_on());
   const bool pad = ff->config.embedding_padding;
   const KernelApiPad* pda = ff->api->pad;
+  // ... and a padded table that pools with AGGR_MODE_AVG takes their mean forms (include/ff_hip_pad_mean.h; compile() has checked that the library has
+  // them): the gather, the fused update and the apply.  The early sort stays the pad sort, which serves either apply.
+  const bool pad_mean = pad && aggr == FFH_AGGR_MODE_AVG;
+  const KernelApiPadMean* pma = ff->api->pad_mean;
   struct Group { std::vector<ffh_emb_table> t; std::vector<ffh_emb_table_bf16> t16; std::vector<ffh_emb_state> st; std::vector<int> bag;
                  std::vector<ffh_emb_table_q8> tq; std::vector<int> bagq; };      // tq, bagq: the tables an evaluation gathers from their 8-bit row images
   // --eval-embedding-dtype int8: the gather of eval_batch() reads the images (include/ff_hip_q8.h), in the same groups.  eval_batch() has made stale images
@@ -89,6 +93,12 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
         ff->n_early_sorts++; ff->n_ragged_early_sorts++;
         return;
       }
+      if (pad_mean) {
+        if (what == kApplyOnly) ff->check(pma->ffh_embedding_bwd_apply_multi_bags_pad_mean(cx, &u, s), "embedding_bwd_apply_multi_bags_pad_mean");
+        else ff->check(pma->ffh_embedding_bwd_fused_multi_bags_pad_mean(cx, &u, s), "embedding_bwd_fused_multi_bags_pad_mean");
+        ff->n_pad_mean_updates++;
+        return;
+      }
       if (pad) {
         if (what == kApplyOnly) ff->check(pda->ffh_embedding_bwd_apply_multi_bags_pad(cx, &u, s), "embedding_bwd_apply_multi_bags_pad");
         else ff->check(pda->ffh_embedding_bwd_fused_multi_bags_pad(cx, &u, s), "embedding_bwd_fused_multi_bags_pad");
@@ -118,7 +128,10 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
         const int L = g.bag[b];       // a uniform call's bag size is its own tables' (a whole group of mixed sizes holds several)
         switch (what) {
           case kGather:
-            if (pad) {
+            if (pad_mean) {
+              ff->check(pma->ffh_embedding_fwd_multi_bags_pad_mean_bf16(cx, tb, g.bag.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags_pad_mean_bf16");
+              ff->n_pad_mean_gathers++;
+            } else if (pad) {
               ff->check(pda->ffh_embedding_fwd_multi_bags_pad_bf16(cx, tb, g.bag.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags_pad_bf16");
               ff->n_pad_gathers++;
             } else if (ragged && differ(b, n)) {
@@ -152,7 +165,10 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
       const int L = g.bag[b];
       switch (what) {
         case kGather:
-          if (pad) {
+          if (pad_mean) {
+            ff->check(pma->ffh_embedding_fwd_multi_bags_pad_mean(cx, tabs.data() + b, g.bag.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags_pad_mean");
+            ff->n_pad_mean_gathers++;
+          } else if (pad) {
             ff->check(pda->ffh_embedding_fwd_multi_bags_pad(cx, tabs.data() + b, g.bag.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags_pad");
             ff->n_pad_gathers++;
           } else if (ragged && differ(b, n)) {

@@ -29,8 +29,8 @@
  * entries with equal in_dims (the ragged headers promise that this equals the uniform call): there are no _pad forms of the uniform entries.
  *
  * MEAN POOLING (FFH_AGGR_MODE_AVG) is refused with FFH_ERR_UNSUPPORTED by every entry here that takes an aggregation mode, and nothing is
- * launched: a mean over the lookups that are there needs each bag's count of them in the gather's epilogue and in the apply phase.  That
- * is left out.
+ * launched: a mean over the lookups that are there needs each bag's count of them in the gather's epilogue and in the apply phase.  The
+ * mean forms that keep that count are an extension of their own, include/ff_hip_pad_mean.h.
  *
  * ROUTES (ffh_embedding_last_route): "bags:small:pad" and "bags:lsd:passes=P:pad", under the ragged update's rules.  The radix plan of a
  * table covers the bits of num_entries (the pad key) instead of those of num_entries - 1, so a table whose row count is a power of the
