@@ -176,268 +176,30 @@ _SIGS = {
 }
 
 
-# include/ff_hip_bf16.h: the optional bf16-table extension (its own list and version; libffhip.so exports it, the oracle does not)
-BF16_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_bf16.h")
-BF16_ROUND_STOCHASTIC, BF16_ROUND_NEAREST = 0, 1
-
-
-class EmbTableBf16(C.Structure):
-    """struct ffh_emb_table_bf16"""
-    _fields_ = [("idx", P), ("weight", P), ("io", P), ("num_entries", L), ("ld", L), ("table", C.c_int32), ("col0", C.c_int32)]
-
-
-class Bf16Rounding(C.Structure):
-    """struct ffh_bf16_rounding"""
-    _fields_ = [("mode", C.c_int32), ("reserved_", C.c_int32), ("seed", U64), ("counter", P)]
-
-
-_SIGS_BF16 = {
-    "ffh_bf16_abi_version": (I, []),
-    "ffh_embedding_fwd_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), I, I, I, L, I, P]),
-    "ffh_embedding_bwd_sgd_fused_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), I, I, I, L, I, F, C.POINTER(Bf16Rounding), P]),
-    "ffh_embedding_bwd_sort_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), I, I, I, L, P]),
-    "ffh_embedding_bwd_sgd_apply_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), I, I, I, L, I, F, C.POINTER(Bf16Rounding), P]),
-    "ffh_init_uniform_bf16": (I, [P, P, L, U64, F, F, P]),
-    "ffh_bf16_counter_advance": (I, [P, P, P]),
-    "ffh_embedding_bwd_opt_fused_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), C.POINTER(Bf16Rounding), P]),
-    "ffh_embedding_bwd_opt_apply_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), C.POINTER(Bf16Rounding), P]),
-}
-
-
-# include/ff_hip_ctr.h: the optional CTR extension (binary cross-entropy, evaluation histograms); same rule as the bf16 extension
-CTR_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_ctr.h")
-METRIC_BCE = 16
-AUC_BINS = 65536
-
-
-class CtrEval(C.Structure):
-    """struct ffh_ctr_eval"""
-    _fields_ = [("samples", U64), ("positives", U64), ("correct", U64), ("nan_predictions", U64), ("logloss_sum", F), ("pad_", F * 3),
-                ("hist_pos", U64 * AUC_BINS), ("hist_neg", U64 * AUC_BINS)]
-
-
-_SIGS_CTR = {
-    "ffh_ctr_abi_version": (I, []),
-    "ffh_bce_bwd_metrics": (I, [P, P, P, P, P, P, L, I, F, I, P]),
-    "ffh_linear_bwd_bce": (I, [P, P, L, P, L, P, L, P, L, P, P, P, I, I, L, I, I, P, F, P, P, I, P]),
-    "ffh_ctr_eval_update": (I, [P, P, P, P, L, P]),
-}
-
-
-# include/ff_hip_lr.h: the optional learning-rate extension (schedule state in device memory, optimizer entries that read it); same rule
-LR_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_lr.h")
-
-
-class LrSchedule(C.Structure):
-    """struct ffh_lr_schedule"""
-    _fields_ = [("base", C.c_double), ("warmup_steps", L), ("decay_start", L), ("decay_steps", L), ("beta1", C.c_double), ("beta2", C.c_double)]
-
-
-class LrValues(C.Structure):
-    """struct ffh_lr_values"""
-    _fields_ = [("k", L), ("lr", F), ("alpha_t", F), ("beta1_t", C.c_double), ("beta2_t", C.c_double)]
-
-
-_SIGS_LR = {
-    "ffh_lr_abi_version": (I, []),
-    "ffh_lr_state_bytes": (SZ, []),
-    "ffh_lr_state_init": (I, [P, P, C.POINTER(LrSchedule), L, P]),
-    "ffh_lr_state_advance": (I, [P, P, P]),
-    "ffh_lr_state_read": (I, [P, P, C.POINTER(LrValues), P]),
-    "ffh_sgd_update_ex_lr": (I, [P, P, P, P, L, P, F, F, I, I, P]),
-    "ffh_adam_update_lr": (I, [P, P, P, P, P, L, P, F, F, F, F, I, P]),
-    "ffh_embedding_bwd_opt_fused_multi_lr": (I, [P, C.POINTER(EmbTable), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), P, P]),
-    "ffh_embedding_bwd_opt_apply_multi_lr": (I, [P, C.POINTER(EmbTable), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), P, P]),
-    "ffh_embedding_bwd_opt_fused_multi_bf16_lr": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), C.POINTER(Bf16Rounding), P, P]),
-    "ffh_embedding_bwd_opt_apply_multi_bf16_lr": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), C.POINTER(Bf16Rounding), P, P]),
-}
-
-
-# include/ff_hip_data.h: the optional data extension (one shuffled training batch gathered in one launch); same rule
-DATA_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_data.h")
-GATHER_LOCAL_ROWS, GATHER_GLOBAL_ROWS = 0, 1
-GATHER_MAX_SEGMENTS = 64
-
-
-class GatherSegment(C.Structure):
-    """struct ffh_gather_segment"""
-    _fields_ = [("src", P), ("dst", P), ("row_bytes", C.c_int32), ("kind", C.c_int32)]
-
-
-class BatchOrder(C.Structure):
-    """struct ffh_batch_order"""
-    _fields_ = [("seed", U64), ("epoch", L), ("step", L), ("local_batch", L), ("n_local", L), ("world", C.c_int32), ("rank", C.c_int32)]
-
-
-_SIGS_DATA = {
-    "ffh_data_abi_version": (I, []),
-    "ffh_batch_gather": (I, [P, C.POINTER(GatherSegment), I, C.POINTER(BatchOrder), P]),
-}
-
-
-# include/ff_hip_cross.h: the optional cross extension (the elementwise combine of a DCNv2 low-rank cross layer); same rule
-CROSS_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_cross.h")
-CROSS_SKIP, CROSS_STORE, CROSS_ADD = 0, 1, 2
-
-_SIGS_CROSS = {
-    "ffh_cross_abi_version": (I, []),
-    "ffh_cross_fwd": (I, [P, P, L, P, L, P, L, P, L, L, L, P]),
-    "ffh_cross_bwd": (I, [P, P, L, P, L, P, L, P, L, P, L, I, P, L, I, L, L, P]),
-}
-
-
-def cross_header_symbols(header_path: str = CROSS_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_CROSS_API_LIST X-macro in include/ff_hip_cross.h."""
-    text = open(header_path).read()
-    m = re.search(r"#define FFH_CROSS_API_LIST\(X\)(.*?)\n\n", text, re.S)
+def _header_symbols(header_path: str, prefix: str) -> list[str]:
+    """Every symbol of the <prefix>_API_LIST X-macro of a header: include/ff_hip.h (prefix FFH) or an extension's (FFH_<X>)."""
+    m = re.search(r"#define %s_API_LIST\(X\)(.*?)\n\n" % prefix, open(header_path).read(), re.S)
     if not m:
-        raise RuntimeError("FFH_CROSS_API_LIST not found in " + header_path)
+        raise RuntimeError(prefix + "_API_LIST not found in " + header_path)
     return re.findall(r"X\((\w+)\)", m.group(1))
 
 
-def cross_header_abi_version(header_path: str = CROSS_HEADER_PATH) -> int:
-    """FFH_CROSS_ABI_VERSION of include/ff_hip_cross.h."""
-    m = re.search(r"#define\s+FFH_CROSS_ABI_VERSION\s+(\d+)", open(header_path).read())
+def _header_abi_version(header_path: str, prefix: str) -> int:
+    """<prefix>_ABI_VERSION of a header."""
+    m = re.search(r"#define\s+%s_ABI_VERSION\s+(\d+)" % prefix, open(header_path).read())
     if not m:
-        raise RuntimeError("FFH_CROSS_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
-
-
-# include/ff_hip_adagrad.h: the optional Adagrad extension (the dense launch; FFH_SPARSE_OPT_ADAGRAD in the table update); same rule
-ADAGRAD_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_adagrad.h")
-
-_SIGS_ADAGRAD = {
-    "ffh_adagrad_abi_version": (I, []),
-    "ffh_adagrad_update": (I, [P, P, P, P, L, F, F, F, I, P]),
-    "ffh_adagrad_update_lr": (I, [P, P, P, P, L, P, F, F, I, P]),
-}
-
-
-def adagrad_header_symbols(header_path: str = ADAGRAD_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_ADAGRAD_API_LIST X-macro in include/ff_hip_adagrad.h."""
-    text = open(header_path).read()
-    m = re.search(r"#define FFH_ADAGRAD_API_LIST\(X\)(.*?)\n\n", text, re.S)
-    if not m:
-        raise RuntimeError("FFH_ADAGRAD_API_LIST not found in " + header_path)
-    return re.findall(r"X\((\w+)\)", m.group(1))
-
-
-def adagrad_header_abi_version(header_path: str = ADAGRAD_HEADER_PATH) -> int:
-    """FFH_ADAGRAD_ABI_VERSION of include/ff_hip_adagrad.h."""
-    m = re.search(r"#define\s+FFH_ADAGRAD_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_ADAGRAD_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
-
-
-# include/ff_hip_rowwise.h: the optional row-wise Adagrad extension (FFH_SPARSE_OPT_ROWWISE_ADAGRAD in the table update; no launch of its own)
-ROWWISE_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_rowwise.h")
-
-_SIGS_ROWWISE = {
-    "ffh_rowwise_abi_version": (I, []),
-}
-
-
-def rowwise_header_symbols(header_path: str = ROWWISE_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_ROWWISE_API_LIST X-macro in include/ff_hip_rowwise.h."""
-    text = open(header_path).read()
-    m = re.search(r"#define FFH_ROWWISE_API_LIST\(X\)(.*?)\n\n", text, re.S)
-    if not m:
-        raise RuntimeError("FFH_ROWWISE_API_LIST not found in " + header_path)
-    return re.findall(r"X\((\w+)\)", m.group(1))
-
-
-def rowwise_header_abi_version(header_path: str = ROWWISE_HEADER_PATH) -> int:
-    """FFH_ROWWISE_ABI_VERSION of include/ff_hip_rowwise.h."""
-    m = re.search(r"#define\s+FFH_ROWWISE_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_ROWWISE_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
-
-
-def data_header_symbols(header_path: str = DATA_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_DATA_API_LIST X-macro in include/ff_hip_data.h."""
-    text = open(header_path).read()
-    m = re.search(r"#define FFH_DATA_API_LIST\(X\)(.*?)\n\n", text, re.S)
-    if not m:
-        raise RuntimeError("FFH_DATA_API_LIST not found in " + header_path)
-    return re.findall(r"X\((\w+)\)", m.group(1))
-
-
-def data_header_abi_version(header_path: str = DATA_HEADER_PATH) -> int:
-    """FFH_DATA_ABI_VERSION of include/ff_hip_data.h."""
-    m = re.search(r"#define\s+FFH_DATA_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_DATA_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
-
-
-def lr_header_symbols(header_path: str = LR_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_LR_API_LIST X-macro in include/ff_hip_lr.h."""
-    text = open(header_path).read()
-    m = re.search(r"#define FFH_LR_API_LIST\(X\)(.*?)\n\n", text, re.S)
-    if not m:
-        raise RuntimeError("FFH_LR_API_LIST not found in " + header_path)
-    return re.findall(r"X\((\w+)\)", m.group(1))
-
-
-def lr_header_abi_version(header_path: str = LR_HEADER_PATH) -> int:
-    """FFH_LR_ABI_VERSION of include/ff_hip_lr.h."""
-    m = re.search(r"#define\s+FFH_LR_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_LR_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
-
-
-def ctr_header_symbols(header_path: str = CTR_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_CTR_API_LIST X-macro in include/ff_hip_ctr.h."""
-    text = open(header_path).read()
-    m = re.search(r"#define FFH_CTR_API_LIST\(X\)(.*?)\n\n", text, re.S)
-    if not m:
-        raise RuntimeError("FFH_CTR_API_LIST not found in " + header_path)
-    return re.findall(r"X\((\w+)\)", m.group(1))
-
-
-def ctr_header_abi_version(header_path: str = CTR_HEADER_PATH) -> int:
-    """FFH_CTR_ABI_VERSION of include/ff_hip_ctr.h."""
-    m = re.search(r"#define\s+FFH_CTR_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_CTR_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
-
-
-def bf16_header_symbols(header_path: str = BF16_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_BF16_API_LIST X-macro in include/ff_hip_bf16.h."""
-    text = open(header_path).read()
-    m = re.search(r"#define FFH_BF16_API_LIST\(X\)(.*?)\n\n", text, re.S)
-    if not m:
-        raise RuntimeError("FFH_BF16_API_LIST not found in " + header_path)
-    return re.findall(r"X\((\w+)\)", m.group(1))
-
-
-def bf16_header_abi_version(header_path: str = BF16_HEADER_PATH) -> int:
-    """FFH_BF16_ABI_VERSION of include/ff_hip_bf16.h."""
-    m = re.search(r"#define\s+FFH_BF16_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_BF16_ABI_VERSION not found in " + header_path)
+        raise RuntimeError(prefix + "_ABI_VERSION not found in " + header_path)
     return int(m.group(1))
 
 
 def header_symbols(header_path: str = HEADER_PATH) -> list[str]:
     """Every symbol of the FFH_API_LIST X-macro in include/ff_hip.h."""
-    text = open(header_path).read()
-    m = re.search(r"#define FFH_API_LIST\(X\)(.*?)\n\n", text, re.S)
-    if not m:
-        raise RuntimeError("FFH_API_LIST not found in " + header_path)
-    return re.findall(r"X\((\w+)\)", m.group(1))
+    return _header_symbols(header_path, "FFH")
 
 
 def header_abi_version(header_path: str = HEADER_PATH) -> int:
     """FFH_ABI_VERSION of include/ff_hip.h."""
-    m = re.search(r"#define\s+FFH_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
+    return _header_abi_version(header_path, "FFH")
 
 
 class FFHError(RuntimeError):
@@ -455,6 +217,14 @@ def ptr(x) -> int:
     if hasattr(x, "ctypes"):
         return x.ctypes.data
     raise TypeError(f"cannot take the address of {type(x)}")
+
+
+def _ctx_args(sigs: dict, name: str, args) -> list:
+    """`args` as `name(ctx, *args)` of `sigs` takes them: the count checked, void pointers taken from tensors/arrays/ints/None."""
+    sig = sigs[name][1][1:]
+    if len(args) != len(sig):
+        raise TypeError(f"{name}: expected {len(sig)} args, got {len(args)}")
+    return [ptr(a) if t is P else a for a, t in zip(args, sig)]
 
 
 class FFHLib:
@@ -490,13 +260,7 @@ class FFHLib:
 
     def call(self, name: str, *args):
         """Call `name(ctx, *args)`; pointers may be tensors/arrays/ints/None."""
-        conv = []
-        sig = _SIGS[name][1][1:]
-        for a, t in zip(args, sig):
-            conv.append(ptr(a) if t is P else a)
-        if len(args) != len(sig):
-            raise TypeError(f"{name}: expected {len(sig)} args, got {len(args)}")
-        self.check(getattr(self.lib, name)(self.ctx, *conv), name)
+        self.check(getattr(self.lib, name)(self.ctx, *_ctx_args(_SIGS, name, args)), name)
 
     def set_workspace(self, buf, nbytes: int):
         self._ws_keepalive = buf
@@ -556,30 +320,100 @@ class FFHLib:
         self.check(getattr(self.lib, name)(self.ctx, ptr(big), out_blk, pa, ba, la, n, num_blocks, ptr(stream)), name)
 
 
-class Bf16Api:
-    """The bf16-table extension (include/ff_hip_bf16.h) of a loaded FFHLib; `bf16_api(lib)` builds it or raises."""
+# ---- the optional extensions (include/ff_hip_<x>.h): each has a list and a version of its own; libffhip.so exports them, the oracle does not ----
+class Extension:
+    """What differs between the optional extensions: the header (and with it the macro prefix and the version symbol), the signatures, and the
+    labels of the two messages.  The blocks below hold one each, in the order the host layer loads them (host/backend.h, FFH_EXTENSIONS)."""
+
+    def __init__(self, key: str, sigs: dict, label: str, version_label: str | None = None):
+        self.key = key                                        # bags_update: include/ff_hip_bags_update.h, FFH_BAGS_UPDATE_*, ffh_bags_update_abi_version
+        self.header = f"include/ff_hip_{key}.h"
+        self.header_path = os.path.join(REPO_ROOT, "include", f"ff_hip_{key}.h")
+        self.prefix = "FFH_" + key.upper()
+        self.version_symbol = f"ffh_{key}_abi_version"
+        self.sigs = sigs
+        self.label = label                                    # "no <label> extension"
+        self.version_label = version_label or label           # "<label> ABI version ..."
+
+    def header_symbols(self, header_path: str | None = None) -> list[str]:
+        """Every symbol of the extension's FFH_<X>_API_LIST X-macro."""
+        return _header_symbols(header_path or self.header_path, self.prefix)
+
+    def header_abi_version(self, header_path: str | None = None) -> int:
+        """The extension's FFH_<X>_ABI_VERSION."""
+        return _header_abi_version(header_path or self.header_path, self.prefix)
+
+
+EXTENSIONS: dict[str, Extension] = {}
+
+
+def _extension(key: str, sigs: dict, label: str, version_label: str | None = None) -> Extension:
+    EXTENSIONS[key] = Extension(key, sigs, label, version_label)
+    return EXTENSIONS[key]
+
+
+class ExtensionApi:
+    """An extension of a loaded FFHLib, by the one rule: absent is an FFHError (e.g. on the CPU oracle); present means every symbol of the
+    extension's signatures and the header's version.  A subclass names its extension (`ext`) and adds the helpers of its own; `<x>_api(lib)`
+    builds it or raises."""
+    ext: Extension
 
     def __init__(self, lib: FFHLib):
+        e = self.ext
         self.base = lib
-        for name, (res, args) in _SIGS_BF16.items():
+        for name, (res, args) in e.sigs.items():
             fn = getattr(lib.lib, name, None)
             if fn is None:
-                raise FFHError(f"{lib.path}: no bf16-table extension ({name} missing; include/ff_hip_bf16.h)")
+                raise FFHError(f"{lib.path}: no {e.label} extension ({name} missing; {e.header})")
             fn.restype = res
             fn.argtypes = args
-        got = lib.lib.ffh_bf16_abi_version()
-        if got != bf16_header_abi_version():
-            raise FFHError(f"{lib.path}: bf16 ABI version {got}, include/ff_hip_bf16.h says {bf16_header_abi_version()} (rebuild)")
+        got, want = getattr(lib.lib, e.version_symbol)(), e.header_abi_version()
+        if got != want:
+            raise FFHError(f"{lib.path}: {e.version_label} ABI version {got}, {e.header} says {want} (rebuild)")
         self.lib = lib.lib
         self.ctx = lib.ctx
 
+    def rc(self, name: str, *args) -> int:
+        """`name(ctx, *args)` of the extension, returning its status code (FFH_OK, FFH_ERR_UNSUPPORTED, ...); pointers may be tensors / arrays /
+        ints / None, struct arrays as the subclass builds them."""
+        return getattr(self.lib, name)(self.ctx, *_ctx_args(self.ext.sigs, name, args))
+
     def call(self, name: str, *args):
-        """Call `name(ctx, *args)` of the extension; pointers may be tensors/arrays/ints/None."""
-        sig = _SIGS_BF16[name][1][1:]
-        if len(args) != len(sig):
-            raise TypeError(f"{name}: expected {len(sig)} args, got {len(args)}")
-        conv = [ptr(a) if t is P else a for a, t in zip(args, sig)]
-        self.base.check(getattr(self.lib, name)(self.ctx, *conv), name)
+        """Call `name(ctx, *args)` of the extension; FFHError unless it returns FFH_OK."""
+        self.base.check(self.rc(name, *args), name)
+
+
+# ---- the bf16-table extension (include/ff_hip_bf16.h) -------------------------------------------------------------------------------------
+BF16_ROUND_STOCHASTIC, BF16_ROUND_NEAREST = 0, 1
+
+
+class EmbTableBf16(C.Structure):
+    """struct ffh_emb_table_bf16"""
+    _fields_ = [("idx", P), ("weight", P), ("io", P), ("num_entries", L), ("ld", L), ("table", C.c_int32), ("col0", C.c_int32)]
+
+
+class Bf16Rounding(C.Structure):
+    """struct ffh_bf16_rounding"""
+    _fields_ = [("mode", C.c_int32), ("reserved_", C.c_int32), ("seed", U64), ("counter", P)]
+
+
+_SIGS_BF16 = {
+    "ffh_bf16_abi_version": (I, []),
+    "ffh_embedding_fwd_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), I, I, I, L, I, P]),
+    "ffh_embedding_bwd_sgd_fused_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), I, I, I, L, I, F, C.POINTER(Bf16Rounding), P]),
+    "ffh_embedding_bwd_sort_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), I, I, I, L, P]),
+    "ffh_embedding_bwd_sgd_apply_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), I, I, I, L, I, F, C.POINTER(Bf16Rounding), P]),
+    "ffh_init_uniform_bf16": (I, [P, P, L, U64, F, F, P]),
+    "ffh_bf16_counter_advance": (I, [P, P, P]),
+    "ffh_embedding_bwd_opt_fused_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), C.POINTER(Bf16Rounding), P]),
+    "ffh_embedding_bwd_opt_apply_multi_bf16": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), C.POINTER(Bf16Rounding), P]),
+}
+BF16_EXT = _extension("bf16", _SIGS_BF16, "bf16-table", version_label="bf16")
+BF16_HEADER_PATH, bf16_header_symbols, bf16_header_abi_version = BF16_EXT.header_path, BF16_EXT.header_symbols, BF16_EXT.header_abi_version
+
+
+class Bf16Api(ExtensionApi):
+    ext = BF16_EXT
 
     @staticmethod
     def tables(entries) -> "C.Array":
@@ -598,70 +432,68 @@ class Bf16Api:
         return Bf16Rounding(int(mode), 0, int(seed) & (2**64 - 1), ptr(counter))
 
 
-def bf16_api(lib: FFHLib) -> Bf16Api:
-    """The bf16-table entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
-    return Bf16Api(lib)
+bf16_api = Bf16Api
 
 
-class CtrApi:
-    """The CTR extension (include/ff_hip_ctr.h) of a loaded FFHLib; `ctr_api(lib)` builds it or raises."""
-
-    def __init__(self, lib: FFHLib):
-        self.base = lib
-        for name, (res, args) in _SIGS_CTR.items():
-            fn = getattr(lib.lib, name, None)
-            if fn is None:
-                raise FFHError(f"{lib.path}: no CTR extension ({name} missing; include/ff_hip_ctr.h)")
-            fn.restype = res
-            fn.argtypes = args
-        got = lib.lib.ffh_ctr_abi_version()
-        if got != ctr_header_abi_version():
-            raise FFHError(f"{lib.path}: CTR ABI version {got}, include/ff_hip_ctr.h says {ctr_header_abi_version()} (rebuild)")
-        self.lib = lib.lib
-        self.ctx = lib.ctx
-
-    def rc(self, name: str, *args) -> int:
-        """`name(ctx, *args)` of the extension, returning its status code (FFH_OK, FFH_ERR_UNSUPPORTED, ...)."""
-        sig = _SIGS_CTR[name][1][1:]
-        if len(args) != len(sig):
-            raise TypeError(f"{name}: expected {len(sig)} args, got {len(args)}")
-        conv = [ptr(a) if t is P else a for a, t in zip(args, sig)]
-        return getattr(self.lib, name)(self.ctx, *conv)
-
-    def call(self, name: str, *args):
-        """Call `name(ctx, *args)` of the extension; pointers may be tensors/arrays/ints/None."""
-        self.base.check(self.rc(name, *args), name)
+# ---- the CTR extension (include/ff_hip_ctr.h): binary cross-entropy, evaluation histograms ------------------------------------------------
+METRIC_BCE = 16
+AUC_BINS = 65536
 
 
-def ctr_api(lib: FFHLib) -> CtrApi:
-    """The CTR entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
-    return CtrApi(lib)
+class CtrEval(C.Structure):
+    """struct ffh_ctr_eval"""
+    _fields_ = [("samples", U64), ("positives", U64), ("correct", U64), ("nan_predictions", U64), ("logloss_sum", F), ("pad_", F * 3),
+                ("hist_pos", U64 * AUC_BINS), ("hist_neg", U64 * AUC_BINS)]
 
 
-class LrApi:
-    """The learning-rate extension (include/ff_hip_lr.h) of a loaded FFHLib; `lr_api(lib)` builds it or raises."""
+_SIGS_CTR = {
+    "ffh_ctr_abi_version": (I, []),
+    "ffh_bce_bwd_metrics": (I, [P, P, P, P, P, P, L, I, F, I, P]),
+    "ffh_linear_bwd_bce": (I, [P, P, L, P, L, P, L, P, L, P, P, P, I, I, L, I, I, P, F, P, P, I, P]),
+    "ffh_ctr_eval_update": (I, [P, P, P, P, L, P]),
+}
+CTR_EXT = _extension("ctr", _SIGS_CTR, "CTR")
+CTR_HEADER_PATH, ctr_header_symbols, ctr_header_abi_version = CTR_EXT.header_path, CTR_EXT.header_symbols, CTR_EXT.header_abi_version
 
-    def __init__(self, lib: FFHLib):
-        self.base = lib
-        for name, (res, args) in _SIGS_LR.items():
-            fn = getattr(lib.lib, name, None)
-            if fn is None:
-                raise FFHError(f"{lib.path}: no learning-rate extension ({name} missing; include/ff_hip_lr.h)")
-            fn.restype = res
-            fn.argtypes = args
-        got = lib.lib.ffh_lr_abi_version()
-        if got != lr_header_abi_version():
-            raise FFHError(f"{lib.path}: learning-rate ABI version {got}, include/ff_hip_lr.h says {lr_header_abi_version()} (rebuild)")
-        self.lib = lib.lib
-        self.ctx = lib.ctx
 
-    def call(self, name: str, *args):
-        """Call `name(ctx, *args)` of the extension; pointers may be tensors/arrays/ints/None."""
-        sig = _SIGS_LR[name][1][1:]
-        if len(args) != len(sig):
-            raise TypeError(f"{name}: expected {len(sig)} args, got {len(args)}")
-        conv = [ptr(a) if t is P else a for a, t in zip(args, sig)]
-        self.base.check(getattr(self.lib, name)(self.ctx, *conv), name)
+class CtrApi(ExtensionApi):
+    ext = CTR_EXT
+
+
+ctr_api = CtrApi
+
+
+# ---- the learning-rate extension (include/ff_hip_lr.h): schedule state in device memory, optimizer entries that read it -------------------
+
+class LrSchedule(C.Structure):
+    """struct ffh_lr_schedule"""
+    _fields_ = [("base", C.c_double), ("warmup_steps", L), ("decay_start", L), ("decay_steps", L), ("beta1", C.c_double), ("beta2", C.c_double)]
+
+
+class LrValues(C.Structure):
+    """struct ffh_lr_values"""
+    _fields_ = [("k", L), ("lr", F), ("alpha_t", F), ("beta1_t", C.c_double), ("beta2_t", C.c_double)]
+
+
+_SIGS_LR = {
+    "ffh_lr_abi_version": (I, []),
+    "ffh_lr_state_bytes": (SZ, []),
+    "ffh_lr_state_init": (I, [P, P, C.POINTER(LrSchedule), L, P]),
+    "ffh_lr_state_advance": (I, [P, P, P]),
+    "ffh_lr_state_read": (I, [P, P, C.POINTER(LrValues), P]),
+    "ffh_sgd_update_ex_lr": (I, [P, P, P, P, L, P, F, F, I, I, P]),
+    "ffh_adam_update_lr": (I, [P, P, P, P, P, L, P, F, F, F, F, I, P]),
+    "ffh_embedding_bwd_opt_fused_multi_lr": (I, [P, C.POINTER(EmbTable), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), P, P]),
+    "ffh_embedding_bwd_opt_apply_multi_lr": (I, [P, C.POINTER(EmbTable), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), P, P]),
+    "ffh_embedding_bwd_opt_fused_multi_bf16_lr": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), C.POINTER(Bf16Rounding), P, P]),
+    "ffh_embedding_bwd_opt_apply_multi_bf16_lr": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(EmbState), I, I, I, L, I, C.POINTER(SparseOpt), C.POINTER(Bf16Rounding), P, P]),
+}
+LR_EXT = _extension("lr", _SIGS_LR, "learning-rate")
+LR_HEADER_PATH, lr_header_symbols, lr_header_abi_version = LR_EXT.header_path, LR_EXT.header_symbols, LR_EXT.header_abi_version
+
+
+class LrApi(ExtensionApi):
+    ext = LR_EXT
 
     def state_bytes(self) -> int:
         return int(self.lib.ffh_lr_state_bytes())
@@ -676,27 +508,34 @@ class LrApi:
         return v
 
 
-def lr_api(lib: FFHLib) -> LrApi:
-    """The learning-rate entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
-    return LrApi(lib)
+lr_api = LrApi
 
 
-class DataApi:
-    """The data extension (include/ff_hip_data.h) of a loaded FFHLib; `data_api(lib)` builds it or raises."""
+# ---- the data extension (include/ff_hip_data.h): one shuffled training batch gathered in one launch ----------------------------------------
+GATHER_LOCAL_ROWS, GATHER_GLOBAL_ROWS = 0, 1
+GATHER_MAX_SEGMENTS = 64
 
-    def __init__(self, lib: FFHLib):
-        self.base = lib
-        for name, (res, args) in _SIGS_DATA.items():
-            fn = getattr(lib.lib, name, None)
-            if fn is None:
-                raise FFHError(f"{lib.path}: no data extension ({name} missing; include/ff_hip_data.h)")
-            fn.restype = res
-            fn.argtypes = args
-        got = lib.lib.ffh_data_abi_version()
-        if got != data_header_abi_version():
-            raise FFHError(f"{lib.path}: data ABI version {got}, include/ff_hip_data.h says {data_header_abi_version()} (rebuild)")
-        self.lib = lib.lib
-        self.ctx = lib.ctx
+
+class GatherSegment(C.Structure):
+    """struct ffh_gather_segment"""
+    _fields_ = [("src", P), ("dst", P), ("row_bytes", C.c_int32), ("kind", C.c_int32)]
+
+
+class BatchOrder(C.Structure):
+    """struct ffh_batch_order"""
+    _fields_ = [("seed", U64), ("epoch", L), ("step", L), ("local_batch", L), ("n_local", L), ("world", C.c_int32), ("rank", C.c_int32)]
+
+
+_SIGS_DATA = {
+    "ffh_data_abi_version": (I, []),
+    "ffh_batch_gather": (I, [P, C.POINTER(GatherSegment), I, C.POINTER(BatchOrder), P]),
+}
+DATA_EXT = _extension("data", _SIGS_DATA, "data")
+DATA_HEADER_PATH, data_header_symbols, data_header_abi_version = DATA_EXT.header_path, DATA_EXT.header_symbols, DATA_EXT.header_abi_version
+
+
+class DataApi(ExtensionApi):
+    ext = DATA_EXT
 
     def batch_gather_rc(self, segments, seed, epoch, step, local_batch, n_local, world=1, rank=0, stream=None) -> int:
         """ffh_batch_gather; `segments`: (src, dst, row_bytes, kind) tuples, pointers as tensors/arrays/ints/None.  Returns the status code."""
@@ -710,53 +549,39 @@ class DataApi:
         self.base.check(self.batch_gather_rc(segments, seed, epoch, step, local_batch, n_local, world, rank, stream), "ffh_batch_gather")
 
 
-def data_api(lib: FFHLib) -> DataApi:
-    """The data entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
-    return DataApi(lib)
+data_api = DataApi
 
 
-# include/ff_hip_digest.h: the optional digest extension (a 64-bit digest of a strided device buffer); same rule
-DIGEST_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_digest.h")
+# ---- the cross extension (include/ff_hip_cross.h): the elementwise combine of a DCNv2 low-rank cross layer --------------------------------
+CROSS_SKIP, CROSS_STORE, CROSS_ADD = 0, 1, 2
 
+_SIGS_CROSS = {
+    "ffh_cross_abi_version": (I, []),
+    "ffh_cross_fwd": (I, [P, P, L, P, L, P, L, P, L, L, L, P]),
+    "ffh_cross_bwd": (I, [P, P, L, P, L, P, L, P, L, P, L, I, P, L, I, L, L, P]),
+}
+CROSS_EXT = _extension("cross", _SIGS_CROSS, "cross")
+CROSS_HEADER_PATH, cross_header_symbols, cross_header_abi_version = CROSS_EXT.header_path, CROSS_EXT.header_symbols, CROSS_EXT.header_abi_version
+
+
+class CrossApi(ExtensionApi):
+    ext = CROSS_EXT
+
+
+cross_api = CrossApi
+
+
+# ---- the digest extension (include/ff_hip_digest.h): a 64-bit digest of a strided device buffer -------------------------------------------
 _SIGS_DIGEST = {
     "ffh_digest_abi_version": (I, []),
     "ffh_state_digest": (I, [P, P, L, L, L, C.c_uint64, C.c_uint64, P, P]),
 }
+DIGEST_EXT = _extension("digest", _SIGS_DIGEST, "digest")
+DIGEST_HEADER_PATH, digest_header_symbols, digest_header_abi_version = DIGEST_EXT.header_path, DIGEST_EXT.header_symbols, DIGEST_EXT.header_abi_version
 
 
-def digest_header_symbols(header_path: str = DIGEST_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_DIGEST_API_LIST X-macro in include/ff_hip_digest.h."""
-    text = open(header_path).read()
-    m = re.search(r"#define FFH_DIGEST_API_LIST\(X\)(.*?)\n\n", text, re.S)
-    if not m:
-        raise RuntimeError("FFH_DIGEST_API_LIST not found in " + header_path)
-    return re.findall(r"X\((ffh_[a-z0-9_]+)\)", m.group(1))
-
-
-def digest_header_abi_version(header_path: str = DIGEST_HEADER_PATH) -> int:
-    """FFH_DIGEST_ABI_VERSION of include/ff_hip_digest.h."""
-    m = re.search(r"#define\s+FFH_DIGEST_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_DIGEST_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
-
-
-class DigestApi:
-    """The digest extension (include/ff_hip_digest.h) of a loaded FFHLib; `digest_api(lib)` builds it or raises."""
-
-    def __init__(self, lib: FFHLib):
-        self.base = lib
-        for name, (res, args) in _SIGS_DIGEST.items():
-            fn = getattr(lib.lib, name, None)
-            if fn is None:
-                raise FFHError(f"{lib.path}: no digest extension ({name} missing; include/ff_hip_digest.h)")
-            fn.restype = res
-            fn.argtypes = args
-        got = lib.lib.ffh_digest_abi_version()
-        if got != digest_header_abi_version():
-            raise FFHError(f"{lib.path}: digest ABI version {got}, include/ff_hip_digest.h says {digest_header_abi_version()} (rebuild)")
-        self.lib = lib.lib
-        self.ctx = lib.ctx
+class DigestApi(ExtensionApi):
+    ext = DIGEST_EXT
 
     def state_digest_rc(self, base, rows, row_bytes, ld_bytes, seed, index_base, acc, stream=None) -> int:
         """ffh_state_digest, returning its status code (FFH_OK, FFH_ERR_BAD_ARG, ...): *acc += the digest."""
@@ -768,109 +593,43 @@ class DigestApi:
         self.base.check(self.state_digest_rc(base, rows, row_bytes, ld_bytes, seed, index_base, acc, stream), "ffh_state_digest")
 
 
-def digest_api(lib: FFHLib) -> DigestApi:
-    """The digest entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
-    return DigestApi(lib)
+digest_api = DigestApi
 
 
-class CrossApi:
-    """The cross extension (include/ff_hip_cross.h) of a loaded FFHLib; `cross_api(lib)` builds it or raises."""
-
-    def __init__(self, lib: FFHLib):
-        self.base = lib
-        for name, (res, args) in _SIGS_CROSS.items():
-            fn = getattr(lib.lib, name, None)
-            if fn is None:
-                raise FFHError(f"{lib.path}: no cross extension ({name} missing; include/ff_hip_cross.h)")
-            fn.restype = res
-            fn.argtypes = args
-        got = lib.lib.ffh_cross_abi_version()
-        if got != cross_header_abi_version():
-            raise FFHError(f"{lib.path}: cross ABI version {got}, include/ff_hip_cross.h says {cross_header_abi_version()} (rebuild)")
-        self.lib = lib.lib
-        self.ctx = lib.ctx
-
-    def rc(self, name: str, *args) -> int:
-        """`name(ctx, *args)` of the extension, returning its status code (FFH_OK, FFH_ERR_BAD_ARG, ...)."""
-        sig = _SIGS_CROSS[name][1][1:]
-        if len(args) != len(sig):
-            raise TypeError(f"{name}: expected {len(sig)} args, got {len(args)}")
-        conv = [ptr(a) if t is P else a for a, t in zip(args, sig)]
-        return getattr(self.lib, name)(self.ctx, *conv)
-
-    def call(self, name: str, *args):
-        """Call `name(ctx, *args)` of the extension; pointers may be tensors/arrays/ints/None."""
-        self.base.check(self.rc(name, *args), name)
+# ---- the Adagrad extension (include/ff_hip_adagrad.h): the dense launch; FFH_SPARSE_OPT_ADAGRAD in the table update -----------------------
+_SIGS_ADAGRAD = {
+    "ffh_adagrad_abi_version": (I, []),
+    "ffh_adagrad_update": (I, [P, P, P, P, L, F, F, F, I, P]),
+    "ffh_adagrad_update_lr": (I, [P, P, P, P, L, P, F, F, I, P]),
+}
+ADAGRAD_EXT = _extension("adagrad", _SIGS_ADAGRAD, "Adagrad")
+ADAGRAD_HEADER_PATH, adagrad_header_symbols, adagrad_header_abi_version = ADAGRAD_EXT.header_path, ADAGRAD_EXT.header_symbols, ADAGRAD_EXT.header_abi_version
 
 
-def cross_api(lib: FFHLib) -> CrossApi:
-    """The cross entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
-    return CrossApi(lib)
+class AdagradApi(ExtensionApi):
+    ext = ADAGRAD_EXT
 
 
-class AdagradApi:
-    """The Adagrad extension (include/ff_hip_adagrad.h) of a loaded FFHLib; `adagrad_api(lib)` builds it or raises."""
-
-    def __init__(self, lib: FFHLib):
-        self.base = lib
-        for name, (res, args) in _SIGS_ADAGRAD.items():
-            fn = getattr(lib.lib, name, None)
-            if fn is None:
-                raise FFHError(f"{lib.path}: no Adagrad extension ({name} missing; include/ff_hip_adagrad.h)")
-            fn.restype = res
-            fn.argtypes = args
-        got = lib.lib.ffh_adagrad_abi_version()
-        if got != adagrad_header_abi_version():
-            raise FFHError(f"{lib.path}: Adagrad ABI version {got}, include/ff_hip_adagrad.h says {adagrad_header_abi_version()} (rebuild)")
-        self.lib = lib.lib
-        self.ctx = lib.ctx
-
-    def rc(self, name: str, *args) -> int:
-        """`name(ctx, *args)` of the extension, returning its status code (FFH_OK, FFH_ERR_BAD_ARG, ...)."""
-        sig = _SIGS_ADAGRAD[name][1][1:]
-        if len(args) != len(sig):
-            raise TypeError(f"{name}: expected {len(sig)} args, got {len(args)}")
-        conv = [ptr(a) if t is P else a for a, t in zip(args, sig)]
-        return getattr(self.lib, name)(self.ctx, *conv)
-
-    def call(self, name: str, *args):
-        """Call `name(ctx, *args)` of the extension; pointers may be tensors/arrays/ints/None."""
-        self.base.check(self.rc(name, *args), name)
+adagrad_api = AdagradApi
 
 
-def adagrad_api(lib: FFHLib) -> AdagradApi:
-    """The Adagrad entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
-    return AdagradApi(lib)
+# ---- the row-wise Adagrad extension (include/ff_hip_rowwise.h): FFH_SPARSE_OPT_ROWWISE_ADAGRAD in the table update; no launch of its own ----
+_SIGS_ROWWISE = {
+    "ffh_rowwise_abi_version": (I, []),
+}
+ROWWISE_EXT = _extension("rowwise", _SIGS_ROWWISE, "row-wise Adagrad")
+ROWWISE_HEADER_PATH, rowwise_header_symbols, rowwise_header_abi_version = ROWWISE_EXT.header_path, ROWWISE_EXT.header_symbols, ROWWISE_EXT.header_abi_version
 
 
-class RowwiseApi:
-    """The row-wise Adagrad extension (include/ff_hip_rowwise.h) of a loaded FFHLib; `rowwise_api(lib)` builds it or raises.  The rule itself is
-    reached through the table update's entry points of `lib` with SparseOpt.kind = SPARSE_OPT_ROWWISE_ADAGRAD."""
-
-    def __init__(self, lib: FFHLib):
-        self.base = lib
-        for name, (res, args) in _SIGS_ROWWISE.items():
-            fn = getattr(lib.lib, name, None)
-            if fn is None:
-                raise FFHError(f"{lib.path}: no row-wise Adagrad extension ({name} missing; include/ff_hip_rowwise.h)")
-            fn.restype = res
-            fn.argtypes = args
-        got = lib.lib.ffh_rowwise_abi_version()
-        if got != rowwise_header_abi_version():
-            raise FFHError(f"{lib.path}: row-wise Adagrad ABI version {got}, include/ff_hip_rowwise.h says {rowwise_header_abi_version()} (rebuild)")
-        self.lib = lib.lib
-        self.ctx = lib.ctx
+class RowwiseApi(ExtensionApi):
+    """The rule itself is reached through the table update's entry points of `lib` with SparseOpt.kind = SPARSE_OPT_ROWWISE_ADAGRAD."""
+    ext = ROWWISE_EXT
 
 
-def rowwise_api(lib: FFHLib) -> RowwiseApi:
-    """The row-wise Adagrad extension of `lib`; FFHError when the library does not export it (e.g. the CPU oracle)."""
-    return RowwiseApi(lib)
+rowwise_api = RowwiseApi
 
 
 # ---- the fold extension (include/ff_hip_fold.h): small embedding tables folded out of the first top layer's forward GEMM --------------------
-FOLD_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_fold.h")
-
-
 class FoldGroup(C.Structure):
     """struct ffh_fold_group"""
     _fields_ = [("e", P), ("lde", L), ("col0", L), ("p", P), ("rows", L)]
@@ -897,40 +656,12 @@ _SIGS_FOLD = {
     "ffh_fold_table_update": (I, [P, C.POINTER(FoldGroup), I, P, L, I, I, C.c_float, P]),
     "ffh_fold_table_update_lr": (I, [P, C.POINTER(FoldGroup), I, P, L, I, I, P, P]),
 }
+FOLD_EXT = _extension("fold", _SIGS_FOLD, "fold")
+FOLD_HEADER_PATH, fold_header_symbols, fold_header_abi_version = FOLD_EXT.header_path, FOLD_EXT.header_symbols, FOLD_EXT.header_abi_version
 
 
-def fold_header_symbols(header_path: str = FOLD_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_FOLD_API_LIST X-macro in include/ff_hip_fold.h."""
-    m = re.search(r"#define FFH_FOLD_API_LIST\(X\)(.*?)\n\n", open(header_path).read(), re.S)
-    if not m:
-        raise RuntimeError("FFH_FOLD_API_LIST not found in " + header_path)
-    return re.findall(r"X\((\w+)\)", m.group(1))
-
-
-def fold_header_abi_version(header_path: str = FOLD_HEADER_PATH) -> int:
-    """FFH_FOLD_ABI_VERSION of include/ff_hip_fold.h."""
-    m = re.search(r"#define\s+FFH_FOLD_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_FOLD_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
-
-
-class FoldApi:
-    """The fold extension (include/ff_hip_fold.h) of a loaded FFHLib; `fold_api(lib)` builds it or raises."""
-
-    def __init__(self, lib: "FFHLib"):
-        self.base = lib
-        for name, (res, args) in _SIGS_FOLD.items():
-            fn = getattr(lib.lib, name, None)
-            if fn is None:
-                raise FFHError(f"{lib.path}: no fold extension ({name} missing; include/ff_hip_fold.h)")
-            fn.restype = res
-            fn.argtypes = args
-        got = lib.lib.ffh_fold_abi_version()
-        if got != fold_header_abi_version():
-            raise FFHError(f"{lib.path}: fold ABI version {got}, include/ff_hip_fold.h says {fold_header_abi_version()} (rebuild)")
-        self.lib = lib.lib
-        self.ctx = lib.ctx
+class FoldApi(ExtensionApi):
+    ext = FOLD_EXT
 
     @staticmethod
     def groups(entries) -> "C.Array":
@@ -950,25 +681,11 @@ class FoldApi:
             arr[k] = FoldSeg(int(k0), int(n))
         return arr
 
-    def rc(self, name: str, *args) -> int:
-        """`name(ctx, *args)` of the extension, returning its status code; pointers may be tensors / arrays / ints / None, struct arrays as built above."""
-        sig = _SIGS_FOLD[name][1][1:]
-        if len(args) != len(sig):
-            raise TypeError(f"{name}: expected {len(sig)} args, got {len(args)}")
-        conv = [ptr(a) if t is P else a for a, t in zip(args, sig)]
-        return getattr(self.lib, name)(self.ctx, *conv)
 
-    def call(self, name: str, *args):
-        self.base.check(self.rc(name, *args), name)
-
-
-def fold_api(lib: "FFHLib") -> FoldApi:
-    """The fold entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
-    return FoldApi(lib)
+fold_api = FoldApi
 
 
 # ---- the bags extension (include/ff_hip_bags.h): the gather with a bag size per table, one launch ------------------------------------------
-BAGS_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_bags.h")
 BAGS_MAX_IN_DIM = 65535
 
 _SIGS_BAGS = {
@@ -977,40 +694,12 @@ _SIGS_BAGS = {
     "ffh_embedding_fwd_multi_bags": (I, [P, C.POINTER(EmbTable), C.POINTER(I), I, I, L, I, P]),
     "ffh_embedding_fwd_multi_bags_bf16": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(I), I, I, L, I, P]),
 }
+BAGS_EXT = _extension("bags", _SIGS_BAGS, "bags")
+BAGS_HEADER_PATH, bags_header_symbols, bags_header_abi_version = BAGS_EXT.header_path, BAGS_EXT.header_symbols, BAGS_EXT.header_abi_version
 
 
-def bags_header_symbols(header_path: str = BAGS_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_BAGS_API_LIST X-macro in include/ff_hip_bags.h."""
-    m = re.search(r"#define FFH_BAGS_API_LIST\(X\)(.*?)\n\n", open(header_path).read(), re.S)
-    if not m:
-        raise RuntimeError("FFH_BAGS_API_LIST not found in " + header_path)
-    return re.findall(r"X\((\w+)\)", m.group(1))
-
-
-def bags_header_abi_version(header_path: str = BAGS_HEADER_PATH) -> int:
-    """FFH_BAGS_ABI_VERSION of include/ff_hip_bags.h."""
-    m = re.search(r"#define\s+FFH_BAGS_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_BAGS_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
-
-
-class BagsApi:
-    """The bags extension (include/ff_hip_bags.h) of a loaded FFHLib; `bags_api(lib)` builds it or raises."""
-
-    def __init__(self, lib: "FFHLib"):
-        self.base = lib
-        for name, (res, args) in _SIGS_BAGS.items():
-            fn = getattr(lib.lib, name, None)
-            if fn is None:
-                raise FFHError(f"{lib.path}: no bags extension ({name} missing; include/ff_hip_bags.h)")
-            fn.restype = res
-            fn.argtypes = args
-        got = lib.lib.ffh_bags_abi_version()
-        if got != bags_header_abi_version():
-            raise FFHError(f"{lib.path}: bags ABI version {got}, include/ff_hip_bags.h says {bags_header_abi_version()} (rebuild)")
-        self.lib = lib.lib
-        self.ctx = lib.ctx
+class BagsApi(ExtensionApi):
+    ext = BAGS_EXT
 
     @staticmethod
     def in_dims(sizes) -> "C.Array":
@@ -1027,13 +716,10 @@ class BagsApi:
         self.base.check(self.rc(name, *args, **kw), name)
 
 
-def bags_api(lib: "FFHLib") -> BagsApi:
-    """The ragged-gather entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
-    return BagsApi(lib)
+bags_api = BagsApi
 
 
 # ---- the bags-update extension (include/ff_hip_bags_update.h): the fused table update with a bag size per table, one call -----------------
-BAGS_UPDATE_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_bags_update.h")
 BAGS_UPDATE_MAX_TABLES = MAX_TABLES
 
 
@@ -1050,40 +736,13 @@ _SIGS_BAGS_UPDATE = {
     "ffh_embedding_bwd_bags_workspace_bytes": (SZ, [C.POINTER(I), I, I, L]),
     "ffh_embedding_bwd_fused_multi_bags": (I, [P, C.POINTER(BagsUpdate), P]),
 }
+BAGS_UPDATE_EXT = _extension("bags_update", _SIGS_BAGS_UPDATE, "bags-update")
+BAGS_UPDATE_HEADER_PATH, bags_update_header_symbols, bags_update_header_abi_version = (
+    BAGS_UPDATE_EXT.header_path, BAGS_UPDATE_EXT.header_symbols, BAGS_UPDATE_EXT.header_abi_version)
 
 
-def bags_update_header_symbols(header_path: str = BAGS_UPDATE_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_BAGS_UPDATE_API_LIST X-macro in include/ff_hip_bags_update.h."""
-    m = re.search(r"#define FFH_BAGS_UPDATE_API_LIST\(X\)(.*?)\n\n", open(header_path).read(), re.S)
-    if not m:
-        raise RuntimeError("FFH_BAGS_UPDATE_API_LIST not found in " + header_path)
-    return re.findall(r"X\((\w+)\)", m.group(1))
-
-
-def bags_update_header_abi_version(header_path: str = BAGS_UPDATE_HEADER_PATH) -> int:
-    """FFH_BAGS_UPDATE_ABI_VERSION of include/ff_hip_bags_update.h."""
-    m = re.search(r"#define\s+FFH_BAGS_UPDATE_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_BAGS_UPDATE_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
-
-
-class BagsUpdateApi:
-    """The bags-update extension (include/ff_hip_bags_update.h) of a loaded FFHLib; `bags_update_api(lib)` builds it or raises."""
-
-    def __init__(self, lib: "FFHLib"):
-        self.base = lib
-        for name, (res, args) in _SIGS_BAGS_UPDATE.items():
-            fn = getattr(lib.lib, name, None)
-            if fn is None:
-                raise FFHError(f"{lib.path}: no bags-update extension ({name} missing; include/ff_hip_bags_update.h)")
-            fn.restype = res
-            fn.argtypes = args
-        got = lib.lib.ffh_bags_update_abi_version()
-        if got != bags_update_header_abi_version():
-            raise FFHError(f"{lib.path}: bags-update ABI version {got}, include/ff_hip_bags_update.h says {bags_update_header_abi_version()} (rebuild)")
-        self.lib = lib.lib
-        self.ctx = lib.ctx
+class BagsUpdateApi(ExtensionApi):
+    ext = BAGS_UPDATE_EXT
 
     def kernarg_bytes(self) -> int:
         return int(self.lib.ffh_bags_update_kernarg_bytes())
@@ -1129,54 +788,23 @@ class BagsUpdateApi:
         self.base.check(self.rc(u, stream), "ffh_embedding_bwd_fused_multi_bags")
 
 
-def bags_update_api(lib: "FFHLib") -> BagsUpdateApi:
-    """The ragged-update entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
-    return BagsUpdateApi(lib)
+bags_update_api = BagsUpdateApi
 
 
 # ---- the bags-sort extension (include/ff_hip_bags_sort.h): the ragged update in two calls, sort (ids only) then apply ----------------------
-BAGS_SORT_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_bags_sort.h")
-
 _SIGS_BAGS_SORT = {
     "ffh_bags_sort_abi_version": (I, []),
     "ffh_embedding_bwd_sort_multi_bags": (I, [P, C.POINTER(BagsUpdate), P]),
     "ffh_embedding_bwd_apply_multi_bags": (I, [P, C.POINTER(BagsUpdate), P]),
 }
+BAGS_SORT_EXT = _extension("bags_sort", _SIGS_BAGS_SORT, "bags-sort")
+BAGS_SORT_HEADER_PATH, bags_sort_header_symbols, bags_sort_header_abi_version = (
+    BAGS_SORT_EXT.header_path, BAGS_SORT_EXT.header_symbols, BAGS_SORT_EXT.header_abi_version)
 
 
-def bags_sort_header_symbols(header_path: str = BAGS_SORT_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_BAGS_SORT_API_LIST X-macro in include/ff_hip_bags_sort.h."""
-    m = re.search(r"#define FFH_BAGS_SORT_API_LIST\(X\)(.*?)\n\n", open(header_path).read(), re.S)
-    if not m:
-        raise RuntimeError("FFH_BAGS_SORT_API_LIST not found in " + header_path)
-    return re.findall(r"X\((\w+)\)", m.group(1))
-
-
-def bags_sort_header_abi_version(header_path: str = BAGS_SORT_HEADER_PATH) -> int:
-    """FFH_BAGS_SORT_ABI_VERSION of include/ff_hip_bags_sort.h."""
-    m = re.search(r"#define\s+FFH_BAGS_SORT_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_BAGS_SORT_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
-
-
-class BagsSortApi:
-    """The bags-sort extension (include/ff_hip_bags_sort.h) of a loaded FFHLib; `bags_sort_api(lib)` builds it or raises.  Both calls take
-    the descriptor of the fused ragged update (BagsUpdateApi.descriptor)."""
-
-    def __init__(self, lib: "FFHLib"):
-        self.base = lib
-        for name, (res, args) in _SIGS_BAGS_SORT.items():
-            fn = getattr(lib.lib, name, None)
-            if fn is None:
-                raise FFHError(f"{lib.path}: no bags-sort extension ({name} missing; include/ff_hip_bags_sort.h)")
-            fn.restype = res
-            fn.argtypes = args
-        got = lib.lib.ffh_bags_sort_abi_version()
-        if got != bags_sort_header_abi_version():
-            raise FFHError(f"{lib.path}: bags-sort ABI version {got}, include/ff_hip_bags_sort.h says {bags_sort_header_abi_version()} (rebuild)")
-        self.lib = lib.lib
-        self.ctx = lib.ctx
+class BagsSortApi(ExtensionApi):
+    """Both calls take the descriptor of the fused ragged update (BagsUpdateApi.descriptor)."""
+    ext = BAGS_SORT_EXT
 
     def sort_rc(self, u: BagsUpdate | None, stream=None) -> int:
         """ffh_embedding_bwd_sort_multi_bags, returning its status code."""
@@ -1193,13 +821,10 @@ class BagsSortApi:
         self.base.check(self.apply_rc(u, stream), "ffh_embedding_bwd_apply_multi_bags")
 
 
-def bags_sort_api(lib: "FFHLib") -> BagsSortApi:
-    """The ragged sort / apply entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
-    return BagsSortApi(lib)
+bags_sort_api = BagsSortApi
 
 
 # ---- the pad extension (include/ff_hip_pad.h): variable-length bags, the id EMB_PAD_ID being "no lookup" ---------------------------------
-PAD_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_pad.h")
 EMB_PAD_ID = -1
 
 _SIGS_PAD = {
@@ -1211,41 +836,13 @@ _SIGS_PAD = {
     "ffh_embedding_bwd_apply_multi_bags_pad": (I, [P, C.POINTER(BagsUpdate), P]),
     "ffh_pad_mask_indices": (I, [P, P, L, C.c_uint64, L, F, P]),
 }
+PAD_EXT = _extension("pad", _SIGS_PAD, "pad")
+PAD_HEADER_PATH, pad_header_symbols, pad_header_abi_version = PAD_EXT.header_path, PAD_EXT.header_symbols, PAD_EXT.header_abi_version
 
 
-def pad_header_symbols(header_path: str = PAD_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_PAD_API_LIST X-macro in include/ff_hip_pad.h."""
-    m = re.search(r"#define FFH_PAD_API_LIST\(X\)(.*?)\n\n", open(header_path).read(), re.S)
-    if not m:
-        raise RuntimeError("FFH_PAD_API_LIST not found in " + header_path)
-    return re.findall(r"X\((\w+)\)", m.group(1))
-
-
-def pad_header_abi_version(header_path: str = PAD_HEADER_PATH) -> int:
-    """FFH_PAD_ABI_VERSION of include/ff_hip_pad.h."""
-    m = re.search(r"#define\s+FFH_PAD_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_PAD_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
-
-
-class PadApi:
-    """The pad extension (include/ff_hip_pad.h) of a loaded FFHLib; `pad_api(lib)` builds it or raises.  The gathers take the arguments of
-    BagsApi.rc, the update entries the descriptor of the ragged update (BagsUpdateApi.descriptor)."""
-
-    def __init__(self, lib: "FFHLib"):
-        self.base = lib
-        for name, (res, args) in _SIGS_PAD.items():
-            fn = getattr(lib.lib, name, None)
-            if fn is None:
-                raise FFHError(f"{lib.path}: no pad extension ({name} missing; include/ff_hip_pad.h)")
-            fn.restype = res
-            fn.argtypes = args
-        got = lib.lib.ffh_pad_abi_version()
-        if got != pad_header_abi_version():
-            raise FFHError(f"{lib.path}: pad ABI version {got}, include/ff_hip_pad.h says {pad_header_abi_version()} (rebuild)")
-        self.lib = lib.lib
-        self.ctx = lib.ctx
+class PadApi(ExtensionApi):
+    """The gathers take the arguments of BagsApi.rc, the update entries the descriptor of the ragged update (BagsUpdateApi.descriptor)."""
+    ext = PAD_EXT
 
     def fwd_rc(self, tables, in_dims, ntables: int, out_dim: int, batch: int, aggr: int, bf16: bool = False, stream=None) -> int:
         """ffh_embedding_fwd_multi_bags_pad[_bf16], returning its status code; `in_dims` from BagsApi.in_dims (or None: a null pointer)."""
@@ -1284,14 +881,10 @@ class PadApi:
         self.base.check(self.mask_rc(*args, **kw), "ffh_pad_mask_indices")
 
 
-def pad_api(lib: "FFHLib") -> PadApi:
-    """The pad entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
-    return PadApi(lib)
+pad_api = PadApi
 
 
 # ---- the pad-mean extension (include/ff_hip_pad_mean.h): the pad entries with a mean over the lookups that are there ---------------------
-PAD_MEAN_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_pad_mean.h")
-
 _SIGS_PAD_MEAN = {
     "ffh_pad_mean_abi_version": (I, []),
     "ffh_embedding_fwd_multi_bags_pad_mean": (I, [P, C.POINTER(EmbTable), C.POINTER(I), I, I, L, I, P]),
@@ -1300,41 +893,14 @@ _SIGS_PAD_MEAN = {
     "ffh_embedding_bwd_fused_multi_bags_pad_mean": (I, [P, C.POINTER(BagsUpdate), P]),
     "ffh_embedding_bwd_apply_multi_bags_pad_mean": (I, [P, C.POINTER(BagsUpdate), P]),
 }
+PAD_MEAN_EXT = _extension("pad_mean", _SIGS_PAD_MEAN, "pad-mean")
+PAD_MEAN_HEADER_PATH, pad_mean_header_symbols, pad_mean_header_abi_version = (
+    PAD_MEAN_EXT.header_path, PAD_MEAN_EXT.header_symbols, PAD_MEAN_EXT.header_abi_version)
 
 
-def pad_mean_header_symbols(header_path: str = PAD_MEAN_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_PAD_MEAN_API_LIST X-macro in include/ff_hip_pad_mean.h."""
-    m = re.search(r"#define FFH_PAD_MEAN_API_LIST\(X\)(.*?)\n\n", open(header_path).read(), re.S)
-    if not m:
-        raise RuntimeError("FFH_PAD_MEAN_API_LIST not found in " + header_path)
-    return re.findall(r"X\((\w+)\)", m.group(1))
-
-
-def pad_mean_header_abi_version(header_path: str = PAD_MEAN_HEADER_PATH) -> int:
-    """FFH_PAD_MEAN_ABI_VERSION of include/ff_hip_pad_mean.h."""
-    m = re.search(r"#define\s+FFH_PAD_MEAN_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_PAD_MEAN_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
-
-
-class PadMeanApi:
-    """The pad-mean extension (include/ff_hip_pad_mean.h) of a loaded FFHLib; `pad_mean_api(lib)` builds it or raises.  PadApi's methods without
-    the sort (the pad sort serves either apply), and the workspace query of the update."""
-
-    def __init__(self, lib: "FFHLib"):
-        self.base = lib
-        for name, (res, args) in _SIGS_PAD_MEAN.items():
-            fn = getattr(lib.lib, name, None)
-            if fn is None:
-                raise FFHError(f"{lib.path}: no pad-mean extension ({name} missing; include/ff_hip_pad_mean.h)")
-            fn.restype = res
-            fn.argtypes = args
-        got = lib.lib.ffh_pad_mean_abi_version()
-        if got != pad_mean_header_abi_version():
-            raise FFHError(f"{lib.path}: pad-mean ABI version {got}, include/ff_hip_pad_mean.h says {pad_mean_header_abi_version()} (rebuild)")
-        self.lib = lib.lib
-        self.ctx = lib.ctx
+class PadMeanApi(ExtensionApi):
+    """PadApi's methods without the sort (the pad sort serves either apply), and the workspace query of the update."""
+    ext = PAD_MEAN_EXT
 
     def fwd_rc(self, tables, in_dims, ntables: int, out_dim: int, batch: int, aggr: int, bf16: bool = False, stream=None) -> int:
         """ffh_embedding_fwd_multi_bags_pad_mean[_bf16], returning its status code; `in_dims` from BagsApi.in_dims (or None: a null pointer)."""
@@ -1367,15 +933,10 @@ class PadMeanApi:
         self.base.check(self.apply_rc(u, stream), "ffh_embedding_bwd_apply_multi_bags_pad_mean")
 
 
-def pad_mean_api(lib: "FFHLib") -> PadMeanApi:
-    """The pad-mean entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
-    return PadMeanApi(lib)
+pad_mean_api = PadMeanApi
 
 
 # ---- the q8 extension (include/ff_hip_q8.h): tables as 8-bit rows with a scale and a bias each; a quantizer and the gathers that read them ----
-Q8_HEADER_PATH = os.path.join(REPO_ROOT, "include", "ff_hip_q8.h")
-
-
 class EmbTableQ8(C.Structure):
     """struct ffh_emb_table_q8"""
     _fields_ = [("idx", P), ("rows", P), ("io", P), ("num_entries", L), ("ld", L), ("row_bytes", L)]
@@ -1394,40 +955,12 @@ _SIGS_Q8 = {
     "ffh_embedding_fwd_multi_q8": (I, [P, C.POINTER(EmbTableQ8), I, I, I, L, I, P]),
     "ffh_embedding_fwd_multi_bags_q8": (I, [P, C.POINTER(EmbTableQ8), C.POINTER(I), I, I, L, I, P]),
 }
+Q8_EXT = _extension("q8", _SIGS_Q8, "q8")
+Q8_HEADER_PATH, q8_header_symbols, q8_header_abi_version = Q8_EXT.header_path, Q8_EXT.header_symbols, Q8_EXT.header_abi_version
 
 
-def q8_header_symbols(header_path: str = Q8_HEADER_PATH) -> list[str]:
-    """Every symbol of the FFH_Q8_API_LIST X-macro in include/ff_hip_q8.h."""
-    m = re.search(r"#define FFH_Q8_API_LIST\(X\)(.*?)\n\n", open(header_path).read(), re.S)
-    if not m:
-        raise RuntimeError("FFH_Q8_API_LIST not found in " + header_path)
-    return re.findall(r"X\((\w+)\)", m.group(1))
-
-
-def q8_header_abi_version(header_path: str = Q8_HEADER_PATH) -> int:
-    """FFH_Q8_ABI_VERSION of include/ff_hip_q8.h."""
-    m = re.search(r"#define\s+FFH_Q8_ABI_VERSION\s+(\d+)", open(header_path).read())
-    if not m:
-        raise RuntimeError("FFH_Q8_ABI_VERSION not found in " + header_path)
-    return int(m.group(1))
-
-
-class Q8Api:
-    """The q8 extension (include/ff_hip_q8.h) of a loaded FFHLib; `q8_api(lib)` builds it or raises."""
-
-    def __init__(self, lib: "FFHLib"):
-        self.base = lib
-        for name, (res, args) in _SIGS_Q8.items():
-            fn = getattr(lib.lib, name, None)
-            if fn is None:
-                raise FFHError(f"{lib.path}: no q8 extension ({name} missing; include/ff_hip_q8.h)")
-            fn.restype = res
-            fn.argtypes = args
-        got = lib.lib.ffh_q8_abi_version()
-        if got != q8_header_abi_version():
-            raise FFHError(f"{lib.path}: q8 ABI version {got}, include/ff_hip_q8.h says {q8_header_abi_version()} (rebuild)")
-        self.lib = lib.lib
-        self.ctx = lib.ctx
+class Q8Api(ExtensionApi):
+    ext = Q8_EXT
 
     def row_bytes(self, out_dim: int) -> int:
         return int(self.lib.ffh_q8_row_bytes(int(out_dim)))
@@ -1482,9 +1015,7 @@ class Q8Api:
         self.base.check(self.fwd_bags_rc(*args, **kw), "ffh_embedding_fwd_multi_bags_q8")
 
 
-def q8_api(lib: "FFHLib") -> Q8Api:
-    """The 8-bit-row entry points of `lib`; FFHError when the library does not export them (e.g. the CPU oracle)."""
-    return Q8Api(lib)
+q8_api = Q8Api
 
 
 _hip_singleton: FFHLib | None = None

@@ -24,6 +24,44 @@ std::string default_backend_path() {
   return dir + "/../csrc/libffhip.so";
 }
 
+// The rule for an optional extension (a line of FFH_EXTENSIONS in backend.h), stated once: absent is fine (the library loads as before),
+// present means complete and of the header's version.  `older` is the one allowance a line may make: a library of that ABI version is taken
+// as it is, and the entries whose names begin with one of `may_lack` may be missing from it (they stay null).
+namespace {
+struct OlderAbi {
+  int version = 0;                       // 0: none
+  const char* may_lack[4] = {};
+};
+
+struct ExtensionLoad {
+  void* h;
+  const std::string& path;
+  const char* label;
+  const char* header;
+  int expected, got;                     // the header's version, what the library's version symbol returns
+  OlderAbi older;
+
+  bool older_abi() const { return older.version && got == older.version; }
+
+  template <class Fn>
+  void entry(Fn& slot, const char* name) const {
+    slot = reinterpret_cast<Fn>(dlsym(h, name));
+    if (slot) return;
+    if (older_abi())
+      for (const char* p : older.may_lack)
+        if (p && !strncmp(name, p, strlen(p))) return;
+    fprintf(stderr, "FATAL: %s exports part of include/%s: %s is missing\n", path.c_str(), header, name);
+    abort();
+  }
+
+  void check_version() const {
+    if (got == expected || older_abi()) return;
+    fprintf(stderr, "FATAL: %s has %s ABI version %d, expected %d\n", path.c_str(), label, got, expected);
+    abort();
+  }
+};
+}  // namespace
+
 const KernelApi* load_kernel_api(const std::string& path_in) {
   static std::map<std::string, KernelApi*>& cache = *new std::map<std::string, KernelApi*>();   // one table per library for the life of the process
   static std::mutex mu;
@@ -53,264 +91,19 @@ const KernelApi* load_kernel_api(const std::string& path_in) {
     fprintf(stderr, "FATAL: %s has ABI version %d, expected %d\n", path.c_str(), api->ffh_abi_version(), FFH_ABI_VERSION);
     abort();
   }
-  // the bf16-table extension: absent is fine (the library loads as before), present means complete and of this version
-  if (dlsym(h, "ffh_bf16_abi_version")) {
-    KernelApiBf16* b = new KernelApiBf16();
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_bf16.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
+  // the optional extensions, in the list's order: the version symbol says whether one is there
+#define FFH_LOAD_ENTRY(name) ext.entry(b->name, #name);
+#define FFH_LOAD_EXTENSION(field, Struct, LIST, version_symbol, VERSION, label, header, ...)               \
+  if (auto version = reinterpret_cast<int (*)(void)>(dlsym(h, #version_symbol))) {                          \
+    const ExtensionLoad ext{h, path, label, header, VERSION, version(), {__VA_ARGS__}};                     \
+    Struct* b = new Struct();                                                                               \
+    LIST(FFH_LOAD_ENTRY)                                                                                    \
+    ext.check_version();                                                                                    \
+    api->field = b;                                                                                         \
   }
-    FFH_BF16_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_bf16_abi_version() != FFH_BF16_ABI_VERSION) {
-      fprintf(stderr, "FATAL: %s has bf16 ABI version %d, expected %d\n", path.c_str(), b->ffh_bf16_abi_version(), FFH_BF16_ABI_VERSION);
-      abort();
-    }
-    api->bf16 = b;
-  }
-  // the CTR extension (include/ff_hip_ctr.h): the same rule
-  if (dlsym(h, "ffh_ctr_abi_version")) {
-    KernelApiCtr* b = new KernelApiCtr();
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_ctr.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
-  }
-    FFH_CTR_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_ctr_abi_version() != FFH_CTR_ABI_VERSION) {
-      fprintf(stderr, "FATAL: %s has CTR ABI version %d, expected %d\n", path.c_str(), b->ffh_ctr_abi_version(), FFH_CTR_ABI_VERSION);
-      abort();
-    }
-    api->ctr = b;
-  }
-  // the learning-rate extension (include/ff_hip_lr.h): the same rule
-  if (dlsym(h, "ffh_lr_abi_version")) {
-    KernelApiLr* b = new KernelApiLr();
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_lr.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
-  }
-    FFH_LR_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_lr_abi_version() != FFH_LR_ABI_VERSION) {
-      fprintf(stderr, "FATAL: %s has learning-rate ABI version %d, expected %d\n", path.c_str(), b->ffh_lr_abi_version(), FFH_LR_ABI_VERSION);
-      abort();
-    }
-    api->lr = b;
-  }
-  // the data extension (include/ff_hip_data.h): the same rule
-  if (dlsym(h, "ffh_data_abi_version")) {
-    KernelApiData* b = new KernelApiData();
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_data.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
-  }
-    FFH_DATA_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_data_abi_version() != FFH_DATA_ABI_VERSION) {
-      fprintf(stderr, "FATAL: %s has data ABI version %d, expected %d\n", path.c_str(), b->ffh_data_abi_version(), FFH_DATA_ABI_VERSION);
-      abort();
-    }
-    api->data = b;
-  }
-  // the cross extension (include/ff_hip_cross.h): the same rule
-  if (dlsym(h, "ffh_cross_abi_version")) {
-    KernelApiCross* b = new KernelApiCross();
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_cross.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
-  }
-    FFH_CROSS_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_cross_abi_version() != FFH_CROSS_ABI_VERSION) {
-      fprintf(stderr, "FATAL: %s has cross ABI version %d, expected %d\n", path.c_str(), b->ffh_cross_abi_version(), FFH_CROSS_ABI_VERSION);
-      abort();
-    }
-    api->cross = b;
-  }
-  // the digest extension (include/ff_hip_digest.h): the same rule
-  if (dlsym(h, "ffh_digest_abi_version")) {
-    KernelApiDigest* b = new KernelApiDigest();
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_digest.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
-  }
-    FFH_DIGEST_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_digest_abi_version() != FFH_DIGEST_ABI_VERSION) {
-      fprintf(stderr, "FATAL: %s has digest ABI version %d, expected %d\n", path.c_str(), b->ffh_digest_abi_version(), FFH_DIGEST_ABI_VERSION);
-      abort();
-    }
-    api->digest = b;
-  }
-  // the Adagrad extension (include/ff_hip_adagrad.h): the same rule
-  if (dlsym(h, "ffh_adagrad_abi_version")) {
-    KernelApiAdagrad* b = new KernelApiAdagrad();
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_adagrad.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
-  }
-    FFH_ADAGRAD_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_adagrad_abi_version() != FFH_ADAGRAD_ABI_VERSION) {
-      fprintf(stderr, "FATAL: %s has Adagrad ABI version %d, expected %d\n", path.c_str(), b->ffh_adagrad_abi_version(), FFH_ADAGRAD_ABI_VERSION);
-      abort();
-    }
-    api->adagrad = b;
-  }
-  // the row-wise Adagrad extension (include/ff_hip_rowwise.h): the same rule
-  if (dlsym(h, "ffh_rowwise_abi_version")) {
-    KernelApiRowwise* b = new KernelApiRowwise();
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_rowwise.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
-  }
-    FFH_ROWWISE_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_rowwise_abi_version() != FFH_ROWWISE_ABI_VERSION) {
-      fprintf(stderr, "FATAL: %s has row-wise Adagrad ABI version %d, expected %d\n", path.c_str(), b->ffh_rowwise_abi_version(), FFH_ROWWISE_ABI_VERSION);
-      abort();
-    }
-    api->rowwise = b;
-  }
-  // the fold extension (include/ff_hip_fold.h): the same rule
-  // ... except that a library of ABI 2 is taken as it is: the entries ABI 3 added (the data-gradient half) stay null and that half of the route is off
-  if (dlsym(h, "ffh_fold_abi_version")) {
-    KernelApiFold* b = new KernelApiFold();
-    const int fold_abi = reinterpret_cast<int (*)(void)>(dlsym(h, "ffh_fold_abi_version"))();
-    auto abi3_entry = [](const char* n) { return !strncmp(n, "ffh_fold_linear_bwd_dx", 22) || !strncmp(n, "ffh_fold_table_update", 21); };
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name && !(fold_abi == 2 && abi3_entry(#name))) {                    \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_fold.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
-  }
-    FFH_FOLD_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_fold_abi_version() != FFH_FOLD_ABI_VERSION && fold_abi != 2) {
-      fprintf(stderr, "FATAL: %s has fold ABI version %d, expected %d\n", path.c_str(), b->ffh_fold_abi_version(), FFH_FOLD_ABI_VERSION);
-      abort();
-    }
-    api->fold = b;
-  }
-  // the bags extension (include/ff_hip_bags.h): the same rule
-  if (dlsym(h, "ffh_bags_abi_version")) {
-    KernelApiBags* b = new KernelApiBags();
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_bags.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
-  }
-    FFH_BAGS_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_bags_abi_version() != FFH_BAGS_ABI_VERSION) {
-      fprintf(stderr, "FATAL: %s has bags ABI version %d, expected %d\n", path.c_str(), b->ffh_bags_abi_version(), FFH_BAGS_ABI_VERSION);
-      abort();
-    }
-    api->bags = b;
-  }
-  // the bags-update extension (include/ff_hip_bags_update.h): the same rule
-  if (dlsym(h, "ffh_bags_update_abi_version")) {
-    KernelApiBagsUpdate* b = new KernelApiBagsUpdate();
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_bags_update.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
-  }
-    FFH_BAGS_UPDATE_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_bags_update_abi_version() != FFH_BAGS_UPDATE_ABI_VERSION) {
-      fprintf(stderr, "FATAL: %s has bags-update ABI version %d, expected %d\n", path.c_str(), b->ffh_bags_update_abi_version(), FFH_BAGS_UPDATE_ABI_VERSION);
-      abort();
-    }
-    api->bags_update = b;
-  }
-  // the bags-sort extension (include/ff_hip_bags_sort.h): the same rule
-  if (dlsym(h, "ffh_bags_sort_abi_version")) {
-    KernelApiBagsSort* b = new KernelApiBagsSort();
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_bags_sort.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
-  }
-    FFH_BAGS_SORT_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_bags_sort_abi_version() != FFH_BAGS_SORT_ABI_VERSION) {
-      fprintf(stderr, "FATAL: %s has bags-sort ABI version %d, expected %d\n", path.c_str(), b->ffh_bags_sort_abi_version(), FFH_BAGS_SORT_ABI_VERSION);
-      abort();
-    }
-    api->bags_sort = b;
-  }
-  // the pad extension (include/ff_hip_pad.h): the same rule
-  if (dlsym(h, "ffh_pad_abi_version")) {
-    KernelApiPad* b = new KernelApiPad();
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_pad.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
-  }
-    FFH_PAD_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_pad_abi_version() != FFH_PAD_ABI_VERSION) {
-      fprintf(stderr, "FATAL: %s has pad ABI version %d, expected %d\n", path.c_str(), b->ffh_pad_abi_version(), FFH_PAD_ABI_VERSION);
-      abort();
-    }
-    api->pad = b;
-  }
-  // the pad-mean extension (include/ff_hip_pad_mean.h): the same rule
-  if (dlsym(h, "ffh_pad_mean_abi_version")) {
-    KernelApiPadMean* b = new KernelApiPadMean();
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_pad_mean.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
-  }
-    FFH_PAD_MEAN_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_pad_mean_abi_version() != FFH_PAD_MEAN_ABI_VERSION) {
-      fprintf(stderr, "FATAL: %s has pad-mean ABI version %d, expected %d\n", path.c_str(), b->ffh_pad_mean_abi_version(), FFH_PAD_MEAN_ABI_VERSION);
-      abort();
-    }
-    api->pad_mean = b;
-  }
-  // the q8 extension (include/ff_hip_q8.h): the same rule
-  if (dlsym(h, "ffh_q8_abi_version")) {
-    KernelApiQ8* b = new KernelApiQ8();
-#define FFH_LOAD(name)                                                        \
-  b->name = reinterpret_cast<decltype(b->name)>(dlsym(h, #name));             \
-  if (!b->name) {                                                             \
-    fprintf(stderr, "FATAL: %s exports part of include/ff_hip_q8.h: %s is missing\n", path.c_str(), #name);   \
-    abort();                                                                  \
-  }
-    FFH_Q8_API_LIST(FFH_LOAD)
-#undef FFH_LOAD
-    if (b->ffh_q8_abi_version() != FFH_Q8_ABI_VERSION) {
-      fprintf(stderr, "FATAL: %s has q8 ABI version %d, expected %d\n", path.c_str(), b->ffh_q8_abi_version(), FFH_Q8_ABI_VERSION);
-      abort();
-    }
-    api->q8 = b;
-  }
+  FFH_EXTENSIONS(FFH_LOAD_EXTENSION)
+#undef FFH_LOAD_EXTENSION
+#undef FFH_LOAD_ENTRY
   if (path_in.empty() && g_env_override)
     fprintf(stderr, "[DLRM] FFH_BACKEND_LIB: kernel library %s (%s)\n", path.c_str(), api->ffh_backend_name());
   cache[path] = api;
