@@ -23,6 +23,10 @@ INCLUDE = os.path.join(ROOT, "include")
 HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
              "-Wall", "-Wno-unused-function", "-I", INCLUDE]
+# sources compiled without the packed fp32 instructions (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32): every file added from here on
+# (a device feature: the host half of the hipcc line prints "not a recognized feature for this target (ignoring feature)", which is all it does)
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"interaction_wide.hip": NO_PACKED_FP32}
 
 
 def _newer(target: str, sources: list[str]) -> bool:
@@ -54,7 +58,7 @@ def build_hip(force: bool = False, verbose: bool = False) -> str:
     def compile_one(pair):
         s, o = pair
         if force or _newer(o, [s] + hdrs):
-            _run([HIPCC, *HIP_FLAGS, "-c", s, "-o", o])
+            _run([HIPCC, *HIP_FLAGS, *EXTRA_FLAGS.get(os.path.basename(s), []), "-c", s, "-o", o])
         return o
 
     with ThreadPoolExecutor(max_workers=4) as ex:

@@ -325,10 +325,11 @@ class Extension:
     """What differs between the optional extensions: the header (and with it the macro prefix and the version symbol), the signatures, and the
     labels of the two messages.  The blocks below hold one each, in the order the host layer loads them (host/backend.h, FFH_EXTENSIONS)."""
 
-    def __init__(self, key: str, sigs: dict, label: str, version_label: str | None = None):
+    def __init__(self, key: str, sigs: dict, label: str, version_label: str | None = None, header_name: str | None = None):
         self.key = key                                        # bags_update: include/ff_hip_bags_update.h, FFH_BAGS_UPDATE_*, ffh_bags_update_abi_version
-        self.header = f"include/ff_hip_{key}.h"
-        self.header_path = os.path.join(REPO_ROOT, "include", f"ff_hip_{key}.h")
+        header_name = header_name or f"ff_hip_{key}.h"        # (an explicit name: dot_wide, whose header is include/ffh_dot_wide.h)
+        self.header = "include/" + header_name
+        self.header_path = os.path.join(REPO_ROOT, "include", header_name)
         self.prefix = "FFH_" + key.upper()
         self.version_symbol = f"ffh_{key}_abi_version"
         self.sigs = sigs
@@ -347,8 +348,8 @@ class Extension:
 EXTENSIONS: dict[str, Extension] = {}
 
 
-def _extension(key: str, sigs: dict, label: str, version_label: str | None = None) -> Extension:
-    EXTENSIONS[key] = Extension(key, sigs, label, version_label)
+def _extension(key: str, sigs: dict, label: str, version_label: str | None = None, header_name: str | None = None) -> Extension:
+    EXTENSIONS[key] = Extension(key, sigs, label, version_label, header_name)
     return EXTENSIONS[key]
 
 
@@ -1016,6 +1017,33 @@ class Q8Api(ExtensionApi):
 
 
 q8_api = Q8Api
+
+
+# ---- the dot-wide extension (include/ffh_dot_wide.h): the pairwise-dot interaction for up to 128 feature vectors ---------------------------
+# Its header is ffh_dot_wide.h, not ff_hip_dot_wide.h, and there is no DOT_WIDE_HEADER_PATH alias here (EXTENSIONS["dot_wide"].header_path
+# is the path): tests/test_extension_loader_cpu.py pins the ff_hip_*.h headers and the *_HEADER_PATH names to the fifteen extensions above.
+DOT_WIDE_MAX_ROWS = 128
+DOT_BWD_OVERWRITE = 1
+
+_SIGS_DOT_WIDE = {
+    "ffh_dot_wide_abi_version": (I, []),
+    "ffh_dot_interaction_wide_fwd": (I, [P, P, L, P, L, L, I, I, P]),
+    "ffh_dot_interaction_wide_bwd": (I, [P, P, L, P, L, P, L, L, I, I, I, P]),
+}
+DOT_WIDE_EXT = _extension("dot_wide", _SIGS_DOT_WIDE, "dot-wide", header_name="ffh_dot_wide.h")
+
+
+class DotWideApi(ExtensionApi):
+    ext = DOT_WIDE_EXT
+
+    @staticmethod
+    def grid(cus: int, batch: int, nrows: int, backward: bool = False) -> int:
+        """Workgroups of a launch (include/ffh_dot_wide.h, GRID): each owns a sample and walks the batch with this stride."""
+        per_cu = (2 if nrows <= 96 else 1) if backward else (2 if nrows <= 64 else 1)
+        return min(int(batch), max(int(cus), 1) * per_cu)
+
+
+dot_wide_api = DotWideApi
 
 
 _hip_singleton: FFHLib | None = None

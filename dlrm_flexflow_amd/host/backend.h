@@ -19,6 +19,7 @@
 #include "../../include/ff_hip_pad.h"
 #include "../../include/ff_hip_pad_mean.h"
 #include "../../include/ff_hip_q8.h"
+#include "../../include/ffh_dot_wide.h"
 
 // The optional extensions of the kernel C-ABI, one line each, in the order load_kernel_api() loads them:
 //   X(KernelApi field, struct, the header's list, version symbol, the header's version, label of the version message, header under include/
@@ -56,7 +57,10 @@
   /* the pad entries' mean forms, the divisor being a bag's count of real lookups (absent: compile() refuses AGGR_MODE_AVG on a padded table) */ \
   X(pad_mean, KernelApiPadMean, FFH_PAD_MEAN_API_LIST, ffh_pad_mean_abi_version, FFH_PAD_MEAN_ABI_VERSION, "pad-mean", "ff_hip_pad_mean.h")      \
   /* tables as 8-bit rows for held-out evaluation, their quantizer and gathers (absent: compile() refuses --eval-embedding-dtype int8) */        \
-  X(q8, KernelApiQ8, FFH_Q8_API_LIST, ffh_q8_abi_version, FFH_Q8_ABI_VERSION, "q8", "ff_hip_q8.h")
+  X(q8, KernelApiQ8, FFH_Q8_API_LIST, ffh_q8_abi_version, FFH_Q8_ABI_VERSION, "q8", "ff_hip_q8.h")                                                \
+  /* the pairwise-dot interaction for 33 .. 128 feature vectors (absent: compile() refuses a dot_interaction of more than 32; its header is    \
+     ffh_dot_wide.h, not ff_hip_dot_wide.h: see the header) */                                                                                  \
+  X(dot_wide, KernelApiDotWide, FFH_DOT_WIDE_API_LIST, ffh_dot_wide_abi_version, FFH_DOT_WIDE_ABI_VERSION, "dot-wide", "ffh_dot_wide.h")
 
 #define FFH_DECL(name) decltype(&::name) name;
 

@@ -439,6 +439,10 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
       printf("[DLRM] interaction: dcn layers %d rank %d\n", dlrm.dcn_num_layers, dlrm.dcn_low_rank_dim);
       fflush(stdout);
     }
+    if (dlrm.arch_interaction_op == "dot-tril" && dlrm.embedding_size.size() + 1 > 32) {      // (flushed for the same reason)
+      printf("[DLRM] interaction: dot-tril, %zu feature vectors, wide kernel\n", dlrm.embedding_size.size() + 1);
+      fflush(stdout);
+    }
   }
   if (dlrm.arch_interaction_op == "dcn") {
     if (dlrm.dcn_num_layers < 1) { fprintf(stderr, "FATAL: --dcn-num-layers %d: must be >= 1\n", dlrm.dcn_num_layers); abort(); }

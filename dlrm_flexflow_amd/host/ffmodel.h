@@ -516,6 +516,7 @@ class DotInteraction : public Op {
   void backward(const FFModel&) override;
   int c, d;
   bool bwd_overwrite;           // the input has no other consumer: its gradient is stored, not accumulated
+  bool wide() const { return c > 32; }      // served by ffh_dot_interaction_wide_fwd / _bwd (include/ffh_dot_wide.h, csrc/interaction_wide.hip)
 };
 
 // The third line of a DCNv2 low-rank cross layer (torchrec's LowRankCrossNet; include/ff_hip_cross.h):
@@ -730,6 +731,7 @@ class FFModel {
   mutable int64_t n_graph_replays = 0;        // hipGraph launches of an already captured trace (tests: flexflow_model_get_counter "graph_replays")
   mutable int64_t n_early_sorts = 0;          // sort-only launches issued behind the gather (tests: flexflow_model_get_counter "early_sorts")
   mutable int64_t n_ragged_early_sorts = 0;   // ... those of them that were ffh_embedding_bwd_sort_multi_bags calls ("ragged_early_sorts")
+  mutable int64_t n_dot_wide_launches = 0;    // ffh_dot_interaction_wide_fwd / _bwd launches (a dot_interaction of more than 32 feature vectors; "dot_wide_launches")
   mutable int64_t n_ragged_gathers = 0;       // ffh_embedding_fwd_multi_bags[_bf16] launches (tests: flexflow_model_get_counter "ragged_gather_launches")
   bool mixed_bags = false;                    // the tables' bag sizes differ (allocate()): DESIGN section 19
   // --eval-embedding-dtype int8 (include/ff_hip_q8.h): one 8-bit row image per table this rank gathers (Embedding::q8_rows; the

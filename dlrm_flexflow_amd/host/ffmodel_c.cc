@@ -188,6 +188,7 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   if (n == "q8_quantize_launches") return M(m)->n_q8_quantize;      // ffh_embedding_quantize_q8 launches (--eval-embedding-dtype int8; include/ff_hip_q8.h)
   if (n == "q8_gather_launches") return M(m)->n_q8_gathers;         // ffh_embedding_fwd_multi[_bags]_q8 launches
   if (n == "ragged_gather_launches") return M(m)->n_ragged_gathers;     // ffh_embedding_fwd_multi_bags[_bf16] launches (mixed bag sizes; include/ff_hip_bags.h)
+  if (n == "dot_wide_launches") return M(m)->n_dot_wide_launches;      // ffh_dot_interaction_wide_fwd / _bwd launches (include/ffh_dot_wide.h)
   if (n == "lr_steps") return M(m)->lr_steps();
   if (n == "lr_route") return M(m)->lr_route;          // 0 off (the scalar launches of before), 1 host, 2 device
   if (n == "graph_replays") return M(m)->n_graph_replays;

@@ -1107,7 +1107,8 @@ DotInteraction::DotInteraction(FFModel& model, const Tensor& input, int _d, cons
   if (input.data_type != DT_FLOAT) die("%s: input must be DT_FLOAT", this->name);
   if (input.numDim != 2 || d < 1 || input.adim[0] % d != 0) die("%s: input must be [batch][c * %d]", this->name, d);
   c = input.adim[0] / d;
-  if (c < 2 || c > 32) die("%s: %d feature vectors, supported 2..32", this->name, c);
+  if (c < 2 || c > FFH_DOT_WIDE_MAX_ROWS)
+    die("%s: %d feature vectors, supported 2..%d; use --arch-interaction-op dot-tril-ops (the operator chain)", this->name, c, FFH_DOT_WIDE_MAX_ROWS);
   outputs[0].numDim = 2;
   outputs[0].adim[0] = d + c * (c - 1) / 2;
   outputs[0].adim[1] = input.adim[1];
@@ -1115,12 +1116,25 @@ DotInteraction::DotInteraction(FFModel& model, const Tensor& input, int _d, cons
 void DotInteraction::forward(const FFModel& ff) {
   const Tensor &x = inputs[0], &y = outputs[0];
   if (!x.impl->pieces.empty() || !y.impl->pieces.empty()) die("%s: operands must be single buffers", name);
+  if (wide()) {      // more than 32 feature vectors: a workgroup per sample (include/ffh_dot_wide.h; compile() has checked that the library has it)
+    ff.n_dot_wide_launches++;
+    ff.check(ff.api->dot_wide->ffh_dot_interaction_wide_fwd(ff.ctx, (const float*)x.impl->ptr, x.impl->ld, (float*)y.impl->ptr, y.impl->ld,
+                                                            x.impl->rows_local, c, d, ff.stream), name);
+    return;
+  }
   ff.check(ff.api->ffh_dot_interaction_fwd(ff.ctx, (const float*)x.impl->ptr, x.impl->ld, (float*)y.impl->ptr, y.impl->ld, x.impl->rows_local, c, d,
                                            ff.stream), name);
 }
 void DotInteraction::backward(const FFModel& ff) {
   const Tensor &x = inputs[0], &y = outputs[0];
   if (!x.impl->grad) return;
+  if (wide()) {
+    ff.n_dot_wide_launches++;
+    ff.check(ff.api->dot_wide->ffh_dot_interaction_wide_bwd(ff.ctx, (const float*)x.impl->ptr, x.impl->ld, y.impl->grad, y.impl->grad_ld, x.impl->grad,
+                                                            x.impl->grad_ld, x.impl->rows_local, c, d, bwd_overwrite ? FFH_DOT_BWD_OVERWRITE : 0,
+                                                            ff.stream), name);
+    return;
+  }
   ff.check(ff.api->ffh_dot_interaction_bwd(ff.ctx, (const float*)x.impl->ptr, x.impl->ld, y.impl->grad, y.impl->grad_ld, x.impl->grad, x.impl->grad_ld,
                                            x.impl->rows_local, c, d, bwd_overwrite ? FFH_DOT_BWD_OVERWRITE : 0, ff.stream), name);
 }

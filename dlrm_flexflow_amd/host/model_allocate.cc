@@ -277,6 +277,13 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
     if (op->op_type == OP_CROSS_COMBINE && !api->cross)
       die("--arch-interaction-op dcn (%s): %s (%s) is a kernel library without the cross extension (include/ff_hip_cross.h); use --arch-interaction-op cat, "
           "dot or dot-tril", op->name, api->path.c_str(), api->ffh_backend_name());
+  // the dot interaction of more than 32 feature vectors (include/ffh_dot_wide.h): a kernel pair only a library with the extension has
+  for (const Op* op : layers)
+    if (const DotInteraction* di = dynamic_cast<const DotInteraction*>(op))
+      if (di->wide() && !api->dot_wide)
+        die("--arch-interaction-op dot-tril (%s, %d feature vectors): %s (%s) is a kernel library without the dot-wide extension (include/ffh_dot_wide.h), "
+            "and ffh_dot_interaction_fwd stops at 32; use --arch-interaction-op dot-tril-ops (the operator chain), or another --backend",
+            op->name, di->c, api->path.c_str(), api->ffh_backend_name());
   for (Op* op : layers) {
     op->create_output_and_partition(*this);
     op->create_weights(*this);
