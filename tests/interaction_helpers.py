@@ -2,7 +2,10 @@
 
 Used by tests/test_interaction_sweep_cpu.py (the oracle library, on a CPU: proves the harness) and tests/test_gpu_interaction_sweep.py (the four
 MFMA kernels of csrc/interaction.hip).  Nothing here calls the oracle library: the reference is plain numpy in float64, written from the contract
-in the header.  tests/dot_helpers.py is the model-level helper and has nothing to do with this file.
+in the header.  tests/dot_helpers.py is the model-level helper and has nothing to do with this file.  The wide entries of include/ffh_dot_wide.h
+(up to 128 rows, csrc/interaction_wide.hip) have the same contract: the same generator, reference, bound and checker serve them, with their own
+dispatch (wide_predicates, wide_kernel), call (run_wide_case), edge table and random draws (wide_edge_table, draw_wide_cases) below, used by
+tests/test_dot_wide_sweep_cpu.py and tests/test_gpu_dot_wide_sweep.py.  The narrow tables (MAX_C, edge_table, EDGE_NAMES, draw_cases) do not change.
 
   forward    out[b, :d]                    =  z[b, 0, :]                                   (bit for bit)
              out[b, d + i (i - 1) / 2 + j] =  sum_k z[b, i, k] z[b, j, k]      i > j
@@ -60,6 +63,7 @@ class Case:
         self.ldg = self.wo + 3 if ldg is None else int(ldg)
         self.z_off, self.out_off, self.g_off, self.zg_off = int(z_off), int(out_off), int(g_off), int(zg_off)
         self.overwrite, self.dist, self.seed = bool(overwrite), dist, int(seed)
+        self.wide = False                                           # run_wide_case and the wide tables set it: served by the wide entries
 
     @property
     def flags(self):
@@ -68,8 +72,8 @@ class Case:
     def __repr__(self):
         s = f"Case({self.name}: {self.kind} B={self.batch} c={self.c} d={self.d} {self.dist} seed={self.seed} ldz={self.ldz}+{self.z_off}"
         if self.kind == "fwd":
-            return s + f" ldo={self.ldo}+{self.out_off} -> {kernel(self)})"
-        return s + f" ldg={self.ldg}+{self.g_off} ldzg={self.ldzg}+{self.zg_off} overwrite={self.overwrite} -> {kernel(self)})"
+            return s + f" ldo={self.ldo}+{self.out_off} -> {kernel_of(self)})"
+        return s + f" ldg={self.ldg}+{self.g_off} ldzg={self.ldzg}+{self.zg_off} overwrite={self.overwrite} -> {kernel_of(self)})"
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -98,6 +102,45 @@ def kernel(case):
 
 ALL_KERNELS = (["fwd_lds<OV=4>", "fwd_lds<OV=1>", "fwd<VEC=4,OV=4>", "fwd<VEC=4,OV=1>", "fwd<VEC=1,OV=1>"]
                + [f"bwd_d128<ACCUM={a}>" for a in (0, 1)] + [f"bwd<VEC={v},ACCUM={a}>" for v in (4, 1) for a in (0, 1)])
+
+
+# the dispatch rules of ffh_dot_interaction_wide_fwd / _bwd (csrc/interaction_wide.hip; include/ffh_dot_wide.h), the same way.  The context's
+# zero block is taken to exist (the forward's LDS-DMA form needs it where d is no multiple of 128; every context of the tests has one).
+WIDE_MAX_C = 128                      # FFH_DOT_WIDE_MAX_ROWS
+WIDE_CHUNK = 128                      # columns of a forward k-chunk
+WIDE_ITEM = 64                        # columns of a backward item
+
+
+def wide_predicates(case):
+    T = (case.c + 31) // 32
+    if case.kind == "fwd":
+        v4 = case.d % 4 == 0 and case.ldz % 4 == 0 and case.z_off % 4 == 0
+        return {"v4": v4, "o4": v4 and case.ldo % 4 == 0 and case.out_off % 4 == 0, "T": T, "chunks": -(-case.d // WIDE_CHUNK),
+                "per_cu": 2 if T <= 2 else 1}                    # FFH_DOT_WIDE_FWD_PER_CU
+    v4 = case.d % 4 == 0 and case.ldz % 4 == 0 and case.ldzg % 4 == 0 and case.z_off % 4 == 0 and case.zg_off % 4 == 0
+    return {"v4": v4, "T": T, "items": T * -(-case.d // WIDE_ITEM), "overwrite": case.overwrite,
+            "per_cu": 2 if T <= 3 else 1}                        # FFH_DOT_WIDE_BWD_PER_CU
+
+
+def wide_kernel(case):
+    """The instantiation of csrc/interaction_wide.hip that serves the case."""
+    p = wide_predicates(case)
+    if case.kind == "fwd":
+        return f"wide_fwd<VEC={4 if p['v4'] else 1},OV={4 if p['o4'] else 1}>"
+    return f"wide_bwd<T={p['T']},VEC={4 if p['v4'] else 1},ACCUM={0 if case.overwrite else 1}>"
+
+
+ALL_WIDE_KERNELS = (["wide_fwd<VEC=4,OV=4>", "wide_fwd<VEC=4,OV=1>", "wide_fwd<VEC=1,OV=1>"]
+                    + [f"wide_bwd<T={t},VEC={v},ACCUM={a}>" for t in (1, 2, 3, 4) for v in (4, 1) for a in (0, 1)])
+
+
+def kernel_of(case):
+    return wide_kernel(case) if case.wide else kernel(case)
+
+
+def wide_grid(cus, c, backward=False):
+    """"Gf(c)" / "Gb(c)": workgroups of a launch on a batch that fills the grid; a workgroup's second sample is sample G + its index."""
+    return capi.DotWideApi.grid(cus, 1 << 30, c, backward=backward)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -156,6 +199,36 @@ def run_case(lib, be, case, args=None, null=(), inp=None):
     for _, b in inputs + outputs:
         b.fetch()
     return Result(case, inp, rc, inputs, outputs)
+
+
+def run_wide_case(wide, be, case, args=None, null=(), inp=None):
+    """run_case on ffh_dot_interaction_wide_fwd / _bwd (`wide`: capi.dot_wide_api(lib)).  The case is filed under its wide kernel from here on."""
+    case.wide = True
+    inp = inp or make_inputs(case)
+    B, c, d = case.batch, case.c, case.d
+    a = dict(nrows=c, d=d, batch=B, ldz=case.ldz, ldo=case.ldo, ldg=case.ldg, ldzg=case.ldzg, flags=case.flags)
+    a.update(args or {})
+    Z = Buf(be, B, c * d, case.ldz, case.z_off, inp["z"])
+    at = lambda name, buf: None if name in null else buf.ptr
+    if case.kind == "fwd":
+        O = Buf(be, B, case.wo, case.ldo, case.out_off)
+        inputs, outputs = [("z", Z)], [("out", O)]
+        rc = wide.rc("ffh_dot_interaction_wide_fwd", at("z", Z), a["ldz"], at("out", O), a["ldo"], a["batch"], a["nrows"], a["d"], None)
+    else:
+        Gr = Buf(be, B, case.wo, case.ldg, case.g_off, inp["g"])
+        ZG = Buf(be, B, c * d, case.ldzg, case.zg_off, inp["old"])
+        inputs, outputs = [("z", Z), ("out_grad", Gr)], [("z_grad", ZG)]
+        rc = wide.rc("ffh_dot_interaction_wide_bwd", at("z", Z), a["ldz"], at("out_grad", Gr), a["ldg"], at("z_grad", ZG), a["ldzg"], a["batch"],
+                     a["nrows"], a["d"], a["flags"], None)
+    be.sync()
+    for _, b in inputs + outputs:
+        b.fetch()
+    return Result(case, inp, rc, inputs, outputs)
+
+
+def run_and_check_wide(wide, be, case):
+    res = run_wide_case(wide, be, case)
+    return res, check(res)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -227,7 +300,7 @@ def compare_slice(case, inp, got, lo, hi):
 
 
 def note_worst(case, worst):
-    kern = kernel(case)
+    kern = kernel_of(case)
     WORST[kern] = max(WORST.get(kern, 0.0), worst)
 
 
@@ -374,3 +447,124 @@ def draw_cases(seed, cus, count=6):
     """The cases of one seed.  Batches come from {1..9, A +- 3, 2A +- 3}: nothing beyond the capped grids (the edge table has those)."""
     rng = np.random.default_rng(seed)
     return [draw_case(rng, cus, name=f"seed{seed}.{i}") for i in range(count)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the wide entries (33 .. 128 rows; include/ffh_dot_wide.h): the same generator, reference and bound, their own edge table and random draws
+WIDE_TILE_EDGES = (2, 3, 31, 32, 33, 34, 63, 64, 65, 66, 95, 96, 97, 98, 127, 128)     # both sides of every 32-row tile edge, the minimum, the maximum
+WIDE_MAX_ELEMS = 1 << 24              # floats of a buffer of any case of the two wide tables
+WIDE_SEEDS = range(8)
+
+
+def _wide_trio(cus, name, batch, c, d, dists=("uniform",), kinds=("fwd", "bwd"), **kw):
+    """_trio on the wide entries.  `batch` may be a function of G: the forward leg then gets batch(Gf(c)), the backward legs batch(Gb(c))."""
+    out = []
+    for kind in kinds:
+        B = batch(wide_grid(cus, c, backward=kind == "bwd")) if callable(batch) else batch
+        out += _trio(name, B, c, d, dists, kinds=(kind,), **kw)
+    for case in out:
+        case.wide = True
+    return out
+
+
+def _differing_strides(c, d):
+    """Four different strides and four different nonzero offsets, all multiples of 4 (those of the narrow table's strides-differ)."""
+    wo = d + c * (c - 1) // 2
+    return dict(ldz=_up4(c * d) + 8, z_off=4, ldo=_up4(wo) + 4, out_off=8, ldg=_up4(wo) + 12, g_off=12, ldzg=_up4(c * d) + 16, zg_off=16)
+
+
+def wide_edge_table(cus):
+    """name -> list of cases of the wide entries; every entry is the smallest shape that reaches its branch.  Gf(c) / Gb(c) = wide_grid: a
+    workgroup of a full grid takes sample G + its index second, 2 G + its index third.  Entries that share a prefix are one subject, split so that
+    each stays a matter of seconds; wide_entries(table, prefix) joins them again."""
+    UI, US = ("uniform", "integer"), ("uniform", "scaled")
+    trio = lambda *a, **kw: _wide_trio(cus, *a, **kw)
+    t = {}
+    # the forward's image 1 above 64 rows (LDS bytes 49152.. at T = 3, 65536.. at T = 4) is only read for a workgroup's second item: a second
+    # sample here.  The backward legs: the register prefetch of the next sample's triangle at T = 3 and 4.
+    for c in (65, 96, 97, 128):
+        t[f"second-image-high-c{c}"] = trio("second-image-high", lambda G: G + 3, c, 128, UI)
+    t["second-image-high-third-sample"] = trio("second-image-high third", lambda G: 2 * G + 1, 128, 128, UI)
+    # the LDS-DMA forward over two and three k-chunks (double buffering inside a sample, acc kept across chunks, a last chunk of 4 columns whose
+    # other pieces are the zero block); with an even number of chunks the next sample's first chunk lands in image 0 again, with an odd one in
+    # the other image
+    for d in (132, 256, 260):
+        t[f"chunks-vec4-d{d}"] = [case for c in (33, 64, 65, 128) for case in trio("chunks-vec4", 3, c, d, UI)]
+    for c, d in ((33, 132), (33, 256), (128, 260)):
+        t[f"chunks-vec4-next-sample-{c}x{d}"] = _wide_trio(cus, "chunks-vec4 next", lambda G, gf=wide_grid(cus, c): gf + 2, c, d, UI)
+    # the pass-through stores with the LDS-DMA image: 4-byte because of the stride, 4-byte because of the base, 16-byte at a nonzero base
+    t["fwd-ov1"] = []
+    for c in (33, 97):
+        for d in (36, 128, 260):
+            wo = d + c * (c - 1) // 2
+            t["fwd-ov1"] += (trio("fwd-ov1 stride", 3, c, d, UI, kinds=("fwd",), ldo=(wo + 1) | 1)
+                             + trio("fwd-ov1 base", 3, c, d, UI, kinds=("fwd",), ldo=_up4(wo) + 4, out_off=1)
+                             + trio("fwd-ov4-base", 3, c, d, UI, kinds=("fwd",), ldo=_up4(wo) + 4, out_off=4))
+    # the scalar form at T = 1 .. 4: odd d (the `col + 1 < d` guards of the backward, the forward's jmax tail), and d = 128 that has to leave the
+    # 16-byte forms because of a base or a stride (zg_off: the backward alone)
+    for c in (31, 33, 65, 97):
+        t[f"scalar-every-T-c{c}"] = ([case for d in (1, 3, 63, 65, 129) for case in trio("scalar odd-d", 3, c, d, US)]
+                                     + trio("scalar z_off", 3, c, 128, US, z_off=1) + trio("scalar ldz", 3, c, 128, US, ldz=c * 128 + 2)
+                                     + trio("scalar zg_off", 3, c, 128, US, kinds=("bwd",), zg_off=1))
+    t["scalar-every-T-extremes"] = trio("scalar extremes", 3, 128, 1, US) + trio("scalar extremes", 3, 2, 2, US)
+    # the 8-byte backward: T ceil(d / 64) items against four waves (1 .. 20 items), a last column block of 4, 60 and 64 columns
+    for c in (33, 128):
+        t[f"bwd-column-blocks-c{c}"] = [case for d in (4, 60, 64, 68, 124, 132, 192, 260) for case in trio("bwd-column-blocks", 3, c, d, UI, kinds=("bwd",))]
+    # every triangle size: the store guards i < c && j < i, the row clamps to c - 1, the DMA's odd half piece
+    for T in (1, 2, 3, 4):
+        t[f"c-range-d8-T{T}"] = [case for c in range(max(2, 32 * T - 31), 32 * T + 1) for case in trio("c-range", 2, c, 8, ("integer",))]
+    t["c-range-d128"] = [case for c in WIDE_TILE_EDGES for case in trio("c-range", 2, c, 128, UI)]
+    t["strides-differ"] = [case for c, d in ((40, 12), (100, 128)) for case in trio("strides-differ", 11, c, d, UI, **_differing_strides(c, d))]
+    # idle workgroups; a ragged last pass and a workgroup's fourth sample
+    t["batches-128x128"] = [case for B in (1, 2, 3, 4, 5) for case in trio("batches", B, 128, 128)]
+    t["batches-33x8"] = [case for f in (lambda G: G - 1, lambda G: G, lambda G: G + 1, lambda G: 3 * G + 2) for case in trio("batches", f, 33, 8, UI)]
+    return t
+
+
+WIDE_EDGE_NAMES = list(wide_edge_table(1))
+
+
+def wide_entries(table, prefix):
+    """The cases of every entry of the table whose name starts with the prefix."""
+    return [case for name, cases in table.items() if name.startswith(prefix) for case in cases]
+
+
+def draw_wide_case(rng, cus, name="random"):
+    """draw_case for the wide entries: c from 2 .. 128, half the draws from the tile edges; d, strides and offsets as draw_case draws them;
+    batches from {1..9, G +- 3, 2 G +- 3} with G the grid of the drawn kind.  A case beyond 2^24 floats draws d again from 1 .. 32."""
+    kind = "fwd" if rng.random() < 0.375 else "bwd"                 # (3 forward forms, 16 backward ones)
+    c = int(rng.choice(WIDE_TILE_EDGES)) if rng.random() < 0.5 else int(rng.integers(2, WIDE_MAX_C + 1))
+    m = int(rng.integers(3))
+    d = 128 if m == 0 else 4 * int(rng.integers(1, 76)) if m == 1 else int(rng.integers(1, 301))
+    G = wide_grid(cus, c, backward=kind == "bwd")
+    m = int(rng.integers(3))
+    batch = int(rng.integers(1, 10)) if m == 0 else max(1, m * G + int(rng.integers(-3, 4)))
+    if batch * c * d > WIDE_MAX_ELEMS - (batch + 1) * 64:          # (the margin: the padding of the strides and offsets below)
+        d = int(rng.integers(1, 33))
+    wo = d + c * (c - 1) // 2
+    if rng.random() < 0.6:       # strides and offsets that keep a 16-byte alignment the width allows
+        pad, off = (lambda: 4 * int(rng.integers(0, 4))), (lambda: 4 * int(rng.integers(0, 3)))
+        ldz, ldzg, ldo = _up4(c * d) + pad(), _up4(c * d) + pad(), _up4(wo) + pad()
+    else:
+        pad, off = (lambda: int(rng.choice([0, 0, 1, 2, 3, 4, 5, 8]))), (lambda: int(rng.integers(0, 6)))
+        ldz, ldzg, ldo = c * d + pad(), c * d + pad(), wo + pad()
+    case = Case(name, kind, batch, c, d, ldz=ldz, z_off=off(), ldo=ldo, out_off=off(), ldg=wo + int(rng.choice([0, 1, 2, 3, 4, 7])),
+                g_off=int(rng.integers(0, 6)), ldzg=ldzg, zg_off=off(), overwrite=bool(rng.random() < 0.5), dist=str(rng.choice(DISTS)),
+                seed=int(rng.integers(1 << 30)))
+    case.wide = True
+    return case
+
+
+def draw_wide_cases(seed, cus, count=6):
+    rng = np.random.default_rng([seed, 23])
+    return [draw_wide_case(rng, cus, name=f"wide-seed{seed}.{i}") for i in range(count)]
+
+
+def buffer_elems(case):
+    """Floats of the largest buffer of the case, as Buf allocates it."""
+    sizes = [case.z_off + case.batch * case.ldz]
+    if case.kind == "fwd":
+        sizes.append(case.out_off + case.batch * case.ldo)
+    else:
+        sizes += [case.g_off + case.batch * case.ldg, case.zg_off + case.batch * case.ldzg]
+    return max(sizes)

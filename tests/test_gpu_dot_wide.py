@@ -1,15 +1,15 @@
 """GPU tests (-m gpu) of the pairwise-dot interaction for up to 128 feature vectors (include/ffh_dot_wide.h, csrc/interaction_wide.hip).
 
 The float64 reference, the input distributions, the sentinel buffers and the derived bound |got - ref| <= (k + 2) 2^-23 mass + k tiny32 are those of
-tests/interaction_helpers.py (nothing in them depends on c <= 32); only the two calls are restated, because the helper's run_case calls the narrow
-entries.  `integer` inputs make every fp32 operation exact: the result has to equal the reference.
+tests/interaction_helpers.py (nothing in them depends on c <= 32), the calls its run_wide_case.  `integer` inputs make every fp32 operation exact:
+the result has to equal the reference.  tests/test_gpu_dot_wide_sweep.py is the sweep of every kernel form; these are the shapes of the models.
 """
 import numpy as np
 import pytest
 
 from dlrm_flexflow_amd import capi, ffmodel
 import interaction_helpers as IH
-from interaction_helpers import Buf, Case
+from interaction_helpers import Case
 
 pytestmark = pytest.mark.gpu
 
@@ -29,24 +29,8 @@ def wide(hip):
 
 
 def run(wide, be, case, args=None):
-    """interaction_helpers.run_case on the wide entries; `args` replaces arguments of the call without changing what is allocated."""
-    inp = IH.make_inputs(case)
-    a = dict(nrows=case.c, ldo=case.ldo, flags=case.flags)
-    a.update(args or {})
-    Z = Buf(be, case.batch, case.c * case.d, case.ldz, case.z_off, inp["z"])
-    if case.kind == "fwd":
-        O = Buf(be, case.batch, case.wo, case.ldo, case.out_off)
-        inputs, outputs = [("z", Z)], [("out", O)]
-        rc = wide.rc("ffh_dot_interaction_wide_fwd", Z.ptr, case.ldz, O.ptr, a["ldo"], case.batch, a["nrows"], case.d, None)
-    else:
-        Gr = Buf(be, case.batch, case.wo, case.ldg, case.g_off, inp["g"])
-        ZG = Buf(be, case.batch, case.c * case.d, case.ldzg, case.zg_off, inp["old"])
-        inputs, outputs = [("z", Z), ("out_grad", Gr)], [("z_grad", ZG)]
-        rc = wide.rc("ffh_dot_interaction_wide_bwd", Z.ptr, case.ldz, Gr.ptr, case.ldg, ZG.ptr, case.ldzg, case.batch, a["nrows"], case.d, a["flags"], None)
-    be.sync()
-    for _, b in inputs + outputs:
-        b.fetch()
-    return IH.Result(case, inp, rc, inputs, outputs)
+    """interaction_helpers.run_wide_case; `args` replaces arguments of the call without changing what is allocated."""
+    return IH.run_wide_case(wide, be, case, args)
 
 
 @pytest.mark.parametrize("dist", ["uniform", "integer"])
