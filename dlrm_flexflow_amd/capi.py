@@ -686,6 +686,24 @@ class FoldApi(ExtensionApi):
 fold_api = FoldApi
 
 
+# ---- the fused-gather extension (include/ffh_fused_gather.h): the fold's forward gather-add inside the first top GEMM's epilogue ---------------
+# Like dot_wide below: a header outside ff_hip_*.h and no FUSED_GATHER_HEADER_PATH alias (EXTENSIONS["fused_gather"].header_path is the path).
+_SIGS_FUSED_GATHER = {
+    "ffh_fused_gather_abi_version": (I, []),
+    # (tables, ntables, bag, aggr, x, ldx, y, ldy, w, bias, in, out, batch, act, keep, nkeep[, stream])
+    "ffh_fused_gather_linear_fwd": (I, [P, C.POINTER(EmbTable), I, I, I, P, L, P, L, P, P, I, I, L, I, C.POINTER(FoldSeg), I, P]),
+    "ffh_fused_gather_linear_fwd_plan": (I, [P, C.POINTER(EmbTable), I, I, I, P, L, P, L, P, P, I, I, L, I, C.POINTER(FoldSeg), I]),
+}
+FUSED_GATHER_EXT = _extension("fused_gather", _SIGS_FUSED_GATHER, "fused-gather", header_name="ffh_fused_gather.h")
+
+
+class FusedGatherApi(ExtensionApi):
+    ext = FUSED_GATHER_EXT
+
+
+fused_gather_api = FusedGatherApi
+
+
 # ---- the bags extension (include/ff_hip_bags.h): the gather with a bag size per table, one launch ------------------------------------------
 BAGS_MAX_IN_DIM = 65535
 

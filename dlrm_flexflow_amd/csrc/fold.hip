@@ -25,6 +25,7 @@
 #include "lr_state.h"
 
 #include "../../include/ff_hip_fold.h"
+#include "../../include/ffh_fused_gather.h"
 
 using namespace ffh_gemm;
 
@@ -504,6 +505,46 @@ int ffh_fold_linear_fwd(ffh_ctx* c, const float* x, int64_t ldx, float* y, int64
   FFH_LAUNCH_CHECK(c, "fold_gemm_kernel (forward)");
   ffh_route_add(c, "fold_linear_fwd gemm|mfma_32x64x16");
   return FFH_OK;
+}
+
+namespace {
+// what ffh_fused_gather_linear_fwd and its plan query share: 1 launched (dry: would be), or the error left in the ctx
+int fold_fwd_gather(ffh_ctx* c, const ffh_emb_table* tables, int ntables, int bag, int aggr, const float* x, int64_t ldx, float* y, int64_t ldy, const float* w,
+                    const float* bias, int in, int out, int64_t batch, int act, const ffh_fold_seg* keep, int nkeep, bool dry, ffh_stream s) {
+  FFH_REQUIRE(c, tables && ntables >= 1 && bag >= 1, "fold_linear_fwd_gather: bad table list");
+  const int rc = fold_fwd_check(c, x, ldx, y, ldy, w, in, out, batch, keep, nkeep, nullptr, 0);
+  if (rc != FFH_OK) return rc;
+  for (int t = 0; t < ntables && t < FFH_FUSED_GATHER_MAX_TABLES; t++)
+    FFH_REQUIRE(c, tables[t].weight && tables[t].num_entries >= 1 && (batch == 0 || tables[t].idx), "fold_linear_fwd_gather: bad table");
+  if (aggr != FFH_AGGR_MODE_SUM) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_linear_fwd_gather: sum aggregation only");
+  if (ntables > FFH_FUSED_GATHER_MAX_TABLES || bag > FFH_FUSED_GATHER_MAX_BAG || ntables * bag > FFH_FUSED_GATHER_MAX_TERMS)
+    return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_linear_fwd_gather: at most 16 tables, 4 ids per sample and table, 32 ids per sample");
+  if (act != FFH_AC_MODE_NONE && act != FFH_AC_MODE_RELU && act != FFH_AC_MODE_SIGMOID && act != FFH_AC_MODE_GELU)
+    return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_linear_fwd_gather: activation not supported (NONE, RELU, SIGMOID, GELU)");
+  unsigned long long mask[2]; int nk = 0;
+  if (batch == 0 || !fold_fwd_served(c, x, ldx, y, ldy, w, in, out, keep, nkeep, nullptr, 0) || !fold_keep_mask(in, keep, nkeep, mask, &nk) || (bias && !al16(bias)))
+    return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_linear_fwd_gather: the layer does not run whole tiles on the persistent forward kernel");
+  FoldGatherList gl{};
+  for (int t = 0; t < ntables; t++) { gl.idx[t] = tables[t].idx; gl.p[t] = tables[t].weight; }
+  gl.ldp = out; gl.ntables = ntables; gl.L = bag;
+  if (!dry) ffh_route_clear(c);
+  const int r = launch_gemm_sk_fold_gather(c, fold_fwd_gemm(x, ldx, y, ldy, w, bias, in, out, batch, act), mask, nk, gl, dry, s, "fold_linear_fwd_gather gemm");
+  if (r == 0) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "fold_linear_fwd_gather: the layer does not run whole tiles on the persistent forward kernel, or a product is not aligned");
+  return r;
+}
+}  // namespace
+
+int ffh_fused_gather_abi_version(void) { return FFH_FUSED_GATHER_ABI_VERSION; }
+
+int ffh_fused_gather_linear_fwd_plan(ffh_ctx* c, const ffh_emb_table* tables, int ntables, int bag, int aggr, const float* x, int64_t ldx, const float* y, int64_t ldy,
+                                    const float* w, const float* bias, int in, int out, int64_t batch, int act, const ffh_fold_seg* keep, int nkeep) {
+  return fold_fwd_gather(c, tables, ntables, bag, aggr, x, ldx, const_cast<float*>(y), ldy, w, bias, in, out, batch, act, keep, nkeep, true, nullptr);
+}
+
+int ffh_fused_gather_linear_fwd(ffh_ctx* c, const ffh_emb_table* tables, int ntables, int bag, int aggr, const float* x, int64_t ldx, float* y, int64_t ldy,
+                               const float* w, const float* bias, int in, int out, int64_t batch, int act, const ffh_fold_seg* keep, int nkeep, ffh_stream s) {
+  const int r = fold_fwd_gather(c, tables, ntables, bag, aggr, x, ldx, y, ldy, w, bias, in, out, batch, act, keep, nkeep, false, s);
+  return r == 1 ? FFH_OK : r;
 }
 
 // G_t = the segmented sum of dy over the hits of every row, in the fused table update's canonical order.  Wide aligned rows: that update's sort run to

@@ -2,6 +2,7 @@
 // helpers and the entry point of the bf16-pipe GEMMs (linear_bf16.hip), which linear.hip calls for the two bf16 math modes.
 #pragma once
 #include "ffh_common.h"
+#include "../../include/ffh_fused_gather.h"
 
 #include <hip/hip_runtime.h>
 
@@ -111,6 +112,19 @@ int launch_gemm_sk(ffh_ctx* c, const GemmArgs& g, int form, ffh_stream s, const 
 // read in the epilogue (include/ff_hip_fold.h); g describes the whole layer.  dry: decide only (1: would launch)
 int launch_gemm_sk_fold(ffh_ctx* c, const GemmArgs& g, const unsigned long long keep[2], int nk_kept, const float* addend, int64_t ldadd, bool dry,
                         ffh_stream s, const char* name);
+// ... whether that form serves the layer, and with which grid and operand extents (what the launch above and the one below share)
+struct SkFoldPlan { int64_t lda, ldb, a_bytes, b_bytes; int G; };
+bool gemm_sk_fold_plan(const ffh_ctx* c, const GemmArgs& g, int nk_kept, SkFoldPlan& p);
+// ... and the same form with the addend gathered in the epilogue from rows of the folded tables' products (include/ffh_fused_gather.h,
+// ffh_fused_gather_linear_fwd; linear_sk_gather.hip): term j = t * L + l of row m is p[t][idx[t][m * L + l] * ldp + column]
+struct FoldGatherList {
+  const int64_t* idx[FFH_FUSED_GATHER_MAX_TABLES];
+  const float*   p[FFH_FUSED_GATHER_MAX_TABLES];
+  int64_t        ldp;
+  int            ntables, L;
+};
+int launch_gemm_sk_fold_gather(ffh_ctx* c, const GemmArgs& g, const unsigned long long keep[2], int nk_kept, const FoldGatherList& gl, bool dry, ffh_stream s,
+                               const char* name);
 // ... the weight-gradient form over the kept 128-column tiles of dW only (`tiles`: nkept ascending tile indices; include/ff_hip_fold.h); g describes
 // the whole layer's weight gradient.  dry: decide only (1: would launch)
 int launch_gemm_sk_kept(ffh_ctx* c, const GemmArgs& g, const int* tiles, int nkept, bool dry, ffh_stream s, const char* name);

@@ -20,6 +20,7 @@
 #include "../../include/ff_hip_pad_mean.h"
 #include "../../include/ff_hip_q8.h"
 #include "../../include/ffh_dot_wide.h"
+#include "../../include/ffh_fused_gather.h"
 
 // The optional extensions of the kernel C-ABI, one line each, in the order load_kernel_api() loads them:
 //   X(KernelApi field, struct, the header's list, version symbol, the header's version, label of the version message, header under include/
@@ -60,7 +61,10 @@
   X(q8, KernelApiQ8, FFH_Q8_API_LIST, ffh_q8_abi_version, FFH_Q8_ABI_VERSION, "q8", "ff_hip_q8.h")                                                \
   /* the pairwise-dot interaction for 33 .. 128 feature vectors (absent: compile() refuses a dot_interaction of more than 32; its header is    \
      ffh_dot_wide.h, not ff_hip_dot_wide.h: see the header) */                                                                                  \
-  X(dot_wide, KernelApiDotWide, FFH_DOT_WIDE_API_LIST, ffh_dot_wide_abi_version, FFH_DOT_WIDE_ABI_VERSION, "dot-wide", "ffh_dot_wide.h")
+  X(dot_wide, KernelApiDotWide, FFH_DOT_WIDE_API_LIST, ffh_dot_wide_abi_version, FFH_DOT_WIDE_ABI_VERSION, "dot-wide", "ffh_dot_wide.h")                          \
+  /* the fold's forward gather-add inside the first top GEMM's epilogue (absent: the gather-add stays a pass of its own; its header is         \
+     ffh_fused_gather.h: see the header) */                                                                                                      \
+  X(fused_gather, KernelApiFusedGather, FFH_FUSED_GATHER_API_LIST, ffh_fused_gather_abi_version, FFH_FUSED_GATHER_ABI_VERSION, "fused-gather", "ffh_fused_gather.h")
 
 #define FFH_DECL(name) decltype(&::name) name;
 

@@ -151,6 +151,7 @@ class FFConfig {
   bool embedding_padding;      // variable-length bags: the id -1 in a sparse input is "no lookup" (include/ff_hip_pad.h; --embedding-padding).  The
                                // gather and the fused update then run on the pad forms of the ragged entries, whether or not the bag sizes differ
   bool fold_small_tables;      // small embedding tables folded out of the first top layer's forward GEMM (include/ff_hip_fold.h; A/B: --no-fold-small-tables)
+  bool fold_fused_gather;      // the forward's gather-add inside the kept-column GEMM's epilogue, no pass of its own and no S (A/B: --no-fold-fused-gather)
   int64_t fold_max_rows;       // ... tables of at most this many rows (--fold-max-rows N)
   bool fold_dw;                // ... and out of its weight-gradient GEMM (A/B: --no-fold-dw)
   bool fold_dx;                // ... and out of its data-gradient GEMM, their update one dense product (A/B: --no-fold-dx; needs fold_dw)
@@ -795,6 +796,7 @@ class FFModel {
     std::vector<ffh_fold_seg> keep;        // the column runs of the layer's input the GEMM keeps
     float* P = nullptr;                    // [sum of R_t][out] products
     float* S = nullptr;                    // [local batch][out] gathered sum
+    bool fused_gather = false;             // the side-stream route forms that sum in the GEMM's epilogue (ffh_fused_gather_linear_fwd) and leaves S alone
     // ... and out of the same layer's weight-gradient GEMM ("the weight gradient"): the forward-folded tables whose column blocks
     // are whole 128-column tiles of dW.   G_t = segmented sum of dy over the table's rows  ->  GEMM over the kept column tiles  ->  dW[:, cols_t] += G_t^T E_t
     std::vector<Embedding*> dw_tables;     // empty: the layer's weight gradient is the GEMM of before
@@ -831,11 +833,13 @@ class FFModel {
   mutable bool fold_x_read_recorded = false;
   mutable int64_t n_fold_dw_on_compute = 0, n_fold_update_early = 0;   // steps issued that way (tests: flexflow_model_get_counter)
   ffh_event ev_fold_w = nullptr;           // recorded on `stream` at the top of forward(): the optimizer of the step before has written W
-  ffh_event ev_fold_done = nullptr;        // recorded on the side stream behind the gather-add
+  ffh_event ev_fold_done = nullptr;        // recorded on the side stream behind the gather-add (fold.fused_gather: behind the products)
+  mutable int64_t n_fold_fused_gather = 0;  // forward() calls that gathered in the GEMM's epilogue (tests: flexflow_model_get_counter)
   mutable bool fold_w_recorded = false, fold_on_side = false;
   void plan_fold();                        // allocate(): the route conditions and the buffers
   void plan_fold_dw(FoldRoute& r);         // ... of the weight-gradient half
   void plan_fold_dx(FoldRoute& r);         // ... of the data-gradient half
+  void fold_products(ffh_stream s, ffh_ctx* cx) const;
   void fold_products_and_sum(ffh_stream s, ffh_ctx* cx) const;
   void fold_linear_forward(const Linear* li) const;
   int z_reader_layer;           // the lowest-index Linear that reads a Concat output the tables are gathered into (-1: unknown): behind ITS

@@ -1205,6 +1205,13 @@ void FFModel::plan_fold() {
       }
       col += in.adim[0];
     }
+    // the gather-add in that GEMM's epilogue, where the library has the extension (include/ffh_fused_gather.h) and runs the layer on the persistent kernel ("The gather in
+    // the epilogue"); forward() takes it on the side-stream route only
+    r.fused_gather = config.fold_fused_gather && api->fused_gather &&
+                     api->fused_gather->ffh_fused_gather_linear_fwd_plan(ctx, r.gather.data(), (int)r.gather.size(), r.tables[0]->inputs[0].adim[0], FFH_AGGR_MODE_SUM,
+                                                                (const float*)x.impl->ptr, x.impl->ld, (const float*)li->outputs[0].impl->ptr, li->outputs[0].impl->ld,
+                                                                (const float*)li->weights[0].impl->ptr, li->use_bias ? (const float*)li->weights[1].impl->ptr : nullptr,
+                                                                li->in_padded, out, local_rows(li->outputs[0], this), (int)li->activation, r.keep.data(), (int)r.keep.size()) == 1;
     r.layer = li;
     plan_fold_dw(r);
     fold = r;

@@ -49,6 +49,7 @@ FFConfig::FFConfig() {
   fold_dx = true;
   fold_dw_behind_sum = false;
   fold_update_behind_products = false;
+  fold_fused_gather = true;
   trace_mode = -1;
   bucket_allreduce = -1;
   allreduce_bucket_floats = 1 << 20;
@@ -180,6 +181,7 @@ void FFConfig::parse_args(char** argv, int argc) {
     if (is("--no-fold-dx")) { fold_dx = false; continue; }
     if (is("--fold-dw-behind-sum")) { fold_dw_behind_sum = true; continue; }
     if (is("--fold-update-behind-products")) { fold_update_behind_products = true; continue; }
+    if (is("--no-fold-fused-gather")) { fold_fused_gather = false; continue; }
     if (is("--fold-max-rows")) { fold_max_rows = atoll(next()); continue; }
     if (is("--always-replay")) { trace_mode = 1; continue; }
     if (is("--adaptive-replay")) { trace_mode = 0; continue; }

@@ -125,8 +125,9 @@ void FFModel::issue_embedding_forward_on_side_stream() const {
       // behind the gather: this stream already stands behind the table update of the step before (it ran here), ev_fold_w adds the
       // optimizer.  The bottom MLP's forward is the window; what sticks out of it the first top layer waits for (ev_fold_done)
       check(api->ffh_stream_wait_event(ctx, side_stream, ev_fold_w), "fold: weights ready");
-      fold_products_and_sum(side_stream, ctx);
-      check(api->ffh_event_record(ctx, ev_fold_done, side_stream), "fold: sum ready");
+      if (fold.fused_gather) fold_products(side_stream, ctx);      // the sum is the GEMM's own: it waits for the products only
+      else fold_products_and_sum(side_stream, ctx);
+      check(api->ffh_event_record(ctx, ev_fold_done, side_stream), fold.fused_gather ? "fold: products ready" : "fold: sum ready");
       fold_on_side = true;
     }
     if (early_sort_possible(1)) {       // behind the join: nothing waits for it until this step's update
@@ -138,11 +139,15 @@ void FFModel::issue_embedding_forward_on_side_stream() const {
   emb_forward_joined = false;
 }
 
+void FFModel::fold_products(ffh_stream s, ffh_ctx* cx) const {
+  const Linear* li = fold.layer;
+  check(api->fold->ffh_fold_product(cx, fold.groups.data(), (int)fold.groups.size(), (const float*)li->weights[0].impl->ptr, li->in_padded, fold.tables[0]->out_channels,
+                                    li->out_channels, s), "fold_product");
+}
 void FFModel::fold_products_and_sum(ffh_stream s, ffh_ctx* cx) const {
   const Linear* li = fold.layer;
   const Embedding* e0 = fold.tables[0];
-  check(api->fold->ffh_fold_product(cx, fold.groups.data(), (int)fold.groups.size(), (const float*)li->weights[0].impl->ptr, li->in_padded, e0->out_channels,
-                                    li->out_channels, s), "fold_product");
+  fold_products(s, cx);
   check(api->fold->ffh_fold_gather_add(cx, fold.gather.data(), (int)fold.gather.size(), e0->inputs[0].adim[0], li->out_channels, local_batch, FFH_AGGR_MODE_SUM,
                                        fold.S, li->out_channels, s), "fold_gather_add");
 }
@@ -217,6 +222,14 @@ void FFModel::fold_linear_forward(const Linear* li) const {
   else fold_products_and_sum(stream, ctx);
   const Tensor& x = li->inputs[0];
   const Tensor& y = li->outputs[0];
+  if (fold_on_side && fold.fused_gather) {
+    check(api->fused_gather->ffh_fused_gather_linear_fwd(ctx, fold.gather.data(), (int)fold.gather.size(), fold.tables[0]->inputs[0].adim[0], FFH_AGGR_MODE_SUM, (const float*)x.impl->ptr,
+                                                x.impl->ld, (float*)y.impl->ptr, y.impl->ld, (const float*)li->weights[0].impl->ptr,
+                                                li->use_bias ? (const float*)li->weights[1].impl->ptr : nullptr, li->in_padded, li->out_channels, local_rows(y, this),
+                                                (int)li->activation, fold.keep.data(), (int)fold.keep.size(), stream), li->name);
+    n_fold_fused_gather++;
+    return;
+  }
   check(api->fold->ffh_fold_linear_fwd(ctx, (const float*)x.impl->ptr, x.impl->ld, (float*)y.impl->ptr, y.impl->ld, (const float*)li->weights[0].impl->ptr,
                                        li->use_bias ? (const float*)li->weights[1].impl->ptr : nullptr, li->in_padded, li->out_channels, local_rows(y, this),
                                        (int)li->activation, fold.keep.data(), (int)fold.keep.size(), fold.S, li->out_channels, stream), li->name);

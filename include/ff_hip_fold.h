@@ -1,6 +1,6 @@
 /* ff_hip_fold.h -- optional extension of the kernel C-ABI (include/ff_hip.h): small embedding tables folded out of the forward
  * GEMM, (ABI 2, further down) out of the weight-gradient GEMM, and (ABI 3, at the end) out of the data-gradient GEMM, of the Linear
- * layer that reads their rows through a Concat.
+ * layer that reads their rows through a Concat.  The forward's gather-add inside the GEMM's epilogue is an extension of its own: ffh_fused_gather.h.
  *
  * A library may export this list or not; include/ff_hip.h and its symbol list are unchanged by it.  libffhip.so exports it,
  * the CPU oracle does not.  Callers load it separately (host/backend: KernelApi::fold, null when absent).
