@@ -1064,6 +1064,70 @@ class DotWideApi(ExtensionApi):
 dot_wide_api = DotWideApi
 
 
+# ---- the bag-weights extension (include/ffh_bag_weights.h): per-sample weights on embedding bags, weighted forms of the pad entries ----------
+# Like dot_wide: a header outside ff_hip_*.h and no BAG_WEIGHTS_HEADER_PATH alias (EXTENSIONS["bag_weights"].header_path is the path).
+class BagsUpdateWeighted(C.Structure):
+    """struct ffh_bags_update_weighted"""
+    _fields_ = [("u", BagsUpdate), ("weights", C.POINTER(P))]
+
+
+_SIGS_BAG_WEIGHTS = {
+    "ffh_bag_weights_abi_version": (I, []),
+    "ffh_embedding_fwd_multi_bags_weighted": (I, [P, C.POINTER(EmbTable), C.POINTER(P), C.POINTER(I), I, I, L, I, P]),
+    "ffh_embedding_fwd_multi_bags_weighted_bf16": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(P), C.POINTER(I), I, I, L, I, P]),
+    "ffh_embedding_bwd_fused_multi_bags_weighted": (I, [P, C.POINTER(BagsUpdateWeighted), P]),
+    "ffh_embedding_bwd_apply_multi_bags_weighted": (I, [P, C.POINTER(BagsUpdateWeighted), P]),
+}
+BAG_WEIGHTS_EXT = _extension("bag_weights", _SIGS_BAG_WEIGHTS, "bag-weights", header_name="ffh_bag_weights.h")
+
+
+class BagWeightsApi(ExtensionApi):
+    """The gathers take the arguments of PadApi.fwd_rc and a list of weight buffers; the update entries a descriptor that wraps the ragged
+    update's (BagsUpdateApi.descriptor) and adds that list.  The sort of the pair is PadApi.sort."""
+    ext = BAG_WEIGHTS_EXT
+
+    @staticmethod
+    def weights(bufs):
+        """`bufs`: one [batch][L] float32 device buffer per table (None: a null pointer), or None for a null array."""
+        return None if bufs is None else (P * max(len(bufs), 1))(*[ptr(b) for b in bufs])
+
+    def fwd_rc(self, tables, weights, in_dims, ntables: int, out_dim: int, batch: int, aggr: int, bf16: bool = False, stream=None) -> int:
+        """ffh_embedding_fwd_multi_bags_weighted[_bf16], returning its status code; `in_dims` from BagsApi.in_dims (or None: a null pointer)."""
+        fn = self.lib.ffh_embedding_fwd_multi_bags_weighted_bf16 if bf16 else self.lib.ffh_embedding_fwd_multi_bags_weighted
+        return fn(self.ctx, tables, self.weights(weights), in_dims, int(ntables), int(out_dim), int(batch), int(aggr), ptr(stream))
+
+    def fwd(self, *args, **kw):
+        self.base.check(self.fwd_rc(*args, **kw), "ffh_embedding_fwd_multi_bags_weighted")
+
+    def descriptor(self, u: BagsUpdate, weights) -> BagsUpdateWeighted:
+        """A struct ffh_bags_update_weighted around `u`; it keeps `u`'s arrays and the pointer array alive."""
+        d = BagsUpdateWeighted()
+        d.u = u
+        arr = self.weights(weights)
+        if arr is not None:
+            d.weights = C.cast(arr, C.POINTER(P))
+        d._keep = [u, getattr(u, "_keep", None), arr, weights]
+        return d
+
+    def _u(self, name: str, d: BagsUpdateWeighted | None, stream) -> int:
+        return getattr(self.lib, name)(self.ctx, C.byref(d) if d is not None else None, ptr(stream))
+
+    def fused_rc(self, d: BagsUpdateWeighted | None, stream=None) -> int:
+        return self._u("ffh_embedding_bwd_fused_multi_bags_weighted", d, stream)
+
+    def apply_rc(self, d: BagsUpdateWeighted | None, stream=None) -> int:
+        return self._u("ffh_embedding_bwd_apply_multi_bags_weighted", d, stream)
+
+    def fused(self, d: BagsUpdateWeighted, stream=None):
+        self.base.check(self.fused_rc(d, stream), "ffh_embedding_bwd_fused_multi_bags_weighted")
+
+    def apply(self, d: BagsUpdateWeighted, stream=None):
+        self.base.check(self.apply_rc(d, stream), "ffh_embedding_bwd_apply_multi_bags_weighted")
+
+
+bag_weights_api = BagWeightsApi
+
+
 _hip_singleton: FFHLib | None = None
 
 

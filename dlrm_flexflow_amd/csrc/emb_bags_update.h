@@ -8,6 +8,9 @@
 // argument structs and the geometry.
 #pragma once
 #include "emb_reduce.h"
+#include "../../include/ff_hip_bags_update.h"
+
+#include <cstring>
 
 namespace ffh_emb {
 
@@ -121,6 +124,27 @@ constexpr int kCountSlots = 1024;       // id slots a workgroup takes at most, i
 // the bags of a table with bag size L that one workgroup counts, and the table's workgroups: host and kernel compute the flat map with these
 __host__ __device__ inline int count_bags_per_wg(int L) { return L >= kCountSlots ? 1 : kCountSlots / L; }
 __host__ __device__ inline int64_t count_wgs(int64_t batch, int L) { const int b = count_bags_per_wg(L); return (batch + b - 1) / b; }
+
+// The weighted forms (include/ffh_bag_weights.h; kernels in embedding_bag_weights.hip): 64 more pointers do not fit beside 64 descriptors in
+// 4 KB, so a table's descriptor carries its weights itself -- t[i] holds a BagWTable, the row count (<= 2^32 - 2 in every pad form) and the
+// gradient rows' leading dimension in 32 bits each -- and the kernel arguments keep their size and every other member its place.
+struct BagWTable {
+  const int64_t* idx; float* weight; float* io;
+  uint32_t num_entries, ld;
+  const float* w;                       // [batch][L] like idx
+};
+static_assert(sizeof(BagWTable) == sizeof(ffh_emb_table) && alignof(BagWTable) == alignof(ffh_emb_table), "a BagWTable travels in an ffh_emb_table's place");
+inline ffh_emb_table bag_w_pack(const ffh_emb_table& t, const float* w) {
+  const BagWTable p = {t.idx, t.weight, t.io, (uint32_t)t.num_entries, (uint32_t)t.ld, w};
+  ffh_emb_table o;
+  memcpy(&o, &p, sizeof o);
+  return o;
+}
+__device__ __forceinline__ const float* bag_w_unpack(const ffh_emb_table& packed, ffh_emb_table* t) {
+  const BagWTable& p = reinterpret_cast<const BagWTable&>(packed);
+  t->idx = p.idx; t->weight = p.weight; t->io = p.io; t->num_entries = p.num_entries; t->ld = p.ld;
+  return p.w;
+}
 
 constexpr size_t kBagsKernargBytes = sizeof(BagsRedArgs) > sizeof(BagsSmallArgs)
                                          ? (sizeof(BagsRedArgs) > sizeof(BagsSortArgs) ? sizeof(BagsRedArgs) : sizeof(BagsSortArgs))
@@ -246,6 +270,7 @@ __global__ __launch_bounds__(kSortThreads) void bags_radix_scatter_kernel(const 
 // apply, sorted route: emb_sgd_reduce_kernel's LSD form on the flat map.  Cross-workgroup traffic as there: a tile's partial rows and slot
 // records go out written through and completed before it counts itself in; the last tile of a 1024-block folds the block, the last folded
 // block of a table folds the table.  No workgroup waits for another.
+// (embedding_bag_weights.hip holds a copy of the pad form, emb_bagw_reduce_kernel: a change to the protocol here goes there too.)
 // ---------------------------------------------------------------------------
 template <int VEC, RowRule R, class WT, bool LRP, bool PAD = false, bool MEAN = false>
 __global__ __launch_bounds__(kRedThreads, (red_waves_per_simd<VEC, R, WT, false>())) void emb_bags_reduce_kernel(const BagsRedArgs a) {
@@ -327,6 +352,7 @@ __global__ __launch_bounds__(kRedThreads, (red_waves_per_simd<VEC, R, WT, false>
 // ---------------------------------------------------------------------------
 // apply, small route (every N_t <= kSmallMax): emb_sgd_small_kernel with the table's own N_t -- sort, reduce and folds of a table in its
 // one workgroup
+// (embedding_bag_weights.hip holds a copy of the pad form, emb_bagw_small_kernel: a change here goes there too.)
 // ---------------------------------------------------------------------------
 template <int VEC, RowRule R, class WT, bool LRP, bool PAD = false, bool MEAN = false>
 __global__ __launch_bounds__(kSmallThreads) void emb_bags_small_kernel(const BagsSmallArgs a) {
@@ -478,5 +504,10 @@ __attribute__((visibility("hidden"))) bool emb_pad_sort_first_pass(const BagsSor
 __attribute__((visibility("hidden"))) bool emb_padmean_update_launch_f32(const BagsUpdateLaunch& u);   // embedding_update_padmean_f32.hip
 __attribute__((visibility("hidden"))) bool emb_padmean_update_launch_bf16(const BagsUpdateLaunch& u);  // embedding_update_padmean_bf16.hip
 __attribute__((visibility("hidden"))) void emb_padmean_count(const BagsCountArgs& a, hipStream_t stream);      // embedding_update_padmean_f32.hip
+// the weighted forms (include/ffh_bag_weights.h): the apply kernels that multiply a gradient row by its lookup's weight as they load it
+__attribute__((visibility("hidden"))) bool emb_bagw_update_launch_f32(const BagsUpdateLaunch& u);      // embedding_bag_weights.hip
+__attribute__((visibility("hidden"))) bool emb_bagw_update_launch_bf16(const BagsUpdateLaunch& u);     // embedding_bag_weights.hip
+// ... and the ragged update in that form (embedding.hip): the fused call (do_sort) or the apply alone
+__attribute__((visibility("hidden"))) int emb_bwd_bags_weighted(ffh_ctx* c, const ffh_bags_update* u, const float* const* weights, ffh_stream s, bool do_sort);
 
 }  // namespace ffh_emb

@@ -73,6 +73,34 @@ static_assert(sizeof(RedArgs) <= 4096 && sizeof(SmallArgs) <= 4096, "kernel argu
 
 namespace {
 
+// n / d for the 32-bit n and a divisor 1 <= d <= 65535 that is constant over a launch: a multiply-high, an add and two shifts (the round-up
+// method: m = floor(2^32 (2^s - d) / d) + 1 with s = ceil(log2 d), n / d = (t + ((n - t) >> 1)) >> (s - 1) with t = mulhi(m, n); exact for every
+// 32-bit n).  The magic number comes from two 32-bit divisions, once per workgroup.
+struct BagDiv {
+  uint32_t m;
+  int sh;        // s - 1; -1: d == 1
+  __host__ __device__ explicit BagDiv(const uint32_t d) {
+    m = 0; sh = -1;
+    if (d > 1) {
+      int s = 0;
+      while ((1u << s) < d) s++;
+      const uint32_t r = (1u << s) - d;                    // < d < 2^16
+      const uint32_t q1 = (r << 16) / d, r1 = (r << 16) - q1 * d;
+      m = (q1 << 16) + (r1 << 16) / d + 1u;
+      sh = s - 1;
+    }
+  }
+  __host__ __device__ uint32_t quot(const uint32_t n) const {
+    if (sh < 0) return n;
+#ifdef __HIP_DEVICE_COMPILE__
+    const uint32_t t = __umulhi(m, n);
+#else
+    const uint32_t t = (uint32_t)(((uint64_t)m * n) >> 32);
+#endif
+    return (t + ((n - t) >> 1)) >> sh;
+  }
+};
+
 template <int VEC>
 __device__ __forceinline__ void load_grad(float (&dst)[VEC], const float* rowp, int c, float invdiv, bool avg) {
   if (VEC == 4) {
@@ -149,11 +177,17 @@ struct RedShared {
 // MEAN (include/ff_hip_pad_mean.h; PAD forms only): the divisor of entry i is the count of real lookups of its sample, cnt[s_pos[i]] (the
 // table's 16-bit counts, [batch]), read where the gradient row is loaded, in place of (float)L.  An entry that is summed is a real lookup, so
 // its count is at least 1.  With MEAN false the body is what it was.
-template <int VEC, bool AGENT, RowRule R, class WT, bool PAD = false, bool MEAN = false>
+// WGT (include/ffh_bag_weights.h; PAD forms only, SUM): entry i carries the weight wgt[flat position], the table's [batch][L] floats.  s_pos keeps
+// the FLAT position e.y instead of the sample (no LDS beside it: 2 KB more in RedShared cost the plain fp32 kernel a workgroup per CU), the sample
+// is taken from it where the gradient row is loaded -- the table's constant divisor as a multiply and a shift (BagDiv) -- and the weight is read
+// from global memory at the flat position beside that load (one address per lane-group), then multiplied in: one product per element, rounded
+// on its own, before any sum.  With WGT false the body is what it was.
+template <int VEC, bool AGENT, RowRule R, class WT, bool PAD = false, bool MEAN = false, bool WGT = false>
 __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const uint2* kp,
                                                  float* partial_t, uint2* meta_t, int64_t N, int nchunks, int tile, int tile_index,
                                                  int L, int D_, bool avg_, const OptP& op, float* st0, float* st1, const SrKey& sk, RedShared& sh, const int tid = threadIdx.x,
-                                                 const bool preloaded = false, const uint16_t* __restrict__ cnt = nullptr) {
+                                                 const bool preloaded = false, const uint16_t* __restrict__ cnt = nullptr,
+                                                 const float* __restrict__ wgt = nullptr) {
   uint32_t* s_key = sh.key;
   uint32_t* s_pos = sh.pos;
   uint16_t* s_start = sh.start;
@@ -168,7 +202,8 @@ __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const 
     for (int i = tid; i < n; i += kRedThreads) {
       const uint2 e = kp[tile0 + i];
       s_key[1 + i] = e.x;
-      s_pos[i] = a.L == 1 ? e.y : e.y / (uint32_t)a.L;      // the sample (gradient row) of the entry
+      if constexpr (WGT) s_pos[i] = e.y;                    // the flat position: the weight's index; the sample is taken from it by row_of
+      else s_pos[i] = a.L == 1 ? e.y : e.y / (uint32_t)a.L;      // the sample (gradient row) of the entry
     }
     if (tid == 0) {
       s_key[0] = (tile0 > 0 && tile0 < N) ? kp[tile0 - 1].x : 0xFFFFFFFFu;   // no valid key equals it when tile0 == 0 (checked below)
@@ -224,6 +259,18 @@ __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const 
     if constexpr (MEAN) return (float)cnt[s_pos[q]];
     else return Lf;
   };
+  const BagDiv bdiv(WGT ? a.L : 1);
+  auto grad_of = [&](float (&dst)[VEC], const int q, const int c) {      // vector c of the gradient row of sorted entry q of the tile
+    if constexpr (WGT) {
+      const uint32_t p = s_pos[q];
+      const float wv = wgt[p];
+      load_grad<VEC>(dst, tb.io + (int64_t)bdiv.quot(p) * tb.ld, c, Lf, false);
+#pragma unroll
+      for (int v = 0; v < VEC; v++) dst[v] = wv * dst[v];
+    } else {
+      load_grad<VEC>(dst, tb.io + (int64_t)s_pos[q] * tb.ld, c, div_of(q), avg);
+    }
+  };
 
   // (Several sub-runs per lane-group in flight at once were tried -- 2 and 4, with and without the registers capped for eight
   //  waves per SIMD -- and changed nothing: with every tile resident the kernel runs at the rate the memory system takes random
@@ -247,10 +294,10 @@ __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const 
       if constexpr (opt_rowwise(R)) {
         if (single) {      // the whole row at once; the sub-run's sum of vector c as the loop below forms it, in order
           apply_row_rowwise<VEC, WT>(op, wrow, st0 + key, D, nvec, lpr, c0, lane, [&](int c, float (&acc)[VEC]) {
-            load_grad<VEC>(acc, tb.io + (int64_t)s_pos[s] * tb.ld, c, div_of(s), avg);
+            grad_of(acc, s, c);
             for (int q = s + 1; q < e; q++) {
               float v0[VEC];
-              load_grad<VEC>(v0, tb.io + (int64_t)s_pos[q] * tb.ld, c, div_of(q), avg);
+              grad_of(v0, q, c);
 #pragma unroll
               for (int v = 0; v < VEC; v++) acc[v] = acc[v] + v0[v];
             }
@@ -260,21 +307,21 @@ __device__ __forceinline__ void reduce_tile_body(const ffh_emb_table& tb, const 
       }
       for (int c = c0; c < nvec; c += lpr) {
         float acc[VEC];
-        load_grad<VEC>(acc, tb.io + (int64_t)s_pos[s] * tb.ld, c, div_of(s), avg);
+        grad_of(acc, s, c);
         int q = s + 1;
         // four independent row loads in flight, summed in order
         for (; q + 4 <= e; q += 4) {
           float v0[VEC], v1[VEC], v2[VEC], v3[VEC];
-          load_grad<VEC>(v0, tb.io + (int64_t)s_pos[q] * tb.ld, c, div_of(q), avg);
-          load_grad<VEC>(v1, tb.io + (int64_t)s_pos[q + 1] * tb.ld, c, div_of(q + 1), avg);
-          load_grad<VEC>(v2, tb.io + (int64_t)s_pos[q + 2] * tb.ld, c, div_of(q + 2), avg);
-          load_grad<VEC>(v3, tb.io + (int64_t)s_pos[q + 3] * tb.ld, c, div_of(q + 3), avg);
+          grad_of(v0, q, c);
+          grad_of(v1, q + 1, c);
+          grad_of(v2, q + 2, c);
+          grad_of(v3, q + 3, c);
 #pragma unroll
           for (int v = 0; v < VEC; v++) acc[v] = (((acc[v] + v0[v]) + v1[v]) + v2[v]) + v3[v];
         }
         for (; q < e; q++) {
           float v0[VEC];
-          load_grad<VEC>(v0, tb.io + (int64_t)s_pos[q] * tb.ld, c, div_of(q), avg);
+          grad_of(v0, q, c);
 #pragma unroll
           for (int v = 0; v < VEC; v++) acc[v] = acc[v] + v0[v];
         }

@@ -617,12 +617,13 @@ inline int bags_dims_check(const int* in_dims, int nt, int64_t batch) {
 }
 
 typedef bool (*BagsUpdateOfFn)(const BagsUpdateLaunch&);
-constexpr BagsUpdateOfFn kBagsUpdateOf[3][2] = {{emb_bags_update_launch_f32, emb_bags_update_launch_bf16},      // [BagsForm][bf16 rows]
+constexpr BagsUpdateOfFn kBagsUpdateOf[4][2] = {{emb_bags_update_launch_f32, emb_bags_update_launch_bf16},      // [BagsForm][bf16 rows]
                                                 {emb_pad_update_launch_f32, emb_pad_update_launch_bf16},
-                                                {emb_padmean_update_launch_f32, emb_padmean_update_launch_bf16}};
+                                                {emb_padmean_update_launch_f32, emb_padmean_update_launch_bf16},
+                                                {emb_bagw_update_launch_f32, emb_bagw_update_launch_bf16}};
 // the form of a ragged update call: plain, the pad form (include/ff_hip_pad.h) or the pad form with a mean over the lookups that are there
-// (include/ff_hip_pad_mean.h)
-enum BagsForm { kBagsPlain = 0, kBagsPad = 1, kBagsPadMean = 2 };
+// (include/ff_hip_pad_mean.h), or the pad form with a weight per lookup (include/ffh_bag_weights.h)
+enum BagsForm { kBagsPlain = 0, kBagsPad = 1, kBagsPadMean = 2, kBagsPadW = 3 };
 
 // The mean form's counts: one uint16 per (table, bag), [table][batch], in a region behind the ragged layout -- the sort phase, which sizes and
 // writes only that layout, never touches it.
@@ -645,15 +646,29 @@ inline int validate_sort_tables(ffh_ctx* c, const ffh_emb_table* t, int nt, int 
 // per table, and the apply kernels drop that key's segment; the layout, the grids and the workspace are those of the call without pads.
 // kBagsPadMean (include/ff_hip_pad_mean.h; apply and fused only -- the sort is the pad form's): the apply phase first counts every bag's real
 // lookups into the region behind the layout (one small launch), and its kernels divide each gradient row by its bag's count.
+// kBagsPadW (include/ffh_bag_weights.h; apply and fused only, SUM only): `wts[i]` is table i's [batch][L_i] floats; the apply kernels multiply each
+// gradient row by its lookup's weight as they load it.  The weight pointer travels inside the table's descriptor (BagWTable): same launches, same
+// grids, same workspace as the pad form.
 int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, int nt, int D, int64_t batch, int aggr, float lr, ffh_stream s,
                  const bool do_sort, const bool do_apply,
-                 const ffh_sparse_opt* opt, const ffh_emb_state* states, const Bf16Cfg* b16, const ffh_lr_state* lr_block, const BagsForm form) {
-  const bool pad = form != kBagsPlain, mean = form == kBagsPadMean;
+                 const ffh_sparse_opt* opt, const ffh_emb_state* states, const Bf16Cfg* b16, const ffh_lr_state* lr_block, const BagsForm form,
+                 const float* const* wts = nullptr) {
+  const bool pad = form != kBagsPlain, mean = form == kBagsPadMean, wgt = form == kBagsPadW;
   int rc = bags_dims_check(in_dims, nt, batch);
   if (rc == FFH_ERR_BAD_ARG) return ffh_fail(c, rc, "embedding_bwd_fused_multi_bags: ntables out of range, null in_dims or in_dims[i] < 1");
   if (rc) return ffh_fail(c, rc, "embedding_bwd_fused_multi_bags: in_dims[i] > FFH_BAGS_MAX_IN_DIM (65535) or batch*in_dims[i] >= 2^31");
   rc = do_apply ? validate_tables(c, tables, nt, 1, D, batch, aggr) : validate_sort_tables(c, tables, nt, D, batch);
   if (rc) return rc;
+  if (wgt) {
+    if (aggr == FFH_AGGR_MODE_AVG)
+      return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags_weighted: aggr must be FFH_AGGR_MODE_SUM (weights with mean pooling are not supported; the "
+                                          "unweighted mean is ffh_embedding_bwd_fused_multi_bags_pad_mean / ffh_embedding_bwd_apply_multi_bags_pad_mean)");
+    if (nt > 0 && !wts) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags_weighted: null weights");
+    for (int i = 0; i < nt; i++) {
+      if ((batch > 0 && !wts[i]) || ((uintptr_t)wts[i] & 3)) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags_weighted: weights[i] is null or not 4-byte aligned");
+      if (tables[i].ld >= (1LL << 32)) return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags_weighted: ld >= 2^32");
+    }
+  }
   if (pad && !mean && aggr == FFH_AGGR_MODE_AVG)      // (a mean over the lookups that are there needs each bag's count in the apply phase: include/ff_hip_pad_mean.h)
     return ffh_fail(c, FFH_ERR_UNSUPPORTED, "embedding_bwd_fused_multi_bags_pad: FFH_AGGR_MODE_AVG is not supported with pad ids");
   if (mean && aggr != FFH_AGGR_MODE_AVG)
@@ -708,12 +723,12 @@ int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, in
   };
 
   if (lay.maxN <= kSmallMax) {
-    snprintf(c->emb_route, sizeof c->emb_route, mean ? "bags:small:pad:mean" : pad ? "bags:small:pad" : "bags:small");
+    snprintf(c->emb_route, sizeof c->emb_route, wgt ? "bags:small:pad:w" : mean ? "bags:small:pad:mean" : pad ? "bags:small:pad" : "bags:small");
     if (!do_apply) return FFH_OK;      // (the sort lives inside the one launch: the sort call only leaves the note)
     if (mean) count_bags();
     BagsSmallArgs sm;
     memset(&sm, 0, sizeof sm);
-    for (int i = 0; i < nt; i++) sm.t[i] = tables[i];
+    for (int i = 0; i < nt; i++) sm.t[i] = wgt ? bag_w_pack(tables[i], wts[i]) : tables[i];
     fill_passes(tables, nt, rp.rb, sm.npass, nullptr, more_keys);
     sm.kp = (uint2*)(ws + lay.kp_a);
     set_ws_slots(sm, ws, lay);
@@ -725,12 +740,12 @@ int emb_bwd_bags(ffh_ctx* c, const ffh_emb_table* tables, const int* in_dims, in
     return FFH_OK;
   }
 
-  snprintf(c->emb_route, sizeof c->emb_route, mean ? "bags:lsd:passes=%d:pad:mean" : pad ? "bags:lsd:passes=%d:pad" : "bags:lsd:passes=%d", rp.passes);
+  snprintf(c->emb_route, sizeof c->emb_route, wgt ? "bags:lsd:passes=%d:pad:w" : mean ? "bags:lsd:passes=%d:pad:mean" : pad ? "bags:lsd:passes=%d:pad" : "bags:lsd:passes=%d", rp.passes);
   BagsSortArgs sa;
   memset(&sa, 0, sizeof sa);
   BagsRedArgs ra;
   memset(&ra, 0, sizeof ra);
-  for (int i = 0; i < nt; i++) { sa.idx[i] = tables[i].idx; ra.t[i] = tables[i]; sa.padkey[i] = (uint32_t)tables[i].num_entries; }
+  for (int i = 0; i < nt; i++) { sa.idx[i] = tables[i].idx; ra.t[i] = wgt ? bag_w_pack(tables[i], wts[i]) : tables[i]; sa.padkey[i] = (uint32_t)tables[i].num_entries; }
   fill_passes(tables, nt, rp.rb, sa.npass, ra.parity, more_keys);
   sa.hist = (uint32_t*)(ws + lay.hist);
   sa.bits = rp.rb; sa.g = lay.g;
@@ -772,7 +787,8 @@ size_t ffh_embedding_bwd_bags_workspace_bytes(const int* in_dims, int nt, int D,
 
 // the descriptor of the three ragged entries: the fused call (do_sort && do_apply) and the pair of include/ff_hip_bags_sort.h.  The sort phase
 // takes the fields it reads (tables, in_dims, ntables, out_dim, batch) and nothing else.
-static int emb_bwd_bags_desc(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s, const bool do_sort, const bool do_apply, const BagsForm pad = kBagsPlain) {
+static int emb_bwd_bags_desc(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s, const bool do_sort, const bool do_apply, const BagsForm pad = kBagsPlain,
+                             const float* const* wts = nullptr) {
   if (!u) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: null descriptor");
   if ((u->tables != nullptr) == (u->tables_bf16 != nullptr)) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: exactly one of tables / tables_bf16");
   if (do_apply && u->lr_block && !u->opt) return ffh_fail(c, FFH_ERR_BAD_ARG, "embedding_bwd_fused_multi_bags: lr_block needs opt");
@@ -781,14 +797,14 @@ static int emb_bwd_bags_desc(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s,
   const ffh_sparse_opt* opt = do_apply ? u->opt : nullptr;
   const ffh_emb_state* states = do_apply ? u->states : nullptr;
   const ffh_lr_state* lr_block = do_apply ? u->lr_block : nullptr;
-  if (u->tables) return emb_bwd_bags(c, u->tables, u->in_dims, u->ntables, u->out_dim, u->batch, aggr, lr, s, do_sort, do_apply, opt, states, nullptr, lr_block, pad);
+  if (u->tables) return emb_bwd_bags(c, u->tables, u->in_dims, u->ntables, u->out_dim, u->batch, aggr, lr, s, do_sort, do_apply, opt, states, nullptr, lr_block, pad, wts);
   ffh_emb_table t[FFH_MAX_TABLES];
   Bf16Cfg cfg;
   memset(&cfg, 0, sizeof cfg);
   cfg.r = do_apply ? u->rounding : nullptr;
   const int rc = bf16_tables(c, u->tables_bf16, u->ntables, t, &cfg.keys);
   if (rc) return rc;
-  return emb_bwd_bags(c, t, u->in_dims, u->ntables, u->out_dim, u->batch, aggr, lr, s, do_sort, do_apply, opt, states, &cfg, lr_block, pad);
+  return emb_bwd_bags(c, t, u->in_dims, u->ntables, u->out_dim, u->batch, aggr, lr, s, do_sort, do_apply, opt, states, &cfg, lr_block, pad, wts);
 }
 
 int ffh_embedding_bwd_fused_multi_bags(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, true, true); }
@@ -812,3 +828,10 @@ int ffh_embedding_bwd_fused_multi_bags_pad_mean(ffh_ctx* c, const ffh_bags_updat
 int ffh_embedding_bwd_apply_multi_bags_pad_mean(ffh_ctx* c, const ffh_bags_update* u, ffh_stream s) { return emb_bwd_bags_desc(c, u, s, false, true, kBagsPadMean); }
 
 }  // extern "C"
+
+// include/ffh_bag_weights.h: the fused call (do_sort) and the apply with a weight per lookup, for the entries in embedding_bag_weights.hip
+namespace ffh_emb {
+int emb_bwd_bags_weighted(ffh_ctx* c, const ffh_bags_update* u, const float* const* weights, ffh_stream s, const bool do_sort) {
+  return emb_bwd_bags_desc(c, u, s, do_sort, true, kBagsPadW, weights);
+}
+}  // namespace ffh_emb

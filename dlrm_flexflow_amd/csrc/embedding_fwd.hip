@@ -30,7 +30,7 @@ using namespace ffh_emb;
 
 // VEC = table elements per lane per access: 4 (fp32 tables: 16-B accesses; bf16 tables, WT = uint16_t (ff_hip_bf16.h): 8-B accesses)
 // or 1 (any D / alignment).  A bf16 element widens exactly and the sums run in the same order: the same bits as the fp32 gather on
-// the widened table.
+// the widened table.  (RowVec, row_elem and RowLanes are copied in embedding_bag_weights.hip, RowLanes in embedding_q8.hip too: keep them alike.)
 template <int VEC, class WT> struct RowVec { typedef typename std::conditional<VEC == 4, float4, float>::type type; };
 template <> struct RowVec<4, uint16_t> { typedef uint2 type; };
 template <> struct RowVec<1, uint16_t> { typedef unsigned short type; };

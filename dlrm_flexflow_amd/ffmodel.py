@@ -99,6 +99,7 @@ def lib() -> C.CDLL:
         "flexflow_tensor_create": (H, [H, I, IP, I, B]),
         "flexflow_model_add_dense": (H, [H, H, I, I, B, H, H, C.c_char_p]),
         "flexflow_model_add_embedding": (H, [H, H, I, I, I, H, C.c_char_p]),
+        "flexflow_model_add_weighted_embedding": (H, [H, H, H, I, I, I, H, C.c_char_p]),
         "flexflow_model_add_concat": (H, [H, I, C.POINTER(H), I, C.c_char_p]),
         "flexflow_model_add_batch_matmul": (H, [H, H, H, I, I]),
         "flexflow_model_add_flat": (H, [H, H, C.c_char_p]),
@@ -238,6 +239,18 @@ def padded_bag_reference(W, idx, mean: bool = False) -> np.ndarray:
     if mean:
         inv = np.float32(1) / np.maximum(padded_bag_counts(idx), 1).astype(np.float32)
         out = out * inv[:, None]
+    return out
+
+
+def weighted_bag_reference(W, idx, w) -> np.ndarray:
+    """The weighted gather of include/ffh_bag_weights.h in numpy: acc = +0, then for ascending slot j with idx[b][j] >= 0
+    acc = acc + w[b][j] * W[idx[b][j]] -- a float32 multiply, then a float32 add.  `W` is [rows][D] float32 (a bf16 table: widened), `idx`
+    [batch][L] integers, `w` [batch][L] float32; a pad's weight is never looked at, a bag of only pads gives a row of +0."""
+    W, idx, w = np.asarray(W, np.float32), np.asarray(idx, np.int64), np.asarray(w, np.float32)
+    out = np.zeros((idx.shape[0], W.shape[1]), np.float32)
+    for j in range(idx.shape[1]):
+        live = idx[:, j] >= 0
+        out[live] = out[live] + w[live, j][:, None] * W[idx[live, j]]
     return out
 
 
@@ -632,7 +645,13 @@ class FFModel:
                                                      kernel_initializer or _NULL, bias_initializer or _NULL,
                                                      name.encode() if name else None), self)
 
-    def embedding(self, input: Tensor, num_entries, out_dim, aggr=capi.AGGR_MODE_SUM, kernel_initializer=None, name=None) -> Tensor:
+    def embedding(self, input: Tensor, num_entries, out_dim, aggr=capi.AGGR_MODE_SUM, kernel_initializer=None, name=None,
+                  per_sample_weights: Tensor | None = None) -> Tensor:
+        """per_sample_weights: an input tensor [batch][bag] of DT_FLOAT beside `input` (EmbeddingBag's per_sample_weights, SUM pooling only;
+        include/ffh_bag_weights.h): the bag is the weighted sum of its rows.  The weights are data: no gradient is formed for them."""
+        if per_sample_weights is not None:
+            return Tensor(lib().flexflow_model_add_weighted_embedding(self.h, input.h, per_sample_weights.h, num_entries, out_dim, aggr,
+                                                                      kernel_initializer or _NULL, name.encode() if name else None), self)
         return Tensor(lib().flexflow_model_add_embedding(self.h, input.h, num_entries, out_dim, aggr,
                                                          kernel_initializer or _NULL, name.encode() if name else None), self)
 

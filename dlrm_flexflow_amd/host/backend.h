@@ -21,6 +21,7 @@
 #include "../../include/ff_hip_q8.h"
 #include "../../include/ffh_dot_wide.h"
 #include "../../include/ffh_fused_gather.h"
+#include "../../include/ffh_bag_weights.h"
 
 // The optional extensions of the kernel C-ABI, one line each, in the order load_kernel_api() loads them:
 //   X(KernelApi field, struct, the header's list, version symbol, the header's version, label of the version message, header under include/
@@ -64,7 +65,10 @@
   X(dot_wide, KernelApiDotWide, FFH_DOT_WIDE_API_LIST, ffh_dot_wide_abi_version, FFH_DOT_WIDE_ABI_VERSION, "dot-wide", "ffh_dot_wide.h")                          \
   /* the fold's forward gather-add inside the first top GEMM's epilogue (absent: the gather-add stays a pass of its own; its header is         \
      ffh_fused_gather.h: see the header) */                                                                                                      \
-  X(fused_gather, KernelApiFusedGather, FFH_FUSED_GATHER_API_LIST, ffh_fused_gather_abi_version, FFH_FUSED_GATHER_ABI_VERSION, "fused-gather", "ffh_fused_gather.h")
+  X(fused_gather, KernelApiFusedGather, FFH_FUSED_GATHER_API_LIST, ffh_fused_gather_abi_version, FFH_FUSED_GATHER_ABI_VERSION, "fused-gather", "ffh_fused_gather.h") \
+  /* per-sample weights on embedding bags: the weighted forms of the pad gather and of the pad update (its header is ffh_bag_weights.h: see     \
+     the header) */                                                                                                                              \
+  X(bag_weights, KernelApiBagWeights, FFH_BAG_WEIGHTS_API_LIST, ffh_bag_weights_abi_version, FFH_BAG_WEIGHTS_ABI_VERSION, "bag-weights", "ffh_bag_weights.h")
 
 #define FFH_DECL(name) decltype(&::name) name;
 

@@ -77,6 +77,8 @@ void parse_input_args(char** argv, int argc, DLRMConfig& config) {
         config.pooling_given = true;
         continue;
       }
+      // (a switch: --embedding-per-sample-weights or --embedding-per-sample-weights=1)
+      if (is("--embedding-per-sample-weights")) { config.per_sample_weights = eq ? atoi(eq + 1) != 0 : true; continue; }
       if (is("--dcn-num-layers")) { config.dcn_num_layers = atoi(next()); continue; }
       if (is("--dcn-low-rank-dim")) { config.dcn_low_rank_dim = atoi(next()); continue; }
     }
@@ -112,11 +114,11 @@ Tensor create_mlp(FFModel* model, const Tensor& input, std::vector<int> ln, int 
 }
 
 // [ref: examples/cpp/DLRM/dlrm.cc:41-47]: U(-sqrt(1/R), sqrt(1/R)), AGGR_MODE_SUM (`aggr`: --embedding-pooling mean gives AGGR_MODE_AVG)
-Tensor create_emb(FFModel* model, const Tensor& input, int input_dim, int output_dim, int idx, AggrMode aggr) {
+Tensor create_emb(FFModel* model, const Tensor& input, int input_dim, int output_dim, int idx, AggrMode aggr, const Tensor* per_sample_weights) {
   (void)idx;
   float range = std::sqrt(1.0f / input_dim);
   Initializer* embed_init = model->own(new UniformInitializer(model->next_seed(), -range, range));
-  return model->embedding(input, input_dim, output_dim, aggr, NULL /*weight_sharing*/, embed_init);
+  return model->embedding(input, input_dim, output_dim, aggr, NULL /*weight_sharing*/, embed_init, NULL /*name*/, per_sample_weights);
 }
 
 // [ref: examples/cpp/DLRM/dlrm.cc:49-65]: the reference implements "cat" and asserts on "dot" (a TODO).
@@ -157,13 +159,15 @@ Tensor interact_features(FFModel* model, const Tensor& x, const std::vector<Tens
 static void check_eval_batches(int eval_batches, int nb);
 
 // =============================================================================================
-DataLoader::DataLoader(FFModel& ff, const DLRMConfig& dlrm, const std::vector<Tensor>& sparse_inputs, Tensor dense_input, Tensor label)
+DataLoader::DataLoader(FFModel& ff, const DLRMConfig& dlrm, const std::vector<Tensor>& sparse_inputs, Tensor dense_input, Tensor label,
+                       const std::vector<Tensor>& weight_inputs)
     : num_samples(0), next_index(0), epoch(0), batch_sparse_inputs(sparse_inputs), batch_dense_input(dense_input), batch_label(label),
-      full_dense(nullptr), full_label(nullptr), model(&ff) {
+      batch_weight_inputs(weight_inputs), full_dense(nullptr), full_label(nullptr), model(&ff) {
   num_train = 0;
   for (size_t t = 0; t < sparse_inputs.size(); t++) bags.push_back(dlrm.bag_of(t));
   dense_dim = dense_input.adim[0];
   full_sparse.assign(sparse_inputs.size(), nullptr);
+  full_weights.assign(sparse_inputs.size(), nullptr);
   if (dlrm.dataset_path != "") load_hdf5(ff, dlrm);
   else generate_random(ff, dlrm);
   ff.check(ff.api->ffh_stream_sync(ff.ctx, ff.stream), "dataset sync");
@@ -172,6 +176,8 @@ DataLoader::DataLoader(FFModel& ff, const DLRMConfig& dlrm, const std::vector<Te
   if (ff.config.data_randomize) {
     for (size_t t = 0; t < batch_sparse_inputs.size(); t++)
       segments.push_back({full_sparse[t], full_sparse[t] ? batch_sparse_inputs[t].impl->ptr : nullptr, 8 * bags[t], FFH_GATHER_GLOBAL_ROWS});
+    for (size_t t = 0; t < batch_weight_inputs.size(); t++)      // a table's weights travel with its ids
+      if (full_weights[t]) segments.push_back({full_weights[t], batch_weight_inputs[t].impl->ptr, 4 * bags[t], FFH_GATHER_GLOBAL_ROWS});
     segments.push_back({full_dense, batch_dense_input.impl->ptr, 4 * dense_dim, FFH_GATHER_LOCAL_ROWS});
     segments.push_back({full_label, batch_label.impl->ptr, 4, FFH_GATHER_LOCAL_ROWS});
   }
@@ -212,6 +218,16 @@ void DataLoader::generate_random(FFModel& ff, const DLRMConfig& dlrm) {
     // indexed by the slot's global position, so every rank that holds the table's ids masks them alike
     if (ff.config.embedding_padding && dlrm.synthetic_bag_fill < 1.0)
       ff.check(ff.api->pad->ffh_pad_mask_indices(ff.ctx, full_sparse[t], n, s0 + 0x9AD + 31 * t, 0, (float)dlrm.synthetic_bag_fill, ff.stream), "pad_mask_indices");
+    // --embedding-per-sample-weights: a weight per slot, uniform in [0.5, 1.5), from the counter stream of include/ffh_rng.h -- a stream per table,
+    // indexed by the slot's global position, so every rank that holds the table's ids holds the same weights.  Drawn on the host: the same code feeds
+    // every kernel library.
+    if (!batch_weight_inputs.empty() && batch_weight_inputs[t].impl->ptr) {
+      std::vector<float> w((size_t)n);
+      for (int64_t i = 0; i < n; i++) w[(size_t)i] = ffh_uniform(ffh_hash(s0 + 0xB46 + 37 * t, (uint64_t)i), 0.5f, 1.5f);
+      full_weights[t] = (float*)ff.dmalloc((size_t)n * sizeof(float));
+      ff.check(ff.api->ffh_memcpy_h2d(ff.ctx, full_weights[t], w.data(), (size_t)n * sizeof(float), ff.stream), "bag weights H2D");
+      ff.check(ff.api->ffh_stream_sync(ff.ctx, ff.stream), "bag weights sync");      // w leaves scope
+    }
   }
   // dense features and labels: this rank's slice [rank*Bl, (rank+1)*Bl) of every batch
   full_dense = (float*)ff.dmalloc((size_t)nb * Bl * dense_dim * sizeof(float));
@@ -357,6 +373,7 @@ void DataLoader::load_hdf5(FFModel& ff, const DLRMConfig& dlrm) {
 
 DataLoader::~DataLoader() {
   for (int64_t* p : full_sparse) if (p) model->api->ffh_free(model->ctx, p);
+  for (float* p : full_weights) if (p) model->api->ffh_free(model->ctx, p);
   if (full_dense) model->api->ffh_free(model->ctx, full_dense);
   if (full_label) model->api->ffh_free(model->ctx, full_label);
 }
@@ -396,6 +413,9 @@ void DataLoader::load_batch(FFModel& ff, int k) {
     if (!full_sparse[t]) continue;
     ff.check(ff.api->ffh_memcpy_d2d(ff.ctx, batch_sparse_inputs[t].impl->ptr, full_sparse[t] + first * bags[t],
                                     (size_t)B * bags[t] * sizeof(int64_t), ff.stream), "load sparse");
+    if (full_weights[t])
+      ff.check(ff.api->ffh_memcpy_d2d(ff.ctx, batch_weight_inputs[t].impl->ptr, full_weights[t] + first * bags[t], (size_t)B * bags[t] * sizeof(float),
+                                      ff.stream), "load bag weights");
   }
   ff.check(ff.api->ffh_memcpy_d2d(ff.ctx, batch_dense_input.impl->ptr, full_dense + (int64_t)k * Bl * dense_dim,
                                   (size_t)Bl * dense_dim * sizeof(float), ff.stream), "load dense");
@@ -479,6 +499,7 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
   for (size_t i = 0; i < dlrm.embedding_size.size(); i++) {
     const int dims[] = {ffconfig.batchSize, dlrm.bag_of(i)};
     sparse_inputs.push_back(ff->create_tensor<2>(dims, DT_INT64));
+    if (dlrm.per_sample_weights) weight_inputs.push_back(ff->create_tensor<2>(dims, DT_FLOAT));      // a weight beside every id (include/ffh_bag_weights.h)
   }
   {
     const int dims[] = {ffconfig.batchSize, dlrm.mlp_bot[0]};
@@ -488,7 +509,8 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
   Tensor x = create_mlp(ff, dense_input, dlrm.mlp_bot, dlrm.sigmoid_bot);
   std::vector<Tensor> ly;
   for (size_t i = 0; i < dlrm.embedding_size.size(); i++)
-    ly.push_back(create_emb(ff, sparse_inputs[i], dlrm.embedding_size[i], dlrm.sparse_feature_size, (int)i, dlrm.mean_pooling ? AGGR_MODE_AVG : AGGR_MODE_SUM));
+    ly.push_back(create_emb(ff, sparse_inputs[i], dlrm.embedding_size[i], dlrm.sparse_feature_size, (int)i, dlrm.mean_pooling ? AGGR_MODE_AVG : AGGR_MODE_SUM,
+                            dlrm.per_sample_weights ? &weight_inputs[i] : NULL));
   Tensor z = interact_features(ff, x, ly, dlrm.arch_interaction_op, dlrm.dcn_num_layers, dlrm.dcn_low_rank_dim);
   create_mlp(ff, z, dlrm.mlp_top, (int)dlrm.mlp_top.size() - 2);
   if (dlrm.loss_threshold > 0.0f && dlrm.loss_threshold < 1.0f) {
@@ -533,6 +555,7 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
     abort();
   }
   ff->compile(optimizer, (LossType)ffconfig.driver_loss, metrics);
+  if (chatty && dlrm.per_sample_weights) printf("[DLRM] embedding weights: per sample, synthetic uniform [0.5, 1.5)\n");
   if (chatty && ffconfig.embedding_padding) printf("[DLRM] embedding padding: id -1 is no lookup (synthetic fill %g)\n", dlrm.synthetic_bag_fill);
   // --embedding-pooling, only when given: a mean divides by a table's bag size L_t, or under --embedding-padding by the lookups a bag really has
   if (chatty && dlrm.pooling_given)
@@ -570,7 +593,7 @@ DLRMApp::DLRMApp(int argc, char** argv, const ffcomm* comm) : ff(nullptr), loade
            ffconfig.embedding_rounding == FFH_BF16_ROUND_NEAREST ? "nearest" : "stochastic", n16, ff->embeddings.size(), bytes / 1e9,
            ff->rank, fp32_tables.empty() ? "none" : fp32_tables.c_str());
   }
-  loader = new DataLoader(*ff, dlrm, sparse_inputs, dense_input, ff->label_tensor);
+  loader = new DataLoader(*ff, dlrm, sparse_inputs, dense_input, ff->label_tensor, weight_inputs);
   ff->init_layers();
   // checkpoint / resume; silent without the flags
   if (ffconfig.checkpoint_every_epochs > 0 && ffconfig.save_checkpoint_dir.empty()) {

@@ -26,6 +26,7 @@ struct DLRMConfig {
   bool bag_fill_given = false;
   bool mean_pooling = false;         // --embedding-pooling sum|mean: every table pools with AGGR_MODE_AVG instead of AGGR_MODE_SUM (not a reference flag)
   bool pooling_given = false;
+  bool per_sample_weights = false;   // --embedding-per-sample-weights: every table gets synthetic per-sample weights, uniform in [0.5, 1.5) (include/ffh_bag_weights.h; not a reference flag)
   double zipf_alpha;   // > 0: synthetic ids follow a power law instead of the reference's uniform draw (not a reference flag)
   int dcn_num_layers, dcn_low_rank_dim;   // --arch-interaction-op dcn: --dcn-num-layers L (3), --dcn-low-rank-dim R (512) (not reference flags)
 };
@@ -33,7 +34,8 @@ struct DLRMConfig {
 void parse_input_args(char** argv, int argc, DLRMConfig& config);
 
 Tensor create_mlp(FFModel* model, const Tensor& input, std::vector<int> ln, int sigmoid_layer);
-Tensor create_emb(FFModel* model, const Tensor& input, int input_dim, int output_dim, int idx, AggrMode aggr = AGGR_MODE_SUM);
+Tensor create_emb(FFModel* model, const Tensor& input, int input_dim, int output_dim, int idx, AggrMode aggr = AGGR_MODE_SUM,
+                  const Tensor* per_sample_weights = NULL);
 Tensor interact_features(FFModel* model, const Tensor& x, const std::vector<Tensor>& ly, std::string interaction, int dcn_num_layers = 3,
                          int dcn_low_rank_dim = 512);
 
@@ -43,7 +45,9 @@ Tensor interact_features(FFModel* model, const Tensor& x, const std::vector<Tens
 // per-table row count (the reference asserts all tables equal, :349-354 -- lifted).
 class DataLoader {
  public:
-  DataLoader(FFModel& ff, const DLRMConfig& dlrm, const std::vector<Tensor>& sparse_inputs, Tensor dense_input, Tensor label);
+  // weight_inputs: one [batch][bag] float tensor per table (--embedding-per-sample-weights), or empty
+  DataLoader(FFModel& ff, const DLRMConfig& dlrm, const std::vector<Tensor>& sparse_inputs, Tensor dense_input, Tensor label,
+             const std::vector<Tensor>& weight_inputs = std::vector<Tensor>());
   ~DataLoader();
   // the next TRAINING batch (wraps at num_train).  --data-randomize total: batch next_index / B of epoch `epoch`'s order, one gather launch
   // (include/ff_hip_data.h); a wrap without reset() moves on to the next epoch's order
@@ -64,6 +68,8 @@ class DataLoader {
   std::vector<Tensor> batch_sparse_inputs;
   Tensor batch_dense_input, batch_label;
   std::vector<int64_t*> full_sparse;   // per owned table: [num_samples][bags[t]]
+  std::vector<Tensor> batch_weight_inputs;   // --embedding-per-sample-weights: the tables' weight inputs (else empty) ...
+  std::vector<float*> full_weights;          // ... and per owned table its weights, laid out as its ids are: [num_samples][bags[t]]
   float *full_dense, *full_label;      // this rank's samples of every batch: [num_samples/world][...]
   std::vector<int> bags;               // bag size per table
   int dense_dim;
@@ -78,6 +84,7 @@ struct DLRMApp {
   DataLoader* loader;
   Optimizer* optimizer = nullptr;
   std::vector<Tensor> sparse_inputs;
+  std::vector<Tensor> weight_inputs;   // --embedding-per-sample-weights: one per table, beside sparse_inputs (else empty)
   Tensor dense_input;
   bool warmed_up;
   int start_epoch = 0;           // --load-checkpoint: the epochs the checkpoint had completed; run_epochs() goes on from there

@@ -453,6 +453,10 @@ class Embedding : public Op {
   float* opt_state[2] = {nullptr, nullptr};   // --sparse-embedding-optimizer: per-row state of this rank's slice (SGD momentum: V; Adam: M, V)
   bool held_here(int rank) const { return owner_rank == rank || column_sharded || row_sharded || replicated; }
   bool bf16_weights() const { return weights[0].data_type == DT_BF16; }   // --embedding-dtype bf16: 16-bit storage (include/ff_hip_bf16.h)
+  // per-sample weights (include/ffh_bag_weights.h): a model input [batch][bag] of floats beside the ids, or none.  Data, not a
+  // parameter: no gradient is formed for it.  Held where the ids are held.
+  bool weighted = false;
+  Tensor weights_in;
   uint8_t* q8_rows = nullptr;   // --eval-embedding-dtype int8: [num_entries][q8_row_bytes] image of the table for evaluation (include/ff_hip_q8.h), or null
   int64_t q8_row_bytes = 0;
 };
@@ -565,8 +569,9 @@ class FFModel {
   explicit FFModel(FFConfig& config);
   ~FFModel();
 
+  // per_sample_weights: an input tensor [batch][bag] of DT_FLOAT beside `input`, or NULL (EmbeddingBag's per_sample_weights; SUM pooling only)
   Tensor embedding(const Tensor& input, int num_entires, int outDim, AggrMode aggr, const Op* shared_op = NULL,
-                   Initializer* kernel_initializer = NULL, const char* name = NULL);
+                   Initializer* kernel_initializer = NULL, const char* name = NULL, const Tensor* per_sample_weights = NULL);
   Tensor batch_matmul(const Tensor& A, const Tensor& B, int a_seq_length_dim = -1, int b_seq_length_dim = -1);
   Tensor dense(const Tensor& input, int outDim, ActiMode activation = AC_MODE_NONE, bool use_bias = true,
                const Op* shared_op = NULL, Initializer* kernel_initializer = NULL,
@@ -752,7 +757,11 @@ class FFModel {
   mutable int64_t n_pad_updates = 0;          // ffh_embedding_bwd_fused_multi_bags_pad / ffh_embedding_bwd_apply_multi_bags_pad calls ("pad_update_launches")
   mutable int64_t n_pad_mean_gathers = 0;     // ffh_embedding_fwd_multi_bags_pad_mean[_bf16] launches (padded tables with AGGR_MODE_AVG; "pad_mean_gather_launches")
   mutable int64_t n_pad_mean_updates = 0;     // ffh_embedding_bwd_fused_multi_bags_pad_mean / ffh_embedding_bwd_apply_multi_bags_pad_mean calls ("pad_mean_update_launches")
-  bool bags_path() const { return mixed_bags || config.embedding_padding; }      // the tables go through the ragged entries: their bag sizes differ, or an id may be a pad
+  mutable int64_t n_bag_weight_gathers = 0;   // ffh_embedding_fwd_multi_bags_weighted[_bf16] launches (tables with per-sample weights; "bag_weight_gather_launches")
+  mutable int64_t n_bag_weight_updates = 0;   // ffh_embedding_bwd_fused_multi_bags_weighted / ffh_embedding_bwd_apply_multi_bags_weighted calls ("bag_weight_update_launches")
+  bool weighted_bags = false;                 // some table has per-sample weights: the model runs on the pad forms, as under --embedding-padding
+  bool pad_forms() const { return config.embedding_padding || weighted_bags; }
+  bool bags_path() const { return mixed_bags || pad_forms(); }      // the tables go through the ragged entries: their bag sizes differ, or an id may be a pad
   mutable int64_t n_ragged_updates = 0;       // ffh_embedding_bwd_fused_multi_bags calls (tests: flexflow_model_get_counter "ragged_update_launches")
   bool ragged_update_on() const;              // the tables' bag sizes differ and their fused update is the ragged call (the library has it, the flag allows it)
   bool ragged_early_sort_on() const;          // ... and --early-sort asks for its sort behind the gather, with a library that has the pair (include/ff_hip_bags_sort.h)

@@ -82,6 +82,10 @@ flexflow_tensor_t flexflow_model_add_embedding(flexflow_model_t m, flexflow_tens
                                                flexflow_initializer_t ki, const char* name) {
   return wrap(M(m)->embedding(*T(in), num_entries, out_dim, (AggrMode)aggr, NULL, I(ki), name));
 }
+flexflow_tensor_t flexflow_model_add_weighted_embedding(flexflow_model_t m, flexflow_tensor_t in, flexflow_tensor_t weights, int num_entries, int out_dim, int aggr,
+                                                        flexflow_initializer_t ki, const char* name) {
+  return wrap(M(m)->embedding(*T(in), num_entries, out_dim, (AggrMode)aggr, NULL, I(ki), name, T(weights)));
+}
 flexflow_tensor_t flexflow_model_add_concat(flexflow_model_t m, int n, const flexflow_tensor_t* ins, int axis, const char* name) {
   std::vector<Tensor> v;
   for (int i = 0; i < n; i++) v.push_back(*T(ins[i]));
@@ -184,6 +188,8 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   if (n == "pad_gather_launches") return M(m)->n_pad_gathers;      // ffh_embedding_fwd_multi_bags_pad[_bf16] launches (--embedding-padding; include/ff_hip_pad.h)
   if (n == "pad_mean_gather_launches") return M(m)->n_pad_mean_gathers;      // ffh_embedding_fwd_multi_bags_pad_mean[_bf16] launches (include/ff_hip_pad_mean.h)
   if (n == "pad_mean_update_launches") return M(m)->n_pad_mean_updates;      // ffh_embedding_bwd_{fused,apply}_multi_bags_pad_mean calls
+  if (n == "bag_weight_gather_launches") return M(m)->n_bag_weight_gathers;      // ffh_embedding_fwd_multi_bags_weighted[_bf16] launches (include/ffh_bag_weights.h)
+  if (n == "bag_weight_update_launches") return M(m)->n_bag_weight_updates;      // ffh_embedding_bwd_{fused,apply}_multi_bags_weighted calls
   if (n == "pad_update_launches") return M(m)->n_pad_updates;      // ffh_embedding_bwd_{fused,apply}_multi_bags_pad calls
   if (n == "q8_quantize_launches") return M(m)->n_q8_quantize;      // ffh_embedding_quantize_q8 launches (--eval-embedding-dtype int8; include/ff_hip_q8.h)
   if (n == "q8_gather_launches") return M(m)->n_q8_gathers;         // ffh_embedding_fwd_multi[_bags]_q8 launches

@@ -79,6 +79,9 @@ flexflow_tensor_t flexflow_model_add_dense(flexflow_model_t, flexflow_tensor_t i
                                            flexflow_initializer_t kernel_init, flexflow_initializer_t bias_init, const char* name);
 flexflow_tensor_t flexflow_model_add_embedding(flexflow_model_t, flexflow_tensor_t input, int num_entries, int out_dim, int aggr,
                                                flexflow_initializer_t kernel_init, const char* name);
+/* the embedding with per-sample weights: `weights` is an input tensor [batch][bag] of floats beside `input` (include/ffh_bag_weights.h) */
+flexflow_tensor_t flexflow_model_add_weighted_embedding(flexflow_model_t, flexflow_tensor_t input, flexflow_tensor_t weights, int num_entries, int out_dim, int aggr,
+                                                        flexflow_initializer_t kernel_init, const char* name);
 flexflow_tensor_t flexflow_model_add_concat(flexflow_model_t, int n, const flexflow_tensor_t* inputs, int axis, const char* name);
 flexflow_tensor_t flexflow_model_add_flat(flexflow_model_t, flexflow_tensor_t input, const char* name);
 flexflow_tensor_t flexflow_model_add_dot_interaction(flexflow_model_t, flexflow_tensor_t input, int d, const char* name);   /* [batch][c*d] -> [batch][d + c(c-1)/2] */

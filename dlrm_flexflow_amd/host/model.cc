@@ -485,9 +485,17 @@ Tensor FFModel::dense(const Tensor& input, int outDim, ActiMode activation, bool
 }
 
 Tensor FFModel::embedding(const Tensor& input, int num_entries, int outDim, AggrMode aggr, const Op* shared_op,
-                          Initializer* kernel_initializer, const char* name) {
+                          Initializer* kernel_initializer, const char* name, const Tensor* per_sample_weights) {
   if (kernel_initializer == nullptr) kernel_initializer = new GlorotUniform(next_seed());   // [ref: src/ops/embedding.cu:19-34]
   Embedding* e = new Embedding(*this, input, num_entries, outDim, aggr, shared_op, kernel_initializer, name);
+  if (per_sample_weights) {
+    const Tensor& w = *per_sample_weights;
+    if (w.data_type != DT_FLOAT || w.numDim != 2 || w.owner_op != nullptr || w.adim[0] != input.adim[0] || w.adim[1] != input.adim[1])
+      die("%s: per-sample weights must be a DT_FLOAT model input tensor of the ids' shape [batch][bag]", e->name);
+    e->weighted = true;
+    e->weights_in = w;
+    weighted_bags = true;
+  }
   e->layer_index = (int)layers.size();
   layers.push_back(e);
   return e->outputs[0];

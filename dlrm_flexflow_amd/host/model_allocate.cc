@@ -185,6 +185,36 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
       die("--embedding-padding: %s (%s) is a kernel library without the pad extension (include/ff_hip_pad.h); drop --embedding-padding, or use another "
           "--backend", api->path.c_str(), api->ffh_backend_name());
   }
+  // per-sample weights (include/ffh_bag_weights.h): a weighted table is gathered and updated by the weighted forms of the pad
+  // ragged entries, and the whole model runs on the pad forms.  What those forms do not cover is refused here, each with the flag to drop.
+  if (weighted_bags) {
+    for (const Embedding* e : embeddings) {
+      if (e->weighted && e->aggr == AGGR_MODE_AVG)
+        die("per-sample weights: %s pools with AGGR_MODE_AVG; weights with mean pooling are not supported: use AGGR_MODE_SUM (drop --embedding-pooling mean) "
+            "or drop the weights (--embedding-per-sample-weights)", e->name);
+      const char* flag = e->row_sharded ? "--row-shard-rows" : e->column_sharded ? "--column-shard-rows" : e->replicated ? "--replicate-embedding-rows" : nullptr;
+      if (flag)
+        die("per-sample weights: %s is %s; weighted tables are table-wise: drop %s or drop the weights (--embedding-per-sample-weights)", e->name,
+            e->row_sharded ? "row-sharded" : e->column_sharded ? "column-sharded" : "replicated", flag);
+    }
+    if (config.dense_embedding_update)
+      die("per-sample weights need the fused sparse table update: drop --dense-embedding-update or drop the weights (--embedding-per-sample-weights)");
+    if (!fused_embedding_update())      // (plain SGD and Adagrad without weight decay take the fused update by themselves: fused_embedding_update())
+      die("per-sample weights need the fused sparse table update, which this optimizer (SGD with momentum or weight decay, Adam) takes only with "
+          "--sparse-embedding-optimizer: add it or drop the weights (--embedding-per-sample-weights)");
+    if (!config.dataset_path.empty())
+      die("per-sample weights: --dataset %s is an HDF5 file of X_int, X_cat and y, which defines no weight column: drop --dataset (synthetic data draws "
+          "its weights) or drop the weights (--embedding-per-sample-weights)", config.dataset_path.c_str());
+    if (!config.ragged_gather)
+      die("per-sample weights gather through the ragged entries' weighted forms: drop --no-ragged-gather or drop the weights (--embedding-per-sample-weights)");
+    if (!config.ragged_update)
+      die("per-sample weights update through the ragged entries' weighted forms: drop --no-ragged-update or drop the weights (--embedding-per-sample-weights)");
+    if (q8_on())
+      die("per-sample weights: the 8-bit gathers have no weighted form; drop --eval-embedding-dtype int8 or drop the weights (--embedding-per-sample-weights)");
+    if (!api->bag_weights || !api->pad || !api->bags || !api->bags_update)
+      die("per-sample weights: %s (%s) is a kernel library without the bag-weights extension (include/ffh_bag_weights.h); drop the weights "
+          "(--embedding-per-sample-weights), or use another --backend", api->path.c_str(), api->ffh_backend_name());
+  }
   // --eval-embedding-dtype int8 (include/ff_hip_q8.h): eval_batch() gathers table-wise tables from 8-bit row images; every case
   // that does not cover is refused here, each with the flag to drop -- before the library checks: a library without the extensions shows them too.
   // (The gather destinations' 16-byte form follows from the layer structure: q8_check_destinations().)
@@ -399,6 +429,8 @@ void FFModel::allocate() {
   // ---- 2. inputs and label ----------------------------------------------------------------------
   std::map<TensorImpl*, Embedding*> sparse_of;
   for (Embedding* e : embeddings) sparse_of[e->inputs[0].impl] = e;
+  for (Embedding* e : embeddings)
+    if (e->weighted) sparse_of[e->weights_in.impl] = e;      // per-sample weights lie where the ids lie: with the table's owner, for the global batch
   auto alloc_rows = [&](const Tensor& t, int64_t nrows) {
     TensorImpl* im = t.impl;
     im->ld = t.adim[0];
@@ -945,17 +977,17 @@ void FFModel::allocate() {
     // ... or once per group of mixed bag sizes (the ragged update, include/ff_hip_bags_update.h): a group's calls as launch_shard_groups cuts them.  The
     // sizing above stays beside it: the roofline probe and --no-ragged-update run the calls per bag size
     if (ragged_update_on()) {
-      std::map<std::pair<int, bool>, std::vector<int>> bags_of;
+      std::map<std::tuple<int, bool, bool>, std::vector<int>> bags_of;      // (weighted tables: groups of their own, as launch_shard_groups cuts them)
       for (const EmbShard& sh : shards)
-        if (sh.owner == rank) bags_of[{sh.cols, sh.e->bf16_weights()}].push_back(sh.e->inputs[0].adim[0]);
+        if (sh.owner == rank) bags_of[std::make_tuple(sh.cols, sh.e->bf16_weights(), sh.e->weighted)].push_back(sh.e->inputs[0].adim[0]);
       for (const auto& kv : bags_of) {
-        const size_t per = kv.first.second ? bf16_tables_per_launch() : (size_t)FFH_MAX_TABLES;
+        const size_t per = std::get<1>(kv.first) ? bf16_tables_per_launch() : (size_t)FFH_MAX_TABLES;
         for (size_t b = 0; b < kv.second.size(); b += per) {
           const int n = (int)std::min(per, kv.second.size() - b);
-          workspace_bytes = std::max(workspace_bytes, api->bags_update->ffh_embedding_bwd_bags_workspace_bytes(kv.second.data() + b, n, kv.first.first, config.batchSize) + 256);
+          workspace_bytes = std::max(workspace_bytes, api->bags_update->ffh_embedding_bwd_bags_workspace_bytes(kv.second.data() + b, n, std::get<0>(kv.first), config.batchSize) + 256);
           // (a padded table that pools with AGGR_MODE_AVG: the mean update keeps its bags' counts behind that layout, include/ff_hip_pad_mean.h)
           if (config.embedding_padding && api->pad_mean && embeddings[0]->aggr == AGGR_MODE_AVG)
-            workspace_bytes = std::max(workspace_bytes, api->pad_mean->ffh_embedding_bwd_bags_pad_mean_workspace_bytes(kv.second.data() + b, n, kv.first.first, config.batchSize) + 256);
+            workspace_bytes = std::max(workspace_bytes, api->pad_mean->ffh_embedding_bwd_bags_pad_mean_workspace_bytes(kv.second.data() + b, n, std::get<0>(kv.first), config.batchSize) + 256);
         }
       }
     }
@@ -1145,7 +1177,7 @@ void FFModel::plan_fold() {
   fold = FoldRoute();
   if (!config.fold_small_tables || !api->fold || exchange || world_size != 1 || embeddings.empty()) return;
   if (mixed_bags) return;      // the fold is planned on one bag size
-  if (config.embedding_padding) return;      // ... and on ids that are all rows: a folded table's gather-add and segmented sum take no pad
+  if (pad_forms()) return;      // ... and on ids that are all rows (per-sample weights: the fold is off as well): a folded table's gather-add and segmented sum take no pad
   if (config.allow_tensor_op_math_conversion || config.fp32_split_bf16x3) return;
   for (Op* op : layers) {
     Linear* li = dynamic_cast<Linear*>(op);

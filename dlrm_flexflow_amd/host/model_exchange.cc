@@ -28,18 +28,21 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
   // --embedding-padding (include/ff_hip_pad.h): an id may be -1, which only the pad forms of the ragged entries take -- every chunk of every group
   // goes through them, whether or not its bag sizes differ (compile() has refused every configuration in which one of the three is off).
   const bool ragged = fwd ? ff->ragged_gather_on() : (what == kFusedUpdate ? ff->ragged_update_on() : ff->ragged_early_sort_on());
-  const bool pad = ff->config.embedding_padding;
+  const bool pad = ff->pad_forms();
+  // ... and a table with per-sample weights takes their weighted forms (include/ffh_bag_weights.h; compile() has checked the library and that such a
+  // table pools with a sum): groups of their own, which carry one weight pointer per table.  The early sort stays the pad sort.
+  const KernelApiBagWeights* bwa = ff->api->bag_weights;
   const KernelApiPad* pda = ff->api->pad;
   // ... and a padded table that pools with AGGR_MODE_AVG takes their mean forms (include/ff_hip_pad_mean.h; compile() has checked that the library has
   // them): the gather, the fused update and the apply.  The early sort stays the pad sort, which serves either apply.
   const bool pad_mean = pad && aggr == FFH_AGGR_MODE_AVG;
   const KernelApiPadMean* pma = ff->api->pad_mean;
   struct Group { std::vector<ffh_emb_table> t; std::vector<ffh_emb_table_bf16> t16; std::vector<ffh_emb_state> st; std::vector<int> bag;
-                 std::vector<ffh_emb_table_q8> tq; std::vector<int> bagq; };      // tq, bagq: the tables an evaluation gathers from their 8-bit row images
+                 std::vector<const float*> w; std::vector<ffh_emb_table_q8> tq; std::vector<int> bagq; };      // tq, bagq: the tables an evaluation gathers from their 8-bit row images
   // --eval-embedding-dtype int8: the gather of eval_batch() reads the images (include/ff_hip_q8.h), in the same groups.  eval_batch() has made stale images
   // again before it issued this forward pass (on the calling thread: this function may run on a launch worker, and reads the images' addresses only)
   const bool q8 = fwd && ff->evaluating && ff->q8_on() && !idx_override && !all_tables;
-  std::map<std::tuple<int, bool, int>, Group> groups;
+  std::map<std::tuple<int, bool, int, bool>, Group> groups;
   size_t owned_i = 0;
   for (const FFModel::EmbShard& sh : ff->shards) {
     if (sh.owner != ff->rank) continue;
@@ -59,7 +62,7 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
       t.ld = ff->rank_width[ff->rank];
     }
     const int bag = e->inputs[0].adim[0];
-    Group& g = groups[std::make_tuple(sh.cols, e->bf16_weights(), ragged ? 0 : bag)];
+    Group& g = groups[std::make_tuple(sh.cols, e->bf16_weights(), ragged ? 0 : bag, e->weighted)];
     if (q8 && e->q8_rows) {
       g.tq.push_back(ffh_emb_table_q8{t.idx, e->q8_rows, t.io, t.num_entries, t.ld, e->q8_row_bytes});
       g.bagq.push_back(bag);
@@ -69,11 +72,13 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
     else g.t.push_back(t);
     g.st.push_back(ffh_emb_state{e->opt_state[0], e->opt_state[1]});
     g.bag.push_back(bag);
+    if (e->weighted) g.w.push_back((const float*)e->weights_in.impl->ptr);
   }
   const int64_t B = ff->config.batchSize;
   for (auto& kv : groups) {
     const int D = std::get<0>(kv.first);
     const Group& g = kv.second;
+    const bool wgt = std::get<3>(kv.first);
     // tables [b, b + n) of the group in one ragged launch: where their bag sizes differ (else the call stays the uniform one)
     auto differ = [&](size_t b, int n) {
       if (pad) return true;
@@ -91,6 +96,13 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
         if (pad) ff->check(pda->ffh_embedding_bwd_sort_multi_bags_pad(cx, &u, s), "embedding_bwd_sort_multi_bags_pad");
         else ff->check(ff->api->bags_sort->ffh_embedding_bwd_sort_multi_bags(cx, &u, s), "embedding_bwd_sort_multi_bags");
         ff->n_early_sorts++; ff->n_ragged_early_sorts++;
+        return;
+      }
+      if (wgt) {
+        const ffh_bags_update_weighted uw = {u, g.w.data() + b};
+        if (what == kApplyOnly) ff->check(bwa->ffh_embedding_bwd_apply_multi_bags_weighted(cx, &uw, s), "embedding_bwd_apply_multi_bags_weighted");
+        else ff->check(bwa->ffh_embedding_bwd_fused_multi_bags_weighted(cx, &uw, s), "embedding_bwd_fused_multi_bags_weighted");
+        ff->n_bag_weight_updates++;
         return;
       }
       if (pad_mean) {
@@ -128,7 +140,10 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
         const int L = g.bag[b];       // a uniform call's bag size is its own tables' (a whole group of mixed sizes holds several)
         switch (what) {
           case kGather:
-            if (pad_mean) {
+            if (wgt) {
+              ff->check(bwa->ffh_embedding_fwd_multi_bags_weighted_bf16(cx, tb, g.w.data() + b, g.bag.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags_weighted_bf16");
+              ff->n_bag_weight_gathers++;
+            } else if (pad_mean) {
               ff->check(pma->ffh_embedding_fwd_multi_bags_pad_mean_bf16(cx, tb, g.bag.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags_pad_mean_bf16");
               ff->n_pad_mean_gathers++;
             } else if (pad) {
@@ -165,7 +180,10 @@ void launch_shard_groups(const FFModel* ff, ShardLaunch what, ffh_stream s, ffh_
       const int L = g.bag[b];
       switch (what) {
         case kGather:
-          if (pad_mean) {
+          if (wgt) {
+            ff->check(bwa->ffh_embedding_fwd_multi_bags_weighted(cx, tabs.data() + b, g.w.data() + b, g.bag.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags_weighted");
+            ff->n_bag_weight_gathers++;
+          } else if (pad_mean) {
             ff->check(pma->ffh_embedding_fwd_multi_bags_pad_mean(cx, tabs.data() + b, g.bag.data() + b, n, D, B, aggr, s), "embedding_fwd_multi_bags_pad_mean");
             ff->n_pad_mean_gathers++;
           } else if (pad) {
@@ -382,7 +400,7 @@ bool FFModel::early_sort_possible(int where) const {
   const bool exact_gemms = !config.allow_tensor_op_math_conversion && !config.fp32_split_bf16x3;
   const int mode = config.early_sort > 0 ? config.early_sort : ((!exchange && local_batch >= 8192 && exact_gemms) ? early_sort_big_batch_mode : 1);
   if (mode != where) return false;
-  if (config.embedding_padding && !ragged_early_sort_on()) return false;      // (the uniform sort takes no pad id: only the pad pair sorts early, on --early-sort)
+  if (pad_forms() && !ragged_early_sort_on()) return false;      // (the uniform sort takes no pad id: only the pad pair sorts early, on --early-sort)
   int n = 0, cols = -1, bag = -1;
   for (const EmbShard& sh : shards) {
     if (sh.owner != rank) continue;
