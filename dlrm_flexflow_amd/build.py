@@ -26,7 +26,8 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp
 # sources compiled without the packed fp32 instructions (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32): every file added from here on
 # (a device feature: the host half of the hipcc line prints "not a recognized feature for this target (ignoring feature)", which is all it does)
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"interaction_wide.hip": NO_PACKED_FP32, "linear_sk_gather.hip": NO_PACKED_FP32, "embedding_bag_weights.hip": NO_PACKED_FP32}
+EXTRA_FLAGS = {"interaction_wide.hip": NO_PACKED_FP32, "linear_sk_gather.hip": NO_PACKED_FP32, "embedding_bag_weights.hip": NO_PACKED_FP32,
+               "embedding_bag_weights_grad.hip": NO_PACKED_FP32}
 
 
 def _newer(target: str, sources: list[str]) -> bool:

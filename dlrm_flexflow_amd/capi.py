@@ -1128,6 +1128,43 @@ class BagWeightsApi(ExtensionApi):
 bag_weights_api = BagWeightsApi
 
 
+# ---- the bag-weights-grad extension (include/ffh_bag_weights_grad.h): gw[b][l] = dY[b] . W[idx[b][l]], the gradient of per-sample weights ------
+# Like bag_weights: a header outside ff_hip_*.h and no *_HEADER_PATH alias (EXTENSIONS["bag_weights_grad"].header_path is the path).
+BAG_WGRAD_ACCUMULATE = 1
+
+_SIGS_BAG_WEIGHTS_GRAD = {
+    "ffh_bag_weights_grad_abi_version": (I, []),
+    "ffh_bag_weights_grad_grid_cap": (L, []),
+    "ffh_bag_weights_grad": (I, [P, C.POINTER(EmbTable), C.POINTER(P), C.POINTER(L), C.POINTER(I), I, I, L, I, P]),
+    "ffh_bag_weights_grad_bf16": (I, [P, C.POINTER(EmbTableBf16), C.POINTER(P), C.POINTER(L), C.POINTER(I), I, I, L, I, P]),
+}
+BAG_WEIGHTS_GRAD_EXT = _extension("bag_weights_grad", _SIGS_BAG_WEIGHTS_GRAD, "bag-weights-grad", header_name="ffh_bag_weights_grad.h")
+
+
+class BagWeightsGradApi(ExtensionApi):
+    """The table list is the weighted gather's (hip.emb_tables / Bf16Api.tables) with `io` the table's slice of the embedding output gradient;
+    `gw` one destination per table (a device buffer, an address or None), `gw_ld` their leading dimensions."""
+    ext = BAG_WEIGHTS_GRAD_EXT
+
+    def grid_cap(self) -> int:
+        return int(self.lib.ffh_bag_weights_grad_grid_cap())
+
+    def grad_rc(self, tables, gw, gw_ld, in_dims, ntables: int, out_dim: int, batch: int, accumulate: bool = False, bf16: bool = False, flags=None,
+                stream=None) -> int:
+        """ffh_bag_weights_grad[_bf16], returning its status code; `in_dims` from BagsApi.in_dims; `gw`, `gw_ld` or `in_dims` None: a null pointer."""
+        fn = self.lib.ffh_bag_weights_grad_bf16 if bf16 else self.lib.ffh_bag_weights_grad
+        dst = None if gw is None else (P * max(len(gw), 1))(*[ptr(b) for b in gw])
+        lds = None if gw_ld is None else (L * max(len(gw_ld), 1))(*[int(v) for v in gw_ld])
+        fl = (BAG_WGRAD_ACCUMULATE if accumulate else 0) if flags is None else int(flags)
+        return fn(self.ctx, tables, dst, lds, in_dims, int(ntables), int(out_dim), int(batch), fl, ptr(stream))
+
+    def grad(self, *args, **kw):
+        self.base.check(self.grad_rc(*args, **kw), "ffh_bag_weights_grad")
+
+
+bag_weights_grad_api = BagWeightsGradApi
+
+
 _hip_singleton: FFHLib | None = None
 
 

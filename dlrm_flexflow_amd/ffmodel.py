@@ -254,6 +254,17 @@ def weighted_bag_reference(W, idx, w) -> np.ndarray:
     return out
 
 
+def bag_weights_grad_reference(W, idx, dY) -> np.ndarray:
+    """The gradient of per-sample bag weights (include/ffh_bag_weights_grad.h) in numpy, float64: gw[b][l] = sum_d dY[b][d] * W[idx[b][l]][d], and
+    0 for a pad (idx < 0).  `W` is [rows][D] (a bf16 table: widened), `idx` [batch][L] integers, `dY` [batch][D].  The weight itself does not enter."""
+    W, idx, dY = np.asarray(W, np.float64), np.asarray(idx, np.int64), np.asarray(dY, np.float64)
+    out = np.zeros(idx.shape, np.float64)
+    for j in range(idx.shape[1]):
+        live = idx[:, j] >= 0
+        out[live, j] = (dY[live] * W[idx[live, j]]).sum(1)
+    return out
+
+
 def state_digest_reference(data, seed: int, index_base: int = 0, row_bytes: int | None = None) -> int:
     """The digest of include/ff_hip_digest.h restated in numpy: `data` is a 2-D array (its rows are the rows, row_bytes their length in bytes:
     whatever its strides are, only the elements count, so the result does not depend on a leading dimension), a 1-D array (one row), or
@@ -647,8 +658,9 @@ class FFModel:
 
     def embedding(self, input: Tensor, num_entries, out_dim, aggr=capi.AGGR_MODE_SUM, kernel_initializer=None, name=None,
                   per_sample_weights: Tensor | None = None) -> Tensor:
-        """per_sample_weights: an input tensor [batch][bag] of DT_FLOAT beside `input` (EmbeddingBag's per_sample_weights, SUM pooling only;
-        include/ffh_bag_weights.h): the bag is the weighted sum of its rows.  The weights are data: no gradient is formed for them."""
+        """per_sample_weights: a tensor [batch][bag] of DT_FLOAT beside `input` (EmbeddingBag's per_sample_weights, SUM pooling only;
+        include/ffh_bag_weights.h): the bag is the weighted sum of its rows.  An input tensor is data, and no gradient is formed for it; another
+        operator's output (a position-weight or gating layer) gets its gradient from the embedding's backward (include/ffh_bag_weights_grad.h)."""
         if per_sample_weights is not None:
             return Tensor(lib().flexflow_model_add_weighted_embedding(self.h, input.h, per_sample_weights.h, num_entries, out_dim, aggr,
                                                                       kernel_initializer or _NULL, name.encode() if name else None), self)

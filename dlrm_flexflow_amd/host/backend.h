@@ -22,6 +22,7 @@
 #include "../../include/ffh_dot_wide.h"
 #include "../../include/ffh_fused_gather.h"
 #include "../../include/ffh_bag_weights.h"
+#include "../../include/ffh_bag_weights_grad.h"
 
 // The optional extensions of the kernel C-ABI, one line each, in the order load_kernel_api() loads them:
 //   X(KernelApi field, struct, the header's list, version symbol, the header's version, label of the version message, header under include/
@@ -68,7 +69,10 @@
   X(fused_gather, KernelApiFusedGather, FFH_FUSED_GATHER_API_LIST, ffh_fused_gather_abi_version, FFH_FUSED_GATHER_ABI_VERSION, "fused-gather", "ffh_fused_gather.h") \
   /* per-sample weights on embedding bags: the weighted forms of the pad gather and of the pad update (its header is ffh_bag_weights.h: see     \
      the header) */                                                                                                                              \
-  X(bag_weights, KernelApiBagWeights, FFH_BAG_WEIGHTS_API_LIST, ffh_bag_weights_abi_version, FFH_BAG_WEIGHTS_ABI_VERSION, "bag-weights", "ffh_bag_weights.h")
+  X(bag_weights, KernelApiBagWeights, FFH_BAG_WEIGHTS_API_LIST, ffh_bag_weights_abi_version, FFH_BAG_WEIGHTS_ABI_VERSION, "bag-weights", "ffh_bag_weights.h") \
+  /* the gradient of per-sample weights that an operator produces: gw[b][l] = dY[b] . W[idx[b][l]] (its header is ffh_bag_weights_grad.h: see    \
+     the header) */                                                                                                                              \
+  X(bag_weights_grad, KernelApiBagWeightsGrad, FFH_BAG_WEIGHTS_GRAD_API_LIST, ffh_bag_weights_grad_abi_version, FFH_BAG_WEIGHTS_GRAD_ABI_VERSION, "bag-weights-grad", "ffh_bag_weights_grad.h")
 
 #define FFH_DECL(name) decltype(&::name) name;
 

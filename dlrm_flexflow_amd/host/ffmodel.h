@@ -457,6 +457,10 @@ class Embedding : public Op {
   // parameter: no gradient is formed for it.  Held where the ids are held.
   bool weighted = false;
   Tensor weights_in;
+  // ... or another operator's output (include/ffh_bag_weights_grad.h): the embedding's backward then forms its gradient,
+  // gw[b][l] = dY[b] . W[idx[b][l]], stored into the tensor's gradient buffer -- or added, where the tensor has another consumer
+  bool weights_produced = false;
+  bool gw_accumulate = false;
   uint8_t* q8_rows = nullptr;   // --eval-embedding-dtype int8: [num_entries][q8_row_bytes] image of the table for evaluation (include/ff_hip_q8.h), or null
   int64_t q8_row_bytes = 0;
 };
@@ -569,7 +573,8 @@ class FFModel {
   explicit FFModel(FFConfig& config);
   ~FFModel();
 
-  // per_sample_weights: an input tensor [batch][bag] of DT_FLOAT beside `input`, or NULL (EmbeddingBag's per_sample_weights; SUM pooling only)
+  // per_sample_weights: a tensor [batch][bag] of DT_FLOAT beside `input`, or NULL (EmbeddingBag's per_sample_weights; SUM pooling only): a model
+  // input (data: no gradient) or another operator's output, which gets its gradient from the embedding's backward (include/ffh_bag_weights_grad.h)
   Tensor embedding(const Tensor& input, int num_entires, int outDim, AggrMode aggr, const Op* shared_op = NULL,
                    Initializer* kernel_initializer = NULL, const char* name = NULL, const Tensor* per_sample_weights = NULL);
   Tensor batch_matmul(const Tensor& A, const Tensor& B, int a_seq_length_dim = -1, int b_seq_length_dim = -1);
@@ -759,6 +764,14 @@ class FFModel {
   mutable int64_t n_pad_mean_updates = 0;     // ffh_embedding_bwd_fused_multi_bags_pad_mean / ffh_embedding_bwd_apply_multi_bags_pad_mean calls ("pad_mean_update_launches")
   mutable int64_t n_bag_weight_gathers = 0;   // ffh_embedding_fwd_multi_bags_weighted[_bf16] launches (tables with per-sample weights; "bag_weight_gather_launches")
   mutable int64_t n_bag_weight_updates = 0;   // ffh_embedding_bwd_fused_multi_bags_weighted / ffh_embedding_bwd_apply_multi_bags_weighted calls ("bag_weight_update_launches")
+  mutable int64_t n_bag_weight_grads = 0;     // ffh_bag_weights_grad[_bf16] launches (tables whose weights an operator produces; "bag_weight_grad_launches")
+  bool produced_bag_weights = false;          // some table's per-sample weights are an operator's output: the gather goes behind that operator, the weights get a gradient
+  int bag_gw_wait_layer = -1;                 // the last layer (in layer order) that produces such weights: its backward waits for ev_bag_gw
+  bool bag_gw_accumulates = false;            // such a tensor has another reader, which adds into the same gradient buffer: the wait moves up to the tables
+  ffh_event ev_bag_gw = nullptr;              // recorded behind the ffh_bag_weights_grad launches, on the stream of the table update they stand in front of
+  mutable bool bag_gw_issued = false;         // this step's launches are out (backward() clears it) ...
+  mutable bool bag_gw_recorded = false;       // ... on the side stream, with ev_bag_gw behind them: the compute stream has to wait for it
+  void bag_weight_grads(ffh_stream s, ffh_ctx* cx) const;      // the launches, group by group as launch_shard_groups cuts the weighted update
   bool weighted_bags = false;                 // some table has per-sample weights: the model runs on the pad forms, as under --embedding-padding
   bool pad_forms() const { return config.embedding_padding || weighted_bags; }
   bool bags_path() const { return mixed_bags || pad_forms(); }      // the tables go through the ragged entries: their bag sizes differ, or an id may be a pad

@@ -190,6 +190,7 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   if (n == "pad_mean_update_launches") return M(m)->n_pad_mean_updates;      // ffh_embedding_bwd_{fused,apply}_multi_bags_pad_mean calls
   if (n == "bag_weight_gather_launches") return M(m)->n_bag_weight_gathers;      // ffh_embedding_fwd_multi_bags_weighted[_bf16] launches (include/ffh_bag_weights.h)
   if (n == "bag_weight_update_launches") return M(m)->n_bag_weight_updates;      // ffh_embedding_bwd_{fused,apply}_multi_bags_weighted calls
+  if (n == "bag_weight_grad_launches") return M(m)->n_bag_weight_grads;      // ffh_bag_weights_grad[_bf16] launches (include/ffh_bag_weights_grad.h)
   if (n == "pad_update_launches") return M(m)->n_pad_updates;      // ffh_embedding_bwd_{fused,apply}_multi_bags_pad calls
   if (n == "q8_quantize_launches") return M(m)->n_q8_quantize;      // ffh_embedding_quantize_q8 launches (--eval-embedding-dtype int8; include/ff_hip_q8.h)
   if (n == "q8_gather_launches") return M(m)->n_q8_gathers;         // ffh_embedding_fwd_multi[_bags]_q8 launches

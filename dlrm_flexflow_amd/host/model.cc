@@ -379,6 +379,7 @@ FFModel::FFModel(FFConfig& _config)
   check((config.timing_events ? api->ffh_event_create : api->ffh_event_create_sync)(ctx, &ev_join), "event create");
   check((config.timing_events ? api->ffh_event_create : api->ffh_event_create_sync)(ctx, &ev_grad_ready), "event create");
   check((config.timing_events ? api->ffh_event_create : api->ffh_event_create_sync)(ctx, &ev_update_done), "event create");
+  check((config.timing_events ? api->ffh_event_create : api->ffh_event_create_sync)(ctx, &ev_bag_gw), "event create");
 }
 
 FFModel::~FFModel() {
@@ -410,6 +411,7 @@ FFModel::~FFModel() {
   if (ev_fold_e_read) api->ffh_event_destroy(ctx, ev_fold_e_read);
   if (ev_fold_w_read) api->ffh_event_destroy(ctx, ev_fold_w_read);
   if (ev_fold_x_read) api->ffh_event_destroy(ctx, ev_fold_x_read);
+  if (ev_bag_gw) api->ffh_event_destroy(ctx, ev_bag_gw);
   for (void* p : {(void*)fold.P, (void*)fold.S, (void*)fold.G, fold.sum_ws}) if (p) api->ffh_free(ctx, p);
   if (fold.sum_ctx) api->ffh_ctx_destroy(fold.sum_ctx);
   for (auto& kv : trace_tune) for (ffh_event& e : kv.second.ev) if (e) { api->ffh_event_destroy(ctx, e); e = nullptr; }
@@ -490,11 +492,17 @@ Tensor FFModel::embedding(const Tensor& input, int num_entries, int outDim, Aggr
   Embedding* e = new Embedding(*this, input, num_entries, outDim, aggr, shared_op, kernel_initializer, name);
   if (per_sample_weights) {
     const Tensor& w = *per_sample_weights;
-    if (w.data_type != DT_FLOAT || w.numDim != 2 || w.owner_op != nullptr || w.adim[0] != input.adim[0] || w.adim[1] != input.adim[1])
-      die("%s: per-sample weights must be a DT_FLOAT model input tensor of the ids' shape [batch][bag]", e->name);
+    if (w.data_type != DT_FLOAT || w.numDim != 2 || w.adim[0] != input.adim[0] || w.adim[1] != input.adim[1])
+      die("%s: per-sample weights must be a DT_FLOAT tensor of the ids' shape [batch][bag]", e->name);
     e->weighted = true;
     e->weights_in = w;
     weighted_bags = true;
+    // an operator's output: the weights are computed by the model and get a gradient (include/ffh_bag_weights_grad.h)
+    if (w.owner_op != nullptr) {
+      e->weights_produced = true;
+      produced_bag_weights = true;
+      bag_gw_wait_layer = std::max(bag_gw_wait_layer, w.owner_op->layer_index);
+    }
   }
   e->layer_index = (int)layers.size();
   layers.push_back(e);
@@ -843,6 +851,13 @@ void Embedding::forward(const FFModel& ff) {
   // in front of the tables (the bottom MLP), so the GPU runs those while the host walks the exchange callback.
   if (ff.emb_forward_issued) return;
   if (ff.config.overlap_embedding) {
+    if (ff.produced_bag_weights) {
+      // some table's weights are an operator's output: the gather forks here, behind that operator (compile() has checked that it stands in front of
+      // the first table), not at the top of forward()
+      ff.check(ff.api->ffh_event_record(ff.ctx, ff.ev_fork, ff.stream), "fork");
+      ff.fork_recorded = true;
+      ff.inputs_dirty = false;
+    }
     ff.issue_embedding_forward_on_side_stream();
   } else {
     ff.embedding_group_forward(ff.stream);
@@ -858,6 +873,13 @@ void Embedding::backward(const FFModel& ff) {
   // into the dense slab on the compute stream; the slab's all-reduce and optimizer launch in update() then treat it like any
   // MLP parameter
   ff.replicated_embedding_grads();
+  // weights that an operator produces: their gradient reads the table rows before this step's update writes them.  The side-stream update carries the
+  // launches in front of itself (embedding_group_update); an update that update() issues comes too late for the producing operators' backward, so the
+  // launches go out here, on the stream that update will run on
+  if (ff.produced_bag_weights && !(ff.fused_embedding_update() && ff.config.overlap_embedding)) {
+    ff.bag_weight_grads(ff.stream, ff.ctx);
+    ff.bag_gw_issued = true;
+  }
   if (ff.fused_embedding_update()) {
     if (ff.config.overlap_embedding) {
       // gradients of every table are complete here; the side-stream update itself is issued at the END of

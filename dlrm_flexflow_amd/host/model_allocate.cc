@@ -188,32 +188,53 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
   // per-sample weights (include/ffh_bag_weights.h): a weighted table is gathered and updated by the weighted forms of the pad
   // ragged entries, and the whole model runs on the pad forms.  What those forms do not cover is refused here, each with the flag to drop.
   if (weighted_bags) {
+    // (weights that an operator produces come from no driver flag: the advice is to build the table without them)
+    const char* drop = produced_bag_weights ? "pass no per_sample_weights to FFModel::embedding" : "drop the weights (--embedding-per-sample-weights)";
     for (const Embedding* e : embeddings) {
       if (e->weighted && e->aggr == AGGR_MODE_AVG)
         die("per-sample weights: %s pools with AGGR_MODE_AVG; weights with mean pooling are not supported: use AGGR_MODE_SUM (drop --embedding-pooling mean) "
-            "or drop the weights (--embedding-per-sample-weights)", e->name);
+            "or %s", e->name, drop);
       const char* flag = e->row_sharded ? "--row-shard-rows" : e->column_sharded ? "--column-shard-rows" : e->replicated ? "--replicate-embedding-rows" : nullptr;
       if (flag)
-        die("per-sample weights: %s is %s; weighted tables are table-wise: drop %s or drop the weights (--embedding-per-sample-weights)", e->name,
-            e->row_sharded ? "row-sharded" : e->column_sharded ? "column-sharded" : "replicated", flag);
+        die("per-sample weights: %s is %s; weighted tables are table-wise: drop %s or %s", e->name,
+            e->row_sharded ? "row-sharded" : e->column_sharded ? "column-sharded" : "replicated", flag, drop);
     }
     if (config.dense_embedding_update)
-      die("per-sample weights need the fused sparse table update: drop --dense-embedding-update or drop the weights (--embedding-per-sample-weights)");
+      die("per-sample weights need the fused sparse table update: drop --dense-embedding-update or %s", drop);
     if (!fused_embedding_update())      // (plain SGD and Adagrad without weight decay take the fused update by themselves: fused_embedding_update())
       die("per-sample weights need the fused sparse table update, which this optimizer (SGD with momentum or weight decay, Adam) takes only with "
-          "--sparse-embedding-optimizer: add it or drop the weights (--embedding-per-sample-weights)");
+          "--sparse-embedding-optimizer: add it or %s", drop);
     if (!config.dataset_path.empty())
       die("per-sample weights: --dataset %s is an HDF5 file of X_int, X_cat and y, which defines no weight column: drop --dataset (synthetic data draws "
-          "its weights) or drop the weights (--embedding-per-sample-weights)", config.dataset_path.c_str());
+          "its weights) or %s", config.dataset_path.c_str(), drop);
     if (!config.ragged_gather)
-      die("per-sample weights gather through the ragged entries' weighted forms: drop --no-ragged-gather or drop the weights (--embedding-per-sample-weights)");
+      die("per-sample weights gather through the ragged entries' weighted forms: drop --no-ragged-gather or %s", drop);
     if (!config.ragged_update)
-      die("per-sample weights update through the ragged entries' weighted forms: drop --no-ragged-update or drop the weights (--embedding-per-sample-weights)");
+      die("per-sample weights update through the ragged entries' weighted forms: drop --no-ragged-update or %s", drop);
     if (q8_on())
-      die("per-sample weights: the 8-bit gathers have no weighted form; drop --eval-embedding-dtype int8 or drop the weights (--embedding-per-sample-weights)");
+      die("per-sample weights: the 8-bit gathers have no weighted form; drop --eval-embedding-dtype int8 or %s", drop);
+    // ... and weights that an operator produces get a gradient (include/ffh_bag_weights_grad.h).  Everything above holds for them as
+    // it stands; what is added: the producing operators run in front of the first table (its forward issues the gather of every table), the weights
+    // lie with the samples (one rank: an owner elsewhere would need them exchanged), and the library has the kernel.
+    if (produced_bag_weights) {
+      for (const Embedding* e : embeddings)
+        if (e->weights_produced && e->weights_in.owner_op->layer_index > embeddings[0]->layer_index)
+          die("per-sample weights: %s takes its weights from %s, which is added behind the first table %s; the gather of every table is issued with the "
+              "first: add the producing operators in front of the tables", e->name, e->weights_in.owner_op->name, embeddings[0]->name);
+      if (exchange || world_size > 1)
+        die("per-sample weights produced by an operator are supported on one rank only (they lie with the samples, the tables with their owners): run "
+            "one rank, or feed the weights as a model input");
+      // the launch workers issue the table update, and with it the gradient launch and its event, from another host thread than the one that
+      // issues the producing operators' backward
+      if (config.async_launch)
+        die("per-sample weights produced by an operator are issued inline: drop --async-launch, or feed the weights as a model input");
+      if (!api->bag_weights_grad)
+        die("per-sample weights produced by an operator: %s (%s) is a kernel library without the bag-weights-grad extension "
+            "(include/ffh_bag_weights_grad.h); feed the weights as a model input, or use another --backend", api->path.c_str(), api->ffh_backend_name());
+    }
     if (!api->bag_weights || !api->pad || !api->bags || !api->bags_update)
-      die("per-sample weights: %s (%s) is a kernel library without the bag-weights extension (include/ffh_bag_weights.h); drop the weights "
-          "(--embedding-per-sample-weights), or use another --backend", api->path.c_str(), api->ffh_backend_name());
+      die("per-sample weights: %s (%s) is a kernel library without the bag-weights extension (include/ffh_bag_weights.h); %s, or use another "
+          "--backend", api->path.c_str(), api->ffh_backend_name(), drop);
   }
   // --eval-embedding-dtype int8 (include/ff_hip_q8.h): eval_batch() gathers table-wise tables from 8-bit row images; every case
   // that does not cover is refused here, each with the flag to drop -- before the library checks: a library without the extensions shows them too.
@@ -425,12 +446,14 @@ void FFModel::allocate() {
   std::map<TensorImpl*, int> consumers;
   for (Op* op : layers)
     for (int i = 0; i < op->numInputs; i++) consumers[op->inputs[i].impl]++;
+  for (Embedding* e : embeddings)      // weights that an operator produces: the table reads them, and adds to (or stores) their gradient
+    if (e->weights_produced) consumers[e->weights_in.impl]++;
 
   // ---- 2. inputs and label ----------------------------------------------------------------------
   std::map<TensorImpl*, Embedding*> sparse_of;
   for (Embedding* e : embeddings) sparse_of[e->inputs[0].impl] = e;
   for (Embedding* e : embeddings)
-    if (e->weighted) sparse_of[e->weights_in.impl] = e;      // per-sample weights lie where the ids lie: with the table's owner, for the global batch
+    if (e->weighted && !e->weights_produced) sparse_of[e->weights_in.impl] = e;      // per-sample weights lie where the ids lie: with the table's owner, for the global batch
   auto alloc_rows = [&](const Tensor& t, int64_t nrows) {
     TensorImpl* im = t.impl;
     im->ld = t.adim[0];
@@ -678,6 +701,15 @@ void FFModel::allocate() {
           below->inputs[0].impl->pieces.empty() && li->outputs[0].impl->pieces.empty() && li->layer_index == below->layer_index + 1)
         below->pair_upper = li;
     }
+    if (Embedding* e = dynamic_cast<Embedding*>(op)) {
+      // weights that an operator produces: their gradient is stored where this table is the tensor's only reader, added otherwise (behind the memset)
+      e->gw_accumulate = e->weights_produced && consumers[e->weights_in.impl] != 1;
+      if (e->gw_accumulate) need_zero_act_grads = true;
+      // ... and the other readers add into the same buffer on the compute stream.  Those above the tables must all have done so before the side
+      // stream's launch starts (the "gradients ready" event is then recorded at the tables, not attached to an earlier kernel: step 4c), those below
+      // wait for it: the compute stream joins the launch right behind the tables instead of in front of the producing layer
+      if (e->gw_accumulate) { bag_gw_accumulates = true; bag_gw_wait_layer = (int)layers.size(); }
+    }
     if (DotInteraction* di = dynamic_cast<DotInteraction*>(op)) {
       di->bwd_overwrite = consumers[di->inputs[0].impl] == 1;
       if (!di->bwd_overwrite) need_zero_act_grads = true;
@@ -712,7 +744,7 @@ void FFModel::allocate() {
   // nothing to launch (every input writes its gradient slice in place) the op before it -- the first top-MLP layer --
   // produces those gradients, and the "gradients ready" event for the side-stream update can ride on its kernel.
   grad_attach_layer = -1;
-  if (!embeddings.empty() && config.attach_events && config.overlap_embedding && !exchange && !use_workers() && fused_embedding_update()) {
+  if (!embeddings.empty() && config.attach_events && config.overlap_embedding && !exchange && !use_workers() && fused_embedding_update() && !bag_gw_accumulates) {
     size_t l = (size_t)embeddings.back()->layer_index + 1;
     while (l < layers.size()) {
       Concat* c = dynamic_cast<Concat*>(layers[l]);

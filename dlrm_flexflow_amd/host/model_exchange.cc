@@ -496,6 +496,42 @@ void FFModel::replicated_embedding_grads() const {
   check(api->ffh_ctx_set_workspace(ctx, workspace, workspace_bytes), "set workspace");
 }
 
+// gw[b][l] = dY[b] . W[idx[b][l]] for every table whose weights an operator produces, into that tensor's gradient buffer: one launch per group of
+// tables of one width and storage (and of one mode: stored where the table is the tensor's only reader, added otherwise).  Tables that share a
+// weights tensor add into one buffer, and a launch's destinations must not overlap (the header): the k-th table on a buffer goes into the k-th
+// launch, and stream order makes the adds follow each other
+void FFModel::bag_weight_grads(ffh_stream s, ffh_ctx* cx) const {
+  struct Group { std::vector<ffh_emb_table> t; std::vector<ffh_emb_table_bf16> t16; std::vector<float*> gw; std::vector<int64_t> ld; std::vector<int> bag; };
+  std::map<std::tuple<int, bool, bool, int>, Group> groups;
+  std::map<const float*, int> tables_on;
+  for (const EmbShard& sh : shards) {
+    const Embedding* e = sh.e;
+    if (sh.owner != rank || !e->weights_produced) continue;
+    const TensorImpl* out = e->outputs[0].impl;
+    const TensorImpl* w = e->weights_in.impl;
+    Group& g = groups[std::make_tuple(sh.cols, e->bf16_weights(), e->gw_accumulate, tables_on[w->grad]++)];
+    const ffh_emb_table t{(const int64_t*)e->inputs[0].impl->ptr, (float*)e->weights[0].impl->ptr, out->grad, e->num_entries, out->grad_ld};
+    if (e->bf16_weights()) g.t16.push_back(ffh_emb_table_bf16{t.idx, (uint16_t*)t.weight, t.io, t.num_entries, t.ld, e->table_index, sh.col0});
+    else g.t.push_back(t);
+    g.gw.push_back(w->grad);
+    g.ld.push_back(w->grad_ld);
+    g.bag.push_back(e->inputs[0].adim[0]);
+  }
+  const KernelApiBagWeightsGrad* ga = api->bag_weights_grad;
+  for (const auto& kv : groups) {
+    const Group& g = kv.second;
+    const int D = std::get<0>(kv.first), flags = std::get<2>(kv.first) ? FFH_BAG_WGRAD_ACCUMULATE : 0;
+    for (size_t b = 0; b < g.gw.size(); b += FFH_MAX_TABLES) {
+      const int n = (int)std::min<size_t>(FFH_MAX_TABLES, g.gw.size() - b);
+      if (std::get<1>(kv.first))
+        check(ga->ffh_bag_weights_grad_bf16(cx, g.t16.data() + b, g.gw.data() + b, g.ld.data() + b, g.bag.data() + b, n, D, config.batchSize, flags, s), "bag_weights_grad_bf16");
+      else
+        check(ga->ffh_bag_weights_grad(cx, g.t.data() + b, g.gw.data() + b, g.ld.data() + b, g.bag.data() + b, n, D, config.batchSize, flags, s), "bag_weights_grad");
+      n_bag_weight_grads++;
+    }
+  }
+}
+
 void FFModel::embedding_group_update(ffh_stream s, ffh_ctx* on_ctx, bool advance_rate) const {
   if (embeddings.empty()) return;
   if (exchange) {
@@ -505,6 +541,17 @@ void FFModel::embedding_group_update(ffh_stream s, ffh_ctx* on_ctx, bool advance
       die("alltoall (embedding backward) failed");
     probe_record(7, s, on_ctx ? on_ctx : ctx);
     bwd_alltoall_issued = true;
+  }
+  // the gradient of operator-produced bag weights (include/ffh_bag_weights_grad.h) directly in front of the update, on its stream: dY is final here, and
+  // stream order has the table rows read before the update writes them.  Off the compute stream an event behind the launches tells backward() when
+  // the producing operators may read the gradient
+  if (produced_bag_weights && !bag_gw_issued) {
+    bag_weight_grads(s, on_ctx ? on_ctx : ctx);
+    bag_gw_issued = true;
+    if (s != stream) {
+      check(api->ffh_event_record(on_ctx ? on_ctx : ctx, ev_bag_gw, s), "bag weights' gradient ready");
+      bag_gw_recorded = true;
+    }
   }
   launch_shard_groups(this, emb_sorted_early ? kApplyOnly : kFusedUpdate, s, on_ctx ? on_ctx : ctx);
   emb_sorted_early = false;

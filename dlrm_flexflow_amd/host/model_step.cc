@@ -52,7 +52,9 @@ void FFModel::forward(int _seq_length) {
   emb_forward_issued = emb_forward_joined = false;
   fold_w_recorded = fold_on_side = false;
   // gather (+ all-to-all) go to the side stream beside the bottom MLP: the fork point is here (inputs ready)
-  if (config.overlap_embedding && !embeddings.empty()) {
+  // (per-sample weights that an operator produces: the gather reads that operator's output, so it forks where the first table stands in the layer
+  //  order -- Embedding::forward records the fork event there)
+  if (config.overlap_embedding && !embeddings.empty() && !produced_bag_weights) {
     // The side stream already runs behind everything it depends on from earlier steps (the table update is on it);
     // what it must additionally see is a batch that was copied in on `stream`.  No new batch (the reference reuses
     // the warm-up batch for random input), no event: each record / wait is a barrier packet on the critical stream.
@@ -335,6 +337,7 @@ void FFModel::backward(int _seq_length) {
   fold_e_read_recorded = false;
   fold_w_read_recorded = false;
   fold_x_read_recorded = false;
+  bag_gw_issued = bag_gw_recorded = false;
   fold_dw_pending = nullptr;
   fold_dw_defer = true;      // (a layer's backward() called on its own -- time_kernel(7) -- issues the GEMM at once)
   fold_dx_event = nullptr;
@@ -401,7 +404,15 @@ void FFModel::backward(int _seq_length) {
     }
     up->db_from_upper = false;
   };
+  // the gradient of operator-produced bag weights is written on the side stream, in front of the table update: the producing operators' backward reads
+  // it on `stream`, behind ev_bag_gw (in a captured step this wait is the graph edge)
+  auto join_bag_gw = [&] {
+    if (!bag_gw_recorded) return;
+    check(api->ffh_stream_wait_event(ctx, stream, ev_bag_gw), "bag weights' gradient ready");
+    bag_gw_recorded = false;
+  };
   for (int l = first; l >= 0; l--) {
+    if (l <= bag_gw_wait_layer) join_bag_gw();
     if (bucketed_now()) issue_grad_buckets(l);     // the buckets every layer above l has completed
     if (l == grad_attach_layer) {
       // (the dx-folded layer takes the event as an argument of its data-gradient call: nothing armed in the ctx)
@@ -458,6 +469,7 @@ void FFModel::backward(int _seq_length) {
     layers[l]->backward(*this);
     mark_z_free(l);
   }
+  join_bag_gw();
   fold_dw_defer = false;
   if (fold_dw_pending) {
     // the fold layer's kept-tile weight-gradient GEMM, behind the backward of the layers below it on `stream` (fold_dw_on_compute)
@@ -573,7 +585,8 @@ void FFModel::update() {
     if (config.overlap_embedding) {
       // launched in backward() on the side stream.  Its only consumer, the next gather, runs on that same stream, and
       // every host read of a table syncs both streams -- so `stream` joins it only where a capture must close the fork
-      if (!embeddings.empty() && (capturing_trace >= 0 || use_workers()))
+      // (operator-produced bag weights: the weighted update reads them, and the next forward pass rewrites them on `stream`)
+      if (!embeddings.empty() && (capturing_trace >= 0 || use_workers() || produced_bag_weights))
         check(api->ffh_stream_wait_event(ctx, stream, ev_update_done), "join update");
     } else if (!config.profiling) {     // (--profiling: timed as the embedding group's backward)
       embedding_group_update(stream);
