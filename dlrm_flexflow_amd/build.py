@@ -27,7 +27,7 @@ HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp
 # (a device feature: the host half of the hipcc line prints "not a recognized feature for this target (ignoring feature)", which is all it does)
 NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {"interaction_wide.hip": NO_PACKED_FP32, "linear_sk_gather.hip": NO_PACKED_FP32, "embedding_bag_weights.hip": NO_PACKED_FP32,
-               "embedding_bag_weights_grad.hip": NO_PACKED_FP32}
+               "embedding_bag_weights_grad.hip": NO_PACKED_FP32, "linear_q8.hip": NO_PACKED_FP32}
 
 
 def _newer(target: str, sources: list[str]) -> bool:

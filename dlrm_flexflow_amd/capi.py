@@ -1165,6 +1165,67 @@ class BagWeightsGradApi(ExtensionApi):
 bag_weights_grad_api = BagWeightsGradApi
 
 
+# ---- the q8-linear extension (include/ffh_q8_linear.h): Linear layers on the int8 matrix pipe for held-out evaluation -------------------------
+# Like dot_wide: a header outside ff_hip_*.h and no Q8_LINEAR_HEADER_PATH alias (EXTENSIONS["q8_linear"].header_path is the path).
+Q8_LINEAR_MIN_DIM, Q8_LINEAR_KSTEP, Q8_LINEAR_MAX_LAYERS, Q8_LINEAR_BIG_TILES = 64, 64, 32, 256
+
+
+class Q8LinearRows(C.Structure):
+    """struct ffh_q8_linear_rows"""
+    _fields_ = [("src", P), ("ld", L), ("codes", P), ("scales", P), ("rows", L), ("in_dim", C.c_int32), ("reserved_", C.c_int32)]
+
+
+_SIGS_Q8_LINEAR = {
+    "ffh_q8_linear_abi_version": (I, []),
+    "ffh_q8_linear_ldq": (L, [I]),
+    "ffh_q8_linear_quantize_max_workgroups": (I, []),
+    "ffh_q8_linear_quantize_weights": (I, [P, C.POINTER(Q8LinearRows), I, P]),
+    "ffh_q8_linear_quantize_rows": (I, [P, P, L, P, P, L, I, P]),
+    "ffh_q8_linear_fwd": (I, [P, P, P, P, P, P, P, L, L, I, I, I, P]),
+}
+Q8_LINEAR_EXT = _extension("q8_linear", _SIGS_Q8_LINEAR, "q8-linear", header_name="ffh_q8_linear.h")
+
+
+class Q8LinearApi(ExtensionApi):
+    """Images are int8 device buffers [rows][ldq(in_dim)], scales float32 [rows]; pointers may be tensors, addresses or None."""
+    ext = Q8_LINEAR_EXT
+
+    def ldq(self, in_dim: int) -> int:
+        return int(self.lib.ffh_q8_linear_ldq(int(in_dim)))
+
+    def quantize_max_workgroups(self) -> int:
+        return int(self.lib.ffh_q8_linear_quantize_max_workgroups())
+
+    def quantize_weights_rc(self, layers, stream=None) -> int:
+        """`layers`: iterable of (src, ld, codes, scales, rows, in_dim), or None for a null list."""
+        if layers is None:
+            return self.lib.ffh_q8_linear_quantize_weights(self.ctx, None, 1, ptr(stream))
+        layers = list(layers)
+        arr = (Q8LinearRows * max(1, len(layers)))()
+        for k, (src, ld, codes, scales, rows, in_dim) in enumerate(layers):
+            arr[k] = Q8LinearRows(ptr(src), int(ld), ptr(codes), ptr(scales), int(rows), int(in_dim), 0)
+        return self.lib.ffh_q8_linear_quantize_weights(self.ctx, arr, len(layers), ptr(stream))
+
+    def quantize_rows_rc(self, x, ldx: int, xq, sx, batch: int, in_dim: int, stream=None) -> int:
+        return self.lib.ffh_q8_linear_quantize_rows(self.ctx, ptr(x), int(ldx), ptr(xq), ptr(sx), int(batch), int(in_dim), ptr(stream))
+
+    def fwd_rc(self, xq, wq, sx, sw, bias, y, ldy: int, batch: int, in_dim: int, out_dim: int, act: int, stream=None) -> int:
+        return self.lib.ffh_q8_linear_fwd(self.ctx, ptr(xq), ptr(wq), ptr(sx), ptr(sw), ptr(bias), ptr(y), int(ldy), int(batch), int(in_dim),
+                                          int(out_dim), int(act), ptr(stream))
+
+    def quantize_weights(self, *args, **kw):
+        self.base.check(self.quantize_weights_rc(*args, **kw), "ffh_q8_linear_quantize_weights")
+
+    def quantize_rows(self, *args, **kw):
+        self.base.check(self.quantize_rows_rc(*args, **kw), "ffh_q8_linear_quantize_rows")
+
+    def fwd(self, *args, **kw):
+        self.base.check(self.fwd_rc(*args, **kw), "ffh_q8_linear_fwd")
+
+
+q8_linear_api = Q8LinearApi
+
+
 _hip_singleton: FFHLib | None = None
 
 

@@ -90,6 +90,7 @@ def lib() -> C.CDLL:
         "flexflow_config_set_ragged_update": (None, [H, B]), "flexflow_config_set_embedding_padding": (None, [H, B]),
         "flexflow_config_set_embedding_dtype": (None, [H, I]), "flexflow_config_set_embedding_rounding": (None, [H, I]),
         "flexflow_config_set_eval_embedding_dtype": (None, [H, I]),
+        "flexflow_config_set_eval_mlp_dtype": (None, [H, I]),
         "flexflow_config_set_lr_schedule": (None, [H, C.c_int64, C.c_int64, C.c_int64, I]),
         "flexflow_lr_schedule_value": (D, [C.c_int64, D, C.c_int64, C.c_int64, C.c_int64]),
         "flexflow_model_get_current_lr": (D, [H]),
@@ -463,6 +464,45 @@ def q8_dequantize_reference(codes, scale, bias) -> np.ndarray:
         return (codes.astype(np.float32) * scale[..., None]).astype(np.float32) + bias[..., None]
 
 
+def q8_linear_quantize_reference(v):
+    """Rows of a [rows][K] float32 matrix as symmetric 8-bit codes with a scale per row, as include/ffh_q8_linear.h states the rule: float32
+    throughout, every operation rounded on its own.  Returns (codes int8 [rows][K], scale float32 [rows])."""
+    v = np.asarray(v, dtype=np.float32)
+    f = np.float32
+    with np.errstate(all="ignore"):
+        a = np.abs(v).max(axis=-1) if v.shape[-1] else np.zeros(v.shape[:-1], f)
+        scale = (a / f(127.0)).astype(f)
+        inv = np.where(a > 0, (f(127.0) / a).astype(f), f(0.0)).astype(f)
+        q = np.rint((v * inv[..., None]).astype(f))                                   # round half to even
+    return q.astype(np.int8), scale
+
+
+def q8_linear_reference(x, W, bias=None, act=None, pre_activation: bool = False) -> np.ndarray:
+    """y = act((float)acc * (sx * sw) + bias) of include/ffh_q8_linear.h for x [batch][in], W [out][in], bias [out] or None: the int32 sums
+    exactly, the three float32 operations each rounded on its own.  `act`: an AC_MODE_* (None: AC_MODE_NONE); the sigmoid and the GELU are
+    float32 numpy, which need not round as the device's expf / tanhf do -- `pre_activation` returns the value in front of them."""
+    from . import capi
+    f = np.float32
+    qx, sx = q8_linear_quantize_reference(x)
+    qw, sw = q8_linear_quantize_reference(W)
+    acc = np.rint(qx.astype(np.float64) @ qw.astype(np.float64).T).astype(np.int64)   # exact: |acc| < 2^31 (FFH_Q8_LINEAR_MAX_IN), far below 2^53
+    with np.errstate(all="ignore"):
+        s = (sx[:, None] * sw[None, :]).astype(f)
+        t = (acc.astype(np.int32).astype(f) * s).astype(f)
+        if bias is not None:
+            t = (t + np.asarray(bias, dtype=f)[None, :]).astype(f)
+        if pre_activation or act in (None, capi.AC_MODE_NONE):
+            return t
+        if act == capi.AC_MODE_RELU:
+            return np.where(t > 0, t, f(0.0)).astype(f)
+        if act == capi.AC_MODE_SIGMOID:
+            return (f(1.0) / (f(1.0) + np.exp(-t, dtype=f))).astype(f)
+        if act == capi.AC_MODE_GELU:
+            B, Cc = f(0.7978845608028654), f(0.035677408136300125)
+            return (t * (f(0.5) + f(0.5) * np.tanh(t * (Cc * t * t + B), dtype=f))).astype(f)
+    raise ValueError(f"q8_linear_reference: activation {act!r}")
+
+
 def q8_pack_rows(codes, scale, bias, row_bytes: int | None = None) -> np.ndarray:
     """The byte layout of include/ff_hip_q8.h: uint8 [rows][row_bytes] = D codes, fp32 scale, fp32 bias, zeros.  row_bytes defaults to D + 8."""
     codes = np.ascontiguousarray(codes, dtype=np.uint8)
@@ -590,13 +630,15 @@ class FFConfig:
     def set(self, seed=None, device=None, enable_graph=None, overlap_embedding=None, dense_embedding_update=None,
             embedding_dtype=None, embedding_rounding=None, lr_warmup_steps=None, lr_decay_start_step=None, lr_num_decay_steps=None,
             device_lr=None, adagrad_eps=None, adagrad_initial_accumulator=None, adagrad_rowwise=None, ragged_update=None,
-            eval_embedding_dtype=None, embedding_padding=None):
+            eval_embedding_dtype=None, embedding_padding=None, eval_mlp_dtype=None):
         """embedding_dtype: "fp32" | "bf16"; embedding_rounding: "stochastic" | "nearest" (the --embedding-* flags).
         lr_*: the schedule of --lr-num-warmup-steps / --lr-decay-start-step / --lr-num-decay-steps; device_lr: True = --device-lr,
         False = --host-lr-schedule, None = compile() chooses the route.
         adagrad_eps / adagrad_initial_accumulator: --adagrad-eps / --adagrad-initial-accumulator, what an AdagradOptimizer without its own takes.
         adagrad_rowwise: --adagrad-rowwise, the tables of an AdagradOptimizer keep one accumulator per row (include/ff_hip_rowwise.h).
         eval_embedding_dtype: "fp32" | "int8" (--eval-embedding-dtype): eval_batch() gathers from 8-bit row images of the tables (include/ff_hip_q8.h).
+        eval_mlp_dtype: "fp32" | "int8" (--eval-mlp-dtype): eval_batch() runs the Linear layers of at least 64 x 64 on the int8 matrix pipe, from
+        dynamically quantized activations and int8 images of the weights (include/ffh_q8_linear.h).
         embedding_padding: --embedding-padding, the id -1 in a sparse input is "no lookup" (variable-length bags; include/ff_hip_pad.h).
         FFModel(config) copies the config: call set() before the model is built (as for every other field)."""
         if embedding_padding is not None: lib().flexflow_config_set_embedding_padding(self.h, bool(embedding_padding))
@@ -628,6 +670,11 @@ class FFConfig:
             if q is None:
                 raise ValueError(f"eval_embedding_dtype {eval_embedding_dtype!r}: 'fp32' or 'int8'")
             lib().flexflow_config_set_eval_embedding_dtype(self.h, q)
+        if eval_mlp_dtype is not None:
+            q = {"fp32": 0, "int8": 1}.get(eval_mlp_dtype)
+            if q is None:
+                raise ValueError(f"eval_mlp_dtype {eval_mlp_dtype!r}: 'fp32' or 'int8'")
+            lib().flexflow_config_set_eval_mlp_dtype(self.h, q)
         if embedding_rounding is not None:
             mode = {"stochastic": ROUND_STOCHASTIC, "nearest": ROUND_NEAREST}.get(embedding_rounding)
             if mode is None:

@@ -23,6 +23,7 @@
 #include "../../include/ffh_fused_gather.h"
 #include "../../include/ffh_bag_weights.h"
 #include "../../include/ffh_bag_weights_grad.h"
+#include "../../include/ffh_q8_linear.h"
 
 // The optional extensions of the kernel C-ABI, one line each, in the order load_kernel_api() loads them:
 //   X(KernelApi field, struct, the header's list, version symbol, the header's version, label of the version message, header under include/
@@ -72,7 +73,10 @@
   X(bag_weights, KernelApiBagWeights, FFH_BAG_WEIGHTS_API_LIST, ffh_bag_weights_abi_version, FFH_BAG_WEIGHTS_ABI_VERSION, "bag-weights", "ffh_bag_weights.h") \
   /* the gradient of per-sample weights that an operator produces: gw[b][l] = dY[b] . W[idx[b][l]] (its header is ffh_bag_weights_grad.h: see    \
      the header) */                                                                                                                              \
-  X(bag_weights_grad, KernelApiBagWeightsGrad, FFH_BAG_WEIGHTS_GRAD_API_LIST, ffh_bag_weights_grad_abi_version, FFH_BAG_WEIGHTS_GRAD_ABI_VERSION, "bag-weights-grad", "ffh_bag_weights_grad.h")
+  X(bag_weights_grad, KernelApiBagWeightsGrad, FFH_BAG_WEIGHTS_GRAD_API_LIST, ffh_bag_weights_grad_abi_version, FFH_BAG_WEIGHTS_GRAD_ABI_VERSION, "bag-weights-grad", "ffh_bag_weights_grad.h") \
+  /* Linear layers on the int8 matrix pipe for held-out evaluation: the two quantizers and the GEMM (absent: compile() refuses --eval-mlp-dtype    \
+     int8; its header is ffh_q8_linear.h: see the header) */                                                                                     \
+  X(q8_linear, KernelApiQ8Linear, FFH_Q8_LINEAR_API_LIST, ffh_q8_linear_abi_version, FFH_Q8_LINEAR_ABI_VERSION, "q8-linear", "ffh_q8_linear.h")
 
 #define FFH_DECL(name) decltype(&::name) name;
 

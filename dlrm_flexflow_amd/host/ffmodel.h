@@ -181,6 +181,7 @@ class FFConfig {
   bool force_exchange;         // run the all-to-all / all-reduce path even with one rank (tests the collectives on 1 GPU)
   DataType embedding_dtype;    // --embedding-dtype fp32|bf16: storage of the tables the fused update owns (table-wise; compile() refuses sharded ones); DT_FLOAT or DT_BF16
   int embedding_rounding;      // --embedding-rounding stochastic|nearest: FFH_BF16_ROUND_STOCHASTIC / _NEAREST (include/ffh_bf16.h) of the bf16 table update
+  int eval_mlp_dtype;          // --eval-mlp-dtype fp32|int8: 0 (the bits of before) or 1: eval_batch() runs the Linear layers of at least 64 x 64 on the int8 matrix pipe (include/ffh_q8_linear.h)
   int eval_embedding_dtype;    // --eval-embedding-dtype fp32|int8: 0 (the bits of before) or 1: eval_batch() gathers from 8-bit row images of the tables (include/ff_hip_q8.h)
   // learning-rate schedule (include/ff_hip_lr.h): linear warm-up over lr_warmup_steps, then the optimizer's rate, then a quadratic
   // decay over lr_num_decay_steps from lr_decay_start_step on; all 0: the constant rate of before
@@ -416,6 +417,8 @@ class Linear : public Op {
   bool dx_twin_registered = false;
   bool dx_image = false;           // split mode: backward() leaves the three-plane image of the data gradient it stores (allocate() step 7)
   bool out_twin_x3 = false;        // ... split mode: out_twin is the output's three-plane image (ffh_convert_f32_to_bf16x3 finds it by the registration)
+  int8_t* q8_w = nullptr;          // --eval-mlp-dtype int8: [out_channels][ffh_q8_linear_ldq(in_padded)] image of the kernel for evaluation (include/ffh_q8_linear.h), or null
+  float* q8_sw = nullptr;          // ... and its scale per output channel
   std::vector<Linear*> chain_bwd;  // non-empty on the TOP layer of the chain FFModel::backward runs as one call (ffh_mlp_chain_bwd): members bottom -> top
   Initializer *kernel_initializer, *bias_initializer;
 };
@@ -758,6 +761,21 @@ class FFModel {
   void q8_allocate();                         // compile(), behind allocate(): the images
   void q8_quantize(ffh_stream s, ffh_ctx* cx) const;      // every image from its table: one launch per group of <= FFH_MAX_TABLES tables of one width and storage
   std::string q8_line() const;                // the driver's start-up line
+  // --eval-mlp-dtype int8 (include/ffh_q8_linear.h): an int8 image and a scale vector per Linear of at least FFH_Q8_LINEAR_MIN_DIM
+  // both ways (Linear::q8_w / q8_sw; the fold's layer keeps its fp32 path), one activation scratch for all of them.  Derived state with the rule of
+  // q8_stale: stale after compile(), a step (a replayed trace included), Tensor::set / an initializer / load_checkpoint on a kernel that has an image;
+  // the first eval_batch() that finds them stale re-quantizes, all layers in one launch per FFH_Q8_LINEAR_MAX_LAYERS.  Calling thread only.
+  mutable bool q8l_stale = true;
+  mutable int64_t n_q8l_quantize = 0, n_q8l_gemms = 0;      // tests: flexflow_model_get_counter "q8_linear_quantize_launches" / "q8_linear_gemm_launches"
+  int q8l_layers = 0, q8l_kept = 0;           // Linear layers with an image / without one
+  size_t q8l_bytes = 0;                       // bytes of the images and their scales
+  int8_t* q8l_xq = nullptr;                   // the activation scratch: [local batch][widest image row] codes ...
+  float* q8l_sx = nullptr;                    // ... and [local batch] scales
+  bool q8l_on() const { return config.eval_mlp_dtype == 1; }
+  void q8l_allocate();                        // compile(), behind allocate(): the images and the scratch
+  void q8l_quantize(ffh_stream s, ffh_ctx* cx) const;      // every image from its kernel
+  void q8l_forward(const Linear* li) const;   // Linear::forward of a layer with an image, inside eval_batch()
+  std::string q8l_line() const;               // the driver's start-up line
   mutable int64_t n_pad_gathers = 0;          // ffh_embedding_fwd_multi_bags_pad[_bf16] launches (--embedding-padding; "pad_gather_launches")
   mutable int64_t n_pad_updates = 0;          // ffh_embedding_bwd_fused_multi_bags_pad / ffh_embedding_bwd_apply_multi_bags_pad calls ("pad_update_launches")
   mutable int64_t n_pad_mean_gathers = 0;     // ffh_embedding_fwd_multi_bags_pad_mean[_bf16] launches (padded tables with AGGR_MODE_AVG; "pad_mean_gather_launches")

@@ -51,6 +51,10 @@ void flexflow_config_set_eval_embedding_dtype(flexflow_config_t h, int int8) {
   if (int8 != 0 && int8 != 1) { fprintf(stderr, "FATAL: evaluation embedding type %d: 0 (fp32) or 1 (int8)\n", int8); abort(); }
   C(h)->eval_embedding_dtype = int8;
 }
+void flexflow_config_set_eval_mlp_dtype(flexflow_config_t h, int int8) {
+  if (int8 != 0 && int8 != 1) { fprintf(stderr, "FATAL: evaluation MLP type %d: 0 (fp32) or 1 (int8)\n", int8); abort(); }
+  C(h)->eval_mlp_dtype = int8;
+}
 void flexflow_config_set_lr_schedule(flexflow_config_t h, int64_t warmup_steps, int64_t decay_start_step, int64_t num_decay_steps, int device_lr) {
   C(h)->lr_warmup_steps = warmup_steps; C(h)->lr_decay_start_step = decay_start_step; C(h)->lr_num_decay_steps = num_decay_steps;
   C(h)->device_lr = device_lr == 1;
@@ -194,6 +198,8 @@ int64_t flexflow_model_get_counter(flexflow_model_t m, const char* name) {
   if (n == "pad_update_launches") return M(m)->n_pad_updates;      // ffh_embedding_bwd_{fused,apply}_multi_bags_pad calls
   if (n == "q8_quantize_launches") return M(m)->n_q8_quantize;      // ffh_embedding_quantize_q8 launches (--eval-embedding-dtype int8; include/ff_hip_q8.h)
   if (n == "q8_gather_launches") return M(m)->n_q8_gathers;         // ffh_embedding_fwd_multi[_bags]_q8 launches
+  if (n == "q8_linear_quantize_launches") return M(m)->n_q8l_quantize;      // ffh_q8_linear_quantize_weights launches (--eval-mlp-dtype int8; include/ffh_q8_linear.h)
+  if (n == "q8_linear_gemm_launches") return M(m)->n_q8l_gemms;             // ffh_q8_linear_fwd launches
   if (n == "ragged_gather_launches") return M(m)->n_ragged_gathers;     // ffh_embedding_fwd_multi_bags[_bf16] launches (mixed bag sizes; include/ff_hip_bags.h)
   if (n == "dot_wide_launches") return M(m)->n_dot_wide_launches;      // ffh_dot_interaction_wide_fwd / _bwd launches (include/ffh_dot_wide.h)
   if (n == "lr_steps") return M(m)->lr_steps();

@@ -553,15 +553,19 @@ void Linear::forward(const FFModel& ff) {
   const Tensor& x = inputs[0];
   const Tensor& y = outputs[0];
   const int64_t b = local_rows(y, &ff);
+  // --eval-mlp-dtype int8, inside eval_batch(): a layer with an image quantizes its input and runs on the int8 pipe (include/ffh_q8_linear.h); a layer
+  // without one takes its own fp32 launch, not a chain or a pair that would also compute a layer that has one
+  const bool q8_eval = ff.evaluating && ff.q8l_on();
+  if (q8_eval && q8_w) { ff.q8l_forward(this); return; }
   if (fwd_done_by_pair) { fwd_done_by_pair = false; return; }      // the layer below computed this output in its launch
   if (fwd_done_by_chain) { fwd_done_by_chain = false; return; }    // ... or the lowest layer of its chain did
-  if (!chain_fwd.empty() && ff.mlp_chain_usable(b, true)) {
+  if (!q8_eval && !chain_fwd.empty() && ff.mlp_chain_usable(b, true)) {
     const int rc = ff.run_chain_fwd(this);
     if (rc == FFH_OK) { for (size_t i = 1; i < chain_fwd.size(); i++) chain_fwd[i]->fwd_done_by_chain = true; return; }
     if (rc != FFH_ERR_UNSUPPORTED) ff.check(rc, name);
     chain_fwd.clear();                                             // not a chain the library serves: the per-layer calls from now on
   }
-  if (pair_upper) {
+  if (pair_upper && !q8_eval) {
     Linear* up = pair_upper;
     const Tensor& yu = up->outputs[0];
     const int rc = ff.api->ffh_linear_pair_fwd(ff.ctx, (const float*)x.impl->ptr, x.impl->ld, (const float*)weights[0].impl->ptr,

@@ -266,6 +266,22 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
       die("--eval-embedding-dtype int8: %s (%s) is a kernel library without the q8 extension (include/ff_hip_q8.h); drop --eval-embedding-dtype int8, or "
           "use another --backend", api->path.c_str(), api->ffh_backend_name());
   }
+  // --eval-mlp-dtype int8 (include/ffh_q8_linear.h): eval_batch() runs the wide Linear layers from int8 images; what that does not
+  // cover is refused here, each with the flag to drop, the library last
+  if (q8l_on()) {
+    if (!want_auc && config.eval_batches <= 0)
+      die("--eval-mlp-dtype int8 is read by held-out evaluation only, and this run has none: add --eval-batches N (METRICS_AUC), or drop "
+          "--eval-mlp-dtype int8");
+    if (config.allow_tensor_op_math_conversion)
+      die("--eval-mlp-dtype int8: the layers that keep fp32 would read bf16 twins that the int8 layers do not write: drop "
+          "--allow-tensor-op-math-conversion or drop --eval-mlp-dtype int8");
+    if (config.fp32_split_bf16x3)
+      die("--eval-mlp-dtype int8: the layers that keep fp32 would read three-plane images that the int8 layers do not write: drop "
+          "--fp32-split-bf16x3 or drop --eval-mlp-dtype int8");
+    if (!api->q8_linear)
+      die("--eval-mlp-dtype int8: %s (%s) is a kernel library without the q8-linear extension (include/ffh_q8_linear.h); drop --eval-mlp-dtype int8, or "
+          "use another --backend", api->path.c_str(), api->ffh_backend_name());
+  }
   // binary cross-entropy and evaluation (include/ff_hip_ctr.h): refused here, before anything is allocated or launched
   if (bce || want_auc || (metrics_flags & FFH_METRIC_BCE)) {
     const char* what = bce ? "--loss bce" : (want_auc ? "METRICS_AUC" : "METRICS_BINARY_CROSSENTROPY");
@@ -389,6 +405,7 @@ void FFModel::compile(Optimizer* _optimizer, LossType _loss_type, const std::vec
   // (ffh_sparse_opt).  Data-parallel (replicated) tables live in the dense slab and follow the MLP's optimizer launch either way.
   allocate();
   if (q8_on() && !embeddings.empty()) q8_allocate();
+  if (q8l_on()) q8l_allocate();
   for (Op* op : layers) {
     if (Linear* li = dynamic_cast<Linear*>(op)) {
       if (li->in_padded != li->in_channels) {

@@ -300,6 +300,64 @@ std::string FFModel::q8_line() const {
   return buf;
 }
 
+// =============================================================================================
+// --eval-mlp-dtype int8 (include/ffh_q8_linear.h)
+// =============================================================================================
+void FFModel::q8l_allocate() {
+  q8l_layers = q8l_kept = 0;
+  q8l_bytes = 0;
+  int64_t widest = 0, rows = 0;
+  for (Op* op : layers) {
+    Linear* li = dynamic_cast<Linear*>(op);
+    if (!li) continue;
+    // (the fold's layer reads an input without the folded columns: its fp32 path is kept)
+    if (li->in_channels < FFH_Q8_LINEAR_MIN_DIM || li->out_channels < FFH_Q8_LINEAR_MIN_DIM || fold.layer == li) { q8l_kept++; continue; }
+    const int64_t ldq = api->q8_linear->ffh_q8_linear_ldq(li->in_padded);
+    if (ldq <= 0) die("--eval-mlp-dtype int8: %s has %d input columns, more than an int32 sum of int8 products can take (%d): drop --eval-mlp-dtype int8", li->name, li->in_padded, FFH_Q8_LINEAR_MAX_IN);
+    li->q8_w = (int8_t*)dmalloc((size_t)li->out_channels * (size_t)ldq);
+    li->q8_sw = (float*)dmalloc((size_t)li->out_channels * sizeof(float));
+    q8l_bytes += (size_t)li->out_channels * ((size_t)ldq + sizeof(float));
+    q8l_layers++;
+    widest = std::max(widest, ldq);
+    rows = std::max(rows, local_rows(li->outputs[0], this));
+  }
+  if (q8l_layers) {
+    q8l_xq = (int8_t*)dmalloc((size_t)rows * (size_t)widest);
+    q8l_sx = (float*)dmalloc((size_t)rows * sizeof(float));
+  }
+  q8l_stale = true;
+}
+
+void FFModel::q8l_quantize(ffh_stream s, ffh_ctx* cx) const {
+  std::vector<ffh_q8_linear_rows> list;
+  for (const Op* op : layers)
+    if (const Linear* li = dynamic_cast<const Linear*>(op))
+      if (li->q8_w)
+        list.push_back(ffh_q8_linear_rows{(const float*)li->weights[0].impl->ptr, li->weights[0].impl->ld, li->q8_w, li->q8_sw, li->out_channels, li->in_padded, 0});
+  for (size_t b = 0; b < list.size(); b += FFH_Q8_LINEAR_MAX_LAYERS) {
+    const int n = (int)std::min<size_t>(FFH_Q8_LINEAR_MAX_LAYERS, list.size() - b);
+    check(api->q8_linear->ffh_q8_linear_quantize_weights(cx, list.data() + b, n, s), "q8_linear_quantize_weights");
+    n_q8l_quantize++;
+  }
+  q8l_stale = false;
+}
+
+void FFModel::q8l_forward(const Linear* li) const {
+  const Tensor& x = li->inputs[0];
+  const Tensor& y = li->outputs[0];
+  const int64_t b = local_rows(y, this);
+  check(api->q8_linear->ffh_q8_linear_quantize_rows(ctx, (const float*)x.impl->ptr, x.impl->ld, q8l_xq, q8l_sx, b, li->in_padded, stream), li->name);
+  check(api->q8_linear->ffh_q8_linear_fwd(ctx, q8l_xq, li->q8_w, q8l_sx, li->q8_sw, li->use_bias ? (const float*)li->weights[1].impl->ptr : nullptr,
+                                          (float*)y.impl->ptr, y.impl->ld, b, li->in_padded, li->out_channels, (int)li->activation, stream), li->name);
+  n_q8l_gemms++;
+}
+
+std::string FFModel::q8l_line() const {
+  char buf[160];
+  snprintf(buf, sizeof buf, "int8 (%d layers, %d keep fp32), %zu bytes of images", q8l_layers, q8l_kept, q8l_bytes);
+  return buf;
+}
+
 bool FFModel::ragged_gather_on() const { return bags_path() && config.ragged_gather && api->bags; }
 // how a model of mixed bag sizes gathers (the driver prints it): the launches of one gather over this rank's tables
 std::string FFModel::bag_gather_line() const {

@@ -83,6 +83,7 @@ FFConfig::FFConfig() {
   deterministic = false;
   embedding_dtype = DT_FLOAT;
   eval_embedding_dtype = 0;
+  eval_mlp_dtype = 0;
   embedding_rounding = FFH_BF16_ROUND_STOCHASTIC;
   lr_warmup_steps = lr_decay_start_step = lr_num_decay_steps = 0;
   device_lr = false;
@@ -218,6 +219,13 @@ void FFConfig::parse_args(char** argv, int argc) {
       if (!strcmp(v, "fp32")) eval_embedding_dtype = 0;
       else if (!strcmp(v, "int8")) eval_embedding_dtype = 1;
       else die("--eval-embedding-dtype %s: 'fp32' or 'int8'", v);
+      continue;
+    }
+    if (is("--eval-mlp-dtype")) {
+      const char* v = next();
+      if (!strcmp(v, "fp32")) eval_mlp_dtype = 0;
+      else if (!strcmp(v, "int8")) eval_mlp_dtype = 1;
+      else die("--eval-mlp-dtype %s: 'fp32' or 'int8'", v);
       continue;
     }
     if (is("--lr-num-warmup-steps")) { lr_warmup_steps = atoll(next()); continue; }

@@ -42,6 +42,11 @@ void FFModel::note_weight_write(const void* p) const {
   // (before compile() has allocated the images they are stale anyway)
   for (const Embedding* e : embeddings)
     if (e->q8_rows && e->weights[0].impl && p == e->weights[0].impl->ptr) { q8_stale = true; break; }
+  // --eval-mlp-dtype int8: the same rule for a Linear kernel that has an image (include/ffh_q8_linear.h)
+  if (q8l_layers)
+    for (const Op* op : layers)
+      if (const Linear* li = dynamic_cast<const Linear*>(op))
+        if (li->q8_w && li->weights[0].impl && p == li->weights[0].impl->ptr) { q8l_stale = true; break; }
   if (w_twin && (const char*)p >= (const char*)mlp_weights && (const char*)p < (const char*)(mlp_weights + mlp_count)) w_twin_dirty = true;
 }
 
@@ -489,6 +494,7 @@ void FFModel::backward(int _seq_length) {
 void FFModel::update() {
   n_update_calls++;              // (a replayed step counts: its update is in the graph)
   q8_stale = true;               // ... and so the 8-bit row images of the tables are behind (--eval-embedding-dtype int8)
+  q8l_stale = true;              // ... and the int8 images of the Linear kernels (--eval-mlp-dtype int8)
   if (replaying_trace >= 0) return;
   optimizer->next();
   opt_next_done = true;
@@ -736,6 +742,11 @@ void FFModel::eval_batch() {
   if (q8_on() && q8_stale && !embeddings.empty()) {
     sync();
     q8_quantize(stream, ctx);
+  }
+  // --eval-mlp-dtype int8: the same for the images of the Linear kernels, which the optimizer writes on `stream` or, bucketed, behind the streams sync() drains
+  if (q8l_layers && q8l_stale) {
+    sync();
+    q8l_quantize(stream, ctx);
   }
   evaluating = true;
   inputs_dirty = true;
